@@ -20,14 +20,19 @@ the `weak` object of the same JSON line when N > 1).  The only collectives are o
 moments of all minibatches per collect and one flat 52.7 MB gradient all-reduce per optimiser step (`allreduce` object:
 time inside the loop, stand-alone time, bus bandwidth).
 
+A plain run sets up, warms up, times exactly `--steps` cycles in one region and prints the JSON line (`--dump-outputs DIR`:
+then writes what the last timed cycle computed as DIR/<name>.npy).  `--full` adds everything else the benchmark measures:
+three timed regions (value = the median), the secondary measurements below, the weak-scaling shape and the stand-alone
+all-reduce (N > 1) and the `--detail-file` sidecar.
+
 Extra objects on the JSON line:
   roofline      dominant kernel = fused LBS kernel (blend GEMM + skinning + SDF epilogue); achieved = 2*469*31425
                 FLOP/body * bodies per launch / average launch duration measured with HIP events recorded around that
-                kernel inside the timed region; peak stated for the blend mode in use; `in_scene` = the same launch timed
-                with every body inside the scene (SDF queue path live)
-  cpu_baseline  the CPU oracle (port of the reference's per-agent, x4-replicated structure) timed on the host cores on a
-                bounded sample (rank 0, N = 1 only): all threads, one thread, and a batched-CPU (A = 64) variant
-  other_configs (N = 1) the same loop on BASELINE configs[2] (`--scene box`) and on the reference-default shape
+                kernel inside the timed region; peak stated for the blend mode in use; `in_scene` (--full) = the same launch
+                timed with every body inside the scene (SDF queue path live)
+  cpu_baseline  (--full) the CPU oracle (port of the reference's per-agent, x4-replicated structure) timed on the host cores
+                on a bounded sample (rank 0, N = 1 only): all threads, one thread, and a batched-CPU (A = 64) variant
+  other_configs (--full, N = 1) the same loop on BASELINE configs[2] (`--scene box`) and on the reference-default shape
                 (256 agents, 1024 transitions per collect)
 """
 import argparse
@@ -69,7 +74,7 @@ def get_args():
     p.add_argument("--scaling", type=str, default="strong", choices=["weak", "strong"],
                    help="strong: --agents / --batch-size are totals split over the ranks (512 agents: the BASELINE metric); "
                         "weak: both are per GPU")
-    p.add_argument("--also-weak", type=int, default=1, help="N > 1 with --scaling strong: time the weak-scaling shape as well")
+    p.add_argument("--also-weak", type=int, default=1, help="--full, N > 1 with --scaling strong: time the weak-scaling shape as well")
     p.add_argument("--num-verts", type=int, default=10475)
     p.add_argument("--skin-weights", type=int, default=4, help="non-zero skinning weights per vertex of the synthetic body (4..16)")
     p.add_argument("--body", type=str, default="iid", choices=["iid", "structured"],
@@ -82,18 +87,31 @@ def get_args():
                    help="arithmetic of the PPO update's products (GAMMAPPOPolicy update_precision): three / two / one bf16 terms per operand")
     p.add_argument("--policy-prec", type=str, default="bf16x2", choices=["f32", "bf16x2", "bf16"],
                    help="arithmetic of the rollout policy's dense layers (egx_policy_set_precision)")
-    p.add_argument("--repeats", type=int, default=3, help="timed regions of --steps cycles each; value = the median region")
+    p.add_argument("--full", action="store_true",
+                   help="also measure everything beyond the headline: repeated timed regions, CPU baseline, other configurations, "
+                        "in-scene LBS launches, weak shape and stand-alone all-reduce (N > 1), detail sidecar")
+    p.add_argument("--dump-outputs", type=str, default="", metavar="DIR",
+                   help="write what the last timed cycle computed (rollout batch, update losses, a fixed sample of the updated "
+                        "parameters) as DIR/<name>.npy")
+    p.add_argument("--repeats", type=int, default=None,
+                   help="timed regions of --steps cycles each; value = the median region (default: 3 with --full, else 1)")
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--cpu-seconds", type=float, default=12.0, help="time cap of each secondary CPU-baseline leg")
     p.add_argument("--cpu-repeats", type=int, default=2, help="repeats of the headline CPU leg (min / median reported)")
     p.add_argument("--cpu-agent-steps", type=int, default=200, help="agent-steps of each sequential CPU-baseline leg (or the time cap)")
     p.add_argument("--extra-configs", type=int, default=1,
-                   help="N = 1: 1 = also time configs[2], the strictly fp32-equivalent arithmetic and the reference-default shape (scalars of "
-                        "the stdout line); 2 = secondary shapes as well (detail file only); 0 = none")
-    p.add_argument("--detail-file", type=str, default="bench_detail.json", help="full record (sidecar of the <= 4 KB stdout line); '' = none")
+                   help="--full, N = 1: 1 = also time configs[2], the strictly fp32-equivalent arithmetic and the reference-default shape "
+                        "(scalars of the stdout line); 2 = secondary shapes as well (detail file only); 0 = none")
+    p.add_argument("--detail-file", type=str, default=None,
+                   help="full record (sidecar of the <= 4 KB stdout line); default bench_detail.json with --full, else none; '' = none")
     p.add_argument("--graph", type=int, default=0, help="capture the env step into a HIP graph")
     p.add_argument("--update-graph", type=int, default=1, help="replay the PPO minibatch update as HIP graphs")
-    return p.parse_args()
+    args = p.parse_args()
+    if args.repeats is None:
+        args.repeats = 3 if args.full else 1
+    if args.detail_file is None:
+        args.detail_file = "bench_detail.json" if args.full else ""
+    return args
 
 
 class PolicyArgs:
@@ -385,8 +403,32 @@ def _spawn_ranks(args):
     sys.exit(subprocess.call(cmd, env=env))
 
 
-def _measure(args, world, rank, A, batch_local, scene, ops, steps, warmup, with_lbs_events=True, repeats=1):
-    """Build env + policy for `A` agents on this rank, run `warmup` untimed and `steps` timed on-policy cycles."""
+DUMP_ELEMS_PER_ARRAY = 1 << 20     # larger outputs are written as a fixed, seeded sample of this many elements (<= 64 MB in all)
+
+
+def _dump_outputs(out_dir, batch, stats, policy):
+    """What a caller of the timed cycle receives from its last step, as out_dir/<name>.npy: the rollout batch of the collect
+    (observations, actions, rollout policy outputs, rewards, values, GAE returns / advantages), the loss terms of every
+    minibatch of the update and the updated parameters.  An array above DUMP_ELEMS_PER_ARRAY elements is flattened and
+    sampled at indices drawn from a generator seeded by its size, so two builds write the same elements."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: getattr(batch, k) for k in ("state", "ego", "dist", "time", "act", "mu", "logvar", "logp_old", "rew", "term",
+                                             "values", "returns", "adv")}
+    arrays["params"] = torch.cat([p.detach().reshape(-1) for _, p in sorted(policy.named_parameters())])
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy()
+        if a.size > DUMP_ELEMS_PER_ARRAY:
+            idx = np.sort(np.random.default_rng(a.size).choice(a.size, DUMP_ELEMS_PER_ARRAY, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+    for k, v in stats.items():
+        np.save(os.path.join(out_dir, k.replace("/", "_") + ".npy"), np.asarray(v, np.float64))
+    _log(f"outputs of the last timed step written to {out_dir}")
+
+
+def _measure(args, world, rank, A, batch_local, scene, ops, steps, warmup, with_lbs_events=True, repeats=1, dump_dir=""):
+    """Build env + policy for `A` agents on this rank, run `warmup` untimed and `steps` timed on-policy cycles (`dump_dir`: then
+    write what the last of them computed)."""
     from egogen_amd import _lib, setup_world as sw
     from egogen_amd.trainer import Collector
     lib = _lib.load()
@@ -395,18 +437,25 @@ def _measure(args, world, rank, A, batch_local, scene, ops, steps, warmup, with_
     pa.update_graph = bool(args.update_graph)
     pa.update_precision = args.update_prec
     env = sw.build_env(A, scene, body, prior, vposer, seed=rank, use_graph=bool(args.graph))
-    policy = sw.build_policy(pa)
+    # the orthogonal init runs a LAPACK QR whose last bits depend on the thread count: one thread = the same weights on every host
+    n_threads = torch.get_num_threads()
+    torch.set_num_threads(1)
+    try:
+        policy = sw.build_policy(pa)
+    finally:
+        torch.set_num_threads(n_threads)
     policy.train()
     collector = Collector(policy, env)
     collector.reset()
     n_vec = args.vec_steps
     global_bs = batch_local * world
     n_mb = max(1, (n_vec * A) // batch_local)
+    last = {}
 
     def one_step():
         batch = collector.collect(n_vec)
         policy.process_fn(batch)
-        return policy.learn(batch, global_bs, 1)
+        last["batch"], last["stats"] = batch, policy.learn(batch, global_bs, 1)
 
     for i in range(warmup):
         one_step()
@@ -454,6 +503,8 @@ def _measure(args, world, rank, A, batch_local, scene, ops, steps, warmup, with_
         if world > 1:
             policy.allreduce_events = []
         extra_regions.append(timed_region())
+    if dump_dir and rank == 0:
+        _dump_outputs(dump_dir, last["batch"], last["stats"], policy)
 
     if args.graph and evs:
         # a captured step cannot carry per-launch events: time the same kernel on eager passes right after the region
@@ -475,13 +526,15 @@ def _measure(args, world, rank, A, batch_local, scene, ops, steps, warmup, with_
         in_loop = [a.elapsed_time(b) for a, b in policy._allreduce_done]
         policy.allreduce_events, policy._allreduce_done = [], []
         flat = policy._flat_grad
-        dist.barrier()
-        torch.cuda.synchronize()
-        t1 = time.perf_counter()
-        for _ in range(10):
-            dist.all_reduce(flat)
-        torch.cuda.synchronize()
-        alone_ms = (time.perf_counter() - t1) / 10 * 1e3
+        alone_ms = None
+        if args.full:
+            dist.barrier()
+            torch.cuda.synchronize()
+            t1 = time.perf_counter()
+            for _ in range(10):
+                dist.all_reduce(flat)
+            torch.cuda.synchronize()
+            alone_ms = (time.perf_counter() - t1) / 10 * 1e3
         nbytes = flat.numel() * 4
         n_buckets = len(policy._grad_buckets())
         overl = bool(policy.overlap_allreduce and n_buckets == 2 and args.update_graph)
@@ -501,8 +554,8 @@ def _measure(args, world, rank, A, batch_local, scene, ops, steps, warmup, with_
               "in_loop_avg_ms": float(np.mean(in_loop)) if in_loop else None,
               "in_loop_ms_per_step": float(np.sum(in_loop)) / steps if in_loop else None,
               "exposed_ms_per_step": exposed, "beside_backward_ms_per_step": hidden, "standalone_ms": alone_ms,
-              "standalone_algbw_GBps": nbytes / (alone_ms * 1e-3) / 1e9,
-              "standalone_busbw_GBps": nbytes / (alone_ms * 1e-3) / 1e9 * 2 * (world - 1) / world,
+              "standalone_algbw_GBps": nbytes / (alone_ms * 1e-3) / 1e9 if alone_ms else None,
+              "standalone_busbw_GBps": nbytes / (alone_ms * 1e-3) / 1e9 * 2 * (world - 1) / world if alone_ms else None,
               "note": "in_loop = every all-reduce call of the timed region, events on the issuing stream, including the wait for the slowest "
                       "rank.  Default: ONE call per optimiser step between the two graphs (all of it exposed).  EGX_DP_OVERLAP=1: two "
                       "buckets, bucket 0 beside the encoders' backward (beside_backward: at most ~60 us of it can hide), bucket 1 exposed; "
@@ -644,7 +697,7 @@ def _main():
     ops = (body, sw.build_motion_prior(seed=0), sw.build_vposer(seed=0))
     scene = sw.build_scene(args.scene, sdf_res=args.sdf_res, seed=0)
     _log("assets built")
-    m = _measure(args, world, rank, A, bs_local, scene, ops, args.steps, args.warmup, repeats=args.repeats)
+    m = _measure(args, world, rank, A, bs_local, scene, ops, args.steps, args.warmup, repeats=args.repeats, dump_dir=args.dump_outputs)
     ms_list = m["lbs_ms"]
     regions = m["regions"]
     elapsed = float(np.median(regions))      # `value` / `ms_per_step` = the MEDIAN of the timed regions (each exactly --steps cycles)
@@ -697,11 +750,11 @@ def _main():
     cull_loop = _cull_stats()          # the last launch of the timed loop
     # mixed blend: vertices the last launch re-evaluated in fp32 (the ones its fp16 product / two-plane skinning could not decide)
     fix_loop = bm_handle.fix_stats(bodies) if (blend == 3 and m["env"].sdf is not None) else None
-    in_scene = _lbs_in_scene_ms(m["env"], lib)
+    in_scene = _lbs_in_scene_ms(m["env"], lib) if args.full else None
     if in_scene is not None:
         in_scene["culling"] = _cull_stats()
         in_scene["fixups"] = bm_handle.fix_stats(bodies) if blend == 3 else None
-    penetrating = _lbs_penetrating_ms(m["env"], lib) if args.scene == "single_box" else None
+    penetrating = _lbs_penetrating_ms(m["env"], lib) if (args.full and args.scene == "single_box") else None
     if penetrating is not None:
         penetrating["culling"] = _cull_stats()
         penetrating["fixups"] = bm_handle.fix_stats(bodies) if blend == 3 else None
@@ -775,14 +828,14 @@ def _main():
         result["allreduce"] = m["allreduce"]
     del m
     torch.cuda.empty_cache()
-    if world > 1 and args.scaling == "strong" and args.also_weak:
+    if args.full and world > 1 and args.scaling == "strong" and args.also_weak:
         mw = _measure(args, world, rank, args.agents, args.batch_size, scene, ops, args.steps, args.warmup, with_lbs_events=False)
         result["weak"] = {"value": mw["transitions"] / mw["elapsed"], "unit": "env-steps/s", "ms_per_step": mw["elapsed"] / args.steps * 1e3,
                           "agents_per_gpu": args.agents, "minibatch_per_gpu": args.batch_size, "allreduce": mw["allreduce"],
                           "update_paths": mw["update_paths"]}
         del mw
         torch.cuda.empty_cache()
-    if world == 1 and args.extra_configs and args.scene == "single_box" and args.agents == 512:
+    if args.full and world == 1 and args.extra_configs and args.scene == "single_box" and args.agents == 512:
         # each extra configuration in a fresh process (a second environment + policy inside this one measurably disturbs the
         # timing: allocator state, captured graphs of the first policy).  --extra-configs 1 (default): the three whose values
         # are scalars of the stdout line; 2: the secondary ones as well (detail file only)
@@ -799,7 +852,7 @@ def _main():
                   (None, "headline workload on a synthetic body with 12 skinning weights per vertex (real SMPL-X has 4..~12)", ["--skin-weights", "12"]))
         others = []
         for key, label, flags in first + (second if args.extra_configs >= 2 else ()):
-            cmd = [sys.executable, os.path.abspath(__file__), "--no-cpu-baseline", "--extra-configs", "0", "--steps", str(args.steps),
+            cmd = [sys.executable, os.path.abspath(__file__), "--full", "--no-cpu-baseline", "--extra-configs", "0", "--steps", str(args.steps),
                    "--warmup", str(args.warmup), "--num-verts", str(args.num_verts), "--sdf-res", str(args.sdf_res),
                    "--vec-steps", str(args.vec_steps), "--batch-size", str(args.batch_size), "--detail-file", ""] + flags
             try:
@@ -818,7 +871,7 @@ def _main():
                 others.append({"workload": label, "value": None, "error": f"{type(e).__name__}: {e}"})
                 _log(f"extra config FAILED: {label[:60]}: {type(e).__name__}: {e}")
         result["other_configs"] = others
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         _log("cpu baseline ...")
         try:
             result["cpu_baseline"] = cpu_baseline(args, scene)

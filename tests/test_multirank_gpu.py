@@ -343,7 +343,7 @@ def test_bench_gpus2_spawns_two_ranks(tmp_path):
     """bench.py --gpus 2 launches its own ranks; here both sit on one device over gloo (test knobs).  The stdout line is the
     compact (< 4 KB) record; the full one is the --detail-file sidecar."""
     detail = str(tmp_path / "detail.json")
-    r = _bench({"EGX_SINGLE_DEVICE": "1", "EGX_DIST_BACKEND": "gloo"}, "--gpus", "2", "--detail-file", detail)
+    r = _bench({"EGX_SINGLE_DEVICE": "1", "EGX_DIST_BACKEND": "gloo"}, "--gpus", "2", "--full", "--detail-file", detail)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-6000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout

@@ -610,6 +610,18 @@ def _oracle_p3(sd, obs, act, adv, ret, lpo, dtype):
     return out, {k: v.grad.detach().double() for k, v in P.items()}, zs
 
 
+def _build_policy_one_thread(a):
+    """sw.build_policy with one host thread: its orthogonal init is a LAPACK QR whose last bits depend on the thread count, so
+    otherwise the weights - and the figures the test below holds to fixed bounds - would change with the host's thread count."""
+    from egogen_amd import setup_world as sw
+    n = torch.get_num_threads()
+    torch.set_num_threads(1)
+    try:
+        return sw.build_policy(a)
+    finally:
+        torch.set_num_threads(n)
+
+
 def _unambiguous_rows(pol, n_rows, band, seed):
     """The first `n_rows` candidate transitions none of whose 9216 leaky-ReLU arguments lies within `band` x (rms of that
     layer's arguments) of zero IN FLOAT64.  Inside that band two correct evaluations in different arithmetic may take
@@ -640,10 +652,9 @@ def test_train_step_matches_oracle_fp64(mode):
     """csrc/update3.hip (`egx_policy_train_step`, 256-row minibatch = the training shape) against the float64 oracle of
     ppo_policy.py:189-247: loss terms and EVERY parameter gradient, with |oracle-fp32 - fp64| as the yardstick.
     EGX_P3_TABLE=<file>: append the per-parameter table (committed as profiles/r04_p3_yardstick.txt)."""
-    from egogen_amd import setup_world as sw
     a = _Args()
     a.update_precision = mode
-    pol = sw.build_policy(a)
+    pol = _build_policy_one_thread(a)
     assert pol.update_precision == mode
     with torch.no_grad():   # non-trivial biases; some raw logvars outside [-2.5, 2.5] so that the clamp mask is exercised
         for p_ in pol.parameters():
