@@ -109,26 +109,47 @@ struct PoseConsts {
   float hand_comps[2 * 12 * 45];
   float hand_mean[2 * 45];
   float fix_c[NJ];   // per joint: largest |pose-corrective base column| (3-vector norm) over its 9 columns and all vertices
-  float v_norm_max;  // largest |v_template| + 0.25 m for the blend offsets: bound of a vertex before skinning
+  float fix_d[NJ];   // per joint: largest |fp16(column) - column| (3-vector norm) over its columns of the fp16 k-steps and all vertices
+  float fix_pf;      // largest Frobenius norm of one vertex's pose-corrective block (459 columns x 3)
+  float fix_dpf;     // largest Frobenius norm of one vertex's fp16 rounding errors of the columns of the fp16 k-steps
+  float shape_c[10]; // per shape component: largest |shapedirs column| (3-vector norm) over all vertices
+  float vt_max;      // largest |v_template|
+  float w_abs_max;   // largest sum_j |W[v, j]| over the vertices (1 for convex skinning weights)
 };
 
-// Fix-up of the mixed blend (mode 3).  The count-only tiles evaluate the pose-corrective columns as ONE fp16 product: a vertex moves by
-// up to ~2e-5 m against the fp32 chain, and one that lies that close to the scene surface may be counted differently from the
-// reference's fp32 evaluation (crowd_env_2f.py:169-177).  So the cheap evaluation only CLASSIFIES: a vertex whose interpolated SDF
-// value is further from zero than the value change its position error can cause keeps the cheap decision; the few inside that band
-// are re-evaluated by their wave in fp32 (three-plane operand images, fp32 skinning: lbs_fix_process) and counted from that.
-// Position error of a body: the rounding errors of the 448 x 3 products are independent, std ~0.2 x
-//   bound(body) = 2^-11 sqrt(sum_j ||R_j - I||_F^2 C_j^2),  C_j = PoseConsts::fix_c
-// (scripts/emulate_lbs_fixup.py: error / bound rms 0.20, max 0.66 over 5e5 vertex samples, ordinary and wild poses); the band is
-// LBS_FIX_KAPPA x bound = ten standard deviations, plus a constant for the fp32 round-off of the rest of the chain.
-constexpr float LBS_FIX_KAPPA = 2.0f;
+// Fix-up of the mixed blend (mode 3).  The count-only tiles evaluate the pose-corrective columns as ONE fp16 product, and one vertex
+// that lies close to the scene surface may then be counted differently from the reference's fp32 evaluation
+// (crowd_env_2f.py:169-177).  So the cheap evaluation only CLASSIFIES: a vertex whose interpolated SDF value is further from zero
+// than the value change its position error can cause keeps the cheap decision; the ones inside that band are re-evaluated in fp32
+// (vertex-major fp32 bases, fp32 skinning: lbs_fix_process / egx_lbs_fix_kernel) and counted from that.  The band is a HARD bound
+// of the position error of the cheap evaluation, whatever the rounding pattern (pose kernel, per body, u = 2^-11):
+//   fp16 k-steps (columns k = 16..463, set H): features F_k and bases P_k rounded to fp16, products exact in the fp32 accumulator:
+//     f~ p~ - F P = dF_k P_k + f~_k dP_k  EXACTLY, with dF = f~ - F computed in the pose kernel and dP = p~ - P known at load, so
+//     |error| <= min( |dF_H|_2 PF + |f~_H|_2 DPF ,  sum_j (sum_{e in H} |dF_je|) C_j + (sum_{e in H} |f~_je|) D_j )
+//     (Cauchy-Schwarz over the columns, or the triangle inequality per joint: PF, DPF, C_j, D_j = fix_pf, fix_dpf, fix_c, fix_d).
+//     Since dF and dP are the actual rounding errors, fp16 subnormals (features of near-identity rotations, small base entries)
+//     are covered as they are; for normal numbers the second form is at most (2u + u^2) sum_j |R_j - I|_1 C_j.
+//   two-plane bf16 columns (betas and the 11 pose columns of k-steps 0 and 29): hi.hi + hi.mid + mid.hi, each operand's hi + mid
+//     off by <= 2^-18 relative, the dropped mid.mid <= 2^-18 (1 + 2^-8)^2: <= LBS_TWO_PLANE_ERR |f| |b| per column.  The template
+//     column (its third term rides on column 470) is off by < 2^-36 |v_template|.
+//   fp32 accumulation, one rounding of <= 2^-24 |partial sum| per product added: the first LBS_ACC_ADDS_OFFSETS additions sum
+//     shape and pose offsets only (|partial| <= O = sum_k |beta_k| S_k + min(|F|_2 PF, sum_j |F_j|_1 C_j)), the last
+//     LBS_ACC_ADDS_LAST (k-step 29: three MFMAs of 16 products) also the template (|partial| <= |v| <= VB = vt_max + O).
+//   skinning: the blend error reaches the posed vertex through sum_j W[v, j] R_j - times at most w_abs_max.
+// The result is scaled by LBS_FIX_MARGIN for the fp32 evaluation of the bound itself; LBS_FIX_SLACK_M allows for the fp32 round-off
+// both evaluations have apart from the blend (rotations, joint transforms, world / voxel map, interpolation): it is what the test
+// band of 2e-5 m allows against float64, not a worst case.  tests/lbs_mode3.py mirrors this formula and builds a body for which a
+// statistical band (ten standard deviations of independent roundings) is off by a factor of three.
 constexpr float LBS_FIX_SLACK_M = 3e-6f;
-// Matrix-pipe skinning of the count-only tiles (lbs_skin_cell): weights and transforms as two bf16 planes, products hi.hi + hi.mid +
+constexpr float LBS_TWO_PLANE_ERR = 1.2e-5f;        // >= 3.02 x 2^-18
+constexpr float LBS_ACC_ADDS_OFFSETS = 496.f;       // k-step 0 (3 x 16) + k-steps 1..28 (28 x 16)
+constexpr float LBS_ACC_ADDS_LAST = 48.f;           // k-step 29 (3 x 16)
+constexpr float LBS_FIX_MARGIN = 1.001f;
+// Matrix-pipe skinning of the count-only tiles (lbs_epilogue_cell): weights and transforms as two bf16 planes, products hi.hi + hi.mid +
 // mid.hi.  Each operand is off by <= 2^-18 relative and the dropped mid.mid term is <= 2^-18, so a coordinate moves by at most
-// 3 x 2^-18 (|v| + |t_j|) and the position by sqrt(3) times that = 2.0e-5 (|v| + max_j |t_j|) in the worst case of every rounding
-// pointing the same way.  The roundings are independent: over 3.4e5 vertex samples of ordinary and wild poses the worst error is
-// 0.27 of that bound (scripts/emulate_lbs_fixup.py skin); the band allows half of it, twice the worst case seen.
-constexpr float LBS_SKIN_ERR = 1.0e-5f;
+// 3.02 x 2^-18 sum_j |W[v, j]| (|v| + |t_j|) and the position by sqrt(3) times that <= 2.0e-5 w_abs_max (VB + max_j |t_j|): the hard
+// bound, with VB the body's bound of |v_posed| above.
+constexpr float LBS_SKIN_ERR = 2.0e-5f;
 // The fix-up queue is LBS_FIX_NQ sub-queues, a workgroup appends to sub-queue blockIdx % NQ: one counter for the whole launch made
 // every append (and, in the first version, every processed vertex) an atomic on ONE address - ~12 ns each at the L2, 190 us for
 // 16 000 vertices.  Counters sit 128 bytes apart: fix_stats[LBS_FIX_CNT0 + 32 q]; fix_stats[0] counts the vertices re-evaluated
@@ -304,17 +325,39 @@ __global__ __launch_bounds__(256) void egx_pose_chain_kernel(const PoseConsts* _
     }
     for (int e = 0; e < 9; ++e) sR[w][j][e] = R[e];
   }
-  if (fix_e) {   // wave-uniform: every lane of the body's wave takes part in the reduction
-    float q = 0.f;
-    if (j >= 1 && j < NJ) {
+  float fix_vb = 0.f;   // the body's bound of |v_posed| (mixed blend: see LBS_FIX_SLACK_M)
+  if (fix_e) {   // wave-uniform: every lane of the body's wave takes part in the reductions
+    // lane j: joint j's nine features (k = k0 + e; the fp16 k-steps hold k = 16..463), lanes 0..9: the shape term
+    float s[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};   // |dF_H|^2, |f~_H|^2, |F|^2, L1 form, two-plane pose, sum |F_j|_1 C_j, shape
+    if (j >= 1 && j < NJ && (j < 22 || j > 24)) {
+      const int k0 = 10 + egx_compact_joint(j) * 9;
+      float adf = 0.f, aft = 0.f, af = 0.f, afb = 0.f;
       for (int e = 0; e < 9; ++e) {
         const float dlt = R[e] - ((e == 0 || e == 4 || e == 8) ? 1.f : 0.f);
-        q += dlt * dlt;
+        s[2] += dlt * dlt;
+        af += fabsf(dlt);
+        if (k0 + e >= 16 && k0 + e < 464) {
+          const float h = (float)(_Float16)dlt;   // what the fp16 plane of the feature image holds (egx_f16_rne)
+          const float d = h - dlt;                // exact
+          s[0] += d * d; s[1] += h * h;
+          adf += fabsf(d); aft += fabsf(h);
+        } else {
+          afb += fabsf(dlt);
+        }
       }
-      q *= pc->fix_c[j] * pc->fix_c[j];
+      s[3] = adf * pc->fix_c[j] + aft * pc->fix_d[j];
+      s[4] = afb * pc->fix_c[j];
+      s[5] = af * pc->fix_c[j];
     }
-    for (int o = 32; o > 0; o >>= 1) q += __shfl_xor(q, o);
-    if (live && j == 0) fix_e[slot] = LBS_FIX_KAPPA * 0.00048828125f * sqrtf(q) + LBS_FIX_SLACK_M;
+    if (j < 10) s[6] = fabsf(be[j]) * pc->shape_c[j];
+#pragma unroll
+    for (int i = 0; i < 7; ++i)
+      for (int o = 32; o > 0; o >>= 1) s[i] += __shfl_xor(s[i], o);
+    const float prod = fminf(sqrtf(s[0]) * pc->fix_pf + sqrtf(s[1]) * pc->fix_dpf, s[3]) + LBS_TWO_PLANE_ERR * (s[4] + s[6]);
+    const float offs = (s[6] + fminf(sqrtf(s[2]) * pc->fix_pf, s[5])) * LBS_FIX_MARGIN;
+    fix_vb = pc->vt_max + offs;
+    const float accr = 5.9604645e-8f * (LBS_ACC_ADDS_OFFSETS * offs + LBS_ACC_ADDS_LAST * fix_vb);
+    if (live && j == 0) fix_e[slot] = pc->w_abs_max * (prod + accr) * LBS_FIX_MARGIN + LBS_FIX_SLACK_M;
   }
   if (j < NJ) {
     if (live && fvec) {
@@ -456,7 +499,7 @@ __global__ __launch_bounds__(256) void egx_pose_chain_kernel(const PoseConsts* _
       ci[3] = 0.f;
       cinit[slot] = ci;
       // the two-plane products of the skinning add to the body's position error bound (see LBS_SKIN_ERR)
-      if (fix_e) fix_e[slot] += LBS_SKIN_ERR * (pc->v_norm_max + tn);
+      if (fix_e) fix_e[slot] += LBS_SKIN_ERR * pc->w_abs_max * (fix_vb + tn) * LBS_FIX_MARGIN;
     }
   }
   if (j < NJ && live) {
@@ -514,7 +557,7 @@ struct LbsParams {
   const int* items;           // [8][items_stride] codes tile_index * nbg + body_group, or null (walk every item)
   const int* item_counts;     // [8]
   int items_stride;
-  // fix-up of the mixed blend (see LBS_FIX_KAPPA)
+  // fix-up of the mixed blend (see LBS_FIX_SLACK_M)
   const float* fix_e;         // [Bp] per slot: position error bound (metres)
   const float* sdf_aux;       // aux floats of the SDF's bracket table (egx_sdf_aux_offset): [0..2] largest sample step per axis
   int* fix_stats;             // [0] vertices re-evaluated inside the fused kernel, [LBS_FIX_CNT0 + 32 q] fill of sub-queue q (cleared by the pose kernel)
@@ -529,6 +572,11 @@ struct LbsParams {
   const bf16x8* skinB;        // [bt] SKIN_BT_BYTES each
   const f32x4* cinit;         // [Bp]
 };
+
+// Operand slot of body column n of 32-body tile bt: the slot itself, or, for the dead columns of the last tile (B % 32 != 0) and of a
+// tile past it, the last live slot - whose feature, transform and skinning records the pose kernel wrote in this call.  The results
+// of those columns are discarded; reading written records keeps them finite, whatever the workspace held before.
+__device__ __forceinline__ int lbs_live_slot(int bt, int n, int B) { return min(bt * 32 + n, B - 1); }
 
 // one v_fma_f32, opaque to the SLP vectoriser (which would pair adjacent rows into v_pk_fma_f32 again)
 __device__ __forceinline__ float lbs_fma(float a, float b, float c) {
@@ -661,7 +709,7 @@ __device__ __forceinline__ void lbs_fix_blend_planes(const LbsParams& p, int lan
   }
 }
 
-// fp32 re-evaluation of ONE vertex the cheap evaluation of the mixed blend could not decide (see LBS_FIX_KAPPA): row `row` of vertex
+// fp32 re-evaluation of ONE vertex the cheap evaluation of the mixed blend could not decide (see LBS_FIX_SLACK_M): row `row` of vertex
 // tile vt for the body in operand slot `slot`.  The whole wave works on it: lane j takes joint j's share of the blend product
 // (below), the sums are reduced across the wave, lane jj < JT applies joint jl[jj] of the tile's list (weight Wt[jj * 32 + row]),
 // and the trilinear sample decides.  ~70 cache lines per vertex (the first version read the MFMA-ordered operand images: 720
@@ -796,7 +844,6 @@ __device__ __forceinline__ void lbs_epilogue(const LbsParams& p, LbsWave& w, f32
   const int lane = w.lane, n = w.n, half = w.half;
   float* s_W = w.s_W; int* s_jl = w.s_jl; int* s_slot = w.s_slot; unsigned* s_masks = w.s_masks; int* s_cnt = w.s_cnt;
   float* lds = w.lds; f32x4* s_queue = w.s_queue;
-  const int num_bt = (p.B + 31) >> 5;
   int qn = w.qn;
   float tr[NB][3];
   int body[NB];
@@ -865,7 +912,8 @@ __device__ __forceinline__ void lbs_epilogue(const LbsParams& p, LbsWave& w, f32
 #pragma unroll
   for (int q = 0; q < NB; ++q) {
     [[maybe_unused]] const unsigned long long q0 = LBS_NOW();
-    const f32x4* Aq = p.A4 + (size_t)min(bt0 + q, num_bt - 1) * NJ * 3 * 32 + n;
+    const int ls = lbs_live_slot(bt0 + q, n, p.B);
+    const f32x4* Aq = p.A4 + (size_t)(ls >> 5) * NJ * 3 * 32 + (ls & 31);
     // rows are handled in adjacent pairs (r, r+1): the accumulator registers, weights and outputs of a pair are
     // neighbours, so the nine transform FMAs and three weight FMAs map onto packed fp32 instructions
     float o[16][3];
@@ -1107,7 +1155,6 @@ __device__ __forceinline__ void lbs_epilogue_cell(const LbsParams& p, LbsWave& w
   const int n = lane & 31, half = lane >> 5;
   int* s_cnt = w.s_cnt;
   f32x4* s_queue = w.s_queue;
-  const int num_bt = (p.B + 31) >> 5;
   int qn = w.qn;
   const unsigned sdf_mask = (unsigned)__builtin_amdgcn_readfirstlane((int)w.s_masks[1]);
   const int ks0 = __builtin_amdgcn_readfirstlane(p.skin_ks_off[vt]);   // JT <= 8 here: one k-step (the caller sends longer lists to the VALU epilogue)
@@ -1149,9 +1196,10 @@ __device__ __forceinline__ void lbs_epilogue_cell(const LbsParams& p, LbsWave& w
     const f32x4 ci = p.cinit[bvalid ? slot : p.B - 1];
     const float fe = p.fix_e[bvalid ? slot : p.B - 1];   // requested here, used after the skinning
     // this lane's records: plane = lane half, body column n; record of joint j at index j * 64
-    const char* tile_base = reinterpret_cast<const char*>(p.skinB) + (size_t)min(bt0 + q, num_bt - 1) * SKIN_BT_BYTES;
-    const u32x4* recA = reinterpret_cast<const u32x4*>(tile_base) + half * 32 + n;
-    const u32x2* recB = reinterpret_cast<const u32x2*>(tile_base + (size_t)SKIN_BT_A * 16) + half * 32 + n;
+    const int ls = lbs_live_slot(bt0 + q, n, p.B);
+    const char* tile_base = reinterpret_cast<const char*>(p.skinB) + (size_t)(ls >> 5) * SKIN_BT_BYTES;
+    const u32x4* recA = reinterpret_cast<const u32x4*>(tile_base) + half * 32 + (ls & 31);
+    const u32x2* recB = reinterpret_cast<const u32x2*>(tile_base + (size_t)SKIN_BT_A * 16) + half * 32 + (ls & 31);
     float o[16][3];
     {
       // all twelve entries of the (up to) eight joints in ONE burst: 16 + 8 bytes per joint and lane
@@ -1281,11 +1329,13 @@ __device__ __forceinline__ void lbs_epilogue_cell(const LbsParams& p, LbsWave& w
 // fp32 blend GEMM of one work item on v_mfma_f32_32x32x2_f32: acc = [v_template | bases] x [1 | features]
 __device__ __forceinline__ void lbs_blend_f32(const LbsParams& p, f32x16 (&acc)[3][LBS_NB], int vt, int bt0, int lane) {
   constexpr int NB = LBS_NB;
-  const int num_bt = (p.B + 31) >> 5;
   const f32x4* dp = p.dirs + (size_t)vt * KGROUPS * 3 * 64 + lane;
   const f32x4* fp[NB];
 #pragma unroll
-  for (int q = 0; q < NB; ++q) fp[q] = p.feat + (size_t)min(bt0 + q, num_bt - 1) * KGROUPS * 64 + lane;
+  for (int q = 0; q < NB; ++q) {
+    const int ls = lbs_live_slot(bt0 + q, lane & 31, p.B);
+    fp[q] = p.feat + (size_t)(ls >> 5) * KGROUPS * 64 + (lane & 32) + (ls & 31);
+  }
 
   // Operand bursts.  Measured on gfx950 (scripts/ubench/mfma_loads.hip): a wave that issues v_mfma_f32_32x32x2_f32
   // while its own global loads are still in flight runs the matrix pipe at about half rate (72 vs 136 TFLOP/s
@@ -1423,12 +1473,14 @@ __device__ __forceinline__ void lbs_blend_split(const LbsParams& p, f32x16 (&acc
                                                 bf16x8* sA, unsigned long long* tacc) {
   using Cfg = Wg4Cfg<NPL>;
   constexpr int NB = LBS_NB, SKS = Cfg::STAGE_KS, SP = Cfg::STAGE_PIECES;
-  const int num_bt = (p.B + 31) >> 5;
   asm volatile("" : "+v"(lane));   // per-lane operand addresses are formed per item (not kept alive as invariants of the persistent loop)
   const bf16x8* dpv = p.dirs3 + (size_t)vt * KS3 * 9 * 64 + lane;  // piece (s, plane, coord) at ((s*3 + plane)*3 + coord)*64
   const bf16x8* fq[NB];
 #pragma unroll
-  for (int q = 0; q < NB; ++q) fq[q] = p.feat3 + (size_t)min(bt0 + q, num_bt - 1) * KS3 * 3 * 64 + lane;
+  for (int q = 0; q < NB; ++q) {
+    const int ls = lbs_live_slot(bt0 + q, lane & 31, p.B);
+    fq[q] = p.feat3 + (size_t)(ls >> 5) * KS3 * 3 * 64 + (lane & 32) + (ls & 31);
+  }
   for (int st = 0; st < Cfg::STAGES; ++st) {
     // burst: this wave's share of the stage's base pieces + its own feature pieces
     constexpr int NGA = (SP + 3) / 4;
@@ -1521,12 +1573,14 @@ __device__ __forceinline__ constexpr int m4_feat0(int st) { return st == 0 ? 0 :
 template <int NB>
 __device__ __forceinline__ void lbs_blend_mixed(const LbsParams& p, f32x16 (&acc)[3][NB], int vt, int bt0, int lane, int wave, bf16x8* sA,
                                                 unsigned long long* tacc) {
-  const int num_bt = (p.B + 31) >> 5;
   asm volatile("" : "+v"(lane));   // per-lane operand addresses are formed per item
   const bf16x8* dpv = p.dirs4 + (size_t)vt * M4_BASE_PIECES * 64 + lane;
   const bf16x8* fq[NB];
 #pragma unroll
-  for (int q = 0; q < NB; ++q) fq[q] = p.feat4 + (size_t)min(bt0 + q, num_bt - 1) * M4_FEAT_PIECES * 64 + lane;
+  for (int q = 0; q < NB; ++q) {
+    const int ls = lbs_live_slot(bt0 + q, lane & 31, p.B);
+    fq[q] = p.feat4 + (size_t)(ls >> 5) * M4_FEAT_PIECES * 64 + (lane & 32) + (ls & 31);
+  }
   M4Regs<NB> R[2];
   auto issue = [&](M4Regs<NB>& r, int st) {
     const int np = m4_precise(st) ? 6 : 3 * M4_FKS, nf = m4_precise(st) ? 2 : M4_FKS;
@@ -1607,12 +1661,14 @@ __device__ __forceinline__ void lbs_blend_mixed(const LbsParams& p, f32x16 (&acc
 template <int NB>
 __device__ __forceinline__ void lbs_blend_split2_small(const LbsParams& p, f32x16 (&acc)[3][NB], int vt, int bt0, int lane, int wave,
                                                        bf16x8* sA) {
-  const int num_bt = (p.B + 31) >> 5;
   asm volatile("" : "+v"(lane));
   const bf16x8* dpv = p.dirs3 + (size_t)vt * KS3 * 9 * 64 + lane;  // piece (s, plane, coord) at ((s*3 + plane)*3 + coord)*64
   const bf16x8* fq[NB];
 #pragma unroll
-  for (int q = 0; q < NB; ++q) fq[q] = p.feat3 + (size_t)min(bt0 + q, num_bt - 1) * KS3 * 3 * 64 + lane;
+  for (int q = 0; q < NB; ++q) {
+    const int ls = lbs_live_slot(bt0 + q, lane & 31, p.B);
+    fq[q] = p.feat3 + (size_t)(ls >> 5) * KS3 * 3 * 64 + (lane & 32) + (ls & 31);
+  }
   static_assert(KS3 % 2 == 0, "stages of two k-steps");
   for (int st = 0; st < KS3 / 2; ++st) {
     bf16x8 ga[3], b[2][2][NB];
@@ -2334,27 +2390,54 @@ extern "C" int egx_body_model_create(const egx_body_model_host* d, egx_body_mode
       pc.J_template[j * 3 + c] = (float)s;
       for (int k = 0; k < 10; ++k) pc.J_shapedirs[(j * 3 + c) * 10 + k] = (float)sd[k];
     }
-  for (int j = 1; j < NJ; ++j) {   // fix-up threshold of the mixed blend: largest pose-corrective column (3-vector norm) per joint
-    double mx = 0.0;
-    for (int e9 = 0; e9 < 9; ++e9)
+  {   // constants of the fix-up band of the mixed blend (see LBS_FIX_SLACK_M), rounded up to fp32
+    auto up = [](double x) { return (float)(x * (1.0 + 1e-6)); };
+    std::vector<double> pf(V, 0.0), dpf(V, 0.0);
+    for (int j = 1; j < NJ; ++j) {
+      const bool movable = j < 22 || j > 24;   // jaw and eyes have no feature: their columns are not in the product
+      double mx = 0.0, mxd = 0.0;
+      for (int e9 = 0; e9 < 9; ++e9) {
+        const int k = movable ? 10 + egx_compact_joint(j) * 9 + e9 : -1;
+        const bool fp16_col = k >= 16 && k < 464;
+        for (int v = 0; v < V; ++v) {
+          double q = 0.0, qd = 0.0;
+          for (int c = 0; c < 3; ++c) {
+            const float b = d->posedirs_host[(size_t)((j - 1) * 9 + e9) * 3 * V + (size_t)v * 3 + c];
+            const double dd = fp16_col ? (double)(float)(_Float16)b - (double)b : 0.0;   // the fp16 plane of dirs4 (egx_f16_rne)
+            q += (double)b * b;
+            qd += dd * dd;
+          }
+          mx = std::max(mx, q);
+          mxd = std::max(mxd, qd);
+          if (movable) { pf[v] += q; dpf[v] += qd; }
+        }
+      }
+      pc.fix_c[j] = up(std::sqrt(mx));
+      pc.fix_d[j] = up(std::sqrt(mxd));
+    }
+    double mpf = 0.0, mdpf = 0.0, mvt = 0.0, mw = 0.0;
+    for (int v = 0; v < V; ++v) {
+      mpf = std::max(mpf, pf[v]);
+      mdpf = std::max(mdpf, dpf[v]);
+      double q = 0.0, w = 0.0;
+      for (int c = 0; c < 3; ++c) q += (double)d->v_template_host[(size_t)v * 3 + c] * d->v_template_host[(size_t)v * 3 + c];
+      for (int j = 0; j < NJ; ++j) w += std::fabs((double)d->lbs_weights_host[(size_t)v * NJ + j]);
+      mvt = std::max(mvt, q);
+      mw = std::max(mw, w);
+    }
+    pc.fix_pf = up(std::sqrt(mpf));
+    pc.fix_dpf = up(std::sqrt(mdpf));
+    pc.vt_max = up(std::sqrt(mvt));
+    pc.w_abs_max = up(mw);
+    for (int k = 0; k < 10; ++k) {
+      double mx = 0.0;
       for (int v = 0; v < V; ++v) {
         double q = 0.0;
-        for (int c = 0; c < 3; ++c) {
-          const double e = d->posedirs_host[(size_t)((j - 1) * 9 + e9) * 3 * V + (size_t)v * 3 + c];
-          q += e * e;
-        }
+        for (int c = 0; c < 3; ++c) q += (double)d->shapedirs_host[((size_t)v * 3 + c) * 10 + k] * d->shapedirs_host[((size_t)v * 3 + c) * 10 + k];
         mx = std::max(mx, q);
       }
-    pc.fix_c[j] = (float)(std::sqrt(mx) * (1.0 + 1e-6));
-  }
-  {
-    double mx = 0.0;
-    for (int v = 0; v < V; ++v) {
-      double q = 0.0;
-      for (int c = 0; c < 3; ++c) q += (double)d->v_template_host[(size_t)v * 3 + c] * d->v_template_host[(size_t)v * 3 + c];
-      mx = std::max(mx, q);
+      pc.shape_c[k] = up(std::sqrt(mx));
     }
-    pc.v_norm_max = (float)std::sqrt(mx) + 0.25f;
   }
   std::memcpy(pc.hand_comps, d->hand_comps_l_host, 12 * 45 * sizeof(float));
   std::memcpy(pc.hand_comps + 12 * 45, d->hand_comps_r_host, 12 * 45 * sizeof(float));

@@ -129,14 +129,15 @@ int egx_lbs_cull_stats(const egx_body_model* m, const void* workspace, int num_b
  *      shape / template k-steps as in mode 2 and run the 28 k-steps that hold only pose-corrective columns (centimetre-scale
  *      offsets) as ONE v_mfma_f32_32x32x16_f16 product on operands rounded to fp16 (2^-11 per operand): 204 instead of 540
  *      MFMAs per wave and work item, a third of the operand bytes.  Those vertices move by ~4e-6 m rms / ~2.2e-5 m worst case
- *      against float64 on the synthetic body, so the cheap product only CLASSIFIES: a vertex whose interpolated SDF value is
- *      closer to zero than its position error can account for (ten standard deviations of the product's rounding error for
- *      that body's pose - plus, in launches of more than 5 120 bodies, whose count-only tiles are also SKINNED on the matrix
- *      pipe in two bf16 planes, an allowance for that - times the steepest slope of the grid) is queued and re-evaluated in
- *      fp32 by a small kernel launched behind the fused one (vertex-major fp32 bases, the body's rotations recomputed from its
- *      parameter row, fp32 skinning) and counted from that - a few per thousand counted vertices.  The counts are those of an
- *      fp32 evaluation (crowd_env_2f.py:169-177): the parity tests hold every mode to the same 2e-5 m level-set band, and
- *      egx_lbs_fix_stats reads how many vertices the last call re-evaluated.  Positions are unaffected.
+ *      against float64 on the synthetic body (and by up to ~4e-4 m on a body built so that every rounding points the same
+ *      way), so the cheap product only CLASSIFIES: a vertex whose interpolated SDF value is closer to zero than its position
+ *      error can account for (a HARD bound of the blend's rounding error for that body's pose, whatever the rounding pattern,
+ *      plus that of the two-plane skinning on the matrix pipe of the count-only tiles, times the steepest slope of the grid)
+ *      is queued and re-evaluated in fp32 by a small kernel launched behind the fused one (vertex-major fp32 bases, the body's
+ *      rotations recomputed from its parameter row, fp32 skinning) and counted from that - a few per thousand counted
+ *      vertices.  The counts are those of an fp32 evaluation (crowd_env_2f.py:169-177): the parity tests hold every mode to
+ *      the same 2e-5 m level-set band, and egx_lbs_fix_stats reads how many vertices the last call re-evaluated.  Positions
+ *      are unaffected.
  * An unrecognised EGX_LBS_BLEND string is an error of the first egx_lbs_forward call (no silent default).
  * (No reference counterpart: smplx evaluates the blend shapes as fp32 einsum/matmul, lbs.py [upstream smplx 0.1.28].) */
 int egx_lbs_set_blend_mode(int mode);

@@ -115,7 +115,9 @@ def build_world(V=1536, A=6, scene_kind="sdf", sdf_res=48, n_pairs=64, n_scenes=
 def level_set_band():
     """Distance from the SDF's zero level set (metres) inside which a penetration count of the HIP path may differ from a CPU
     evaluation: 2e-5 (fp32 round-off of the vertex chain) in EVERY blend mode - mode 3 ("f16mix", the library default) classifies
-    with its fp16 product and re-evaluates in fp32 what that product cannot decide (csrc/body_model.hip: lbs_fix_process)."""
+    with its fp16 product and re-evaluates in fp32 every vertex inside a hard bound of that product's error, whatever the rounding
+    pattern (csrc/body_model.hip: LBS_FIX_SLACK_M; tests/test_lbs_adversarial_gpu.py holds it to a body built to defeat a
+    statistical bound)."""
     return 2e-5
 
 
