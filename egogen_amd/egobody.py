@@ -37,6 +37,10 @@ def read_ply(path: str) -> Tuple[np.ndarray, np.ndarray]:
             elements[-1]["props"].append(tok[1:])
     if fmt not in ("ascii", "binary_little_endian"):
         raise ValueError(f"{path}: unsupported PLY format {fmt!r}")
+    if fmt == "binary_little_endian":
+        fast = _read_binary_triangles(data, end, elements)
+        if fast is not None:
+            return fast
     verts, faces = None, []
     if fmt == "ascii":
         lines = data[end:].decode("ascii").split("\n")
@@ -82,6 +86,36 @@ def read_ply(path: str) -> Tuple[np.ndarray, np.ndarray]:
     if verts is None:
         raise ValueError(f"{path}: no vertex element")
     return verts, np.asarray(faces, np.int64).reshape(-1, 3)
+
+
+def _read_binary_triangles(data: bytes, off: int, elements: List[dict]):
+    """numpy path of `read_ply` for the common binary layout of scans: a vertex element of fixed-size properties followed by a
+    face element whose only property is the index list, every face a triangle.  None for any other file (the row loop reads
+    it); the result equals the row loop's."""
+    if [e["name"] for e in elements] != ["vertex", "face"]:
+        return None
+    ve, fe = elements
+    if any(p[0] == "list" or p[0] not in _PLY_TYPES for p in ve["props"]):
+        return None
+    names = [p[-1] for p in ve["props"]]
+    if not all(c in names for c in ("x", "y", "z")) or len(set(names)) != len(names):
+        return None
+    if len(fe["props"]) != 1 or fe["props"][0][0] != "list" or fe["props"][0][-1] not in ("vertex_indices", "vertex_index"):
+        return None
+    _, cnt_t, idx_t, _ = fe["props"][0]
+    if cnt_t not in _PLY_TYPES or idx_t not in _PLY_TYPES:
+        return None
+    vdt = np.dtype([(n, "<" + _PLY_TYPES[p[0]]) for n, p in zip(names, ve["props"])])
+    fdt = np.dtype([("n", "<" + _PLY_TYPES[cnt_t]), ("i", "<" + _PLY_TYPES[idx_t], (3,))])
+    vend = off + vdt.itemsize * ve["count"]
+    if vend + fdt.itemsize * fe["count"] > len(data):
+        return None
+    vr = np.frombuffer(data, vdt, ve["count"], off)
+    fr = np.frombuffer(data, fdt, fe["count"], vend)
+    if not (fr["n"] == 3).all():
+        return None
+    verts = np.stack([vr[c].astype(np.float64) for c in ("x", "y", "z")], 1).reshape(-1, 3)
+    return verts, fr["i"].astype(np.int64).reshape(-1, 3)
 
 
 def _ring_area(r: np.ndarray) -> float:

@@ -10,11 +10,18 @@ tool for other scenes (README.md:97).  This module produces the same four artefa
   start / target pairs   `sample_pairs`
   files                  `write_ply` (binary little endian, readable by `egobody.read_ply` / trimesh), `save_scene` (npz)
 
-The SDF needs the HIP library; everything else is host-side numpy (offline, once per scene)."""
+Scanned rooms (open triangle soups: walls without backs, holes, duplicated vertices) take the `scene_from_scan` path instead
+(`python -m egogen_amd.prepare_scene`):
+
+  signed-distance grid   `scan_to_sdf_dict` -> HIP kernel `egx_scan_sdf` (BVH nearest triangle, sign from the pseudo-normal of
+                         the nearest feature; host tables: `weld_vertices`, `pseudo_normals`, `build_bvh`)
+  walkable raster        `scan_walkable_grid` -> HIP kernel `egx_walkable_raster` (floor support + clearance per cell; host:
+                         `detect_floor_height`, `disc_erosion`)
+
+The two SDF paths and the scan raster need the HIP library; everything else is host-side numpy (offline, once per scene)."""
 from __future__ import annotations
 
 import ctypes as C
-import struct
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -45,8 +52,9 @@ def write_ply(path: str, vertices: np.ndarray, faces: np.ndarray) -> None:
         fh.write((f"ply\nformat binary_little_endian 1.0\nelement vertex {len(v)}\nproperty float x\nproperty float y\n"
                   f"property float z\nelement face {len(f)}\nproperty list uchar int vertex_indices\nend_header\n").encode())
         fh.write(v.astype("<f4").tobytes())
-        for t in f:
-            fh.write(struct.pack("<Biii", 3, int(t[0]), int(t[1]), int(t[2])))
+        rec = np.zeros(len(f), np.dtype([("n", "u1"), ("i", "<i4", (3,))]))   # packed: the bytes of struct "<Biii" per face
+        rec["n"], rec["i"] = 3, f.reshape(-1, 3)
+        fh.write(rec.tobytes())
 
 
 # ------------------------------------------------------------------------------------------------ SDF
@@ -84,6 +92,230 @@ def scene_sdf_dict(room: Tuple[np.ndarray, np.ndarray], obstacles: Optional[Tupl
         o = mesh_to_sdf_dict(obstacles[0], obstacles[1], res, center, half, inside_is_obstacle=True, device=device)
         d["sdf"] = torch.maximum(d["sdf"], o["sdf"])
     return d
+
+
+# ------------------------------------------------------------------------------------------------ scanned meshes: SDF
+def weld_vertices(vertices: np.ndarray, faces: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
+    """Vertices that share a position become one: (unique vertices [U,3], faces re-indexed [F,3])."""
+    v, f = np.asarray(vertices, np.float64).reshape(-1, 3), np.asarray(faces, np.int64)
+    order = np.lexsort((v[:, 2], v[:, 1], v[:, 0]))
+    vs = v[order]
+    new = np.ones(len(v), bool)
+    new[1:] = np.any(vs[1:] != vs[:-1], axis=1)
+    inv = np.empty(len(v), np.int64)
+    inv[order] = np.cumsum(new) - 1
+    return vs[new], inv[f]
+
+
+def degenerate_faces(vertices: np.ndarray, faces: np.ndarray, rel_eps: float = 1e-12) -> np.ndarray:
+    """Zero-area triangles (after welding): two equal vertices, or |ab x ac| <= rel_eps * longest edge^2."""
+    return _degenerate(*weld_vertices(vertices, faces), rel_eps)
+
+
+def _degenerate(v: np.ndarray, f: np.ndarray, rel_eps: float = 1e-12) -> np.ndarray:
+    t = v[f]
+    n = np.linalg.norm(np.cross(t[:, 1] - t[:, 0], t[:, 2] - t[:, 0]), axis=1)
+    e2 = np.max([((t[:, (k + 1) % 3] - t[:, k]) ** 2).sum(1) for k in range(3)], 0)
+    same = (f[:, 0] == f[:, 1]) | (f[:, 1] == f[:, 2]) | (f[:, 2] == f[:, 0])
+    return same | (n <= rel_eps * e2)
+
+
+def pseudo_normals(vertices: np.ndarray, faces: np.ndarray, flip_normals: bool = False) -> np.ndarray:
+    """Pseudo-normals (Baerentzen & Aanaes 2005) of every triangle's features after welding, [F,7,3]: face, edge ab / bc / ca,
+    vertex a / b / c.  Face: the unit normal (zero for a degenerate triangle).  Edge: the sum of the unit normals of all faces
+    on it (one face on an open boundary, more than two on a non-manifold edge).  Vertex: the angle-weighted sum of the unit
+    normals of its faces.  flip_normals: scans whose normals point into the solid."""
+    v, f = weld_vertices(vertices, faces)
+    t = v[f]
+    n = np.cross(t[:, 1] - t[:, 0], t[:, 2] - t[:, 0])
+    nl = np.linalg.norm(n, axis=1)
+    deg = _degenerate(v, f)
+    fn = np.where(deg[:, None], 0.0, n / np.where(nl > 0, nl, 1.0)[:, None])
+    out = np.zeros((len(f), 7, 3))
+    out[:, 0] = fn
+    V = len(v)
+    ek = [np.minimum(f[:, k], f[:, (k + 1) % 3]) * V + np.maximum(f[:, k], f[:, (k + 1) % 3]) for k in range(3)]
+    uk, inv = np.unique(np.concatenate(ek), return_inverse=True)
+    esum = np.stack([np.bincount(inv, weights=np.tile(fn[:, c], 3), minlength=len(uk)) for c in range(3)], 1)
+    for k in range(3):
+        out[:, 1 + k] = esum[inv[k * len(f):(k + 1) * len(f)]]
+    vsum = np.zeros((V, 3))
+    for k in range(3):
+        a, b = t[:, (k + 1) % 3] - t[:, k], t[:, (k + 2) % 3] - t[:, k]
+        den = np.linalg.norm(a, axis=1) * np.linalg.norm(b, axis=1)
+        ang = np.arccos(np.clip((a * b).sum(1) / np.where(den > 0, den, 1.0), -1.0, 1.0))
+        for c in range(3):
+            vsum[:, c] += np.bincount(f[:, k], weights=ang * fn[:, c], minlength=V)
+    for k in range(3):
+        out[:, 4 + k] = vsum[f[:, k]]
+    return -out if flip_normals else out
+
+
+def _morton3(q: np.ndarray) -> np.ndarray:
+    """30-bit Morton codes of 10-bit integer coordinates [n,3]."""
+    def spread(x):
+        x = x.astype(np.uint64) & 0x3FF
+        x = (x | (x << 16)) & 0x030000FF
+        x = (x | (x << 8)) & 0x0300F00F
+        x = (x | (x << 4)) & 0x030C30C3
+        x = (x | (x << 2)) & 0x09249249
+        return x
+    return (spread(q[:, 0]) << 2) | (spread(q[:, 1]) << 1) | spread(q[:, 2])
+
+
+def build_bvh(triangles: np.ndarray, leaf_size: int = 4, max_levels: int = 24):
+    """Bounding-volume hierarchy of triangles [F,3,3] for egx_scan_sdf: the triangles sorted along the Morton curve of their
+    centroids (a median split along the curve at every level), `leaf_size` consecutive ones per leaf, and the implicit complete
+    binary tree over the leaves (heap order, node h at row h-1, children 2h, 2h+1; padding leaves hold empty boxes).  Boxes are
+    taken over the float32 vertices the kernel reads.  Returns (nodes [2^(L+1)-1, 8] float32 {lo, 0, hi, 0}, order [F] (leaf
+    order -> input triangle), L).  Raises ValueError when the depth L would exceed max_levels."""
+    tri = np.asarray(triangles, np.float32).reshape(-1, 3, 3)
+    F = len(tri)
+    if F == 0:
+        raise ValueError("build_bvh needs at least one triangle")
+    nleaf = -(-F // leaf_size)
+    L = int(np.ceil(np.log2(nleaf))) if nleaf > 1 else 0
+    if L > max_levels:
+        raise ValueError(f"BVH depth {L} exceeds the cap {max_levels} ({F} triangles, {leaf_size} per leaf)")
+    cen = tri.astype(np.float64).mean(1)
+    lo, hi = cen.min(0), cen.max(0)
+    q = np.clip(((cen - lo) / max(float((hi - lo).max()), 1e-30) * 1023.0).astype(np.int64), 0, 1023)
+    order = np.argsort(_morton3(q), kind="stable")
+    t = tri[order]
+    pad = (leaf_size << L) - F
+    tmin = np.concatenate([t.min(1), np.full((pad, 3), np.inf, np.float32)], 0).reshape(1 << L, leaf_size, 3).min(1)
+    tmax = np.concatenate([t.max(1), np.full((pad, 3), -np.inf, np.float32)], 0).reshape(1 << L, leaf_size, 3).max(1)
+    levels = [(tmin, tmax)]
+    for _ in range(L):
+        a, b = levels[-1]
+        levels.append((a.reshape(-1, 2, 3).min(1), b.reshape(-1, 2, 3).max(1)))
+    lo_all = np.concatenate([lv[0] for lv in reversed(levels)], 0)
+    hi_all = np.concatenate([lv[1] for lv in reversed(levels)], 0)
+    nodes = np.zeros((len(lo_all), 8), np.float32)
+    nodes[:, 0:3], nodes[:, 4:7] = lo_all, hi_all
+    return nodes, order, L
+
+
+def scan_sdf_tables(vertices: np.ndarray, faces: np.ndarray, flip_normals: bool = False, leaf_size: int = 4):
+    """Host tables of egx_scan_sdf (include/egogen_hip.h): {'nodes', 'levels', 'leaf_size', 'tris' [F,12], 'pn' [F,21]}."""
+    v, f = np.asarray(vertices, np.float64), np.asarray(faces, np.int64)
+    pn = pseudo_normals(v, f, flip_normals)
+    deg = ~pn[:, 0].any(1)   # zero face normal: a degenerate triangle
+    nodes, order, L = build_bvh(v[f], leaf_size)
+    tris = np.zeros((len(f), 12), np.float32)
+    tris[:, [0, 1, 2, 4, 5, 6, 8, 9, 10]] = v[f[order]].reshape(-1, 9)
+    tris[:, 3] = deg[order]
+    return {"nodes": nodes, "levels": L, "leaf_size": leaf_size, "tris": tris,
+            "pn": pn[order].reshape(-1, 21).astype(np.float32)}
+
+
+def scan_to_sdf_dict(vertices: np.ndarray, faces: np.ndarray, res: int = 256, center: Optional[Sequence[float]] = None,
+                     half: Optional[float] = None, flip_normals: bool = False, device: str = "cuda") -> Dict[str, "object"]:
+    """Signed-distance grid of an open, oriented mesh (a scanned room: walls without backs, holes, duplicated vertices): the
+    `mesh_to_sdf_dict` layout and defaults, exact unsigned distance (BVH), sign from the pseudo-normal of the nearest feature:
+    < 0 on the side the normals face (free space), > 0 behind the surface.  HIP kernel `egx_scan_sdf`."""
+    import torch
+    from . import _lib
+    if not torch.cuda.is_available():
+        raise _lib.EgxError("scan_to_sdf_dict runs on the HIP device only (no CPU fallback)")
+    v, f = np.asarray(vertices, np.float64), np.asarray(faces, np.int64)
+    if center is None:
+        center = (v.min(0) + v.max(0)) / 2
+    if half is None:
+        half = float(np.abs(v - np.asarray(center)).max()) * 1.1
+    tb = scan_sdf_tables(v, f, flip_normals)
+    dev = {k: torch.from_numpy(tb[k]).to(device).contiguous() for k in ("nodes", "tris", "pn")}
+    grid = torch.empty(res, res, res, dtype=torch.float32, device=device)
+    c = (C.c_float * 3)(*[float(x) for x in center])
+    lib = _lib.load()
+    _lib.check(lib.egx_scan_sdf(_lib.ptr(dev["nodes"]), tb["levels"], _lib.ptr(dev["tris"]), _lib.ptr(dev["pn"]), len(f), tb["leaf_size"],
+                                c, float(1.0 / half), res, res, res, _lib.ptr(grid), _lib.current_stream_ptr()), "egx_scan_sdf")
+    return {"sdf": grid, "center": torch.tensor(np.asarray(center, np.float32), device=device),
+            "scale": torch.tensor(np.float32(1.0 / half), device=device)}
+
+
+# ------------------------------------------------------------------------------------------------ scanned meshes: floor
+def detect_floor_height(vertices: np.ndarray, faces: np.ndarray, max_slope_deg: float = 15.0, bin_size: float = 0.02,
+                        share: float = 0.25) -> float:
+    """The lowest height at which up-facing triangles (normal within max_slope_deg of +z) hold a large share of their area:
+    area-weighted histogram of their centroid heights, first bin with >= `share` of the fullest bin's area, refined to the
+    area-weighted mean height over that bin and the next."""
+    v, f = np.asarray(vertices, np.float64), np.asarray(faces, np.int64)
+    t = v[f]
+    n = np.cross(t[:, 1] - t[:, 0], t[:, 2] - t[:, 0])
+    nl = np.linalg.norm(n, axis=1)
+    up = (nl > 0) & (n[:, 2] >= np.cos(np.radians(max_slope_deg)) * nl)
+    if not up.any():
+        raise ValueError("no up-facing triangle: cannot detect the floor (is the mesh z-up?)")
+    z, w = t[up, :, 2].mean(1), 0.5 * nl[up]
+    z0 = float(z.min())
+    b = np.floor((z - z0) / bin_size).astype(np.int64)
+    hist = np.bincount(b, weights=w)
+    k = int(np.flatnonzero(hist >= share * hist.max())[0])
+    sel = (b == k) | (b == k + 1)
+    return float(np.sum(z[sel] * w[sel]) / np.sum(w[sel]))
+
+
+def disc_erosion(mask: np.ndarray, radius: float, cell: float) -> np.ndarray:
+    """Exact disc erosion on the raster: a cell stays iff every raster cell whose centre is closer than `radius` to its centre
+    is set (cells beyond the raster do not count).  Distances are compared in cell units, a cell at exactly `radius` (to 1e-9
+    cells^2: radius 0.2 on 0.05 m cells) is not closer."""
+    mask = np.asarray(mask, bool)
+    r = int(np.ceil(radius / cell))
+    lim = (radius / cell) ** 2 - 1e-9
+    out = mask.copy()
+    P = np.pad(mask, r, constant_values=True)
+    nx, ny = mask.shape
+    for di in range(-r, r + 1):
+        for dj in range(-r, r + 1):
+            if di * di + dj * dj < lim and (di or dj):
+                out &= P[r + di:r + di + nx, r + dj:r + dj + ny]
+    return out
+
+
+def scan_walkable_raster(vertices: np.ndarray, faces: np.ndarray, radius: float = 0.2, cell: float = 0.05,
+                         z_range: Tuple[float, float] = (0.05, 2.0), floor_height: Optional[float] = None, bounds=None,
+                         max_slope_deg: float = 15.0, floor_tol: float = 0.03, device: str = "cuda"):
+    """HIP kernel `egx_walkable_raster` over the floor raster: (support [nx,ny] bool, clearance [nx,ny] float32, origin[2], cell,
+    floor_height).  bounds ((x0, y0), (x1, y1)) defaults to the xy box of the supporting triangles grown by `radius`."""
+    import torch
+    from . import _lib
+    if not torch.cuda.is_available():
+        raise _lib.EgxError("scan_walkable_grid runs on the HIP device only (no CPU fallback)")
+    v, f = np.asarray(vertices, np.float64), np.asarray(faces, np.int64)
+    if floor_height is None:
+        floor_height = detect_floor_height(v, f, max_slope_deg)
+    cos_up = float(np.cos(np.radians(max_slope_deg)))
+    if bounds is None:
+        t = v[f]
+        n = np.cross(t[:, 1] - t[:, 0], t[:, 2] - t[:, 0])
+        nl = np.linalg.norm(n, axis=1)
+        sup = (nl > 0) & (n[:, 2] >= cos_up * nl) & (t[:, :, 2].max(1) >= floor_height - floor_tol) & \
+            (t[:, :, 2].min(1) <= floor_height + floor_tol)
+        if not sup.any():
+            raise ValueError(f"no up-facing triangle near the floor height {floor_height}")
+        bounds = (t[sup, :, :2].reshape(-1, 2).min(0) - radius, t[sup, :, :2].reshape(-1, 2).max(0) + radius)
+    lo, hi = np.asarray(bounds[0], np.float64)[:2], np.asarray(bounds[1], np.float64)[:2]
+    nx, ny = max(int(round((hi[0] - lo[0]) / cell)), 1), max(int(round((hi[1] - lo[1]) / cell)), 1)
+    tris = torch.tensor(v[f].reshape(-1, 9), dtype=torch.float32, device=device).contiguous()
+    support = torch.empty(nx, ny, dtype=torch.int32, device=device)
+    clearance = torch.empty(nx, ny, dtype=torch.float32, device=device)
+    lib = _lib.load()
+    _lib.check(lib.egx_walkable_raster(_lib.ptr(tris), len(f), float(lo[0]), float(lo[1]), float(cell), nx, ny, float(floor_height),
+                                       float(floor_tol), cos_up, float(floor_height + z_range[0]), float(floor_height + z_range[1]),
+                                       _lib.ptr(support), _lib.ptr(clearance), _lib.current_stream_ptr()), "egx_walkable_raster")
+    return support.cpu().numpy() != 0, clearance.cpu().numpy(), lo.copy(), float(cell), float(floor_height)
+
+
+def scan_walkable_grid(vertices: np.ndarray, faces: np.ndarray, radius: float = 0.2, cell: float = 0.05,
+                       z_range: Tuple[float, float] = (0.05, 2.0), floor_height: Optional[float] = None, bounds=None,
+                       max_slope_deg: float = 15.0, floor_tol: float = 0.03, device: str = "cuda"):
+    """Walkable raster of a scanned room: free = (support eroded by the body disc) & (clearance > radius), where a cell is
+    supported when floor lies under its centre and its clearance is the xy distance to anything inside the height slab
+    `z_range` above the floor (detected when not given).  Returns (free [nx,ny] bool, origin[2], cell, floor_height)."""
+    support, clearance, origin, cell, fh = scan_walkable_raster(vertices, faces, radius, cell, z_range, floor_height, bounds,
+                                                                max_slope_deg, floor_tol, device)
+    return disc_erosion(support, radius, cell) & (clearance > radius), origin, cell, fh
 
 
 # ------------------------------------------------------------------------------------------------ walkable region
@@ -257,11 +489,63 @@ def box_scene_from_meshes(floor_lo, floor_hi, obstacle_mesh, radius: float = 0.2
             "nav_v": nav_v, "nav_f": nav_f, "rings": rings}
 
 
+def grid_to_cell_navmesh(free: np.ndarray, origin: np.ndarray, cell: float, floor_height: float = 0.0):
+    """Free cells -> two triangles each on shared corner vertices: a conforming triangulation (no T-junctions), so the union's
+    outline is the set of edges with one triangle - what `egobody.navmesh_walkable_rings` reads from `navmesh_tight.ply`."""
+    ii, jj = np.nonzero(free)
+    corners = np.stack([np.stack([ii, jj], 1), np.stack([ii + 1, jj], 1), np.stack([ii + 1, jj + 1], 1), np.stack([ii, jj + 1], 1)], 1)
+    uniq, inv = np.unique(corners.reshape(-1, 2), axis=0, return_inverse=True)
+    q = inv.reshape(-1, 4)
+    f = np.concatenate([q[:, [0, 1, 2]], q[:, [0, 2, 3]]], 0)
+    v = np.stack([origin[0] + uniq[:, 0] * cell, origin[1] + uniq[:, 1] * cell, np.full(len(uniq), float(floor_height))], 1)
+    return v.astype(np.float64), f.astype(np.int64)
+
+
+def scene_from_scan(vertices: np.ndarray, faces: np.ndarray, res: int = 256, cell: float = 0.05, radius: float = 0.2,
+                    floor_height: Optional[float] = None, flip_normals: bool = False, n_pairs: int = 20000, min_dist: float = 1.7,
+                    seed: int = 0, z_range: Tuple[float, float] = (0.05, 2.0), max_slope_deg: float = 15.0, floor_tol: float = 0.03,
+                    center: Optional[Sequence[float]] = None, half: Optional[float] = None, device: str = "cuda") -> dict:
+    """A scanned room (z-up triangle soup) -> the `box_scene_from_meshes` dict (edges, tris, floor_height, pairs, nav_v, nav_f,
+    rings) plus 'sdf_dict' (scan_to_sdf_dict), 'z_offset', the raster ('free', 'origin', 'cell') and per-stage 'times' [s].
+    The mesh is first shifted down by the floor height (given or detected) - the SDF-kind environment puts bodies on z = 0 -
+    and everything is built from the shifted mesh ('vertices'); 'z_offset' records the shift."""
+    import time
+    import torch
+    times = {}
+    t0 = time.perf_counter()
+    v, f = np.asarray(vertices, np.float64), np.asarray(faces, np.int64)
+    if flip_normals:
+        f = f[:, ::-1].copy()
+    z_off = float(floor_height) if floor_height is not None else detect_floor_height(v, f, max_slope_deg)
+    v = v - np.array([0.0, 0.0, z_off])
+    times["floor"] = time.perf_counter() - t0
+    t0 = time.perf_counter()
+    free, origin, cell, _ = scan_walkable_grid(v, f, radius, cell, z_range, 0.0, None, max_slope_deg, floor_tol, device)
+    times["raster"] = time.perf_counter() - t0
+    t0 = time.perf_counter()
+    nav_v, nav_f = grid_to_navmesh(free, origin, cell, 0.0)
+    rings = grid_to_rings(free, origin, cell)
+    if not rings:
+        raise ValueError("no walkable cell: check the floor height, the body radius and the mesh's orientation (z-up)")
+    pairs = sample_pairs(rings, n_pairs, min_dist, seed, 0.0)
+    times["navmesh"] = time.perf_counter() - t0
+    t0 = time.perf_counter()
+    sdf = scan_to_sdf_dict(v, f, res, center, half, False, device)
+    torch.cuda.synchronize()
+    times["sdf"] = time.perf_counter() - t0
+    from . import synth
+    return {"edges": synth.rings_to_edges(rings).astype(np.float32), "tris": nav_v[nav_f][:, :, :2].reshape(-1, 6).astype(np.float32),
+            "floor_height": 0.0, "pairs": pairs, "nav_v": nav_v, "nav_f": nav_f, "rings": rings, "sdf_dict": sdf, "z_offset": z_off,
+            "free": free, "origin": origin, "cell": cell, "vertices": v, "faces": f, "times": times}
+
+
 def save_scene(path: str, scene: dict, sdf_dict: Optional[dict] = None) -> None:
     """npz pack of a generated scene (polygon rings flattened with offsets; the SDF grid if given)."""
     out = {"edges": scene["edges"], "tris": scene["tris"], "floor_height": np.float32(scene["floor_height"]), "pairs": scene["pairs"],
            "nav_v": scene["nav_v"], "nav_f": scene["nav_f"], "ring_xy": np.concatenate(scene["rings"], 0),
            "ring_off": np.cumsum([0] + [len(r) for r in scene["rings"]]).astype(np.int32)}
+    if "z_offset" in scene:   # scene_from_scan: the height the scan was shifted down by (not read back by load_scene_file)
+        out["z_offset"] = np.float64(scene["z_offset"])
     if sdf_dict is not None:
         for k in ("sdf", "center", "scale"):
             v = sdf_dict[k]

@@ -224,6 +224,33 @@ int egx_sdf_sample(const egx_sdf_grid* sdf, const float* pts, int64_t n, float* 
 int egx_mesh_sdf(const float* triangles, int num_triangles, const float* center_host, float scale, int d0, int d1, int d2,
                  int inside_positive, float* out_grid, void* stream);
 
+/*
+ * egx_scan_sdf - scene preparation from a scanned room (an open, oriented triangle soup): the same grid contract as
+ * egx_mesh_sdf, filled with the exact distance to the nearest triangle (nearest-triangle search through a bounding-volume
+ * hierarchy) signed by the pseudo-normal of the nearest feature (Baerentzen & Aanaes 2005): < 0 on the side the normals
+ * face (free space), > 0 behind the surface.  All tables come from the host builder (scene_gen.scan_sdf_tables):
+ *   bvh_nodes [2^(bvh_levels+1)-1, 8] device: implicit complete binary tree in heap order (node h at row h-1, children 2h and
+ *     2h+1), each row {lo.xyz, 0, hi.xyz, 0}; the leaves (depth bvh_levels) hold leaf_size consecutive triangles each;
+ *   triangles [F,12] device, in leaf order: {a.xyz, degenerate, b.xyz, 0, c.xyz, 0}; a degenerate (zero-area) triangle
+ *     counts for the distance but never decides a sign;
+ *   pseudo_normals [F,21] device: face, edge ab / bc / ca, vertex a / b / c normals of each triangle after welding.
+ */
+int egx_scan_sdf(const float* bvh_nodes, int bvh_levels, const float* triangles, const float* pseudo_normals, int num_triangles,
+                 int leaf_size, const float* center_host, float scale, int d0, int d1, int d2, float* out_grid, void* stream);
+
+/*
+ * egx_walkable_raster - per cell of a floor raster (cell (i,j) centred at origin + (i+0.5, j+0.5) * cell, out[i][j]):
+ *   support   1 iff the centre is covered in xy by an up-facing triangle (unit normal z >= min_up_nz) whose height there is
+ *             within +-floor_tol of floor_height;
+ *   clearance xy distance from the centre to the footprint of the parts of the triangles inside the slab z_lo <= z <= z_hi
+ *             (absolute heights; each triangle is clipped to the slab), about 1.8e19 when no triangle enters it.
+ *   triangles [F,9] device (ax,ay,az,bx,by,bz,cx,cy,cz).  Free cells (erosion of the support, clearance > radius) are decided
+ *   on the host (scene_gen.scan_walkable_grid).
+ */
+int egx_walkable_raster(const float* triangles, int num_triangles, float origin_x, float origin_y, float cell, int nx, int ny,
+                        float floor_height, float floor_tol, float min_up_nz, float z_lo, float z_hi, int* out_support,
+                        float* out_clearance, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Dense layers of the rollout networks.  One fused call replaces nn.Linear + torch.cat + activation
  * (+ residual) as composed in models/baseops.py:615-641 (MLP), models_GAMMA_primitive.py:160-175
