@@ -71,7 +71,10 @@ def get_args(argv=None, extra=(), defaults=None):
     # extensions (not in the reference)
     p.add_argument("--scene", type=str, default=None,
                    help="scene set: room0 | single_box | box (default: room0 for main_ppo, box for main_ppo_box), or the .npz of a "
-                        "scene prepared with egogen_amd.scene_gen.save_scene")
+                        "scene prepared with egogen_amd.scene_gen.save_scene - or a comma-separated list of SDF scenes of the same "
+                        "grid dimensions (a.npz,b.npz,scans/ - a directory stands for its *.npz files, sorted by name; room0 and "
+                        "single_box may be entries) to train ONE policy across all of them: agents are split into contiguous "
+                        "blocks, one per scene, in the train and test envs alike")
     p.add_argument("--sdf-res", type=int, default=256)
     p.add_argument("--save-rollout", type=int, default=None, help="write log/eval_results/motion_*.pkl (default: only with --watch)")
     p.add_argument("--num-verts", type=int, default=synth.NUM_VERTS, help="reduced synthetic body (tests)")

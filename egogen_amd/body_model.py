@@ -57,6 +57,36 @@ class SdfScene:
             self.desc.coarse_minmax = self.coarse.data_ptr()
 
 
+class SdfSceneSet:
+    """Several SDF scenes of the same grid dimensions for one penetration-count launch (`egx_sdf_scene_set_create`): each body is
+    counted in its agent's scene, `BodyModelHandle.forward(..., sdf=SdfSceneSet, agent_scene=[A] int)`.  Built from `SdfScene`s or
+    sdf dicts; keeps them (their grids and bracket tables) alive as long as the set."""
+
+    def __init__(self, scenes, device="cuda"):
+        scenes = list(scenes)
+        if not scenes:
+            raise ValueError("a scene set needs at least one scene")
+        self.scenes = [s if isinstance(s, SdfScene) else SdfScene(s, device=device) for s in scenes]
+        lib = _lib.load()
+        descs = (_lib.SdfGrid * len(self.scenes))(*[s.desc for s in self.scenes])
+        h = C.c_void_p()
+        _lib.check(lib.egx_sdf_scene_set_create(descs, len(self.scenes), C.byref(h)), "egx_sdf_scene_set_create")
+        self.handle = h
+        self.dims = tuple(int(x) for x in self.scenes[0].grid.shape)
+
+    def __len__(self):
+        return len(self.scenes)
+
+    def __del__(self):
+        h = getattr(self, "handle", None)
+        if h:
+            try:
+                _lib.load().egx_sdf_scene_set_destroy(h)
+            except Exception:
+                pass
+            self.handle = None
+
+
 class BodyModelHandle:
     """One immutable device-resident body model (per gender).  Thread-safe for concurrent forwards on
     distinct streams as long as each caller passes its own workspace."""
@@ -138,9 +168,12 @@ class BodyModelHandle:
         return int(n.value)
 
     def forward(self, xb: torch.Tensor, betas: torch.Tensor, frames_per_agent: int, want_verts=False,
-                want_joints=True, want_markers=True, sdf: Optional[SdfScene] = None,
-                R0: Optional[torch.Tensor] = None, T0: Optional[torch.Tensor] = None, out: Optional[dict] = None):
-        """xb[B,93], betas[A,10] (A*frames_per_agent == B).  Returns dict with the requested outputs."""
+                want_joints=True, want_markers=True, sdf=None,
+                R0: Optional[torch.Tensor] = None, T0: Optional[torch.Tensor] = None, out: Optional[dict] = None,
+                agent_scene: Optional[torch.Tensor] = None):
+        """xb[B,93], betas[A,10] (A*frames_per_agent == B).  Returns dict with the requested outputs.
+        `sdf`: an SdfScene, or an SdfSceneSet with `agent_scene` [A] (the scene of each agent; a value outside the set gives its
+        bodies the count -1)."""
         lib = _lib.load()
         B = int(xb.shape[0])
         if xb.dim() != 2 or xb.shape[1] != 93:
@@ -166,6 +199,22 @@ class BodyModelHandle:
             R0 = R0.to(torch.float32).reshape(A, 9).contiguous()
             T0 = T0.to(torch.float32).reshape(A, 3).contiguous()
         ws = self.workspace(B)
+        if isinstance(sdf, SdfSceneSet):
+            if agent_scene is None:
+                raise ValueError("a scene-set forward needs agent_scene [A]")
+            agent_scene = torch.as_tensor(agent_scene).to(device=dev, dtype=torch.int32).reshape(-1).contiguous()
+            if agent_scene.numel() != A:
+                raise ValueError(f"agent_scene must hold one scene index per agent ({A}), got {agent_scene.numel()}")
+            rc = lib.egx_lbs_forward_scenes(self.handle, _lib.ptr(xb), _lib.ptr(betas), B, int(frames_per_agent),
+                                            _lib.ptr(out.get("vertices")) if want_verts else None,
+                                            _lib.ptr(out.get("joints")) if want_joints else None,
+                                            _lib.ptr(out.get("markers")) if want_markers else None,
+                                            sdf.handle, _lib.ptr(agent_scene), _lib.ptr(R0), _lib.ptr(T0),
+                                            _lib.ptr(out["pene_count"]), _lib.ptr(ws), ws.numel(), _lib.current_stream_ptr())
+            _lib.check(rc, "egx_lbs_forward_scenes")
+            return out
+        if agent_scene is not None:
+            raise ValueError("agent_scene needs an SdfSceneSet")
         rc = lib.egx_lbs_forward(self.handle, _lib.ptr(xb), _lib.ptr(betas), B, int(frames_per_agent),
                                  _lib.ptr(out.get("vertices")) if want_verts else None,
                                  _lib.ptr(out.get("joints")) if want_joints else None,

@@ -20,7 +20,7 @@ import numpy as np
 import torch
 
 from . import _lib, synth
-from .body_model import BodyModelHandle, SdfScene
+from .body_model import BodyModelHandle, SdfScene, SdfSceneSet
 from .models import GAMMAPrimitiveCombo, VPoserEncoder
 
 DEFAULT_CFG = {  # crowd_ppo/cfg_samp20/MPVAEPolicy_samp_collision.yaml
@@ -45,11 +45,19 @@ def _rodrigues_np(aa: np.ndarray) -> np.ndarray:
 CAND_POOL = 16   # steps of reset candidates drawn at a time (SDF scenes)
 
 
+def block_scene_assignment(num_agents: int, num_scenes: int) -> np.ndarray:
+    """Scene of every agent of an SDF env over a set of scenes: contiguous blocks, agent a -> floor(a S / A) (balanced and
+    deterministic, like a vector of per-scene envs; a 256-body group of the LBS launch stays inside one scene)."""
+    if not 1 <= num_scenes <= num_agents:
+        raise ValueError(f"an SDF env over {num_scenes} scenes needs 1 <= scenes <= agents ({num_agents})")
+    return (np.arange(num_agents, dtype=np.int64) * num_scenes // num_agents).astype(np.int32)
+
+
 class VecCrowdEnv:
     def __init__(self, num_agents: int, body_model: BodyModelHandle, prior: GAMMAPrimitiveCombo, vposer: VPoserEncoder,
                  scene_kind: str = "sdf", sdf_dict: Optional[dict] = None, rings: Optional[List[np.ndarray]] = None,
                  pairs: Optional[np.ndarray] = None, box_scenes: Optional[List[dict]] = None,
-                 motion_seed: Optional[dict] = None, cfg: Optional[dict] = None, finetuning: bool = False,
+                 sdf_scenes: Optional[List[dict]] = None, motion_seed: Optional[dict] = None, cfg: Optional[dict] = None, finetuning: bool = False,
                  seed: int = 0, num_candidates: Optional[int] = None, use_graph: bool = False,
                  keep_rollout: bool = False, device: str = "cuda", crowd_bbox: Optional[torch.Tensor] = None,
                  crowd_member: int = 0, crowd_pairs=None, crowd_floor_half: float = 4.0,
@@ -64,7 +72,11 @@ class VecCrowdEnv:
         genop_2frame_male | female by it; every sampler but the EgoBody one draws from ['male'], environments.py:254,555,906);
         it is recorded in the saved rollouts.  `crowd_rings` / `crowd_static` / `agent_seeds` / `vp_thresh` / `goal_terminates` are the EgoBody-evaluation variant of
         the crowd scenes (crowd_env_egobody_eval.py, see CrowdGroupEnv): the scene's walkable polygon as exterior, one motion
-        seed (two frames + betas) per agent instead of one table for all, the looser pose filter, no goal termination."""
+        seed (two frames + betas) per agent instead of one table for all, the looser pose filter, no goal termination.
+        `sdf_scenes`: the SDF kind over a SET of scenes of the same grid dimensions, [{sdf_dict, rings, pairs, name}, ...]
+        (`sdf_dict` / `rings` / `pairs` are a set of one).  Agents are assigned to scenes once, in contiguous blocks
+        (`block_scene_assignment`, written to `scene_idx`); each draws its starts from its own scene's valid pairs, its rays hit
+        its own scene's polygon and its penetration count reads its own scene's SDF (one LBS launch over the set)."""
         if not torch.cuda.is_available():
             raise _lib.EgxError("VecCrowdEnv needs a HIP device (no CPU fallback)")
         self.lib = _lib.load()
@@ -128,15 +140,27 @@ class VecCrowdEnv:
 
         # ---- scenes ----
         self.sdf = None
+        self.scene_names = None
         self.R = 1   # reset rounds (box scenes: set below)
         if scene_kind == "sdf":
-            if sdf_dict is None or rings is None or pairs is None:
-                raise ValueError("sdf scene needs sdf_dict, rings (walkable polygon) and start/target pairs")
-            self.sdf = sdf_dict if isinstance(sdf_dict, SdfScene) else SdfScene(sdf_dict, device=self.dev)
-            edges = [synth.rings_to_edges(rings).astype(np.float32)]
-            tris = [np.zeros((0, 6), np.float32)]
-            floor = [0.0]
-            self.pairs_all = torch.tensor(np.asarray(pairs, np.float32), **f32).reshape(-1, 2, 3)
+            if sdf_scenes is None:
+                if sdf_dict is None or rings is None or pairs is None:
+                    raise ValueError("sdf scene needs sdf_dict, rings (walkable polygon) and start/target pairs")
+                sdf_scenes = [dict(sdf_dict=sdf_dict, rings=rings, pairs=pairs, name="scene")]
+            elif sdf_dict is not None or rings is not None or pairs is not None:
+                raise ValueError("pass either sdf_dict / rings / pairs or sdf_scenes, not both")
+            S = len(sdf_scenes)
+            self.scene_idx.copy_(torch.from_numpy(block_scene_assignment(A, S)))
+            self.scene_names = [str(d.get("name", f"scene{s}")) for s, d in enumerate(sdf_scenes)]
+            self.sdf_scenes = [d["sdf_dict"] if isinstance(d["sdf_dict"], SdfScene) else SdfScene(d["sdf_dict"], device=self.dev)
+                               for d in sdf_scenes]
+            # what the LBS call counts in: the scene itself (egx_lbs_forward), or the set with scene_idx as the agents' scenes
+            self.sdf = self.sdf_scenes[0] if S == 1 else SdfSceneSet(self.sdf_scenes)
+            edges = [synth.rings_to_edges(d["rings"]).astype(np.float32) for d in sdf_scenes]
+            tris = [np.zeros((0, 6), np.float32)] * S
+            floor = [0.0] * S
+            self.pairs_scene = [torch.tensor(np.asarray(d["pairs"], np.float32), **f32).reshape(-1, 2, 3) for d in sdf_scenes]
+            self.pairs_all = self.pairs_scene[0] if S == 1 else torch.cat(self.pairs_scene)
             self.K = int(num_candidates or 1)
         elif scene_kind == "box":
             if not box_scenes:
@@ -301,12 +325,23 @@ class VecCrowdEnv:
         io.out_choice = choice.data_ptr() if choice is not None else None
         return io
 
-    def _prevalidate_pairs(self, batch: int = 2048):
+    def _prevalidate_pairs(self):
         """SDF env: the rejection loop of CrowdEnv.reset (crowd_env_2f.py:326-396) accepts a start iff no non-feet
         vertex of the two seed frames has sdf < 0.  For the room sampler that is a deterministic function of the
         start/target pair, so every pair is evaluated once here (sampler kernel -> SMPL-X + SDF kernel) and reset
-        then draws uniformly among the accepted pairs - the same distribution as rejection sampling."""
-        N = self.pairs_all.shape[0]
+        then draws uniformly among the accepted pairs - the same distribution as rejection sampling.  With a set of scenes, each
+        scene's pairs are checked in that scene; an agent draws from its own scene's accepted pairs."""
+        masks = [self._prevalidate_scene(self.pairs_scene[s], self.sdf_scenes[s], s) for s in range(len(self.sdf_scenes))]
+        for s, m in enumerate(masks):
+            if not bool(m.any()):
+                raise RuntimeError(f"no start/target pair of scene {self.scene_names[s]!r} passes the SDF start check")
+        self.pair_valid_mask = masks[0] if len(masks) == 1 else torch.cat(masks)
+        self.valid_pairs = self.pairs_all[self.pair_valid_mask].contiguous()
+        n = torch.tensor([int(m.sum()) for m in masks], dtype=torch.int64, device=self.dev)
+        self._vp_n, self._vp_off = n, torch.cumsum(n, 0) - n   # per scene: accepted pairs, offset into valid_pairs
+
+    def _prevalidate_scene(self, pairs_all, sdf, scene, batch: int = 2048):
+        N = pairs_all.shape[0]
         f32 = dict(dtype=torch.float32, device=self.dev)
         i32 = dict(dtype=torch.int32, device=self.dev)
         valid = torch.zeros(N, dtype=torch.bool, device=self.dev)
@@ -314,21 +349,18 @@ class VecCrowdEnv:
             n = min(batch, N - s)
             tmp = dict(state=torch.zeros(n, 2, 402, **f32), seed=torch.zeros(n, 2, 93, **f32), R0=torch.zeros(n, 3, 3, **f32),
                        T0=torch.zeros(n, 3, **f32), dist=torch.zeros(n, **f32), steps=torch.zeros(n, **i32),
-                       wpath=torch.zeros(n, 2, 3, **f32), scene_idx=torch.zeros(n, **i32))
+                       wpath=torch.zeros(n, 2, 3, **f32), scene_idx=torch.full((n,), int(scene), **i32))
             st = self._make_state_struct(**tmp)
             ego, od, ot = torch.zeros(n, 2, 32, **f32), torch.zeros(n, **f32), torch.zeros(n, **f32)
-            cp = self.pairs_all[s:s + n].reshape(n, 1, 2, 3).contiguous()
+            cp = pairs_all[s:s + n].reshape(n, 1, 2, 3).contiguous()
             io = self._reset_io(n, 1, None, cp, None, None, None, None, ego, od, ot, None)
             _lib.check(self.lib.egx_env_reset(C.byref(self._ec), C.byref(self._sc), C.byref(st), C.byref(io), n,
                                               _lib.current_stream_ptr()), "egx_env_reset")
             betas = self.betas[:1].repeat(n, 1).contiguous()
             out = self.bm.forward(tmp["seed"].reshape(n * 2, 93), betas, 2, want_joints=False, want_markers=False,
-                                  sdf=self.sdf, R0=tmp["R0"], T0=tmp["T0"])
+                                  sdf=sdf, R0=tmp["R0"], T0=tmp["T0"])
             valid[s:s + n] = out["pene_count"].reshape(n, 2).sum(1) == 0
-        self.pair_valid_mask = valid
-        self.valid_pairs = self.pairs_all[valid].contiguous()
-        if self.valid_pairs.shape[0] == 0:
-            raise RuntimeError("no start/target pair passes the SDF start check")
+        return valid
 
     # ------------------------------------------------------------------------------------------
     def sample_candidates(self):
@@ -338,7 +370,12 @@ class VecCrowdEnv:
             # drawn for CAND_POOL steps at a time (one RNG launch + one gather per pool instead of three launches per step);
             # a step's candidates are a slice of the pool, handed to the reset kernel by address
             if self._cand_pool is None or self._cand_pool_pos >= CAND_POOL:
-                idx = torch.randint(0, self.valid_pairs.shape[0], (CAND_POOL * A * K,), generator=g, device=self.dev)
+                if len(self.sdf_scenes) == 1:
+                    idx = torch.randint(0, self.valid_pairs.shape[0], (CAND_POOL * A * K,), generator=g, device=self.dev)
+                else:   # each agent among its own scene's accepted pairs
+                    r = torch.randint(0, 1 << 30, (CAND_POOL, A, K), generator=g, device=self.dev)
+                    sc = self.scene_idx.long().view(1, A, 1)
+                    idx = (self._vp_off[sc] + r % self._vp_n[sc]).reshape(-1)
                 self._cand_pool = self.valid_pairs[idx].reshape(CAND_POOL, A, K, 2, 3)
                 self._cand_pool_pos = 0
             self._cand_step = self._cand_pool[self._cand_pool_pos]
@@ -455,7 +492,8 @@ class VecCrowdEnv:
             _lib.check(lib.egx_profile_next_lbs(ev0, ev1), "egx_profile_next_lbs")
         self.bm.forward(self.pred_params.reshape(A * 20, 93), self.betas, 20, want_verts=False,
                         sdf=self.sdf, R0=self.R0 if self.sdf is not None else None,
-                        T0=self.T0 if self.sdf is not None else None, out=self._lbs_out)
+                        T0=self.T0 if self.sdf is not None else None, out=self._lbs_out,
+                        agent_scene=self.scene_idx if isinstance(self.sdf, SdfSceneSet) else None)
         # VPoser embedding of the 20 body poses (crowd_env_2f.py:197-198)
         self.vposer.encode_mean_into(self.pred_params.reshape(A * 20, 93)[:, 6:], 93, A * 20, self.vp_emb)
         _lib.check(lib.egx_env_step_post(C.byref(self._ec), C.byref(self._sc), C.byref(self._st), C.byref(self._io), A, st),

@@ -236,6 +236,9 @@ __device__ __forceinline__ void lbs_joint_rotation(const PoseConsts* __restrict_
 // ------------------------------------------------------------------------------------------------
 // kernel 1: per-body pose features, rigid chain, joint transforms
 // ------------------------------------------------------------------------------------------------
+// MS (scene sets, egx_lbs_forward_scenes): the agent's scene - agent_scene[agent] of the set's table `scenes` - replaces `sdf` in the
+// canonical-frame -> SDF-cell map, and a body whose agent names no scene of the set gets the count -1 instead of 0.
+template <bool MS>
 __global__ __launch_bounds__(256) void egx_pose_chain_kernel(const PoseConsts* __restrict__ pc,
                                                              const float* __restrict__ xb,
                                                              const float* __restrict__ betas, int B, int fpa,
@@ -254,7 +257,9 @@ __global__ __launch_bounds__(256) void egx_pose_chain_kernel(const PoseConsts* _
                                                              int* __restrict__ fix_stats /* [1] cleared here, or null */,
                                                              unsigned short* __restrict__ skinB /* matrix-pipe skinning operands (see SKIN_BT_BYTES) or null */,
                                                              f32x4* __restrict__ cinit /* [Bp] per slot: cell coordinates of the body's translation */,
-                                                             const float* __restrict__ R0, const float* __restrict__ T0, SdfDev sdf) {
+                                                             const float* __restrict__ R0, const float* __restrict__ T0, SdfDev sdf,
+                                                             const SdfSceneDev* __restrict__ scenes, const int* __restrict__ agent_scene,
+                                                             int n_scenes) {
   __shared__ float sR[4][NJ][9];
   __shared__ float sJ[4][NJ][3];
   __shared__ float sG[4][NJ][12];
@@ -267,7 +272,12 @@ __global__ __launch_bounds__(256) void egx_pose_chain_kernel(const PoseConsts* _
   const bool live = slot < B;
   const int ss = live ? slot : B - 1;
   const int b = agent_of_slot ? agent_of_slot[ss / fpa] * fpa + ss % fpa : ss;
-  if (zero_counts && live && j == 0) zero_counts[b] = 0;   // the SDF epilogue of the skinning kernel adds to these
+  [[maybe_unused]] int scn = 0;   // MS: the agent's scene, -1 when agent_scene names none of the set (reads below use scene 0)
+  if constexpr (MS) {
+    const int v = agent_scene[b / fpa];
+    scn = (v >= 0 && v < n_scenes) ? v : -1;
+  }
+  if (zero_counts && live && j == 0) zero_counts[b] = scn < 0 ? -1 : 0;   // the SDF epilogue of the skinning kernel adds to these
   if (fix_stats && blockIdx.x == 0 && threadIdx.x <= LBS_FIX_NQ) fix_stats[threadIdx.x == 0 ? 0 : LBS_FIX_CNT0 + 32 * (threadIdx.x - 1)] = 0;
   const int bb = b;
   const float* x = xb + (size_t)bb * EGX_XB_DIM;
@@ -451,6 +461,7 @@ __global__ __launch_bounds__(256) void egx_pose_chain_kernel(const PoseConsts* _
     const int ag = bb / fpa;
     float Mc[9], tcv[3];
     {
+      if constexpr (MS) sdf = egx_sdf_scene(sdf, scenes[max(scn, 0)]);
       const float kk[3] = {sdf.scale * (float)sdf.d0 * 0.5f, sdf.scale * (float)sdf.d1 * 0.5f, sdf.scale * (float)sdf.d2 * 0.5f};
       const float cc[3] = {sdf.cx, sdf.cy, sdf.cz};
       const float dd[3] = {(float)sdf.d0, (float)sdf.d1, (float)sdf.d2};
@@ -571,7 +582,21 @@ struct LbsParams {
   const int* skin_ks_off;     // [NVT+1]
   const bf16x8* skinB;        // [bt] SKIN_BT_BYTES each
   const f32x4* cinit;         // [Bp]
+  // scene sets (egx_lbs_forward_scenes, the MS instantiations): the scene of body b is agent_scene[b / fpa], an index into `scenes`;
+  // `sdf` then holds only the grid dimensions the scenes share
+  const SdfSceneDev* scenes;  // [n_scenes] or null (one scene: sdf, sdf_aux)
+  const int* agent_scene;     // [A]
+  int n_scenes;
 };
+
+// Scene of agent `ag` of a set launch: false when agent_scene names no scene of the set (the pose kernel gave that body the count -1;
+// the epilogues then count nothing for it); `s` is clamped into the set either way, so every read stays inside the table.
+__device__ __forceinline__ bool lbs_scene_of(const LbsParams& p, int ag, int& s) {
+  const int v = p.agent_scene[ag];
+  const bool ok = v >= 0 && v < p.n_scenes;
+  s = ok ? v : 0;
+  return ok;
+}
 
 // Operand slot of body column n of 32-body tile bt: the slot itself, or, for the dead columns of the last tile (B % 32 != 0) and of a
 // tile past it, the last live slot - whose feature, transform and skinning records the pose kernel wrote in this call.  The results
@@ -715,11 +740,17 @@ __device__ __forceinline__ void lbs_fix_blend_planes(const LbsParams& p, int lan
 // and the trilinear sample decides.  ~70 cache lines per vertex (the first version read the MFMA-ordered operand images: 720
 // lines, and 22 000 vertices of a launch with every body inside the obstacle took 330 us).
 // Returns -trilinear (wave-uniform); negative = the vertex counts.
-template <bool VERTEX_MAJOR>
+template <bool VERTEX_MAJOR, bool MS = false>
 __device__ __forceinline__ float lbs_fix_one(const LbsParams& p, int lane, int vt, int row, int slot, int JT, const int* jl, const float* Wt) {
   const int bt = slot >> 5, n = slot & 31;
   const int body = p.agent_of_slot ? p.agent_of_slot[slot / p.fpa] * p.fpa + slot % p.fpa : slot;
   const int ag = body / p.fpa;
+  SdfDev sd = p.sdf;   // the body's scene
+  if constexpr (MS) {
+    int sc;
+    lbs_scene_of(p, ag, sc);
+    sd = egx_sdf_scene(p.sdf, p.scenes[sc]);
+  }
   // v_posed = v_template + shape offsets + pose correctives, in fp32 from the vertex-major bases: lane j owns joint j - it
   // recomputes the joint's rotation from the body's parameter row (the pose kernel's formulas) and multiplies its nine R - I
   // entries with the vertex's nine columns of that joint (36 contiguous bytes per coordinate); lane 0 (the global orientation is
@@ -768,9 +799,9 @@ __device__ __forceinline__ float lbs_fix_one(const LbsParams& p, int lane, int v
 #pragma unroll
   for (int a = 0; a < 3; ++a) o[a] = lbs_wave_sum(o[a]) + p.xb[(size_t)body * EGX_XB_DIM + a];
   // canonical frame -> world -> voxel coordinates: the folded affine map of the epilogue
-  const float kk[3] = {p.sdf.scale * (float)p.sdf.d0 * 0.5f, p.sdf.scale * (float)p.sdf.d1 * 0.5f, p.sdf.scale * (float)p.sdf.d2 * 0.5f};
-  const float cc[3] = {p.sdf.cx, p.sdf.cy, p.sdf.cz};
-  const float dd[3] = {(float)p.sdf.d0, (float)p.sdf.d1, (float)p.sdf.d2};
+  const float kk[3] = {sd.scale * (float)sd.d0 * 0.5f, sd.scale * (float)sd.d1 * 0.5f, sd.scale * (float)sd.d2 * 0.5f};
+  const float cc[3] = {sd.cx, sd.cy, sd.cz};
+  const float dd[3] = {(float)sd.d0, (float)sd.d1, (float)sd.d2};
   float vox[3];
 #pragma unroll
   for (int a = 0; a < 3; ++a) {
@@ -780,8 +811,8 @@ __device__ __forceinline__ float lbs_fix_one(const LbsParams& p, int lane, int v
     const float tw = kk[a] * ((p.T0 ? p.T0[(size_t)ag * 3 + a] : 0.f) - cc[a]) + (dd[a] - 1.f) * 0.5f;
     vox[a] = fmaf(Mw[0], o[0], fmaf(Mw[1], o[1], fmaf(Mw[2], o[2], tw)));
   }
-  return egx_sdf_neg_trilinear_at(p.sdf, __builtin_amdgcn_fmed3f(vox[0], 0.f, (float)(p.sdf.d0 - 1)), __builtin_amdgcn_fmed3f(vox[1], 0.f, (float)(p.sdf.d1 - 1)),
-                                  __builtin_amdgcn_fmed3f(vox[2], 0.f, (float)(p.sdf.d2 - 1)));
+  return egx_sdf_neg_trilinear_at(sd, __builtin_amdgcn_fmed3f(vox[0], 0.f, (float)(sd.d0 - 1)), __builtin_amdgcn_fmed3f(vox[1], 0.f, (float)(sd.d1 - 1)),
+                                  __builtin_amdgcn_fmed3f(vox[2], 0.f, (float)(sd.d2 - 1)));
 }
 
 // What a wave does with the vertices of its item that fell into the band (bit r of s_fixmap[q*32 + n] = row r of the item's
@@ -790,7 +821,7 @@ __device__ __forceinline__ float lbs_fix_one(const LbsParams& p, int lane, int v
 // instead (a whole wave busy for several dependent round trips per vertex while the three other waves of its workgroup wait at
 // the next item's barrier) cost 55 us of a 700 us launch for 3 300 vertices; the queue costs one atomic per wave and item
 // that has any.  Only when the queue is full are they re-evaluated on the spot.
-template <int NB>
+template <int NB, bool MS = false>
 __device__ __forceinline__ void lbs_fix_process(const LbsParams& p, const LbsWave& w, int vt, int bt0, int JT) {
   const int lane = w.lane;
   unsigned mybits = lane < 32 * NB ? w.s_fixmap[lane] : 0u;
@@ -830,7 +861,7 @@ __device__ __forceinline__ void lbs_fix_process(const LbsParams& p, const LbsWav
     while (bits != 0u) {
       const int row = __builtin_ctz(bits);
       bits &= bits - 1;
-      const float sv = lbs_fix_one<false>(p, lane, vt, row, slot, JT, w.s_jl, w.s_W);
+      const float sv = lbs_fix_one<false, MS>(p, lane, vt, row, slot, JT, w.s_jl, w.s_W);
       if (lane == 0) {
         if (sv < 0.f) atomicAdd(&w.s_cnt[sl], 1);
         atomicAdd(p.fix_stats, 1);
@@ -839,7 +870,7 @@ __device__ __forceinline__ void lbs_fix_process(const LbsParams& p, const LbsWav
   }
 }
 
-template <bool WRITE_VERTS, bool DO_SDF, int RB, int QCAP, int NB = LBS_NB, bool FIX = false>
+template <bool WRITE_VERTS, bool DO_SDF, int RB, int QCAP, int NB = LBS_NB, bool FIX = false, bool MS = false>
 __device__ __forceinline__ void lbs_epilogue(const LbsParams& p, LbsWave& w, f32x16 (&acc)[3][NB], int vt, int bt0, int JT, bool fix_on = false) {
   const int lane = w.lane, n = w.n, half = w.half;
   float* s_W = w.s_W; int* s_jl = w.s_jl; int* s_slot = w.s_slot; unsigned* s_masks = w.s_masks; int* s_cnt = w.s_cnt;
@@ -864,7 +895,8 @@ __device__ __forceinline__ void lbs_epilogue(const LbsParams& p, LbsWave& w, f32
   [[maybe_unused]] float thr[NB];
 #pragma unroll
   for (int q = 0; q < NB; ++q) thr[q] = 0.f;
-  if constexpr (FIX && DO_SDF) {
+  // (set launches: per body tile, with the body's scene, below - the scene is not kept alive across the skinning)
+  if constexpr (FIX && DO_SDF && !MS) {
     if (fix_on) {
       const float lip = p.sdf_aux[3];   // steepest slope of the interpolated field, value per metre
 #pragma unroll
@@ -883,8 +915,14 @@ __device__ __forceinline__ void lbs_epilogue(const LbsParams& p, LbsWave& w, f32
       const int idx = base + lane;
       if (idx < count) {
         const f32x4 e = s_queue[idx];
-        const int code = __float_as_int(e[3]);   // counter slot | vertex row << 8
-        const float sv = egx_sdf_neg_trilinear_at(p.sdf, e[0], e[1], e[2]);
+        int code = __float_as_int(e[3]);   // counter slot | vertex row << 8 (| scene << 16 in set launches)
+        float sv;
+        if constexpr (MS) {
+          sv = egx_sdf_neg_trilinear_at(egx_sdf_scene(p.sdf, p.scenes[code >> 16]), e[0], e[1], e[2]);
+          code &= 0xffff;
+        } else {
+          sv = egx_sdf_neg_trilinear_at(p.sdf, e[0], e[1], e[2]);
+        }
         if constexpr (FIX) {
           const float t = fix_on ? w.s_thr[code & 63] : 0.f;
           if (sv < -t) atomicAdd(&s_cnt[code & 63], 1);
@@ -977,17 +1015,31 @@ __device__ __forceinline__ void lbs_epilogue(const LbsParams& p, LbsWave& w, f32
       // with 64 different bodies across the lanes that is almost every row.  Undecided points are therefore appended
       // to a wave-private LDS queue and evaluated densely (64 queued points per pass) by sdf_flush().
       const int ag = body[q] / p.fpa;
+      SdfDev sd = p.sdf;   // the body's scene (set launches: its grid, table, center, scale and slope)
+      bool sok = true;     // it exists (always, outside set launches)
+      [[maybe_unused]] int scn = 0;
+      if constexpr (MS) {
+        sok = lbs_scene_of(p, ag, scn);
+        const SdfSceneDev& sc = p.scenes[scn];
+        sd = egx_sdf_scene(p.sdf, sc);
+        if constexpr (FIX) {
+          if (fix_on) {
+            thr[q] = p.fix_e[min((bt0 + q) * 32 + n, p.B - 1)] * sc.slope;
+            w.s_thr[q * 32 + n] = thr[q];
+          }
+        }
+      }
       // canonical frame -> world (R0, T0) -> unclamped voxel coordinates ((w - c) scale + 1) d / 2 - 1 / 2 folded into one
       // affine map per body (align_corners=False, utils.py:58-68); the clamp (padding "border") happens in the lookup /
       // before the exact evaluation.  The folded rounding differs from the reference's chain by ~1e-7 relative - far
       // inside the level-set band the counts are compared in.
       float Mw[9], tw[3];
       {
-        const float kx = p.sdf.scale * (float)p.sdf.d0 * 0.5f, ky = p.sdf.scale * (float)p.sdf.d1 * 0.5f,
-                    kz = p.sdf.scale * (float)p.sdf.d2 * 0.5f;
+        const float kx = sd.scale * (float)sd.d0 * 0.5f, ky = sd.scale * (float)sd.d1 * 0.5f,
+                    kz = sd.scale * (float)sd.d2 * 0.5f;
         const float kk[3] = {kx, ky, kz};
-        const float cc[3] = {p.sdf.cx, p.sdf.cy, p.sdf.cz};
-        const float dd[3] = {(float)p.sdf.d0, (float)p.sdf.d1, (float)p.sdf.d2};
+        const float cc[3] = {sd.cx, sd.cy, sd.cz};
+        const float dd[3] = {(float)sd.d0, (float)sd.d1, (float)sd.d2};
 #pragma unroll
         for (int a = 0; a < 3; ++a) {
 #pragma unroll
@@ -996,7 +1048,7 @@ __device__ __forceinline__ void lbs_epilogue(const LbsParams& p, LbsWave& w, f32
         }
       }
       const float hx = (float)(p.sdf.d0 - 1), hy = (float)(p.sdf.d1 - 1), hz = (float)(p.sdf.d2 - 1);
-      const unsigned mine = bvalid[q] ? (sdf_mask >> (4 * half)) : 0u;  // bit (r&3)+8(r>>2) = this lane's row r
+      const unsigned mine = (bvalid[q] && sok) ? (sdf_mask >> (4 * half)) : 0u;  // bit (r&3)+8(r>>2) = this lane's row r
       int cnt = 0;
       // all sixteen bracket lookups of the lane's rows are issued before the first one is used: one L2 round trip per body
       // tile instead of one per batch of RB rows (round 4; the epilogue is a latency chain - two waves per SIMD - and these
@@ -1014,12 +1066,14 @@ __device__ __forceinline__ void lbs_epilogue(const LbsParams& p, LbsWave& w, f32
         tc[a] = fmaf(0.25f, tw[a], 1.f);
       }
       auto cell = [&](int r, int a) { return fmaf(Mc[a * 3 + 0], o[r][0], fmaf(Mc[a * 3 + 1], o[r][1], fmaf(Mc[a * 3 + 2], o[r][2], tc[a]))); };
-      constexpr int LB = WRITE_VERTS ? RB : 16;   // rows per lookup burst (the vertex-writing variant has no registers to spare)
+      // rows per lookup burst: the vertex-writing variant has no registers to spare, nor has the mixed blend's set launch (its body's
+      // table pointer is live beside the accumulators; this path takes only its picked and long-list tiles, 27 of 328)
+      constexpr int LB = WRITE_VERTS ? RB : ((MS && FIX) ? 8 : 16);
 #pragma unroll
       for (int rb0 = 0; rb0 < 16; rb0 += LB) {
       float2 mm[LB];
 #pragma unroll
-      for (int r = rb0; r < rb0 + LB; ++r) mm[r - rb0] = egx_sdf_coarse_at_cell(p.sdf, cell(r, 0), cell(r, 1), cell(r, 2));
+      for (int r = rb0; r < rb0 + LB; ++r) mm[r - rb0] = egx_sdf_coarse_at_cell(sd, cell(r, 0), cell(r, 1), cell(r, 2));
 #pragma unroll
       for (int r0 = rb0; r0 < rb0 + LB; r0 += RB) {
         if (qn + RB * 64 > QCAP) { sdf_flush(qn); qn = 0; }  // room for one batch: RB rows x 64 lanes
@@ -1039,7 +1093,7 @@ __device__ __forceinline__ void lbs_epilogue(const LbsParams& p, LbsWave& w, f32
               asm volatile("" : "+v"(ln));
               s_queue[pos] = f32x4{__builtin_amdgcn_fmed3f(world(r, 0), 0.f, hx), __builtin_amdgcn_fmed3f(world(r, 1), 0.f, hy),
                                    __builtin_amdgcn_fmed3f(world(r, 2), 0.f, hz),
-                                   __int_as_float((q * 32 + (ln & 31)) | (r << 8) | ((ln >> 5) << 12))};
+                                   __int_as_float((q * 32 + (ln & 31)) | (r << 8) | ((ln >> 5) << 12) | (MS ? scn << 16 : 0))};
             }
             qn += __popcll(bm);
           }
@@ -1109,7 +1163,7 @@ __device__ __forceinline__ void lbs_epilogue(const LbsParams& p, LbsWave& w, f32
     if constexpr (FIX) {
       if (fix_on) {   // wave-uniform
         const unsigned fb = lane < 32 * NB ? w.s_fixmap[lane] : 0u;
-        if (__ballot(fb != 0u) != 0ull) lbs_fix_process<NB>(p, w, vt, bt0, JT);
+        if (__ballot(fb != 0u) != 0ull) lbs_fix_process<NB, MS>(p, w, vt, bt0, JT);
         __builtin_amdgcn_wave_barrier();
       }
     }
@@ -1148,7 +1202,7 @@ __device__ __forceinline__ void lbs_epilogue(const LbsParams& p, LbsWave& w, f32
 // MFMA operands (entry-major, eight joints each) by 48 v_perm_b32: one L2 round trip per body tile instead of one per joint.
 // What it costs: 24 MFMAs per body tile on a matrix pipe that was 23 % busy, and a position error of up to LBS_SKIN_ERR (|v| + |t|),
 // which the fix-up band absorbs - the result only classifies, lbs_fix_process decides the close calls.
-template <int RB, int QCAP, int NB>
+template <int RB, int QCAP, int NB, bool MS = false>
 __device__ __forceinline__ void lbs_epilogue_cell(const LbsParams& p, LbsWave& w, f32x16 (&acc)[3][NB], int vt, int bt0, int JT) {
   int lane = w.lane;
   asm volatile("" : "+v"(lane));   // per-lane operand addresses are formed per item (not kept alive as invariants of the persistent loop)
@@ -1158,7 +1212,8 @@ __device__ __forceinline__ void lbs_epilogue_cell(const LbsParams& p, LbsWave& w
   int qn = w.qn;
   const unsigned sdf_mask = (unsigned)__builtin_amdgcn_readfirstlane((int)w.s_masks[1]);
   const int ks0 = __builtin_amdgcn_readfirstlane(p.skin_ks_off[vt]);   // JT <= 8 here: one k-step (the caller sends longer lists to the VALU epilogue)
-  const float lip = p.sdf_aux[3];   // steepest slope of the interpolated field, value per metre
+  [[maybe_unused]] float lip = 0.f;   // steepest slope of the interpolated field, value per metre (set launches: per body, below)
+  if constexpr (!MS) lip = p.sdf_aux[3];
   const float hx = (float)(p.sdf.d0 - 1), hy = (float)(p.sdf.d1 - 1), hz = (float)(p.sdf.d2 - 1);
   auto sdf_flush = [&](int count) {
     __builtin_amdgcn_wave_barrier();
@@ -1166,8 +1221,14 @@ __device__ __forceinline__ void lbs_epilogue_cell(const LbsParams& p, LbsWave& w
       const int idx = base + lane;
       if (idx < count) {
         const f32x4 e = s_queue[idx];
-        const int code = __float_as_int(e[3]);   // counter slot | accumulator row << 8 | lane half << 12
-        const float sv = egx_sdf_neg_trilinear_at(p.sdf, e[0], e[1], e[2]);
+        int code = __float_as_int(e[3]);   // counter slot | accumulator row << 8 | lane half << 12 (| scene << 16 in set launches)
+        float sv;
+        if constexpr (MS) {
+          sv = egx_sdf_neg_trilinear_at(egx_sdf_scene(p.sdf, p.scenes[code >> 16]), e[0], e[1], e[2]);
+          code &= 0xffff;
+        } else {
+          sv = egx_sdf_neg_trilinear_at(p.sdf, e[0], e[1], e[2]);
+        }
         const float t = w.s_thr[code & 63];
         if (sv < -t) atomicAdd(&s_cnt[code & 63], 1);
         else if (sv <= t) {
@@ -1194,7 +1255,8 @@ __device__ __forceinline__ void lbs_epilogue_cell(const LbsParams& p, LbsWave& w
     const int slot = (bt0 + q) * 32 + n;
     const bool bvalid = slot < p.B;
     const f32x4 ci = p.cinit[bvalid ? slot : p.B - 1];
-    const float fe = p.fix_e[bvalid ? slot : p.B - 1];   // requested here, used after the skinning
+    [[maybe_unused]] float fe = 0.f;
+    if constexpr (!MS) fe = p.fix_e[bvalid ? slot : p.B - 1];   // requested here, used after the skinning (set launches: below)
     // this lane's records: plane = lane half, body column n; record of joint j at index j * 64
     const int ls = lbs_live_slot(bt0 + q, n, p.B);
     const char* tile_base = reinterpret_cast<const char*>(p.skinB) + (size_t)(ls >> 5) * SKIN_BT_BYTES;
@@ -1262,16 +1324,28 @@ __device__ __forceinline__ void lbs_epilogue_cell(const LbsParams& p, LbsWave& w
       }
     }
     // SDF: bracket lookups of all sixteen rows in one burst (cell coordinates are what the skinning produced), decisions with the
-    // body's band, undecided points to the wave's queue as clamped voxel coordinates 4 (cell - 1)
-    const unsigned mine = bvalid ? (sdf_mask >> (4 * half)) : 0u;
+    // body's band, undecided points to the wave's queue as clamped voxel coordinates 4 (cell - 1).  Set launches look the body's
+    // scene up here, after the skinning: its table pointer is not kept alive across the MFMAs
+    bool sok = true;   // the body's scene exists (always, outside set launches)
+    [[maybe_unused]] int scn = 0;
+    SdfDev sd = p.sdf;
+    [[maybe_unused]] float lip_q = lip;
+    if constexpr (MS) {
+      sok = lbs_scene_of(p, (bvalid ? slot : p.B - 1) / p.fpa, scn);
+      const SdfSceneDev& sc = p.scenes[scn];
+      sd = egx_sdf_scene(p.sdf, sc);
+      lip_q = sc.slope;
+      fe = p.fix_e[bvalid ? slot : p.B - 1];
+    }
+    const unsigned mine = (bvalid && sok) ? (sdf_mask >> (4 * half)) : 0u;
     int cnt = 0;
     float2 mm[16];
 #pragma unroll
-    for (int r = 0; r < 16; ++r) mm[r] = egx_sdf_coarse_at_cell(p.sdf, o[r][0], o[r][1], o[r][2]);
+    for (int r = 0; r < 16; ++r) mm[r] = egx_sdf_coarse_at_cell(sd, o[r][0], o[r][1], o[r][2]);
 #ifdef EGX_LBS_THR0   // development builds (A/B timing): no band - the cheap evaluation decides everything
     const float thr = 0.f * fe;
 #else
-    const float thr = fe * lip;
+    const float thr = fe * lip_q;
 #endif
     w.s_thr[q * 32 + n] = thr;   // both lane halves write the same value
 #pragma unroll
@@ -1291,7 +1365,7 @@ __device__ __forceinline__ void lbs_epilogue_cell(const LbsParams& p, LbsWave& w
             asm volatile("" : "+v"(ln));
             s_queue[pos] = f32x4{__builtin_amdgcn_fmed3f(fmaf(4.f, o[r][0], -4.f), 0.f, hx), __builtin_amdgcn_fmed3f(fmaf(4.f, o[r][1], -4.f), 0.f, hy),
                                  __builtin_amdgcn_fmed3f(fmaf(4.f, o[r][2], -4.f), 0.f, hz),
-                                 __int_as_float((q * 32 + (ln & 31)) | (r << 8) | ((ln >> 5) << 12))};
+                                 __int_as_float((q * 32 + (ln & 31)) | (r << 8) | ((ln >> 5) << 12) | (MS ? scn << 16 : 0))};
           }
           qn += __popcll(bm);
         }
@@ -1311,7 +1385,7 @@ __device__ __forceinline__ void lbs_epilogue_cell(const LbsParams& p, LbsWave& w
 #ifdef EGX_LBS_NOFIXPROC   // development builds (A/B timing): the band is kept, what falls into it is dropped
     if (fb != 0u) w.s_fixmap[lane] = 0u;
 #else
-    if (__ballot(fb != 0u) != 0ull) lbs_fix_process<NB>(p, w, vt, bt0, JT);
+    if (__ballot(fb != 0u) != 0ull) lbs_fix_process<NB, MS>(p, w, vt, bt0, JT);
 #endif
     __builtin_amdgcn_wave_barrier();
   }
@@ -1390,7 +1464,8 @@ __device__ __forceinline__ void lbs_blend_f32(const LbsParams& p, f32x16 (&acc)[
 
 }
 
-template <bool WRITE_VERTS, bool DO_SDF>
+// MS: scene-set launch (egx_lbs_forward_scenes) - every read of scene data uses the body's own scene
+template <bool WRITE_VERTS, bool DO_SDF, bool MS = false>
 __global__ __launch_bounds__(LBS_THREADS, 1) void egx_lbs_fused_kernel(LbsParams p) {
   constexpr int NB = LBS_NB;
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
@@ -1438,7 +1513,7 @@ __global__ __launch_bounds__(LBS_THREADS, 1) void egx_lbs_fused_kernel(LbsParams
       if (sum == 123.456f) p.pene[0] = 1;
       continue;
     }
-    lbs_epilogue<WRITE_VERTS, DO_SDF, 8, LBS_QCAP>(p, w, acc, vt, bt0, JT);
+    lbs_epilogue<WRITE_VERTS, DO_SDF, 8, LBS_QCAP, LBS_NB, false, MS>(p, w, acc, vt, bt0, JT);
   }
 }
 
@@ -1719,7 +1794,7 @@ template <int NBW> constexpr int lbs3_ring_bytes() { return NBW == 1 ? 2 * M4_RI
 template <int NBW> constexpr size_t lbs3_lds_bytes() { return (size_t)lbs3_ring_bytes<NBW>() + 7424 + 4 * lbs3_wave_bytes<NBW>(); }
 static_assert(lbs3_lds_bytes<1>() <= 53504, "three workgroups of the small wave tile share a CU's LDS: not above round 5's size");
 
-template <int NPL, bool DO_SDF, int NBW = LBS_NB>
+template <int NPL, bool DO_SDF, int NBW = LBS_NB, bool MS = false>
 __global__ __launch_bounds__(256, NBW == 1 ? 3 : 2) void egx_lbs_fused3_kernel(LbsParams p) {
   constexpr int NB = NBW;
   static_assert(NBW == LBS_NB || NPL == 4, "the small wave tile exists for the mixed blend only");
@@ -1831,14 +1906,14 @@ __global__ __launch_bounds__(256, NBW == 1 ? 3 : 2) void egx_lbs_fused3_kernel(L
     constexpr bool FIX = NPL == 4 && DO_SDF;
 #endif
 #ifdef EGX_LBS_VALU_SKIN   // development builds: the count-only tiles skinned on the VALU as well (fix-up only), for A/B timing
-    lbs_epilogue<false, DO_SDF, LBS3_RB, lbs3_qcap<NB>(), NB, FIX>(p, w, acc, vt, bt0, JT, FIX && vti >= p.n_precise);
+    lbs_epilogue<false, DO_SDF, LBS3_RB, lbs3_qcap<NB>(), NB, FIX, MS>(p, w, acc, vt, bt0, JT, FIX && vti >= p.n_precise);
 #else
     // count-only tiles whose joint list fits one k-step (eight joints: 309 of the 328 tiles of the synthetic body) are skinned on
     // the matrix pipe; the tiles with picked vertices (exact positions) and the long lists take the VALU epilogue - the latter with
     // the fix-up band as well, since their blend product is the cheap one too.  The small wave tile (three workgroups per CU, 168
     // registers) has no room for the twelve operands: VALU epilogue throughout.
-    if (FIX && NB == LBS_NB && vti >= p.n_precise && JT <= 8) lbs_epilogue_cell<LBS3_RB, lbs3_qcap<NB>(), NB>(p, w, acc, vt, bt0, JT);
-    else lbs_epilogue<false, DO_SDF, LBS3_RB, lbs3_qcap<NB>(), NB, FIX>(p, w, acc, vt, bt0, JT, FIX && vti >= p.n_precise);
+    if (FIX && NB == LBS_NB && vti >= p.n_precise && JT <= 8) lbs_epilogue_cell<LBS3_RB, lbs3_qcap<NB>(), NB, MS>(p, w, acc, vt, bt0, JT);
+    else lbs_epilogue<false, DO_SDF, LBS3_RB, lbs3_qcap<NB>(), NB, FIX, MS>(p, w, acc, vt, bt0, JT, FIX && vti >= p.n_precise);
 #endif
 #ifdef EGX_LBS_TIMING
     w.et[4] += LBS_NOW() - item_t0; w.et[5] += 1;
@@ -1878,6 +1953,7 @@ __global__ __launch_bounds__(256, NBW == 1 ? 3 : 2) void egx_lbs_fused3_kernel(L
 constexpr int LBS_FIXQ_CAP = 1 << 12;   // entries per sub-queue: 64 x 4096 x 8 bytes = 2 MB of workspace, 25 vertices per body at 10 240 bodies
 constexpr int LBS_FIX_BLOCKS = 1024;
 static_assert((LBS_FIX_BLOCKS * 4) % LBS_FIX_NQ == 0, "waves of the fix-up kernel per sub-queue");
+template <bool MS>
 __global__ __launch_bounds__(256) void egx_lbs_fix_kernel(LbsParams p) {
   const int lane = threadIdx.x & 63;
   const int wave = blockIdx.x * 4 + (threadIdx.x >> 6), n_waves = gridDim.x * 4;
@@ -1888,7 +1964,7 @@ __global__ __launch_bounds__(256) void egx_lbs_fix_kernel(LbsParams p) {
     if (e.x < 0) continue;   // wave-uniform
     const int vt = e.x >> 5, row = e.x & 31, slot = e.y;
     const int j_lo = p.tj_off[vt], JT = p.tj_off[vt + 1] - j_lo;
-    const float sv = lbs_fix_one<true>(p, lane, vt, row, slot, JT, p.tj_idx + j_lo, p.tj_w + (size_t)j_lo * 32);
+    const float sv = lbs_fix_one<true, MS>(p, lane, vt, row, slot, JT, p.tj_idx + j_lo, p.tj_w + (size_t)j_lo * 32);
     if (lane == 0 && sv < 0.f) {
       const int body = p.agent_of_slot ? p.agent_of_slot[slot / p.fpa] * p.fpa + slot % p.fpa : slot;
       atomicAdd(p.pene + body, 1);
@@ -2745,20 +2821,94 @@ extern "C" int egx_lbs_joints(const egx_body_model* m, const float* xb, const fl
     return EGX_ERR_WORKSPACE;
   }
   char* ws = static_cast<char*>(workspace);
-  hipLaunchKernelGGL(egx_pose_chain_kernel, dim3(egx_ceil_div(B, 4)), dim3(256), 0, static_cast<hipStream_t>(stream_), m->pc, xb,
+  hipLaunchKernelGGL(egx_pose_chain_kernel<false>, dim3(egx_ceil_div(B, 4)), dim3(256), 0, static_cast<hipStream_t>(stream_), m->pc, xb,
                      betas, B, fpa, static_cast<float*>(nullptr), static_cast<unsigned short*>(nullptr),
                      reinterpret_cast<f32x4*>(ws + wl.A4), out_joints55, NJ, 0.f, static_cast<unsigned short*>(nullptr), static_cast<int*>(nullptr),
                      static_cast<const int*>(nullptr), static_cast<float*>(nullptr), static_cast<float*>(nullptr), 0, static_cast<float*>(nullptr),
                      static_cast<int*>(nullptr), static_cast<unsigned short*>(nullptr), static_cast<f32x4*>(nullptr),
-                     static_cast<const float*>(nullptr), static_cast<const float*>(nullptr), SdfDev{});
+                     static_cast<const float*>(nullptr), static_cast<const float*>(nullptr), SdfDev{},
+                     static_cast<const SdfSceneDev*>(nullptr), static_cast<const int*>(nullptr), 0);
   EGX_HIP_CHECK(hipGetLastError());
   return EGX_OK;
 }
 
-extern "C" int egx_lbs_forward(const egx_body_model* m, const float* xb, const float* betas, int B, int fpa,
-                               float* out_verts, float* out_joints, float* out_markers, const egx_sdf_grid* sdf,
-                               const float* R0, const float* T0, int32_t* out_pene_count, void* workspace,
-                               size_t workspace_bytes, void* stream_) {
+// ------------------------------------------------------------------------------------------------
+// SDF scene sets: the per-scene records of egx_lbs_forward_scenes, made once
+// ------------------------------------------------------------------------------------------------
+struct egx_sdf_scene_set {
+  int S = 0;
+  egx_sdf_grid dims{};          // scene 0's descriptor: the grid dimensions every scene of the set shares
+  SdfSceneDev* table = nullptr; // device [S]
+};
+
+extern "C" int egx_sdf_scene_set_create(const egx_sdf_grid* scenes, int num_scenes, egx_sdf_scene_set** out) {
+  EGX_REQUIRE(scenes && out, "null argument");
+  EGX_REQUIRE(num_scenes >= 1 && num_scenes < (1 << 15), "a scene set holds 1 .. 32767 scenes");   // the fused kernels queue the index in 15 bits
+  std::vector<SdfSceneDev> rec((size_t)num_scenes);
+  const egx_sdf_grid& s0 = scenes[0];
+  // every check comes before the first device access (the slope reads below): a rejected set touches no pointer it was given
+  for (int i = 0; i < num_scenes; ++i) {
+    const egx_sdf_grid& g = scenes[i];
+    if (g.d0 != s0.d0 || g.d1 != s0.d1 || g.d2 != s0.d2) {
+      egx_set_error("egx_sdf_scene_set_create: scene " + std::to_string(i) + " has grid dimensions " + std::to_string(g.d0) + "x" +
+                    std::to_string(g.d1) + "x" + std::to_string(g.d2) + ", scene 0 " + std::to_string(s0.d0) + "x" +
+                    std::to_string(s0.d1) + "x" + std::to_string(s0.d2) + ": the scenes of a set share their dimensions");
+      return EGX_ERR_ARG;
+    }
+  }
+  for (int i = 0; i < num_scenes; ++i) {
+    const egx_sdf_grid& g = scenes[i];
+    if (!g.grid || !g.coarse_minmax || !egx_sdf_dims_ok(g.d0, g.d1, g.d2) || g.d0 <= 0 || g.d1 <= 0) {
+      egx_set_error("egx_sdf_scene_set_create: scene " + std::to_string(i) +
+                    " needs a grid with d2 >= 2 and fewer than 2^32 samples and its bracket table (egx_sdf_build_coarse)");
+      return EGX_ERR_ARG;
+    }
+  }
+  // the slopes (aux[3] of each table) were written by egx_sdf_build_coarse on some stream: wait for it, then read them once
+  EGX_HIP_CHECK(hipDeviceSynchronize());
+  const int c0 = egx_ceil_div(s0.d0, 4), c1 = egx_ceil_div(s0.d1, 4), c2 = egx_ceil_div(s0.d2, 4);
+  for (int i = 0; i < num_scenes; ++i) {
+    const egx_sdf_grid& g = scenes[i];
+    SdfSceneDev& r = rec[(size_t)i];
+    r.grid = g.grid;
+    r.coarse = static_cast<const float2*>(g.coarse_minmax);
+    r.cx = g.center[0]; r.cy = g.center[1]; r.cz = g.center[2]; r.scale = g.scale;
+    EGX_HIP_CHECK(hipMemcpy(&r.slope, static_cast<const char*>(g.coarse_minmax) + egx_sdf_aux_offset(c0, c1, c2) + 3 * sizeof(float),
+                            sizeof(float), hipMemcpyDeviceToHost));
+    r.pad = 0.f;
+  }
+  auto* set = new egx_sdf_scene_set();
+  set->S = num_scenes;
+  set->dims = s0;
+  if (int rc = upload(&set->table, rec)) { (void)hipFree(set->table); delete set; return rc; }
+  *out = set;
+  return EGX_OK;
+}
+
+extern "C" void egx_sdf_scene_set_destroy(egx_sdf_scene_set* set) {
+  if (!set) return;
+  (void)hipFree(set->table);
+  delete set;
+}
+
+extern "C" int egx_sdf_scene_set_size(const egx_sdf_scene_set* set) { return set ? set->S : 0; }
+
+// Set of one through the one-scene kernels: bodies whose agent names no scene of the set get the count -1 (after the count was formed).
+__global__ __launch_bounds__(256) void egx_lbs_scene_mark_kernel(const int* __restrict__ agent_scene, int n_scenes, int B, int fpa,
+                                                                 int* __restrict__ pene) {
+  const int b = blockIdx.x * 256 + threadIdx.x;
+  if (b >= B) return;
+  const int v = agent_scene[b / fpa];
+  if (v < 0 || v >= n_scenes) pene[b] = -1;
+}
+
+// The launcher of egx_lbs_forward (one scene: `sdf`, set = null) and egx_lbs_forward_scenes (`set` with agent_scene; sdf = the set's
+// shared dimensions).  Set launches take the MS instantiations of the pose, fused and fix-up kernels and are never culled.
+static int lbs_forward_launch(const egx_body_model* m, const float* xb, const float* betas, int B, int fpa,
+                              float* out_verts, float* out_joints, float* out_markers, const egx_sdf_grid* sdf,
+                              const egx_sdf_scene_set* set, const int32_t* agent_scene,
+                              const float* R0, const float* T0, int32_t* out_pene_count, void* workspace,
+                              size_t workspace_bytes, void* stream_) {
   EGX_REQUIRE(m && xb && betas, "null model/xb/betas");
   EGX_REQUIRE(B > 0 && fpa > 0, "num_bodies and frames_per_agent must be positive");
   EGX_REQUIRE(!sdf || (sdf->grid && out_pene_count && sdf->d0 > 0 && sdf->d1 > 0 && sdf->d2 > 0), "sdf needs grid + out_pene_count");
@@ -2782,7 +2932,8 @@ extern "C" int egx_lbs_forward(const egx_body_model* m, const float* xb, const f
   const bool split3 = mode >= 1 && !out_verts;
   const int nbg_all = egx_ceil_div(B, BODY_PAD);
   // free-space culling: SDF counts on the split kernels, a convex-weight model, whole agents, enough items to deal to 8 XCDs
-  const bool cull = split3 && sdf && m->cull_ok && culling_on() && B % fpa == 0 && m->n_sdf_tiles > m->n_pick_tiles &&
+  const bool ms = set != nullptr;
+  const bool cull = !ms && split3 && sdf && m->cull_ok && culling_on() && B % fpa == 0 && m->n_sdf_tiles > m->n_pick_tiles &&
                     (size_t)m->n_sdf_tiles * nbg_all >= 8;
   SdfDev sd;
   std::memset(&sd, 0, sizeof(sd));
@@ -2808,12 +2959,14 @@ extern "C" int egx_lbs_forward(const egx_body_model* m, const float* xb, const f
     hipLaunchKernelGGL(egx_lbs_agent_order_kernel, dim3(1), dim3(256), (size_t)A * sizeof(int), stream, xb, R0, T0, sd, mips, A, fpa,
                        pel[0], pel[1], pel[2], order, flags, m->n_sdf_tiles * nbg_all, counts);
   }
-  hipLaunchKernelGGL(egx_pose_chain_kernel, dim3(egx_ceil_div(B, 4)), dim3(256), 0, stream, m->pc, xb, betas, B, fpa,
+  const SdfSceneDev* scene_tab = ms ? set->table : nullptr;
+  const int n_scenes = ms ? set->S : 0;
+  hipLaunchKernelGGL(ms ? egx_pose_chain_kernel<true> : egx_pose_chain_kernel<false>, dim3(egx_ceil_div(B, 4)), dim3(256), 0, stream, m->pc, xb, betas, B, fpa,
                      split3 ? nullptr : feat, split3 ? reinterpret_cast<unsigned short*>(feat) : nullptr, A4, out_joints,
                      EGX_NUM_JOINTS_OUT, (split3 && mode >= 2) ? 1.f : 0.f, (split3 && mode == 3) ? feat4 : nullptr, sdf ? out_pene_count : nullptr,
                      static_cast<const int*>(order), fvec, jpos, (int)wl.Bp, fix ? reinterpret_cast<float*>(ws + wl.fix_e) : nullptr,
                      reinterpret_cast<int*>(ws + wl.fix_stats), fix ? reinterpret_cast<unsigned short*>(ws + wl.skinB) : nullptr,
-                     reinterpret_cast<f32x4*>(ws + wl.cinit), R0, T0, sd);
+                     reinterpret_cast<f32x4*>(ws + wl.cinit), R0, T0, sd, scene_tab, static_cast<const int*>(agent_scene), n_scenes);
   if (cull) {
     const int n_np = m->n_sdf_tiles - m->n_pick_tiles;
     hipLaunchKernelGGL(egx_lbs_cull_kernel, dim3(nbg_all, egx_ceil_div(n_np, CULL_TILES_PER_BLOCK)), dim3(256), 0, stream, m->sdf_tiles,
@@ -2857,7 +3010,8 @@ extern "C" int egx_lbs_forward(const egx_body_model* m, const float* xb, const f
     p.fixq = reinterpret_cast<int2*>(ws + wl.fixq); p.fixq_cap = g_fixq_cap.load() > 0 ? g_fixq_cap.load() : LBS_FIXQ_CAP;
     p.dirs_rm = m->dirs_rm; p.pc = m->pc; p.betas = betas;
     p.skinB = reinterpret_cast<const bf16x8*>(ws + wl.skinB); p.cinit = reinterpret_cast<const f32x4*>(ws + wl.cinit);
-    p.sdf_aux = sdf ? reinterpret_cast<const float*>(static_cast<const char*>(sdf->coarse_minmax) + egx_sdf_aux_offset(sd.c0, sd.c1, sd.c2)) : nullptr;
+    p.sdf_aux = (sdf && !ms) ? reinterpret_cast<const float*>(static_cast<const char*>(sdf->coarse_minmax) + egx_sdf_aux_offset(sd.c0, sd.c1, sd.c2)) : nullptr;
+    p.scenes = scene_tab; p.agent_scene = agent_scene; p.n_scenes = n_scenes;
     // one persistent workgroup per CU; per-device launch facts (CU count, raised dynamic-LDS caps) are set up once per device
     constexpr size_t lds_meta = (size_t)8 * LBS_META_BYTES, lds_verts = (size_t)8 * (LBS_META_BYTES + LBS_VERT_BYTES),
                      lds_sdf = (size_t)8 * (LBS_META_BYTES + LBS_QCAP * 16);
@@ -2884,6 +3038,11 @@ extern "C" int egx_lbs_forward(const egx_body_model* m, const float* xb, const f
         EGX_HIP_CHECK(raise(reinterpret_cast<const void*>(&egx_lbs_fused3_kernel<4, false>), lds3a));
         EGX_HIP_CHECK(raise(reinterpret_cast<const void*>(&egx_lbs_fused3_kernel<4, true, 1>), lbs3_lds_bytes<1>()));
         EGX_HIP_CHECK(raise(reinterpret_cast<const void*>(&egx_lbs_fused3_kernel<4, false, 1>), lbs3_lds_bytes<1>()));
+        EGX_HIP_CHECK(raise(reinterpret_cast<const void*>(&egx_lbs_fused_kernel<true, true, true>), lds_verts));
+        EGX_HIP_CHECK(raise(reinterpret_cast<const void*>(&egx_lbs_fused_kernel<false, true, true>), lds_sdf));
+        EGX_HIP_CHECK(raise(reinterpret_cast<const void*>(&egx_lbs_fused3_kernel<3, true, LBS_NB, true>), lds3a));
+        EGX_HIP_CHECK(raise(reinterpret_cast<const void*>(&egx_lbs_fused3_kernel<2, true, LBS_NB, true>), lds3a));
+        EGX_HIP_CHECK(raise(reinterpret_cast<const void*>(&egx_lbs_fused3_kernel<4, true, LBS_NB, true>), lds3a));
         di.num_cu = prop.multiProcessorCount;
       }
     }
@@ -2917,7 +3076,9 @@ extern "C" int egx_lbs_forward(const egx_body_model* m, const float* xb, const f
       // item repeats the bases traffic and the barriers), profiles/r05_lbs_mixed.md section 5.  EGX_LBS_WAVE_TILE=1 | 2 forces one.
       const int forced_tile = wave_tile();
       const bool small_tile = forced_tile == 1 || (forced_tile != 2 && p.nbg <= 20);
-      if (mode == 3 && small_tile && !p.items) {
+      // set launches of two or more scenes always take the 32 x 64 tile: the small tile's epilogue has no registers for the body's
+      // scene (its one-scene form already spills 5 VGPRs; a set form spilled 4), so it has no set instantiation
+      if (mode == 3 && small_tile && !p.items && !ms) {
         LbsParams q = p;
         q.nbg = egx_ceil_div(B, 128);
         q.bg_block = 2 * p.bg_block;
@@ -2927,26 +3088,33 @@ extern "C" int egx_lbs_forward(const egx_body_model* m, const float* xb, const f
         if (sdf) hipLaunchKernelGGL((egx_lbs_fused3_kernel<4, true, 1>), dim3(g1), dim3(256), lbs3_lds_bytes<1>(), stream, q);
         else hipLaunchKernelGGL((egx_lbs_fused3_kernel<4, false, 1>), dim3(g1), dim3(256), lbs3_lds_bytes<1>(), stream, q);
       } else if (mode == 3) {
-        if (sdf) hipLaunchKernelGGL((egx_lbs_fused3_kernel<4, true>), dim3(grid3), dim3(256), lds3, stream, p);
+        if (ms) hipLaunchKernelGGL((egx_lbs_fused3_kernel<4, true, LBS_NB, true>), dim3(grid3), dim3(256), lds3, stream, p);
+        else if (sdf) hipLaunchKernelGGL((egx_lbs_fused3_kernel<4, true>), dim3(grid3), dim3(256), lds3, stream, p);
         else hipLaunchKernelGGL((egx_lbs_fused3_kernel<4, false>), dim3(grid3), dim3(256), lds3, stream, p);
       } else if (mode == 2) {
-        if (sdf) hipLaunchKernelGGL((egx_lbs_fused3_kernel<2, true>), dim3(grid3), dim3(256), lds3, stream, p);
+        if (ms) hipLaunchKernelGGL((egx_lbs_fused3_kernel<2, true, LBS_NB, true>), dim3(grid3), dim3(256), lds3, stream, p);
+        else if (sdf) hipLaunchKernelGGL((egx_lbs_fused3_kernel<2, true>), dim3(grid3), dim3(256), lds3, stream, p);
         else hipLaunchKernelGGL((egx_lbs_fused3_kernel<2, false>), dim3(grid3), dim3(256), lds3, stream, p);
       } else {
-        if (sdf) hipLaunchKernelGGL((egx_lbs_fused3_kernel<3, true>), dim3(grid3), dim3(256), lds3, stream, p);
+        if (ms) hipLaunchKernelGGL((egx_lbs_fused3_kernel<3, true, LBS_NB, true>), dim3(grid3), dim3(256), lds3, stream, p);
+        else if (sdf) hipLaunchKernelGGL((egx_lbs_fused3_kernel<3, true>), dim3(grid3), dim3(256), lds3, stream, p);
         else hipLaunchKernelGGL((egx_lbs_fused3_kernel<3, false>), dim3(grid3), dim3(256), lds3, stream, p);
       }
-    } else if (out_verts && sdf)
+    } else if (out_verts && ms)
+      hipLaunchKernelGGL((egx_lbs_fused_kernel<true, true, true>), dim3(grid), dim3(LBS_THREADS), lds, stream, p);
+    else if (out_verts && sdf)
       hipLaunchKernelGGL((egx_lbs_fused_kernel<true, true>), dim3(grid), dim3(LBS_THREADS), lds, stream, p);
     else if (out_verts)
       hipLaunchKernelGGL((egx_lbs_fused_kernel<true, false>), dim3(grid), dim3(LBS_THREADS), lds, stream, p);
+    else if (ms)
+      hipLaunchKernelGGL((egx_lbs_fused_kernel<false, true, true>), dim3(grid), dim3(LBS_THREADS), lds, stream, p);
     else if (sdf)
       hipLaunchKernelGGL((egx_lbs_fused_kernel<false, true>), dim3(grid), dim3(LBS_THREADS), lds, stream, p);
     else
       hipLaunchKernelGGL((egx_lbs_fused_kernel<false, false>), dim3(grid), dim3(LBS_THREADS), lds, stream, p);
     // mixed blend with counts: the vertices the fused kernel queued for the fp32 re-evaluation (inside the profiled interval: it is
     // part of what the mode costs)
-    if (fix) hipLaunchKernelGGL(egx_lbs_fix_kernel, dim3(LBS_FIX_BLOCKS), dim3(256), 0, stream, p);
+    if (fix) hipLaunchKernelGGL(ms ? egx_lbs_fix_kernel<true> : egx_lbs_fix_kernel<false>, dim3(LBS_FIX_BLOCKS), dim3(256), 0, stream, p);
     if (ev1) EGX_HIP_CHECK(hipEventRecord(ev1, stream));
   }
   if (need_picks)
@@ -2954,4 +3122,32 @@ extern "C" int egx_lbs_forward(const egx_body_model* m, const float* xb, const f
                        m->extra_slot, m->lmk_slot, m->lmk_bary, out_joints, out_markers);
   EGX_HIP_CHECK(hipGetLastError());
   return EGX_OK;
+}
+
+extern "C" int egx_lbs_forward(const egx_body_model* m, const float* xb, const float* betas, int B, int fpa,
+                               float* out_verts, float* out_joints, float* out_markers, const egx_sdf_grid* sdf,
+                               const float* R0, const float* T0, int32_t* out_pene_count, void* workspace,
+                               size_t workspace_bytes, void* stream) {
+  return lbs_forward_launch(m, xb, betas, B, fpa, out_verts, out_joints, out_markers, sdf, nullptr, nullptr, R0, T0, out_pene_count,
+                            workspace, workspace_bytes, stream);
+}
+
+extern "C" int egx_lbs_forward_scenes(const egx_body_model* m, const float* xb, const float* betas, int B, int fpa,
+                                      float* out_verts, float* out_joints, float* out_markers, const egx_sdf_scene_set* scenes,
+                                      const int32_t* agent_scene, const float* R0, const float* T0, int32_t* out_pene_count,
+                                      void* workspace, size_t workspace_bytes, void* stream) {
+  EGX_REQUIRE(scenes && agent_scene && out_pene_count, "a scene-set call needs the set, agent_scene and out_pene_count");
+  if (scenes->S == 1) {
+    // a set of one runs the one-scene kernels (the general ones cost +11 % at 10 240 bodies, profiles/scene_set.md) and may be culled
+    // like a one-scene call; the bodies of agents whose index is not 0 then get their -1 behind the launch
+    if (int rc = lbs_forward_launch(m, xb, betas, B, fpa, out_verts, out_joints, out_markers, &scenes->dims, nullptr, nullptr, R0, T0,
+                                    out_pene_count, workspace, workspace_bytes, stream))
+      return rc;
+    hipLaunchKernelGGL(egx_lbs_scene_mark_kernel, dim3(egx_ceil_div(B, 256)), dim3(256), 0, static_cast<hipStream_t>(stream), agent_scene,
+                       1, B, fpa, out_pene_count);
+    EGX_HIP_CHECK(hipGetLastError());
+    return EGX_OK;
+  }
+  return lbs_forward_launch(m, xb, betas, B, fpa, out_verts, out_joints, out_markers, &scenes->dims, scenes, agent_scene, R0, T0,
+                            out_pene_count, workspace, workspace_bytes, stream);
 }

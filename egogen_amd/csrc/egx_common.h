@@ -56,6 +56,23 @@ struct SdfDev {
   int c0, c1, c2;
 };
 
+// One scene of an SDF scene set (egx_sdf_scene_set, device table of 40-byte records): what the LBS count reads per body.  Every
+// scene of a set has the grid dimensions of the launch's SdfDev; only the pointers, the map to voxels and the slope differ.
+struct SdfSceneDev {
+  const float* grid;
+  const float2* coarse;   // bracket table (egx_sdf_build_coarse)
+  float cx, cy, cz, scale;
+  float slope;            // aux[3] of the table: steepest slope of the interpolated field (fix-up band of the mixed blend)
+  float pad;
+};
+static_assert(sizeof(SdfSceneDev) == 40, "scene record");
+__host__ __device__ inline SdfDev egx_sdf_scene(const SdfDev& dims, const SdfSceneDev& e) {
+  SdfDev s = dims;
+  s.grid = e.grid; s.coarse = e.coarse;
+  s.cx = e.cx; s.cy = e.cy; s.cz = e.cz; s.scale = e.scale;
+  return s;
+}
+
 // Free-space pyramid behind the bracket table (same buffer, after the float2 entries, 256-byte aligned): level l = 1..4 holds,
 // per block of 2^l x 2^l x 2^l PADDED bracket cells, the maximum of their `max` entries.  A box of padded cells whose pyramid
 // entries are all < 0 contains only points whose interpolated value is < 0 (convexity of the interpolation), i.e. free space

@@ -9,7 +9,7 @@ bodies/scenes").
 from __future__ import annotations
 
 import os
-from typing import Dict, Optional
+from typing import Dict, List, Optional
 
 import numpy as np
 import torch
@@ -231,10 +231,47 @@ def load_scene_file(path: str) -> dict:
                                                "pairs": d["pairs"]}])
 
 
+def scene_entries(spec: str) -> List[str]:
+    """The entries of a `--scene` value: comma-separated; an entry that is a directory stands for its `*.npz` files, sorted by
+    name.  One entry without a comma is returned as it is."""
+    out = []
+    for e in [x.strip() for x in spec.split(",")]:
+        if not e:
+            raise ValueError(f"empty entry in the scene list {spec!r}")
+        if os.path.isdir(e):
+            files = sorted(f for f in os.listdir(e) if f.endswith(".npz"))
+            if not files:
+                raise ValueError(f"scene directory {e!r} holds no .npz scene")
+            out += [os.path.join(e, f) for f in files]
+        else:
+            out.append(e)
+    return out
+
+
 def build_scene(kind: str, sdf_res: int = 256, seed: int = 0, data_dir: str = "data"):
     """kind: 'room0' (Replica room0 polygon + pairs, SDF from data/room0_sdf.pkl if present else a synthetic room0-shaped
     grid), 'single_box' (BASELINE config 2), 'box' (random_box_obstacle_new stand-in), or the path of a `.npz` scene
-    prepared with `egogen_amd.scene_gen.save_scene` (new scenes)."""
+    prepared with `egogen_amd.scene_gen.save_scene` (new scenes) - or a LIST of SDF scenes: comma-separated
+    entries of those kinds (a directory = its `*.npz` files, sorted by name), all SDF scenes of the same grid dimensions, for one
+    env over the set (`VecCrowdEnv(sdf_scenes=...)`).  A single entry behaves exactly as before."""
+    entries = scene_entries(kind) if ("," in kind or os.path.isdir(kind)) else [kind]
+    if len(entries) > 1 or entries[0] != kind:
+        scenes, dims = [], None
+        for e in entries:
+            sc = build_scene(e, sdf_res=sdf_res, seed=seed, data_dir=data_dir)
+            if sc["scene_kind"] != "sdf":
+                raise ValueError(f"scene list entry {e!r} is a {sc['scene_kind']} scene: a scene list holds SDF scenes only")
+            d = tuple(int(x) for x in sc["sdf_dict"]["sdf"].squeeze().shape)
+            if dims is None:
+                dims, first = d, e
+            elif d != dims:
+                raise ValueError(f"scene list entry {e!r} has an SDF grid of {d}, entry {first!r} {dims}: the scenes of a set "
+                                 "share their grid dimensions")
+            scenes.append(dict(sdf_dict=sc["sdf_dict"], rings=sc["rings"], pairs=sc["pairs"],
+                               name=os.path.splitext(os.path.basename(e))[0]))
+        if len(scenes) == 1:
+            return dict(scene_kind="sdf", sdf_dict=scenes[0]["sdf_dict"], rings=scenes[0]["rings"], pairs=scenes[0]["pairs"])
+        return dict(scene_kind="sdf", sdf_scenes=scenes)
     if kind.endswith(".npz"):
         return load_scene_file(kind)
     if kind == "box":

@@ -90,11 +90,16 @@ class Collector:
         fr = env.prev_frame.cpu()
         pel = env.joints.reshape(self.A, 20, -1, 3)[:, :, 0].cpu()
         tm = term.cpu().numpy()
+        names = getattr(env, "scene_names", None)
+        multi = names is not None and len(names) > 1
+        sidx = env.scene_idx.cpu().numpy() if multi else None
         for a in range(self.A):
             mp = [mb[a:a + 1], pp[a:a + 1], env.betas[a].cpu(), getattr(env, "gender", "male"), fr[a, :9].reshape(3, 3), fr[a, 9:].reshape(1, 3), pel[a:a + 1], "2-frame"]
             self._episodes[a].append(mp)
             if tm[a]:
                 scene = {"wpath": self._wpath_before[a], "navmesh_path": "synthetic"}
+                if multi:   # a set of scenes: which one the episode ran in
+                    scene["scene_path"] = names[int(sidx[a])]
                 save_rollout_results(scene, self._episodes[a], self.rollout_dir)
                 self._episodes[a] = []
 
@@ -174,7 +179,26 @@ class Collector:
             if bool((got.sum() >= min(n_episode, self.A)).item()):
                 break
         n = max(float(got.sum().item()), 1.0)
-        return {"rew": float(first_ret.sum().item()) / n, "len": float(first_len.sum().item()) / n, "n/ep": n}
+        res = {"rew": float(first_ret.sum().item()) / n, "len": float(first_len.sum().item()) / n, "n/ep": n}
+        names = getattr(self.env, "scene_names", None)
+        if names is not None and len(names) > 1:
+            # a set of scenes: the same means per scene (the agents of each scene's block)
+            sc = self.env.scene_idx.long()
+            per = {}
+            for s, name in enumerate(names):
+                m = (sc == s).to(got.dtype) * got
+                k = max(float(m.sum().item()), 1.0)
+                per[name] = {"rew": float((first_ret * m).sum().item()) / k, "len": float((first_len * m).sum().item()) / k}
+            res["per_scene"] = per
+        return res
+
+
+def _test_scalars(result: Dict) -> Dict[str, float]:
+    """test/ scalars of one evaluation: reward and length, and with a set of scenes the same per scene (reward_<scene>, ...)."""
+    out = {"reward": result["rew"], "length": result["len"]}
+    for name, r in result.get("per_scene", {}).items():
+        out[f"reward_{name}"], out[f"length_{name}"] = r["rew"], r["len"]
+    return out
 
 
 class ScalarLogger:
@@ -359,7 +383,7 @@ def onpolicy_trainer(policy: GAMMAPPOPolicy, train_collector: Collector, test_co
         r0 = test_collector.collect_episodes(episode_per_test)
         best_reward, best_epoch = r0["rew"], 0
         if logger is not None and rank == 0:
-            logger.write("test", 0, {"reward": r0["rew"], "length": r0["len"]})
+            logger.write("test", 0, _test_scalars(r0))
         if verbose and rank == 0:
             print(f"Epoch #0: test_reward: {r0['rew']:.6f}", flush=True)
     if save_best_fn is not None and rank == 0:
@@ -392,7 +416,7 @@ def onpolicy_trainer(policy: GAMMAPPOPolicy, train_collector: Collector, test_co
             policy.eval()
             result = test_collector.collect_episodes(episode_per_test)
             if logger is not None and rank == 0:
-                logger.write("test", env_step, {"reward": result["rew"], "length": result["len"]})
+                logger.write("test", env_step, _test_scalars(result))
             if result["rew"] > best_reward:
                 best_reward, best_epoch = result["rew"], epoch
                 if save_best_fn is not None and rank == 0:

@@ -180,6 +180,37 @@ int egx_lbs_forward(const egx_body_model* m, const float* xb, const float* betas
                     void* workspace, size_t workspace_bytes, void* stream);
 
 /*
+ * SDF scene sets - one penetration-count launch over bodies in DIFFERENT scenes (no reference counterpart: crowd_env_2f.py trains
+ * in one scene per process).  egx_sdf_scene_set_create copies, once, a device table of S records {grid, bracket table, center,
+ * scale, steepest slope} from S descriptors, each with its bracket table (egx_sdf_build_coarse) and all with the same d0, d1, d2 -
+ * otherwise it fails and names the scene.  It synchronises the device (the slopes are read from the tables); after it nothing is
+ * allocated or copied per call, so egx_lbs_forward_scenes can be captured in a graph.  The set points at the callers' grids and
+ * tables, which must outlive it; destroy frees the table only.
+ */
+typedef struct egx_sdf_scene_set egx_sdf_scene_set; /* opaque */
+int egx_sdf_scene_set_create(const egx_sdf_grid* scenes, int num_scenes, egx_sdf_scene_set** out);
+void egx_sdf_scene_set_destroy(egx_sdf_scene_set* set);
+int egx_sdf_scene_set_size(const egx_sdf_scene_set* set);
+
+/*
+ * egx_lbs_forward_scenes - egx_lbs_forward with a scene per agent: body b is counted in scene agent_scene[b / frames_per_agent]
+ * of `scenes` (agent_scene: device int32 [A]).  Every read of scene data - the canonical-frame -> SDF-cell map, the bracket
+ * lookups, trilinear gathers and border clamp of the count, the fix-up band of blend mode 3 (that scene's slope) and the fp32
+ * re-evaluation - uses the body's own scene, so each body's count, joints and markers are bit-identical to an egx_lbs_forward call
+ * with that scene's descriptor on the same bodies.  All blend modes, with and without out_verts.  out_pene_count is required.
+ *   An agent_scene value < 0 or >= S reads nothing outside the set: that agent's bodies get out_pene_count = -1 (their joints,
+ *   markers and vertices are computed as usual).
+ *   A set of one runs the one-scene kernels of egx_lbs_forward (and, after them, sets the -1 of bad indices); sets of two or more
+ *   scenes run kernels that read the body's scene per body, in blend mode 3 always with the 32 x 64 wave tile
+ *   (egx_lbs_set_wave_tile does not apply to them).  Free-space culling (EGX_LBS_CULL) is one-scene only: calls with a set
+ *   of two or more scenes run unculled (counts are identical either way).
+ */
+int egx_lbs_forward_scenes(const egx_body_model* m, const float* xb, const float* betas, int num_bodies, int frames_per_agent,
+                           float* out_verts, float* out_joints, float* out_markers, const egx_sdf_scene_set* scenes,
+                           const int32_t* agent_scene, const float* R0, const float* T0, int32_t* out_pene_count,
+                           void* workspace, size_t workspace_bytes, void* stream);
+
+/*
  * egx_lbs_joints - the 55 kinematic-tree joints of B bodies without the vertex pass: out_joints55 [B,55,3] =
  * bm(**bparam).joints[:, :55].  This is all SMPLXParser.get_new_coordinate (models/baseops.py:485: joints 0,1,2) and
  * calc_calibrate_offset (:529: joint 0 at zero global_orient / transl) take from their full SMPL-X evaluation.
