@@ -76,6 +76,11 @@ def get_args(argv=None, extra=(), defaults=None):
                         "single_box may be entries) to train ONE policy across all of them: agents are split into contiguous "
                         "blocks, one per scene, in the train and test envs alike")
     p.add_argument("--sdf-res", type=int, default=256)
+    p.add_argument("--scene-resample-every", type=int, default=0, metavar="N",
+                   help="with generated scenes in --scene (boxes:SxK = S rooms of K random boxes each, built on the GPU; "
+                        "scan.npz+boxes:SxK = S variants of a prepared scene): every N epochs the training env's generated scenes "
+                        "are replaced by new layouts (generation g = (epoch - 1) / N, a function of --seed, g and the scene number: "
+                        "the same on every rank); the test env keeps generation 0.  0 = never")
     p.add_argument("--save-rollout", type=int, default=None, help="write log/eval_results/motion_*.pkl (default: only with --watch)")
     p.add_argument("--num-verts", type=int, default=synth.NUM_VERTS, help="reduced synthetic body (tests)")
     p.add_argument("--policy-dtype", type=str, default=None, choices=["fp32", "bf16x2", "bf16"],
@@ -103,6 +108,12 @@ def _apply_policy_dtype(args, default="bf16x2"):
 
 
 def main(args, scene_kind=SCENE_DEFAULT, cfg_name=CFG_NAME, ckpt_with_optim=True):
+    resample = int(getattr(args, "scene_resample_every", 0) or 0)
+    if resample < 0:
+        raise SystemExit(f"--scene-resample-every {resample}: N >= 0")
+    if resample and not sw.scene_spec_generates(args.scene or scene_kind):
+        raise SystemExit(f"--scene-resample-every {resample}: --scene {args.scene or scene_kind!r} generates nothing; it needs "
+                         "generated entries (boxes:SxK, file.npz+boxes:SxK)")
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -159,13 +170,26 @@ def main(args, scene_kind=SCENE_DEFAULT, cfg_name=CFG_NAME, ckpt_with_optim=True
     if not args.watch:
         train_env = sw.build_env(n_train, scene, body, prior, vposer, finetuning=args.finetune, seed=args.seed + rank, cfg=env_cfg)
         train_collector = Collector(policy, train_env)
+
+        def epoch_begin_fn(epoch):
+            # every rank derives the generation from the epoch alone: the same layouts everywhere, no collective
+            if resample and epoch > 1 and (epoch - 1) % resample == 0:
+                train_env.replace_sdf_scenes(scene["scene_factory"]((epoch - 1) // resample))
+                train_collector.reset()
+
         result = onpolicy_trainer(policy, train_collector, test_collector, args.epoch, args.step_per_epoch,
                                   args.repeat_per_collect, args.test_num, args.batch_size,
                                   step_per_collect=args.step_per_collect, save_best_fn=save_best_fn, logger=logger,
-                                  save_checkpoint_fn=save_checkpoint_fn, save_interval=args.save_interval)
+                                  save_checkpoint_fn=save_checkpoint_fn, save_interval=args.save_interval,
+                                  epoch_begin_fn=epoch_begin_fn if resample else None)
         writer.flush()               # every checkpoint of the run is on disk from here on
         if rank == 0:
             pprint.pprint(result)
+            if "scene_factory" in scene:   # which layouts the run ended on (train) and was evaluated on (test)
+                import json
+                lay = lambda env: [None if b is None else np.round(np.asarray(b, np.float64), 6).tolist() for b in env.scene_boxes]
+                print("Scene layouts: " + json.dumps({"train_generation": train_env.scene_generation, "train_boxes": lay(train_env),
+                                                      "test_generation": test_env.scene_generation, "test_boxes": lay(test_env)}))
 
     # Let's watch its performance!  (main_ppo.py:238-243)
     policy.eval()

@@ -141,7 +141,9 @@ class VecCrowdEnv:
         # ---- scenes ----
         self.sdf = None
         self.scene_names = None
+        self.scene_boxes = None
         self.R = 1   # reset rounds (box scenes: set below)
+        self.scene_generation = 0   # swaps of the scene set so far (replace_sdf_scenes)
         if scene_kind == "sdf":
             if sdf_scenes is None:
                 if sdf_dict is None or rings is None or pairs is None:
@@ -152,6 +154,7 @@ class VecCrowdEnv:
             S = len(sdf_scenes)
             self.scene_idx.copy_(torch.from_numpy(block_scene_assignment(A, S)))
             self.scene_names = [str(d.get("name", f"scene{s}")) for s, d in enumerate(sdf_scenes)]
+            self.scene_boxes = [d.get("boxes") for d in sdf_scenes]   # generated scenes: their box layouts (scene_gen)
             self.sdf_scenes = [d["sdf_dict"] if isinstance(d["sdf_dict"], SdfScene) else SdfScene(d["sdf_dict"], device=self.dev)
                                for d in sdf_scenes]
             # what the LBS call counts in: the scene itself (egx_lbs_forward), or the set with scene_idx as the agents' scenes
@@ -331,16 +334,57 @@ class VecCrowdEnv:
         start/target pair, so every pair is evaluated once here (sampler kernel -> SMPL-X + SDF kernel) and reset
         then draws uniformly among the accepted pairs - the same distribution as rejection sampling.  With a set of scenes, each
         scene's pairs are checked in that scene; an agent draws from its own scene's accepted pairs."""
-        masks = [self._prevalidate_scene(self.pairs_scene[s], self.sdf_scenes[s], s) for s in range(len(self.sdf_scenes))]
+        self.__dict__.update(self._validated_pairs(self.pairs_scene, self.sdf_scenes, self.scene_names, self._sc))
+
+    def _validated_pairs(self, pairs_scene, sdf_scenes, names, sc) -> dict:
+        """The pair tables of a scene set ({pairs_all, pair_valid_mask, valid_pairs, _vp_n, _vp_off}); RuntimeError when a scene
+        has no pair that passes the start check.  Changes nothing on the env."""
+        masks = [self._prevalidate_scene(pairs_scene[s], sdf_scenes[s], s, sc) for s in range(len(sdf_scenes))]
         for s, m in enumerate(masks):
             if not bool(m.any()):
-                raise RuntimeError(f"no start/target pair of scene {self.scene_names[s]!r} passes the SDF start check")
-        self.pair_valid_mask = masks[0] if len(masks) == 1 else torch.cat(masks)
-        self.valid_pairs = self.pairs_all[self.pair_valid_mask].contiguous()
+                raise RuntimeError(f"no start/target pair of scene {names[s]!r} passes the SDF start check")
+        pairs_all = pairs_scene[0] if len(masks) == 1 else torch.cat(pairs_scene)
+        mask = masks[0] if len(masks) == 1 else torch.cat(masks)
         n = torch.tensor([int(m.sum()) for m in masks], dtype=torch.int64, device=self.dev)
-        self._vp_n, self._vp_off = n, torch.cumsum(n, 0) - n   # per scene: accepted pairs, offset into valid_pairs
+        # per scene: accepted pairs, offset into valid_pairs
+        return dict(pairs_all=pairs_all, pair_valid_mask=mask, valid_pairs=pairs_all[mask].contiguous(), _vp_n=n, _vp_off=torch.cumsum(n, 0) - n)
 
-    def _prevalidate_scene(self, pairs_all, sdf, scene, batch: int = 2048):
+    def replace_sdf_scenes(self, sdf_scenes: List[dict]):
+        """Swap the scenes of a running SDF env for others (domain randomisation over layouts): as many scenes as now, of the
+        current grid dimensions, [{sdf_dict, rings, pairs, name}, ...] like the constructor's.  Everything is built first - the
+        scenes' bracket tables, the set, the edge table, each scene's pre-validated pairs -, then swapped; if a scene has no valid
+        pair the RuntimeError of the constructor is raised and the env is untouched and usable.  After the swap the candidate
+        pool and a captured graph are dropped (both hold the old scenes), all agents are reset and `scene_generation` counts up."""
+        if self.scene_kind != "sdf":
+            raise ValueError("replace_sdf_scenes: an SDF env only")
+        sdf_scenes = list(sdf_scenes)
+        if len(sdf_scenes) != len(self.sdf_scenes):
+            raise ValueError(f"replace_sdf_scenes: {len(sdf_scenes)} scenes for an env over {len(self.sdf_scenes)} (agents keep their scene numbers)")
+        f32 = dict(dtype=torch.float32, device=self.dev)
+        new = [d["sdf_dict"] if isinstance(d["sdf_dict"], SdfScene) else SdfScene(d["sdf_dict"], device=self.dev) for d in sdf_scenes]
+        dims = tuple(self.sdf_scenes[0].grid.shape)
+        for d, sc in zip(sdf_scenes, new):
+            if tuple(sc.grid.shape) != dims:
+                raise ValueError(f"replace_sdf_scenes: scene {d.get('name')!r} has an SDF grid of {tuple(sc.grid.shape)}, the env's scenes {dims}")
+        sdf = new[0] if len(new) == 1 else SdfSceneSet(new)
+        names = [str(d.get("name", f"scene{s}")) for s, d in enumerate(sdf_scenes)]
+        edges = [synth.rings_to_edges(d["rings"]).astype(np.float32) for d in sdf_scenes]
+        edges_t = torch.tensor(np.concatenate(edges, 0), **f32).contiguous()
+        edge_off = torch.tensor(np.cumsum([0] + [len(e) for e in edges]), dtype=torch.int32, device=self.dev)
+        sc = _lib.EnvScenes.from_buffer_copy(self._sc)
+        sc.edges, sc.edge_off = edges_t.data_ptr(), edge_off.data_ptr()
+        pairs_scene = [torch.tensor(np.asarray(d["pairs"], np.float32), **f32).reshape(-1, 2, 3) for d in sdf_scenes]
+        tables = self._validated_pairs(pairs_scene, new, names, sc)     # raises before anything of the env changed
+        self._graph = None                                              # captured with the old grids' addresses
+        self._cand_pool, self._cand_pool_pos, self._cand_step = None, 0, None   # drawn from the old scenes' pairs
+        self._injected = False
+        self.sdf_scenes, self.sdf, self.scene_names, self.scene_boxes = new, sdf, names, [d.get("boxes") for d in sdf_scenes]
+        self.edges, self.edge_off, self._sc, self.pairs_scene = edges_t, edge_off, sc, pairs_scene
+        self.__dict__.update(tables)
+        self.scene_generation += 1
+        return self.reset()
+
+    def _prevalidate_scene(self, pairs_all, sdf, scene, sc=None, batch: int = 2048):
         N = pairs_all.shape[0]
         f32 = dict(dtype=torch.float32, device=self.dev)
         i32 = dict(dtype=torch.int32, device=self.dev)
@@ -354,7 +398,7 @@ class VecCrowdEnv:
             ego, od, ot = torch.zeros(n, 2, 32, **f32), torch.zeros(n, **f32), torch.zeros(n, **f32)
             cp = pairs_all[s:s + n].reshape(n, 1, 2, 3).contiguous()
             io = self._reset_io(n, 1, None, cp, None, None, None, None, ego, od, ot, None)
-            _lib.check(self.lib.egx_env_reset(C.byref(self._ec), C.byref(self._sc), C.byref(st), C.byref(io), n,
+            _lib.check(self.lib.egx_env_reset(C.byref(self._ec), C.byref(sc if sc is not None else self._sc), C.byref(st), C.byref(io), n,
                                               _lib.current_stream_ptr()), "egx_env_reset")
             betas = self.betas[:1].repeat(n, 1).contiguous()
             out = self.bm.forward(tmp["seed"].reshape(n * 2, 93), betas, 2, want_joints=False, want_markers=False,

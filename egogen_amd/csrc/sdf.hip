@@ -4,6 +4,9 @@
 // removed).
 #include "egx_common.h"
 
+#include <cmath>
+#include <cstring>
+
 #ifndef EGX_SDF_PPT
 #define EGX_SDF_PPT 4   // points per lane and trip: their 4 x PPT corner-pair gathers are in flight together
 #endif
@@ -314,6 +317,128 @@ extern "C" int egx_mesh_sdf(const float* triangles, int num_triangles, const flo
   hipLaunchKernelGGL(egx_mesh_sdf_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream_),
                      triangles, num_triangles, center_host[0], center_host[1], center_host[2], 1.f / scale, d0, d1, d2, inside_positive,
                      out_grid);
+  EGX_HIP_CHECK(hipGetLastError());
+  return EGX_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// egx_sdf_boxes: analytic room + oriented-box grids written straight into device memory (what synth.make_sdf_scene builds on
+// the host in float64 for one axis-aligned box; the layouts are the reference's random box scenes, environments.py:386-402),
+// or the boxes composed onto an existing grid (a scan).  Stored value: max(start, max_k(-d_k)), d_k the exact signed distance
+// to box k (negative inside) in the box's frame, start = the base sample or the signed distance to the room box.
+// One lane per run of four consecutive z samples: the (x, y) terms of the room and of every box are computed once per run,
+// and a run is one 16-byte load (composition) and one 16-byte store.  Grids whose rows are no multiple of four samples (or
+// whose pointers are not 16-byte aligned) take the same code with scalar accesses and a guarded tail.  A lane reads its own
+// run of the base before it writes it, so out_grid == base_grid is safe.  The boxes travel as kernel arguments (uniform
+// scalar loads): no device table, no copy, no synchronisation.
+// ---------------------------------------------------------------------------------------------------------
+namespace {
+struct BoxDev { float cx, cy, c, s, hx, hy, zc, hz; };   // centre, cos / sin of the yaw, half extents, z centre and half height
+struct BoxesArg { BoxDev room; BoxDev b[EGX_SDF_MAX_BOXES]; };
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void egx_sdf_boxes_kernel(const float* base, BoxesArg a, int nb, float cx, float cy, float cz,
+                                                           float inv_scale, int d0, int d1, int d2, int r2, float* out) {
+  const unsigned long long runs = (unsigned long long)d0 * d1 * r2;   // < 2^32 (egx_sdf_dims_ok)
+  for (unsigned long long r = (unsigned long long)blockIdx.x * 256 + threadIdx.x; r < runs; r += (unsigned long long)gridDim.x * 256) {
+    const unsigned ru = (unsigned)r;
+    const unsigned ij = ru / (unsigned)r2;
+    const int k0 = (int)(ru - ij * (unsigned)r2) * 4, j = (int)(ij % (unsigned)d1), i = (int)(ij / (unsigned)d1);
+    const size_t off = (size_t)ij * d2 + k0;
+    const float px = cx + ((2 * i + 1) / (float)d0 - 1.f) * inv_scale;
+    const float py = cy + ((2 * j + 1) / (float)d1 - 1.f) * inv_scale;
+    float pz[4], v[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) pz[u] = cz + ((2 * (k0 + u) + 1) / (float)d2 - 1.f) * inv_scale;
+    if (base) {
+      if (VEC) {
+        const float4 b4 = *reinterpret_cast<const float4*>(base + off);
+        v[0] = b4.x; v[1] = b4.y; v[2] = b4.z; v[3] = b4.w;
+      } else {
+#pragma unroll
+        for (int u = 0; u < 4; ++u) v[u] = base[off + (k0 + u < d2 ? u : 0)];
+      }
+    } else {   // signed distance to the room box (axis-aligned), negative inside
+      const float qx = fabsf(px - a.room.cx) - a.room.hx, qy = fabsf(py - a.room.cy) - a.room.hy;
+      const float ox = fmaxf(qx, 0.f), oy = fmaxf(qy, 0.f);
+      const float o2 = ox * ox + oy * oy, m = fmaxf(qx, qy);
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const float qz = fabsf(pz[u] - a.room.zc) - a.room.hz, oz = fmaxf(qz, 0.f);
+        const float s2 = o2 + oz * oz;   // > 0 outside (distance squared), else the point is inside at depth -max(q)
+        v[u] = s2 > 0.f ? __builtin_amdgcn_sqrtf(s2) : fmaxf(m, qz);
+      }
+    }
+    // max_k(-d_k) with one square root per sample: d_k = sqrt(s2_k) outside box k (s2_k > 0) and max(q) <= 0 inside or on
+    // it.  A box the sample is inside of (value >= 0) beats every box it is outside of (value < 0), and among those the
+    // square root is monotone: -sqrt(min_k s2_k).
+    float s2min[4], depth[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) { s2min[u] = 3.4e38f; depth[u] = 0.f; }
+#pragma unroll 4
+    for (int k = 0; k < nb; ++k) {
+      const BoxDev& b = a.b[k];
+      const float dx = px - b.cx, dy = py - b.cy;
+      const float qx = fabsf(b.c * dx + b.s * dy) - b.hx, qy = fabsf(b.c * dy - b.s * dx) - b.hy;   // (p - c) rotated by -yaw
+      const float ox = fmaxf(qx, 0.f), oy = fmaxf(qy, 0.f);
+      const float o2 = ox * ox + oy * oy, m = fmaxf(qx, qy);
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const float qz = fabsf(pz[u] - b.zc) - b.hz, oz = fmaxf(qz, 0.f);
+        s2min[u] = fminf(s2min[u], o2 + oz * oz);
+        depth[u] = fmaxf(depth[u], -fminf(fmaxf(m, qz), 0.f));
+      }
+    }
+    if (nb > 0) {
+#pragma unroll
+      for (int u = 0; u < 4; ++u) v[u] = fmaxf(v[u], s2min[u] > 0.f ? -__builtin_amdgcn_sqrtf(s2min[u]) : depth[u]);
+    }
+    if (VEC) {
+      *reinterpret_cast<float4*>(out + off) = make_float4(v[0], v[1], v[2], v[3]);
+    } else {
+#pragma unroll
+      for (int u = 0; u < 4; ++u)
+        if (k0 + u < d2) out[off + u] = v[u];
+    }
+  }
+}
+}  // namespace
+
+extern "C" int egx_sdf_boxes(const float* base_grid, const float* room_lo_hi, const float* boxes, int num_boxes, const float* center_host,
+                             float scale, int d0, int d1, int d2, float* out_grid, void* stream_) {
+  EGX_REQUIRE(center_host && out_grid, "null centre / grid");
+  EGX_REQUIRE(base_grid || room_lo_hi, "a base grid or a room box is needed to start from");
+  EGX_REQUIRE(num_boxes >= 0 && num_boxes <= EGX_SDF_MAX_BOXES && (num_boxes == 0 || boxes), "0 <= num_boxes <= EGX_SDF_MAX_BOXES boxes");
+  EGX_REQUIRE(scale > 0.f && d0 > 0 && d1 > 0 && egx_sdf_dims_ok(d0, d1, d2),
+              "scale must be positive, the grid needs d2 >= 2 and fewer than 2^32 samples");
+  BoxesArg a;
+  memset(&a, 0, sizeof(a));
+  if (!base_grid) {
+    const float* r = room_lo_hi;
+    EGX_REQUIRE(r[3] > r[0] && r[4] > r[1] && r[5] > r[2], "room box: hi must exceed lo");
+    a.room = BoxDev{(float)(0.5 * ((double)r[0] + r[3])), (float)(0.5 * ((double)r[1] + r[4])), 1.f, 0.f,
+                    (float)(0.5 * ((double)r[3] - r[0])), (float)(0.5 * ((double)r[4] - r[1])),
+                    (float)(0.5 * ((double)r[2] + r[5])), (float)(0.5 * ((double)r[5] - r[2]))};
+  }
+  for (int k = 0; k < num_boxes; ++k) {
+    const float* b = boxes + 7 * k;   // cx, cy, half_x, half_y, z_lo, z_hi, yaw
+    bool finite = true;
+    for (int e = 0; e < 7; ++e) finite = finite && std::isfinite(b[e]);
+    EGX_REQUIRE(finite && b[2] > 0.f && b[3] > 0.f && b[5] > b[4], "box: finite entries, positive half extents, z_hi > z_lo");
+    a.b[k] = BoxDev{b[0], b[1], (float)cos((double)b[6]), (float)sin((double)b[6]), b[2], b[3],
+                    (float)(0.5 * ((double)b[4] + b[5])), (float)(0.5 * ((double)b[5] - b[4]))};
+  }
+  const int r2 = egx_ceil_div(d2, 4);
+  const unsigned long long runs = (unsigned long long)d0 * d1 * r2;
+  const unsigned blocks = (unsigned)((runs + 255) / 256 < 2048 ? (runs + 255) / 256 : 2048);   // grid-stride above 2048 blocks
+  const bool vec = d2 % 4 == 0 && ((uintptr_t)out_grid % 16 == 0) && ((uintptr_t)base_grid % 16 == 0);
+  hipStream_t st = static_cast<hipStream_t>(stream_);
+  if (vec)
+    hipLaunchKernelGGL(egx_sdf_boxes_kernel<true>, dim3(blocks), dim3(256), 0, st, base_grid, a, num_boxes, center_host[0], center_host[1],
+                       center_host[2], 1.f / scale, d0, d1, d2, r2, out_grid);
+  else
+    hipLaunchKernelGGL(egx_sdf_boxes_kernel<false>, dim3(blocks), dim3(256), 0, st, base_grid, a, num_boxes, center_host[0],
+                       center_host[1], center_host[2], 1.f / scale, d0, d1, d2, r2, out_grid);
   EGX_HIP_CHECK(hipGetLastError());
   return EGX_OK;
 }

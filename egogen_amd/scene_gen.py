@@ -9,6 +9,8 @@ tool for other scenes (README.md:97).  This module produces the same four artefa
                          on a raster of the floor; rectangles of free cells as triangles, the free region's outline as rings)
   start / target pairs   `sample_pairs`
   files                  `write_ply` (binary little endian, readable by `egobody.read_ply` / trimesh), `save_scene` (npz)
+  random box scenes      `random_box_layout` -> `box_layout_scene` (analytic room + oriented boxes; HIP kernel `egx_sdf_boxes`
+                         writes the grid on the device), `add_boxes_to_scene` (the same boxes composed onto a prepared scene)
 
 Scanned rooms (open triangle soups: walls without backs, holes, duplicated vertices) take the `scene_from_scan` path instead
 (`python -m egogen_amd.prepare_scene`):
@@ -539,11 +541,209 @@ def scene_from_scan(vertices: np.ndarray, faces: np.ndarray, res: int = 256, cel
             "free": free, "origin": origin, "cell": cell, "vertices": v, "faces": f, "times": times}
 
 
+# ------------------------------------------------------------------------------------------------ random box scenes
+# Room, cube centre and half size of `synth.make_sdf_scene` ('single_box'): what `boxes:SxK` scenes are built in.
+ROOM_LO, ROOM_HI = (-3.9, -3.9, 0.0), (3.9, 3.9, 4.9)
+ROOM_CENTER, ROOM_HALF = (0.0, 0.0, 1.0), 4.0
+MAX_BOXES = 16   # EGX_SDF_MAX_BOXES (include/egogen_hip.h)
+
+
+def _box_frame(x, y, box):
+    """|(p - c) rotated by -yaw| - half extents: the two horizontal terms of the box distance."""
+    cx, cy, hx, hy, yaw = float(box[0]), float(box[1]), float(box[2]), float(box[3]), float(box[6])
+    c, s = np.cos(yaw), np.sin(yaw)
+    dx, dy = np.asarray(x, np.float64) - cx, np.asarray(y, np.float64) - cy
+    return np.abs(c * dx + s * dy) - hx, np.abs(c * dy - s * dx) - hy
+
+
+def oriented_box_sdf(points: np.ndarray, box: Sequence[float]) -> np.ndarray:
+    """Exact signed distance (float64, negative inside) of points [...,3] to one box of a layout,
+    (cx, cy, half_x, half_y, z_lo, z_hi, yaw): the box |x| <= half_x, |y| <= half_y, z_lo <= z <= z_hi rotated by yaw about z
+    and moved to (cx, cy).  With q = |R(-yaw)(p - c)| - h per axis:  d = |max(q, 0)| + min(max(q_x, q_y, q_z), 0).  This is the
+    definition `egx_sdf_boxes` evaluates in float32."""
+    p = np.asarray(points, np.float64)
+    qx, qy = _box_frame(p[..., 0], p[..., 1], box)
+    z0, z1 = float(box[4]), float(box[5])
+    q = np.stack([qx, qy, np.abs(p[..., 2] - 0.5 * (z0 + z1)) - 0.5 * (z1 - z0)], -1)
+    return np.linalg.norm(np.maximum(q, 0.0), axis=-1) + np.minimum(q.max(-1), 0.0)
+
+
+def footprint_distance(x: np.ndarray, y: np.ndarray, box: Sequence[float]) -> np.ndarray:
+    """Signed distance in the floor plane to a box's footprint (its rotated rectangle), negative inside."""
+    q = np.stack(_box_frame(x, y, box), -1)
+    return np.linalg.norm(np.maximum(q, 0.0), axis=-1) + np.minimum(q.max(-1), 0.0)
+
+
+def footprint_ring(box: Sequence[float], ccw: bool = False) -> np.ndarray:
+    """The footprint's corners as a closed ring [5,2] (clockwise by default: a hole of the walkable polygon)."""
+    cx, cy, hx, hy, yaw = float(box[0]), float(box[1]), float(box[2]), float(box[3]), float(box[6])
+    c, s = np.cos(yaw), np.sin(yaw)
+    loc = np.array([[-hx, -hy], [hx, -hy], [hx, hy], [-hx, hy], [-hx, -hy]])
+    r = np.stack([cx + c * loc[:, 0] - s * loc[:, 1], cy + s * loc[:, 0] + c * loc[:, 1]], 1)
+    return r if ccw else r[::-1].copy()
+
+
+def random_box_layout(rng: np.random.Generator, num_boxes: int, room_lo: Sequence[float], room_hi: Sequence[float],
+                      size: Tuple[float, float] = (0.5, 1.5), height: Tuple[float, float] = (0.5, 1.5), yaw: bool = True,
+                      wall_margin: float = 0.6, gap: float = 0.8, max_tries: int = 2000) -> np.ndarray:
+    """`num_boxes` boxes standing on the floor of the room, [K,7] float64 rows (cx, cy, half_x, half_y, z_lo, z_hi, yaw): side
+    lengths and heights uniform in `size` / `height` (the reference's box obstacles are 0.5 - 1.5 m, environments.py:386-402),
+    yaw uniform in [-pi, pi) (0 without `yaw`).  Sequential rejection on bounding circles (radius = half diagonal of the
+    footprint): a box's circle lies `wall_margin` inside the walls and its centre at least r_i + r_j + gap from every box placed
+    before, so footprints are disjoint holes of the walkable polygon and a body passes between any two.  Every draw (size, yaw
+    and centre) counts as one try; ValueError after `max_tries` tries for the whole layout."""
+    lo, hi = np.asarray(room_lo, np.float64)[:2], np.asarray(room_hi, np.float64)[:2]
+    out = np.zeros((int(num_boxes), 7))
+    rad = np.zeros(int(num_boxes))
+    k = tries = 0
+    while k < num_boxes:
+        if tries >= max_tries:
+            raise ValueError(f"random_box_layout: placed {k} of {num_boxes} boxes in {max_tries} tries (room {lo} .. {hi}, wall margin "
+                             f"{wall_margin}, gap {gap}): fewer boxes or a larger room")
+        tries += 1
+        half = rng.uniform(size[0], size[1], 2) / 2
+        h = rng.uniform(height[0], height[1])
+        a = rng.uniform(-np.pi, np.pi) if yaw else 0.0
+        u = rng.uniform(0.0, 1.0, 2)
+        r = float(np.hypot(half[0], half[1]))
+        span = hi - lo - 2 * (r + wall_margin)
+        if np.any(span <= 0):
+            continue
+        c = lo + r + wall_margin + u * span
+        if k and np.any(np.linalg.norm(out[:k, :2] - c, axis=1) < rad[:k] + r + gap):
+            continue
+        out[k], rad[k] = (c[0], c[1], half[0], half[1], 0.0, h, a), r
+        k += 1
+    return out
+
+
+def sdf_boxes(layout: np.ndarray, center: Sequence[float], scale: float, dims: Optional[Sequence[int]] = None,
+              room: Optional[Tuple[Sequence[float], Sequence[float]]] = None, base=None, out=None, device: str = "cuda"):
+    """HIP kernel `egx_sdf_boxes`: max(start, max_k(-oriented_box_sdf(., box_k))) on the sample grid of `mesh_to_sdf_dict`, start
+    = `base` (a float32 device grid; `out` may be the same tensor: in place) or the signed distance to the `room` (lo[3], hi[3]).
+    Returns the device grid [d0,d1,d2]."""
+    import torch
+    from . import _lib
+    if not torch.cuda.is_available():
+        raise _lib.EgxError("sdf_boxes runs on the HIP device only (no CPU fallback)")
+    if base is not None:
+        if not (isinstance(base, torch.Tensor) and base.is_cuda and base.dtype == torch.float32 and base.dim() == 3 and base.is_contiguous()):
+            raise ValueError("base: a contiguous float32 [d0,d1,d2] tensor on the device")
+        dims = tuple(base.shape) if dims is None else tuple(dims)
+        if tuple(base.shape) != tuple(dims):
+            raise ValueError(f"base grid {tuple(base.shape)} != dims {tuple(dims)}")
+    if dims is None:
+        raise ValueError("dims or a base grid is needed")
+    d0, d1, d2 = [int(x) for x in dims]
+    if out is None:
+        out = torch.empty(max(d0, 0), max(d1, 0), max(d2, 0), dtype=torch.float32, device=base.device if base is not None else device)
+    elif not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (d0, d1, d2)):
+        raise ValueError("out: a contiguous float32 device tensor of the grid's dimensions")
+    lay = np.ascontiguousarray(np.asarray(layout, np.float32).reshape(-1, 7))
+    K = len(lay)
+    boxes = (C.c_float * max(7 * K, 1))(*lay.reshape(-1).tolist())
+    rm = None if room is None else (C.c_float * 6)(*[float(x) for x in list(room[0])[:3] + list(room[1])[:3]])
+    c = (C.c_float * 3)(*[float(x) for x in center])
+    _lib.check(_lib.load().egx_sdf_boxes(_lib.ptr(base), rm, boxes, K, c, float(scale), d0, d1, d2, C.c_void_p(out.data_ptr()),
+                                         _lib.current_stream_ptr()), "egx_sdf_boxes")
+    return out
+
+
+def sample_clear_pairs(layout: np.ndarray, room_lo, room_hi, n: int, clearance: float = 0.5, min_dist: float = 1.7, seed=0,
+                       floor_height: float = 0.0) -> np.ndarray:
+    """n (start, target) pairs [n,2,3] float32, at least `min_dist` apart, both ends at least `clearance` from every footprint of
+    the layout and from the walls of the room rectangle."""
+    rng = np.random.default_rng(seed)
+    lo, hi = np.asarray(room_lo, np.float64)[:2] + clearance, np.asarray(room_hi, np.float64)[:2] - clearance
+    if np.any(hi <= lo):
+        raise ValueError("the room is narrower than twice the clearance")
+    out = np.zeros((0, 2, 3))
+    for _ in range(200):
+        p = rng.uniform(lo, hi, (4 * n, 2, 2))
+        ok = np.linalg.norm(p[:, 0] - p[:, 1], axis=-1) >= min_dist
+        for b in np.asarray(layout, np.float64).reshape(-1, 7):
+            ok &= (footprint_distance(p[..., 0], p[..., 1], b) >= clearance).all(1)
+        p = p[ok]
+        out = np.concatenate([out, np.concatenate([p, np.full(p.shape[:2] + (1,), floor_height)], -1)], 0)
+        if len(out) >= n:
+            return out[:n].astype(np.float32)
+    raise ValueError(f"only {len(out)} of {n} pairs found: the boxes leave too little room at clearance {clearance}")
+
+
+def box_layout_rings(layout: np.ndarray, room_lo, room_hi) -> List[np.ndarray]:
+    """Walkable polygon of a box layout: the room rectangle counter-clockwise, one clockwise ring per (un-inflated) footprint -
+    what `synth.sdf_scene_polygon` gives for 'single_box'."""
+    from . import synth
+    return [synth.rect_ring(np.asarray(room_lo, np.float64)[:2], np.asarray(room_hi, np.float64)[:2], True)] + \
+        [footprint_ring(b) for b in np.asarray(layout, np.float64).reshape(-1, 7)]
+
+
+def box_layout_scene(layout: np.ndarray, res: int = 256, device: str = "cuda", n_pairs: int = 4096, clearance: float = 0.5,
+                     seed=0, name: Optional[str] = None) -> dict:
+    """One entry of `VecCrowdEnv(sdf_scenes=[...])` from a box layout in `make_sdf_scene`'s room: {'sdf_dict' (the grid is built on
+    the device by `egx_sdf_boxes` and stays there), 'rings', 'pairs', 'name', 'boxes'}."""
+    import torch
+    lay = np.asarray(layout, np.float64).reshape(-1, 7)
+    grid = sdf_boxes(lay, ROOM_CENTER, 1.0 / ROOM_HALF, (res, res, res), room=(ROOM_LO, ROOM_HI), device=device)
+    sdf = {"sdf": grid, "center": torch.tensor(np.asarray(ROOM_CENTER, np.float32), device=grid.device),
+           "scale": torch.tensor(np.float32(1.0 / ROOM_HALF), device=grid.device)}
+    return {"sdf_dict": sdf, "rings": box_layout_rings(lay, ROOM_LO, ROOM_HI),
+            "pairs": sample_clear_pairs(lay, ROOM_LO, ROOM_HI, n_pairs, clearance, seed=seed),
+            "name": name or f"boxes{len(lay)}", "boxes": lay}
+
+
+def stamp_boxes(free: np.ndarray, origin: np.ndarray, cell: float, layout: np.ndarray, radius: float = 0.2) -> np.ndarray:
+    """The walkable raster with the boxes of a layout on it: a cell stays free iff it was free and its centre is farther than
+    `radius` (the body radius the raster was inflated by) from every footprint - `walkable_grid`'s rule."""
+    free = np.asarray(free, bool).copy()
+    nx, ny = free.shape
+    X, Y = np.meshgrid(origin[0] + (np.arange(nx) + 0.5) * cell, origin[1] + (np.arange(ny) + 0.5) * cell, indexing="ij")
+    for b in np.asarray(layout, np.float64).reshape(-1, 7):
+        free &= footprint_distance(X, Y, b) > radius
+    return free
+
+
+def add_boxes_to_scene(scene: dict, layout: np.ndarray, radius: float = 0.2, n_pairs: Optional[int] = None, min_dist: float = 1.7,
+                       seed=0, name: Optional[str] = None, device: str = "cuda") -> dict:
+    """Boxes on the floor of a prepared scene that carries its raster ('free', 'origin', 'cell': `scene_from_scan`, or a file
+    saved from one): the cells under the inflated footprints are stamped out, rings and pairs are re-derived with
+    `grid_to_rings` / `sample_pairs`, and the boxes are composed onto the scene's SDF grid IN PLACE when it is a device tensor
+    (a host grid is uploaded first).  Returns {'sdf_dict', 'rings', 'pairs', 'name', 'boxes', 'free', 'origin', 'cell'}."""
+    import torch
+    for k in ("free", "origin", "cell", "sdf_dict"):
+        if k not in scene:
+            raise ValueError(f"add_boxes_to_scene: the scene has no {k!r}; it needs its raster (free, origin, cell) and SDF grid")
+    lay = np.asarray(layout, np.float64).reshape(-1, 7)
+    origin, cell = np.asarray(scene["origin"], np.float64), float(scene["cell"])
+    free = stamp_boxes(scene["free"], origin, cell, lay, radius)
+    rings = grid_to_rings(free, origin, cell)
+    if not rings:
+        raise ValueError("no walkable cell is left after placing the boxes")
+    fh = float(scene.get("floor_height", 0.0))
+    pairs = sample_pairs(rings, int(n_pairs or len(scene["pairs"])), min_dist, seed, fh)
+    sd = scene["sdf_dict"]
+    g = sd["sdf"]
+    if not (isinstance(g, torch.Tensor) and g.is_cuda):
+        g = torch.as_tensor(np.asarray(g, np.float32)).to(device)
+    g = g.squeeze()
+    if g.dtype != torch.float32 or not g.is_contiguous():
+        g = g.float().contiguous()
+    c = sd["center"]
+    c = (c.detach().cpu().numpy() if hasattr(c, "detach") else np.asarray(c)).reshape(-1)
+    s = sd["scale"]
+    s = float(s.item() if hasattr(s, "item") else s)
+    sdf_boxes(lay, c, s, base=g, out=g)
+    return {"sdf_dict": {"sdf": g, "center": sd["center"], "scale": sd["scale"]}, "rings": rings, "pairs": pairs,
+            "name": name or f"{scene.get('name', 'scene')}+boxes{len(lay)}", "boxes": lay, "free": free, "origin": origin, "cell": cell}
+
+
 def save_scene(path: str, scene: dict, sdf_dict: Optional[dict] = None) -> None:
     """npz pack of a generated scene (polygon rings flattened with offsets; the SDF grid if given)."""
     out = {"edges": scene["edges"], "tris": scene["tris"], "floor_height": np.float32(scene["floor_height"]), "pairs": scene["pairs"],
            "nav_v": scene["nav_v"], "nav_f": scene["nav_f"], "ring_xy": np.concatenate(scene["rings"], 0),
            "ring_off": np.cumsum([0] + [len(r) for r in scene["rings"]]).astype(np.int32)}
+    if all(k in scene for k in ("free", "origin", "cell")):   # the walkable raster: what add_boxes_to_scene stamps boxes onto
+        out["free"], out["origin"], out["cell"] = np.asarray(scene["free"], bool), np.asarray(scene["origin"], np.float64), np.float64(scene["cell"])
     if "z_offset" in scene:   # scene_from_scan: the height the scan was shifted down by (not read back by load_scene_file)
         out["z_offset"] = np.float64(scene["z_offset"])
     if sdf_dict is not None:

@@ -217,18 +217,75 @@ def build_policy(args, device="cuda", policy_cfg: Optional[dict] = None) -> GAMM
     return policy
 
 
-def load_scene_file(path: str) -> dict:
+def load_scene_file(path: str, raster: bool = False) -> dict:
     """A scene prepared with `egogen_amd.scene_gen` (`save_scene`): with an SDF grid -> the room kind (SDF penetration term,
-    walkable polygon for the egosensing rays, start / target pairs); without -> one scene of the box kind (walkability map)."""
+    walkable polygon for the egosensing rays, start / target pairs); without -> one scene of the box kind (walkability map).
+    `raster`: also pass through the walkable raster the file carries ('free', 'origin', 'cell', with 'floor_height'), as
+    `scene_gen.add_boxes_to_scene` needs it; a file without one gives the dict without these keys."""
     with np.load(path) as z:
         d = {k: z[k] for k in z.files}
     off = d["ring_off"]
     rings = [d["ring_xy"][off[i]:off[i + 1]] for i in range(len(off) - 1)]
+    extra = {}
+    if raster and all(k in d for k in ("free", "origin", "cell")):
+        extra = {"free": d["free"].astype(bool), "origin": d["origin"].astype(np.float64), "cell": float(d["cell"]),
+                 "floor_height": float(d["floor_height"])}
     if "sdf_sdf" in d:
         return dict(scene_kind="sdf", sdf_dict={"sdf": d["sdf_sdf"], "center": d["sdf_center"], "scale": d["sdf_scale"]}, rings=rings,
-                    pairs=d["pairs"])
+                    pairs=d["pairs"], **extra)
     return dict(scene_kind="box", box_scenes=[{"edges": d["edges"], "tris": d["tris"], "floor_height": float(d["floor_height"]),
-                                               "pairs": d["pairs"]}])
+                                               "pairs": d["pairs"]}], **extra)
+
+
+MAX_SPEC_BOXES = 4   # `random_box_layout` in the 7.8 m room: 4 boxes never failed in 500 layouts, 6 failed 10 times, 8 every other time
+
+
+def parse_box_spec(entry: str) -> Optional[dict]:
+    """A generated entry of a `--scene` value -> {'base': file or None, 'scenes': S, 'boxes': K}; None for any other entry.
+      boxes:S | boxes:SxK           S analytic rooms (`make_sdf_scene`'s room and cube, grid `--sdf-res`) with K random boxes each
+      <file.npz>+boxes:S[xK]        S variants of that prepared scene, K random boxes composed onto each
+    K defaults to 1, 1 <= K <= 4, S >= 1.  ValueError for an entry that names `boxes:` but is malformed."""
+    base, sep, tail = entry.rpartition("+")
+    if not sep:
+        base, tail = None, entry
+    if not tail.startswith("boxes:"):
+        return None
+    nums = tail[len("boxes:"):].split("x")
+    if len(nums) not in (1, 2) or not all(n.isdigit() for n in nums):
+        raise ValueError(f"scene entry {entry!r}: expected boxes:S or boxes:SxK with whole numbers S, K")
+    S, K = int(nums[0]), int(nums[1]) if len(nums) == 2 else 1
+    if S < 1 or not 1 <= K <= MAX_SPEC_BOXES:
+        raise ValueError(f"scene entry {entry!r}: needs S >= 1 scenes and 1 <= K <= {MAX_SPEC_BOXES} boxes per scene")
+    if base is not None and not base.endswith(".npz"):
+        raise ValueError(f"scene entry {entry!r}: boxes are composed onto a prepared .npz scene, got {base!r}")
+    return {"base": base, "scenes": S, "boxes": K}
+
+
+def scene_spec_generates(spec: str) -> bool:
+    """Does a `--scene` value hold a generated entry (`parse_box_spec`)?  Needs no GPU."""
+    return any(parse_box_spec(e) is not None for e in (scene_entries(spec) if ("," in spec or os.path.isdir(spec)) else [spec]))
+
+
+def _generated_scenes(spec: dict, first: int, generation: int, sdf_res: int, seed: int, base: Optional[dict]) -> List[dict]:
+    """The S scenes of one generated entry.  Scene number `first + s` of generation `generation`: its layout and pairs are a
+    function of (seed, generation, scene number) alone, so every rank and every env built from the same spec agree."""
+    from . import scene_gen
+    out = []
+    for s in range(spec["scenes"]):
+        key = [int(seed), int(generation), first + s]
+        rng = np.random.default_rng(key)
+        if base is None:
+            lay = scene_gen.random_box_layout(rng, spec["boxes"], scene_gen.ROOM_LO, scene_gen.ROOM_HI)
+            out.append(scene_gen.box_layout_scene(lay, sdf_res, n_pairs=4096, seed=key + [1], name=f"boxes{first + s}"))
+        else:
+            r = base["raster"]
+            lo = r["origin"]
+            hi = lo + np.asarray(r["free"].shape) * r["cell"]
+            lay = scene_gen.random_box_layout(rng, spec["boxes"], lo, hi)
+            g = torch.as_tensor(np.asarray(base["sdf_dict"]["sdf"], np.float32)).squeeze().cuda()   # every variant its own grid
+            sc = dict(r, sdf_dict=dict(base["sdf_dict"], sdf=g), pairs=base["pairs"], name=base["name"])
+            out.append(scene_gen.add_boxes_to_scene(sc, lay, seed=key + [1], name=f"{base['name']}+boxes{first + s}"))
+    return out
 
 
 def scene_entries(spec: str) -> List[str]:
@@ -253,8 +310,13 @@ def build_scene(kind: str, sdf_res: int = 256, seed: int = 0, data_dir: str = "d
     grid), 'single_box' (BASELINE config 2), 'box' (random_box_obstacle_new stand-in), or the path of a `.npz` scene
     prepared with `egogen_amd.scene_gen.save_scene` (new scenes) - or a LIST of SDF scenes: comma-separated
     entries of those kinds (a directory = its `*.npz` files, sorted by name), all SDF scenes of the same grid dimensions, for one
-    env over the set (`VecCrowdEnv(sdf_scenes=...)`).  A single entry behaves exactly as before."""
+    env over the set (`VecCrowdEnv(sdf_scenes=...)`).  A single entry behaves exactly as before.  Entries of the forms
+    `boxes:SxK` and `<file.npz>+boxes:SxK` (`parse_box_spec`) are generated on the device: S scenes with K random boxes each; the
+    returned dict then carries `scene_factory(generation)`, which builds the list again with other layouts."""
     entries = scene_entries(kind) if ("," in kind or os.path.isdir(kind)) else [kind]
+    specs = [parse_box_spec(e) for e in entries]
+    if any(sp is not None for sp in specs):
+        return _build_generated(entries, specs, sdf_res, seed, data_dir)
     if len(entries) > 1 or entries[0] != kind:
         scenes, dims = [], None
         for e in entries:
@@ -300,7 +362,42 @@ def build_scene(kind: str, sdf_res: int = 256, seed: int = 0, data_dir: str = "d
     raise ValueError(f"unknown scene {kind!r}")
 
 
+def _build_generated(entries: List[str], specs: List[Optional[dict]], sdf_res: int, seed: int, data_dir: str) -> dict:
+    """A scene list with generated entries (`parse_box_spec`): the fixed entries are built once, the generated ones by
+    `scene_factory(generation)`, which returns the whole list again with new layouts in the generated positions (for
+    `VecCrowdEnv.replace_sdf_scenes`); the returned set is generation 0."""
+    fixed, bases = {}, {}
+    for i, (e, sp) in enumerate(zip(entries, specs)):
+        if sp is None:
+            sc = build_scene(e, sdf_res=sdf_res, seed=seed, data_dir=data_dir)
+            if sc["scene_kind"] != "sdf":
+                raise ValueError(f"scene list entry {e!r} is a {sc['scene_kind']} scene: a scene list holds SDF scenes only")
+            fixed[i] = dict(sdf_dict=sc["sdf_dict"], rings=sc["rings"], pairs=sc["pairs"], name=os.path.splitext(os.path.basename(e))[0])
+        elif sp["base"] is not None:
+            sc = load_scene_file(sp["base"], raster=True)
+            if "free" not in sc:
+                raise ValueError(f"scene file {sp['base']!r} carries no walkable raster (free / origin / cell), which placing boxes in "
+                                 "it needs: re-run `python -m egogen_amd.prepare_scene` to write the file again")
+            if sc["scene_kind"] != "sdf":
+                raise ValueError(f"scene file {sp['base']!r} holds no SDF grid")
+            bases[i] = dict(raster={k: sc[k] for k in ("free", "origin", "cell", "floor_height")}, sdf_dict=sc["sdf_dict"],
+                            pairs=sc["pairs"], name=os.path.splitext(os.path.basename(sp["base"]))[0])
+
+    def scene_factory(generation: int) -> List[dict]:
+        scenes = []
+        for i, (e, sp) in enumerate(zip(entries, specs)):
+            scenes += [fixed[i]] if sp is None else _generated_scenes(sp, len(scenes), generation, sdf_res, seed, bases.get(i))
+        dims = [tuple(int(x) for x in d["sdf_dict"]["sdf"].squeeze().shape) for d in scenes]
+        for d, sc in zip(dims, scenes):
+            if d != dims[0]:
+                raise ValueError(f"scene {sc['name']!r} has an SDF grid of {d}, scene {scenes[0]['name']!r} {dims[0]}: the scenes of a "
+                                 "set share their grid dimensions")
+        return scenes
+
+    return dict(scene_kind="sdf", sdf_scenes=scene_factory(0), scene_factory=scene_factory)
+
+
 def build_env(num_agents: int, scene: dict, body: BodyModelHandle, prior: GAMMAPrimitiveCombo, vposer: VPoserEncoder,
               finetuning=False, seed=0, keep_rollout=False, use_graph=False, cfg: Optional[dict] = None) -> VecCrowdEnv:
     return VecCrowdEnv(num_agents, body, prior, vposer, finetuning=finetuning, seed=seed, keep_rollout=keep_rollout,
-                       use_graph=use_graph, cfg=cfg, **scene)
+                       use_graph=use_graph, cfg=cfg, **{k: v for k, v in scene.items() if k != "scene_factory"})

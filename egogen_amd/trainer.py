@@ -368,7 +368,10 @@ class CheckpointWriter:
 def onpolicy_trainer(policy: GAMMAPPOPolicy, train_collector: Collector, test_collector: Optional[Collector], max_epoch: int,
                      step_per_epoch: int, repeat_per_collect: int, episode_per_test: int, batch_size: int,
                      step_per_collect: int, save_best_fn: Optional[Callable] = None, logger: Optional[ScalarLogger] = None,
-                     save_checkpoint_fn: Optional[Callable] = None, save_interval: int = 2, verbose: bool = True):
+                     save_checkpoint_fn: Optional[Callable] = None, save_interval: int = 2, verbose: bool = True,
+                     epoch_begin_fn: Optional[Callable] = None):
+    """`epoch_begin_fn(epoch)`: called on every rank before the first collect of each epoch (main_ppo.py swaps the training
+    env's generated scenes there); None changes nothing."""
     world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
     rank = dist.get_rank() if world > 1 else 0
     A_global = train_collector.A * world
@@ -391,6 +394,8 @@ def onpolicy_trainer(policy: GAMMAPPOPolicy, train_collector: Collector, test_co
     train_collector.reset()
     forced_seen = 0
     for epoch in range(1, max_epoch + 1):
+        if epoch_begin_fn is not None:
+            epoch_begin_fn(epoch)
         policy.train()
         steps_in_epoch = 0
         while steps_in_epoch < step_per_epoch:

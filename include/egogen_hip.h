@@ -256,6 +256,23 @@ int egx_mesh_sdf(const float* triangles, int num_triangles, const float* center_
                  int inside_positive, float* out_grid, void* stream);
 
 /*
+ * egx_sdf_boxes - analytic scenes on the device: a room box with up to EGX_SDF_MAX_BOXES oriented boxes standing in it, in the
+ * grid contract of egx_mesh_sdf (sample (i,j,k) at center + ((2i+1)/d - 1) / scale).  Replaces the host builder
+ * synth.make_sdf_scene (float64 numpy, one axis-aligned box) for the reference's training distribution of random box scenes
+ * (random_box_obstacle_new, environments.py:386-402).  Stored value, make_sdf_scene's convention (> 0 inside obstacles and
+ * outside the room):  v = max(start, max_k(-d_k)),  d_k = exact signed distance to box k, negative inside, evaluated in the
+ * box's frame (p - c rotated by -yaw about z);  start = base_grid's sample when base_grid is given (composition onto an
+ * existing grid, e.g. a scan), else the signed distance to the room box.
+ *   base_grid  device [d0][d1][d2] or NULL; out_grid == base_grid (in place) is allowed;
+ *   room_lo_hi host [6] (lo.xyz, hi.xyz) or NULL; at least one of base_grid / room_lo_hi; base_grid wins when both are given;
+ *   boxes      host [num_boxes][7]: cx, cy, half_x, half_y, z_lo, z_hi, yaw; passed to the kernel by value (no device
+ *              allocation, no copy, no synchronisation); 0 <= num_boxes <= EGX_SDF_MAX_BOXES.
+ */
+#define EGX_SDF_MAX_BOXES 16
+int egx_sdf_boxes(const float* base_grid, const float* room_lo_hi, const float* boxes, int num_boxes, const float* center_host,
+                  float scale, int d0, int d1, int d2, float* out_grid, void* stream);
+
+/*
  * egx_scan_sdf - scene preparation from a scanned room (an open, oriented triangle soup): the same grid contract as
  * egx_mesh_sdf, filled with the exact distance to the nearest triangle (nearest-triangle search through a bounding-volume
  * hierarchy) signed by the pseudo-normal of the nearest feature (Baerentzen & Aanaes 2005): < 0 on the side the normals
