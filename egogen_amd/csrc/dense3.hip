@@ -77,6 +77,18 @@ __device__ __forceinline__ void d3_mma_tiles(const bf16x8 (&fa)[MI][NPL], const 
   }
 }
 
+// Every pointer of D3Plain / D3Gru is a device-memory address, but the kernels copy those structs out of the kernel-argument
+// segment as ints (d3_kernarg), which hides that from the compiler: it then emits FLAT loads and stores, and those count on the
+// LDS counter as well as on the vector-memory one, so that every wait for an LDS read also waits for all of them.  d3_g() states
+// the address space where a pointer is used: global loads and stores, which the epilogues can keep in flight across LDS traffic.
+#if defined(__HIP_DEVICE_COMPILE__)
+#define D3_GLOBAL __attribute__((address_space(1)))
+#else
+#define D3_GLOBAL
+#endif
+template <class T>
+__device__ __forceinline__ D3_GLOBAL T* d3_g(T* p) { return (D3_GLOBAL T*)p; }
+
 __device__ __forceinline__ float d3_act(float v, int act, float slope) {
   switch (act) {
     case 1: return tanhf(v);
@@ -187,22 +199,29 @@ void egx_launch_pack3(hipStream_t st, const D3Pack* jobs, int njobs) {
   hipLaunchKernelGGL(egx_pack3_kernel, dim3(egx_ceil_div(total, 4)), dim3(256), 0, st, J);
 }
 
-// One output element after the reduction (bias already added): activation, saved activation, residual, fp32 stores, and the
-// value that goes into the packed images (0 outside the matrix).
-__device__ __forceinline__ float d3_finish(const D3Plain& a, float v, int m, int n, int row_base) {
+// One output element after the reduction (bias already added): activation, saved activation, residual, and the value that goes
+// into the packed images (0 outside the matrix).  The element's residual and saved-activation operands come in as values (the
+// kernel requests them ahead of the reduction barrier) and its fp32 outputs leave as values (v_act, v_out: stored by
+// d3_store once the lane's last element is finished), so that no memory operation waits for another one in here.
+__device__ __forceinline__ float d3_finish(const D3Plain& a, float v, int m, int n, float resv, float dactv, float& v_act, float& v_out) {
   v = d3_act(v, a.act, a.slope);
   const bool live = m < a.M && n < a.N;
-  if (live && a.out_act) a.out_act[(size_t)m * a.ldact + n] = v;   // activation before the skip connection (saved for backward)
-  if (live && a.res && !(a.n_split > 0 && n >= a.n_split)) v += a.res[(size_t)(row_base + m) * a.ldr + n];
-  if (live && a.n_split > 0 && n >= a.n_split) {
-    // weight-gradient launch: the B operand's extra row of ones makes column n_split the bias gradient
-    if (n == a.n_split && a.bias_out) a.bias_out[m] = v;
-  } else if (live && a.out) {
-    a.out[(size_t)(row_base + m) * a.ldo + n] = v;
-  }
+  v_act = v;   // activation before the skip connection (saved for backward)
+  if (live && a.res && !(a.n_split > 0 && n >= a.n_split)) v += resv;
+  v_out = v;
   // gradient launches: what goes on to the next products is v x act'(saved activation of the layer below)
-  if (live && a.dact) v *= d3_act_grad(a.dact[(size_t)m * a.lddact + n], a.dact_code, a.dact_slope);
+  if (live && a.dact) v *= d3_act_grad(dactv, a.dact_code, a.dact_slope);
   return live ? v : 0.f;
+}
+__device__ __forceinline__ void d3_store(const D3Plain& a, float v_act, float v_out, int m, int n, int row_base) {
+  if (!(m < a.M && n < a.N)) return;
+  if (a.out_act) d3_g(a.out_act)[(size_t)m * a.ldact + n] = v_act;
+  if (a.n_split > 0 && n >= a.n_split) {
+    // weight-gradient launch: the B operand's extra row of ones makes column n_split the bias gradient
+    if (n == a.n_split && a.bias_out) d3_g(a.bias_out)[m] = v_out;
+  } else if (a.out) {
+    d3_g(a.out)[(size_t)(row_base + m) * a.ldo + n] = v_out;
+  }
 }
 
 // Packed images of a finished tile (values in `tile`, pitch TN + 4).  Row-major image (the consumer's A operand): 16-row tiles
@@ -216,14 +235,14 @@ __device__ __forceinline__ void d3_write_packed(const D3Plain& a, const float* t
   const int m_ksteps = (a.M + 31) >> 5, n_ksteps = (a.N + 31) >> 5;   // extents of the images (even tile counts)
   for (int task = wave; task < ntask; task += NW) {
     float x[8];
-    bf16x8* o;
+    D3_GLOBAL bf16x8* o;
     if (a.out3 && task < NR) {
       const int i = task / (NI / 2), j = task % (NI / 2);
       if (MI * mt + i >= 2 * m_ksteps || nt * (NI / 2) + j >= n_ksteps) continue;   // past the image (ragged last tile)
       const int row = 16 * i + (lane & 15), g = lane >> 4;
       const f32x4 x0 = *reinterpret_cast<const f32x4*>(&tile[row * PITCH + 32 * j + 8 * g]), x1 = *reinterpret_cast<const f32x4*>(&tile[row * PITCH + 32 * j + 8 * g + 4]);
       x[0] = x0[0]; x[1] = x0[1]; x[2] = x0[2]; x[3] = x0[3]; x[4] = x1[0]; x[5] = x1[1]; x[6] = x1[2]; x[7] = x1[3];
-      o = a.out3 + (size_t)batch * a.batch_stride3 + ((size_t)(MI * mt + i) * a.S3 + a.s30 + nt * (NI / 2) + j) * 3 * 64 + lane;
+      o = d3_g(a.out3) + (size_t)batch * a.batch_stride3 + ((size_t)(MI * mt + i) * a.S3 + a.s30 + nt * (NI / 2) + j) * 3 * 64 + lane;
     } else {
       const int tt = task - (a.out3 ? NR : 0);
       const int j = tt / (MI / 2), i = tt % (MI / 2);
@@ -231,7 +250,7 @@ __device__ __forceinline__ void d3_write_packed(const D3Plain& a, const float* t
       const int c = 16 * j + (lane & 15), kg = lane >> 4;
 #pragma unroll
       for (int e = 0; e < 8; ++e) x[e] = tile[(32 * i + 8 * kg + e) * PITCH + c];
-      o = a.out3T + ((size_t)(NI * nt + j) * a.S3T + a.s3T0 + mt * (MI / 2) + i) * 3 * 64 + lane;
+      o = d3_g(a.out3T) + ((size_t)(NI * nt + j) * a.S3T + a.s3T0 + mt * (MI / 2) + i) * 3 * 64 + lane;
     }
     bf16x8 pl[NPL];
     d3_split<NPL>(x, pl);
@@ -252,24 +271,27 @@ struct D3Args4 {
 
 // The layer a block works on.  Picking one of the four structs by reference (`which == 0 ? four.p0 : ...`) makes the
 // compiler copy all of the kernel arguments to scratch in every wave and read the fields back with vector loads; selecting
-// field by field keeps them in SGPRs but loads all four structs.  Reading the one struct straight from the kernel-argument
-// segment (constant address space, uniform offset: scalar loads) touches only what is used.  D3Args4 is the kernels' only
-// argument, so p0 sits at offset 0 of the segment.
-__device__ __forceinline__ D3Plain d3_pick(int which) {
-  D3Plain a;
-  static_assert(offsetof(D3Args4, p0) == 0 && offsetof(D3Args4, p1) == sizeof(D3Plain) && sizeof(D3Plain) % 4 == 0, "layout");
+// field by field keeps them in SGPRs but loads all four structs, or reads each field where it is first used - a scalar round
+// trip in the middle of the epilogue.  Reading the one struct straight from the kernel-argument segment (constant address
+// space, uniform offset: scalar loads, all at the top of the kernel) touches only what is used.  The array of structs is the
+// kernels' first argument, so element 0 sits at offset 0 of the segment.
+template <class T>
+__device__ __forceinline__ T d3_kernarg(int which) {
+  T a;
+  static_assert(sizeof(T) % 4 == 0, "layout");
 #if defined(__HIP_DEVICE_COMPILE__)
   typedef const __attribute__((address_space(4))) char* kptr;
   typedef const __attribute__((address_space(4))) int* iptr;
-  iptr src = (iptr)((kptr)__builtin_amdgcn_kernarg_segment_ptr() + (size_t)which * sizeof(D3Plain));
+  iptr src = (iptr)((kptr)__builtin_amdgcn_kernarg_segment_ptr() + (size_t)which * sizeof(T));
   int* dst = reinterpret_cast<int*>(&a);
 #pragma unroll
-  for (int i = 0; i < (int)(sizeof(D3Plain) / 4); ++i) dst[i] = src[i];
+  for (int i = 0; i < (int)(sizeof(T) / 4); ++i) dst[i] = src[i];
 #else
   (void)which;
 #endif
   return a;
 }
+static_assert(offsetof(D3Args4, p0) == 0 && offsetof(D3Args4, p1) == sizeof(D3Plain), "layout");
 
 // MI x NI MFMA tiles of 16 x 16 per workgroup of NW waves (instantiated: 2 x 2 tiles; four waves, eight for 9..16 k-steps).
 template <int TRIP, int MI, int NI, int NW, int NPL>
@@ -277,7 +299,7 @@ __global__ __launch_bounds__(64 * NW) void egx_dense3_kernel(D3Args4 four) {
   constexpr int TM = 16 * MI, TN = 16 * NI, NACC = MI * NI * 4, PITCH = TN + 4;
   const int bx = (int)blockIdx.x;
   const int which = bx < four.end0 ? 0 : (bx < four.end1 ? 1 : (bx < four.end2 ? 2 : 3));
-  const D3Plain a = d3_pick(which);
+  const D3Plain a = d3_kernarg<D3Plain>(which);
   const int bid = bx - (which == 0 ? 0 : (which == 1 ? four.end0 : (which == 2 ? four.end1 : four.end2)));
   extern __shared__ __attribute__((aligned(16))) float d3_smem[];
   float* red = d3_smem;                      // [NW waves][NACC][64]
@@ -289,7 +311,7 @@ __global__ __launch_bounds__(64 * NW) void egx_dense3_kernel(D3Args4 four) {
   const int batch = bid / per_batch;
   int mt, nt;
   if (!d3_tile(bid - batch * per_batch, MT, NT, mt, nt, rowmap)) return;
-  const bf16x8* Ab = a.A + (size_t)batch * a.batch_strideA;
+  const D3_GLOBAL bf16x8* Ab = d3_g(a.A) + (size_t)batch * a.batch_strideA;
   const int per = (a.S + NW - 1) / NW;
   const int s_lo = wave * per, s_hi = min(a.S, s_lo + per);
   f32x4 acc[MI][NI];
@@ -300,12 +322,12 @@ __global__ __launch_bounds__(64 * NW) void egx_dense3_kernel(D3Args4 four) {
   // fragment streams of this tile: A row tiles MI mt + i (k-steps sa0 + s of a buffer with SA per row tile); B column tiles
   // NI nt + j, clamped to the image (packed images hold an even number of 16-row tiles; columns past N are never stored)
   const int a_tiles = 2 * ((a.M + 31) >> 5), b_tiles = 2 * ((a.N + 31) >> 5);
-  const bf16x8* pa[MI];
-  const bf16x8* pb[NI];
+  const D3_GLOBAL bf16x8* pa[MI];
+  const D3_GLOBAL bf16x8* pb[NI];
 #pragma unroll
   for (int i = 0; i < MI; ++i) pa[i] = Ab + ((size_t)min(MI * mt + i, a_tiles - 1) * a.SA + a.sa0) * 3 * 64 + lane;
 #pragma unroll
-  for (int j = 0; j < NI; ++j) pb[j] = a.B + (size_t)min(NI * nt + j, b_tiles - 1) * a.S * 3 * 64 + lane;
+  for (int j = 0; j < NI; ++j) pb[j] = d3_g(a.B) + (size_t)min(NI * nt + j, b_tiles - 1) * a.S * 3 * 64 + lane;
   for (int s = s_lo; s < s_hi; s += TRIP) {
     bf16x8 fa[TRIP][MI][NPL], fb[TRIP][NI][NPL];
 #pragma unroll
@@ -336,15 +358,45 @@ __global__ __launch_bounds__(64 * NW) void egx_dense3_kernel(D3Args4 four) {
     for (int ni = 0; ni < NI; ++ni)
 #pragma unroll
       for (int r = 0; r < 4; ++r) red[(wave * NACC + (mi * NI + ni) * 4 + r) * 64 + lane] = acc[mi][ni][r];
-  __syncthreads();
+  // The elements this lane finishes - tiles t = wave, wave + NW, ..., rows 4 (lane >> 4) + r of each - follow from wave and lane
+  // alone, so everything their epilogue reads from memory (bias, residual, the saved activation of a gradient launch) is
+  // requested HERE as one batch: the round trip runs under the barrier and the LDS reduction.  (Ahead of the k-loop it would
+  // ride on the operand wait for nothing at all, but the nine registers per tile would have to live through the loop, and
+  // <3,2,2,4,2> and <2,2,2,8,3> sit exactly on an occupancy step: profiles/dense3_epilogue.md.)  Out-of-range lanes read a
+  // clamped element - never an address past the matrix - and d3_finish masks the value.
+  constexpr int TW = (MI * NI + NW - 1) / NW;   // tiles per wave
   const int row_base = batch * a.batch_rows_out;
+  float pre_bias[TW], pre_res[TW][4], pre_dact[TW][4];
 #pragma unroll
-  for (int t0 = 0; t0 < MI * NI; t0 += NW) {
-    const int t = t0 + wave;
+  for (int k = 0; k < TW; ++k) {
+    pre_bias[k] = 0.f;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) pre_res[k][r] = pre_dact[k][r] = 0.f;
+    const int t = k * NW + wave;
+    if (t >= MI * NI) continue;
+    const int mi = t / NI, ni = t % NI;
+    const int n = nt * TN + 16 * ni + (lane & 15);
+    const int nc = min(n, a.N - 1), nr = min(n, (a.n_split > 0 ? a.n_split : a.N) - 1);   // res has no columns >= n_split
+    const int m0 = mt * TM + 16 * mi + 4 * (lane >> 4);
+    if (a.bias) pre_bias[k] = d3_g(a.bias)[nc];
+    if (a.res) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) pre_res[k][r] = d3_g(a.res)[(size_t)(row_base + min(m0 + r, a.M - 1)) * a.ldr + nr];
+    }
+    if (a.dact) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) pre_dact[k][r] = d3_g(a.dact)[(size_t)min(m0 + r, a.M - 1) * a.lddact + nc];
+    }
+  }
+  __syncthreads();
+#pragma unroll
+  for (int k = 0; k < TW; ++k) {
+    const int t = k * NW + wave;
     if (t >= MI * NI) continue;
     const int mi = t / NI, ni = t % NI;
     const int col = 16 * ni + (lane & 15), n = nt * TN + col;
-    const float bsv = (a.bias && n < a.N) ? a.bias[n] : 0.f;
+    const float bsv = n < a.N ? pre_bias[k] : 0.f;
+    float v_act[4], v_out[4];
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int q = t * 4 + r;
@@ -352,8 +404,11 @@ __global__ __launch_bounds__(64 * NW) void egx_dense3_kernel(D3Args4 four) {
 #pragma unroll
       for (int w2 = 3; w2 < NW; ++w2) v += red[(w2 * NACC + q) * 64 + lane];
       const int row = 16 * mi + 4 * (lane >> 4) + r, m = mt * TM + row;
-      tile[row * PITCH + col] = d3_finish(a, v + bsv, m, n, row_base);
+      tile[row * PITCH + col] = d3_finish(a, v + bsv, m, n, pre_res[k][r], pre_dact[k][r], v_act[r], v_out[r]);
     }
+    // all fp32 stores of the tile together, after its last load
+#pragma unroll
+    for (int r = 0; r < 4; ++r) d3_store(a, v_act[r], v_out[r], mt * TM + 16 * mi + 4 * (lane >> 4) + r, n, row_base);
   }
   if (!a.out3 && !a.out3T) return;
   __syncthreads();
@@ -373,13 +428,14 @@ struct D3Gru2 {
   int blocks0;   // blocks [0, blocks0) work on g0, the rest on g1 (the policy's two encoders)
   int rowmap;
 };
+static_assert(offsetof(D3Gru2, g0) == 0 && offsetof(D3Gru2, g1) == sizeof(D3Gru), "layout");
 template <int TRIP, int NPL>
 __global__ __launch_bounds__(512) void egx_gru3_kernel(D3Gru2 two) {
   // eight waves: waves 0-3 split the reduction of the x side (x W_ih^T), waves 4-7 that of the h side (h W_hh^T) - the two
   // products are independent, so their operand bursts are in flight together and a cell whose sides are each <= 4 TRIP
   // k-steps deep (the decoder cell: 8 + 8) is ONE memory round trip instead of two
   const bool second = (int)blockIdx.x >= two.blocks0;
-  const D3Gru& a = second ? two.g1 : two.g0;
+  const D3Gru a = d3_kernarg<D3Gru>(second ? 1 : 0);   // all fields in SGPRs from the start: no scalar load in the epilogue
   const int gru_bid = second ? (int)blockIdx.x - two.blocks0 : (int)blockIdx.x;
   extern __shared__ __attribute__((aligned(16))) float gsm[];
   float* red = gsm;                  // [8 waves][24][64]
@@ -389,19 +445,42 @@ __global__ __launch_bounds__(512) void egx_gru3_kernel(D3Gru2 two) {
   int mt, ct;
   if (!d3_tile(gru_bid, MT, CT, mt, ct, d3_rowmap(two.rowmap, a.M, 3 * a.H))) return;
   const int sd = wave >> 2, w4 = wave & 3;
+  // The element this lane finishes after the reduction - wave w takes position (mi, r) = (w >> 2, w & 3) of every lane - is
+  // known from the start, and so is everything its gate math reads from memory: gi_in and both biases of the three gates, and
+  // h_prev.  They are requested as ONE batch (ten loads in flight, one round trip) on a wait the kernel pays anyway: ahead of
+  // the k-loop, where they come back with the first operand burst, when the registers allow it (three planes: 1 workgroup per
+  // CU either way), else between the partial sums' LDS writes and the barrier (no register lives through the loop: the
+  // two-plane and one-plane kernels keep their 2 workgroups per CU).  Rows >= M load nothing.
+  constexpr bool EARLY = NPL == 3;
+  const int e_mi = wave >> 2, e_r = wave & 3;
+  const int e_col = lane & 15, e_c = ct * 16 + e_col;
+  const int e_row = 16 * e_mi + 4 * (lane >> 4) + e_r, e_m = mt * 32 + e_row;
+  float pre_gi[3] = {0.f, 0.f, 0.f}, pre_bi[3] = {0.f, 0.f, 0.f}, pre_bh[3] = {0.f, 0.f, 0.f}, pre_hp = 0.f;
+  auto prefetch = [&]() __attribute__((always_inline)) {
+    if (e_m >= a.M) return;
+#pragma unroll
+    for (int g = 0; g < 3; ++g) {
+      const int n = g * a.H + e_c;
+      if (a.gi_in) pre_gi[g] = d3_g(a.gi_in)[(size_t)e_m * 3 * a.H + n];
+      if (a.bias_i) pre_bi[g] = d3_g(a.bias_i)[n];
+      pre_bh[g] = d3_g(a.bias_h)[n];
+    }
+    if (a.h_prev) pre_hp = d3_g(a.h_prev)[(size_t)e_m * a.ldh + e_c];
+  };
+  if (EARLY) prefetch();
   f32x4 acc[2][3];   // [row half][gate] of this wave's side
 #pragma unroll
   for (int mi = 0; mi < 2; ++mi)
 #pragma unroll
     for (int g = 0; g < 3; ++g) acc[mi][g] = f32x4{0.f, 0.f, 0.f, 0.f};
   {
-    const bf16x8* A = sd ? a.Ah : a.Ai;
-    const bf16x8* B = sd ? a.Bh : a.Bi;
+    const D3_GLOBAL bf16x8* A = d3_g(sd ? a.Ah : a.Ai);
+    const D3_GLOBAL bf16x8* B = d3_g(sd ? a.Bh : a.Bi);
     const int S = A ? (sd ? a.Sh : a.Si) : 0, SA = sd ? a.SAh : a.SAi, sa0 = sd ? a.sah0 : a.sai0;
     const int per = (S + 3) >> 2;
     const int s_lo = w4 * per, s_hi = min(S, s_lo + per);
-    const bf16x8* pa[2];
-    const bf16x8* pb[3];
+    const D3_GLOBAL bf16x8* pa[2];
+    const D3_GLOBAL bf16x8* pb[3];
 #pragma unroll
     for (int mi = 0; mi < 2; ++mi) pa[mi] = A + ((size_t)(2 * mt + mi) * SA + sa0) * 3 * 64 + lane;
 #pragma unroll
@@ -436,12 +515,11 @@ __global__ __launch_bounds__(512) void egx_gru3_kernel(D3Gru2 two) {
     for (int mi = 0; mi < 2; ++mi)
 #pragma unroll
       for (int r = 0; r < 4; ++r) red[(wave * 24 + (g * 2 + mi) * 4 + r) * 64 + lane] = acc[mi][g][r];
+  if (!EARLY) prefetch();
   __syncthreads();
-  // wave w finishes position (mi, r) = (w >> 2, w & 3) of every lane: all six gate values of an element in one thread
+  // all six gate values of the lane's element in one thread; loads are all behind it, so the stores go out together at the end
   {
-    const int mi = wave >> 2, r = wave & 3;
-    const int col = lane & 15, c = ct * 16 + col;
-    const int row = 16 * mi + 4 * (lane >> 4) + r, m = mt * 32 + row;
+    const int mi = e_mi, r = e_r, col = e_col, c = e_c, row = e_row, m = e_m;
     float gv[2][3];
 #pragma unroll
     for (int s2 = 0; s2 < 2; ++s2)
@@ -456,18 +534,27 @@ __global__ __launch_bounds__(512) void egx_gru3_kernel(D3Gru2 two) {
       float gi[3], gh[3];
 #pragma unroll
       for (int g = 0; g < 3; ++g) {
-        const int n = g * a.H + c;
-        gi[g] = (a.gi_in ? a.gi_in[(size_t)m * 3 * a.H + n] : 0.f) + gv[0][g] + (a.bias_i ? a.bias_i[n] : 0.f);
-        gh[g] = gv[1][g] + a.bias_h[n];
-        if (a.gi_out) a.gi_out[(size_t)m * 3 * a.H + n] = gi[g];
-        if (a.gh_out) a.gh_out[(size_t)m * 3 * a.H + n] = gh[g];
+        gi[g] = pre_gi[g] + gv[0][g] + pre_bi[g];
+        gh[g] = gv[1][g] + pre_bh[g];
       }
       const float rg = 1.f / (1.f + expf(-(gi[0] + gh[0])));
       const float zg = 1.f / (1.f + expf(-(gi[1] + gh[1])));
       const float ng = tanhf(gi[2] + rg * gh[2]);
-      const float hp = a.h_prev ? a.h_prev[(size_t)m * a.ldh + c] : 0.f;
-      hv = (1.f - zg) * ng + zg * hp;
-      if (a.h_out) a.h_out[(size_t)m * a.ldo + c] = hv;
+      const float hp = pre_hp;
+      {
+        // both products rounded, then added: with h_prev already in a register the compiler would otherwise contract one of them
+        // into a fused multiply-add, and h would differ in its last bit from what this kernel has always computed
+#pragma clang fp contract(off)
+        const float keep = (1.f - zg) * ng, carry = zg * hp;
+        hv = keep + carry;
+      }
+#pragma unroll
+      for (int g = 0; g < 3; ++g) {
+        const int n = g * a.H + c;
+        if (a.gi_out) d3_g(a.gi_out)[(size_t)m * 3 * a.H + n] = gi[g];
+        if (a.gh_out) d3_g(a.gh_out)[(size_t)m * 3 * a.H + n] = gh[g];
+      }
+      if (a.h_out) d3_g(a.h_out)[(size_t)m * a.ldo + c] = hv;
     }
     tile[row * 20 + col] = hv;
   }
@@ -480,7 +567,7 @@ __global__ __launch_bounds__(512) void egx_gru3_kernel(D3Gru2 two) {
     for (int e = 0; e < 8; ++e) x[e] = tile[(8 * kg + e) * 20 + c];
     bf16x8 pl[NPL];
     d3_split<NPL>(x, pl);
-    bf16x8* o = a.h_out3T + ((size_t)((a.col0T >> 4) + ct) * a.S3T + a.s3T0 + mt) * 3 * 64 + lane;
+    D3_GLOBAL bf16x8* o = d3_g(a.h_out3T) + ((size_t)((a.col0T >> 4) + ct) * a.S3T + a.s3T0 + mt) * 3 * 64 + lane;
 #pragma unroll
     for (int p = 0; p < NPL; ++p) o[p * 64] = pl[p];
   }
@@ -492,7 +579,7 @@ __global__ __launch_bounds__(512) void egx_gru3_kernel(D3Gru2 two) {
       const float x[8] = {x0[0], x0[1], x0[2], x0[3], x1[0], x1[1], x1[2], x1[3]};
       bf16x8 pl[NPL];
       d3_split<NPL>(x, pl);
-      bf16x8* o = a.h_out3 + ((size_t)(2 * mt + wave) * a.S3 + a.s30 + (ct >> 1)) * 3 * 64 + 32 * (ct & 1) + lane;
+      D3_GLOBAL bf16x8* o = d3_g(a.h_out3) + ((size_t)(2 * mt + wave) * a.S3 + a.s30 + (ct >> 1)) * 3 * 64 + 32 * (ct & 1) + lane;
 #pragma unroll
       for (int p = 0; p < NPL; ++p) o[p * 64] = pl[p];
     }

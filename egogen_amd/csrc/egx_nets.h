@@ -77,6 +77,10 @@ void egx_launch_posenc3(hipStream_t st, const float* dist, const float* time, in
                         void* out3T = nullptr, int S3T = 0, int col0T = 0, float* zero6 = nullptr /* six floats cleared by the launch */);
 
 // One GRU cell step (gate order r, z, n; weights [3H, K] packed): see egx_gru3_kernel.
+// Aliasing contract: a buffer may be both an input and an output of one launch only ELEMENT FOR ELEMENT (gi_out == gi_in with
+// the same layout - the decoder's running sum -, h_out == h_prev with ldo == ldh).  The kernel reads everything an element
+// needs (gi_in, the biases, h_prev) before the reduction and stores the element's outputs after its last load, every element in
+// the one thread that owns it, so such a pair is safe; an output that overlaps OTHER elements of an input is not.
 struct D3Gru {
   const bf16x8* Ai = nullptr;   // x side
   int SAi = 0, sai0 = 0;
