@@ -1,0 +1,146 @@
+"""The rollout-side networks are fp32-equivalent: egx_policy_forward at precision 0, egx_sample_prior and egx_vposer_encode
+(three bf16 planes per operand, csrc/dense3.hip) are at most R = 3 times as far from the float64 oracle as the float32 oracle
+is, plus one ulp of the stored result, per output group (tests/precision_yardstick.py).  The north-star tolerances of the other
+tests of these entry points (1e-4, 2e-4, 2e-5 relative) would let a two-plane kernel through on every output but the regressed
+rotations; this bound does not: test_fp32_yardstick_cpu.py shows it on the CPU for the very inputs used here, and
+test_policy_two_planes_miss_the_bound on the device.
+
+Every test prints max|hip - f64| per group next to its ratio to max|f32 - f64|; EGX_F32_TABLE=<file> appends the tables to a file
+(committed as profiles/fp32_equivalence.md)."""
+import pytest
+import torch
+
+from tests import precision_yardstick as py
+
+pytestmark = pytest.mark.gpu
+
+
+def _assert_within(case, err, what):
+    for g, e in err.items():
+        assert e <= case.bound(g), (what, g, e, case.bound(g), e / case.err32[g])
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# egx_policy_forward
+# ---------------------------------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def policy():
+    from egogen_amd.models import ActorCritic, GAMMAActor, GAMMACritic, GAMMAPolicyBase, POLICY_CFG, PolicyHipRunner
+    case = py.policy_case()
+    ac = ActorCritic(GAMMAActor(POLICY_CFG), GAMMACritic(POLICY_CFG), GAMMAPolicyBase(POLICY_CFG))
+    ac.load_state_dict(case.sd, strict=True)
+    ac.cuda()
+    run = PolicyHipRunner(ac.shared_net, ac.actor, ac.critic)
+    obs = {k: v.cuda() for k, v in case.inputs[0].items()}
+
+    def call(n=py.POLICY_N, actor=True, critic=True):
+        out = run.forward({k: v[:n].contiguous() for k, v in obs.items()}, want_actor=actor, want_critic=critic)
+        torch.cuda.synchronize()
+        return {k: v.clone() for k, v in out.items()}
+
+    return case, call
+
+
+def test_policy_prec0_is_fp32_equivalent(policy):
+    """n = 33: two full row tiles and a ragged one; actor and critic together (the triple launches)."""
+    from egogen_amd import _lib
+    case, call = policy
+    assert _lib.load().egx_policy_get_precision() == 0
+    err = case.error(call())
+    py.emit(py.table(case, "egx_policy_forward, prec 0, n = 33, actor + critic (MI355X)", {"hip": err}))
+    assert set(err) == {"mu", "logvar", "value"}
+    _assert_within(case, err, "policy prec 0")
+
+
+def test_policy_two_planes_miss_the_bound(policy):
+    """The control on the device: the same call in the two-plane arithmetic (prec 2) is outside the bound on every output, and
+    switching back gives the bits of the first call."""
+    from egogen_amd import _lib
+    lib = _lib.load()
+    case, call = policy
+    first = call()
+    try:
+        _lib.check(lib.egx_policy_set_precision(2), "egx_policy_set_precision")
+        two = call()
+    finally:
+        _lib.check(lib.egx_policy_set_precision(0), "egx_policy_set_precision")
+    again = call()
+    err = case.error(two)
+    py.emit(py.table(case, "egx_policy_forward, prec 2 (two planes: the control), n = 33 (MI355X)", {"hip prec 2": err}))
+    for g in ("mu", "logvar", "value"):
+        assert err[g] > case.bound(g), (g, err[g], case.bound(g))
+        assert torch.equal(again[g], first[g]), g
+
+
+@pytest.mark.parametrize("n,actor,critic", [(1, True, True), (1, True, False), (33, True, False), (33, False, True)])
+def test_policy_prec0_other_launch_shapes(policy, n, actor, critic):
+    """One observation, and one head only (the pair and single launches instead of the triple): the same bound against the same
+    rows of the same oracle."""
+    case, call = policy
+    out = call(n, actor, critic)
+    assert set(out) == ({"mu", "logvar"} if actor else set()) | ({"value"} if critic else set())
+    err = case.error(out, rows=lambda g, ref: ref[:n])
+    py.emit(py.table(case, f"egx_policy_forward, prec 0, n = {n}, actor {actor}, critic {critic} (MI355X)", {"hip": err}))
+    _assert_within(case, err, f"policy prec 0 n={n} actor={actor} critic={critic}")
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# egx_sample_prior (no precision switch: always three planes)
+# ---------------------------------------------------------------------------------------------------------------------------
+def test_sample_prior_is_fp32_equivalent():
+    """A = 33: the C-VAE decoder's 18 steps and the fused regressor; markers, translation, rotations (as matrices), hands."""
+    from egogen_amd.models import GAMMAPrimitiveCombo, PREDICTOR_CFG, REGRESSOR_CFG
+    case = py.prior_case()
+    combo = GAMMAPrimitiveCombo(PREDICTOR_CFG, REGRESSOR_CFG)
+    combo.load_state_dict(case.sd, strict=True)
+    combo.cuda()
+    X, betas, z = (t.cuda() for t in case.inputs)
+    Y, Yb = combo.sample_prior(X, betas, z)
+    torch.cuda.synchronize()
+    assert Y.shape == (18, py.PRIOR_A, 201) and Yb.shape == (18, py.PRIOR_A, 93)
+    err = case.error(py.prior_groups(Y, Yb))
+    py.emit(py.table(case, "egx_sample_prior, A = 33 (MI355X)", {"hip": err}))
+    assert set(err) == {"Y", "transl", "rot", "hands"}
+    _assert_within(case, err, "sample_prior")
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# egx_vposer_encode (no precision switch), with the BN-folded weights of VPoserEncoder.fold
+# ---------------------------------------------------------------------------------------------------------------------------
+def test_vposer_encode_is_fp32_equivalent():
+    from egogen_amd.models import VPoserEncoder
+    case = py.vposer_case()
+    enc = VPoserEncoder().eval()
+    enc.load_state_dict(case.sd)
+    enc.cuda()
+    out = enc.encode_mean(case.inputs[0].cuda())
+    torch.cuda.synchronize()
+    err = case.error({"mean": out})
+    py.emit(py.table(case, "egx_vposer_encode, n = 100 (MI355X)", {"hip": err}))
+    _assert_within(case, err, "vposer_encode")
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# egx_gemm3: the split into planes on operands far from 1
+# ---------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("trans_a", [False, True])
+def test_gemm3_identity_returns_operand_over_40_decades(trans_a):
+    """A . I = A to within one fp32 ulp of every element, for magnitudes 1e-20 ... 1e20 with mixed signs, zeros and a -0.0 mixed
+    within every row (M = 37, K = N = 64).  Three bf16 planes hold the 24 bits of an fp32 number at any exponent; a plane lost,
+    flushed or scaled shows as a relative error of 2^-16 or more."""
+    from egogen_amd.fused_ops import gemm3
+    M, K = 37, 64
+    g = torch.Generator().manual_seed(37)
+    mag = torch.logspace(-20, 20, M * K)[torch.randperm(M * K, generator=g)]
+    A = ((torch.rand(M * K, generator=g) + 1.0) * mag * (torch.randint(0, 2, (M * K,), generator=g) * 2 - 1).float()).reshape(M, K)
+    A[::5, ::7] = 0.0
+    A[3, 3] = -0.0
+    assert bool(torch.isfinite(A).all()) and float(A.abs().max()) > 1e19 and float(A[A != 0].abs().min()) < 1e-19
+    Ad = A.t().contiguous().cuda() if trans_a else A.cuda()
+    out = gemm3(Ad, trans_a, torch.eye(K).cuda(), False).cpu()
+    ulp = torch.nextafter(A.abs(), torch.full_like(A, float("inf"))) - A.abs()
+    ulp[A == 0] = 0.0
+    diff = (out.double() - A.double()).abs()
+    worst = float((diff / ulp.double().clamp_min(1e-300)).max())
+    print(f"gemm3 identity, trans_a {trans_a}: worst error {worst:.2f} ulp")
+    assert bool((diff <= ulp.double()).all()), worst
