@@ -245,6 +245,107 @@ class BodyModelHandle:
         return out
 
 
+class _PointsFn(torch.autograd.Function):
+    """points (and joints55) of a `BodyPoints` as one autograd node: `egx_points_forward` / `egx_points_backward`.  xb and betas
+    arrive as contiguous fp32 device tensors; the backward recomputes the forward from them, so only they are saved."""
+
+    @staticmethod
+    def forward(ctx, xb, betas, owner, fpa, want_joints):
+        lib = _lib.load()
+        B = int(xb.shape[0])
+        points = torch.empty(B, owner.P, 3, dtype=torch.float32, device=xb.device)
+        joints = torch.empty(B, 55, 3, dtype=torch.float32, device=xb.device) if want_joints else None
+        _lib.check(lib.egx_points_forward(owner.handle, _lib.ptr(xb), _lib.ptr(betas), B, fpa, _lib.ptr(points), _lib.ptr(joints),
+                                          _lib.current_stream_ptr()), "egx_points_forward")
+        ctx.save_for_backward(xb, betas)
+        ctx.owner, ctx.fpa = owner, fpa
+        ctx.set_materialize_grads(False)
+        return (points, joints) if want_joints else points
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_points, g_joints=None):
+        xb, betas = ctx.saved_tensors
+        if g_points is None and g_joints is None:
+            return None, None, None, None, None
+        lib = _lib.load()
+        B, A = int(xb.shape[0]), int(betas.shape[0])
+        prep = lambda g: None if g is None else g.to(dtype=torch.float32).contiguous()
+        g_points, g_joints = prep(g_points), prep(g_joints)
+        g_xb = torch.empty(B, 93, dtype=torch.float32, device=xb.device)
+        g_bb = torch.empty(B, 10, dtype=torch.float32, device=xb.device)
+        _lib.check(lib.egx_points_backward(ctx.owner.handle, _lib.ptr(xb), _lib.ptr(betas), B, ctx.fpa, _lib.ptr(g_points),
+                                           _lib.ptr(g_joints), _lib.ptr(g_xb), _lib.ptr(g_bb), _lib.current_stream_ptr()),
+                   "egx_points_backward")
+        g_betas = None
+        if ctx.needs_input_grad[1]:
+            g_betas = g_bb if ctx.fpa == 1 else g_bb.view(A, ctx.fpa, 10).sum(1)   # the frames of an agent share its shape
+        return (g_xb if ctx.needs_input_grad[0] else None), g_betas, None, None, None
+
+
+class BodyPoints:
+    """Differentiable rows of the body model: `bm(return_verts=True, **bparam).vertices[:, vids]` (models/baseops.py:382) and the
+    55 kinematic-tree joints, with `loss.backward()` reaching xb and betas (the gradient models_GAMMA_primitive.py:617-633 takes
+    through the body).  Forward and backward are one fused HIP kernel each (`egx_points_forward` / `egx_points_backward`);
+    1 <= len(vids) <= 1024, ids may repeat.  There is no CPU fallback."""
+
+    def __init__(self, bm: Dict[str, np.ndarray], vids):
+        lib = _lib.load()
+        if not torch.cuda.is_available():
+            raise _lib.EgxError("no HIP device visible - the body points operator has no CPU fallback")
+        vids = np.asarray(vids)
+        if vids.ndim != 1 or vids.size == 0:
+            raise ValueError(f"vids must be a non-empty list of vertex ids, got shape {vids.shape}")
+        keep = {k: _as_f32(bm[k]) for k in ("v_template", "shapedirs", "posedirs", "J_regressor", "lbs_weights",
+                                            "hand_comps_l", "hand_comps_r", "hand_mean_l", "hand_mean_r")}
+        keep["parents"] = _as_i32(bm["parents"])
+        keep["vids"] = _as_i32(vids)
+        d = _lib.BodyModelHost()
+        d.num_verts = int(keep["v_template"].shape[0])
+        if keep["shapedirs"].shape != (d.num_verts, 3, 10) or keep["posedirs"].shape != (486, 3 * d.num_verts) or \
+                keep["J_regressor"].shape != (55, d.num_verts) or keep["lbs_weights"].shape != (d.num_verts, 55):
+            raise ValueError("body model arrays do not have the SMPL-X shapes")
+        for f, key in (("v_template_host", "v_template"), ("shapedirs_host", "shapedirs"), ("posedirs_host", "posedirs"),
+                       ("J_regressor_host", "J_regressor"), ("parents_host", "parents"), ("lbs_weights_host", "lbs_weights"),
+                       ("hand_comps_l_host", "hand_comps_l"), ("hand_comps_r_host", "hand_comps_r"),
+                       ("hand_mean_l_host", "hand_mean_l"), ("hand_mean_r_host", "hand_mean_r")):
+            setattr(d, f, keep[key].ctypes.data)
+        h = C.c_void_p()
+        _lib.check(lib.egx_point_set_create(C.byref(d), keep["vids"].ctypes.data, int(keep["vids"].shape[0]), C.byref(h)),
+                   "egx_point_set_create")
+        self.handle = h
+        self.device = torch.cuda.current_device()     # the tables live on the device that was current here
+        self.V = d.num_verts
+        self.P = int(lib.egx_point_set_size(h))
+        self.vids = [int(v) for v in keep["vids"]]
+
+    def __del__(self):
+        h = getattr(self, "handle", None)
+        if h:
+            try:
+                _lib.load().egx_point_set_destroy(h)
+            except Exception:
+                pass
+            self.handle = None
+
+    def __call__(self, xb: torch.Tensor, betas: torch.Tensor, frames_per_agent: int = 1, want_joints: bool = False):
+        """xb[B,93], betas[A,10] (A * frames_per_agent == B) -> points[B,P,3], or (points, joints55[B,55,3]).  Differentiable in
+        xb and betas when they require grad; runs on the current stream and never synchronises with the host."""
+        fpa = int(frames_per_agent)
+        if xb.dim() != 2 or xb.shape[1] != 93 or xb.shape[0] == 0:
+            raise ValueError(f"xb must be a non-empty [B,93], got {tuple(xb.shape)}")
+        B = int(xb.shape[0])
+        if betas.dim() != 2 or betas.shape[1] != 10 or fpa < 1 or int(betas.shape[0]) * fpa != B:
+            raise ValueError(f"betas must be [B/frames_per_agent,10]; got {tuple(betas.shape)} for B={B}, fpa={frames_per_agent}")
+        if not xb.is_cuda or betas.device != xb.device:
+            raise _lib.EgxError("xb and betas must be on the same HIP device - the body points operator has no CPU fallback")
+        if xb.device.index != self.device or torch.cuda.current_device() != self.device:
+            raise _lib.EgxError(f"this point set was built on device {self.device}; inputs and the current device must be that one")
+        xb = xb.to(dtype=torch.float32).contiguous()
+        betas = betas.to(dtype=torch.float32).contiguous()
+        return _PointsFn.apply(xb, betas, self, fpa, bool(want_joints))
+
+
 class SMPLXOutput:
     """What `bm(return_verts=True, ...)` returns in the reference (fields used on this path)."""
 

@@ -190,6 +190,22 @@ class MarkerBodyModel(torch.nn.Module):
         return _mv3(TR, v_posed) + Tt + xb[:, None, :3]
 
 
+class HipMarkerBodyModel(torch.nn.Module):
+    """The call signature of `MarkerBodyModel`, (xb[n,93], betas[n,10]) -> markers[n,m,3], over `BodyPoints`: forward and backward
+    are one fused HIP kernel each (`egx_points_forward` / `egx_points_backward`) instead of a chain of torch ops."""
+
+    def __init__(self, bm: Dict[str, np.ndarray], marker_vids):
+        super().__init__()
+        from .body_model import BodyPoints
+        self.points = BodyPoints(bm, marker_vids)
+
+    def forward(self, xb: torch.Tensor, betas: torch.Tensor) -> torch.Tensor:
+        return self.points(xb, betas)
+
+
+MARKER_BODY_MODELS = {"torch": MarkerBodyModel, "hip": HipMarkerBodyModel}
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # the train operator
 # ---------------------------------------------------------------------------------------------------------------------
@@ -228,7 +244,8 @@ class GAMMARegressorTrainOP:
 
     def build_model(self, body_model: Optional[Dict[str, np.ndarray]] = None, markers=None):
         """:595-613.  `body_model` / `markers`: the SMPL-X tensors and SSM2 vertex ids; by default the ones the rest of the
-        package uses (setup_world.load_body_model: the real SMPLX_<GENDER>.npz when present, else the synthetic body)."""
+        package uses (setup_world.load_body_model: the real SMPLX_<GENDER>.npz when present, else the synthetic body).
+        trainconfig["marker_body_model"]: "torch" (default, `MarkerBodyModel`) or "hip" (`HipMarkerBodyModel`)."""
         if self.modelconfig["body_repr"] != "ssm2_67":
             raise ValueError("other marker placement is not considered yet.")
         self.model = MoshRegressorTrain(self.modelconfig).to(self.device)
@@ -242,7 +259,11 @@ class GAMMARegressorTrainOP:
         if markers is None:
             markers = synth.marker_ids(body_model["v_template"].shape[0])
         self.markers = self.model.markers = [int(v) for v in markers]
-        self.bm = MarkerBodyModel(body_model, self.markers).to(self.device)
+        kind = self.trainconfig.get("marker_body_model", "torch")
+        if kind not in MARKER_BODY_MODELS:
+            raise ValueError(f"trainconfig['marker_body_model'] must be one of {sorted(MARKER_BODY_MODELS)}, got {kind!r}")
+        with torch.cuda.device(self.device):          # the fused model's tables are allocated on the current device
+            self.bm = MARKER_BODY_MODELS[kind](body_model, self.markers).to(self.device)
 
     def calc_loss(self, x_ref, xb, betas):
         """:617-633: x_ref[n,67,3], xb[n,93] (axis-angle rotations), betas[n,10]."""

@@ -47,6 +47,8 @@ if __name__ == "__main__":
     traincfg["resume_training"] = args.resume_training == 1
     traincfg["verbose"] = args.verbose == 1
     traincfg["gpu_index"] = args.gpu_index
+    if "marker_body_model" in cfg["trainconfig"]:      # "torch" | "hip": how calc_loss evaluates the marker rows of the body
+        traincfg["marker_body_model"] = str(cfg["trainconfig"]["marker_body_model"])
     batch_gen = BatchGeneratorAMASSCanonicalized(amass_data_path=traincfg["dataset_path"], amass_subset_name=traincfg.get("subsets"),
                                                  sample_rate=int(traincfg.get("sample_rate", 3)), body_repr=modelcfg["body_repr"],
                                                  read_to_ram=False)

@@ -180,6 +180,32 @@ int egx_lbs_forward(const egx_body_model* m, const float* xb, const float* betas
                     void* workspace, size_t workspace_bytes, void* stream);
 
 /*
+ * Differentiable points - the rows of the body model at a list of vertex ids plus the 55 kinematic-tree joints, forward and
+ * reverse mode: what `bm(return_verts=True, **bparam)` (models/baseops.py:382) gives under torch autograd, the gradient the
+ * regressor's loss takes through the body (models_GAMMA_primitive.py:617-633).
+ *
+ * egx_point_set_create (models/baseops.py:382, models_GAMMA_primitive.py:617-633) gathers, once, the tables of num_points
+ *   (1..1024) vertex ids from the host description egx_body_model_create takes; ids may repeat (their gradients add, as in
+ *   `verts[:, vids]`); an id outside [0, V) or a count outside the range fails.  The joint regressor is folded into the
+ *   template and the shape directions in float64.  destroy frees the device tables; size returns num_points.
+ * egx_points_forward (models/baseops.py:382): out_points [B,P,3] = vertices[:, vids], out_joints55 [B,55,3] or NULL =
+ *   joints[:, :55]; translation included, jaw and eyes at rest, betas [B / frames_per_agent, 10].
+ * egx_points_backward (models_GAMMA_primitive.py:617-633 `loss.backward()`): grad_points [B,P,3] and grad_joints55 [B,55,3]
+ *   (either may be NULL, not both) -> grad_xb [B,93], grad_betas_body [B,10] (one row per body; the caller sums the
+ *   frames_per_agent rows of an agent).  It recomputes the forward from xb / betas: nothing is saved, there is no workspace, and
+ *   no atomics are used, so the result is bit-reproducible.  batch_rodrigues [upstream smplx 0.1.28] is differentiated as
+ *   written (angle = |r + 1e-8|), which is finite at the rest pose.
+ */
+typedef struct egx_point_set egx_point_set; /* opaque */
+int egx_point_set_create(const egx_body_model_host* desc, const int32_t* vids_host, int num_points, egx_point_set** out);
+void egx_point_set_destroy(egx_point_set* set);
+int egx_point_set_size(const egx_point_set* set);
+int egx_points_forward(const egx_point_set* set, const float* xb, const float* betas, int num_bodies, int frames_per_agent,
+                       float* out_points, float* out_joints55, void* stream);
+int egx_points_backward(const egx_point_set* set, const float* xb, const float* betas, int num_bodies, int frames_per_agent,
+                        const float* grad_points, const float* grad_joints55, float* grad_xb, float* grad_betas_body, void* stream);
+
+/*
  * SDF scene sets - one penetration-count launch over bodies in DIFFERENT scenes (no reference counterpart: crowd_env_2f.py trains
  * in one scene per process).  egx_sdf_scene_set_create copies, once, a device table of S records {grid, bracket table, center,
  * scale, steepest slope} from S descriptors, each with its bracket table (egx_sdf_build_coarse) and all with the same d0, d1, d2 -
