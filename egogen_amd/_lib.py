@@ -82,6 +82,13 @@ class PolicyGrads(C.Structure):
                 ("critic_w", C.c_void_p * 4), ("critic_b", C.c_void_p * 4), ("critic_out_w", C.c_void_p), ("critic_out_b", C.c_void_p)]
 
 
+class UpdateHead(C.Structure):
+    _fields_ = [("perm", C.c_void_p), ("cursor", C.c_void_p), ("max_cursor", C.c_int), ("num_src_rows", C.c_int)] + \
+               [(n, C.c_void_p) for n in ("state", "egosensing", "dist", "time", "act", "adv", "ret", "logp_old",
+                                          "act_c", "adv_c", "ret_c", "logp_old_c", "stats")] + \
+               [("compute_stats", C.c_int), ("log", C.c_void_p)]
+
+
 class VposerWeights(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("fc1_w", "fc1_b", "fc2_w", "fc2_b", "mu_w", "mu_b", "fc1_w3", "fc2_w3", "mu_w3")]
 
@@ -217,6 +224,11 @@ SIGNATURES = {
     "egx_policy_train_step_heads": (C.c_int, [C.c_void_p] * 9 + [C.c_float] * 6 + [C.c_void_p, C.c_void_p]),
     "egx_policy_train_step_encoders": (C.c_int, [C.c_void_p, C.c_void_p]),
     "egx_policy_train_set_precision": (C.c_int, [C.c_void_p, C.c_int]),
+    "egx_policy_train_head": (C.c_int, [C.c_void_p, C.POINTER(UpdateHead), C.c_void_p]),
+    "egx_policy_train_step_cursor": (C.c_int, [C.c_void_p, C.POINTER(UpdateHead), C.c_void_p] + [C.c_float] * 6 + [C.c_void_p]),
+    "egx_policy_train_step_heads_cursor": (C.c_int, [C.c_void_p, C.POINTER(UpdateHead), C.c_void_p] + [C.c_float] * 6 + [C.c_void_p]),
+    "egx_adamw_clip_step_cursor": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_float] +
+                                   [C.c_double] * 5 + [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "egx_pack3_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "egx_pack3": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "egx_gemm3_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),

@@ -594,53 +594,8 @@ __global__ __launch_bounds__(256) void egx_posenc3_kernel(const float* __restric
   // (the update chain's loss kernel accumulates six sums with atomics: cleared here, several launches ahead of it, instead of
   // by a launch of their own)
   if (zero6 && blockIdx.x == 0 && threadIdx.x < 6) zero6[threadIdx.x] = 0.f;
-  int frag = blockIdx.x * 4 + (threadIdx.x >> 6);
-  const int lane = threadIdx.x & 63;
-  const int RT = 2 * ((n + 31) >> 5);
-  if (frag >= RT * 4) {
-    // training: the same 128 columns as rows col0T .. col0T + 127 of the transposed image (reduction index = batch row)
-    frag -= RT * 4;
-    const int Sn = (n + 31) >> 5;
-    if (!out3T || frag >= 8 * Sn) return;
-    const int t = frag / Sn, s = frag % Sn;
-    const int c = 16 * t + (lane & 15), m0 = 32 * s + 8 * (lane >> 4);
-    float x[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      const int m = m0 + e;
-      float v = 0.f;
-      if (m < n) {
-        const float f = ((c < 64) ? dist[m] : time[m]) * exp2f((float)((c & 63) >> 1));
-        v = (c & 1) ? cosf(f) : sinf(f);
-      }
-      x[e] = v;
-    }
-    bf16x8 pl[3];
-    d3_split(x, pl);
-    bf16x8* o = out3T + ((size_t)((col0T >> 4) + t) * S3T + s) * 3 * 64 + lane;
-#pragma unroll
-    for (int p = 0; p < 3; ++p) o[p * 64] = pl[p];
-    return;
-  }
-  const int rt = frag >> 2, s = frag & 3;
-  const int row = rt * 16 + (lane & 15), c0 = s * 32 + 8 * (lane >> 4);
-  float x[8];
-#pragma unroll
-  for (int e = 0; e < 8; ++e) {
-    const int c = c0 + e;
-    float v = 0.f;
-    if (row < n) {
-      const float f = ((c < 64) ? dist[row] : time[row]) * exp2f((float)((c & 63) >> 1));
-      v = (c & 1) ? cosf(f) : sinf(f);
-      out[(size_t)row * ld + c] = v;
-    }
-    x[e] = v;
-  }
-  bf16x8 pl[3];
-  d3_split(x, pl);
-  bf16x8* o = out3 + ((size_t)rt * S3 + s0 + s) * 3 * 64 + lane;
-#pragma unroll
-  for (int p = 0; p < 3; ++p) o[p * 64] = pl[p];
+  egx_posenc3_role(dist, time, n, out, ld, out3, S3, s0, out3T, S3T, col0T, (int)blockIdx.x, EgxRowsIdentity(),
+                   [](const float (&x)[8], bf16x8 (&pl)[3]) { d3_split(x, pl); });   // the body: egx_nets.h
 }
 void egx_launch_posenc3(hipStream_t st, const float* dist, const float* time, int n, float* out, int ld, void* out3, int S3, int s0,
                         void* out3T, int S3T, int col0T, float* zero6) {

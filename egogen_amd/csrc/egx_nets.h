@@ -72,9 +72,116 @@ void egx_launch_dense3_triple(hipStream_t st, const D3Plain& p, const D3Plain& q
 int egx_ppo_loss_packed_precleared(const float* zp, const float* value, const float* act, const float* adv, const float* ret,
                                    const float* logp_old, const float* adv_stats, const float* scale, float adv_eps, float min_logvar,
                                    float max_logvar, float eps_clip, float vf_coef, float ent_coef, int num_rows, float* g_zp,
-                                   float* g_value, float* out_terms, void* stream_);
+                                   float* g_value, float* out_terms, void* stream_, const int* cursor = nullptr, int max_cursor = 0);
+// (cursor != null: the sums go to row min(*cursor, max_cursor) of out_terms, six floats a row - the update's per-epoch log)
 void egx_launch_posenc3(hipStream_t st, const float* dist, const float* time, int n, float* out, int ld, void* out3, int S3, int s0,
                         void* out3T = nullptr, int S3T = 0, int col0T = 0, float* zero6 = nullptr /* six floats cleared by the launch */);
+
+// ---- roles shared by the update's stand-alone kernels (egx_pack3_table_kernel, egx_posenc3_kernel, egx_adv_stats_kernel) and by
+// egx_update_head_kernel (update3.hip), which runs them on GATHERED rows in one launch.  One body per role, parameterised on the
+// row map, so that the two forms cannot drift apart (EGX_UPDATE_HEAD=0 / 1 are held to bit equality).
+#if defined(__HIPCC__)
+struct EgxRowsIdentity {   // source row of row r: r
+  __device__ __forceinline__ size_t operator()(int r) const { return (size_t)r; }
+};
+struct EgxRowsGathered {   // row idx[r] of the rollout, clamped to its rows: a bad index reads a wrong row, never another allocation
+  const long long* __restrict__ idx;
+  int num_src;
+  __device__ __forceinline__ size_t operator()(int r) const {
+    const long long s = idx[r];
+    return (size_t)min(max(s, 0LL), (long long)num_src - 1);
+  }
+};
+
+// positional_encoding (models_policy_ppo.py:276-285) of dist and time, work of block `bid` (four fragments): the 128 columns as
+// fp32 into `out` (row stride ld) and packed into k-steps s0 .. s0 + 3 of `out3`; blocks past those, with out3T != null: the same
+// columns as rows col0T .. col0T + 127 of the transposed image (reduction index = batch row).  `split`: x[8] -> three bf16 planes.
+template <class Rows, class Split>
+__device__ __forceinline__ void egx_posenc3_role(const float* __restrict__ dist, const float* __restrict__ time, int n,
+                                                 float* __restrict__ out, int ld, bf16x8* __restrict__ out3, int S3, int s0,
+                                                 bf16x8* __restrict__ out3T, int S3T, int col0T, int bid, const Rows& rows,
+                                                 const Split& split) {
+  int frag = bid * 4 + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  const int RT = 2 * ((n + 31) >> 5);
+  if (frag >= RT * 4) {
+    frag -= RT * 4;
+    const int Sn = (n + 31) >> 5;
+    if (!out3T || frag >= 8 * Sn) return;
+    const int t = frag / Sn, s = frag % Sn;
+    const int c = 16 * t + (lane & 15), m0 = 32 * s + 8 * (lane >> 4);
+    float x[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const int m = m0 + e;
+      float v = 0.f;
+      if (m < n) {
+        const size_t sm = rows(m);
+        const float f = ((c < 64) ? dist[sm] : time[sm]) * exp2f((float)((c & 63) >> 1));
+        v = (c & 1) ? cosf(f) : sinf(f);
+      }
+      x[e] = v;
+    }
+    bf16x8 pl[3];
+    split(x, pl);
+    bf16x8* o = out3T + ((size_t)((col0T >> 4) + t) * S3T + s) * 3 * 64 + lane;
+#pragma unroll
+    for (int p = 0; p < 3; ++p) o[p * 64] = pl[p];
+    return;
+  }
+  const int rt = frag >> 2, s = frag & 3;
+  const int row = rt * 16 + (lane & 15), c0 = s * 32 + 8 * (lane >> 4);
+  const size_t srow = row < n ? rows(row) : 0;
+  float x[8];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    const int c = c0 + e;
+    float v = 0.f;
+    if (row < n) {
+      const float f = ((c < 64) ? dist[srow] : time[srow]) * exp2f((float)((c & 63) >> 1));
+      v = (c & 1) ? cosf(f) : sinf(f);
+      out[(size_t)row * ld + c] = v;
+    }
+    x[e] = v;
+  }
+  bf16x8 pl[3];
+  split(x, pl);
+  bf16x8* o = out3 + ((size_t)rt * S3 + s0 + s) * 3 * 64 + lane;
+#pragma unroll
+  for (int p = 0; p < 3; ++p) o[p * 64] = pl[p];
+}
+
+// mean and UNBIASED standard deviation of the minibatch advantages (ppo_policy.py:195-197: adv.mean(), adv.std()); one
+// workgroup of 256 threads, two-pass variance, double accumulation in a fixed order
+template <class Rows>
+__device__ __forceinline__ void egx_adv_stats_role(const float* __restrict__ adv, int n, float* __restrict__ out, const Rows& rows) {
+  __shared__ double red[256];
+  __shared__ double s_mean;
+  double a = 0.0;
+  for (int i = threadIdx.x; i < n; i += 256) a += adv[rows(i)];
+  red[threadIdx.x] = a;
+  __syncthreads();
+  for (int st = 128; st > 0; st >>= 1) {
+    if (threadIdx.x < st) red[threadIdx.x] += red[threadIdx.x + st];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) s_mean = red[0] / n;
+  __syncthreads();
+  const double mean = s_mean;
+  double b = 0.0;  // second pass around the mean (two-pass variance)
+  for (int i = threadIdx.x; i < n; i += 256) { const double d = adv[rows(i)] - mean; b += d * d; }
+  red[threadIdx.x] = b;
+  __syncthreads();
+  for (int st = 128; st > 0; st >>= 1) {
+    if (threadIdx.x < st) red[threadIdx.x] += red[threadIdx.x + st];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    out[0] = (float)mean;
+    out[1] = (n > 1) ? (float)sqrt(red[0] / (n - 1)) : nanf("");
+  }
+}
+#endif
 
 // One GRU cell step (gate order r, z, n; weights [3H, K] packed): see egx_gru3_kernel.
 // Aliasing contract: a buffer may be both an input and an output of one launch only ELEMENT FOR ELEMENT (gi_out == gi_in with

@@ -2,7 +2,7 @@
 // policy's two encoders, so that the autograd graph of one minibatch is ~40 kernels instead of ~300 tiny elementwise ones.
 #include <algorithm>
 #include <cstring>
-#include "egx_common.h"
+#include "egx_nets.h"
 
 namespace {
 constexpr float LOG_SQRT_2PI = 0.91893853320467274178f;
@@ -26,8 +26,10 @@ __global__ __launch_bounds__(256) void egx_ppo_loss_kernel(const float* __restri
                                                           float max_lv, float eps_clip, float vf_coef, float ent_coef, int n,
                                                           int stride /* row pitch of mu, logvar, g_mu, g_logvar */,
                                                           float* __restrict__ g_mu, float* __restrict__ g_logvar,
-                                                          float* __restrict__ g_value, float* __restrict__ out_terms) {
+                                                          float* __restrict__ g_value, float* __restrict__ out_terms,
+                                                          const int* __restrict__ cursor, int max_cursor) {
   __shared__ float sh[4][6];
+  if (cursor) out_terms += 6 * (size_t)min(max(*cursor, 0), max_cursor);   // row of the update's per-epoch log (update3.hip)
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const float scale = scale_ptr[0];
   float acc[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
@@ -184,31 +186,7 @@ __global__ __launch_bounds__(256) void egx_gather_rows_kernel(GatherArgs a) {
 
 // mean and UNBIASED standard deviation of the minibatch advantages (ppo_policy.py:195-197: adv.mean(), adv.std())
 __global__ __launch_bounds__(256) void egx_adv_stats_kernel(const float* __restrict__ adv, int n, float* __restrict__ out) {
-  __shared__ double red[256];
-  __shared__ double s_mean;
-  double a = 0.0;
-  for (int i = threadIdx.x; i < n; i += 256) a += adv[i];
-  red[threadIdx.x] = a;
-  __syncthreads();
-  for (int st = 128; st > 0; st >>= 1) {
-    if (threadIdx.x < st) red[threadIdx.x] += red[threadIdx.x + st];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) s_mean = red[0] / n;
-  __syncthreads();
-  const double mean = s_mean;
-  double b = 0.0;  // second pass around the mean (two-pass variance)
-  for (int i = threadIdx.x; i < n; i += 256) { const double d = adv[i] - mean; b += d * d; }
-  red[threadIdx.x] = b;
-  __syncthreads();
-  for (int st = 128; st > 0; st >>= 1) {
-    if (threadIdx.x < st) red[threadIdx.x] += red[threadIdx.x + st];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) {
-    out[0] = (float)mean;
-    out[1] = (n > 1) ? (float)sqrt(red[0] / (n - 1)) : nanf("");
-  }
+  egx_adv_stats_role(adv, n, out, EgxRowsIdentity());   // the body: egx_nets.h (shared with egx_update_head_kernel)
 }
 
 // episode bookkeeping of the collector (tianshou Collector.collect [upstream]: running return / length per env, sums over
@@ -309,7 +287,8 @@ __global__ __launch_bounds__(256) void egx_sumsq_partial_kernel(const float* __r
 // pass 1b (one workgroup): total norm -> clip coefficient; bias corrections of the new step count
 __global__ __launch_bounds__(256) void egx_adamw_consts_kernel(const float* __restrict__ partials, int n_partials, int do_clip,
                                                                float max_norm, double lr, double b1, double b2,
-                                                               const float* __restrict__ step, float* __restrict__ consts) {
+                                                               const float* __restrict__ step, float* __restrict__ consts,
+                                                               int* __restrict__ cursor) {
   __shared__ double red[256];
   double a = 0.0;
   for (int i = threadIdx.x; i < n_partials; i += 256) a += partials[i];
@@ -327,6 +306,9 @@ __global__ __launch_bounds__(256) void egx_adamw_consts_kernel(const float* __re
     consts[0] = coef;
     consts[1] = (float)(lr / bc1);
     consts[2] = sqrtf(bc2);
+    // the update's minibatch cursor (update3.hip): advanced HERE, by a single-block launch that runs after every reader of
+    // this minibatch (head launch, loss kernel) and before the next one's, never by a block of a launch that reads it
+    if (cursor) *cursor += 1;
   }
 }
 
@@ -389,7 +371,7 @@ extern "C" int egx_ppo_loss(const float* mu, const float* logvar, const float* v
   hipLaunchKernelGGL(egx_zero_terms_kernel, dim3(1), dim3(64), 0, st, out_terms);
   hipLaunchKernelGGL(egx_ppo_loss_kernel, dim3(ppo_loss_blocks(num_rows)), dim3(256), 0, st, mu, logvar, value, act, adv, ret, logp_old,
                      adv_stats, scale, adv_eps, min_logvar, max_logvar, eps_clip, vf_coef, ent_coef, num_rows, 128, g_mu, g_logvar,
-                     g_value, out_terms);
+                     g_value, out_terms, nullptr, 0);
   EGX_HIP_CHECK(hipGetLastError());
   return EGX_OK;
 }
@@ -398,12 +380,12 @@ extern "C" int egx_ppo_loss(const float* mu, const float* logvar, const float* v
 int egx_ppo_loss_packed_precleared(const float* zp, const float* value, const float* act, const float* adv, const float* ret,
                                    const float* logp_old, const float* adv_stats, const float* scale, float adv_eps, float min_logvar,
                                    float max_logvar, float eps_clip, float vf_coef, float ent_coef, int num_rows, float* g_zp,
-                                   float* g_value, float* out_terms, void* stream_) {
+                                   float* g_value, float* out_terms, void* stream_, const int* cursor, int max_cursor) {
   EGX_REQUIRE(zp && value && act && adv && ret && logp_old && scale && g_zp && g_value && out_terms && num_rows > 0, "bad arguments");
   hipStream_t st = static_cast<hipStream_t>(stream_);
   hipLaunchKernelGGL(egx_ppo_loss_kernel, dim3(ppo_loss_blocks(num_rows)), dim3(256), 0, st, zp, zp + 128, value, act, adv, ret, logp_old, adv_stats,
                      scale, adv_eps, min_logvar, max_logvar, eps_clip, vf_coef, ent_coef, num_rows, 256, g_zp, g_zp + 128, g_value,
-                     out_terms);
+                     out_terms, cursor, max_cursor);
   EGX_HIP_CHECK(hipGetLastError());
   return EGX_OK;
 }
@@ -417,7 +399,7 @@ extern "C" int egx_ppo_loss_packed(const float* zp, const float* value, const fl
   hipLaunchKernelGGL(egx_zero_terms_kernel, dim3(1), dim3(64), 0, st, out_terms);
   hipLaunchKernelGGL(egx_ppo_loss_kernel, dim3(ppo_loss_blocks(num_rows)), dim3(256), 0, st, zp, zp + 128, value, act, adv, ret, logp_old, adv_stats,
                      scale, adv_eps, min_logvar, max_logvar, eps_clip, vf_coef, ent_coef, num_rows, 256, g_zp, g_zp + 128, g_value,
-                     out_terms);
+                     out_terms, nullptr, 0);
   EGX_HIP_CHECK(hipGetLastError());
   return EGX_OK;
 }
@@ -507,19 +489,33 @@ extern "C" int egx_rollout_store(const float* state, const float* egosensing, co
 
 extern "C" size_t egx_adamw_workspace_floats(void) { return 1024 + 8; }
 
-extern "C" int egx_adamw_clip_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, size_t n, size_t n_clip,
-                                   float max_norm, double lr, double beta1, double beta2, double eps, double weight_decay,
-                                   float* step, float* workspace, void* stream_) {
+static int adamw_clip_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, size_t n, size_t n_clip,
+                           float max_norm, double lr, double beta1, double beta2, double eps, double weight_decay,
+                           float* step, float* workspace, int* cursor, void* stream_) {
   EGX_REQUIRE(param && grad && exp_avg && exp_avg_sq && step && workspace && n > 0 && n_clip <= n, "bad arguments");
   hipStream_t st = static_cast<hipStream_t>(stream_);
   const int nb = 1024;
   const bool do_clip = max_norm > 0.f && n_clip > 0;
   hipLaunchKernelGGL(egx_sumsq_partial_kernel, dim3(nb), dim3(256), 0, st, grad, do_clip ? n_clip : (size_t)0, workspace, step);
   hipLaunchKernelGGL(egx_adamw_consts_kernel, dim3(1), dim3(256), 0, st, workspace, nb, do_clip ? 1 : 0, max_norm, lr, beta1, beta2,
-                     step, workspace + nb);
+                     step, workspace + nb, cursor);
   const size_t blocks = (n + 1023) / 1024;
   hipLaunchKernelGGL(egx_adamw_flat_kernel, dim3((unsigned)blocks), dim3(256), 0, st, param, grad, exp_avg, exp_avg_sq, n, n_clip,
                      workspace + nb, lr, beta1, beta2, eps, weight_decay);
   EGX_HIP_CHECK(hipGetLastError());
   return EGX_OK;
+}
+
+extern "C" int egx_adamw_clip_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, size_t n, size_t n_clip,
+                                   float max_norm, double lr, double beta1, double beta2, double eps, double weight_decay,
+                                   float* step, float* workspace, void* stream_) {
+  return adamw_clip_step(param, grad, exp_avg, exp_avg_sq, n, n_clip, max_norm, lr, beta1, beta2, eps, weight_decay, step, workspace,
+                         nullptr, stream_);
+}
+
+extern "C" int egx_adamw_clip_step_cursor(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, size_t n, size_t n_clip,
+                                          float max_norm, double lr, double beta1, double beta2, double eps, double weight_decay,
+                                          float* step, float* workspace, int32_t* cursor, void* stream_) {
+  return adamw_clip_step(param, grad, exp_avg, exp_avg_sq, n, n_clip, max_norm, lr, beta1, beta2, eps, weight_decay, step, workspace,
+                         cursor, stream_);
 }

@@ -9,8 +9,8 @@
 //             gradient one more output column; input- and weight-gradient products of the actor AND the critic share a launch;
 //   GRU       cell forward = one launch per time step for both encoders (dense3 gru kernel), cell backward = one launch per
 //             step producing the gate gradients directly as packed images.
-// ~27 launches per minibatch instead of ~85.  Gradients are WRITTEN (not accumulated) into the flat gradient buffer - every
-// parameter is used exactly once per minibatch - so the buffer needs no zero fill.
+// 22 launches per minibatch (egx_update_head_kernel first) instead of ~85.  Gradients are WRITTEN (not accumulated) into the flat
+// gradient buffer - every parameter is used exactly once per minibatch - so the buffer needs no zero fill.
 #include <algorithm>
 #include <cstring>
 #include <vector>
@@ -49,6 +49,42 @@ struct PackEntry {
   int S_total2;              //              and its k-steps per row tile
 };
 
+// one fragment of a plain (transpose 0) or transposed (1) table entry: shared by egx_pack3_table_kernel (rows as they are) and
+// egx_update_head_kernel (gathered rows), so that the two cannot drift apart
+template <class Rows>
+__device__ __forceinline__ void u3_pack_fragment(const PackEntry& e, const float* __restrict__ src, int frag, int lane, int nplanes,
+                                                 const Rows& rows) {
+  float x[8];
+  int rt, s;
+  if (!e.transpose) {
+    const int S = (e.cols + 31) >> 5;
+    rt = frag / S; s = frag % S;
+    const int row = rt * 16 + (lane & 15), k0 = s * 32 + 8 * (lane >> 4);
+    const size_t srow = row < e.red ? rows(row) : 0;
+#pragma unroll
+    for (int q = 0; q < 8; ++q) x[q] = (row < e.red && k0 + q < e.cols) ? src[srow * e.ld + e.col0 + k0 + q] : 0.f;
+  } else {
+    const int S = (e.red + 31) >> 5;
+    rt = frag / S; s = frag % S;
+    const int irow = rt * 16 + (lane & 15), k0 = s * 32 + 8 * (lane >> 4);
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+      float v = 0.f;
+      if (k0 + q < e.red) {
+        if (irow < e.cols) v = src[rows(k0 + q) * e.ld + e.col0 + irow];
+        else if (irow == e.ones_row) v = 1.f;
+      }
+      x[q] = v;
+    }
+  }
+  bf16x8 pl[3];
+  u3_split(x, pl);
+  bf16x8* o = e.dst + ((size_t)rt * e.S_total + e.s0 + s) * 3 * 64 + lane;
+#pragma unroll
+  for (int p = 0; p < 3; ++p)
+    if (p < nplanes) o[p * 64] = pl[p];   // planes no consumer reads are not written (a third of the image bytes per plane)
+}
+
 __global__ __launch_bounds__(256) void egx_pack3_table_kernel(const PackEntry* __restrict__ tab, int n, int nplanes) {
   int frag = blockIdx.x * 4 + (threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
@@ -61,7 +97,6 @@ __global__ __launch_bounds__(256) void egx_pack3_table_kernel(const PackEntry* _
   const PackEntry e = tab[lo];
   frag -= lo > 0 ? tab[lo - 1].frag_end : 0;
   float x[8];
-  int rt, s;
   if (e.transpose == 2) {
     // weight matrix W [red, cols] -> image of W (the forward products' operand) and image of W^T (the input-gradient
     // products'): the wave reads its 32 x 32 block once, writes W's two fragments from registers and W^T's two after a
@@ -105,32 +140,84 @@ __global__ __launch_bounds__(256) void egx_pack3_table_kernel(const PackEntry* _
     }
     return;
   }
-  if (!e.transpose) {
-    const int S = (e.cols + 31) >> 5;
-    rt = frag / S; s = frag % S;
-    const int row = rt * 16 + (lane & 15), k0 = s * 32 + 8 * (lane >> 4);
-#pragma unroll
-    for (int q = 0; q < 8; ++q) x[q] = (row < e.red && k0 + q < e.cols) ? e.src[(size_t)row * e.ld + e.col0 + k0 + q] : 0.f;
-  } else {
-    const int S = (e.red + 31) >> 5;
-    rt = frag / S; s = frag % S;
-    const int irow = rt * 16 + (lane & 15), k0 = s * 32 + 8 * (lane >> 4);
-#pragma unroll
-    for (int q = 0; q < 8; ++q) {
-      float v = 0.f;
-      if (k0 + q < e.red) {
-        if (irow < e.cols) v = e.src[(size_t)(k0 + q) * e.ld + e.col0 + irow];
-        else if (irow == e.ones_row) v = 1.f;
-      }
-      x[q] = v;
+  u3_pack_fragment(e, e.src, frag, lane, nplanes, EgxRowsIdentity());
+}
+
+// ---- the head of a minibatch: ONE launch for what used to be five (index copy aside): the row gather, the advantage
+// statistics, the input images, the positional encoding and the clearing of the loss sums.  The grid is partitioned by role;
+// no role reads what another one writes, so the blocks are independent (no fence, no ticket, no last-block epilogue):
+//   [0, b_pack)          egx_pack3_table_kernel's work on the input table, entry row r reading row idx[r] of the ROLLOUT's
+//                        state / egosensing (the first half of the table's entries is the state's, the second the ego's)
+//   [.., + b_pe)         egx_posenc3_kernel's work on dist[idx[r]] / time[idx[r]]; its first block clears the six loss sums
+//   [.., + b_gather)     act, adv, returns, logp_old rows idx[r] into the compact buffers the loss kernel reads (8 rows a block)
+//   one more (optional)  mean / unbiased std of adv[idx[.]] in the reduction order of egx_adv_stats_kernel (ppo.hip)
+// idx = perm + k n with k = *cursor (a device scalar a LATER single-block launch of the chain advances, egx_adamw_consts_kernel:
+// never a block of this launch), clamped to [0, max_cursor]; the loss sums of minibatch k are row k of `log`.  Row indices are
+// clamped to the rollout's rows: a bad index reads a wrong row, never another allocation.
+struct HeadArgs {
+  const PackEntry* tab;
+  int n_tab, frags_tab, nplanes;
+  const float *state, *ego;
+  const long long* perm;
+  const int* cursor;
+  int max_cursor, n, num_src;
+  const float *dist, *time, *act, *adv, *ret, *logp;
+  float *act_c, *adv_c, *ret_c, *logp_c;
+  float* stats;   // null: no statistics role (data parallel: the caller wrote the global ones)
+  float* log;
+  float* pe_out;
+  int pe_ld;
+  bf16x8* pe3;
+  int S3, s0;
+  bf16x8* pe3T;
+  int S3T, col0T;
+  int b_pack, b_pe, b_gather;
+};
+__device__ __forceinline__ int head_cursor(const HeadArgs& a) {
+  const int k = a.cursor ? *a.cursor : 0;
+  return min(max(k, 0), a.max_cursor);
+}
+
+__global__ __launch_bounds__(256) void egx_update_head_kernel(HeadArgs a) {
+  const int k = head_cursor(a);
+  const EgxRowsGathered rows{a.perm + (size_t)k * a.n, a.num_src};
+  const int lane = threadIdx.x & 63;
+  int bid = blockIdx.x;
+  if (bid < a.b_pack) {   // ---- input images (egx_pack3_table_kernel, transpose 0 / 1, gathered rows)
+    int frag = bid * 4 + (threadIdx.x >> 6);
+    const PackEntry* __restrict__ tab = a.tab;
+    if (frag >= a.frags_tab) return;
+    int lo = 0, hi = a.n_tab - 1;
+    while (lo < hi) {
+      const int mid = (lo + hi) >> 1;
+      if (frag >= tab[mid].frag_end) lo = mid + 1; else hi = mid;
     }
+    const PackEntry e = tab[lo];
+    const float* __restrict__ src = (lo < (a.n_tab >> 1)) ? a.state : a.ego;
+    frag -= lo > 0 ? tab[lo - 1].frag_end : 0;
+    u3_pack_fragment(e, src, frag, lane, a.nplanes, rows);
+    return;
   }
-  bf16x8 pl[3];
-  u3_split(x, pl);
-  bf16x8* o = e.dst + ((size_t)rt * e.S_total + e.s0 + s) * 3 * 64 + lane;
-#pragma unroll
-  for (int p = 0; p < 3; ++p)
-    if (p < nplanes) o[p * 64] = pl[p];   // planes no consumer reads are not written (a third of the image bytes per plane)
+  bid -= a.b_pack;
+  if (bid < a.b_pe) {   // ---- positional encoding (egx_posenc3_kernel, dense3.hip) of the gathered dist / time
+    if (bid == 0 && threadIdx.x < 6) a.log[6 * (size_t)k + threadIdx.x] = 0.f;
+    egx_posenc3_role(a.dist, a.time, a.n, a.pe_out, a.pe_ld, a.pe3, a.S3, a.s0, a.pe3T, a.S3T, a.col0T, bid, rows,
+                     [](const float (&x)[8], bf16x8 (&pl)[3]) { u3_split(x, pl); });
+    return;
+  }
+  bid -= a.b_pe;
+  if (bid < a.b_gather) {   // ---- compact rows for the loss kernel: 8 rows per block, 32 threads x 16 bytes = one act row
+    const int r = bid * 8 + (threadIdx.x >> 5), c4 = threadIdx.x & 31;
+    if (r >= a.n) return;
+    const size_t srow = rows(r);
+    reinterpret_cast<f32x4*>(a.act_c + (size_t)r * 128)[c4] = reinterpret_cast<const f32x4*>(a.act + srow * 128)[c4];
+    if (c4 == 0) a.adv_c[r] = a.adv[srow];
+    else if (c4 == 1) a.ret_c[r] = a.ret[srow];
+    else if (c4 == 2) a.logp_c[r] = a.logp[srow];
+    return;
+  }
+  if (!a.stats) return;
+  egx_adv_stats_role(a.adv, a.n, a.stats, rows);   // egx_adv_stats_kernel's body on adv[idx[.]]: same additions, same order
 }
 
 inline int img_tiles(int rows) { return 2 * egx_ceil_div(rows, 32); }   // 16-row tiles, even count
@@ -433,6 +520,9 @@ extern "C" int egx_policy_train_create(const egx_policy_weights* w, const egx_po
     add(h->h_inputs, nullptr, n, d, 2 * d, d, En.xT, 2 * Sn, Sn, 1, d);
   }
   h->n_inputs = (int)h->h_inputs.size();
+  // uploaded now with no sources: the head launch (egx_update_head_kernel) takes the rollout's state / egosensing as kernel
+  // arguments and reads only the destinations; egx_policy_train_bind fills in the sources the table kernel reads
+  if ((rc = upload_table(h->h_inputs, &h->tab_inputs, &h->frags_inputs))) return fail(rc);
   std::vector<PackEntry> tl;
   for (int b = 0; b < 2; ++b) {
     Branch& B = h->br[b];
@@ -481,7 +571,7 @@ extern "C" int egx_policy_train_packed(const egx_policy_train* h, egx_policy_pac
 
 extern "C" int egx_policy_train_bind(egx_policy_train* h, const float* state, const float* egosensing) {
   EGX_REQUIRE(h && state && egosensing, "null argument");
-  if (h->bound_state == state && h->bound_ego == egosensing && h->tab_inputs) return EGX_OK;
+  if (h->bound_state == state && h->bound_ego == egosensing) return EGX_OK;
   for (int i = 0; i < 4; ++i) h->h_inputs[i].src = state;
   for (int i = 4; i < 8; ++i) h->h_inputs[i].src = egosensing;
   int rc = upload_table(h->h_inputs, &h->tab_inputs, &h->frags_inputs);
@@ -493,7 +583,7 @@ extern "C" int egx_policy_train_bind(egx_policy_train* h, const float* state, co
 static int train_step_parts(egx_policy_train* h, const float* dist, const float* time, const float* act, const float* adv,
                             const float* ret, const float* logp_old, const float* adv_stats, const float* scale, float adv_eps,
                             float min_logvar, float max_logvar, float eps_clip, float vf_coef, float ent_coef, float* out_terms,
-                            void* stream_, int parts);
+                            void* stream_, int parts, const egx_update_head* hd = nullptr);
 
 extern "C" int egx_policy_train_step(egx_policy_train* h, const float* dist, const float* time, const float* act, const float* adv,
                                      const float* ret, const float* logp_old, const float* adv_stats, const float* scale,
@@ -514,18 +604,75 @@ extern "C" int egx_policy_train_step_heads(egx_policy_train* h, const float* dis
   return train_step_parts(h, dist, time, act, adv, ret, logp_old, adv_stats, scale, adv_eps, min_logvar, max_logvar, eps_clip, vf_coef,
                           ent_coef, out_terms, stream_, 1);
 }
+// ---- the same chain behind ONE head launch (egx_update_head_kernel): the minibatch is named by row indices into the rollout
+static int head_args_ok(const egx_policy_train* h, const egx_update_head* a) {
+  EGX_REQUIRE(h && a, "null argument");
+  EGX_REQUIRE(a->perm && a->state && a->egosensing && a->dist && a->time && a->act && a->adv && a->ret && a->logp_old &&
+                  a->act_c && a->adv_c && a->ret_c && a->logp_old_c && a->stats && a->log, "null field in egx_update_head");
+  EGX_REQUIRE(h->n_inputs == 8 && h->tab_inputs, "the input table must hold four state entries followed by four egosensing entries");
+  EGX_REQUIRE(a->num_src_rows > 0 && a->max_cursor >= 0, "egx_update_head: num_src_rows must be positive, max_cursor non-negative");
+  return EGX_OK;
+}
+static void launch_head(egx_policy_train* h, const egx_update_head* a, hipStream_t st) {
+  constexpr int S_HD = HD / 32, S_CAT = CAT / 32;
+  const int n = h->n, Sn = h->Sn;
+  HeadArgs k;
+  k.tab = h->tab_inputs; k.n_tab = h->n_inputs; k.frags_tab = h->frags_inputs; k.nplanes = planes_of(h->prec);
+  k.state = a->state; k.ego = a->egosensing;
+  k.perm = reinterpret_cast<const long long*>(a->perm); k.cursor = a->cursor; k.max_cursor = a->max_cursor; k.n = n;
+  k.num_src = a->num_src_rows;
+  k.dist = a->dist; k.time = a->time; k.act = a->act; k.adv = a->adv; k.ret = a->ret; k.logp = a->logp_old;
+  k.act_c = a->act_c; k.adv_c = a->adv_c; k.ret_c = a->ret_c; k.logp_c = a->logp_old_c;
+  k.stats = a->compute_stats ? a->stats : nullptr;
+  k.log = a->log;
+  k.pe_out = h->catf + 2 * HD; k.pe_ld = CAT; k.pe3 = h->cat_r; k.S3 = S_CAT; k.s0 = 2 * S_HD;
+  k.pe3T = h->catT; k.S3T = Sn; k.col0T = 2 * HD;
+  k.b_pack = egx_ceil_div(h->frags_inputs, 4);
+  k.b_pe = egx_ceil_div(2 * Sn * 4 + 8 * Sn, 4);
+  k.b_gather = egx_ceil_div(n, 8);
+  const int blocks = k.b_pack + k.b_pe + k.b_gather + (k.stats ? 1 : 0);
+  hipLaunchKernelGGL(egx_update_head_kernel, dim3(blocks), dim3(256), 0, st, k);
+}
+
+extern "C" int egx_policy_train_head(egx_policy_train* h, const egx_update_head* head, void* stream_) {
+  int rc = head_args_ok(h, head);
+  if (rc) return rc;
+  launch_head(h, head, static_cast<hipStream_t>(stream_));
+  EGX_HIP_CHECK(hipGetLastError());
+  return EGX_OK;
+}
+extern "C" int egx_policy_train_step_cursor(egx_policy_train* h, const egx_update_head* head, const float* scale, float adv_eps,
+                                            float min_logvar, float max_logvar, float eps_clip, float vf_coef, float ent_coef,
+                                            void* stream_) {
+  int rc = head_args_ok(h, head);
+  if (rc) return rc;
+  return train_step_parts(h, head->dist, head->time, head->act_c, head->adv_c, head->ret_c, head->logp_old_c, head->stats, scale, adv_eps,
+                          min_logvar, max_logvar, eps_clip, vf_coef, ent_coef, head->log, stream_, 3, head);
+}
+extern "C" int egx_policy_train_step_heads_cursor(egx_policy_train* h, const egx_update_head* head, const float* scale, float adv_eps,
+                                                  float min_logvar, float max_logvar, float eps_clip, float vf_coef, float ent_coef,
+                                                  void* stream_) {
+  int rc = head_args_ok(h, head);
+  if (rc) return rc;
+  return train_step_parts(h, head->dist, head->time, head->act_c, head->adv_c, head->ret_c, head->logp_old_c, head->stats, scale, adv_eps,
+                          min_logvar, max_logvar, eps_clip, vf_coef, ent_coef, head->log, stream_, 1, head);
+}
 extern "C" int egx_policy_train_step_encoders(egx_policy_train* h, void* stream_) {
   EGX_REQUIRE(h, "null handle");
   return train_step_parts(h, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, nullptr,
                           stream_, 2);
 }
 
+// Launches of one minibatch (parts = 3): 22 with `hd` - head 1 | GRU steps 2, layers 4, output layers 1 | loss 1, its images 1 |
+// backward of the blocks 8 (output-layer weight gradients, 5 input gradients, 2 x four weight gradients) | GRU encoders 4 - and
+// 23 without (input images and positional encoding instead of the head; the caller's gather and statistics launches come on
+// top: 25).  parts = 1 ends after the blocks' backward (18 / 19), parts = 2 is the encoders' 4.
 static int train_step_parts(egx_policy_train* h, const float* dist, const float* time, const float* act, const float* adv,
                             const float* ret, const float* logp_old, const float* adv_stats, const float* scale, float adv_eps,
                             float min_logvar, float max_logvar, float eps_clip, float vf_coef, float ent_coef, float* out_terms,
-                            void* stream_, int parts) {
+                            void* stream_, int parts, const egx_update_head* hd) {
   EGX_REQUIRE(h && (!(parts & 1) || (dist && time && act && adv && ret && logp_old && scale && out_terms)), "null argument");
-  EGX_REQUIRE(h->tab_inputs, "egx_policy_train_bind has not been called");
+  EGX_REQUIRE(hd || !(parts & 1) || h->bound_state, "egx_policy_train_bind has not been called");
   hipStream_t st = static_cast<hipStream_t>(stream_);
   const int n = h->n, Sn = h->Sn;
   constexpr int S_HD = HD / 32, S_CAT = CAT / 32, S_G = 3 * HD / 32;
@@ -543,8 +690,12 @@ static int train_step_parts(egx_policy_train* h, const float* dist, const float*
   int rc = EGX_OK;
   if (parts & 1) {
   // ================= forward =================
-  run_table(st, h->tab_inputs, h->n_inputs, h->frags_inputs, planes_of(h->prec));
-  egx_launch_posenc3(st, dist, time, n, h->catf + 2 * HD, CAT, h->cat_r, S_CAT, 2 * S_HD, h->catT, Sn, 2 * HD, out_terms);   // also clears the loss sums
+  if (hd) {
+    launch_head(h, hd, st);   // gather, statistics, input images, positional encoding, cleared loss sums: one launch
+  } else {
+    run_table(st, h->tab_inputs, h->n_inputs, h->frags_inputs, planes_of(h->prec));
+    egx_launch_posenc3(st, dist, time, n, h->catf + 2 * HD, CAT, h->cat_r, S_CAT, 2 * S_HD, h->catT, Sn, 2 * HD, out_terms);   // also clears the loss sums
+  }
   {
     D3Gru g[2];
     for (int e = 0; e < 2; ++e) {   // step 1: zero previous state
@@ -604,7 +755,8 @@ static int train_step_parts(egx_policy_train* h, const float* dist, const float*
   }
   // ================= loss and its gradient w.r.t. the two heads (ppo_policy.py:189-241) =================
   rc = egx_ppo_loss_packed_precleared(h->br[0].head, h->br[1].head, act, adv, ret, logp_old, adv_stats, scale, adv_eps, min_logvar, max_logvar,
-                               eps_clip, vf_coef, ent_coef, n, h->br[0].ghead, h->br[1].ghead, out_terms, st);
+                               eps_clip, vf_coef, ent_coef, n, h->br[0].ghead, h->br[1].ghead, out_terms, st, hd ? hd->cursor : nullptr,
+                               hd ? hd->max_cursor : 0);
   if (rc) return rc;
   run_table(st, h->tab_loss, h->n_loss, h->frags_loss, planes_of(h->prec));
   // ================= backward =================

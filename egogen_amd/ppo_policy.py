@@ -145,6 +145,8 @@ class GAMMAPPOPolicy(nn.Module):
         # the data-parallel code path (global advantage moments, graph 1 | all-reduce | graph 2): taken with more than one
         # rank - and, for testing the RCCL calls between graph replays on a one-GPU box, with ONE rank when asked for
         self._dp = self.world_size > 1 or (os.environ.get("EGX_FORCE_DP_PATH") == "1" and dist.is_available() and dist.is_initialized())
+        self._img_key = None               # (parameter versions, precisions) the weight images were last made from
+        self.refresh_counts = {"total": 0, "learn_top": 0, "learn_bottom": 0}   # launches of _refresh_images, and who asked
         self.update_paths: dict = {}       # minibatches of learn() by formulation: "chain", "chain+graph", "autograd", "autograd+graph"
         self.allreduce_events: list = []   # [(start, stop)] torch.cuda.Event pairs, one consumed per gradient all-reduce
         self._allreduce_done: list = []
@@ -351,12 +353,20 @@ class GAMMAPPOPolicy(nn.Module):
         _lib.check(lib.egx_policy_train_set_precision(h, _UPDATE_PREC[self.update_precision]), "egx_policy_train_set_precision")
         dev = self._flat_grad.device
         f = dict(dtype=torch.float32, device=dev)
-        bufs = [torch.empty(n, 804, **f), torch.empty(n, 64, **f), torch.empty(n, 1, **f), torch.empty(n, 1, **f),
+        # EGX_UPDATE_HEAD=0: the minibatch's head as the five launches it used to be (gather, statistics, input images,
+        # positional encoding; index copy and log clone around a replay) - the A/B switch of profiles/update_head.md
+        head = os.environ.get("EGX_UPDATE_HEAD", "1") != "0"
+        # compact copies of the minibatch's rows: with the head launch only what the loss kernel reads (act, adv, returns,
+        # logp_old) - the observations are read from the rollout in place
+        bufs = [None if head else torch.empty(n, 804, **f), None if head else torch.empty(n, 64, **f),
+                None if head else torch.empty(n, 1, **f), None if head else torch.empty(n, 1, **f),
                 torch.empty(n, 128, **f), torch.empty(n, 1, **f), torch.empty(n, 1, **f), torch.empty(n, 1, **f)]
-        _lib.check(lib.egx_policy_train_bind(h, _lib.ptr(bufs[0]), _lib.ptr(bufs[1])), "egx_policy_train_bind")
+        if not head:
+            _lib.check(lib.egx_policy_train_bind(h, _lib.ptr(bufs[0]), _lib.ptr(bufs[1])), "egx_policy_train_bind")
         packed = _lib.PolicyPacked3()
         _lib.check(lib.egx_policy_train_packed(h, C.byref(packed)), "egx_policy_train_packed")
-        hs = {"h": h, "bufs": bufs, "stats": torch.zeros(2, **f), "key": (w.x_enc_w_ih, g.x_enc_w_ih), "packed": packed}
+        hs = {"h": h, "n": int(n), "bufs": bufs, "stats": torch.zeros(2, **f), "key": (w.x_enc_w_ih, g.x_enc_w_ih), "packed": packed,
+              "head": head}
         self._train_handles[n] = hs
         if len(self._train_handles) == 1:   # the rollout forward reads the images this handle keeps current
             self._runner.adopt_packed(packed, refresh=self._refresh_images)
@@ -392,6 +402,16 @@ class GAMMAPPOPolicy(nn.Module):
         except Exception:
             pass
 
+    def _prec_key(self):
+        """The precisions that decide which planes of the weight images a refresh writes."""
+        return (int(_lib.load().egx_policy_get_precision()), self.update_precision)
+
+    def _img_key_now(self):
+        """What the weight images depend on, as far as the host can see it: every in-place edit torch versions (optim.step(),
+        load_state_dict, copy_) and the precisions in force.  Writes by address (the flat AdamW kernel) are followed by a
+        refresh of their own."""
+        return (sum(int(p._version) for p in self.parameters()), self._prec_key())
+
     def _refresh_images(self):
         """Re-make the packed weight images of every update handle (one launch each) - after anything that changed the
         parameters."""
@@ -400,11 +420,24 @@ class GAMMAPPOPolicy(nn.Module):
         lib, st = _lib.load(), _lib.current_stream_ptr()
         for hs in self._train_handles.values():
             _lib.check(lib.egx_policy_train_refresh(hs["h"], st), "egx_policy_train_refresh")
+        self._img_key = self._img_key_now()
+        self.refresh_counts["total"] += 1
 
-    def _fwd_bwd_train_step(self, hs, batch, idx, gstats, log_out, part: str = "all"):
-        """gather + forward + loss + backward of one minibatch: 2 + ~21 launches, gradients written into the flat buffer.
+    def _refresh_images_if_stale(self, who: str):
+        """learn()'s own refreshes: only when a parameter's version or a precision differs from what the last refresh saw (a
+        replayed graph's captured refresh counts with the precisions of its capture)."""
+        if self._train_handles and self._img_key != self._img_key_now():
+            self._refresh_images()
+            self.refresh_counts[who] += 1
+
+    def _fwd_bwd_train_step(self, hs, batch, idx, gstats, log_out, part: str = "all", cursor=None):
+        """head + forward + loss + backward of one minibatch: 1 + 21 launches (head | 2 GRU steps, 4 layers, output layers | loss,
+        its images | 12 of the backward), gradients written into the flat buffer; with EGX_UPDATE_HEAD=0 the head is the four
+        launches it used to be (gather, statistics, input images, positional encoding).
         `part`: "all"; "heads" = everything up to the last actor / critic weight gradient (data-parallel training all-reduces that
-        bucket while "encoders" - the GRU encoders' backward - runs)."""
+        bucket while "encoders" - the GRU encoders' backward - runs).
+        `cursor` (head path): int32 device scalar k - the minibatch is rows idx[k n : (k + 1) n] and its loss terms go to row k
+        of `log_out`; None: k = 0, idx is the minibatch."""
         from .fused_ops import gather_rows
         lib, st = _lib.load(), _lib.current_stream_ptr()
         if part == "encoders":
@@ -413,6 +446,35 @@ class GAMMAPPOPolicy(nn.Module):
         N = batch.n * batch.A
         obs_all = batch.obs_flat()
         b = hs["bufs"]
+        if hs["head"]:
+            n = hs["n"]
+            idx = idx.contiguous()
+            rows = int(idx.numel()) // n
+            assert idx.dtype == torch.long and rows >= 1 and (cursor is not None or int(idx.numel()) == n), (idx.dtype, idx.shape, n)
+            assert log_out.is_contiguous() and log_out.dtype == torch.float32 and log_out.numel() >= 6 * rows, log_out.shape
+            srcs = (obs_all["state"], obs_all["egosensing"], obs_all["dist"], obs_all["time"], batch.act, batch.adv, batch.returns,
+                    batch.logp_old)
+            assert all(t.dtype == torch.float32 and t.is_contiguous() for t in srcs)
+            dev = b[4].device
+            if gstats is None:
+                scale = self._scale_cache.get((n, dev))
+                if scale is None:
+                    scale = torch.full((1,), 1.0 / n, dtype=torch.float32, device=dev)
+                    self._scale_cache[(n, dev)] = scale
+            else:
+                hs["stats"].copy_(torch.stack([gstats[0], gstats[1]]).float())
+                scale = (1.0 / gstats[2]).reshape(1).float()
+            hd = _lib.UpdateHead()
+            hd.perm, hd.cursor = idx.data_ptr(), (cursor.data_ptr() if cursor is not None else None)
+            hd.max_cursor, hd.num_src_rows = rows - 1, N
+            (hd.state, hd.egosensing, hd.dist, hd.time, hd.act, hd.adv, hd.ret, hd.logp_old) = (t.data_ptr() for t in srcs)
+            hd.act_c, hd.adv_c, hd.ret_c, hd.logp_old_c = (b[i].data_ptr() for i in (4, 5, 6, 7))
+            hd.stats, hd.compute_stats, hd.log = hs["stats"].data_ptr(), int(gstats is None), log_out.data_ptr()
+            fn = lib.egx_policy_train_step_heads_cursor if part == "heads" else lib.egx_policy_train_step_cursor
+            rc = fn(hs["h"], C.byref(hd), _lib.ptr(scale), float(_EPS), float(self.actor.min_logvar), float(self.actor.max_logvar),
+                    float(self._eps_clip), float(self._weight_vf), float(self._weight_ent), st)
+            _lib.check(rc, "egx_policy_train_step_cursor")
+            return
         gather_rows(idx, [obs_all["state"].reshape(N, 804), obs_all["egosensing"].reshape(N, 64), obs_all["dist"].reshape(N, 1),
                           obs_all["time"].reshape(N, 1), batch.act.reshape(N, 128), batch.adv.reshape(N, 1), batch.returns.reshape(N, 1),
                           batch.logp_old.reshape(N, 1)], out=b)
@@ -434,12 +496,15 @@ class GAMMAPPOPolicy(nn.Module):
                 _lib.ptr(log_out), st)
         _lib.check(rc, "egx_policy_train_step")
 
-    def _fwd_bwd(self, batch, idx, gstats, log_out) -> str:
+    def _fwd_bwd(self, batch, idx, gstats, log_out, cursor=None, n=None) -> str:
         """Forward, loss and backward of one minibatch into the flat gradient; returns which formulation ran ("chain": the
-        hand-written launch chain of csrc/update3.hip, "autograd": the autograd nodes)."""
-        hs = self._train_handle(int(idx.shape[0])) if idx.is_cuda else None
+        hand-written launch chain of csrc/update3.hip, "autograd": the autograd nodes).  `cursor`, `n`: see
+        _fwd_bwd_train_step (chain with the head launch only)."""
+        hs = self._train_handle(int(idx.shape[0]) if n is None else int(n)) if idx.is_cuda else None
+        if cursor is not None and (hs is None or not hs["head"]):
+            raise _lib.EgxError("a minibatch cursor needs the update chain with its head launch")
         if hs is not None:
-            self._fwd_bwd_train_step(hs, batch, idx, gstats, log_out)
+            self._fwd_bwd_train_step(hs, batch, idx, gstats, log_out, cursor=cursor)
             return "chain"
         obs, act, adv, ret, lpo = self._gather(batch, idx)
         v_s = batch.values[:batch.n].reshape(-1).index_select(0, idx) if self._value_clip else None
@@ -459,19 +524,25 @@ class GAMMAPPOPolicy(nn.Module):
             log_out.copy_(torch.stack([terms[k].detach() for k in ("loss", "loss/clip", "loss/vf", "loss/ent", "loss/kld", "approx_kl")]))
         return "autograd"
 
-    def _clip_and_step(self):
+    def _clip_and_step(self, cursor=None):
+        """`cursor`: the update's minibatch cursor (int32 device scalar), advanced by the optimiser's single-block launch."""
         if self.use_flat_optimizer and self._flat_opt_state == "ready":
             g = self.optim.param_groups[0]
             lib = _lib.load()
             b1, b2 = g["betas"]
-            rc = lib.egx_adamw_clip_step(_lib.ptr(self._flat_p), _lib.ptr(self._flat_grad), _lib.ptr(self._flat_m), _lib.ptr(self._flat_v),
-                                         self._flat_p.numel(), self._n_clip, float(self._grad_norm or 0.0), float(g["lr"]), float(b1),
-                                         float(b2), float(g["eps"]), float(g["weight_decay"]), _lib.ptr(self._step_t),
-                                         _lib.ptr(self._adamw_ws), _lib.current_stream_ptr())
+            args = (_lib.ptr(self._flat_p), _lib.ptr(self._flat_grad), _lib.ptr(self._flat_m), _lib.ptr(self._flat_v),
+                    self._flat_p.numel(), self._n_clip, float(self._grad_norm or 0.0), float(g["lr"]), float(b1),
+                    float(b2), float(g["eps"]), float(g["weight_decay"]), _lib.ptr(self._step_t), _lib.ptr(self._adamw_ws))
+            if cursor is None:
+                rc = lib.egx_adamw_clip_step(*args, _lib.current_stream_ptr())
+            else:
+                rc = lib.egx_adamw_clip_step_cursor(*args, _lib.ptr(cursor), _lib.current_stream_ptr())
             _lib.check(rc, "egx_adamw_clip_step")
             self._runner.mark_dirty()   # parameters written by address: the rollout runner's packed images are stale
             self._refresh_images()      # ... and so are the update's own (re-made by one launch, inside the captured graph too)
             return
+        if cursor is not None:
+            raise _lib.EgxError("a minibatch cursor needs the flat optimiser")
         if self._grad_norm:
             nn.utils.clip_grad_norm_(self._actor_critic.parameters(), max_norm=self._grad_norm)
         self.optim.step()
@@ -604,8 +675,20 @@ class GAMMAPPOPolicy(nn.Module):
         if g is not None:
             return g
         dev = batch.act.device
-        st = {"idx": torch.zeros(local_bs, dtype=torch.long, device=dev), "log": torch.zeros(6, device=dev),
-              "gstats": torch.tensor([0.0, 1.0, float(local_bs * self.world_size)], device=dev), "use_gstats": self._dp}
+        st = {"gstats": torch.tensor([0.0, 1.0, float(local_bs * self.world_size)], device=dev), "use_gstats": self._dp}
+        hs0 = self._train_handle(local_bs) if dev.type == "cuda" else None
+        st["head"] = hs0 is not None and hs0["head"] and self.use_flat_optimizer and self._flat_opt_state == "ready"
+        if st["head"]:
+            # the epoch's permutation, the minibatch cursor and one log row per minibatch live on the device: nothing is copied
+            # between two replays (learn() writes the permutation and zeroes the cursor once per epoch)
+            rows = max(1, (batch.n * batch.A) // local_bs)
+            st.update(rows=rows, perm=torch.zeros(rows * local_bs, dtype=torch.long, device=dev), log=torch.zeros(rows, 6, device=dev),
+                      cursor=torch.zeros((), dtype=torch.int32, device=dev))
+            fb_args, fb_kw = (st["perm"], ), dict(cursor=st["cursor"], n=local_bs)
+        else:
+            st.update(idx=torch.zeros(local_bs, dtype=torch.long, device=dev), log=torch.zeros(6, device=dev))
+            fb_args, fb_kw = (st["idx"], ), {}
+        cur = st.get("cursor")
         gs = (lambda: (st["gstats"][0], st["gstats"][1], st["gstats"][2])) if st["use_gstats"] else (lambda: None)
         try:
             # warm-up on a side stream (lazy library init, allocator pools) - it performs real optimiser steps on a
@@ -617,33 +700,33 @@ class GAMMAPPOPolicy(nn.Module):
             side.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(side):
                 for _ in range(3):
-                    self._fwd_bwd(batch, st["idx"], gs(), st["log"])
-                    self._clip_and_step()
+                    self._fwd_bwd(batch, *fb_args, gs(), st["log"], **fb_kw)
+                    self._clip_and_step(cur)
             torch.cuda.current_stream().wait_stream(side)
             torch.cuda.synchronize()
             g1 = torch.cuda.CUDAGraph()
             g2 = None
             if not self._dp:
                 with torch.cuda.graph(g1):
-                    st["path"] = self._fwd_bwd(batch, st["idx"], gs(), st["log"])
-                    self._clip_and_step()
+                    st["path"] = self._fwd_bwd(batch, *fb_args, gs(), st["log"], **fb_kw)
+                    self._clip_and_step(cur)
             else:
-                hs = self._train_handle(local_bs) if st["idx"].is_cuda else None
+                hs = self._train_handle(local_bs) if dev.type == "cuda" else None
                 if hs is not None and len(self._grad_buckets()) == 2 and self.overlap_allreduce:
                     # the chain in two halves: after g1 (heads) the actor + critic bucket is final and its all-reduce runs on a
                     # side stream beside g1b (the encoders' backward)
                     with torch.cuda.graph(g1):
-                        self._fwd_bwd_train_step(hs, batch, st["idx"], gs(), st["log"], part="heads")
+                        self._fwd_bwd_train_step(hs, batch, *fb_args, gs(), st["log"], part="heads", cursor=cur)
                     g1b = torch.cuda.CUDAGraph()
                     with torch.cuda.graph(g1b, pool=g1.pool()):
-                        self._fwd_bwd_train_step(hs, batch, st["idx"], gs(), st["log"], part="encoders")
+                        self._fwd_bwd_train_step(hs, batch, *fb_args, gs(), st["log"], part="encoders")
                     st["g1b"], st["path"] = g1b, "chain"
                 else:
                     with torch.cuda.graph(g1):
-                        st["path"] = self._fwd_bwd(batch, st["idx"], gs(), st["log"])
+                        st["path"] = self._fwd_bwd(batch, *fb_args, gs(), st["log"], **fb_kw)
                 g2 = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(g2, pool=g1.pool()):
-                    self._clip_and_step()
+                    self._clip_and_step(cur)
             # capture does not execute, but the warm-up steps did: restore parameters and optimiser state IN PLACE
             # (the graphs hold the addresses of the live tensors)
             self.load_state_dict(snap)
@@ -653,6 +736,9 @@ class GAMMAPPOPolicy(nn.Module):
                         old_v = osnap[id(p_)].get(k)
                         v.copy_(old_v) if old_v is not None else v.zero_()
             st["g1"], st["g2"] = g1, g2
+            st["prec_key"] = self._prec_key()   # the captured refresh writes the planes of these precisions
+            if cur is not None:
+                cur.zero_()          # the warm-up steps advanced it
             self._refresh_images()   # the packed weight images followed the warm-up steps: back to the restored parameters
         except Exception as e:  # capture unsupported for some op on this stack: run the same ops eagerly
             import warnings
@@ -709,7 +795,7 @@ class GAMMAPPOPolicy(nn.Module):
         self._ensure_flat_grads()
         if self.use_flat_optimizer and batch.act.is_cuda:
             self._flat_optimizer_ready()  # (re-)points parameters / optimiser state BEFORE anything is captured
-        self._refresh_images()            # whatever changed the parameters since the last update (load_state_dict, ...)
+        self._refresh_images_if_stale("learn_top")   # whatever changed the parameters since the last refresh (load_state_dict, ...)
         ws = self.world_size
         dp = self._dp
         N = batch.n * batch.A
@@ -743,11 +829,21 @@ class GAMMAPPOPolicy(nn.Module):
             last_log = None
             spans = [(s, bounds[i + 1] if i + 1 < len(bounds) else N) for i, s in enumerate(bounds)]
             gstats_all = self._global_adv_stats(batch, perm, spans) if dp else None
+            gst = self._graphs_for(batch, local_bs) if (use_graph and spans[0][1] - spans[0][0] == local_bs) else None
+            if gst is not None and gst.get("g1") is None:
+                gst = None
+            vsum = self._img_key_now()[0]   # replays write the parameters by address: no version changes under them
+            head = gst is not None and gst["head"]
+            n_replayed, first_log = 0, len(logs)   # head path: this epoch's replays are logs[first_log : first_log + n_replayed]
+            if head:
+                gst["perm"].copy_(perm[:gst["perm"].numel()])
+                gst["cursor"].zero_()
             for i, (s, e) in enumerate(spans):
                 idx = perm[s:e]
-                st = self._graphs_for(batch, local_bs) if (use_graph and e - s == local_bs) else None
-                if st is not None and st.get("g1") is not None:
-                    st["idx"].copy_(idx)
+                st = gst if e - s == local_bs else None
+                if st is not None:
+                    if not head:
+                        st["idx"].copy_(idx)
                     if dp:
                         st["gstats"].copy_(gstats_all[i])
                     st["g1"].replay()
@@ -768,7 +864,13 @@ class GAMMAPPOPolicy(nn.Module):
                         else:
                             self._all_reduce_grad()
                         st["g2"].replay()
-                    last_log = st["log"].clone()
+                    # the captured refresh re-made the images from the parameters this replay wrote, with the capture's precisions
+                    self._img_key = (vsum, st["prec_key"])
+                    if head:
+                        last_log = None        # row n_replayed of the device log: copied once, after the epoch's last replay
+                        n_replayed += 1
+                    else:
+                        last_log = st["log"].clone()
                     self.update_paths[st["path"] + "+graph"] = self.update_paths.get(st["path"] + "+graph", 0) + 1
                 else:
                     gstats = None
@@ -781,12 +883,16 @@ class GAMMAPPOPolicy(nn.Module):
                     self._clip_and_step()
                     last_log = log
                     self.update_paths[path] = self.update_paths.get(path, 0) + 1
-                logs.append(last_log[:5])
+                logs.append(last_log)   # six terms (None: a replay's row, filled in below)
                 if self._after_minibatch is not None:   # parity tests: the flat gradient / clip coefficient of THIS optimiser step
                     self._after_minibatch(len(logs) - 1)
                 # `loss/kld` of ppo_policy.py:232 reads minibatch.z_mu - the means the ROLLOUT stored - not the current network's:
                 # 0.5 mean(mu_rollout^2) over the minibatch's rows, evaluated for all minibatches at once after the loop
                 kld_rows.append(idx)
+            if n_replayed:   # the replays come first in an epoch (only its last, merged minibatch can be eager); the next epoch
+                snap = gst["log"][:n_replayed].clone()   # clears these rows again
+                logs[first_log:first_log + n_replayed] = list(snap)
+            last_log = logs[-1] if logs else None
             # early stop on the last minibatch's approximate KL (ppo_policy.py:252-257); inert at repeat=1
             if repeat > 1 and last_log is not None:
                 kl = last_log[5].clone()
@@ -795,11 +901,11 @@ class GAMMAPPOPolicy(nn.Module):
                 if float(kl.item()) >= 0.02:
                     break
         self._runner.mark_dirty()   # replayed graphs update the parameters by address: re-pack before the next rollout forward
-        # a captured refresh writes the planes of the precision in force at capture time; one eager refresh here writes those of
-        # the precision in force NOW (e.g. egx_policy_set_precision(0) for an fp32 evaluation after bf16x2 training)
-        self._refresh_images()
+        # a captured refresh writes the planes of the precision in force at capture time; where that is not the precision in
+        # force NOW (e.g. egx_policy_set_precision(0) for an fp32 evaluation after bf16x2 training), one eager refresh here
+        self._refresh_images_if_stale("learn_bottom")
         if logs:
-            L = torch.stack(logs)
+            L = torch.stack(logs)[:, :5].contiguous()
             mu2 = batch.mu.reshape(N, -1).pow(2).mean(1)               # [N]: per-row mean of the rollout's mu^2
             if len({int(r.shape[0]) for r in kld_rows}) == 1:
                 kld = 0.5 * mu2.index_select(0, torch.cat(kld_rows)).reshape(len(kld_rows), -1).mean(1)

@@ -516,6 +516,33 @@ int egx_policy_train_step_heads(egx_policy_train* h, const float* dist, const fl
                                 float min_logvar, float max_logvar, float eps_clip, float vf_coef, float ent_coef, float* out_terms,
                                 void* stream);
 int egx_policy_train_step_encoders(egx_policy_train* h, void* stream);
+/* The same minibatch behind ONE head launch.  The minibatch is named by row indices into the rollout's tensors instead of by
+ * compact copies: rows idx[0..n) with idx = perm + k * n, n = the handle's rows, k = *cursor (device scalar; NULL: k = 0)
+ * clamped to [0, max_cursor]; perm holds (max_cursor + 1) * n indices, each clamped to [0, num_src_rows).  In independent
+ * blocks of one grid the launch writes the input images from rows idx[r] of state / egosensing, the positional encoding of
+ * dist / time at idx[r], the rows idx[r] of act / adv / ret / logp_old into the compact buffers the loss kernel reads, with
+ * compute_stats != 0 stats = {mean, unbiased std} of adv[idx[.]] (the bits of egx_adv_stats on the gathered rows; 0: the
+ * caller wrote stats, e.g. the global moments of data-parallel training), and clears row k of `log` ([max_cursor + 1][6]),
+ * where the loss kernel then accumulates the six loss terms of minibatch k.  Nothing in the chain advances the cursor:
+ * egx_adamw_clip_step_cursor does, in its single-block launch, so replayed graphs need no copy between minibatches. */
+typedef struct egx_update_head {
+  const int64_t* perm;
+  const int32_t* cursor;
+  int max_cursor;
+  int num_src_rows;
+  const float *state, *egosensing, *dist, *time; /* [num_src_rows, 804 | 64 | 1 | 1] */
+  const float *act, *adv, *ret, *logp_old;       /* [num_src_rows, 128 | 1 | 1 | 1]  */
+  float *act_c, *adv_c, *ret_c, *logp_old_c;     /* [n, 128 | 1 | 1 | 1]             */
+  float* stats;                                  /* [2]                              */
+  int compute_stats;
+  float* log;
+} egx_update_head;
+int egx_policy_train_head(egx_policy_train* h, const egx_update_head* head, void* stream); /* the head launch alone */
+int egx_policy_train_step_cursor(egx_policy_train* h, const egx_update_head* head, const float* scale, float adv_eps,
+                                 float min_logvar, float max_logvar, float eps_clip, float vf_coef, float ent_coef, void* stream);
+int egx_policy_train_step_heads_cursor(egx_policy_train* h, const egx_update_head* head, const float* scale, float adv_eps,
+                                       float min_logvar, float max_logvar, float eps_clip, float vf_coef, float ent_coef,
+                                       void* stream);
 /* Arithmetic of every product of the chain (forward, input gradients, weight gradients): 0 = each fp32 operand as three bf16
  * terms, six partial products (2^-24 relative: fp32-equivalent; default), 2 = two terms, three products (16 significant bits
  * per operand, the arithmetic of the LBS blend GEMM's default mode), 1 = operands rounded to bf16, one product ("bf16 MFMA"
@@ -770,6 +797,10 @@ size_t egx_adamw_workspace_floats(void);
 int egx_adamw_clip_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, size_t n, size_t n_clip,
                         float max_norm, double lr, double beta1, double beta2, double eps, double weight_decay, float* step,
                         float* workspace, void* stream);
+/* The same, and the single-block launch in the middle also adds 1 to *cursor (the update's minibatch cursor, egx_update_head). */
+int egx_adamw_clip_step_cursor(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, size_t n, size_t n_clip,
+                               float max_norm, double lr, double beta1, double beta2, double eps, double weight_decay, float* step,
+                               float* workspace, int32_t* cursor, void* stream);
 
 #ifdef __cplusplus
 }
