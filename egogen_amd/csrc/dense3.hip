@@ -5,7 +5,7 @@
 // gfx950 the fp32 MFMA runs at 1/16 of the bf16 rate.  Here every fp32 operand x is carried as three bf16 terms
 // x = hi + mid + lo (24+ significant bits) and a product keeps the six partial products down to 2^-24 relative
 // (mid.mid, hi.lo, lo.hi, hi.mid, mid.hi, hi.hi), accumulated in fp32 by v_mfma_f32_16x16x32_bf16 - the arithmetic of the
-// LBS blend GEMM's three-plane mode (body_model.hip).  What makes it pay for latency-bound layers:
+// LBS blend GEMM's three-plane mode (lbs_fused3.hip).  What makes it pay for latency-bound layers:
 //   * operands live in HBM already split and in MFMA fragment order ("packed": [16-row tile][32-wide k-step][plane][lane]
 //     16 bytes), so a wave's loads are whole contiguous KiB and no consumer spends VALU time on splitting;
 //   * the PRODUCER of an activation writes that packed form from its epilogue (one split per element instead of one per

@@ -115,7 +115,7 @@ def make_body_model(seed: int = 0, num_verts: int = NUM_VERTS, nnz_weights: int 
     component - limb lengths and girths - fading with the component index, plus 5 % detail) and pose correctives act near
     their joint (Gaussian fall-off of 12 cm).  Same shapes, same magnitudes at the affected vertices; what changes is that a
     vertex's offset from ITS joints is bounded by centimetres, which is what lets the work-item culling of the SDF path
-    (csrc/body_model.hip) prove tiles free - with i.i.d. noise in every one of the 469 x 31 425 entries no a-priori bound
+    (csrc/body_model.hip, csrc/lbs_cull.hip) prove tiles free - with i.i.d. noise in every one of the 469 x 31 425 entries no a-priori bound
     is tighter than ~0.4 m.
     """
     rng = np.random.default_rng(seed)

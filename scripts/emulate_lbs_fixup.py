@@ -1,4 +1,4 @@
-"""Float64 emulation behind the fix-up threshold of the mixed blend (LBS blend mode 3, csrc/body_model.hip).
+"""Float64 emulation behind the fix-up threshold of the mixed blend (LBS blend mode 3, csrc/lbs_fused3.hip).
 
 The count-only tiles evaluate the pose-corrective columns (k-steps 1..28) as ONE fp16 product.  A vertex whose SDF value is
 closer to zero than the error that product can cause is re-evaluated in fp32 by the kernel (fix-up).  This script measures, on
@@ -7,7 +7,7 @@ the synthetic body, the actual position error of the fp16 product against
     bound(body) = 2^-11 * sqrt( sum_j ||R_j - I||_F^2 * C_j^2 ),   C_j = max_v max_{k in joint j} |b_k,v|   (3-vector norm)
 
 for ordinary and for wild poses, and prints max / rms of error / bound: the statistics of independent roundings.  The kernel's
-threshold is no longer built on them but on a hard bound (csrc/body_model.hip: LBS_FIX_SLACK_M, mirrored by tests/lbs_mode3.py,
+threshold is no longer built on them but on a hard bound (csrc/lbs.h: LBS_FIX_SLACK_M, mirrored by tests/lbs_mode3.py,
 whose adversarial body puts every rounding error on the same side: ~4e-4 m, four times the old statistical band).
 Run: python scripts/emulate_lbs_fixup.py [num_poses]            the fp16 blend product
      python scripts/emulate_lbs_fixup.py skin [num_poses]       the two-plane matrix-pipe skinning (lbs_epilogue_cell): weights and

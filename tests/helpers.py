@@ -116,7 +116,7 @@ def level_set_band():
     """Distance from the SDF's zero level set (metres) inside which a penetration count of the HIP path may differ from a CPU
     evaluation: 2e-5 (fp32 round-off of the vertex chain) in EVERY blend mode - mode 3 ("f16mix", the library default) classifies
     with its fp16 product and re-evaluates in fp32 every vertex inside a hard bound of that product's error, whatever the rounding
-    pattern (csrc/body_model.hip: LBS_FIX_SLACK_M; tests/test_lbs_adversarial_gpu.py holds it to a body built to defeat a
+    pattern (csrc/lbs.h: LBS_FIX_SLACK_M; tests/test_lbs_adversarial_gpu.py holds it to a body built to defeat a
     statistical bound)."""
     return 2e-5
 

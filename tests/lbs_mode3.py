@@ -1,4 +1,4 @@
-"""Float64 emulation of the cheap evaluation of LBS blend mode 3 ("f16mix", csrc/body_model.hip), the kernel's fix-up band, and a
+"""Float64 emulation of the cheap evaluation of LBS blend mode 3 ("f16mix", csrc/lbs_fused3.hip), the kernel's fix-up band, and a
 body built to defeat a statistical band.  TEST INFRASTRUCTURE ONLY (nothing under egogen_amd/ imports it).
 
 The count-only vertex tiles of mode 3 evaluate the blend GEMM as
@@ -15,7 +15,7 @@ import torch
 
 from egogen_amd import synth
 
-# mirrors of csrc/body_model.hip (tests/test_lbs_mode3_cpu.py::test_band_constants_mirror_the_kernel)
+# mirrors of csrc/lbs.h (tests/test_lbs_mode3_cpu.py::test_band_constants_mirror_the_kernel)
 LBS_FIX_SLACK_M = 3e-6
 LBS_TWO_PLANE_ERR = 1.2e-5
 LBS_ACC_ADDS_OFFSETS = 496.0
@@ -109,7 +109,7 @@ def model_consts(bm):
 
 
 def band(consts, F, betas, tn, skin=True):
-    """fix_e of one body (metres): the pose kernel's hard bound (csrc/body_model.hip, LBS_FIX_SLACK_M), float64.
+    """fix_e of one body (metres): the pose kernel's hard bound (csrc/lbs_pose.hip; csrc/lbs.h, LBS_FIX_SLACK_M), float64.
     F [51, 9] fp32 features, betas [10], tn = max_j |t_j| of the body's joint transforms.  Returns (total, terms)."""
     F = np.asarray(F, np.float32).reshape(-1)
     Ft = f16(F)

@@ -13,7 +13,7 @@ def _band(mode):
     """Distance from the zero level set (metres) inside which a penetration count may differ from the oracle's: 2e-5 = fp32
     round-off of the vertex chain - in EVERY mode.  "f16mix" evaluates the pose-corrective columns of the count-only tiles as one
     fp16 product (~4 um rms, ~22 um worst case on this body), but only to classify: a vertex whose SDF value is closer to zero than
-    a hard bound of that error (every rounding pattern, csrc/body_model.hip: LBS_FIX_SLACK_M) is re-evaluated in fp32 (lbs_fix_process),
+    a hard bound of that error (every rounding pattern, csrc/lbs.h: LBS_FIX_SLACK_M) is re-evaluated in fp32 (lbs_fix_process),
     so its counts are held to the same band as the fp32-equivalent modes.  Positions (markers, joints, landmarks) are held to 2e-5 m in every mode."""
     return 2e-5
 
@@ -417,7 +417,7 @@ def test_lbs_blend_mode_accuracy_report():
 @pytest.mark.parametrize("tile", [1, 2])
 def test_lbs_mixed_blend_reevaluates_what_its_fp16_product_cannot_decide(tile):
     """Mode 3 ("f16mix") classifies the count-only vertices with one fp16 product and re-evaluates in fp32 those whose SDF value
-    lies inside the product's error band (csrc/body_model.hip: lbs_fix_process).  On bodies standing IN the obstacle (thousands of
+    lies inside the product's error band (csrc/lbs_epilogue.h: lbs_fix_process).  On bodies standing IN the obstacle (thousands of
     counted vertices per body): (i) counts within the 2e-5 m band of the float64 oracle - the band of the fp32 modes; (ii) the
     kernel did re-evaluate vertices, and only a few per thousand of what it counted; (iii) the fp16 product alone decides
     vertices of this workload differently from the oracle (float64 emulation of its operand rounding, tests/lbs_mode3.py, first
@@ -537,7 +537,7 @@ def test_lbs_tile_lists_skip_only_what_contributes_nothing(blend_mode):
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
-# Free-space culling of SDF work items (csrc/body_model.hip: egx_lbs_cull_kernel): results must be BIT-identical to the launch
+# Free-space culling of SDF work items (csrc/lbs_cull.hip: egx_lbs_cull_kernel): results must be BIT-identical to the launch
 # that walks every item.
 # ---------------------------------------------------------------------------------------------------------------------------
 def _culling(on):

@@ -9,17 +9,17 @@ import pytest
 from egogen_amd import synth
 from tests import lbs_mode3 as L
 
-SRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "egogen_amd", "csrc", "body_model.hip")
+CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "egogen_amd", "csrc")
 
 
 def test_band_constants_mirror_the_kernel():
-    src = open(SRC).read()
+    src = open(os.path.join(CSRC, "lbs.h")).read()     # the band constants
     for name in ("LBS_FIX_SLACK_M", "LBS_TWO_PLANE_ERR", "LBS_ACC_ADDS_OFFSETS", "LBS_ACC_ADDS_LAST", "LBS_FIX_MARGIN", "LBS_SKIN_ERR"):
         m = re.search(r"constexpr float %s = ([0-9.eE+-]+)f;" % name, src)
         assert m, name
         assert float(m.group(1)) == getattr(L, name), name
     # the columns of the fp16 k-steps: k-steps 1..28 of 16 columns (M4_BASE_PIECES / egx_m4_feat_piece)
-    assert "k0 + e >= 16 && k0 + e < 464" in src
+    assert "k0 + e >= 16 && k0 + e < 464" in open(os.path.join(CSRC, "lbs_pose.hip")).read()
     assert int(L.FP16_COL.sum()) == 28 * 16
 
 
