@@ -1,4 +1,4 @@
-// Internal launch helpers shared by nets.hip / prior.hip (not part of the C ABI).
+// Internal launch helpers shared by the network files (not part of the C ABI).  Device helpers of the dense3 kernels: d3.h.
 #pragma once
 #include "egx_common.h"
 
@@ -18,7 +18,8 @@ int egx_launch_posenc(hipStream_t st, const float* dist, const float* time, int 
 // y[t][a][c] += y[t-1][a][c] for t = 0..T-1 with y[-1] = x_last[a][c] (row stride x_ld): residual chain of the decoder
 void egx_launch_frame_scan(hipStream_t st, float* y, const float* x_last, int x_ld, int A, int width, int T);
 
-// ---- dense3.hip: dense layers on the bf16 matrix pipe, operands as three bf16 planes in MFMA fragment order -------------
+// ---- dense layers on the bf16 matrix pipe, operands as three bf16 planes in MFMA fragment order (d3.h) -----------------
+// pack3.hip
 // Packed image of a row-major fp32 matrix [R, K]: [2 ceil(R/32) row tiles of 16][K/32 k-steps][3 planes][64 lanes] x 16 bytes.
 struct D3Pack {
   const float* src;
@@ -29,7 +30,7 @@ struct D3Pack {
 };
 void egx_launch_pack3(hipStream_t st, const D3Pack* jobs, int njobs);  // njobs <= 4, one launch
 
-// out = act(A B^T + bias) + res.  A: packed activations (k-steps sa0 .. sa0 + S of a buffer with SA k-steps per row tile);
+// dense3.hip: out = act(A B^T + bias) + res.  A: packed activations (k-steps sa0 .. sa0 + S of a buffer with SA k-steps per row tile);
 // B: packed weights [N, K = 32 S].  Outputs: fp32 row-major `out` and / or packed `out3` (the consumer's A operand: this
 // layer's 32-column tile nt is k-step s30 + nt of a buffer with S3 k-steps per row tile; needs N % 32 == 0).  `batches`
 // > 1: the same layer for several row blocks (A advances by batch_strideA fragments, out3 by batch_stride3, fp32 rows by
@@ -52,7 +53,7 @@ struct D3Plain {
   size_t batch_strideA = 0, batch_stride3 = 0;
   int batch_rows_out = 0;
   int prec = 0;   // 0: three planes, six partial products (fp32-equivalent); 2: two planes, three products (16 operand bits);
-                  // 1: leading plane only (operands rounded to bf16).  See dense3.hip::d3_planes.
+                  // 1: leading plane only (operands rounded to bf16).  See d3.h::d3_planes.
   // ---- training (update3.hip)
   float* out_act = nullptr;       // fp32 [M, N] (ld ldact): the activation BEFORE the residual is added (saved for backward)
   int ldact = 0;
@@ -79,7 +80,8 @@ void egx_launch_posenc3(hipStream_t st, const float* dist, const float* time, in
 
 // ---- roles shared by the update's stand-alone kernels (egx_pack3_table_kernel, egx_posenc3_kernel, egx_adv_stats_kernel) and by
 // egx_update_head_kernel (update3.hip), which runs them on GATHERED rows in one launch.  One body per role, parameterised on the
-// row map, so that the two forms cannot drift apart (EGX_UPDATE_HEAD=0 / 1 are held to bit equality).
+// row map, so that the two forms cannot drift apart (EGX_UPDATE_HEAD=0 / 1 are held to bit equality).  The positional-encoding
+// role splits its values into planes and therefore lives in d3.h (egx_posenc3_role).
 #if defined(__HIPCC__)
 struct EgxRowsIdentity {   // source row of row r: r
   __device__ __forceinline__ size_t operator()(int r) const { return (size_t)r; }
@@ -92,64 +94,6 @@ struct EgxRowsGathered {   // row idx[r] of the rollout, clamped to its rows: a 
     return (size_t)min(max(s, 0LL), (long long)num_src - 1);
   }
 };
-
-// positional_encoding (models_policy_ppo.py:276-285) of dist and time, work of block `bid` (four fragments): the 128 columns as
-// fp32 into `out` (row stride ld) and packed into k-steps s0 .. s0 + 3 of `out3`; blocks past those, with out3T != null: the same
-// columns as rows col0T .. col0T + 127 of the transposed image (reduction index = batch row).  `split`: x[8] -> three bf16 planes.
-template <class Rows, class Split>
-__device__ __forceinline__ void egx_posenc3_role(const float* __restrict__ dist, const float* __restrict__ time, int n,
-                                                 float* __restrict__ out, int ld, bf16x8* __restrict__ out3, int S3, int s0,
-                                                 bf16x8* __restrict__ out3T, int S3T, int col0T, int bid, const Rows& rows,
-                                                 const Split& split) {
-  int frag = bid * 4 + (threadIdx.x >> 6);
-  const int lane = threadIdx.x & 63;
-  const int RT = 2 * ((n + 31) >> 5);
-  if (frag >= RT * 4) {
-    frag -= RT * 4;
-    const int Sn = (n + 31) >> 5;
-    if (!out3T || frag >= 8 * Sn) return;
-    const int t = frag / Sn, s = frag % Sn;
-    const int c = 16 * t + (lane & 15), m0 = 32 * s + 8 * (lane >> 4);
-    float x[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      const int m = m0 + e;
-      float v = 0.f;
-      if (m < n) {
-        const size_t sm = rows(m);
-        const float f = ((c < 64) ? dist[sm] : time[sm]) * exp2f((float)((c & 63) >> 1));
-        v = (c & 1) ? cosf(f) : sinf(f);
-      }
-      x[e] = v;
-    }
-    bf16x8 pl[3];
-    split(x, pl);
-    bf16x8* o = out3T + ((size_t)((col0T >> 4) + t) * S3T + s) * 3 * 64 + lane;
-#pragma unroll
-    for (int p = 0; p < 3; ++p) o[p * 64] = pl[p];
-    return;
-  }
-  const int rt = frag >> 2, s = frag & 3;
-  const int row = rt * 16 + (lane & 15), c0 = s * 32 + 8 * (lane >> 4);
-  const size_t srow = row < n ? rows(row) : 0;
-  float x[8];
-#pragma unroll
-  for (int e = 0; e < 8; ++e) {
-    const int c = c0 + e;
-    float v = 0.f;
-    if (row < n) {
-      const float f = ((c < 64) ? dist[srow] : time[srow]) * exp2f((float)((c & 63) >> 1));
-      v = (c & 1) ? cosf(f) : sinf(f);
-      out[(size_t)row * ld + c] = v;
-    }
-    x[e] = v;
-  }
-  bf16x8 pl[3];
-  split(x, pl);
-  bf16x8* o = out3 + ((size_t)rt * S3 + s0 + s) * 3 * 64 + lane;
-#pragma unroll
-  for (int p = 0; p < 3; ++p) o[p * 64] = pl[p];
-}
 
 // mean and UNBIASED standard deviation of the minibatch advantages (ppo_policy.py:195-197: adv.mean(), adv.std()); one
 // workgroup of 256 threads, two-pass variance, double accumulation in a fixed order
@@ -183,7 +127,7 @@ __device__ __forceinline__ void egx_adv_stats_role(const float* __restrict__ adv
 }
 #endif
 
-// One GRU cell step (gate order r, z, n; weights [3H, K] packed): see egx_gru3_kernel.
+// One GRU cell step (gate order r, z, n; weights [3H, K] packed): see egx_gru3_kernel (gru3.hip).
 // Aliasing contract: a buffer may be both an input and an output of one launch only ELEMENT FOR ELEMENT (gi_out == gi_in with
 // the same layout - the decoder's running sum -, h_out == h_prev with ldo == ldh).  The kernel reads everything an element
 // needs (gi_in, the biases, h_prev) before the reduction and stores the element's outputs after its last load, every element in
@@ -217,7 +161,7 @@ struct D3Gru {
 int egx_launch_gru3(hipStream_t st, const D3Gru& g);
 int egx_launch_gru3_pair(hipStream_t st, const D3Gru& g0, const D3Gru& g1);   // two cells (same launch)
 
-// Fused regressor on packed weights (dense3.hip): in_fc split into its marker / xb / betas column blocks
+// Fused regressor on packed weights (regressor3.hip): in_fc split into its marker / xb / betas column blocks
 struct RegWeights3 {
   const bf16x8 *in_m, *in_xb, *in_b3;   // packed in_fc[:, 0:201] (7 k-steps), [:, 201:360] (5), [:, 360:370] (1)
   const float* in_b;
@@ -228,7 +172,7 @@ struct RegWeights3 {
 };
 int egx_launch_regressor3(hipStream_t st, const RegWeights3& w, const float* Y, const float* betas, int A, int M, float* out_Yb);
 
-// Fused VPoser encoder mean on packed weights (dense3.hip): fc1 [512,63] (2 k-steps), fc2 [512,512] (16), mu [32,512] (16)
+// Fused VPoser encoder mean on packed weights (vposer3.hip): fc1 [512,63] (2 k-steps), fc2 [512,512] (16), mu [32,512] (16)
 struct VpWeights3 {
   const bf16x8 *fc1, *fc2, *mu;
   const float *b1, *b2, *bmu;

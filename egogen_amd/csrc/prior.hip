@@ -2,7 +2,7 @@
 // the VPoser encoder, each as one C call that enqueues its chain of fused dense-layer kernels.
 #include <algorithm>
 #include <atomic>
-#include "egx_nets.h"
+#include "d3.h"
 
 namespace {
 constexpr int H = 256, ZD = 128, MK = 201, T_PRED = 18;
@@ -25,27 +25,26 @@ size_t carve_bytes(std::initializer_list<size_t> nfloats) {
 }  // namespace
 
 // packed-activation buffers of the dense3 decoder path: row tiles (of 16) x k-steps x 3072 bytes
-constexpr size_t FRAG_FLOATS = 3 * 64 * 4;   // one (row tile, k-step): three planes of 64 lanes x 16 bytes, in floats
-inline size_t rt16(int A) { return 2 * (size_t)egx_ceil_div(A, 32); }
+constexpr size_t FRAG_FLOATS = D3_FRAG_BYTES / sizeof(float);   // one (row tile, k-step) of an image, in floats
 constexpr int S_MK = 7, S_H = 8, S_HZ = 12, S_512 = 16;   // k-steps of 201 / 256 / 384 / 512 columns
 
 extern "C" size_t egx_sample_prior_workspace_bytes(int A) {
   if (A <= 0) return 0;
   const size_t a = A;
-  const size_t rt = rt16(A);
+  const size_t rt = d3_img_tiles(A);
   return carve_bytes({rt * S_MK * FRAG_FLOATS, rt * S_MK * FRAG_FLOATS, rt * S_HZ * FRAG_FLOATS,
                       rt * S_H * FRAG_FLOATS, rt * S_512 * FRAG_FLOATS, rt * S_H * FRAG_FLOATS,
                       rt * S_H * FRAG_FLOATS, rt * S_H * FRAG_FLOATS, T_PRED * rt * S_H * FRAG_FLOATS,
                       a * 3 * H, a * 3 * H, a * H, a * H, a * H});
 }
 
-// The decoder on packed operands (dense3.hip): every activation between two products lives as three bf16 planes in MFMA
+// The decoder on packed operands (d3.h): every activation between two products lives as three bf16 planes in MFMA
 // fragment order, written by its producer; the GRU cell is one launch.
 static int sample_prior_packed(const egx_prior_weights* w, const float* x0, const float* x1, int x_ld, const float* z, int A,
                                float* out_Y, void* workspace, size_t workspace_bytes, hipStream_t st) {
   const egx_prior_packed3& P = *w->packed3;
   Carver cv(workspace, workspace_bytes);
-  const size_t rt = rt16(A);
+  const size_t rt = d3_img_tiles(A);
   auto take3 = [&](size_t ksteps) { return reinterpret_cast<bf16x8*>(cv.take(rt * ksteps * FRAG_FLOATS)); };
   bf16x8* x0p = take3(S_MK);
   bf16x8* x1p = take3(S_MK);
@@ -169,7 +168,7 @@ constexpr int PS_ST = 13, PS_EGO = 1, PS_HD = 16, PS_CAT = 36;   // k-steps of 4
 extern "C" size_t egx_policy_workspace_bytes(int n) {
   if (n <= 0) return 0;
   const size_t m = n;
-  const size_t rt = rt16(n);
+  const size_t rt = d3_img_tiles(n);
   return carve_bytes({rt * PS_ST * FRAG_FLOATS, rt * PS_ST * FRAG_FLOATS, rt * PS_EGO * FRAG_FLOATS,
                                           rt * PS_EGO * FRAG_FLOATS, rt * PS_HD * FRAG_FLOATS, rt * PS_HD * FRAG_FLOATS,
                                           rt * PS_CAT * FRAG_FLOATS, rt * PS_CAT * FRAG_FLOATS, rt * PS_CAT * FRAG_FLOATS,
@@ -185,7 +184,7 @@ extern "C" int egx_policy_set_precision(int bf16) {
 }
 extern "C" int egx_policy_get_precision(void) { return g_policy_bf16.load(); }
 
-// The policy networks on packed operands (dense3.hip): GAMMAPolicyBase (two 2-step GRUs + positional encoding, outputs written
+// The policy networks on packed operands (d3.h): GAMMAPolicyBase (two 2-step GRUs + positional encoding, outputs written
 // side by side into one [hx | he | pe] buffer), then the actor and critic MLP blocks layer by layer in shared launches.
 static int policy_forward_packed(const egx_policy_weights* w, const float* state, const float* ego, const float* dist,
                                  const float* time, int n, float* out_mu, float* out_logvar, float* out_value, void* workspace,
@@ -193,7 +192,7 @@ static int policy_forward_packed(const egx_policy_weights* w, const float* state
   const egx_policy_packed3& P = *w->packed3;
   const int prec = g_policy_bf16.load();
   Carver cv(workspace, workspace_bytes);
-  const size_t rt = rt16(n), m = n;
+  const size_t rt = d3_img_tiles(n), m = n;
   auto take3 = [&](size_t ksteps) { return reinterpret_cast<bf16x8*>(cv.take(rt * ksteps * FRAG_FLOATS)); };
   bf16x8* s0p = take3(PS_ST);
   bf16x8* s1p = take3(PS_ST);

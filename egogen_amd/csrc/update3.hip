@@ -14,25 +14,9 @@
 #include <algorithm>
 #include <cstring>
 #include <vector>
-#include "egx_nets.h"
+#include "d3.h"
 
 namespace {
-
-typedef __bf16 bf16v8 __attribute__((ext_vector_type(8)));
-__device__ __forceinline__ void u3_split(const float (&x)[8], bf16x8 (&pl)[3]) {
-  float r[8];
-#pragma unroll
-  for (int p = 0; p < 3; ++p) {
-    bf16v8 h;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      const float v = (p == 0) ? x[e] : r[e];
-      h[e] = (__bf16)v;
-      r[e] = v - (float)h[e];
-    }
-    pl[p] = __builtin_bit_cast(bf16x8, h);
-  }
-}
 
 // ---- table-driven packing: any number of matrices per launch, optionally transposed, optionally with a row of ones ----------
 struct PackEntry {
@@ -78,7 +62,7 @@ __device__ __forceinline__ void u3_pack_fragment(const PackEntry& e, const float
     }
   }
   bf16x8 pl[3];
-  u3_split(x, pl);
+  d3_split(x, pl);
   bf16x8* o = e.dst + ((size_t)rt * e.S_total + e.s0 + s) * 3 * 64 + lane;
 #pragma unroll
   for (int p = 0; p < 3; ++p)
@@ -120,7 +104,7 @@ __global__ __launch_bounds__(256) void egx_pack3_table_kernel(const PackEntry* _
 #pragma unroll
       for (int q = 0; q < 8; ++q) sb[16 * t + r][8 * kg + q] = x[q];
       bf16x8 pl[3];
-      u3_split(x, pl);
+      d3_split(x, pl);
       bf16x8* o = e.dst + ((size_t)(2 * bi + t) * e.S_total + e.s0 + bj) * 3 * 64 + lane;
 #pragma unroll
       for (int p = 0; p < 3; ++p)
@@ -132,7 +116,7 @@ __global__ __launch_bounds__(256) void egx_pack3_table_kernel(const PackEntry* _
 #pragma unroll
       for (int q = 0; q < 8; ++q) x[q] = sb[8 * kg + q][16 * t + r];
       bf16x8 pl[3];
-      u3_split(x, pl);
+      d3_split(x, pl);
       bf16x8* o = e.dst2 + ((size_t)(2 * bj + t) * e.S_total2 + bi) * 3 * 64 + lane;
 #pragma unroll
       for (int p = 0; p < 3; ++p)
@@ -199,10 +183,9 @@ __global__ __launch_bounds__(256) void egx_update_head_kernel(HeadArgs a) {
     return;
   }
   bid -= a.b_pack;
-  if (bid < a.b_pe) {   // ---- positional encoding (egx_posenc3_kernel, dense3.hip) of the gathered dist / time
+  if (bid < a.b_pe) {   // ---- positional encoding (egx_posenc3_kernel, pack3.hip) of the gathered dist / time
     if (bid == 0 && threadIdx.x < 6) a.log[6 * (size_t)k + threadIdx.x] = 0.f;
-    egx_posenc3_role(a.dist, a.time, a.n, a.pe_out, a.pe_ld, a.pe3, a.S3, a.s0, a.pe3T, a.S3T, a.col0T, bid, rows,
-                     [](const float (&x)[8], bf16x8 (&pl)[3]) { u3_split(x, pl); });
+    egx_posenc3_role(a.dist, a.time, a.n, a.pe_out, a.pe_ld, a.pe3, a.S3, a.s0, a.pe3T, a.S3T, a.col0T, bid, rows);
     return;
   }
   bid -= a.b_pe;
@@ -219,10 +202,6 @@ __global__ __launch_bounds__(256) void egx_update_head_kernel(HeadArgs a) {
   if (!a.stats) return;
   egx_adv_stats_role(a.adv, a.n, a.stats, rows);   // egx_adv_stats_kernel's body on adv[idx[.]]: same additions, same order
 }
-
-inline int img_tiles(int rows) { return 2 * egx_ceil_div(rows, 32); }   // 16-row tiles, even count
-inline size_t img_frags(int rows, int red) { return (size_t)img_tiles(rows) * egx_ceil_div(red, 32); }
-constexpr size_t FRAG_BYTES = 3 * 64 * 16;
 
 // ---- GRU cell backward (torch.nn.GRU gate order r, z, n) with packed outputs ---------------------------------------------
 //   r = s(gi_r + gh_r), z = s(gi_z + gh_z), nn = tanh(gi_n + r gh_n), h = (1 - z) nn + z hp
@@ -308,7 +287,7 @@ __global__ __launch_bounds__(256) void egx_gru_bwd3_kernel(GruBwd2 two) {
       o = a.dgh_r + ((size_t)(2 * mt + half) * S + (g * H) / 32 + ct) * 3 * 64 + lane;
     }
     bf16x8 pl[3];
-    u3_split(x, pl);
+    d3_split(x, pl);
 #pragma unroll
     for (int p = 0; p < 3; ++p) o[p * 64] = pl[p];
   }
@@ -378,7 +357,7 @@ int upload_table(std::vector<PackEntry>& v, PackEntry** dev, int* frags) {
     } else {
       const int rows = e.transpose ? e.cols + (e.ones_row >= 0 ? 1 : 0) : e.red;
       const int red = e.transpose ? e.red : e.cols;
-      run += (int)img_frags(rows, red);
+      run += (int)d3_img_frags(rows, red);
     }
     e.frag_end = run;
   }
@@ -390,14 +369,13 @@ int upload_table(std::vector<PackEntry>& v, PackEntry** dev, int* frags) {
 void run_table(hipStream_t st, const PackEntry* tab, int n, int frags, int nplanes = 3) {
   hipLaunchKernelGGL(egx_pack3_table_kernel, dim3(egx_ceil_div(frags, 4)), dim3(256), 0, st, tab, n, nplanes);
 }
-inline int planes_of(int prec) { return prec == 0 ? 3 : (prec == 2 ? 2 : 1); }
 
 // carve every buffer of a handle; with ar.base == nullptr this only measures
 void layout(egx_policy_train* h) {
   const int n = h->n, Sn = h->Sn;
   Arena& ar = h->ar;
   ar.off = 0;
-  auto img = [&](int rows, int red) { return static_cast<bf16x8*>(ar.take(img_frags(rows, red) * FRAG_BYTES)); };
+  auto img = [&](int rows, int red) { return static_cast<bf16x8*>(ar.take(d3_img_frags(rows, red) * D3_FRAG_BYTES)); };
   auto f32 = [&](size_t count) { return static_cast<float*>(ar.take(count * sizeof(float))); };
   for (int e = 0; e < 2; ++e) {
     Encoder& E = h->enc[e];
@@ -547,7 +525,7 @@ extern "C" int egx_policy_train_refresh(egx_policy_train* h, void* stream) {
   EGX_REQUIRE(h, "null handle");
   // the weight images are read by this chain (h->prec) and by the rollout forward (egx_policy_get_precision): only the planes
   // one of them uses are written
-  const int planes = std::max(planes_of(h->prec), planes_of(egx_policy_get_precision()));
+  const int planes = std::max(d3_planes(h->prec), d3_planes(egx_policy_get_precision()));
   run_table(static_cast<hipStream_t>(stream), h->tab_weights, h->n_weights, h->frags_weights, planes);
   EGX_HIP_CHECK(hipGetLastError());
   return EGX_OK;
@@ -617,7 +595,7 @@ static void launch_head(egx_policy_train* h, const egx_update_head* a, hipStream
   constexpr int S_HD = HD / 32, S_CAT = CAT / 32;
   const int n = h->n, Sn = h->Sn;
   HeadArgs k;
-  k.tab = h->tab_inputs; k.n_tab = h->n_inputs; k.frags_tab = h->frags_inputs; k.nplanes = planes_of(h->prec);
+  k.tab = h->tab_inputs; k.n_tab = h->n_inputs; k.frags_tab = h->frags_inputs; k.nplanes = d3_planes(h->prec);
   k.state = a->state; k.ego = a->egosensing;
   k.perm = reinterpret_cast<const long long*>(a->perm); k.cursor = a->cursor; k.max_cursor = a->max_cursor; k.n = n;
   k.num_src = a->num_src_rows;
@@ -693,7 +671,7 @@ static int train_step_parts(egx_policy_train* h, const float* dist, const float*
   if (hd) {
     launch_head(h, hd, st);   // gather, statistics, input images, positional encoding, cleared loss sums: one launch
   } else {
-    run_table(st, h->tab_inputs, h->n_inputs, h->frags_inputs, planes_of(h->prec));
+    run_table(st, h->tab_inputs, h->n_inputs, h->frags_inputs, d3_planes(h->prec));
     egx_launch_posenc3(st, dist, time, n, h->catf + 2 * HD, CAT, h->cat_r, S_CAT, 2 * S_HD, h->catT, Sn, 2 * HD, out_terms);   // also clears the loss sums
   }
   {
@@ -758,7 +736,7 @@ static int train_step_parts(egx_policy_train* h, const float* dist, const float*
                                eps_clip, vf_coef, ent_coef, n, h->br[0].ghead, h->br[1].ghead, out_terms, st, hd ? hd->cursor : nullptr,
                                hd ? hd->max_cursor : 0);
   if (rc) return rc;
-  run_table(st, h->tab_loss, h->n_loss, h->frags_loss, planes_of(h->prec));
+  run_table(st, h->tab_loss, h->n_loss, h->frags_loss, d3_planes(h->prec));
   // ================= backward =================
   // Input-gradient products form the dependent chain (out_fc -> unit 2 -> unit 1 -> GRU cells); each layer's weight-gradient
   // product follows the launch that left its gradient image behind.  (Weight gradients on a second stream beside the chain,

@@ -230,7 +230,7 @@ class GAMMAPrimitiveCombo(nn.Module):
             self._comb_b = (wy @ p.d_out.bias.double()).float().contiguous()
         w.d_comb_w, w.d_comb_b = _p(self._comb_w), _p(self._comb_b)
         # the decoder's and the regressor's dense weights as three bf16 planes in MFMA fragment order (egx_prior_packed3,
-        # csrc/dense3.hip): what egx_sample_prior computes from
+        # csrc/d3.h): what egx_sample_prior computes from
         if p.x_enc.weight_ih_l0.is_cuda:
             self._p3_bufs = {}
             p3 = _lib.PriorPacked3()

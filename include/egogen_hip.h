@@ -375,7 +375,7 @@ int egx_posenc(const float* dist, const float* time, int num_agents, float* out,
  *     3 recurrences of a 10-block ResNet, 6D -> axis-angle).
  * Weight pointers alias the torch parameters of the same state_dict keys (`predictor.*`, `regressor.*`).
  * ------------------------------------------------------------------------------------------- */
-/* "Packed" matrices of the rollout dense layers (csrc/dense3.hip).  The rollout networks run their products on the bf16
+/* "Packed" matrices of the rollout dense layers (csrc/d3.h; written by csrc/pack3.hip).  The rollout networks run their products on the bf16
  * matrix pipe with every fp32 operand carried as three bf16 terms (x = hi + mid + lo, six partial products, fp32
  * accumulation: 2^-24 relative, the arithmetic of an fp32 product).  A packed image of a row-major fp32 matrix [R, K] is
  *   [2 ceil(R/32) row tiles of 16][ceil(K/32) k-steps][3 planes][64 lanes] x 8 bf16,

@@ -3,7 +3,7 @@
 //
 // Shape of the motion prior's decoder at 512 agents: 16 row tiles of 32 agents; a layer = [32 x K] x [K x N] per tile with
 // K, N in {256, 512}; every fp32 operand as three bf16 planes in MFMA fragment order (6 bytes per element), six partial products
-// per k (the arithmetic of csrc/dense3.hip).  One workgroup per CU (256 threads): G = 16 workgroups own one row tile - N / G
+// per k (the arithmetic of csrc/d3.h).  One workgroup per CU (256 threads): G = 16 workgroups own one row tile - N / G
 // output columns each - and sit on ONE XCD (workgroups are dealt to the XCDs round-robin: block b -> XCD b % 8), so the tile's
 // activations are exchanged through that XCD's L2:
 //    consume  the whole [32 x K] tile of the previous layer (48 KB at K = 256, 96 KB at K = 512), straight into MFMA registers

@@ -1,7 +1,7 @@
 """The fp32 yardstick of the rollout-side networks (shared by test_fp32_yardstick_cpu.py and test_fp32_equivalence_gpu.py).
 
 egx_policy_forward at precision 0, egx_sample_prior and egx_vposer_encode carry every fp32 operand of a matrix product as three
-bf16 planes (csrc/dense3.hip), which is claimed to be fp32-equivalent.  The claim is held to what fp32 itself costs on the same
+bf16 planes (csrc/d3.h), which is claimed to be fp32-equivalent.  The claim is held to what fp32 itself costs on the same
 weights and inputs: the oracle (oracle/nets.py) is evaluated in float64 and in float32, and per output group
 
     bound = R * max|oracle32 - oracle64| + 2^-23 * max|oracle64|          R = 3 (test_trainer_gpu.py: _P3_MODES["f32"])

@@ -1,4 +1,4 @@
-"""The epilogues of egx_dense3_kernel / egx_gru3_kernel (csrc/dense3.hip) request everything they read from memory as one batch
+"""The epilogues of egx_dense3_kernel / egx_gru3_kernel (csrc/dense3.hip, csrc/gru3.hip) request everything they read from memory as one batch
 ahead of the reduction barrier and store everything after the last load.  A prefetch taken for the wrong element, a load or a
 store outside the matrix, or a store that went missing shows at the smallest shapes with ragged tiles, so these tests drive the
 three entry points built on the two kernels at such shapes:

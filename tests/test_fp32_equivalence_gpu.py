@@ -1,5 +1,5 @@
 """The rollout-side networks are fp32-equivalent: egx_policy_forward at precision 0, egx_sample_prior and egx_vposer_encode
-(three bf16 planes per operand, csrc/dense3.hip) are at most R = 3 times as far from the float64 oracle as the float32 oracle
+(three bf16 planes per operand, csrc/d3.h) are at most R = 3 times as far from the float64 oracle as the float32 oracle
 is, plus one ulp of the stored result, per output group (tests/precision_yardstick.py).  The north-star tolerances of the other
 tests of these entry points (1e-4, 2e-4, 2e-5 relative) would let a two-plane kernel through on every output but the regressed
 rotations; this bound does not: test_fp32_yardstick_cpu.py shows it on the CPU for the very inputs used here, and

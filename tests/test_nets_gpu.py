@@ -100,7 +100,7 @@ def test_sample_prior_matches_oracle():
 
 
 def test_regressor_row_tile_variants_agree(tmp_path):
-    """The fused regressor takes 16, 32 or 48 rows per workgroup depending on the batch (csrc/dense3.hip, egx_launch_regressor3);
+    """The fused regressor takes 16, 32 or 48 rows per workgroup depending on the batch (csrc/regressor3.hip, egx_launch_regressor3);
     an element's arithmetic does not depend on that, so the three variants (forced with EGX_R3_ROWTILES, one process each: the
     switch is read once) give bit-identical parameters on a ragged batch."""
     import subprocess, sys, os
