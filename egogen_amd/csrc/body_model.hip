@@ -695,13 +695,8 @@ extern "C" int egx_lbs_joints(const egx_body_model* m, const float* xb, const fl
 }
 
 // ------------------------------------------------------------------------------------------------
-// SDF scene sets: the per-scene records of egx_lbs_forward_scenes, made once
+// SDF scene sets: the per-scene records of egx_lbs_forward_scenes, made once (struct egx_sdf_scene_set: egx_common.h)
 // ------------------------------------------------------------------------------------------------
-struct egx_sdf_scene_set {
-  int S = 0;
-  egx_sdf_grid dims{};          // scene 0's descriptor: the grid dimensions every scene of the set shares
-  SdfSceneDev* table = nullptr; // device [S]
-};
 
 extern "C" int egx_sdf_scene_set_create(const egx_sdf_grid* scenes, int num_scenes, egx_sdf_scene_set** out) {
   EGX_REQUIRE(scenes && out, "null argument");

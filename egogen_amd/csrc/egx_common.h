@@ -72,6 +72,13 @@ __host__ __device__ inline SdfDev egx_sdf_scene(const SdfDev& dims, const SdfSce
   s.cx = e.cx; s.cy = e.cy; s.cz = e.cz; s.scale = e.scale;
   return s;
 }
+// The opaque egx_sdf_scene_set of the header (made by egx_sdf_scene_set_create, body_model.hip; read by the LBS launcher and by
+// the penalty calls of sdf_grad.hip).
+struct egx_sdf_scene_set {
+  int S = 0;
+  egx_sdf_grid dims{};          // scene 0's descriptor: the grid dimensions every scene of the set shares
+  SdfSceneDev* table = nullptr; // device [S]
+};
 
 // Free-space pyramid behind the bracket table (same buffer, after the float2 entries, 256-byte aligned): level l = 1..4 holds,
 // per block of 2^l x 2^l x 2^l PADDED bracket cells, the maximum of their `max` entries.  A box of padded cells whose pyramid

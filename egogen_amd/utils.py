@@ -12,6 +12,7 @@ import torch
 
 from . import _lib
 from .body_model import SdfScene
+from .scene_sdf import sdf_values
 
 _scene_cache = {}
 
@@ -29,13 +30,21 @@ def _scene_of(sdf_dict) -> SdfScene:
     return sc
 
 
-def calc_sdf(vertices: torch.Tensor, sdf_dict, return_gradient: bool = False) -> torch.Tensor:
-    """vertices[B,V,3] (cuda) , sdf_dict{'center','scale','sdf'} or SdfScene -> [B,V]; negative = penetrating."""
-    if return_gradient:
-        raise NotImplementedError("the reference's gradient branch is commented out (utils.py:69-81)")
+def calc_sdf(vertices: torch.Tensor, sdf_dict, return_gradient: bool = False):
+    """vertices[B,V,3] (cuda) , sdf_dict{'center','scale','sdf'} or SdfScene -> [B,V]; negative = penetrating.
+
+    Under grad mode, with vertices that require grad, the result is an autograd node (once differentiable) that carries the
+    gradient the reference's `F.grid_sample` carries (`egx_sdf_value_grad`).  `return_gradient=True` returns (values[B,V],
+    gradient[B,V,3]) from one launch: the analytic, unnormalised derivative of the returned values with respect to the vertices,
+    in value per metre - exactly 0 along an axis on which the border clamp holds the vertex.  (The reference's branch of that
+    name, utils.py:69-81, looked up and normalised a precomputed `gradient_grid`; it is commented out and never ran.)"""
     if vertices.dim() != 3 or vertices.shape[-1] != 3:
         raise ValueError("vertices must be [B,V,3]")
+    if not vertices.is_cuda:
+        raise _lib.EgxError("vertices must be on the HIP device - calc_sdf has no CPU fallback")
     sc = _scene_of(sdf_dict)
+    if return_gradient or (torch.is_grad_enabled() and vertices.requires_grad):
+        return sdf_values(vertices, sc, return_gradient)
     B, V, _ = vertices.shape
     pts = vertices.to(dtype=torch.float32).contiguous()
     out = torch.empty(B, V, dtype=torch.float32, device=pts.device)

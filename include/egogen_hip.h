@@ -80,7 +80,10 @@ typedef struct egx_sdf_grid {
   int d0, d1, d2;
   float center[3];
   float scale;
-  const void* coarse_minmax; /* device table from egx_sdf_build_coarse: required by egx_lbs_forward, optional (NULL = fine grid only) elsewhere */
+  const void* coarse_minmax; /* device table from egx_sdf_build_coarse: required by egx_lbs_forward, optional (NULL = fine grid only)
+                              * elsewhere.  The table holds a bricked COPY of the grid, and that copy is what egx_sdf_sample,
+                              * egx_sdf_value_grad and the egx_sdf_penalty_* calls read when this is set: the grid must not
+                              * change after egx_sdf_build_coarse (rebuild the table if it does). */
 } egx_sdf_grid;
 
 /* Acceleration tables for the penetration COUNT of egx_lbs_forward: {min,max} of the fine samples each 4x4x4 block's
@@ -269,6 +272,45 @@ int egx_update_transl_glorot(const float* R, const float* T, int num_frames, con
  * gathered from the bricked copy of the grid in that buffer, otherwise from the row-major grid: bit-identical values.
  */
 int egx_sdf_sample(const egx_sdf_grid* sdf, const float* pts, int64_t n, float* out, void* stream);
+
+/*
+ * egx_sdf_value_grad - calc_sdf (crowd_ppo/utils.py:54-84) with its derivative: what torch autograd gives through the
+ * reference's F.grid_sample.  pts [n,3] -> out_val [n] (or NULL) = s, bit-identical to egx_sdf_sample, and out_grad [n,3] =
+ * cotangent_i * g_i with g = d s / d point in value per metre (cotangent [n], NULL = 1).  Value and gradient come from the same
+ * eight corners, gathered once (from the bricked copy when sdf->coarse_minmax is set, else from the row-major grid: the same
+ * bits either way).  Along axis a, g_a = -(bilinear combination, with the other two axes' weights, of the four corner
+ * differences along a) * scale * d_a / 2, and exactly 0 where the unclamped voxel coordinate is <= 0 or >= d_a - 1 (aten's
+ * clip_coordinates_set_grad); on a cell face floor() selects the upper cell, as the value does.  This is the analytic,
+ * unnormalised derivative of the returned values - not a lookup in a precomputed `gradient_grid` (the reference's commented-out
+ * branch, utils.py:69-81).  n = 0 is legal.
+ */
+int egx_sdf_value_grad(const egx_sdf_grid* sdf, const float* pts, int64_t n, const float* cotangent, float* out_val,
+                       float* out_grad, void* stream);
+
+/*
+ * egx_sdf_penalty_forward / egx_sdf_penalty_backward - a differentiable penetration penalty on arbitrary points (no reference
+ * counterpart: crowd_env_2f.py:163-175 only counts).  With s_bp = calc_sdf of point p of body b:
+ *   out_penalty[b] = sum_p w_p * max(margin - s_bp, 0)^power,  power in {1, 2} (2 is C1; for 1 the derivative factor is 1
+ *                    where s < margin strictly, else 0);
+ *   out_count[b]   = #{p : w_p > 0 and s_bp < 0}  (int32, or NULL);
+ *   grad_pts[b,p]  = grad_penalty[b] * w_p * (-power * max(margin - s_bp, 0)^(power-1)) * g_bp,  g as in egx_sdf_value_grad.
+ * pts [B,P,3], 1 <= P <= 2^20; weights [P] or NULL = 1.  Exactly one of sdf / scenes is non-NULL: with `scenes`, body b uses
+ * scene agent_scene[b / frames_per_agent] (device int32 [B / frames_per_agent]); an index outside the set reads nothing and
+ * gives penalty 0, count -1 and a zero gradient, like egx_lbs_forward_scenes.  With `sdf`, agent_scene is ignored.  The scenes
+ * of a set carry their tables, so set calls always read the bricked copies; each body is bit-identical to the one-scene call.
+ * The backward recomputes everything from the points: no workspace, nothing saved, no atomics.  The per-body sum is reduced in
+ * a fixed order, so both directions are bit-reproducible.  The forward interpolates and sums in double (from the float32
+ * samples and points): out_penalty is the float64 penalty rounded once; out_count uses the float32 value, the bits of
+ * egx_sdf_sample.  The backward takes its hinge max(margin - s, 0) and the strict test s < margin from the float32 value: for a
+ * point within one float32 rounding of the hinge the gradient is that of the float32 penalty, not of the reported one (for
+ * power = 1 the factor is 0 or 1 there).
+ */
+int egx_sdf_penalty_forward(const egx_sdf_grid* sdf, const egx_sdf_scene_set* scenes, const int32_t* agent_scene, const float* pts,
+                            int num_bodies, int points_per_body, int frames_per_agent, const float* weights, float margin,
+                            int power, float* out_penalty, int32_t* out_count, void* stream);
+int egx_sdf_penalty_backward(const egx_sdf_grid* sdf, const egx_sdf_scene_set* scenes, const int32_t* agent_scene, const float* pts,
+                             int num_bodies, int points_per_body, int frames_per_agent, const float* weights, float margin,
+                             int power, const float* grad_penalty, float* grad_pts, void* stream);
 
 /*
  * egx_mesh_sdf - scene preparation (the reference ships data/room0_sdf.pkl ready-made and refers to an
