@@ -15,16 +15,13 @@
 //     written body-minor ([tile][joint][row][32 bodies] float4) so the epilogue reads are coalesced;
 //   * the vertex tensor never has to exist: SDF counting and the ~240 picked vertices are epilogues.
 // The kernels live in one file per family (lbs_pose.hip, lbs_fused.hip, lbs_fused3.hip, lbs_fix.hip, lbs_cull.hip; shared
-// declarations in lbs.h); this file packs the model at load, lays out the workspace, holds the process-wide switches and launches.
+// declarations in lbs.h) and the model is packed at load by lbs_pack.hip, host code a CPU test checks byte by byte; this file holds
+// the gather kernel, uploads the packed model, lays out the workspace, holds the process-wide switches and launches.
 #include <algorithm>
-#include <cmath>
-#include <cstring>
-#include <map>
-#include <mutex>
-#include <vector>
-
 #include <atomic>
-#include "lbs.h"
+#include <cstdlib>
+
+#include "lbs_pack.h"
 
 // the events egx_profile_next_lbs hands over: the next launch of this thread records them around its fused and fix-up launches
 static thread_local hipEvent_t g_prof_start = nullptr, g_prof_stop = nullptr;
@@ -35,7 +32,6 @@ extern "C" int egx_profile_next_lbs(void* start_event, void* stop_event) {
 }
 
 namespace {
-constexpr int NLMK = 51, NEXTRA = 21;
 constexpr int BODY_PAD = 256;          // bodies per workgroup of the fused kernel
 }  // namespace
 
@@ -75,436 +71,24 @@ __global__ void egx_gather_kernel(const float* __restrict__ picked, int B, int N
 }
 
 // ------------------------------------------------------------------------------------------------
-// host side: packing + C ABI
+// host side: the loaded model (packed by lbs_pack.hip, uploaded here) + C ABI
 // ------------------------------------------------------------------------------------------------
-template <typename T>
-static int upload(T** dptr, const std::vector<T>& h) {
-  EGX_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(dptr), std::max<size_t>(h.size(), 1) * sizeof(T)));
-  if (!h.empty()) EGX_HIP_CHECK(hipMemcpy(*dptr, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice));
-  return EGX_OK;
-}
-
 extern "C" int egx_body_model_create(const egx_body_model_host* d, egx_body_model** out) {
   EGX_REQUIRE(d && out, "null argument");
-  EGX_REQUIRE(d->num_verts > 0 && d->num_markers >= 0, "bad sizes");
-  EGX_REQUIRE(d->v_template_host && d->shapedirs_host && d->posedirs_host && d->J_regressor_host && d->parents_host &&
-                  d->lbs_weights_host && d->hand_comps_l_host && d->hand_comps_r_host && d->hand_mean_l_host &&
-                  d->hand_mean_r_host && d->extra_vids_host && d->lmk_vids_host && d->lmk_bary_host,
-              "null model array");
-  const int V = d->num_verts, NVT = egx_ceil_div(V, 32), VP = NVT * 32;
+  LbsPacked p;
+  if (int rc = lbs_pack_model(d, &p)) return rc;
   auto* m = new egx_body_model();
-  m->V = V; m->NVT = NVT; m->M = d->num_markers;
-
-  // Joint-coherent vertex order: vertices are sorted by the set of joints they are bound to, so that the 32 vertices
-  // of a tile share few joints and the skinning loop of the epilogue (one pass per joint of the tile) stays short
-  // (synthetic body: 9.8 -> 4.7 joints per tile).  perm[new] = original vertex id (-1 for the padding rows); every
-  // table below is laid out in the new order, outputs are addressed through `vorig` / pick slots.
-  std::vector<int> perm(VP, -1);
-  {
-    std::vector<std::vector<int>> key(V);
-    for (int v = 0; v < V; ++v)
-      for (int j = 0; j < NJ; ++j)
-        if (d->lbs_weights_host[(size_t)v * NJ + j] != 0.f) key[v].push_back(j);
-    std::vector<int> order(V);
-    for (int v = 0; v < V; ++v) order[v] = v;
-    bool natural = false;
-#ifdef EGX_LBS_DEVELOPMENT
-    if (const char* e = getenv("EGX_LBS_VERTEX_ORDER")) natural = std::string(e) == "natural";
-#endif
-    // The vertices the environment reads (markers, vertex joints, landmark corners: 241 of 10 475) come FIRST, packed into
-    // ceil(241 / 32) = 8 tiles: a call that asks for neither all vertices nor SDF counts (box / crowd / EgoBody scenes, reset
-    // tables, get_jts / get_markers) then evaluates 8 vertex tiles instead of every tile that happens to hold one of them
-    // (~half of the 328 under the joint order alone).  Both parts keep the joint-coherent order among themselves.
-    std::vector<char> is_pick(V, 0);
-    auto mark = [&](const int* ids, int n) {
-      for (int i = 0; i < n; ++i)
-        if (ids[i] >= 0 && ids[i] < V) is_pick[ids[i]] = 1;   // out-of-range ids are reported below (slot_of)
-    };
-    if (d->marker_vids_host) mark(d->marker_vids_host, d->num_markers);
-    mark(d->extra_vids_host, NEXTRA);
-    mark(d->lmk_vids_host, NLMK * 3);
-    if (!natural)
-      std::stable_sort(order.begin(), order.end(), [&](int a, int b) {
-        if (is_pick[a] != is_pick[b]) return is_pick[a] > is_pick[b];
-        return key[a] < key[b];
-      });
-    for (int v = 0; v < V; ++v) perm[v] = order[v];
-  }
-
-  // blend bases in MFMA A-operand order: [vt][g][c][lane] float4, element e <-> k = 2*(4g+e) + (lane>>5)
-  std::vector<f32x4> dirs((size_t)NVT * KGROUPS * 3 * 64);
-  for (int vt = 0; vt < NVT; ++vt)
-    for (int g = 0; g < KGROUPS; ++g)
-      for (int c = 0; c < 3; ++c)
-        for (int l = 0; l < 64; ++l) {
-          const int v = perm[vt * 32 + (l & 31)];
-          f32x4 val = {0.f, 0.f, 0.f, 0.f};
-          if (v >= 0)
-            for (int e = 0; e < 4; ++e) {
-              const int k = 2 * (4 * g + e) + (l >> 5);
-              if (k < 10) {
-                val[e] = d->shapedirs_host[((size_t)v * 3 + c) * 10 + k];
-              } else if (k < KACT) {
-                const int jc = (k - 10) / 9, e9 = (k - 10) % 9;
-                const int j = jc + 1 + (jc >= 21 ? 3 : 0);        // inverse of egx_compact_joint
-                val[e] = d->posedirs_host[(size_t)((j - 1) * 9 + e9) * 3 * V + (size_t)v * 3 + c];
-              } else if (k == KACT) {
-                val[e] = d->v_template_host[(size_t)v * 3 + c];  // multiplied by the constant-1 feature
-              }
-            }
-          dirs[(((size_t)vt * KGROUPS + g) * 3 + c) * 64 + l] = val;
-        }
-
-  // the same bases vertex-major (one vertex's 3 x 472 columns contiguous): the single-vertex fp32 re-evaluation of the mixed blend
-  // reads 5.7 KB per vertex from here instead of 720 scattered cache lines of the MFMA-ordered images
-  std::vector<float> dirs_rm((size_t)VP * 3 * KDIM, 0.f);
-  for (int vn = 0; vn < VP; ++vn) {
-    const int v = perm[vn];
-    if (v < 0) continue;
-    for (int c = 0; c < 3; ++c) {
-      float* dst = &dirs_rm[((size_t)vn * 3 + c) * KDIM];
-      for (int k = 0; k < 10; ++k) dst[k] = d->shapedirs_host[((size_t)v * 3 + c) * 10 + k];
-      for (int k = 10; k < KACT; ++k) {
-        const int jc = (k - 10) / 9, e9 = (k - 10) % 9;
-        const int j = jc + 1 + (jc >= 21 ? 3 : 0);
-        dst[k] = d->posedirs_host[(size_t)((j - 1) * 9 + e9) * 3 * V + (size_t)v * 3 + c];
-      }
-      dst[KACT] = d->v_template_host[(size_t)v * 3 + c];
-    }
-  }
-
-  // the same bases as three bf16 planes in the A-operand order of v_mfma_f32_32x32x16_bf16:
-  // [vt][s][plane][c][lane] 8 x bf16, element e <-> k = 16 s + 8 (lane>>5) + e, row = lane & 31
-  std::vector<unsigned short> dirs3((size_t)NVT * KS3 * 9 * 64 * 8, 0);
-  for (int vt = 0; vt < NVT; ++vt)
-    for (int sidx = 0; sidx < KS3; ++sidx)
-      for (int c = 0; c < 3; ++c)
-        for (int l = 0; l < 64; ++l) {
-          const int v = perm[vt * 32 + (l & 31)];
-          if (v < 0) continue;
-          for (int e = 0; e < 8; ++e) {
-            const int k = 16 * sidx + 8 * (l >> 5) + e;
-            float val = 0.f;
-            if (k < 10) {
-              val = d->shapedirs_host[((size_t)v * 3 + c) * 10 + k];
-            } else if (k < KACT) {
-              const int jc = (k - 10) / 9, e9 = (k - 10) % 9;
-              const int j = jc + 1 + (jc >= 21 ? 3 : 0);
-              val = d->posedirs_host[(size_t)((j - 1) * 9 + e9) * 3 * V + (size_t)v * 3 + c];
-            } else if (k == KACT) {
-              val = d->v_template_host[(size_t)v * 3 + c];
-            } else if (k == KACT + 1) {  // what two bf16 terms of the template leave over (feature 470 selects it)
-              const float t = d->v_template_host[(size_t)v * 3 + c];
-              unsigned short ht[3];
-              egx_bf16_split3(t, ht);
-              val = (t - egx_bf16_to_f32(ht[0])) - egx_bf16_to_f32(ht[1]);
-            }
-            unsigned short h[3];
-            egx_bf16_split3(val, h);
-            for (int pl = 0; pl < 3; ++pl)
-              dirs3[(((((size_t)vt * KS3 + sidx) * 3 + pl) * 3 + c) * 64 + l) * 8 + e] = h[pl];
-          }
-        }
-
-  // the mixed-blend image (mode 3): the same values, k-steps 0 and 29 as two bf16 planes, k-steps 1..28 as one fp16 plane
-  std::vector<unsigned short> dirs4((size_t)NVT * M4_BASE_PIECES * 64 * 8, 0);
-  for (int vt = 0; vt < NVT; ++vt)
-    for (int sidx = 0; sidx < KS3; ++sidx)
-      for (int c = 0; c < 3; ++c)
-        for (int l = 0; l < 64; ++l)
-          for (int e = 0; e < 8; ++e) {
-            const size_t src = (((((size_t)vt * KS3 + sidx) * 3 + 0) * 3 + c) * 64 + l) * 8 + e;      // plane 0 of dirs3
-            const size_t pstride = (size_t)3 * 64 * 8;                                               // plane stride in dirs3
-            if (sidx == 0 || sidx == KS3 - 1) {
-              for (int pl = 0; pl < 2; ++pl)
-                dirs4[(((size_t)vt * M4_BASE_PIECES + egx_m4_base_piece(sidx, pl, c)) * 64 + l) * 8 + e] = dirs3[src + pl * pstride];
-            } else {
-              const float val = egx_bf16_to_f32(dirs3[src]) + egx_bf16_to_f32(dirs3[src + pstride]) + egx_bf16_to_f32(dirs3[src + 2 * pstride]);
-              dirs4[(((size_t)vt * M4_BASE_PIECES + egx_m4_base_piece(sidx, 0, c)) * 64 + l) * 8 + e] = egx_f16_rne(val);
-            }
-          }
-
-  // skinning weights -> per-tile joint lists: the joints any of the tile's 32 vertices is bound to, with the dense
-  // [32] weight column of each.  The epilogue walks this list once per body tile (one transform fetch per joint
-  // instead of one per vertex and weight).
-  int NW = 1;
-  for (int v = 0; v < V; ++v) {
-    int c = 0;
-    for (int j = 0; j < NJ; ++j) c += d->lbs_weights_host[(size_t)v * NJ + j] != 0.f;
-    NW = std::max(NW, c);
-  }
-  m->NW = NW;
-  std::vector<int> tj_off(NVT + 1, 0), tj_idx;
-  std::vector<float> tj_w;
-  for (int vt = 0; vt < NVT; ++vt) {
-    for (int j = 0; j < NJ; ++j) {
-      float col[32];
-      bool any = false;
-      for (int r = 0; r < 32; ++r) {
-        const int v = perm[vt * 32 + r];
-        col[r] = (v >= 0) ? d->lbs_weights_host[(size_t)v * NJ + j] : 0.f;
-        any |= col[r] != 0.f;
-      }
-      if (any) {
-        // bits 8..11: which groups of eight rows (rows 8g .. 8g+7 = the four rows of row group g in both lane halves of the
-        // epilogue) hold a non-zero weight of this joint - the epilogue skips the others with a scalar test
-        int gmask = 0;
-        for (int r = 0; r < 32; ++r) gmask |= (col[r] != 0.f) ? (1 << (r >> 3)) : 0;
-        tj_idx.push_back(j | (gmask << 8));
-        tj_w.insert(tj_w.end(), col, col + 32);
-      }
-    }
-    if ((int)tj_idx.size() == tj_off[vt]) {  // a tile without any weight still needs one (zero) entry
-      tj_idx.push_back(0);
-      tj_w.insert(tj_w.end(), 32, 0.f);
-    }
-    tj_off[vt + 1] = (int)tj_idx.size();
-  }
-
-  // matrix-pipe skinning weights of every tile (lbs_epilogue_cell): k-step ks covers joints list[8 ks .. 8 ks + 7] of the tile
-  std::vector<int> skin_ks_off(NVT + 1, 0);
-  for (int vt = 0; vt < NVT; ++vt) skin_ks_off[vt + 1] = skin_ks_off[vt] + (tj_off[vt + 1] - tj_off[vt] + 7) / 8;
-  std::vector<unsigned short> skinW((size_t)skin_ks_off[NVT] * 2 * 64 * 8, 0);
-  for (int vt = 0; vt < NVT; ++vt) {
-    const int JT = tj_off[vt + 1] - tj_off[vt];
-    for (int ks = 0; ks < (JT + 7) / 8; ++ks)
-      for (int l = 0; l < 64; ++l)
-        for (int e = 0; e < 8; ++e) {
-          const int jj = 8 * ks + e;
-          if (jj >= JT) continue;
-          unsigned short hh[3];
-          egx_bf16_split3(tj_w[(size_t)(tj_off[vt] + jj) * 32 + (l & 31)], hh);
-          const size_t base = ((size_t)(skin_ks_off[vt] + ks) * 2) * 64 * 8;
-          skinW[base + (size_t)l * 8 + e] = hh[0];                                   // operand 0: W_hi in both lane halves
-          if (l < 32) skinW[base + (size_t)(64 + l) * 8 + e] = hh[1];                // operand 1: W_mid in lane half 0, zero in half 1
-        }
-  }
-
-  // picked vertices (markers, vertex joints, landmark corners)
-  std::vector<int> pick_slot(VP, -1), marker_slot(d->num_markers), extra_slot(NEXTRA), lmk_slot(NLMK * 3);
-  int NP = 0;
-  std::vector<int> inv(V);  // original vertex id -> position in the sorted order
-  for (int vn = 0; vn < V; ++vn) inv[perm[vn]] = vn;
-  auto slot_of = [&](int v) -> int {
-    if (v < 0 || v >= V) return -1;
-    if (pick_slot[inv[v]] < 0) pick_slot[inv[v]] = NP++;
-    return pick_slot[inv[v]];
-  };
-  bool ok = true;
-  for (int i = 0; i < d->num_markers; ++i) ok &= (marker_slot[i] = slot_of(d->marker_vids_host[i])) >= 0;
-  for (int i = 0; i < NEXTRA; ++i) ok &= (extra_slot[i] = slot_of(d->extra_vids_host[i])) >= 0;
-  for (int i = 0; i < NLMK * 3; ++i) ok &= (lmk_slot[i] = slot_of(d->lmk_vids_host[i])) >= 0;
-  if (!ok) { delete m; egx_set_error("vertex id out of range in marker/extra/landmark tables"); return EGX_ERR_ARG; }
-  m->NP = NP;
-  std::vector<int> pick_tiles;
-  for (int vt = 0; vt < NVT; ++vt) {
-    bool any = false;
-    for (int r = 0; r < 32; ++r) any |= pick_slot[vt * 32 + r] >= 0;
-    if (any) pick_tiles.push_back(vt);
-  }
-  m->n_pick_tiles = (int)pick_tiles.size();
-  std::vector<uint8_t> vflags(VP, 0);
-  for (int v = 0; v < V; ++v) vflags[v] = 2;
-  for (int i = 0; i < d->num_feet; ++i) {
-    const int v = d->feet_vids_host[i];
-    if (v < 0 || v >= V) { delete m; egx_set_error("feet vertex id out of range"); return EGX_ERR_ARG; }
-    vflags[inv[v]] |= 1;
-  }
-  std::vector<int> sdf_tiles;   // tiles of feet vertices only (and no pick) contribute nothing to a picks + SDF-count call
-  for (int vt = 0; vt < NVT; ++vt) {
-    bool any = false;
-    for (int r = 0; r < 32; ++r) any |= pick_slot[vt * 32 + r] >= 0 || (vflags[vt * 32 + r] & 3) == 2;
-    if (any) sdf_tiles.push_back(vt);
-  }
-  m->n_sdf_tiles = (int)sdf_tiles.size();
-  for (int vt : sdf_tiles)
-    for (int r = 0; r < 32; ++r) m->verts_sdf_tiles += (vflags[vt * 32 + r] & 2) ? 1 : 0;
-  for (int vt : pick_tiles)
-    for (int r = 0; r < 32; ++r) m->verts_pick_tiles += (vflags[vt * 32 + r] & 2) ? 1 : 0;
-  std::vector<float> lmk_bary(d->lmk_bary_host, d->lmk_bary_host + NLMK * 3);
-
-  // pose constants; joint regression folded through the shape space in double precision:
-  //   J(betas) = J_regressor (v_template + shapedirs betas) = J_template + J_shapedirs betas
-  std::vector<PoseConsts> pcv(1);
-  PoseConsts& pc = pcv[0];
-  std::memset(&pc, 0, sizeof(pc));
-  pc.max_depth = 0;
-  for (int j = 0; j < NJ; ++j) {
-    pc.parents[j] = d->parents_host[j];
-    if (j > 0 && (pc.parents[j] < 0 || pc.parents[j] >= j)) { delete m; egx_set_error("parents must be topologically ordered"); return EGX_ERR_ARG; }
-    pc.depth[j] = (j == 0) ? 0 : pc.depth[pc.parents[j]] + 1;
-    pc.max_depth = std::max(pc.max_depth, pc.depth[j]);
-  }
-  pc.parents[0] = -1;
-  for (int j = 0; j < NJ; ++j)
-    for (int c = 0; c < 3; ++c) {
-      double s = 0.0;
-      double sd[10] = {0};
-      for (int v = 0; v < V; ++v) {
-        const double w = d->J_regressor_host[(size_t)j * V + v];
-        if (w == 0.0) continue;
-        s += w * d->v_template_host[(size_t)v * 3 + c];
-        for (int k = 0; k < 10; ++k) sd[k] += w * d->shapedirs_host[((size_t)v * 3 + c) * 10 + k];
-      }
-      pc.J_template[j * 3 + c] = (float)s;
-      for (int k = 0; k < 10; ++k) pc.J_shapedirs[(j * 3 + c) * 10 + k] = (float)sd[k];
-    }
-  {   // constants of the fix-up band of the mixed blend (see LBS_FIX_SLACK_M), rounded up to fp32
-    auto up = [](double x) { return (float)(x * (1.0 + 1e-6)); };
-    std::vector<double> pf(V, 0.0), dpf(V, 0.0);
-    for (int j = 1; j < NJ; ++j) {
-      const bool movable = j < 22 || j > 24;   // jaw and eyes have no feature: their columns are not in the product
-      double mx = 0.0, mxd = 0.0;
-      for (int e9 = 0; e9 < 9; ++e9) {
-        const int k = movable ? 10 + egx_compact_joint(j) * 9 + e9 : -1;
-        const bool fp16_col = k >= 16 && k < 464;
-        for (int v = 0; v < V; ++v) {
-          double q = 0.0, qd = 0.0;
-          for (int c = 0; c < 3; ++c) {
-            const float b = d->posedirs_host[(size_t)((j - 1) * 9 + e9) * 3 * V + (size_t)v * 3 + c];
-            const double dd = fp16_col ? (double)(float)(_Float16)b - (double)b : 0.0;   // the fp16 plane of dirs4 (egx_f16_rne)
-            q += (double)b * b;
-            qd += dd * dd;
-          }
-          mx = std::max(mx, q);
-          mxd = std::max(mxd, qd);
-          if (movable) { pf[v] += q; dpf[v] += qd; }
-        }
-      }
-      pc.fix_c[j] = up(std::sqrt(mx));
-      pc.fix_d[j] = up(std::sqrt(mxd));
-    }
-    double mpf = 0.0, mdpf = 0.0, mvt = 0.0, mw = 0.0;
-    for (int v = 0; v < V; ++v) {
-      mpf = std::max(mpf, pf[v]);
-      mdpf = std::max(mdpf, dpf[v]);
-      double q = 0.0, w = 0.0;
-      for (int c = 0; c < 3; ++c) q += (double)d->v_template_host[(size_t)v * 3 + c] * d->v_template_host[(size_t)v * 3 + c];
-      for (int j = 0; j < NJ; ++j) w += std::fabs((double)d->lbs_weights_host[(size_t)v * NJ + j]);
-      mvt = std::max(mvt, q);
-      mw = std::max(mw, w);
-    }
-    pc.fix_pf = up(std::sqrt(mpf));
-    pc.fix_dpf = up(std::sqrt(mdpf));
-    pc.vt_max = up(std::sqrt(mvt));
-    pc.w_abs_max = up(mw);
-    for (int k = 0; k < 10; ++k) {
-      double mx = 0.0;
-      for (int v = 0; v < V; ++v) {
-        double q = 0.0;
-        for (int c = 0; c < 3; ++c) q += (double)d->shapedirs_host[((size_t)v * 3 + c) * 10 + k] * d->shapedirs_host[((size_t)v * 3 + c) * 10 + k];
-        mx = std::max(mx, q);
-      }
-      pc.shape_c[k] = up(std::sqrt(mx));
-    }
-  }
-  std::memcpy(pc.hand_comps, d->hand_comps_l_host, 12 * 45 * sizeof(float));
-  std::memcpy(pc.hand_comps + 12 * 45, d->hand_comps_r_host, 12 * 45 * sizeof(float));
-  std::memcpy(pc.hand_mean, d->hand_mean_l_host, 45 * sizeof(float));
-  std::memcpy(pc.hand_mean + 45, d->hand_mean_r_host, 45 * sizeof(float));
-
-  // ---- bounds for the free-space culling of SDF work items.  A posed vertex is a convex combination over its joints j of
-  // R_j (v~ - J_j) + p_j (p_j: posed joint, J_j: shaped rest joint, v~: template + shape and pose offsets), so it lies in the
-  // convex hull of the balls B(p_j, |v~ - J_j|), and
-  //   |v~ - J_j| <= |v_t - J_t,j| + sum_k |beta_k| |S_k,v - JS_k,j| + sum_j' ||R_j' - I||_F ||P_j',v||_F
-  // (Cauchy-Schwarz per joint block of the pose blend shapes).  Per tile: D0 = max of the first term over the vertices bound
-  // to the joint, E = the maxima of the coefficient norms over the tile's vertices (and its joints, for the shape term).
-  std::vector<float> cull_E((size_t)NVT * 64, 0.f), cull_D0(tj_idx.size(), 0.f);
-  bool convex = true;
-  for (int v = 0; v < V && convex; ++v) {
-    double sum = 0.0;
-    for (int j = 0; j < NJ; ++j) {
-      const float wv = d->lbs_weights_host[(size_t)v * NJ + j];
-      if (wv < 0.f) convex = false;
-      sum += wv;
-    }
-    if (std::fabs(sum - 1.0) > 1e-4) convex = false;
-  }
-  {
-    bool lead = pick_tiles.size() <= sdf_tiles.size();
-    for (size_t i = 0; i < pick_tiles.size() && lead; ++i) lead = sdf_tiles[i] == pick_tiles[i];
-    m->sdf_lead_picks = lead ? 1 : 0;
-  }
-  // the culled launch treats the first n_pick_tiles entries of the SDF tile list as "always evaluated"
-  for (size_t i = 0; i < pick_tiles.size() && convex; ++i) convex = i < sdf_tiles.size() && sdf_tiles[i] == pick_tiles[i];
-  m->cull_ok = convex ? 1 : 0;
-  for (int c = 0; c < 3; ++c) m->rest_pelvis[c] = pc.J_template[c];
-  for (int vt = 0; vt < NVT && convex; ++vt) {
-    float* E = &cull_E[(size_t)vt * 64];
-    for (int r = 0; r < 32; ++r) {
-      const int v = perm[vt * 32 + r];
-      if (v < 0) continue;
-      for (int jj = tj_off[vt]; jj < tj_off[vt + 1]; ++jj) {
-        const int j = tj_idx[jj] & 0xff;
-        if (d->lbs_weights_host[(size_t)v * NJ + j] != 0.f) {
-          double q = 0.0;
-          for (int c = 0; c < 3; ++c) {
-            const double e = (double)d->v_template_host[(size_t)v * 3 + c] - (double)pc.J_template[j * 3 + c];
-            q += e * e;
-          }
-          cull_D0[jj] = std::max(cull_D0[jj], (float)(std::sqrt(q) * (1.0 + 1e-6)));
-        }
-        for (int k = 0; k < 10; ++k) {   // shape term, over every joint of the tile's list (a superset of the vertex's own)
-          double q = 0.0;
-          for (int c = 0; c < 3; ++c) {
-            const double e = (double)d->shapedirs_host[((size_t)v * 3 + c) * 10 + k] - (double)pc.J_shapedirs[(j * 3 + c) * 10 + k];
-            q += e * e;
-          }
-          E[k] = std::max(E[k], (float)(std::sqrt(q) * (1.0 + 1e-6)));
-        }
-      }
-      for (int jc = 0; jc < 51; ++jc) {
-        const int j = jc + 1 + (jc >= 21 ? 3 : 0);
-        double q = 0.0;
-        for (int e9 = 0; e9 < 9; ++e9)
-          for (int c = 0; c < 3; ++c) {
-            const double e = d->posedirs_host[(size_t)((j - 1) * 9 + e9) * 3 * V + (size_t)v * 3 + c];
-            q += e * e;
-          }
-        E[10 + jc] = std::max(E[10 + jc], (float)(std::sqrt(q) * (1.0 + 1e-6)));
-      }
-    }
-  }
-
-  // The bound is only worth evaluating where it is tight: at a reference pose (|beta_k| = 0.8, ||R_j - I||_F = 0.42, i.e.
-  // 0.3 rad at every joint) the blend-shape margin of the median tile must stay below 15 cm.  Learned body models pass (shape
-  // directions are smooth fields, pose correctives act near their joint: centimetres); a model whose blend shapes are
-  // i.i.d. noise in all 469 x 3V entries - the synthetic benchmark body of SURVEY 8(d) - does not (0.56 m: no box is ever
-  // free), and its launches skip the three culling kernels altogether.
-  if (convex) {
-    std::vector<float> ref(NVT);
-    for (int vt = 0; vt < NVT; ++vt) {
-      float mg = 0.f;
-      for (int i = 0; i < 10; ++i) mg += 0.8f * cull_E[(size_t)vt * 64 + i];
-      for (int i = 10; i < 61; ++i) mg += 0.42f * cull_E[(size_t)vt * 64 + i];
-      ref[vt] = mg;
-    }
-    std::nth_element(ref.begin(), ref.begin() + NVT / 2, ref.end());
-    m->cull_ref_margin = ref[NVT / 2];
-    if (m->cull_ref_margin > 0.15f) m->cull_ok = 0;
-  }
-
+  static_cast<LbsModelDims&>(*m) = p;
+  auto u16 = [](bf16x8** dptr) { return reinterpret_cast<unsigned short**>(dptr); };   // the 16-bit images are packed as plain shorts
   int rc = EGX_OK;
-  if ((rc = upload(&m->cull_E, cull_E)) || (rc = upload(&m->cull_D0, cull_D0))) { egx_body_model_destroy(m); return rc; }
-  {
-    unsigned short* d3 = nullptr;
-    if ((rc = upload(&d3, dirs3))) { egx_body_model_destroy(m); return rc; }
-    m->dirs3 = reinterpret_cast<bf16x8*>(d3);
-    unsigned short* d4 = nullptr;
-    if ((rc = upload(&d4, dirs4))) { egx_body_model_destroy(m); return rc; }
-    m->dirs4 = reinterpret_cast<bf16x8*>(d4);
-  }
-  {
-    unsigned short* sw = nullptr;
-    if ((rc = upload(&sw, skinW)) || (rc = upload(&m->skin_ks_off, skin_ks_off)) || (rc = upload(&m->dirs_rm, dirs_rm))) { egx_body_model_destroy(m); return rc; }
-    m->skinW = reinterpret_cast<bf16x8*>(sw);
-  }
-  if ((rc = upload(&m->vorig, perm)) || (rc = upload(&m->pick_tiles, pick_tiles)) ||
-      (rc = upload(&m->sdf_tiles, sdf_tiles))) { egx_body_model_destroy(m); return rc; }
-  if ((rc = upload(&m->dirs, dirs)) || (rc = upload(&m->tj_off, tj_off)) || (rc = upload(&m->tj_idx, tj_idx)) ||
-      (rc = upload(&m->tj_w, tj_w)) || (rc = upload(&m->pick_slot, pick_slot)) || (rc = upload(&m->vflags, vflags)) ||
-      (rc = upload(&m->pc, pcv)) || (rc = upload(&m->marker_slot, marker_slot)) || (rc = upload(&m->extra_slot, extra_slot)) ||
-      (rc = upload(&m->lmk_slot, lmk_slot)) || (rc = upload(&m->lmk_bary, lmk_bary))) {
+  if ((rc = egx_upload(&m->cull_E, p.cull_E)) || (rc = egx_upload(&m->cull_D0, p.cull_D0)) || (rc = egx_upload(u16(&m->dirs3), p.dirs3)) ||
+      (rc = egx_upload(u16(&m->dirs4), p.dirs4)) || (rc = egx_upload(u16(&m->skinW), p.skinW)) || (rc = egx_upload(&m->skin_ks_off, p.skin_ks_off)) ||
+      (rc = egx_upload(&m->dirs_rm, p.dirs_rm)) || (rc = egx_upload(&m->vorig, p.perm)) || (rc = egx_upload(&m->pick_tiles, p.pick_tiles)) ||
+      (rc = egx_upload(&m->sdf_tiles, p.sdf_tiles)) || (rc = egx_upload(&m->dirs, p.dirs)) || (rc = egx_upload(&m->tj_off, p.tj_off)) ||
+      (rc = egx_upload(&m->tj_idx, p.tj_idx)) || (rc = egx_upload(&m->tj_w, p.tj_w)) || (rc = egx_upload(&m->pick_slot, p.pick_slot)) ||
+      (rc = egx_upload(&m->vflags, p.vflags)) || (rc = egx_upload(&m->pc, p.pc)) || (rc = egx_upload(&m->marker_slot, p.marker_slot)) ||
+      (rc = egx_upload(&m->extra_slot, p.extra_slot)) || (rc = egx_upload(&m->lmk_slot, p.lmk_slot)) ||
+      (rc = egx_upload(&m->lmk_bary, p.lmk_bary))) {
     egx_body_model_destroy(m);
     return rc;
   }
@@ -529,21 +113,43 @@ extern "C" int egx_body_model_lbs_vertices(const egx_body_model* m, int with_sdf
 }
 
 namespace {
+// ---- process-wide switches: set through the C ABI, else read from the environment once (the first call that asks)
+template <typename Parse>
+int switch_value(std::atomic<int>& g, const char* env_name, Parse&& parse) {
+  int v = g.load();
+  if (v < 0) {
+    const char* e = getenv(env_name);
+    v = parse(std::string(e ? e : ""));
+    if (v >= 0) g.store(v);
+  }
+  return v;
+}
 // blend mode of the fused kernel: 0 = fp32 MFMA, 1 = 3-term bf16 split, 2 = 2-term bf16 split, 3 = mixed (2-term bf16 shape / template +
 // fp16 pose correctives, the default); vertex-writing calls always use 0
 std::atomic<int> g_blend_mode{-1};
 int blend_mode() {
-  int m = g_blend_mode.load();
-  if (m < 0) {
-    const char* e = getenv("EGX_LBS_BLEND");
-    const std::string v = e ? e : "";
-    // unset = f16mix (mode 3: counts re-evaluated in fp32 where the cheap product cannot decide); an unknown string is an
-    // error of the call that reads it (-2), not a silent default
-    m = (v == "f32" || v == "0") ? 0 : ((v == "bf16x3" || v == "1") ? 1 : ((v == "bf16x2" || v == "2") ? 2 : ((v.empty() || v == "f16mix" || v == "3") ? 3 : -2)));
-    if (m >= 0) g_blend_mode.store(m);
-  }
-  return m;
+  // unset = f16mix (mode 3: counts re-evaluated in fp32 where the cheap product cannot decide); an unknown string is an
+  // error of the call that reads it (-2), not a silent default
+  return switch_value(g_blend_mode, "EGX_LBS_BLEND", [](const std::string& v) {
+    return (v == "f32" || v == "0") ? 0 : ((v == "bf16x3" || v == "1") ? 1 : ((v == "bf16x2" || v == "2") ? 2 : ((v.empty() || v == "f16mix" || v == "3") ? 3 : -2)));
+  });
 }
+// free-space culling of SDF work items: OPT-IN (EGX_LBS_CULL=1 / egx_lbs_set_culling(1)).  Measured on MI355X, 10 240 bodies,
+// structured body (profiles/r04_lbs_culling.md): freshly reset agents standing in the room - 60 % of the items evaluated, fused
+// kernel 1.13 -> 0.77 ms, the three culling kernels + 0.11 ms; bodies inside geometry or outside the room (what a random-init
+// policy produces, i.e. the benchmark loop): nothing to skip, + 0.11 ms.  A win for trained policies on learned body models, a
+// loss in the benchmark loop, hence not the default.
+std::atomic<int> g_cull{-1};
+int culling_on() {
+  return switch_value(g_cull, "EGX_LBS_CULL", [](const std::string& v) { return v == "1" ? 1 : 0; });
+}
+// wave tile of the mixed-blend kernel: 0 = by launch size (see egx_lbs_forward), 1 = 32 x 32 (three workgroups per CU), 2 = 32 x 64
+std::atomic<int> g_wave_tile{-1};
+int wave_tile() {
+  return switch_value(g_wave_tile, "EGX_LBS_WAVE_TILE", [](const std::string& v) { return atoi(v.c_str()); });
+}
+std::atomic<int> g_fixq_cap{0};   // fix-up queue entries per sub-queue in use, 0 = LBS_FIXQ_CAP
+
 struct WsLayout {
   size_t feat, feat4, A4, picked, total;
   // culled SDF launches
@@ -578,40 +184,8 @@ WsLayout ws_layout(const egx_body_model* m, int B) {
   w.total = egx_align_up(w.fixq + (size_t)LBS_FIX_NQ * LBS_FIXQ_CAP * sizeof(int2), 256);
   return w;
 }
-// free-space culling of SDF work items: OPT-IN (EGX_LBS_CULL=1 / egx_lbs_set_culling(1)).  Measured on MI355X, 10 240 bodies,
-// structured body (profiles/r04_lbs_culling.md): freshly reset agents standing in the room - 60 % of the items evaluated, fused
-// kernel 1.13 -> 0.77 ms, the three culling kernels + 0.11 ms; bodies inside geometry or outside the room (what a random-init
-// policy produces, i.e. the benchmark loop): nothing to skip, + 0.11 ms.  A win for trained policies on learned body models, a
-// loss in the benchmark loop, hence not the default.
-std::atomic<int> g_cull{-1};
-int culling_on() {
-  int c = g_cull.load();
-  if (c < 0) {
-    const char* e = getenv("EGX_LBS_CULL");
-    c = (e && std::string(e) == "1") ? 1 : 0;
-    g_cull.store(c);
-  }
-  return c;
-}
 }  // namespace
 
-namespace {
-// wave tile of the mixed-blend kernel: 0 = by launch size (see egx_lbs_forward), 1 = 32 x 32 (three workgroups per CU), 2 = 32 x 64
-std::atomic<int> g_wave_tile{-1};
-int wave_tile() {
-  int t = g_wave_tile.load();
-  if (t < 0) {
-    const char* e = getenv("EGX_LBS_WAVE_TILE");
-    t = e ? atoi(e) : 0;
-    g_wave_tile.store(t);
-  }
-  return t;
-}
-}  // namespace
-
-namespace {
-std::atomic<int> g_fixq_cap{0};   // 0 = LBS_FIXQ_CAP
-}
 extern "C" int egx_lbs_set_fix_queue_capacity(int entries) {
   EGX_REQUIRE(entries >= 0 && entries <= LBS_FIXQ_CAP, "capacity must be 0 (default) .. the workspace's queue size");
   g_fixq_cap.store(entries);
@@ -687,68 +261,14 @@ extern "C" int egx_lbs_joints(const egx_body_model* m, const float* xb, const fl
     return EGX_ERR_WORKSPACE;
   }
   char* ws = static_cast<char*>(workspace);
-  lbs_launch_pose(false, static_cast<hipStream_t>(stream_), m->pc, xb, betas, B, fpa, nullptr, nullptr, reinterpret_cast<f32x4*>(ws + wl.A4),
-                  out_joints55, NJ, 0.f, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                  SdfDev{}, nullptr, nullptr, 0);
+  LbsPoseArgs a;
+  a.pc = m->pc; a.xb = xb; a.betas = betas; a.B = B; a.fpa = fpa;
+  a.A4 = reinterpret_cast<f32x4*>(ws + wl.A4);
+  a.out_joints = out_joints55; a.joints_ld = NJ;
+  lbs_launch_pose(false, static_cast<hipStream_t>(stream_), a);
   EGX_HIP_CHECK(hipGetLastError());
   return EGX_OK;
 }
-
-// ------------------------------------------------------------------------------------------------
-// SDF scene sets: the per-scene records of egx_lbs_forward_scenes, made once (struct egx_sdf_scene_set: egx_common.h)
-// ------------------------------------------------------------------------------------------------
-
-extern "C" int egx_sdf_scene_set_create(const egx_sdf_grid* scenes, int num_scenes, egx_sdf_scene_set** out) {
-  EGX_REQUIRE(scenes && out, "null argument");
-  EGX_REQUIRE(num_scenes >= 1 && num_scenes < (1 << 15), "a scene set holds 1 .. 32767 scenes");   // the fused kernels queue the index in 15 bits
-  std::vector<SdfSceneDev> rec((size_t)num_scenes);
-  const egx_sdf_grid& s0 = scenes[0];
-  // every check comes before the first device access (the slope reads below): a rejected set touches no pointer it was given
-  for (int i = 0; i < num_scenes; ++i) {
-    const egx_sdf_grid& g = scenes[i];
-    if (g.d0 != s0.d0 || g.d1 != s0.d1 || g.d2 != s0.d2) {
-      egx_set_error("egx_sdf_scene_set_create: scene " + std::to_string(i) + " has grid dimensions " + std::to_string(g.d0) + "x" +
-                    std::to_string(g.d1) + "x" + std::to_string(g.d2) + ", scene 0 " + std::to_string(s0.d0) + "x" +
-                    std::to_string(s0.d1) + "x" + std::to_string(s0.d2) + ": the scenes of a set share their dimensions");
-      return EGX_ERR_ARG;
-    }
-  }
-  for (int i = 0; i < num_scenes; ++i) {
-    const egx_sdf_grid& g = scenes[i];
-    if (!g.grid || !g.coarse_minmax || !egx_sdf_dims_ok(g.d0, g.d1, g.d2) || g.d0 <= 0 || g.d1 <= 0) {
-      egx_set_error("egx_sdf_scene_set_create: scene " + std::to_string(i) +
-                    " needs a grid with d2 >= 2 and fewer than 2^32 samples and its bracket table (egx_sdf_build_coarse)");
-      return EGX_ERR_ARG;
-    }
-  }
-  // the slopes (aux[3] of each table) were written by egx_sdf_build_coarse on some stream: wait for it, then read them once
-  EGX_HIP_CHECK(hipDeviceSynchronize());
-  const int c0 = egx_ceil_div(s0.d0, 4), c1 = egx_ceil_div(s0.d1, 4), c2 = egx_ceil_div(s0.d2, 4);
-  for (int i = 0; i < num_scenes; ++i) {
-    const egx_sdf_grid& g = scenes[i];
-    SdfSceneDev& r = rec[(size_t)i];
-    r.grid = g.grid;
-    r.coarse = static_cast<const float2*>(g.coarse_minmax);
-    r.cx = g.center[0]; r.cy = g.center[1]; r.cz = g.center[2]; r.scale = g.scale;
-    EGX_HIP_CHECK(hipMemcpy(&r.slope, static_cast<const char*>(g.coarse_minmax) + egx_sdf_aux_offset(c0, c1, c2) + 3 * sizeof(float),
-                            sizeof(float), hipMemcpyDeviceToHost));
-    r.pad = 0.f;
-  }
-  auto* set = new egx_sdf_scene_set();
-  set->S = num_scenes;
-  set->dims = s0;
-  if (int rc = upload(&set->table, rec)) { (void)hipFree(set->table); delete set; return rc; }
-  *out = set;
-  return EGX_OK;
-}
-
-extern "C" void egx_sdf_scene_set_destroy(egx_sdf_scene_set* set) {
-  if (!set) return;
-  (void)hipFree(set->table);
-  delete set;
-}
-
-extern "C" int egx_sdf_scene_set_size(const egx_sdf_scene_set* set) { return set ? set->S : 0; }
 
 // Set of one through the one-scene kernels: bodies whose agent names no scene of the set get the count -1 (after the count was formed).
 __global__ __launch_bounds__(256) void egx_lbs_scene_mark_kernel(const int* __restrict__ agent_scene, int n_scenes, int B, int fpa,
@@ -792,14 +312,11 @@ static int lbs_forward_launch(const egx_body_model* m, const float* xb, const fl
   const bool ms = set != nullptr;
   const bool cull = !ms && split3 && sdf && m->cull_ok && culling_on() && B % fpa == 0 && m->n_sdf_tiles > m->n_pick_tiles &&
                     (size_t)m->n_sdf_tiles * nbg_all >= 8;
-  SdfDev sd;
-  std::memset(&sd, 0, sizeof(sd));
+  SdfDev sd = {};
   const float* mips = nullptr;
   if (sdf) {
-    sd.grid = sdf->grid; sd.d0 = sdf->d0; sd.d1 = sdf->d1; sd.d2 = sdf->d2;
-    sd.cx = sdf->center[0]; sd.cy = sdf->center[1]; sd.cz = sdf->center[2]; sd.scale = sdf->scale;
+    sd = egx_sdf_dev(*sdf);
     sd.coarse = static_cast<const float2*>(sdf->coarse_minmax);
-    sd.c0 = egx_ceil_div(sdf->d0, 4); sd.c1 = egx_ceil_div(sdf->d1, 4); sd.c2 = egx_ceil_div(sdf->d2, 4);
     mips = reinterpret_cast<const float*>(static_cast<const char*>(sdf->coarse_minmax) + egx_sdf_table_bytes(sd.c0, sd.c1, sd.c2));
   }
   const bool fix = split3 && mode == 3 && sdf;   // mixed blend with counts: the pose kernel also writes the per-body error bound
@@ -812,12 +329,18 @@ static int lbs_forward_launch(const egx_body_model* m, const float* xb, const fl
   if (cull) lbs_launch_cull_order(m, xb, R0, T0, sd, mips, B, fpa, nbg_all, order, flags, counts, stream);
   const SdfSceneDev* scene_tab = ms ? set->table : nullptr;
   const int n_scenes = ms ? set->S : 0;
-  lbs_launch_pose(ms, stream, m->pc, xb, betas, B, fpa,
-                  split3 ? nullptr : feat, split3 ? reinterpret_cast<unsigned short*>(feat) : nullptr, A4, out_joints,
-                  EGX_NUM_JOINTS_OUT, (split3 && mode >= 2) ? 1.f : 0.f, (split3 && mode == 3) ? feat4 : nullptr, sdf ? out_pene_count : nullptr,
-                  static_cast<const int*>(order), fvec, jpos, (int)wl.Bp, fix ? reinterpret_cast<float*>(ws + wl.fix_e) : nullptr,
-                  reinterpret_cast<int*>(ws + wl.fix_stats), fix ? reinterpret_cast<unsigned short*>(ws + wl.skinB) : nullptr,
-                  reinterpret_cast<f32x4*>(ws + wl.cinit), R0, T0, sd, scene_tab, static_cast<const int*>(agent_scene), n_scenes);
+  LbsPoseArgs a;
+  a.pc = m->pc; a.xb = xb; a.betas = betas; a.B = B; a.fpa = fpa; a.A4 = A4; a.out_joints = out_joints; a.joints_ld = EGX_NUM_JOINTS_OUT;
+  if (split3) a.feat3 = reinterpret_cast<unsigned short*>(feat); else a.feat = feat;   // one buffer: bf16 planes or the fp32 operand
+  a.template_lo_feat = (split3 && mode >= 2) ? 1.f : 0.f;
+  a.feat4 = (split3 && mode == 3) ? feat4 : nullptr;
+  a.zero_counts = sdf ? out_pene_count : nullptr;
+  a.agent_of_slot = order; a.fvec = fvec; a.jpos = jpos; a.Bp = (int)wl.Bp;
+  a.fix_e = fix ? reinterpret_cast<float*>(ws + wl.fix_e) : nullptr;
+  a.skinB = fix ? reinterpret_cast<unsigned short*>(ws + wl.skinB) : nullptr;
+  a.fix_stats = reinterpret_cast<int*>(ws + wl.fix_stats); a.cinit = reinterpret_cast<f32x4*>(ws + wl.cinit);
+  a.R0 = R0; a.T0 = T0; a.sdf = sd; a.scenes = scene_tab; a.agent_scene = agent_scene; a.n_scenes = n_scenes;
+  lbs_launch_pose(ms, stream, a);
   if (cull)
     lbs_launch_cull_items(m, fvec, jpos, (int)wl.Bp, order, B, fpa, nbg_all, R0, T0, sd, mips, flags, items, wl.items_stride, counts, stream);
   if (out_verts || need_picks || sdf) {

@@ -16,11 +16,10 @@
 #include <utility>
 #include <vector>
 
-#include "egx_common.h"
+#include "lbs_pack.h"   // NJ; the joint depths and the folded joint regressor shared with the body model
 
 namespace {
 
-constexpr int NJ = 55;           // kinematic-tree joints
 constexpr int NFEAT = 486;       // 54 x 9 pose features
 constexpr int NPOSE = 165;       // 55 x 3 axis-angle entries
 constexpr int PTS_MAX = 1024;
@@ -466,14 +465,9 @@ extern "C" int egx_point_set_create(const egx_body_model_host* d, const int32_t*
   // the tree: parents, joints by depth, children in ascending order
   std::vector<int> tree(T_SIZE, 0), depth(NJ, 0);
   int max_depth = 0;
+  if (!lbs_joint_depths(d->parents_host, depth.data(), &max_depth)) { egx_set_error("egx_point_set_create: parents must be topologically ordered"); return EGX_ERR_ARG; }
   tree[T_PAR] = -1;
-  for (int j = 1; j < NJ; ++j) {
-    const int p = d->parents_host[j];
-    if (p < 0 || p >= j) { egx_set_error("egx_point_set_create: parents must be topologically ordered"); return EGX_ERR_ARG; }
-    tree[T_PAR + j] = p;
-    depth[j] = depth[p] + 1;
-    max_depth = std::max(max_depth, depth[j]);
-  }
+  for (int j = 1; j < NJ; ++j) tree[T_PAR + j] = d->parents_host[j];
   int n = 0;
   for (int lev = 0; lev <= max_depth; ++lev) {
     tree[T_LOFF + lev] = n;
@@ -500,19 +494,7 @@ extern "C" int egx_point_set_create(const egx_body_model_host* d, const int32_t*
     }
     for (int j = 0; j < NJ; ++j) wT[(size_t)j * P + p] = d->lbs_weights_host[v * NJ + j];
   }
-  // rest joints as an affine function of betas: the joint regressor folded in float64
-  for (int j = 0; j < NJ; ++j) {
-    double t[3] = {0, 0, 0}, s[30];
-    for (int e = 0; e < 30; ++e) s[e] = 0;
-    for (int v = 0; v < V; ++v) {
-      const double r = d->J_regressor_host[(size_t)j * V + v];
-      if (r == 0.0) continue;
-      for (int c = 0; c < 3; ++c) t[c] += r * (double)d->v_template_host[(size_t)v * 3 + c];
-      for (int e = 0; e < 30; ++e) s[e] += r * (double)d->shapedirs_host[(size_t)v * 30 + e];
-    }
-    for (int c = 0; c < 3; ++c) Jt[3 * j + c] = (float)t[c];
-    for (int e = 0; e < 30; ++e) Jsd[(size_t)j * 30 + e] = (float)s[e];
-  }
+  lbs_fold_joint_regressor(d, Jt.data(), Jsd.data());   // rest joints as an affine function of betas
   for (int i = 0; i < 12 * 45; ++i) { hc[i] = d->hand_comps_l_host[i]; hc[12 * 45 + i] = d->hand_comps_r_host[i]; }
   for (int i = 0; i < 45; ++i) { hm[i] = d->hand_mean_l_host[i]; hm[45 + i] = d->hand_mean_r_host[i]; }
 

@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <string>
+#include <vector>
 
 #include "../../include/egogen_hip.h"
 
@@ -45,6 +46,14 @@ void egx_set_error(const std::string& msg);
 static inline int egx_ceil_div(int a, int b) { return (a + b - 1) / b; }
 static inline size_t egx_align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
+// device copy of a host vector (an empty one still gets an allocation); the caller frees *dptr, also after a failure
+template <typename T>
+static int egx_upload(T** dptr, const std::vector<T>& h) {
+  EGX_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(dptr), (h.empty() ? 1 : h.size()) * sizeof(T)));
+  if (!h.empty()) EGX_HIP_CHECK(hipMemcpy(*dptr, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice));
+  return EGX_OK;
+}
+
 // Trilinear SDF lookup with torch.grid_sample semantics (align_corners=False, padding 'border'),
 // NEGATED as crowd_ppo/utils.py:83-84 does.  Corner order / weight products follow
 // aten GridSamplerKernel so that fp32 results match the CPU path to the last bits.
@@ -55,6 +64,14 @@ struct SdfDev {
   const float2* coarse;  // optional padded bracket table [(c0+2)][(c1+2)][(c2+2)] {min,max} (egx_sdf_build_coarse)
   int c0, c1, c2;
 };
+
+// The grid of a descriptor: dimensions, the map to voxels and, where egx_sdf_build_coarse has made its tables, their cell counts.
+// What only one caller reads stays with it: the bracket table pointer (LBS launcher), the bricked copy (sdf.hip, sdf_grad.hip).
+inline SdfDev egx_sdf_dev(const egx_sdf_grid& g) {
+  SdfDev s{g.grid, g.d0, g.d1, g.d2, g.center[0], g.center[1], g.center[2], g.scale, nullptr, 0, 0, 0};
+  if (g.coarse_minmax) { s.c0 = egx_ceil_div(g.d0, 4); s.c1 = egx_ceil_div(g.d1, 4); s.c2 = egx_ceil_div(g.d2, 4); }
+  return s;
+}
 
 // One scene of an SDF scene set (egx_sdf_scene_set, device table of 40-byte records): what the LBS count reads per body.  Every
 // scene of a set has the grid dimensions of the launch's SdfDev; only the pointers, the map to voxels and the slope differ.
@@ -72,7 +89,7 @@ __host__ __device__ inline SdfDev egx_sdf_scene(const SdfDev& dims, const SdfSce
   s.cx = e.cx; s.cy = e.cy; s.cz = e.cz; s.scale = e.scale;
   return s;
 }
-// The opaque egx_sdf_scene_set of the header (made by egx_sdf_scene_set_create, body_model.hip; read by the LBS launcher and by
+// The opaque egx_sdf_scene_set of the header (made by egx_sdf_scene_set_create, sdf.hip; read by the LBS launcher and by
 // the penalty calls of sdf_grad.hip).
 struct egx_sdf_scene_set {
   int S = 0;
@@ -83,7 +100,7 @@ struct egx_sdf_scene_set {
 // Free-space pyramid behind the bracket table (same buffer, after the float2 entries, 256-byte aligned): level l = 1..4 holds,
 // per block of 2^l x 2^l x 2^l PADDED bracket cells, the maximum of their `max` entries.  A box of padded cells whose pyramid
 // entries are all < 0 contains only points whose interpolated value is < 0 (convexity of the interpolation), i.e. free space
-// under the count's sign convention (a vertex counts when -trilinear < 0).  Used by the LBS work-item culling (body_model.hip).
+// under the count's sign convention (a vertex counts when -trilinear < 0).  Used by the LBS work-item culling (lbs_cull.hip).
 constexpr int EGX_SDF_MIP_LEVELS = 4;
 __host__ __device__ inline int egx_sdf_mip_dim(int c, int l) { return ((c + 2) + (1 << l) - 1) >> l; }
 __host__ __device__ inline size_t egx_sdf_mip_offset(int c0, int c1, int c2, int l) {   // in floats, from the start of the pyramid

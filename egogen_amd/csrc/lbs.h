@@ -1,6 +1,6 @@
 // What more than one file of the linear-blend-skinning (LBS) forward needs: the layout constants of the blend GEMM, the pose constants,
-// the fix-up band of the mixed blend, the loaded model, the parameter block and per-wave state of the fused kernels, small device
-// helpers, and the host launchers each kernel file exports.  The library is built without relocatable device code: a __global__
+// the fix-up band of the mixed blend, the loaded model (packed on the host by lbs_pack.hip, see lbs_pack.h), the parameter block and
+// per-wave state of the fused kernels, small device helpers, and the host launchers each kernel file exports.  The library is built without relocatable device code: a __global__
 // function is launched, and has its attributes set, only from the file that defines it (lbs_pose.hip, lbs_fused.hip,
 // lbs_fused3.hip, lbs_fix.hip, lbs_cull.hip); device code shared by several kernels is __forceinline__ here and in lbs_epilogue.h.
 #pragma once
@@ -50,6 +50,8 @@ __host__ __device__ inline unsigned short egx_f16_rne(float x) {
   return u;
 }
 __host__ __device__ inline int egx_compact_joint(int j) { return (j - 1) - (j > 24 ? 3 : 0); }  // j in 1..54, j != 22..24
+__host__ __device__ inline int egx_expand_joint(int jc) { return jc + 1 + (jc >= 21 ? 3 : 0); }  // its inverse: jc in 0..50
+constexpr int NLMK = 51, NEXTRA = 21;  // landmarks (three corners each) and vertex joints behind the 55 kinematic joints
 
 }  // namespace
 
@@ -128,8 +130,18 @@ constexpr int LBS_FIXQ_CAP = 1 << 12;   // entries per sub-queue: 64 x 4096 x 8 
 constexpr int SKIN_BT_A = NJ * 2 * 32;            // 16-byte records of rows a = 0, 1 per 32-body tile
 constexpr int SKIN_BT_BYTES = NJ * 2 * 32 * 24;   // both parts
 
-struct egx_body_model {
+// the scalars of a loaded model: the packing (lbs_pack.hip) fills them, egx_body_model_create copies the block as it is
+struct LbsModelDims {
   int V = 0, NVT = 0, NW = 0, M = 0, NP = 0;
+  int n_pick_tiles = 0, n_sdf_tiles = 0;           // entries of pick_tiles / sdf_tiles
+  int verts_pick_tiles = 0, verts_sdf_tiles = 0;   // real vertices inside the two tile lists (work accounting)
+  int cull_ok = 0;             // skinning weights are a convex combination (>= 0, rows sum to 1) and the bound is tight: items are culled
+  int sdf_lead_picks = 0;      // sdf_tiles starts with pick_tiles (in the same order)
+  float rest_pelvis[3] = {0.f, 0.f, 0.f};   // root joint of the mean shape (host copy)
+  float cull_ref_margin = 0.f;              // blend-shape margin of the median tile at the reference pose (metres)
+};
+
+struct egx_body_model : LbsModelDims {
   float* dirs_rm = nullptr;    // [NVT*32 rows][3 coords][KDIM] fp32, vertex-major: what the fp32 re-evaluation of single vertices reads (lbs_fix_one)
   bf16x8* skinW = nullptr;     // matrix-pipe skinning weights (see SKIN_BT_BYTES)
   int* skin_ks_off = nullptr;  // [NVT+1] k-steps (8 joints of the tile's list each) before tile vt
@@ -141,10 +153,7 @@ struct egx_body_model {
   float* tj_w = nullptr;       // [tj_off[NVT]][32] dense weights of the tile's 32 vertices for that joint
   int* pick_slot = nullptr;    // [NVT*32], -1 = not picked
   int* pick_tiles = nullptr;   // [n_pick_tiles] vertex tiles that hold a picked vertex (all a markers-and-joints-only call needs)
-  int n_pick_tiles = 0;
   int* sdf_tiles = nullptr;    // [n_sdf_tiles] tiles that hold a picked vertex or a vertex of the penetration count (non-feet)
-  int n_sdf_tiles = 0;
-  int verts_pick_tiles = 0, verts_sdf_tiles = 0;   // real vertices inside the two tile lists (work accounting)
   uint8_t* vflags = nullptr;   // [NVT*32] bit0 feet, bit1 valid
   int* vorig = nullptr;        // [NVT*32] original vertex id of every (sorted) row, -1 = padding
   PoseConsts* pc = nullptr;
@@ -156,10 +165,6 @@ struct egx_body_model {
   // posed joints it is bound to
   float* cull_E = nullptr;     // [NVT][64]: [0,10) shape terms, [10,61) pose terms per movable joint (compact order), rest 0
   float* cull_D0 = nullptr;    // [tj_off[NVT]]: rest distance bound per (tile, joint of its list)
-  int cull_ok = 0;             // skinning weights are a convex combination (>= 0, rows sum to 1): the bound holds
-  int sdf_lead_picks = 0;      // sdf_tiles starts with pick_tiles (in the same order)
-  float rest_pelvis[3] = {0.f, 0.f, 0.f};   // root joint of the mean shape (host copy)
-  float cull_ref_margin = 0.f;              // blend-shape margin of the median tile at the reference pose (metres)
 };
 
 // Rotation matrix of joint j of one body from its parameter row x[93] (transl 3 | global orient 3 | body pose 63 | hand PCA 12 + 12;
@@ -329,12 +334,24 @@ inline int lbs_device_cus(LbsDeviceInfo (&devs)[kMaxDevices], Raise&& raise_caps
   return EGX_OK;
 }
 
-// lbs_pose.hip: egx_pose_chain_kernel<ms> on ceil(B / 4) blocks; the arguments are the kernel's
-void lbs_launch_pose(bool ms, hipStream_t stream, const PoseConsts* pc, const float* xb, const float* betas, int B, int fpa, float* feat,
-                     unsigned short* feat3, f32x4* A4, float* out_joints, int joints_ld, float template_lo_feat, unsigned short* feat4,
-                     int* zero_counts, const int* agent_of_slot, float* fvec, float* jpos, int Bp, float* fix_e, int* fix_stats,
-                     unsigned short* skinB, f32x4* cinit, const float* R0, const float* T0, SdfDev sdf, const SdfSceneDev* scenes,
-                     const int* agent_scene, int n_scenes);
+// lbs_pose.hip: egx_pose_chain_kernel<ms> on ceil(B / 4) blocks.  The members are the kernel's arguments (documented there), which it
+// takes one by one; null / zero = that output is not wanted.
+struct LbsPoseArgs {
+  const PoseConsts* pc = nullptr;
+  const float *xb = nullptr, *betas = nullptr, *R0 = nullptr, *T0 = nullptr;
+  int B = 0, fpa = 0, joints_ld = 0, Bp = 0;
+  float *feat = nullptr, *out_joints = nullptr, *fvec = nullptr, *jpos = nullptr, *fix_e = nullptr;
+  unsigned short *feat3 = nullptr, *feat4 = nullptr, *skinB = nullptr;
+  f32x4 *A4 = nullptr, *cinit = nullptr;
+  int *zero_counts = nullptr, *fix_stats = nullptr;
+  const int* agent_of_slot = nullptr;
+  float template_lo_feat = 0.f;
+  SdfDev sdf = {};
+  const SdfSceneDev* scenes = nullptr;   // scene sets: the table, the agents' indices into it, its size
+  const int* agent_scene = nullptr;
+  int n_scenes = 0;
+};
+void lbs_launch_pose(bool ms, hipStream_t stream, const LbsPoseArgs& a);
 // lbs_cull.hip: egx_lbs_agent_order_kernel in front of the pose kernel, egx_lbs_cull_kernel + egx_lbs_compact_kernel behind it
 void lbs_launch_cull_order(const egx_body_model* m, const float* xb, const float* R0, const float* T0, const SdfDev& sd, const float* mips,
                            int B, int fpa, int nbg_all, int* order, int* flags, int* counts, hipStream_t stream);

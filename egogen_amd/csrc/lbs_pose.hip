@@ -299,12 +299,9 @@ __global__ __launch_bounds__(256) void egx_pose_chain_kernel(const PoseConsts* _
   }
 }
 
-void lbs_launch_pose(bool ms, hipStream_t stream, const PoseConsts* pc, const float* xb, const float* betas, int B, int fpa, float* feat,
-                     unsigned short* feat3, f32x4* A4, float* out_joints, int joints_ld, float template_lo_feat, unsigned short* feat4,
-                     int* zero_counts, const int* agent_of_slot, float* fvec, float* jpos, int Bp, float* fix_e, int* fix_stats,
-                     unsigned short* skinB, f32x4* cinit, const float* R0, const float* T0, SdfDev sdf, const SdfSceneDev* scenes,
-                     const int* agent_scene, int n_scenes) {
-  hipLaunchKernelGGL(ms ? egx_pose_chain_kernel<true> : egx_pose_chain_kernel<false>, dim3(egx_ceil_div(B, 4)), dim3(256), 0, stream, pc, xb, betas,
-                     B, fpa, feat, feat3, A4, out_joints, joints_ld, template_lo_feat, feat4, zero_counts, agent_of_slot, fvec, jpos, Bp, fix_e,
-                     fix_stats, skinB, cinit, R0, T0, sdf, scenes, agent_scene, n_scenes);
+void lbs_launch_pose(bool ms, hipStream_t stream, const LbsPoseArgs& a) {
+  hipLaunchKernelGGL(ms ? egx_pose_chain_kernel<true> : egx_pose_chain_kernel<false>, dim3(egx_ceil_div(a.B, 4)), dim3(256), 0, stream, a.pc, a.xb,
+                     a.betas, a.B, a.fpa, a.feat, a.feat3, a.A4, a.out_joints, a.joints_ld, a.template_lo_feat, a.feat4, a.zero_counts,
+                     a.agent_of_slot, a.fvec, a.jpos, a.Bp, a.fix_e, a.fix_stats, a.skinB, a.cinit, a.R0, a.T0, a.sdf, a.scenes, a.agent_scene,
+                     a.n_scenes);
 }

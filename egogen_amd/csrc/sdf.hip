@@ -196,11 +196,10 @@ extern "C" int egx_sdf_sample(const egx_sdf_grid* sdf, const float* pts, int64_t
   EGX_REQUIRE(egx_sdf_dims_ok(sdf->d0, sdf->d1, sdf->d2), "sdf grid needs d2 >= 2 and fewer than 2^32 samples");
   if (n == 0) return EGX_OK;  // empty input is legal
   EGX_REQUIRE(pts && out && n > 0, "null points / output");
-  SdfDev s{sdf->grid, sdf->d0, sdf->d1, sdf->d2, sdf->center[0], sdf->center[1], sdf->center[2], sdf->scale, nullptr, 0, 0, 0};
+  const SdfDev s = egx_sdf_dev(*sdf);
   const int64_t blocks = (n + 256 * EGX_SDF_PPT - 1) / (256 * EGX_SDF_PPT);
   const int grid = (int)(blocks < 8192 ? blocks : 8192);
   if (sdf->coarse_minmax) {   // the tables of egx_sdf_build_coarse are there: gather from the bricked copy
-    s.c0 = egx_ceil_div(sdf->d0, 4); s.c1 = egx_ceil_div(sdf->d1, 4); s.c2 = egx_ceil_div(sdf->d2, 4);
     const float* bricks = reinterpret_cast<const float*>(static_cast<const char*>(sdf->coarse_minmax) + egx_sdf_bricks_offset(s.c0, s.c1, s.c2));
     hipLaunchKernelGGL(egx_sdf_sample_bricks_kernel, dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream_), s, bricks, pts, n, out);
   } else {
@@ -209,6 +208,62 @@ extern "C" int egx_sdf_sample(const egx_sdf_grid* sdf, const float* pts, int64_t
   EGX_HIP_CHECK(hipGetLastError());
   return EGX_OK;
 }
+
+// ------------------------------------------------------------------------------------------------
+// SDF scene sets: the per-scene records of egx_lbs_forward_scenes, made once (struct egx_sdf_scene_set: egx_common.h)
+// ------------------------------------------------------------------------------------------------
+
+extern "C" int egx_sdf_scene_set_create(const egx_sdf_grid* scenes, int num_scenes, egx_sdf_scene_set** out) {
+  EGX_REQUIRE(scenes && out, "null argument");
+  EGX_REQUIRE(num_scenes >= 1 && num_scenes < (1 << 15), "a scene set holds 1 .. 32767 scenes");   // the fused kernels queue the index in 15 bits
+  std::vector<SdfSceneDev> rec((size_t)num_scenes);
+  const egx_sdf_grid& s0 = scenes[0];
+  // every check comes before the first device access (the slope reads below): a rejected set touches no pointer it was given
+  for (int i = 0; i < num_scenes; ++i) {
+    const egx_sdf_grid& g = scenes[i];
+    if (g.d0 != s0.d0 || g.d1 != s0.d1 || g.d2 != s0.d2) {
+      egx_set_error("egx_sdf_scene_set_create: scene " + std::to_string(i) + " has grid dimensions " + std::to_string(g.d0) + "x" +
+                    std::to_string(g.d1) + "x" + std::to_string(g.d2) + ", scene 0 " + std::to_string(s0.d0) + "x" +
+                    std::to_string(s0.d1) + "x" + std::to_string(s0.d2) + ": the scenes of a set share their dimensions");
+      return EGX_ERR_ARG;
+    }
+  }
+  for (int i = 0; i < num_scenes; ++i) {
+    const egx_sdf_grid& g = scenes[i];
+    if (!g.grid || !g.coarse_minmax || !egx_sdf_dims_ok(g.d0, g.d1, g.d2) || g.d0 <= 0 || g.d1 <= 0) {
+      egx_set_error("egx_sdf_scene_set_create: scene " + std::to_string(i) +
+                    " needs a grid with d2 >= 2 and fewer than 2^32 samples and its bracket table (egx_sdf_build_coarse)");
+      return EGX_ERR_ARG;
+    }
+  }
+  // the slopes (aux[3] of each table) were written by egx_sdf_build_coarse on some stream: wait for it, then read them once
+  EGX_HIP_CHECK(hipDeviceSynchronize());
+  const int c0 = egx_ceil_div(s0.d0, 4), c1 = egx_ceil_div(s0.d1, 4), c2 = egx_ceil_div(s0.d2, 4);
+  for (int i = 0; i < num_scenes; ++i) {
+    const egx_sdf_grid& g = scenes[i];
+    SdfSceneDev& r = rec[(size_t)i];
+    r.grid = g.grid;
+    r.coarse = static_cast<const float2*>(g.coarse_minmax);
+    r.cx = g.center[0]; r.cy = g.center[1]; r.cz = g.center[2]; r.scale = g.scale;
+    EGX_HIP_CHECK(hipMemcpy(&r.slope, static_cast<const char*>(g.coarse_minmax) + egx_sdf_aux_offset(c0, c1, c2) + 3 * sizeof(float),
+                            sizeof(float), hipMemcpyDeviceToHost));
+    r.pad = 0.f;
+  }
+  auto* set = new egx_sdf_scene_set();
+  set->S = num_scenes;
+  set->dims = s0;
+  if (int rc = egx_upload(&set->table, rec)) { (void)hipFree(set->table); delete set; return rc; }
+  *out = set;
+  return EGX_OK;
+}
+
+extern "C" void egx_sdf_scene_set_destroy(egx_sdf_scene_set* set) {
+  if (!set) return;
+  (void)hipFree(set->table);
+  delete set;
+}
+
+extern "C" int egx_sdf_scene_set_size(const egx_sdf_scene_set* set) { return set ? set->S : 0; }
 
 // ---------------------------------------------------------------------------------------------------------
 // Scene preparation: signed-distance grid of a closed triangle mesh in the storage convention of

@@ -286,12 +286,9 @@ bool grid_ok(const egx_sdf_grid* g) {
 }
 
 SdfDev dev_of(const egx_sdf_grid& g, const float** bricks) {
-  SdfDev s{g.grid, g.d0, g.d1, g.d2, g.center[0], g.center[1], g.center[2], g.scale, nullptr, 0, 0, 0};
-  *bricks = nullptr;
-  if (g.coarse_minmax) {   // the tables of egx_sdf_build_coarse are there: gather from the bricked copy
-    s.c0 = egx_ceil_div(g.d0, 4); s.c1 = egx_ceil_div(g.d1, 4); s.c2 = egx_ceil_div(g.d2, 4);
-    *bricks = reinterpret_cast<const float*>(static_cast<const char*>(g.coarse_minmax) + egx_sdf_bricks_offset(s.c0, s.c1, s.c2));
-  }
+  const SdfDev s = egx_sdf_dev(g);
+  // the tables of egx_sdf_build_coarse are there: gather from the bricked copy
+  *bricks = g.coarse_minmax ? reinterpret_cast<const float*>(static_cast<const char*>(g.coarse_minmax) + egx_sdf_bricks_offset(s.c0, s.c1, s.c2)) : nullptr;
   return s;
 }
 

@@ -90,7 +90,8 @@ def _pose_block(bm):
 
 
 def model_consts(bm):
-    """the band constants egx_body_model_create derives from a model (float64, rounded up to fp32 as there)"""
+    """the band constants the packing (csrc/lbs_pack.hip) derives from a model: float64, rounded up to fp32 as there
+    (compared bit for bit by tests/test_lbs_pack_cpu.py)"""
     up = lambda x: np.float32(np.asarray(x, np.float64) * (1.0 + 1e-6)).astype(np.float64)
     P = _pose_block(bm).astype(np.float64)                                   # [459, V, 3]
     dP = np.where(FP16_COL[:, None, None], f16(P) - P, 0.0)
@@ -185,7 +186,8 @@ def cheap_posed_error(bm, xb, betas, vids=None):
 
 
 def kernel_vertex_order(bm, marker_vids, feet_vids):
-    """perm[row] of egx_body_model_create (picked vertices first, then by the set of joints a vertex is bound to)"""
+    """perm[row] of the packing, csrc/lbs_pack.hip (picked vertices first, then by the set of joints a vertex is bound to;
+    compared by tests/test_lbs_pack_cpu.py)"""
     V = bm["v_template"].shape[0]
     pick = np.zeros(V, bool)
     pick[np.asarray(marker_vids)] = True
