@@ -175,6 +175,12 @@ SIGNATURES = {
     "egx_linear": (C.c_int, [C.POINTER(LinearDesc), C.c_void_p]),
     "egx_gru_pointwise": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "egx_cont6d_to_aa": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+    "egx_cont6d_to_aa_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "egx_primitive_loss_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_void_p,
+                                             C.c_void_p, C.c_void_p]),
+    "egx_primitive_loss_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_void_p,
+                                              C.c_void_p, C.c_void_p]),
+    "egx_primitive_reseed": (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 4 + [C.c_int] * 3 + [C.c_void_p] * 7),
     "egx_posenc": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "egx_sample_prior_workspace_bytes": (C.c_size_t, [C.c_int]),
     "egx_sample_prior": (C.c_int, [C.POINTER(PriorWeights), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int,

@@ -347,3 +347,153 @@ class FlatGrads:
     def zero(self):
         self.attach()
         self.flat.zero_()
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# combo training (train_combo.GAMMAPrimitiveComboTrainOP): the glue between predictor, regressor and body model
+# ---------------------------------------------------------------------------------------------------------------------
+class Cont6dToAaFn(torch.autograd.Function):
+    """MoshRegressor._cont2aa (models_GAMMA_primitive.py:208-219) as one node: xb6[n,159] -> xb[n,93].  Forward is
+    `egx_cont6d_to_aa`, backward `egx_cont6d_to_aa_backward`, which recomputes the forward from xb6 (the only saved tensor)."""
+
+    @staticmethod
+    def forward(ctx, xb6):
+        lib = _lib.load()
+        xb6 = xb6.to(torch.float32).contiguous()
+        n = int(xb6.shape[0])
+        out = torch.empty(n, 93, dtype=torch.float32, device=xb6.device)
+        _lib.check(lib.egx_cont6d_to_aa(_lib.ptr(xb6), n, _lib.ptr(out), 93, _lib.current_stream_ptr()), "egx_cont6d_to_aa")
+        ctx.save_for_backward(xb6)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        lib = _lib.load()
+        (xb6,) = ctx.saved_tensors
+        g = g.to(torch.float32).contiguous()
+        gx = torch.empty_like(xb6)
+        _lib.check(lib.egx_cont6d_to_aa_backward(_lib.ptr(xb6), _lib.ptr(g), int(xb6.shape[0]), _lib.ptr(gx), _lib.current_stream_ptr()),
+                   "egx_cont6d_to_aa_backward")
+        return gx
+
+
+_LOSS_WS = {}
+
+
+class PrimitiveLossFn(torch.autograd.Function):
+    """_calc_loss_rec (models_GAMMA_primitive.py:773-784) on Y, Y_rec [T,b,D]: returns (w_rec rec + w_td td, items[3] =
+    {loss, rec, td}); `egx_primitive_loss_forward` / `_backward`.  Y is a target: only Y_rec receives a gradient."""
+
+    @staticmethod
+    def forward(ctx, Y, Y_rec, w_rec, w_td):
+        lib = _lib.load()
+        if Y.shape != Y_rec.shape or Y.dim() != 3:
+            raise ValueError(f"Y and Y_rec must both be [T,b,D], got {tuple(Y.shape)} and {tuple(Y_rec.shape)}")
+        Y, Y_rec = Y.to(torch.float32).contiguous(), Y_rec.to(torch.float32).contiguous()
+        T, b, D = (int(v) for v in Y.shape)
+        key = (str(Y.device), int(torch.cuda.current_stream(Y.device).cuda_stream))
+        ws = _LOSS_WS.get(key)
+        if ws is None:
+            ws = _LOSS_WS[key] = torch.empty(512, dtype=torch.float64, device=Y.device)   # EGX_PRIMITIVE_LOSS_WS_BYTES
+        out = torch.empty(3, dtype=torch.float32, device=Y.device)
+        _lib.check(lib.egx_primitive_loss_forward(_lib.ptr(Y), _lib.ptr(Y_rec), T, b, D, float(w_rec), float(w_td), _lib.ptr(out),
+                                                  _lib.ptr(ws), _lib.current_stream_ptr()), "egx_primitive_loss_forward")
+        ctx.save_for_backward(Y, Y_rec)
+        ctx.w = (float(w_rec), float(w_td))
+        ctx.mark_non_differentiable(out)
+        return out[0].clone(), out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g, _g_items):
+        lib = _lib.load()
+        Y, Y_rec = ctx.saved_tensors
+        T, b, D = (int(v) for v in Y.shape)
+        g = g.to(torch.float32).reshape(1).contiguous()
+        gy = torch.empty_like(Y_rec)
+        _lib.check(lib.egx_primitive_loss_backward(_lib.ptr(Y), _lib.ptr(Y_rec), T, b, D, ctx.w[0], ctx.w[1], _lib.ptr(g), _lib.ptr(gy),
+                                                   _lib.current_stream_ptr()), "egx_primitive_loss_backward")
+        return None, gy, None, None
+
+
+@torch.no_grad()
+def primitive_reseed(joints, X_prev, Yg, R_prev, T_prev):
+    """The no-grad block of calc_loss_rollout (models_GAMMA_primitive.py:959-984) as one launch (`egx_primitive_reseed`):
+    joints[b,J,3] of the seed body, X_prev[t_his,b,201], Yg[t_pred,b,201] (world), R_prev[b,3,3], T_prev[b,1,3] ->
+    X[t_his,b,201], Y[t_pred,b,201], R_curr[b,3,3], T_curr[b,1,3], R_[b,3,3], T_[b,1,3]."""
+    lib = _lib.load()
+    f = lambda t: t.detach().to(torch.float32).contiguous()
+    joints, X_prev, Yg, R_prev, T_prev = f(joints), f(X_prev), f(Yg), f(R_prev), f(T_prev)
+    b, J = int(joints.shape[0]), int(joints.shape[1])
+    t_his, t_pred = int(X_prev.shape[0]), int(Yg.shape[0])
+    if X_prev.numel() != t_his * b * 201 or Yg.numel() != t_pred * b * 201 or R_prev.numel() != 9 * b or T_prev.numel() != 3 * b:
+        raise ValueError("primitive_reseed: X_prev / Yg must be [t,b,201] and R_prev / T_prev [b,3,3] / [b,1,3] for the b of `joints`")
+    dev = joints.device
+    new = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
+    R_new, T_new, R_curr, T_curr = new(b, 3, 3), new(b, 1, 3), new(b, 3, 3), new(b, 1, 3)
+    X, Y = new(t_his, b, 201), new(t_pred, b, 201)
+    _lib.check(lib.egx_primitive_reseed(_lib.ptr(joints), J, _lib.ptr(X_prev), _lib.ptr(Yg), _lib.ptr(R_prev), _lib.ptr(T_prev), t_his,
+                                        t_pred, b, _lib.ptr(R_new), _lib.ptr(T_new), _lib.ptr(R_curr), _lib.ptr(T_curr), _lib.ptr(X),
+                                        _lib.ptr(Y), _lib.current_stream_ptr()), "egx_primitive_reseed")
+    return X, Y, R_curr, T_curr, R_new, T_new
+
+
+class FrozenLinearFn(torch.autograd.Function):
+    """LinearFn for a layer whose parameters are not trained (the regressor inside the combo step, which Adam never visits,
+    models_GAMMA_primitive.py:1025): the same forward, and of the backward only the input gradient g W - no g^T x product, no
+    bias column sum."""
+
+    @staticmethod
+    def forward(ctx, x, W, b, act, slope, res):
+        x = x.contiguous()
+        if res is not None:
+            res = res.contiguous()
+        a = torch.empty(x.shape[0], W.shape[0], dtype=torch.float32, device=x.device) if (act != 0 and res is not None) else None
+        out = gemm3(x, False, W, False, bias=b, act=act, slope=slope, res=res, out_act=a)
+        ctx.save_for_backward(W, (a if a is not None else out) if act != 0 else None)
+        ctx.act, ctx.slope, ctx.has_res = int(act), float(slope), res is not None
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        lib = _lib.load()
+        W, a = ctx.saved_tensors
+        dout = dout.contiguous()
+        g = dout
+        if ctx.act != 0:
+            g = torch.empty_like(dout)
+            _lib.check(lib.egx_act_bwd_colsum(_lib.ptr(dout), _lib.ptr(a), _lib.ptr(g), None, dout.shape[0], dout.shape[1], ctx.act,
+                                              ctx.slope, _lib.current_stream_ptr()), "egx_act_bwd_colsum")
+        dx = gemm3(g, False, W, True) if ctx.needs_input_grad[0] else None
+        return dx, None, None, None, None, (dout if ctx.has_res else None)
+
+
+class FrozenResMLPFn(torch.autograd.Function):
+    """ResMLPFn without the two weight-gradient products and bias sums (see FrozenLinearFn)."""
+
+    @staticmethod
+    def forward(ctx, x, W1, b1, W2, b2, act, slope):
+        x = x.contiguous()
+        a1 = gemm3(x, False, W1, False, bias=b1, act=act, slope=slope)
+        a2 = torch.empty(x.shape[0], W2.shape[0], dtype=torch.float32, device=x.device)
+        out = gemm3(a1, False, W2, False, bias=b2, act=act, slope=slope, res=x, out_act=a2)
+        ctx.save_for_backward(W1, a1, W2, a2)
+        ctx.act, ctx.slope = int(act), float(slope)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        lib, st = _lib.load(), _lib.current_stream_ptr()
+        W1, a1, W2, a2 = ctx.saved_tensors
+        dout = dout.contiguous()
+        M = dout.shape[0]
+        g2 = torch.empty_like(dout)
+        _lib.check(lib.egx_act_bwd_colsum(_lib.ptr(dout), _lib.ptr(a2), _lib.ptr(g2), None, M, g2.shape[1], ctx.act, ctx.slope, st),
+                   "egx_act_bwd_colsum")
+        d1 = gemm3(g2, False, W2, True)
+        g1 = torch.empty_like(d1)
+        _lib.check(lib.egx_act_bwd_colsum(_lib.ptr(d1), _lib.ptr(a1), _lib.ptr(g1), None, M, g1.shape[1], ctx.act, ctx.slope, st),
+                   "egx_act_bwd_colsum")
+        dx = gemm3(g1, False, W1, True, res=dout) if ctx.needs_input_grad[0] else None
+        return (dx,) + (None,) * 6

@@ -407,6 +407,37 @@ int egx_gru_pointwise(const float* gi, const float* gh, const float* h_prev, int
  * xb6 [n,159] (transl3 | 22x6D | hands24) -> out [n,>=93] (transl3 | 22 axis-angles | hands24). */
 int egx_cont6d_to_aa(const float* xb6, int num_rows, float* out, int out_ld, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Glue of the combo training step (GAMMAPrimitiveComboTrainOP, models_GAMMA_primitive.py:713-1093).  No float atomics and a
+ * fixed summation order: two calls on the same inputs give the same bits.
+ *
+ * egx_cont6d_to_aa_backward: reverse mode of egx_cont6d_to_aa.  xb6 [n,159], g_out [n,93] (gradient of the axis-angle row)
+ *   -> g_xb6 [n,159].  The forward is recomputed from xb6 (nothing saved), per joint in double: normalise, Gram-Schmidt,
+ *   normalise, cross product, the four-branch quaternion extraction on R^T, 2 atan2(|v|, w) / |v| with the w < 0 select.  The
+ *   3 + 24 pass-through columns copy the incoming gradient.  At |v|^2 == 0 (an exact identity) torch's own graph of that
+ *   expression yields NaN (sqrt'(0) * 0); here k = 2 is treated as a constant there and the finite value is returned.
+ * egx_primitive_loss_forward (_calc_loss_rec, :773-784): Y, Y_rec [T,b,D] -> out3 = {w_rec rec + w_td td, rec, td} with
+ *   rec = mean |Y - Y_rec|, td = mean |(Y_rec[1:] - Y_rec[:-1]) - (Y[1:] - Y[:-1])| (0 for T == 1).  The terms are formed in fp32
+ *   as torch forms them, summed in double in an order that depends on the shape alone, and rounded once.  workspace: device
+ *   buffer of EGX_PRIMITIVE_LOSS_WS_BYTES bytes, 8-byte aligned.
+ * egx_primitive_loss_backward: g_Y_rec [T,b,D] = g (w_rec / N sign(Y_rec - Y) + w_td / N_td (sign(D[t-1]) - sign(D[t]))) with D the
+ *   temporal-difference residual, sign(0) = 0 and g = *g_loss (a device scalar); one launch.
+ * egx_primitive_reseed: the no-grad block of calc_loss_rollout (:959-984), one workgroup per sequence.  joints
+ *   [b,joints_per_body,3] of the seed frame, X_prev [t_his,b,67,3], Yg [t_pred,b,67,3] (world), R_prev [b,3,3], T_prev [b,3] ->
+ *   R_new, T_new: the canonical frame of the seed body (baseops.py:214-225, the arithmetic of egx_canonical_frame);
+ *   R_curr = R_prev R_new; T_curr = R_prev T_new + T_prev; X = R_new^T (X_prev - T_new) [t_his,b,201];
+ *   Y = R_curr^T (Yg - T_curr) [t_pred,b,201].  No gradient.
+ * ------------------------------------------------------------------------------------------- */
+#define EGX_PRIMITIVE_LOSS_WS_BYTES 4096
+int egx_cont6d_to_aa_backward(const float* xb6, const float* g_out, int num_rows, float* g_xb6, void* stream);
+int egx_primitive_loss_forward(const float* Y, const float* Y_rec, int T, int b, int D, float w_rec, float w_td, float* out3,
+                               void* workspace, void* stream);
+int egx_primitive_loss_backward(const float* Y, const float* Y_rec, int T, int b, int D, float w_rec, float w_td,
+                                const float* g_loss, float* g_Y_rec, void* stream);
+int egx_primitive_reseed(const float* joints, int joints_per_body, const float* X_prev, const float* Yg, const float* R_prev,
+                         const float* T_prev, int t_his, int t_pred, int num_seqs, float* out_R_new, float* out_T_new,
+                         float* out_R_curr, float* out_T_curr, float* out_X, float* out_Y, void* stream);
+
 /* GAMMAPolicyBase.positional_encoding of obs['dist'] and obs['time'] (models_policy_ppo.py:276-285,302-303):
  * out [A,128] = [posenc(dist) 64 | posenc(time) 64]. */
 int egx_posenc(const float* dist, const float* time, int num_agents, float* out, void* stream);
