@@ -1,0 +1,318 @@
+"""`GAMMAPrimitiveComboGenOP` (motion/models/models_GAMMA_primitive.py:1099-1425, constructed by
+crowd_ppo/primitive_model.py:69): the interface to a trained motion prior outside an environment - one primitive from a motion
+seed (`generate`), the file writer of the primitive evaluation (`generate_primitive_to_files`), and, new here, a chain of
+primitives with the re-canonicalisation between them on the device (`generate_sequence`, kernel egx_primitive_advance): the
+motion-only part of `CrowdEnv.step` (crowd_ppo/crowd_env_2f.py:109-155, 238-265) without scene, rewards or egosensing.
+
+Differences from the reference, all in `generate` unless noted:
+  * `t_his=None` means the model's t_his (the reference computes `20 - None` and fails);
+  * only t_his == 2 is supported (egx_sample_prior takes two history frames): anything else raises ValueError;
+  * with `return_z=True` a supplied `z` is used and returned (the reference ignores it on that path);
+  * inputs may be numpy or torch on either path; `betas` may be (10,), (1,10) or (b,10);
+  * `generate_ppo` is not built: nothing in the reference calls it, and its `policy_model(X, obj_points=, target_ori=,
+    local_map=)` signature belongs to no class in the tree."""
+from __future__ import annotations
+
+import ctypes as C
+import os
+import pickle
+from typing import Optional, Union
+
+import numpy as np
+import torch
+
+from . import _lib
+from .models import GAMMAPrimitiveCombo
+
+T_ALL, T_PRED, NM3, XB = 20, 18, 201, 93
+GENERATE_PPO_NOT_BUILT = ("generate_ppo is not built: nothing in the reference calls it, and its policy_model(X, obj_points=, "
+                          "target_ori=, local_map=) signature belongs to no class in the tree")
+
+
+def _section(cfg, name):
+    """`cfg.modelconfig` (OmegaConf / namespace) or `cfg['modelconfig']` (plain yaml)."""
+    return cfg[name] if isinstance(cfg, dict) else getattr(cfg, name)
+
+
+def _load_ckpt(candidates):
+    """The first readable checkpoint of `candidates` (the reference's try / except chain) -> (state dict, path)."""
+    err = None
+    for f in candidates:
+        try:
+            return torch.load(f, map_location="cpu")["model_state_dict"], f
+        except (OSError, FileNotFoundError) as e:
+            err = e
+    raise FileNotFoundError(f"none of {list(candidates)} could be read: {err}")
+
+
+class PrimitiveSequence:
+    """What `generate_sequence` returns: K primitives of b sequences.
+    markers [K,b,20,67,3] blended markers, params [K,b,20,93], rotmat [K,b,3,3] / transl [K,b,3] the world frame each primitive
+    is expressed in, pelvis [K,b,20,3], z [K,b,128]; betas [b,10]; R0 [b,3,3] / T0 [b,3] the frame after the last primitive."""
+
+    def __init__(self, markers, params, rotmat, transl, pelvis, z, betas, gender, R0, T0):
+        self.markers, self.params, self.rotmat, self.transl, self.pelvis, self.z = markers, params, rotmat, transl, pelvis, z
+        self.betas, self.gender, self.R0, self.T0 = betas, gender, R0, T0
+
+    def primitives(self, i: int) -> list:
+        """Sequence i as the list of 8-item records `utils.save_rollout_results` takes (crowd_env_2f.py:155)."""
+        return [[self.markers[k, i:i + 1], self.params[k, i:i + 1], self.betas[i:i + 1], self.gender, self.rotmat[k, i],
+                 self.transl[k, i:i + 1], self.pelvis[k, i:i + 1], "2-frame"] for k in range(self.markers.shape[0])]
+
+    def save(self, outfolder: str, i: int, man_id=None) -> str:
+        """`motion_<man_id>.pkl` of sequence i with a two-point wpath: first and last pelvis in the world frame."""
+        from .utils import save_rollout_results
+        as_t = lambda x: torch.as_tensor(x)
+        first = as_t(self.rotmat[0, i]) @ as_t(self.pelvis[0, i, 0]) + as_t(self.transl[0, i])
+        last = as_t(self.rotmat[-1, i]) @ as_t(self.pelvis[-1, i, -1]) + as_t(self.transl[-1, i])
+        scene = {"wpath": torch.stack([first, last]), "navmesh_path": None}
+        return save_rollout_results(scene, self.primitives(i), outfolder, man_id=man_id)
+
+
+class GAMMAPrimitiveComboGenOP:
+    """the interface to GAMMA when using it to produce motions"""
+
+    def __init__(self, predictorcfg, regressorcfg, testconfig):
+        self.dtype = torch.float32
+        if not torch.cuda.is_available():
+            raise _lib.EgxError("no HIP device visible - the motion prior has no CPU fallback")
+        _lib.load()
+        self.device = torch.device("cuda", index=testconfig.get("gpu_index", 0))
+        self.predictorcfg, self.regressorcfg, self.testconfig = predictorcfg, regressorcfg, testconfig
+        pm, rm = _section(predictorcfg, "modelconfig"), _section(regressorcfg, "modelconfig")
+        self.use_cont = rm.get("use_cont", False)
+        self.t_his = pm["t_his"]
+        self.var_seed_len = pm.get("var_seed_len", False)
+        self.model: Optional[GAMMAPrimitiveCombo] = None
+        self.body_model = None
+
+    # ------------------------------------------------------------------------------------------------------------------
+    def build_model(self, load_pretrained_model=False, body_model=None):
+        """:1116-1148.  load_pretrained_model: predictor `epoch-400.ckp` (else `epoch-200.ckp`) and regressor `epoch-100.ckp`
+        from the two configs' trainconfig.save_dir (the loader of setup_world.build_motion_prior); otherwise the combo
+        checkpoint `epoch-120.ckp` (else `epoch-10.ckp`) of testconfig['ckpt_dir'], the file train_combo.py writes.  A missing
+        file raises, as in the reference.  `body_model`: the BodyModelHandle of the regressor's gender, needed by
+        `generate_sequence` only."""
+        pm, rm = _section(self.predictorcfg, "modelconfig"), _section(self.regressorcfg, "modelconfig")
+        if load_pretrained_model:
+            from .setup_world import build_motion_prior
+            pdir = _section(self.predictorcfg, "trainconfig")["save_dir"]
+            rdir = _section(self.regressorcfg, "trainconfig")["save_dir"]
+            _, f = _load_ckpt([os.path.join(pdir, "epoch-400.ckp"), os.path.join(pdir, "epoch-200.ckp")])
+            print("[INFO] --load pre-trained predictor: {}".format(f))
+            _, f = _load_ckpt([os.path.join(rdir, "epoch-100.ckp")])
+            print("[INFO] --load pre-trained regressor: {}".format(f))
+            GAMMAPrimitiveCombo(pm, rm)      # the configs must describe the network the loader builds
+            self.model = build_motion_prior(device=self.device, ckpt_dirs=(pdir, rdir))
+        else:
+            self.model = GAMMAPrimitiveCombo(pm, rm)
+            cdir = self.testconfig["ckpt_dir"]
+            sd, f = _load_ckpt([os.path.join(cdir, "epoch-120.ckp"), os.path.join(cdir, "epoch-10.ckp")])
+            self.model.load_state_dict(sd)
+            print("[INFO] --load combo model: {}".format(f))
+            self.model.to(self.device).eval()
+        if body_model is not None:
+            self.body_model = body_model
+
+    def _blend_params(self, body_params, t_his=None):
+        """:1150-1163, in place on [t,b,93]: frames t_his and t_his + 1 become the mean of their neighbours, pose part only."""
+        if t_his is None:
+            t_his = self.t_his
+        start_idx = 6
+        for t in (t_his, t_his + 1):
+            body_params[t, :, start_idx:] = (body_params[t - 1, :, start_idx:] + body_params[t + 1, :, start_idx:]) / 2.0
+        return body_params
+
+    # ------------------------------------------------------------------------------------------------------------------
+    def _dev(self, x, what):
+        if isinstance(x, np.ndarray):
+            x = torch.from_numpy(np.ascontiguousarray(x))
+        elif not torch.is_tensor(x):
+            raise TypeError(f"{what} must be a numpy array or a torch tensor, got {type(x).__name__}")
+        return x.detach().to(self.device, self.dtype)
+
+    def _seed_inputs(self, data, bparams, betas, n_gens, t_his):
+        if self.model is None:
+            raise _lib.EgxError("build_model() first")
+        if t_his is None:
+            t_his = self.t_his
+        if t_his != 2:
+            raise ValueError(f"only t_his == 2 is supported (egx_sample_prior takes two history frames), got {t_his}")
+        X = self._dev(data, "data")[:t_his, :, :NM3]
+        Xb = self._dev(bparams, "bparams")[:t_his]
+        if X.dim() != 3 or X.shape[0] != 2 or X.shape[2] != NM3 or Xb.shape != (2, X.shape[1], XB):
+            raise ValueError(f"data must be [>=2,b,>=201] and bparams [>=2,b,93], got {tuple(data.shape)} / {tuple(bparams.shape)}")
+        bt = self._dev(betas, "betas").reshape(-1, 10)
+        if bt.shape[0] not in (1, X.shape[1]):
+            raise ValueError(f"betas must be (10,), (1,10) or (b,10) with b = {X.shape[1]}, got {tuple(betas.shape)}")
+        if n_gens > 0:
+            X, Xb = X.repeat(1, n_gens, 1), Xb.repeat(1, n_gens, 1)
+            if bt.shape[0] != 1:
+                bt = bt.repeat(n_gens, 1)
+        if bt.shape[0] == 1:
+            bt = bt.repeat(X.shape[1], 1)
+        return X.contiguous(), Xb.contiguous(), bt.contiguous()
+
+    def generate(self, data: Union[torch.Tensor, np.ndarray], bparams: Union[torch.Tensor, np.ndarray],
+                 betas: Union[torch.Tensor, np.ndarray], n_gens: int = -1, to_numpy: bool = True, return_z: bool = False,
+                 param_blending: bool = True, t_his=None, z: Union[None, torch.Tensor, np.ndarray] = None):
+        """generate motion primitives based on a motion seed X (:1166-1249)
+
+        Args:
+            - data: the motion seed, with the shape [t,b,d]
+            - bparams: the body parameters of the motion seed, with the shape [t,b,d]
+            - betas: body shape, (10,), (1,10) or (b,10)
+            - n_gens: how many motions are generated per seed. If -1, it has the same batch size with the input.
+            - to_numpy: produce numpy if true
+            - return_z: return the latent variables if set to True
+            - param_blending: smooth the body poses, to eliminate the first-frame jump and compensate the regressor inaccuracy
+            - t_his: frames in the motion seed; None = the model's t_his; only 2 is supported (ValueError otherwise)
+            - z: latent variables [b',128] (b' = b * n_gens when n_gens > 0), or None for N(0, I)
+
+        Returns Y [b',20,201] (seed and predicted markers), Yb [b',20,93] (seed and regressed body parameters, rotations in
+        axis-angle) and, with return_z, z.  Differences from the reference: see the module docstring."""
+        X, Xb, bt = self._seed_inputs(data, bparams, betas, n_gens, t_his)
+        nb = X.shape[1]
+        if z is None:
+            z = torch.randn(nb, self.model.predictor.z_dim, device=self.device)
+        else:
+            z = self._dev(z, "z")
+            if z.shape != (nb, self.model.predictor.z_dim):
+                raise ValueError(f"z must be [{nb},{self.model.predictor.z_dim}], got {tuple(z.shape)}")
+        Y_pred, Yb_pred = self.model.sample_prior(X, betas=bt, z=z)
+        Y = torch.cat((X, Y_pred), dim=0)
+        Yb = torch.cat((Xb, Yb_pred), dim=0)
+        if param_blending:
+            Yb = self._blend_params(Yb)
+        Y, Yb = Y.permute(1, 0, 2), Yb.permute(1, 0, 2)     # from [t,b,d] to [b,t,d]
+        if to_numpy:
+            Y, Yb = Y.cpu().numpy(), Yb.cpu().numpy()
+            z = z.cpu().numpy()
+        return (Y, Yb, z) if return_z else (Y, Yb)
+
+    def generate_ppo(self, *args, **kwargs):
+        raise NotImplementedError(GENERATE_PPO_NOT_BUILT)
+
+    # ------------------------------------------------------------------------------------------------------------------
+    def generate_sequence(self, data, bparams, betas, n_primitives: int, n_gens: int = -1, z=None, reproj_factor=None,
+                          to_numpy: bool = True, R0=None, T0=None) -> PrimitiveSequence:
+        """A chain of `n_primitives` primitives from the motion seed (data [>=2,b,>=201], bparams [>=2,b,93] in the seed's
+        canonical frame; betas as in `generate`; n_gens variants per seed).  Per primitive: sample_prior_into ->
+        egx_assemble_params -> BodyModelHandle.forward (joints and markers) -> egx_primitive_advance, written into preallocated
+        records; nothing in the loop waits for the device.
+            - z: None (N(0, I) from the torch generator, drawn up front for all primitives) or [n_primitives, b', 128]
+            - reproj_factor: None takes modelconfig['reproj_factor'] of the predictor config (0.5, the policy configs' value,
+              where it has none)
+            - R0 [b',3,3] / T0 [b',3]: the world frame of the seed; the identity when omitted
+        Raises FloatingPointError when a primitive produced a non-finite value (read once, after the loop)."""
+        if self.body_model is None:
+            raise _lib.EgxError("generate_sequence needs the body model: build_model(..., body_model=BodyModelHandle)")
+        K = int(n_primitives)
+        if K < 1:
+            raise ValueError("n_primitives must be >= 1")
+        X, seed, bt = self._seed_inputs(data, bparams, betas, n_gens, None)
+        B, dev, f32 = X.shape[1], self.device, torch.float32
+        zd = self.model.predictor.z_dim
+        if z is None:
+            z = torch.randn(K, B, zd, device=dev)
+        else:
+            z = self._dev(z, "z").contiguous()
+            if z.shape != (K, B, zd):
+                raise ValueError(f"z must be [{K},{B},{zd}], got {tuple(z.shape)}")
+        if reproj_factor is None:
+            reproj_factor = _section(self.predictorcfg, "modelconfig").get("reproj_factor", 0.5)
+        rf = float(reproj_factor)
+        eye = torch.eye(3, device=dev, dtype=f32)
+        R0 = eye.repeat(B, 1, 1) if R0 is None else self._dev(R0, "R0").reshape(B, 3, 3).clone()
+        T0 = torch.zeros(B, 3, device=dev, dtype=f32) if T0 is None else self._dev(T0, "T0").reshape(B, 3).clone()
+        R0, T0 = R0.contiguous(), T0.contiguous()
+        markers = torch.empty(K, B, T_ALL, 67, 3, device=dev, dtype=f32)
+        params = torch.empty(K, B, T_ALL, XB, device=dev, dtype=f32)
+        rotmat = torch.empty(K, B, 3, 3, device=dev, dtype=f32)
+        transl = torch.empty(K, B, 3, device=dev, dtype=f32)
+        pelvis = torch.empty(K, B, T_ALL, 3, device=dev, dtype=f32)
+        xs = [X.contiguous(), torch.empty_like(X)]                  # seed markers [2,B,201], ping-pong (no output aliases an input)
+        seed = seed.permute(1, 0, 2).contiguous()                   # [B,2,93]
+        Y_gen = torch.empty(T_PRED, B, NM3, device=dev, dtype=f32)
+        Yb_gen = torch.empty(T_PRED, B, XB, device=dev, dtype=f32)
+        nonfinite = torch.zeros(1, device=dev, dtype=torch.int32)
+        bm = self.body_model
+        lbs_out = {"joints": torch.empty(B * T_ALL, 127, 3, device=dev, dtype=f32),
+                   "markers": torch.empty(B * T_ALL, bm.M, 3, device=dev, dtype=f32)}
+        if bm.M != 67:
+            raise ValueError(f"the body model carries {bm.M} markers, the motion prior works on 67")
+        # calc_calibrate_offset: joint 0 at zero orientation / translation (the body pose does not move the root)
+        delta_T = bm.joints55(torch.zeros(B, XB, device=dev, dtype=f32), bt, 1)[:, 0].contiguous()
+        bm.workspace(B * T_ALL)
+        self._advance_loop(K, B, rf, z, bt, xs, seed, Y_gen, Yb_gen, lbs_out, delta_T, R0, T0, markers, params, rotmat, transl,
+                           pelvis, nonfinite)
+        n = int(nonfinite.item())
+        if n:
+            raise FloatingPointError(f"{n} primitives of the chain produced non-finite values")
+        res = [markers, params, rotmat, transl, pelvis, z, bt, R0, T0]
+        if to_numpy:
+            res = [t.cpu().numpy() for t in res]
+        gender = str(_section(self.regressorcfg, "modelconfig").get("gender", "male"))
+        return PrimitiveSequence(*res[:7], gender, res[7], res[8])
+
+    def _advance_loop(self, K, B, rf, z, bt, xs, seed, Y_gen, Yb_gen, lbs_out, delta_T, R0, T0, markers, params, rotmat, transl,
+                      pelvis, nonfinite):
+        """The primitive loop of `generate_sequence`: launches only, no allocation that depends on k, no host wait."""
+        lib, bm = _lib.load(), self.body_model
+        st = _lib.current_stream_ptr()
+        for k in range(K):
+            cur, nxt = xs[k % 2], xs[(k + 1) % 2]
+            self.model.sample_prior_into(cur[0], cur[1], NM3, bt, z[k], Y_gen, Yb_gen)
+            pp = params[k]
+            _lib.check(lib.egx_assemble_params(_lib.ptr(seed), _lib.ptr(Yb_gen), B, _lib.ptr(pp), st), "egx_assemble_params")
+            bm.forward(pp.view(B * T_ALL, XB), bt, T_ALL, want_verts=False, want_joints=True, want_markers=True, out=lbs_out)
+            _lib.check(lib.egx_primitive_advance(
+                _lib.ptr(pp), _lib.ptr(Y_gen), C.c_void_p(cur[0].data_ptr()), C.c_void_p(cur[1].data_ptr()), NM3,
+                _lib.ptr(lbs_out["joints"]), 127, _lib.ptr(lbs_out["markers"]), _lib.ptr(delta_T), rf, B, _lib.ptr(R0), _lib.ptr(T0),
+                _lib.ptr(markers[k]), _lib.ptr(pelvis[k]), _lib.ptr(rotmat[k]), _lib.ptr(transl[k]), _lib.ptr(seed),
+                C.c_void_p(nxt[0].data_ptr()), C.c_void_p(nxt[1].data_ptr()), NM3, _lib.ptr(nonfinite), st), "egx_primitive_advance")
+
+    # ------------------------------------------------------------------------------------------------------------------
+    def _compose_body_params_(self, data):
+        transl, glorot = data["transl"], data["glorot"]
+        body_pose = data["poses"][:, :63]
+        hand_pose = np.zeros((transl.shape[0], 24))
+        return np.concatenate([transl, glorot, body_pose, hand_pose], axis=-1)      # [t,d]
+
+    def generate_primitive_to_files(self, batch_gen, n_seqs, n_gens, t_his=None):
+        """:1363-1424.  n_seqs: how many sequences to generate; n_gens: for each input sequence, how many different sequences
+        to predict.  `batch_gen`: anything with `next_sequence()` and `amass_subset_name`; sequences of another gender than the
+        regressor's are skipped.  Writes <result_dir>/mp_gen_seed<seed>/<subset>/results_<body_repr>_<gender>.pkl and returns
+        its path."""
+        keys = ("gt", "betas", "gender", "transf_rotmat", "transf_transl", "markers", "smplx_params", "transl")
+        gen_results: dict = {k: [] for k in keys}
+        gender = _section(self.regressorcfg, "modelconfig")["gender"]
+        idx = 0
+        while idx < n_seqs:
+            print("[INFO] generating with motion seed {}".format(idx))
+            data = batch_gen.next_sequence()
+            if str(data["gender"]) != gender:
+                continue
+            motion_np = np.asarray(data["body_feature"])
+            motion = torch.as_tensor(motion_np, dtype=torch.float32).unsqueeze(1)                  # [t,b,d]
+            bparams = torch.as_tensor(self._compose_body_params_(data), dtype=torch.float32).unsqueeze(1)
+            gen_results["gt"].append(motion_np[:, :NM3].reshape((1, motion_np.shape[0], -1, 3)))
+            gen_results["betas"].append(data["betas"])
+            gen_results["gender"].append(str(data["gender"]))
+            gen_results["transf_rotmat"].append(data["transf_rotmat"])
+            gen_results["transf_transl"].append(data["transf_transl"])
+            gen_results["transl"].append(data["transl"][None, ...])                              # [b,t,d]
+            pred_markers, pred_body_params = self.generate(motion, bparams, betas=np.asarray(data["betas"]), n_gens=n_gens, t_his=t_his)
+            gen_results["markers"].append(np.reshape(pred_markers, (pred_markers.shape[0], pred_markers.shape[1], -1, 3)))
+            gen_results["smplx_params"].append(pred_body_params)
+            idx += 1
+        for k in ("gt", "markers", "smplx_params", "transl"):
+            gen_results[k] = np.stack(gen_results[k])        # markers: [#seq, #genseq_per_pastmotion, t, #markers, 3]
+        outdir = os.path.join(self.testconfig["result_dir"], "mp_gen_seed{}".format(self.testconfig["seed"]),
+                              batch_gen.amass_subset_name[0])
+        os.makedirs(outdir, exist_ok=True)
+        outfilename = os.path.join(outdir, "results_{}_{}.pkl".format(_section(self.predictorcfg, "modelconfig")["body_repr"], gender))
+        print(outfilename)
+        with open(outfilename, "wb") as f:
+            pickle.dump(gen_results, f)
+        return outfilename

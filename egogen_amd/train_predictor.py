@@ -277,3 +277,18 @@ class BatchGeneratorAMASSCanonicalized:
 
     def get_all_data(self):
         return self.data_all.permute(1, 0, 2)
+
+    def next_sequence(self):
+        """batch_gen_amass.py:287-343 for body_repr 'ssm2_67': the next record of `rec_list` with its meta data (what
+        GAMMAPrimitiveComboGenOP.generate_primitive_to_files reads); None for a record with non-finite poses."""
+        rec = self.rec_list[self.index_rec]
+        sr = self.sample_rate
+        with np.load(rec) as d:
+            pose, transl = d["poses"][::sr, :66], d["trans"][::sr]
+            if not (np.isfinite(pose).all() and np.isfinite(transl).all()):
+                return None
+            out = {"betas": d["betas"][:10], "gender": d["gender"], "transl": transl, "glorot": pose[:, :3], "poses": pose[:, 3:],
+                   "body_feature": d["marker_ssm2_67"][::sr].reshape([-1, 67 * 3]), "transf_rotmat": d["transf_rotmat"],
+                   "transf_transl": d["transf_transl"], "pelvis_loc": d["joints"][::sr].reshape([-1, 22, 3])[:, 0, :]}
+        self.index_rec += 1
+        return out

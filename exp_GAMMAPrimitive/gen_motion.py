@@ -1,0 +1,88 @@
+#!/usr/bin/env python3
+"""Turn a motion seed into N seconds of motion in K variants with a trained motion prior, without an environment:
+`GAMMAPrimitiveComboGenOP.generate_sequence` (egogen_amd/genop.py) chained over `--n-primitives` primitives (0.45 s each at
+40 fps) for `--n-gens` variants of one seed, one `motion_<seed>_<variant>.pkl` per variant in the layout
+`utils.rollout_primitives` and the EgoBody consumers read.
+
+`--cfg <name>` is the combo config (`crowd_ppo/cfg_samp20/<name>.yml` under the working directory, else the packaged copy): it
+names the predictor's and the regressor's configs, whose checkpoints are read from `results/crowd_ppo/<config>/checkpoints`
+(predictor `epoch-400.ckp` else `epoch-200.ckp`, regressor `epoch-100.ckp`), or, with `--ckpt-dir`, the combo checkpoint
+`epoch-120.ckp` else `epoch-10.ckp` that train_GAMMACombo.py writes.  Licensed assets (SMPL-X npz, checkpoints) are used when
+present; otherwise the seeded synthetic body and a seeded random-init prior stand in, as in the other drivers."""
+import argparse
+import os
+import pickle
+import sys
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from egogen_amd import setup_world as sw  # noqa: E402
+from egogen_amd import synth  # noqa: E402
+from egogen_amd.body_model import BodyModelHandle, SMPLXParser  # noqa: E402
+from egogen_amd.canonicalize import canonicalize_frames  # noqa: E402
+from egogen_amd.genop import GAMMAPrimitiveComboGenOP  # noqa: E402
+from egogen_amd.models import PREDICTOR_CFG, REGRESSOR_CFG  # noqa: E402
+from egogen_amd.utils import rollout_primitives  # noqa: E402
+
+
+def main(argv=None):
+    parser = argparse.ArgumentParser()
+    parser.add_argument("--cfg", default="MPVAECombo_samp_2frame")
+    parser.add_argument("--n-primitives", type=int, default=10)
+    parser.add_argument("--n-gens", type=int, default=4)
+    parser.add_argument("--seed", type=int, default=0)
+    parser.add_argument("--out", default=os.path.join("results", "exp_GAMMAPrimitive", "gen_motion"))
+    parser.add_argument("--ckpt-dir", default=None, help="directory of a combo checkpoint (train_GAMMACombo.py)")
+    parser.add_argument("--num-verts", type=int, default=synth.NUM_VERTS)
+    parser.add_argument("--start-frame", type=int, default=5)
+    args = parser.parse_args(argv)
+    if not torch.cuda.is_available():
+        raise SystemExit("gen_motion needs a HIP device: the MI355X path has no CPU fallback")
+    np.random.seed(args.seed)
+    torch.manual_seed(args.seed)
+
+    mc = sw._read_yaml(args.cfg + ".yml")["modelconfig"]
+    pdir = os.path.join(sw.RESULTS_ROOT, mc["predictor_config"], "checkpoints")
+    rdir = os.path.join(sw.RESULTS_ROOT, mc["regressor_config"], "checkpoints")
+    gender = "male"
+    op = GAMMAPrimitiveComboGenOP({"modelconfig": dict(PREDICTOR_CFG), "trainconfig": {"save_dir": pdir}},
+                                  {"modelconfig": dict(REGRESSOR_CFG, gender=gender), "trainconfig": {"save_dir": rdir}},
+                                  {"gpu_index": 0, "ckpt_dir": args.ckpt_dir, "result_dir": args.out, "seed": args.seed})
+    bm, real_body = sw.load_body_model(gender, seed=args.seed, num_verts=args.num_verts)
+    body = BodyModelHandle(bm, synth.marker_ids(args.num_verts), synth.feet_vids(args.num_verts))
+    have_pretrained = any(os.path.exists(os.path.join(pdir, f)) for f in ("epoch-400.ckp", "epoch-200.ckp")) and \
+        os.path.exists(os.path.join(rdir, "epoch-100.ckp"))
+    if args.ckpt_dir:
+        op.build_model(load_pretrained_model=False, body_model=body)
+    elif have_pretrained:
+        op.build_model(load_pretrained_model=True, body_model=body)
+    else:
+        print("[INFO] no checkpoints under {} / {}: seeded random-init prior".format(pdir, rdir))
+        op.model, op.body_model = sw.build_motion_prior(seed=args.seed, ckpt_dirs=(pdir, rdir)), body
+    print("[INFO] body model: {}".format("SMPL-X" if real_body else "synthetic"))
+
+    # motion seed: two frames of the packaged mocap clip, moved into the frame of the first (utils_canonicalize_samp.py)
+    ms = synth.load_assets()
+    s = args.start_frame
+    smplx = SMPLXParser({"body_models": {gender: body}})
+    can = canonicalize_frames(smplx, np.asarray(ms["seed_trans"])[s:s + 2], np.asarray(ms["seed_poses"])[s:s + 2], np.asarray(ms["seed_betas"]),
+                              gender)
+    data = can["marker_ssm2_67"].reshape(2, 1, 201).astype(np.float32)
+    bparams = np.zeros((2, 1, 93), np.float32)
+    bparams[:, 0, :3], bparams[:, 0, 3:69] = can["trans"], can["poses"][:, :66]
+    res = op.generate_sequence(data, bparams, can["betas"].astype(np.float32), args.n_primitives, n_gens=args.n_gens,
+                               R0=can["transf_rotmat"].astype(np.float32)[None].repeat(args.n_gens, 0),
+                               T0=can["transf_transl"].astype(np.float32).reshape(1, 3).repeat(args.n_gens, 0))
+    paths = [res.save(args.out, i, man_id="{}_{}".format(args.seed, i)) for i in range(args.n_gens)]
+    for p in paths:
+        print(p)
+    with open(paths[0], "rb") as fh:
+        seq = rollout_primitives(pickle.load(fh)["motion"], body)
+    print("frames: {}".format(seq.shape[0]))
+
+
+if __name__ == "__main__":
+    main()

@@ -782,6 +782,27 @@ int egx_env_get_feature(const float* Y_l, const float* pel, const float* R0, con
 int egx_env_get_map(const float* tris, int num_tris, float floor_height, const float* map_lin, int res, const float* R, const float* T,
                     int num_bodies, float* out_points_scene, float* out_local_map, void* stream);
 
+/* egx_primitive_advance - the motion-only tail of CrowdEnv.step (crowd_ppo/crowd_env_2f.py:144-155, 238-265 without
+ * _get_feature): the hand-off between two primitives of a chain, one workgroup per sequence, one launch, no host round trip.
+ *   pred_params [B,20,93] (egx_assemble_params), Y_gen [18,B,201] (egx_sample_prior), x0 / x1: the two seed frames [B,201] with row
+ *   stride x_ld floats (as egx_sample_prior takes them), joints [B*20,joints_per_body,3] with joints_per_body >= 3 (127 from
+ *   egx_lbs_forward, 55 from egx_lbs_joints), markers_proj [B*20,67,3], delta_T [B,3] (calc_calibrate_offset: joint 0 at zero
+ *   orientation / translation), R0 [B,3,3] / T0 [B,3]: the frame the primitive was generated in, UPDATED IN PLACE.
+ *   out_marker_b [B,20,67,3] = reproj_factor * markers_proj + (1 - reproj_factor) * cat(x, Y_gen)
+ *   out_pelvis [B,20,3] = joint 0;  out_R [B,3,3], out_T [B,3] = R0 / T0 before the update
+ *   (R_, T_) = canonical frame of body (b, 18) from its joints 0, 1, 2 (the arithmetic of egx_canonical_frame)
+ *   T0 <- R0 T_ + T0, then R0 <- R0 R_ (:247-248)
+ *   out_seed_params [B,2,93] = frames 18, 19 of pred_params re-expressed in (R_, T_) (the arithmetic of egx_update_transl_glorot)
+ *   out_x0 / out_x1: the next seed frames [B,201], row stride out_x_ld floats = R_^T (marker_b[:, 18:20] - T_)
+ *   nonfinite [1] (may be NULL): += number of sequences with a non-finite output (the reference stops in pdb instead)
+ * markers_proj and out_marker_b must be 16-byte aligned (whole records of a [K,B,20,67,3] buffer are).  No output may alias an
+ * input except R0 / T0.  Row b of every output depends on row b of the inputs only. */
+int egx_primitive_advance(const float* pred_params, const float* Y_gen, const float* x0, const float* x1, int x_ld,
+                          const float* joints, int joints_per_body, const float* markers_proj, const float* delta_T,
+                          float reproj_factor, int num_sequences, float* R0, float* T0, float* out_marker_b, float* out_pelvis,
+                          float* out_R, float* out_T, float* out_seed_params, float* out_x0, float* out_x1, int out_x_ld,
+                          int32_t* nonfinite, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * PPO rollout glue
  * ------------------------------------------------------------------------------------------- */
