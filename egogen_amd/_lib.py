@@ -198,6 +198,10 @@ SIGNATURES = {
                                   C.c_void_p, C.c_void_p]),
     "egx_primitive_advance": (C.c_int, [C.c_void_p] * 4 + [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_float, C.c_int] +
                               [C.c_void_p] * 9 + [C.c_int, C.c_void_p, C.c_void_p]),
+    "egx_primitive_select": (C.c_int, [C.c_void_p] * 3 + [C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 6 +
+                             [C.POINTER(C.c_float), C.c_float, C.c_float, C.c_float, C.c_int, C.c_int] + [C.c_void_p] * 8),
+    "egx_primitive_advance_select": (C.c_int, [C.c_void_p] * 4 + [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_float,
+                                               C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 10 + [C.c_int, C.c_void_p, C.c_void_p]),
     "egx_sample_action": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_int, C.c_int, C.c_void_p,
                                     C.c_void_p, C.c_void_p]),
     "egx_gae": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double, C.c_void_p,

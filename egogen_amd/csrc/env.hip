@@ -8,6 +8,7 @@
 // ~15 host syncs and 64 shapely ray casts per agent-step here; this file does it in one launch with no sync.
 #include "egx_common.h"
 #include "egx_frame.h"
+#include "egx_reward.h"
 
 namespace {
 
@@ -206,11 +207,7 @@ __device__ __forceinline__ void marker_target_feature(const float* target_l, con
   const float dn = fmaxf(sqrtf(fx * fx + fy * fy + fz * fz), 1e-12f);
   out3[0] = fx / dn; out3[1] = fy / dn; out3[2] = fz / dn;
 }
-// ... and the clipped 3-D distance pelvis -> target
-__device__ __forceinline__ float target_distance(const float* target_l, const float* pelvis) {
-  const float fx = target_l[0] - pelvis[0], fy = target_l[1] - pelvis[1], fz = target_l[2] - pelvis[2];
-  return fmaxf(sqrtf(fx * fx + fy * fy + fz * fz), 1e-12f);
-}
+// ... and the clipped 3-D distance pelvis -> target: target_distance (egx_reward.h)
 
 struct EnvCfg {
   float reproj_factor, goal_thresh, pene_thres;
@@ -311,30 +308,12 @@ __global__ __launch_bounds__(BLK) void egx_env_step_post_kernel(StepArgs p) {
   __syncthreads();
 
   // ---- 2. skate + floor over the 6 feet markers ----------------------------------------------------------
+  const auto mb_at = [&](int t, int i) { return s_mb[t][i]; };
   float part = 0.f;
-  if (tid < 18) {  // central difference frames 1..18
-    float mn = 3.4e38f;
-    for (int k = 0; k < 6; ++k) {
-      const int m = p.feet_marker_idx[k];
-      const float dx = s_mb[tid + 2][m * 3 + 0] - s_mb[tid][m * 3 + 0];
-      const float dy = s_mb[tid + 2][m * 3 + 1] - s_mb[tid][m * 3 + 1];
-      const float dz = s_mb[tid + 2][m * 3 + 2] - s_mb[tid][m * 3 + 2];
-      const float sp = sqrtf(dx * dx + dy * dy + dz * dz) / 2.f / (1.f / 40.f);
-      mn = fminf(mn, sp);
-    }
-    part = fmaxf(mn - 0.075f, 0.f);
-  }
+  if (tid < 18) part = reward_skate_frame(mb_at, tid, p.feet_marker_idx);  // central difference frames 1..18
   const float r_skate = expf(-(block_reduce(part, s_red, 0) / 18.f));
   part = 0.f;
-  if (tid < NT) {
-    float mn = 3.4e38f;
-    for (int k = 0; k < 6; ++k) {
-      const int m = p.feet_marker_idx[k];
-      const float z = (R0o[6] * s_mb[tid][m * 3 + 0] + R0o[7] * s_mb[tid][m * 3 + 1] + R0o[8] * s_mb[tid][m * 3 + 2]) + T0o[2];
-      mn = fminf(mn, z);
-    }
-    part = fabsf(mn - 0.02f);
-  }
+  if (tid < NT) part = reward_floor_frame(R0o, T0o, mb_at, tid, p.feet_marker_idx);
   const float r_floor = expf(-(block_reduce(part, s_red, 0) / (float)NT));
 
   // ---- 3. vposer norm ------------------------------------------------------------------------------------
@@ -359,7 +338,7 @@ __global__ __launch_bounds__(BLK) void egx_env_step_post_kernel(StepArgs p) {
     }
     const float total = block_reduce(cs, s_red, 0);
     const float mx = block_reduce(cm, s_red, 2);
-    r_pene = expf(-(total / (float)NT / 10.f));
+    r_pene = expf(-reward_pene_arg(total));
     penetration = !(mx < 40.f);
   }
 
@@ -368,22 +347,12 @@ __global__ __launch_bounds__(BLK) void egx_env_step_post_kernel(StepArgs p) {
     const float* j19 = J + (size_t)19 * NJO * 3;
     const float* j18 = J + (size_t)18 * NJO * 3;
     // facing
-    float xa0 = j19[2 * 3 + 0] - j19[1 * 3 + 0], xa1 = j19[2 * 3 + 1] - j19[1 * 3 + 1];
-    float nrm = fmaxf(sqrtf(xa0 * xa0 + xa1 * xa1), 1e-12f);
-    xa0 /= nrm; xa1 /= nrm;
-    const float bo0 = -xa1, bo1 = xa0;  // (0,0,1) x x_axis, xy part
-    float tl[3];
-    {
-      const float v[3] = {wp[0] - T0o[0], wp[1] - T0o[1], wp[2] - T0o[2]};
-      mat3T_vec(R0o, v, tl);
-    }
-    float f0 = tl[0] - j19[0], f1 = tl[1] - j19[1];
-    nrm = fmaxf(sqrtf(f0 * f0 + f1 * f1), 1e-12f);
-    f0 /= nrm; f1 /= nrm;
-    const float r_face = ((f0 * bo0 + f1 * bo1) + 1.f) / 2.0f;
+    float tl[3], dir[2];
+    const float r_face = reward_face(j19, R0o, T0o, wp, tl, dir);
+    const float f0 = dir[0], f1 = dir[1];
     // looking: eye x-axis = reye(24) - leye(23)
     float e0 = j19[24 * 3 + 0] - j19[23 * 3 + 0], e1 = j19[24 * 3 + 1] - j19[23 * 3 + 1];
-    nrm = fmaxf(sqrtf(e0 * e0 + e1 * e1), 1e-12f);
+    const float nrm = fmaxf(sqrtf(e0 * e0 + e1 * e1), 1e-12f);
     e0 /= nrm; e1 /= nrm;
     const float r_look = ((f0 * (-e1) + f1 * e0) + 1.f) / 2.0f;
     // target distance

@@ -1,15 +1,22 @@
-// Hand-off between two motion primitives of a chain (one workgroup per sequence, one launch, no sync).
+// Hand-off between two motion primitives of a chain (one workgroup per sequence, one launch, no sync), and the best-of-N search on
+// top of it: scoring and selection of N candidates per sequence (egx_primitive_select) and the hand-off from the chosen one
+// (egx_primitive_advance_select).
 //
 // Reference: the motion-only tail of CrowdEnv.step, motion/crowd_ppo/crowd_env_2f.py:144-155 (pelvis, blended markers) and
 // :238-265 (new canonical frame from the second-last body, accumulated world frame, seed parameters and seed markers in the new
-// frame) without _get_feature; the frame algebra is the code the env kernels use (egx_frame.h).
+// frame) without _get_feature; the frame algebra is the code the env kernels use (egx_frame.h), the cost terms are the arguments
+// of the env's reward terms (:171-235, egx_reward.h).
 #include "egx_common.h"
 #include "egx_frame.h"
+#include "egx_reward.h"
 
 namespace {
 
 constexpr int NT = 20, THIS = 2, NM = 67, MD = NM * 3, XB = EGX_XB_DIM;
 constexpr int BLK = 256;
+constexpr int SEL_BLK = 512, SEL_WAVES = SEL_BLK / 64;   // scoring: 8 waves per sequence, one candidate row per wave at a time
+constexpr int NF = 6;                                     // feet markers
+constexpr int MAXC = EGX_MAX_CANDIDATES;
 constexpr int NV4 = NT * MD / 4;   // float4 packets of one sequence's markers
 static_assert(NT * MD % 4 == 0, "a sequence's markers are whole float4 packets");
 
@@ -30,22 +37,35 @@ struct AdvanceArgs {
   float* out_seed;            // [B,2,93]
   float* out_x0;              // next seed frames, row stride out_x_ld
   float* out_x1;
+  float* out_params;          // [b,20,93] record of the handed-on row, or null
   int* nonfinite;             // [1] or null
   float rf;
-  int B, jpb, x_ld, out_x_ld;
+  int B /* rows of the per-row inputs */, jpb, x_ld, out_x_ld;
 };
 
 __device__ __forceinline__ bool nonfin(float v) { return !isfinite(v); }
 
+// cat(x, Y_gen)[t] of row `row`, coordinate d
+__device__ __forceinline__ float predicted_marker(const AdvanceArgs& p, int row, int t, int d) {
+  return (t == 0)   ? p.x0[(size_t)row * p.x_ld + d]
+         : (t == 1) ? p.x1[(size_t)row * p.x_ld + d]
+                    : p.Y_gen[((size_t)(t - THIS) * p.B + row) * MD + d];
+}
+// the blended marker (:151-152); one expression for the hand-off and the scoring, so both see the same values
+__device__ __forceinline__ float blend_marker(float rf, float proj, float pred) { return rf * proj + (1.f - rf) * pred; }
+
 }  // namespace
 
-__global__ __launch_bounds__(BLK) void egx_primitive_advance_kernel(AdvanceArgs p) {
+// The hand-off of one sequence by one workgroup: reads row `src` of the per-row inputs, writes the record outputs to row `rec`
+// and the next state (R0, T0, seed parameters, seed frames) to the `ndst` rows from `dst0`.  Every read of R0 / T0 precedes the
+// barrier, every write of them follows it.
+__device__ __forceinline__ void advance_body(const AdvanceArgs& p, int src, int rec, int dst0, int ndst) {
   __shared__ float s_mb[THIS][MD];   // blended markers of frames 18, 19 (old frame)
-  __shared__ float s_frame[12];      // R_[9], T_[3]
+  __shared__ float s_frame[24];      // R_[9], T_[3], new R0[9], new T0[3]
   __shared__ float s_seed6[THIS][6];
-  const int b = blockIdx.x, tid = threadIdx.x;
-  const float* J = p.joints + (size_t)b * NT * p.jpb * 3;
-  const float* PP = p.pred_params + (size_t)b * NT * XB;
+  const int tid = threadIdx.x;
+  const float* J = p.joints + (size_t)src * NT * p.jpb * 3;
+  const float* PP = p.pred_params + (size_t)src * NT * XB;
   bool bad = false;
 
   // ---- frame algebra in the last two lanes of the block (one per seed frame); the other waves start on the markers ----
@@ -54,26 +74,26 @@ __global__ __launch_bounds__(BLK) void egx_primitive_advance_kernel(AdvanceArgs 
     const float* j18 = J + (size_t)18 * p.jpb * 3;
     float Rn[9], Tn[3], o6[6];
     canonical_frame(j18 + 0, j18 + 3, j18 + 6, Rn, Tn);
-    const float delta[3] = {p.delta_T[(size_t)b * 3 + 0], p.delta_T[(size_t)b * 3 + 1], p.delta_T[(size_t)b * 3 + 2]};
+    const float delta[3] = {p.delta_T[(size_t)src * 3 + 0], p.delta_T[(size_t)src * 3 + 1], p.delta_T[(size_t)src * 3 + 2]};
     update_transl_glorot(Rn, Tn, delta, PP + (18 + f) * XB, o6);
     for (int e = 0; e < 6; ++e) { s_seed6[f][e] = o6[e]; bad |= nonfin(o6[e]); }
     if (f == 0) {
       float R0o[9], T0o[3], T0n[3], R0n[9];
-      for (int e = 0; e < 9; ++e) R0o[e] = p.R0[(size_t)b * 9 + e];
-      for (int e = 0; e < 3; ++e) T0o[e] = p.T0[(size_t)b * 3 + e];
+      for (int e = 0; e < 9; ++e) R0o[e] = p.R0[(size_t)src * 9 + e];
+      for (int e = 0; e < 3; ++e) T0o[e] = p.T0[(size_t)src * 3 + e];
       mat3_vec(R0o, Tn, T0n);
       T0n[0] += T0o[0]; T0n[1] += T0o[1]; T0n[2] += T0o[2];
       mat3_mul(R0o, Rn, R0n);
       for (int e = 0; e < 9; ++e) {
         s_frame[e] = Rn[e];
-        p.out_R[(size_t)b * 9 + e] = R0o[e];
-        p.R0[(size_t)b * 9 + e] = R0n[e];
+        s_frame[12 + e] = R0n[e];
+        p.out_R[(size_t)rec * 9 + e] = R0o[e];
         bad |= nonfin(R0n[e]);
       }
       for (int e = 0; e < 3; ++e) {
         s_frame[9 + e] = Tn[e];
-        p.out_T[(size_t)b * 3 + e] = T0o[e];
-        p.T0[(size_t)b * 3 + e] = T0n[e];
+        s_frame[21 + e] = T0n[e];
+        p.out_T[(size_t)rec * 3 + e] = T0o[e];
         bad |= nonfin(T0n[e]);
       }
     }
@@ -82,23 +102,22 @@ __global__ __launch_bounds__(BLK) void egx_primitive_advance_kernel(AdvanceArgs 
   // ---- pelvis of the 20 bodies ----------------------------------------------------------------------------------------
   if (tid < NT * 3) {
     const float v = J[(size_t)(tid / 3) * p.jpb * 3 + tid % 3];
-    p.out_pelvis[(size_t)b * NT * 3 + tid] = v;
+    p.out_pelvis[(size_t)rec * NT * 3 + tid] = v;
     bad |= nonfin(v);
   }
+  if (p.out_params)
+    for (int i = tid; i < NT * XB; i += BLK) p.out_params[(size_t)rec * NT * XB + i] = PP[i];
 
   // ---- blended markers: projected and output as float4 across the block, predicted gathered per element ------------------
   const float rf = p.rf;
-  const f32x4* proj4 = reinterpret_cast<const f32x4*>(p.markers_proj + (size_t)b * NT * MD);
-  f32x4* out4 = reinterpret_cast<f32x4*>(p.out_marker_b + (size_t)b * NT * MD);
+  const f32x4* proj4 = reinterpret_cast<const f32x4*>(p.markers_proj + (size_t)src * NT * MD);
+  f32x4* out4 = reinterpret_cast<f32x4*>(p.out_marker_b + (size_t)rec * NT * MD);
   for (int i = tid; i < NV4; i += BLK) {
     const f32x4 pr = proj4[i];
     f32x4 o;
     for (int k = 0; k < 4; ++k) {
       const int e = i * 4 + k, t = e / MD, d = e % MD;
-      const float pred = (t == 0)   ? p.x0[(size_t)b * p.x_ld + d]
-                         : (t == 1) ? p.x1[(size_t)b * p.x_ld + d]
-                                    : p.Y_gen[((size_t)(t - THIS) * p.B + b) * MD + d];
-      const float v = rf * pr[k] + (1.f - rf) * pred;
+      const float v = blend_marker(rf, pr[k], predicted_marker(p, src, t, d));
       o[k] = v;
       if (t >= NT - THIS) s_mb[t - (NT - THIS)][d] = v;
       bad |= nonfin(v);
@@ -107,6 +126,12 @@ __global__ __launch_bounds__(BLK) void egx_primitive_advance_kernel(AdvanceArgs 
   }
   __syncthreads();
 
+  // ---- accumulated world frame of the next primitive, to every row of the group ---------------------------------------------
+  for (int i = tid; i < ndst * 12; i += BLK) {
+    const int n = i / 12, e = i % 12;
+    if (e < 9) p.R0[(size_t)(dst0 + n) * 9 + e] = s_frame[12 + e];
+    else p.T0[(size_t)(dst0 + n) * 3 + (e - 9)] = s_frame[12 + e];
+  }
   // ---- next seed: markers of frames 18, 19 in (R_, T_), parameters with the new transl / glorot ---------------------------
   float Rn[9], Tn[3];
   for (int e = 0; e < 9; ++e) Rn[e] = s_frame[e];
@@ -116,18 +141,159 @@ __global__ __launch_bounds__(BLK) void egx_primitive_advance_kernel(AdvanceArgs 
     const float v[3] = {s_mb[t][m * 3 + 0] - Tn[0], s_mb[t][m * 3 + 1] - Tn[1], s_mb[t][m * 3 + 2] - Tn[2]};
     float ms[3];
     mat3T_vec(Rn, v, ms);
-    float* st = (t == 0 ? p.out_x0 : p.out_x1) + (size_t)b * p.out_x_ld + m * 3;
-    st[0] = ms[0]; st[1] = ms[1]; st[2] = ms[2];
+    for (int n = 0; n < ndst; ++n) {
+      float* st = (t == 0 ? p.out_x0 : p.out_x1) + (size_t)(dst0 + n) * p.out_x_ld + m * 3;
+      st[0] = ms[0]; st[1] = ms[1]; st[2] = ms[2];
+    }
     bad |= nonfin(ms[0]) || nonfin(ms[1]) || nonfin(ms[2]);
   }
   for (int i = tid; i < THIS * XB; i += BLK) {
     const int t = i / XB, d = i % XB;
     const float v = (d < 6) ? s_seed6[t][d] : PP[(18 + t) * XB + d];
-    p.out_seed[((size_t)b * THIS + t) * XB + d] = v;
+    for (int n = 0; n < ndst; ++n) p.out_seed[((size_t)(dst0 + n) * THIS + t) * XB + d] = v;
     bad |= nonfin(v);
   }
   const int any_bad = __syncthreads_or(bad ? 1 : 0);
   if (tid == 0 && any_bad && p.nonfinite) atomicAdd(p.nonfinite, 1);
+}
+
+__global__ __launch_bounds__(BLK) void egx_primitive_advance_kernel(AdvanceArgs p) {
+  const int b = blockIdx.x;
+  advance_body(p, b, b, b, 1);
+}
+
+// workgroup i hands sequence i on from candidate choice[i] of its num_candidates rows (a choice outside the group is clamped)
+__global__ __launch_bounds__(BLK) void egx_primitive_advance_select_kernel(AdvanceArgs p, const int* __restrict__ choice, int N) {
+  const int g = blockIdx.x;
+  const int c = min(max(choice[g], 0), N - 1);
+  advance_body(p, g * N + c, g, g * N, N);
+}
+
+// ---- scoring and selection -----------------------------------------------------------------------------------------------
+// One workgroup of 8 waves per sequence.  A wave scores one candidate row at a time: its 64 lanes gather and blend the six feet
+// markers of the 20 frames (360 values, the only markers the terms read) into the wave's slice of LDS, lanes 0..19 evaluate one
+// frame each, the sums are wave shuffles in a fixed order, lane 0 adds the two scalar terms of the last body.  After the rows,
+// wave 0 reduces (class, cost, index) over the N rows with a total order, so the result does not depend on the reduction tree.
+namespace {
+
+struct SelectArgs {
+  const float* Y_gen;         // [18,B*N,201]
+  const float* x0;
+  const float* x1;
+  const float* joints;        // [B*N*20,jpb,3]
+  const float* markers_proj;  // [B*N*20,67,3]
+  const float* R0;            // [B*N,9]
+  const float* T0;            // [B*N,3]
+  const int* pene_count;      // [B*N*20] or null
+  const float* goal;          // [B,3]
+  const int* feet_marker_idx; // [6]
+  float w_goal, w_skate, w_floor, w_pene, w_face, pene_thres, goal_thresh, rf;
+  int rows, N, jpb, x_ld;
+  int* choice;                // [B]
+  int* status;                // [B]
+  int* reached;               // [B]
+  float* goal_dist;           // [B]
+  float* cost;                // [B*N]
+  float* terms;               // [B*N,5] dist, skate, floor, pene, face
+  int* colliding;             // [B*N]
+};
+
+__device__ __forceinline__ float wave_sum(float v) {   // lane 0 holds the sum; fixed tree
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+  return v;
+}
+__device__ __forceinline__ int wave_max(int v) {
+  for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_down(v, o, 64));
+  return v;
+}
+// the order of the choice: class (0 clean, 1 colliding, 2 / 3 the same with a non-finite value), then cost, then index
+__device__ __forceinline__ bool candidate_before(int ca, float xa, int ia, int cb, float xb, int ib) {
+  if (ca != cb) return ca < cb;
+  if (xa != xb) return xa < xb;
+  return ia < ib;
+}
+
+}  // namespace
+
+__global__ __launch_bounds__(SEL_BLK) void egx_primitive_select_kernel(SelectArgs p) {
+  __shared__ float s_feet[SEL_WAVES][NT][NF * 3];   // blended feet markers of the row a wave is scoring
+  __shared__ float s_cost[MAXC], s_dist[MAXC];
+  __shared__ int s_cls[MAXC];
+  const int g = blockIdx.x, tid = threadIdx.x, w = tid >> 6, lane = tid & 63, N = p.N;
+  const int feet_local[NF] = {0, 1, 2, 3, 4, 5};
+  const float goal[3] = {p.goal[(size_t)g * 3 + 0], p.goal[(size_t)g * 3 + 1], p.goal[(size_t)g * 3 + 2]};
+
+  for (int n0 = 0; n0 < N; n0 += SEL_WAVES) {      // the same trip count in every wave: the barriers are uniform
+    const int n = n0 + w;
+    const bool active = n < N;
+    const size_t row = (size_t)g * N + (active ? n : 0);
+    if (active)
+      for (int e = lane; e < NT * NF * 3; e += 64) {
+        const int t = e / (NF * 3), r = e % (NF * 3);
+        const int m = min(max(p.feet_marker_idx[r / 3], 0), NM - 1), d = m * 3 + r % 3;
+        const float pred = (t == 0)   ? p.x0[row * p.x_ld + d]
+                           : (t == 1) ? p.x1[row * p.x_ld + d]
+                                      : p.Y_gen[((size_t)(t - THIS) * p.rows + row) * MD + d];
+        s_feet[w][t][r] = blend_marker(p.rf, p.markers_proj[(row * NT + t) * MD + d], pred);
+      }
+    __syncthreads();
+    if (active) {
+      float R0[9], T0[3];
+      for (int e = 0; e < 9; ++e) R0[e] = p.R0[row * 9 + e];
+      for (int e = 0; e < 3; ++e) T0[e] = p.T0[row * 3 + e];
+      const auto feet_at = [&](int t, int i) { return s_feet[w][t][i]; };
+      float sk = 0.f, fl = 0.f, cs = 0.f;
+      int cm = 0;
+      if (lane < 18) sk = reward_skate_frame(feet_at, lane, feet_local);   // central difference frames 1..18
+      if (lane < NT) {
+        fl = reward_floor_frame(R0, T0, feet_at, lane, feet_local);
+        if (p.pene_count) {
+          cm = p.pene_count[row * NT + lane];
+          cs = (float)cm;
+        }
+      }
+      const float skate = wave_sum(sk) / 18.f;
+      const float floor_ = wave_sum(fl) / (float)NT;
+      const float pene = reward_pene_arg(wave_sum(cs));
+      const int cmax = wave_max(cm);
+      if (lane == 0) {
+        const float* j19 = p.joints + (row * NT + 19) * p.jpb * 3;
+        float tl[3], dir[2];
+        const float face = 1.f - reward_face(j19, R0, T0, goal, tl, dir);
+        const float dist = target_distance(tl, j19);
+        const float cost = p.w_goal * dist + p.w_skate * skate + p.w_floor * floor_ + p.w_pene * pene + p.w_face * face;
+        const bool collides = p.pene_count && !((float)cmax < p.pene_thres);
+        const bool finite = isfinite(cost) && isfinite(dist) && isfinite(skate) && isfinite(floor_) && isfinite(pene) && isfinite(face);
+        p.cost[row] = cost;
+        float* tm = p.terms + row * 5;
+        tm[0] = dist; tm[1] = skate; tm[2] = floor_; tm[3] = pene; tm[4] = face;
+        p.colliding[row] = collides ? 1 : 0;
+        s_cost[n] = finite ? cost : 0.f;      // a non-finite row is ranked by collision and index only
+        s_dist[n] = dist;
+        s_cls[n] = (finite ? 0 : 2) | (collides ? 1 : 0);
+      }
+    }
+    __syncthreads();
+  }
+
+  if (w == 0) {
+    int bc = 4, bi = 0x7fffffff;
+    float bx = 0.f;
+    for (int n = lane; n < N; n += 64)
+      if (candidate_before(s_cls[n], s_cost[n], n, bc, bx, bi)) { bc = s_cls[n]; bx = s_cost[n]; bi = n; }
+    for (int o = 32; o > 0; o >>= 1) {
+      const int oc = __shfl_xor(bc, o, 64), oi = __shfl_xor(bi, o, 64);
+      const float ox = __shfl_xor(bx, o, 64);
+      if (candidate_before(oc, ox, oi, bc, bx, bi)) { bc = oc; bx = ox; bi = oi; }
+    }
+    if (lane == 0) {
+      const float dist = s_dist[bi];
+      p.choice[g] = bi;
+      p.status[g] = (bc & 1) | (bc & 2);
+      p.reached[g] = (dist < p.goal_thresh) ? 1 : 0;
+      p.goal_dist[g] = dist;
+    }
+  }
 }
 
 extern "C" int egx_primitive_advance(const float* pred_params, const float* Y_gen, const float* x0, const float* x1, int x_ld,
@@ -144,9 +310,58 @@ extern "C" int egx_primitive_advance(const float* pred_params, const float* Y_ge
   AdvanceArgs p;
   p.pred_params = pred_params; p.Y_gen = Y_gen; p.x0 = x0; p.x1 = x1; p.joints = joints; p.markers_proj = markers_proj;
   p.delta_T = delta_T; p.R0 = R0; p.T0 = T0; p.out_marker_b = out_marker_b; p.out_pelvis = out_pelvis; p.out_R = out_R;
-  p.out_T = out_T; p.out_seed = out_seed_params; p.out_x0 = out_x0; p.out_x1 = out_x1; p.nonfinite = nonfinite;
+  p.out_T = out_T; p.out_seed = out_seed_params; p.out_x0 = out_x0; p.out_x1 = out_x1; p.out_params = nullptr; p.nonfinite = nonfinite;
   p.rf = reproj_factor; p.B = num_sequences; p.jpb = joints_per_body; p.x_ld = x_ld; p.out_x_ld = out_x_ld;
   hipLaunchKernelGGL(egx_primitive_advance_kernel, dim3(num_sequences), dim3(BLK), 0, static_cast<hipStream_t>(stream), p);
+  EGX_HIP_CHECK(hipGetLastError());
+  return EGX_OK;
+}
+
+extern "C" int egx_primitive_select(const float* Y_gen, const float* x0, const float* x1, int x_ld, const float* joints,
+                                    int joints_per_body, const float* markers_proj, const float* R0, const float* T0,
+                                    const int32_t* pene_count, const float* goal, const int32_t* feet_marker_idx,
+                                    const float* weights, float pene_thres, float goal_thresh, float reproj_factor,
+                                    int num_sequences, int num_candidates, int32_t* choice, int32_t* status, int32_t* reached,
+                                    float* goal_dist, float* cost, float* cost_terms, int32_t* colliding, void* stream) {
+  EGX_REQUIRE(Y_gen && x0 && x1 && joints && markers_proj && R0 && T0 && goal && feet_marker_idx && weights, "null input");
+  EGX_REQUIRE(choice && status && reached && goal_dist && cost && cost_terms && colliding, "null output");
+  EGX_REQUIRE(num_sequences > 0 && joints_per_body >= 3, "need a non-empty batch and >= 3 joints per body");
+  EGX_REQUIRE(num_candidates >= 1 && num_candidates <= MAXC, "num_candidates must be in [1, EGX_MAX_CANDIDATES]");
+  EGX_REQUIRE(x_ld >= MD, "a seed frame holds 201 floats: the row stride cannot be smaller");
+  SelectArgs p;
+  p.Y_gen = Y_gen; p.x0 = x0; p.x1 = x1; p.joints = joints; p.markers_proj = markers_proj; p.R0 = R0; p.T0 = T0;
+  p.pene_count = pene_count; p.goal = goal; p.feet_marker_idx = feet_marker_idx;
+  p.w_goal = weights[0]; p.w_skate = weights[1]; p.w_floor = weights[2]; p.w_pene = weights[3]; p.w_face = weights[4];
+  p.pene_thres = pene_thres; p.goal_thresh = goal_thresh; p.rf = reproj_factor;
+  p.rows = num_sequences * num_candidates; p.N = num_candidates; p.jpb = joints_per_body; p.x_ld = x_ld;
+  p.choice = choice; p.status = status; p.reached = reached; p.goal_dist = goal_dist; p.cost = cost; p.terms = cost_terms;
+  p.colliding = colliding;
+  hipLaunchKernelGGL(egx_primitive_select_kernel, dim3(num_sequences), dim3(SEL_BLK), 0, static_cast<hipStream_t>(stream), p);
+  EGX_HIP_CHECK(hipGetLastError());
+  return EGX_OK;
+}
+
+extern "C" int egx_primitive_advance_select(const float* pred_params, const float* Y_gen, const float* x0, const float* x1, int x_ld,
+                                            const float* joints, int joints_per_body, const float* markers_proj,
+                                            const float* delta_T, float reproj_factor, int num_sequences, const int32_t* choice,
+                                            int num_candidates, float* R0, float* T0, float* out_marker_b, float* out_pelvis,
+                                            float* out_R, float* out_T, float* out_params, float* out_seed_params, float* out_x0,
+                                            float* out_x1, int out_x_ld, int32_t* nonfinite, void* stream) {
+  EGX_REQUIRE(pred_params && Y_gen && x0 && x1 && joints && markers_proj && delta_T && R0 && T0 && choice, "null input");
+  EGX_REQUIRE(out_marker_b && out_pelvis && out_R && out_T && out_seed_params && out_x0 && out_x1, "null output");
+  EGX_REQUIRE(num_sequences > 0 && joints_per_body >= 3, "need a non-empty batch and >= 3 joints per body");
+  EGX_REQUIRE(num_candidates >= 1 && num_candidates <= MAXC, "num_candidates must be in [1, EGX_MAX_CANDIDATES]");
+  EGX_REQUIRE(x_ld >= MD && out_x_ld >= MD, "a seed frame holds 201 floats: the row strides cannot be smaller");
+  EGX_REQUIRE(((uintptr_t)markers_proj & 15) == 0 && ((uintptr_t)out_marker_b & 15) == 0,
+              "markers_proj and out_marker_b must be 16-byte aligned");
+  AdvanceArgs p;
+  p.pred_params = pred_params; p.Y_gen = Y_gen; p.x0 = x0; p.x1 = x1; p.joints = joints; p.markers_proj = markers_proj;
+  p.delta_T = delta_T; p.R0 = R0; p.T0 = T0; p.out_marker_b = out_marker_b; p.out_pelvis = out_pelvis; p.out_R = out_R;
+  p.out_T = out_T; p.out_seed = out_seed_params; p.out_x0 = out_x0; p.out_x1 = out_x1; p.out_params = out_params;
+  p.nonfinite = nonfinite; p.rf = reproj_factor; p.B = num_sequences * num_candidates; p.jpb = joints_per_body; p.x_ld = x_ld;
+  p.out_x_ld = out_x_ld;
+  hipLaunchKernelGGL(egx_primitive_advance_select_kernel, dim3(num_sequences), dim3(BLK), 0, static_cast<hipStream_t>(stream), p,
+                     choice, num_candidates);
   EGX_HIP_CHECK(hipGetLastError());
   return EGX_OK;
 }

@@ -2,7 +2,10 @@
 crowd_ppo/primitive_model.py:69): the interface to a trained motion prior outside an environment - one primitive from a motion
 seed (`generate`), the file writer of the primitive evaluation (`generate_primitive_to_files`), and, new here, a chain of
 primitives with the re-canonicalisation between them on the device (`generate_sequence`, kernel egx_primitive_advance): the
-motion-only part of `CrowdEnv.step` (crowd_ppo/crowd_env_2f.py:109-155, 238-265) without scene, rewards or egosensing.
+motion-only part of `CrowdEnv.step` (crowd_ppo/crowd_env_2f.py:109-155, 238-265) without scene, rewards or egosensing; and
+`generate_sequence_to_goal`, the greedy best-of-N search over such a chain: per primitive N candidates are scored with the
+arguments of the env's reward terms (:171-235) against a goal and an SDF scene, and every candidate of the next primitive
+continues from the best one (kernels egx_primitive_select, egx_primitive_advance_select).
 
 Differences from the reference, all in `generate` unless noted:
   * `t_his=None` means the model's t_his (the reference computes `20 - None` and fails);
@@ -25,6 +28,8 @@ from . import _lib
 from .models import GAMMAPrimitiveCombo
 
 T_ALL, T_PRED, NM3, XB = 20, 18, 201, 93
+MAX_CANDIDATES = 256        # EGX_MAX_CANDIDATES of include/egogen_hip.h
+SEARCH_WEIGHTS = {"goal": 1.0, "skate": 1.0, "floor": 1.0, "pene": 1.0, "face": 0.0}
 GENERATE_PPO_NOT_BUILT = ("generate_ppo is not built: nothing in the reference calls it, and its policy_model(X, obj_points=, "
                           "target_ori=, local_map=) signature belongs to no class in the tree")
 
@@ -48,23 +53,36 @@ def _load_ckpt(candidates):
 class PrimitiveSequence:
     """What `generate_sequence` returns: K primitives of b sequences.
     markers [K,b,20,67,3] blended markers, params [K,b,20,93], rotmat [K,b,3,3] / transl [K,b,3] the world frame each primitive
-    is expressed in, pelvis [K,b,20,3], z [K,b,128]; betas [b,10]; R0 [b,3,3] / T0 [b,3] the frame after the last primitive."""
+    is expressed in, pelvis [K,b,20,3], z [K,b,128]; betas [b,10]; R0 [b,3,3] / T0 [b,3] the frame after the last primitive.
+    A result of `generate_sequence_to_goal` holds the chosen candidates in those fields and, in `search`, what the selection saw:
+    goal [b,3], choice [K,b], cost [K,b,N], cost_terms [K,b,N,5] (dist, skate, floor, pene, face), colliding [K,b,N],
+    status [K,b] (bit 0: the chosen candidate collides), goal_dist [K,b], n_valid [b] (primitives up to and including the first
+    whose chosen candidate ends within goal_thresh of the goal, K if none does); `primitives` and `save` stop at n_valid."""
+    SEARCH_FIELDS = ("goal", "choice", "cost", "cost_terms", "colliding", "status", "goal_dist", "n_valid")
 
-    def __init__(self, markers, params, rotmat, transl, pelvis, z, betas, gender, R0, T0):
+    def __init__(self, markers, params, rotmat, transl, pelvis, z, betas, gender, R0, T0, search: Optional[dict] = None):
         self.markers, self.params, self.rotmat, self.transl, self.pelvis, self.z = markers, params, rotmat, transl, pelvis, z
         self.betas, self.gender, self.R0, self.T0 = betas, gender, R0, T0
+        self.search = search
+        for k in self.SEARCH_FIELDS:
+            setattr(self, k, None if search is None else search[k])
 
     def primitives(self, i: int) -> list:
         """Sequence i as the list of 8-item records `utils.save_rollout_results` takes (crowd_env_2f.py:155)."""
+        n = self.markers.shape[0] if self.n_valid is None else int(self.n_valid[i])
         return [[self.markers[k, i:i + 1], self.params[k, i:i + 1], self.betas[i:i + 1], self.gender, self.rotmat[k, i],
-                 self.transl[k, i:i + 1], self.pelvis[k, i:i + 1], "2-frame"] for k in range(self.markers.shape[0])]
+                 self.transl[k, i:i + 1], self.pelvis[k, i:i + 1], "2-frame"] for k in range(n)]
 
     def save(self, outfolder: str, i: int, man_id=None) -> str:
-        """`motion_<man_id>.pkl` of sequence i with a two-point wpath: first and last pelvis in the world frame."""
+        """`motion_<man_id>.pkl` of sequence i with a two-point wpath in the world frame: first pelvis, then the goal of a
+        goal-steered result, else the last pelvis."""
         from .utils import save_rollout_results
         as_t = lambda x: torch.as_tensor(x)
         first = as_t(self.rotmat[0, i]) @ as_t(self.pelvis[0, i, 0]) + as_t(self.transl[0, i])
-        last = as_t(self.rotmat[-1, i]) @ as_t(self.pelvis[-1, i, -1]) + as_t(self.transl[-1, i])
+        if self.goal is not None:
+            last = as_t(self.goal[i]).to(first)
+        else:
+            last = as_t(self.rotmat[-1, i]) @ as_t(self.pelvis[-1, i, -1]) + as_t(self.transl[-1, i])
         scene = {"wpath": torch.stack([first, last]), "navmesh_path": None}
         return save_rollout_results(scene, self.primitives(i), outfolder, man_id=man_id)
 
@@ -271,6 +289,155 @@ class GAMMAPrimitiveComboGenOP:
                 _lib.ptr(lbs_out["joints"]), 127, _lib.ptr(lbs_out["markers"]), _lib.ptr(delta_T), rf, B, _lib.ptr(R0), _lib.ptr(T0),
                 _lib.ptr(markers[k]), _lib.ptr(pelvis[k]), _lib.ptr(rotmat[k]), _lib.ptr(transl[k]), _lib.ptr(seed),
                 C.c_void_p(nxt[0].data_ptr()), C.c_void_p(nxt[1].data_ptr()), NM3, _lib.ptr(nonfinite), st), "egx_primitive_advance")
+
+    # ------------------------------------------------------------------------------------------------------------------
+    def generate_sequence_to_goal(self, data, bparams, betas, goal, n_primitives: int, n_candidates: int, scene=None,
+                                  agent_scene=None, weights: Optional[dict] = None, pene_thres: float = 40, goal_thresh=None,
+                                  z=None, reproj_factor=None, to_numpy: bool = True, R0=None, T0=None) -> PrimitiveSequence:
+        """`generate_sequence` steered to a goal through a scene by a greedy best-of-N search: for each of the `n_primitives`
+        primitives, `n_candidates` candidates per sequence are generated, scored and the best one is kept; every candidate of the
+        next primitive continues from it.  data / bparams / betas / reproj_factor / R0 / T0 as in `generate_sequence` (b seeds,
+        one sequence each).
+            - goal: [b,3] or [3], world coordinates
+            - n_candidates: N in [1, 256] (ValueError above)
+            - scene: None (no penetration term, nothing collides), an SdfScene, or an SdfSceneSet with agent_scene [b]
+            - weights: {goal, skate, floor, pene, face} of cost = sum w * term, the terms being the arguments of the env's reward
+              terms (distance to the goal in metres, -ln r_skate, -ln r_floor, -ln r_pene, 1 - r_face_target).  The defaults
+              1, 1, 1, 1, 0 are a stated choice: nobody has measured motion quality with them.
+            - pene_thres: a candidate one of whose 20 bodies has that many vertices inside the scene collides (40: the env's)
+            - goal_thresh: None takes testconfig['goal_thresh'] (the policy configs' trainconfig.goal_thresh) where present, else 0.1
+            - z: None (N(0, I) from the torch generator, drawn up front) or [n_primitives, b * N, 128]; row i * N + n is
+              candidate n of sequence i
+        Choice per sequence: candidates without a non-finite value first, then non-colliding, then the lower cost, then the lower
+        index.  Per primitive: sample_prior_into -> egx_assemble_params -> BodyModelHandle.forward (with penetration counts in a
+        scene) -> egx_primitive_select -> egx_primitive_advance_select; nothing in the loop waits for the device.
+        Raises FloatingPointError when a chosen hand-off, or every candidate of a sequence, held a non-finite value (read once,
+        after the loop)."""
+        from .body_model import SdfScene, SdfSceneSet
+        from . import synth
+        if self.body_model is None:
+            raise _lib.EgxError("generate_sequence_to_goal needs the body model: build_model(..., body_model=BodyModelHandle)")
+        K, N = int(n_primitives), int(n_candidates)
+        if K < 1:
+            raise ValueError("n_primitives must be >= 1")
+        if N < 1 or N > MAX_CANDIDATES:
+            raise ValueError(f"n_candidates must be in [1, {MAX_CANDIDATES}], got {N}")
+        X, seed, bt = self._seed_inputs(data, bparams, betas, -1, None)
+        b, dev, f32, i32 = X.shape[1], self.device, torch.float32, torch.int32
+        BN = b * N
+        goal = self._dev(goal, "goal")
+        if goal.shape == (3,):
+            goal = goal.reshape(1, 3).repeat(b, 1)
+        if goal.shape != (b, 3):
+            raise ValueError(f"goal must be [3] or [{b},3], got {tuple(goal.shape)}")
+        goal = goal.contiguous()
+        rows_scene = None
+        if isinstance(scene, SdfSceneSet):
+            if agent_scene is None:
+                raise ValueError("a scene set needs agent_scene [b]")
+            idx = torch.as_tensor(agent_scene).reshape(-1).to("cpu", torch.int64)
+            if idx.numel() != b or int(idx.min()) < 0 or int(idx.max()) >= len(scene):
+                raise ValueError(f"agent_scene must hold {b} indices in [0, {len(scene)}), got {idx.tolist()}")
+            rows_scene = idx.to(dev, i32).repeat_interleave(N).contiguous()
+        elif agent_scene is not None:
+            raise ValueError("agent_scene needs an SdfSceneSet")
+        elif scene is not None and not isinstance(scene, SdfScene):
+            raise TypeError(f"scene must be None, an SdfScene or an SdfSceneSet, got {type(scene).__name__}")
+        w = dict(SEARCH_WEIGHTS)
+        if weights:
+            unknown = set(weights) - set(w)
+            if unknown:
+                raise ValueError(f"unknown weights {sorted(unknown)}: the terms are {list(w)}")
+            w.update({k: float(v) for k, v in weights.items()})
+        if goal_thresh is None:
+            goal_thresh = self.testconfig.get("goal_thresh", 0.1)
+        zd = self.model.predictor.z_dim
+        if z is None:
+            z = torch.randn(K, BN, zd, device=dev)
+        else:
+            z = self._dev(z, "z").contiguous()
+            if z.shape != (K, BN, zd):
+                raise ValueError(f"z must be [{K},{BN},{zd}], got {tuple(z.shape)}")
+        if reproj_factor is None:
+            reproj_factor = _section(self.predictorcfg, "modelconfig").get("reproj_factor", 0.5)
+        bm = self.body_model
+        if bm.M != 67:
+            raise ValueError(f"the body model carries {bm.M} markers, the motion prior works on 67")
+        eye = torch.eye(3, device=dev, dtype=f32)
+        R0 = eye.repeat(b, 1, 1) if R0 is None else self._dev(R0, "R0").reshape(b, 3, 3)
+        T0 = torch.zeros(b, 3, device=dev, dtype=f32) if T0 is None else self._dev(T0, "T0").reshape(b, 3)
+        rep = lambda t, dim=0: t.repeat_interleave(N, dim=dim).contiguous()
+        bt_rows = rep(bt)
+        s = {"rf": float(reproj_factor), "z": z, "bt": bt_rows, "R0": rep(R0), "T0": rep(T0), "goal": goal,
+             "xs": [rep(X, 1), torch.empty(2, BN, NM3, device=dev, dtype=f32)],            # seed markers, ping-pong
+             "seed": rep(seed.permute(1, 0, 2)),                                             # [BN,2,93]
+             "pp": torch.empty(BN, T_ALL, XB, device=dev, dtype=f32),
+             "Y_gen": torch.empty(T_PRED, BN, NM3, device=dev, dtype=f32), "Yb_gen": torch.empty(T_PRED, BN, XB, device=dev, dtype=f32),
+             "lbs_out": {"joints": torch.empty(BN * T_ALL, 127, 3, device=dev, dtype=f32),
+                         "markers": torch.empty(BN * T_ALL, bm.M, 3, device=dev, dtype=f32)},
+             "scene": scene, "rows_scene": rows_scene,
+             "feet": torch.tensor(synth.feet_marker_idx(), device=dev, dtype=i32),
+             "weights": (C.c_float * 5)(*[w[k] for k in ("goal", "skate", "floor", "pene", "face")]),
+             "pene_thres": float(pene_thres), "goal_thresh": float(goal_thresh),
+             "markers": torch.empty(K, b, T_ALL, 67, 3, device=dev, dtype=f32), "params": torch.empty(K, b, T_ALL, XB, device=dev, dtype=f32),
+             "rotmat": torch.empty(K, b, 3, 3, device=dev, dtype=f32), "transl": torch.empty(K, b, 3, device=dev, dtype=f32),
+             "pelvis": torch.empty(K, b, T_ALL, 3, device=dev, dtype=f32),
+             "choice": torch.empty(K, b, device=dev, dtype=i32), "status": torch.empty(K, b, device=dev, dtype=i32),
+             "reached": torch.empty(K, b, device=dev, dtype=i32), "goal_dist": torch.empty(K, b, device=dev, dtype=f32),
+             "cost": torch.empty(K, b, N, device=dev, dtype=f32), "cost_terms": torch.empty(K, b, N, 5, device=dev, dtype=f32),
+             "colliding": torch.empty(K, b, N, device=dev, dtype=i32),
+             "nonfinite": torch.zeros(1, device=dev, dtype=i32)}
+        if scene is not None:
+            s["lbs_out"]["pene_count"] = torch.empty(BN * T_ALL, device=dev, dtype=i32)
+        # calc_calibrate_offset: joint 0 at zero orientation / translation (the body pose does not move the root)
+        s["delta_T"] = bm.joints55(torch.zeros(BN, XB, device=dev, dtype=f32), bt_rows, 1)[:, 0].contiguous()
+        bm.workspace(BN * T_ALL)
+        self._search_loop(K, b, N, s)
+        n = int(s["nonfinite"].item())
+        status = s["status"]
+        n_all = int((status & 2).ne(0).sum().item())
+        if n or n_all:
+            raise FloatingPointError(f"the search produced non-finite values: {n} chosen hand-offs, {n_all} sequence steps whose "
+                                     f"candidates were all non-finite")
+        reached = s["reached"].ne(0)
+        first = torch.where(reached.any(0), reached.int().argmax(0) + 1, torch.full((b,), K, device=dev, dtype=torch.int64))
+        zc = z.view(K, b, N, zd).gather(2, s["choice"].long().view(K, b, 1, 1).expand(K, b, 1, zd))[:, :, 0]
+        res = [s["markers"], s["params"], s["rotmat"], s["transl"], s["pelvis"], zc, bt, s["R0"][::N].reshape(b, 3, 3).contiguous(), s["T0"][::N].contiguous()]
+        search = {"goal": goal, "choice": s["choice"], "cost": s["cost"], "cost_terms": s["cost_terms"], "colliding": s["colliding"],
+                  "status": status, "goal_dist": s["goal_dist"], "n_valid": first}
+        if to_numpy:
+            res = [t.cpu().numpy() for t in res]
+            search = {k: v.cpu().numpy() for k, v in search.items()}
+        gender = str(_section(self.regressorcfg, "modelconfig").get("gender", "male"))
+        return PrimitiveSequence(*res[:7], gender, res[7], res[8], search=search)
+
+    def _search_loop(self, K, b, N, s):
+        """The primitive loop of `generate_sequence_to_goal`: launches only, no allocation that depends on k, no host wait."""
+        lib, bm = _lib.load(), self.body_model
+        st = _lib.current_stream_ptr()
+        BN = b * N
+        lbs, scene = s["lbs_out"], s["scene"]
+        vp = lambda t: C.c_void_p(t.data_ptr())
+        for k in range(K):
+            cur, nxt = s["xs"][k % 2], s["xs"][(k + 1) % 2]
+            self.model.sample_prior_into(cur[0], cur[1], NM3, s["bt"], s["z"][k], s["Y_gen"], s["Yb_gen"])
+            _lib.check(lib.egx_assemble_params(_lib.ptr(s["seed"]), _lib.ptr(s["Yb_gen"]), BN, _lib.ptr(s["pp"]), st), "egx_assemble_params")
+            if scene is None:
+                bm.forward(s["pp"].view(BN * T_ALL, XB), s["bt"], T_ALL, want_verts=False, want_joints=True, want_markers=True, out=lbs)
+            else:
+                bm.forward(s["pp"].view(BN * T_ALL, XB), s["bt"], T_ALL, want_verts=False, want_joints=True, want_markers=True, out=lbs,
+                           sdf=scene, R0=s["R0"], T0=s["T0"], agent_scene=s["rows_scene"])
+            _lib.check(lib.egx_primitive_select(
+                _lib.ptr(s["Y_gen"]), vp(cur[0]), vp(cur[1]), NM3, _lib.ptr(lbs["joints"]), 127, _lib.ptr(lbs["markers"]),
+                _lib.ptr(s["R0"]), _lib.ptr(s["T0"]), _lib.ptr(lbs.get("pene_count")), _lib.ptr(s["goal"]), _lib.ptr(s["feet"]),
+                s["weights"], s["pene_thres"], s["goal_thresh"], s["rf"], b, N, vp(s["choice"][k]), vp(s["status"][k]),
+                vp(s["reached"][k]), vp(s["goal_dist"][k]), vp(s["cost"][k]), vp(s["cost_terms"][k]), vp(s["colliding"][k]), st),
+                "egx_primitive_select")
+            _lib.check(lib.egx_primitive_advance_select(
+                _lib.ptr(s["pp"]), _lib.ptr(s["Y_gen"]), vp(cur[0]), vp(cur[1]), NM3, _lib.ptr(lbs["joints"]), 127,
+                _lib.ptr(lbs["markers"]), _lib.ptr(s["delta_T"]), s["rf"], b, vp(s["choice"][k]), N, _lib.ptr(s["R0"]), _lib.ptr(s["T0"]),
+                vp(s["markers"][k]), vp(s["pelvis"][k]), vp(s["rotmat"][k]), vp(s["transl"][k]), vp(s["params"][k]), _lib.ptr(s["seed"]),
+                vp(nxt[0]), vp(nxt[1]), NM3, _lib.ptr(s["nonfinite"]), st), "egx_primitive_advance_select")
 
     # ------------------------------------------------------------------------------------------------------------------
     def _compose_body_params_(self, data):

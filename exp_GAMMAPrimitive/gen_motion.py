@@ -4,6 +4,10 @@
 40 fps) for `--n-gens` variants of one seed, one `motion_<seed>_<variant>.pkl` per variant in the layout
 `utils.rollout_primitives` and the EgoBody consumers read.
 
+With `--goal x,y,z` (world coordinates) the variants are steered there by `generate_sequence_to_goal`: `--n-candidates N` candidates
+per primitive and variant, the best one kept (greedy best-of-N on the env's reward arguments), optionally through the SDF scene
+`--scene file.npz` (keys sdf, center, scale: the reference's sdf_dict); a file stops at the primitive that reaches the goal.
+
 `--cfg <name>` is the combo config (`crowd_ppo/cfg_samp20/<name>.yml` under the working directory, else the packaged copy): it
 names the predictor's and the regressor's configs, whose checkpoints are read from `results/crowd_ppo/<config>/checkpoints`
 (predictor `epoch-400.ckp` else `epoch-200.ckp`, regressor `epoch-100.ckp`), or, with `--ckpt-dir`, the combo checkpoint
@@ -38,7 +42,12 @@ def main(argv=None):
     parser.add_argument("--ckpt-dir", default=None, help="directory of a combo checkpoint (train_GAMMACombo.py)")
     parser.add_argument("--num-verts", type=int, default=synth.NUM_VERTS)
     parser.add_argument("--start-frame", type=int, default=5)
+    parser.add_argument("--goal", default=None, help="x,y,z in world coordinates: steer every variant there (best-of-N search)")
+    parser.add_argument("--n-candidates", type=int, default=16, help="candidates per primitive and variant (with --goal)")
+    parser.add_argument("--scene", default=None, help="npz with sdf, center, scale: penalise and avoid penetration (with --goal)")
     args = parser.parse_args(argv)
+    if args.goal is None and args.scene is not None:
+        parser.error("--scene needs --goal")
     if not torch.cuda.is_available():
         raise SystemExit("gen_motion needs a HIP device: the MI355X path has no CPU fallback")
     np.random.seed(args.seed)
@@ -73,9 +82,24 @@ def main(argv=None):
     data = can["marker_ssm2_67"].reshape(2, 1, 201).astype(np.float32)
     bparams = np.zeros((2, 1, 93), np.float32)
     bparams[:, 0, :3], bparams[:, 0, 3:69] = can["trans"], can["poses"][:, :66]
-    res = op.generate_sequence(data, bparams, can["betas"].astype(np.float32), args.n_primitives, n_gens=args.n_gens,
-                               R0=can["transf_rotmat"].astype(np.float32)[None].repeat(args.n_gens, 0),
-                               T0=can["transf_transl"].astype(np.float32).reshape(1, 3).repeat(args.n_gens, 0))
+    R0 = can["transf_rotmat"].astype(np.float32)[None].repeat(args.n_gens, 0)
+    T0 = can["transf_transl"].astype(np.float32).reshape(1, 3).repeat(args.n_gens, 0)
+    if args.goal is None:
+        res = op.generate_sequence(data, bparams, can["betas"].astype(np.float32), args.n_primitives, n_gens=args.n_gens, R0=R0, T0=T0)
+    else:
+        from egogen_amd.body_model import SdfScene
+        goal = np.asarray([float(v) for v in args.goal.split(",")], np.float32)
+        if goal.shape != (3,):
+            raise SystemExit("--goal takes x,y,z")
+        scene = None
+        if args.scene:
+            with np.load(args.scene) as f:
+                scene = SdfScene({k: f[k] for k in ("sdf", "center", "scale")})
+        res = op.generate_sequence_to_goal(data.repeat(args.n_gens, 1), bparams.repeat(args.n_gens, 1), can["betas"].astype(np.float32),
+                                           goal, args.n_primitives, args.n_candidates, scene=scene, R0=R0, T0=T0)
+        for i in range(args.n_gens):
+            print("[INFO] variant {}: {} primitives, final distance to the goal {:.3f} m, colliding choices {}".format(
+                i, int(res.n_valid[i]), float(res.goal_dist[int(res.n_valid[i]) - 1, i]), int((res.status[:int(res.n_valid[i]), i] & 1).sum())))
     paths = [res.save(args.out, i, man_id="{}_{}".format(args.seed, i)) for i in range(args.n_gens)]
     for p in paths:
         print(p)

@@ -32,6 +32,7 @@ extern "C" {
 #define EGX_NUM_JOINTS 55      /* SMPL-X kinematic joints                */
 #define EGX_NUM_JOINTS_OUT 127 /* 55 + 21 vertex joints + 51 landmarks   */
 #define EGX_XB_DIM 93          /* transl3 glorot3 body63 lhand12 rhand12 */
+#define EGX_MAX_CANDIDATES 256 /* candidates per sequence of egx_primitive_select */
 #define EGX_NUM_BETAS 10
 #define EGX_POSE_FEAT 486
 #define EGX_BLEND_K 472        /* GEMM K: 10 betas + 9 x 51 movable joints = 469, padded to 8 (jaw/eyes are always identity here) */
@@ -802,6 +803,45 @@ int egx_primitive_advance(const float* pred_params, const float* Y_gen, const fl
                           float reproj_factor, int num_sequences, float* R0, float* T0, float* out_marker_b, float* out_pelvis,
                           float* out_R, float* out_T, float* out_seed_params, float* out_x0, float* out_x1, int out_x_ld,
                           int32_t* nonfinite, void* stream);
+
+/* egx_primitive_select - best-of-N search over motion primitives, the scoring and the choice: one launch, one workgroup per
+ * sequence.  Row r = i * num_candidates + n is candidate n of sequence i; the per-row inputs are the ones egx_primitive_advance
+ * reads (Y_gen [18,rows,201], x0 / x1 with row stride x_ld, joints [rows*20,joints_per_body,3], markers_proj [rows*20,67,3]) plus
+ * R0 [rows,3,3] / T0 [rows,3] (the frame the primitive was generated in, read only), pene_count [rows*20] from egx_lbs_forward (NULL:
+ * no scene, the penetration term is 0 and nothing collides), goal [num_sequences,3] in world coordinates, feet_marker_idx [6] and
+ * weights [5] = goal, skate, floor, pene, face (HOST memory).  On the blended markers mb = reproj_factor * markers_proj +
+ * (1 - reproj_factor) * cat(x, Y_gen) (the values egx_primitive_advance writes) each term is the argument of a reward term of
+ * CrowdEnv.step, never its exponential:
+ *   skate = mean_{t=1..18} max(min_feet |mb[t+1] - mb[t-1]| / 2 * 40 - 0.075, 0)       (crowd_env_2f.py:181-185)
+ *   floor = mean_t |min_feet (R0 mb[t] + T0).z - 0.02|                                  (:190-194)
+ *   pene  = sum_t pene_count[t] / 20 / 10;  colliding = max_t pene_count[t] >= pene_thres  (:174-177)
+ *   dist  = max(|R0^T (goal - T0) - joint 0 of body 19|, 1e-12)                         (:232)
+ *   face  = 1 - r_face_target                                                           (:217-219)
+ *   cost  = w_goal dist + w_skate skate + w_floor floor + w_pene pene + w_face face     (float32, in this order)
+ * cost [rows], cost_terms [rows,5] = dist, skate, floor, pene, face, colliding [rows].  Per sequence: choice = the first row in the
+ * order (all values finite before any non-finite; non-colliding before colliding; lower cost; lower index), status bit 0 = the
+ * chosen row collides, bit 1 = every row held a non-finite value, reached = chosen dist < goal_thresh, goal_dist = chosen dist.
+ * pred_params is not among the inputs: no term reads it.  num_candidates in [1, EGX_MAX_CANDIDATES].  No float atomics: a
+ * sequence's outputs depend on its own rows only and are the same bits in any batch. */
+int egx_primitive_select(const float* Y_gen, const float* x0, const float* x1, int x_ld, const float* joints, int joints_per_body,
+                         const float* markers_proj, const float* R0, const float* T0, const int32_t* pene_count, const float* goal,
+                         const int32_t* feet_marker_idx, const float* weights, float pene_thres, float goal_thresh,
+                         float reproj_factor, int num_sequences, int num_candidates, int32_t* choice, int32_t* status,
+                         int32_t* reached, float* goal_dist, float* cost, float* cost_terms, int32_t* colliding, void* stream);
+
+/* egx_primitive_advance_select - egx_primitive_advance from the chosen candidate: workgroup i reads the per-row inputs (rows =
+ * num_sequences * num_candidates of them) at row i * num_candidates + choice[i] (a choice outside [0, num_candidates) is clamped),
+ * writes the records out_marker_b / out_pelvis / out_R / out_T and, where not NULL, out_params [num_sequences,20,93] (the chosen
+ * row of pred_params) to row i of [num_sequences,...] buffers, and the next state (R0, T0 in place, out_seed_params, out_x0 /
+ * out_x1) to all num_candidates rows of its group, so that every candidate of the next primitive starts from the winner
+ * (crowd_env_2f.py:238-265).  The same arithmetic as egx_primitive_advance (one device function); with num_candidates = 1 and
+ * choice = 0 the same bits.  nonfinite counts the sequences whose handed-on values are not finite. */
+int egx_primitive_advance_select(const float* pred_params, const float* Y_gen, const float* x0, const float* x1, int x_ld,
+                                 const float* joints, int joints_per_body, const float* markers_proj, const float* delta_T,
+                                 float reproj_factor, int num_sequences, const int32_t* choice, int num_candidates, float* R0,
+                                 float* T0, float* out_marker_b, float* out_pelvis, float* out_R, float* out_T, float* out_params,
+                                 float* out_seed_params, float* out_x0, float* out_x1, int out_x_ld, int32_t* nonfinite,
+                                 void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * PPO rollout glue
