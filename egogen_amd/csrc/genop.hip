@@ -1,6 +1,9 @@
 // Hand-off between two motion primitives of a chain (one workgroup per sequence, one launch, no sync), and the best-of-N search on
 // top of it: scoring and selection of N candidates per sequence (egx_primitive_select) and the hand-off from the chosen one
-// (egx_primitive_advance_select).
+// (egx_primitive_advance_select).  The beam search keeps W partial paths per sequence: egx_primitive_beam_select scores the W * N
+// rows of a sequence with the same row scoring and keeps the W best path keys, egx_primitive_advance_beam hands each kept row on
+// to the N rows of its slot (one workgroup per slot, R0 / T0 from one buffer into another), egx_beam_backtrack gathers the
+// records of the returned path.
 //
 // Reference: the motion-only tail of CrowdEnv.step, motion/crowd_ppo/crowd_env_2f.py:144-155 (pelvis, blended markers) and
 // :238-265 (new canonical frame from the second-last body, accumulated world frame, seed parameters and seed markers in the new
@@ -28,8 +31,10 @@ struct AdvanceArgs {
   const float* joints;        // [B*20,jpb,3]
   const float* markers_proj;  // [B*20,67,3]
   const float* delta_T;       // [B,3]
-  float* R0;                  // [B,9] in place
-  float* T0;                  // [B,3] in place
+  const float* R0;            // [B,9] read before the barrier ...
+  const float* T0;            // [B,3]
+  float* R0_out;              // ... written after it: the same buffers in the one-workgroup-per-group entries (in place), other
+  float* T0_out;              // buffers where several workgroups share a group (egx_primitive_advance_beam)
   float* out_marker_b;        // [B,20,67,3]
   float* out_pelvis;          // [B,20,3]
   float* out_R;               // [B,9]
@@ -39,6 +44,7 @@ struct AdvanceArgs {
   float* out_x1;
   float* out_params;          // [b,20,93] record of the handed-on row, or null
   int* nonfinite;             // [1] or null
+  int* beam_status;           // [b*W] of the beam hand-off: bit 2 of row `rec` is set on a non-finite value (no counter there)
   float rf;
   int B /* rows of the per-row inputs */, jpb, x_ld, out_x_ld;
 };
@@ -58,7 +64,8 @@ __device__ __forceinline__ float blend_marker(float rf, float proj, float pred) 
 
 // The hand-off of one sequence by one workgroup: reads row `src` of the per-row inputs, writes the record outputs to row `rec`
 // and the next state (R0, T0, seed parameters, seed frames) to the `ndst` rows from `dst0`.  Every read of R0 / T0 precedes the
-// barrier, every write of them follows it.
+// barrier, every write of them (to R0_out / T0_out) follows it.  BEAM: a non-finite value marks beam_status[rec], not the counter.
+template <bool BEAM>
 __device__ __forceinline__ void advance_body(const AdvanceArgs& p, int src, int rec, int dst0, int ndst) {
   __shared__ float s_mb[THIS][MD];   // blended markers of frames 18, 19 (old frame)
   __shared__ float s_frame[24];      // R_[9], T_[3], new R0[9], new T0[3]
@@ -129,8 +136,8 @@ __device__ __forceinline__ void advance_body(const AdvanceArgs& p, int src, int 
   // ---- accumulated world frame of the next primitive, to every row of the group ---------------------------------------------
   for (int i = tid; i < ndst * 12; i += BLK) {
     const int n = i / 12, e = i % 12;
-    if (e < 9) p.R0[(size_t)(dst0 + n) * 9 + e] = s_frame[12 + e];
-    else p.T0[(size_t)(dst0 + n) * 3 + (e - 9)] = s_frame[12 + e];
+    if (e < 9) p.R0_out[(size_t)(dst0 + n) * 9 + e] = s_frame[12 + e];
+    else p.T0_out[(size_t)(dst0 + n) * 3 + (e - 9)] = s_frame[12 + e];
   }
   // ---- next seed: markers of frames 18, 19 in (R_, T_), parameters with the new transl / glorot ---------------------------
   float Rn[9], Tn[3];
@@ -154,19 +161,32 @@ __device__ __forceinline__ void advance_body(const AdvanceArgs& p, int src, int 
     bad |= nonfin(v);
   }
   const int any_bad = __syncthreads_or(bad ? 1 : 0);
-  if (tid == 0 && any_bad && p.nonfinite) atomicAdd(p.nonfinite, 1);
+  if (BEAM) {
+    if (tid == 0 && any_bad) p.beam_status[rec] |= 4;
+  } else {
+    if (tid == 0 && any_bad && p.nonfinite) atomicAdd(p.nonfinite, 1);
+  }
 }
 
 __global__ __launch_bounds__(BLK) void egx_primitive_advance_kernel(AdvanceArgs p) {
   const int b = blockIdx.x;
-  advance_body(p, b, b, b, 1);
+  advance_body<false>(p, b, b, b, 1);
 }
 
 // workgroup i hands sequence i on from candidate choice[i] of its num_candidates rows (a choice outside the group is clamped)
 __global__ __launch_bounds__(BLK) void egx_primitive_advance_select_kernel(AdvanceArgs p, const int* __restrict__ choice, int N) {
   const int g = blockIdx.x;
   const int c = min(max(choice[g], 0), N - 1);
-  advance_body(p, g * N + c, g, g * N, N);
+  advance_body<false>(p, g * N + c, g, g * N, N);
+}
+
+// workgroup (i, s) hands slot s of sequence i on from row beam_row[i,s] of the sequence's W * N rows (clamped into the group) to the
+// N rows of slot s.  Another slot of the group may read the row this one overwrites: R0 / T0 and the seed frames go to other
+// buffers than they are read from; pred_params, joints and markers are only read.
+__global__ __launch_bounds__(BLK) void egx_primitive_advance_beam_kernel(AdvanceArgs p, const int* __restrict__ beam_row, int W, int N) {
+  const int slot = blockIdx.x, g = slot / W;
+  const int r = min(max(beam_row[slot], 0), W * N - 1);
+  advance_body<true>(p, g * W * N + r, slot, slot * N, N);
 }
 
 // ---- scoring and selection -----------------------------------------------------------------------------------------------
@@ -215,18 +235,27 @@ __device__ __forceinline__ bool candidate_before(int ca, float xa, int ia, int c
 
 }  // namespace
 
-__global__ __launch_bounds__(SEL_BLK) void egx_primitive_select_kernel(SelectArgs p) {
-  __shared__ float s_feet[SEL_WAVES][NT][NF * 3];   // blended feet markers of the row a wave is scoring
-  __shared__ float s_cost[MAXC], s_dist[MAXC];
-  __shared__ int s_cls[MAXC];
-  const int g = blockIdx.x, tid = threadIdx.x, w = tid >> 6, lane = tid & 63, N = p.N;
+namespace {
+
+// what lane 0 of the scoring wave knows of a row; q is the cost without its goal term, accumulated on its own
+struct RowScore {
+  float cost, q, dist;
+  bool collides, finite;
+};
+
+// The row scoring of both searches: the 8 waves of the workgroup score the M rows of group g (rows g * M ...), one row per wave at
+// a time; lane 0 of the wave writes cost / terms / colliding of the row and hands its RowScore to keep(n, score).  Ends on a
+// barrier: what keep() put into LDS is visible to the whole workgroup.
+template <class Keep>
+__device__ __forceinline__ void score_group(const SelectArgs& p, int g, int M, float (*s_feet)[NT][NF * 3], Keep keep) {
+  const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
   const int feet_local[NF] = {0, 1, 2, 3, 4, 5};
   const float goal[3] = {p.goal[(size_t)g * 3 + 0], p.goal[(size_t)g * 3 + 1], p.goal[(size_t)g * 3 + 2]};
 
-  for (int n0 = 0; n0 < N; n0 += SEL_WAVES) {      // the same trip count in every wave: the barriers are uniform
+  for (int n0 = 0; n0 < M; n0 += SEL_WAVES) {      // the same trip count in every wave: the barriers are uniform
     const int n = n0 + w;
-    const bool active = n < N;
-    const size_t row = (size_t)g * N + (active ? n : 0);
+    const bool active = n < M;
+    const size_t row = (size_t)g * M + (active ? n : 0);
     if (active)
       for (int e = lane; e < NT * NF * 3; e += 64) {
         const int t = e / (NF * 3), r = e % (NF * 3);
@@ -262,19 +291,32 @@ __global__ __launch_bounds__(SEL_BLK) void egx_primitive_select_kernel(SelectArg
         const float face = 1.f - reward_face(j19, R0, T0, goal, tl, dir);
         const float dist = target_distance(tl, j19);
         const float cost = p.w_goal * dist + p.w_skate * skate + p.w_floor * floor_ + p.w_pene * pene + p.w_face * face;
+        const float q = p.w_skate * skate + p.w_floor * floor_ + p.w_pene * pene + p.w_face * face;
         const bool collides = p.pene_count && !((float)cmax < p.pene_thres);
         const bool finite = isfinite(cost) && isfinite(dist) && isfinite(skate) && isfinite(floor_) && isfinite(pene) && isfinite(face);
         p.cost[row] = cost;
         float* tm = p.terms + row * 5;
         tm[0] = dist; tm[1] = skate; tm[2] = floor_; tm[3] = pene; tm[4] = face;
         p.colliding[row] = collides ? 1 : 0;
-        s_cost[n] = finite ? cost : 0.f;      // a non-finite row is ranked by collision and index only
-        s_dist[n] = dist;
-        s_cls[n] = (finite ? 0 : 2) | (collides ? 1 : 0);
+        keep(n, RowScore{cost, q, dist, collides, finite});
       }
     }
     __syncthreads();
   }
+}
+
+}  // namespace
+
+__global__ __launch_bounds__(SEL_BLK) void egx_primitive_select_kernel(SelectArgs p) {
+  __shared__ float s_feet[SEL_WAVES][NT][NF * 3];   // blended feet markers of the row a wave is scoring
+  __shared__ float s_cost[MAXC], s_dist[MAXC];
+  __shared__ int s_cls[MAXC];
+  const int g = blockIdx.x, tid = threadIdx.x, w = tid >> 6, lane = tid & 63, N = p.N;
+  score_group(p, g, N, s_feet, [&](int n, const RowScore& r) {
+    s_cost[n] = r.finite ? r.cost : 0.f;      // a non-finite row is ranked by collision and index only
+    s_dist[n] = r.dist;
+    s_cls[n] = (r.finite ? 0 : 2) | (r.collides ? 1 : 0);
+  });
 
   if (w == 0) {
     int bc = 4, bi = 0x7fffffff;
@@ -296,6 +338,130 @@ __global__ __launch_bounds__(SEL_BLK) void egx_primitive_select_kernel(SelectArg
   }
 }
 
+// ---- beam: scoring and top-W selection -------------------------------------------------------------------------------------
+// One workgroup per sequence scores its W * N rows as above, then every row counts the rows whose path key precedes its own:
+// (non-finite, colliding nodes on the path, accumulated cost, row index) is a total order, so that count is the row's rank
+// whatever the order of the comparisons, and the rows of rank < W are the beam, slot = rank.
+namespace {
+
+struct BeamArgs {
+  const float* acc;      // [b,W] sum of q along the path into each slot
+  const int* ncoll;      // [b,W] colliding nodes on it
+  int* beam_row;         // [b,W] outputs per kept slot
+  int* parent;
+  float* acc_out;
+  int* ncoll_out;
+  float* path_cost;
+  int* beam_status;
+  float* goal_dist;
+  int* reached;
+  int W, N;
+};
+
+constexpr int NONFINITE_KEY = 1 << 30;   // above any count of colliding nodes
+
+__device__ __forceinline__ bool path_before(int ca, float xa, int ia, int cb, float xb, int ib) {
+  if (ca != cb) return ca < cb;
+  if (xa != xb) return xa < xb;
+  return ia < ib;
+}
+
+}  // namespace
+
+__global__ __launch_bounds__(SEL_BLK) void egx_primitive_beam_select_kernel(SelectArgs p, BeamArgs q) {
+  __shared__ float s_feet[SEL_WAVES][NT][NF * 3];
+  __shared__ float s_path[MAXC], s_q[MAXC], s_dist[MAXC];   // path cost (0 where non-finite), q and dist of every row
+  __shared__ int s_key[MAXC], s_flag[MAXC];                 // (non-finite, colliding nodes) in one int; bit 0 collides, bit 1 non-finite
+  const int g = blockIdx.x, tid = threadIdx.x, W = q.W, N = q.N, M = W * N;
+  score_group(p, g, M, s_feet, [&](int n, const RowScore& r) {
+    const int s = n / N;
+    const float path = q.acc[(size_t)g * W + s] + (r.finite ? r.cost : 0.f);
+    const int nc = q.ncoll[(size_t)g * W + s] + (r.collides ? 1 : 0);
+    const bool finite = r.finite && isfinite(path);          // a path through a non-finite node stays non-finite
+    s_path[n] = finite ? path : 0.f;
+    s_q[n] = r.q;
+    s_dist[n] = r.dist;
+    s_key[n] = finite ? min(max(nc, 0), NONFINITE_KEY - 1) : NONFINITE_KEY + min(max(nc, 0), NONFINITE_KEY - 1);
+    s_flag[n] = (r.collides ? 1 : 0) | (finite ? 0 : 2);
+  });
+
+  if (tid < M) {
+    const int kc = s_key[tid];
+    const float kx = s_path[tid];
+    int rank = 0;
+    for (int m = 0; m < M; ++m) rank += path_before(s_key[m], s_path[m], m, kc, kx, tid) ? 1 : 0;
+    if (rank < W) {
+      const int s = tid / N;
+      const size_t o = (size_t)g * W + rank;
+      q.beam_row[o] = tid;
+      q.parent[o] = s;
+      q.acc_out[o] = q.acc[(size_t)g * W + s] + s_q[tid];
+      q.ncoll_out[o] = q.ncoll[(size_t)g * W + s] + (s_flag[tid] & 1);
+      q.path_cost[o] = kx;
+      q.beam_status[o] = s_flag[tid];
+      q.goal_dist[o] = s_dist[tid];
+      q.reached[o] = (s_dist[tid] < p.goal_thresh) ? 1 : 0;
+    }
+  }
+}
+
+// ---- beam: the returned path --------------------------------------------------------------------------------------------
+// Workgroup (k, i) walks from slot 0 of the last depth back to depth k along `parent` and copies the records of the slot it lands
+// on into row (k, i) of the [K,b,...] outputs.
+namespace {
+
+struct BacktrackArgs {
+  const int* parent;         // [K,b,W]
+  const int* beam_row;       // [K,b,W] per-slot records of the selection ...
+  const int* beam_status;
+  const float* goal_dist;
+  const int* reached;
+  const float* rec_marker_b; // [K,b,W,20,67,3] ... and of the hand-off
+  const float* rec_pelvis;   // [K,b,W,20,3]
+  const float* rec_R;        // [K,b,W,9]
+  const float* rec_T;        // [K,b,W,3]
+  const float* rec_params;   // [K,b,W,20,93]
+  int K, b, W;
+  int* path_slot;            // [K,b]
+  int* choice;
+  int* status;
+  float* out_goal_dist;
+  int* out_reached;
+  float* out_marker_b;       // [K,b,20,67,3]
+  float* out_pelvis;
+  float* out_R;
+  float* out_T;
+  float* out_params;
+};
+
+constexpr int NP4 = NT * XB / 4;
+static_assert(NT * XB % 4 == 0, "a sequence's parameters are whole float4 packets");
+
+}  // namespace
+
+__global__ __launch_bounds__(BLK) void egx_beam_backtrack_kernel(BacktrackArgs p) {
+  const int k = blockIdx.x / p.b, i = blockIdx.x % p.b, tid = threadIdx.x, W = p.W;
+  int slot = 0;                                               // every lane walks the same few words
+  for (int d = p.K - 1; d > k; --d) slot = min(max(p.parent[((size_t)d * p.b + i) * W + slot], 0), W - 1);
+  const size_t src = ((size_t)k * p.b + i) * W + slot, dst = (size_t)k * p.b + i;
+  if (tid == 0) {
+    p.path_slot[dst] = slot;
+    p.choice[dst] = p.beam_row[src];
+    p.status[dst] = p.beam_status[src];
+    p.out_goal_dist[dst] = p.goal_dist[src];
+    p.out_reached[dst] = p.reached[src];
+  }
+  const f32x4* m4 = reinterpret_cast<const f32x4*>(p.rec_marker_b + src * NT * MD);
+  f32x4* om4 = reinterpret_cast<f32x4*>(p.out_marker_b + dst * NT * MD);
+  for (int e = tid; e < NV4; e += BLK) om4[e] = m4[e];
+  const f32x4* p4 = reinterpret_cast<const f32x4*>(p.rec_params + src * NT * XB);
+  f32x4* op4 = reinterpret_cast<f32x4*>(p.out_params + dst * NT * XB);
+  for (int e = tid; e < NP4; e += BLK) op4[e] = p4[e];
+  if (tid < NT * 3) p.out_pelvis[dst * NT * 3 + tid] = p.rec_pelvis[src * NT * 3 + tid];
+  if (tid >= 64 && tid < 64 + 9) p.out_R[dst * 9 + (tid - 64)] = p.rec_R[src * 9 + (tid - 64)];
+  if (tid >= 128 && tid < 128 + 3) p.out_T[dst * 3 + (tid - 128)] = p.rec_T[src * 3 + (tid - 128)];
+}
+
 extern "C" int egx_primitive_advance(const float* pred_params, const float* Y_gen, const float* x0, const float* x1, int x_ld,
                                      const float* joints, int joints_per_body, const float* markers_proj, const float* delta_T,
                                      float reproj_factor, int num_sequences, float* R0, float* T0, float* out_marker_b,
@@ -309,7 +475,7 @@ extern "C" int egx_primitive_advance(const float* pred_params, const float* Y_ge
               "markers_proj and out_marker_b must be 16-byte aligned");
   AdvanceArgs p;
   p.pred_params = pred_params; p.Y_gen = Y_gen; p.x0 = x0; p.x1 = x1; p.joints = joints; p.markers_proj = markers_proj;
-  p.delta_T = delta_T; p.R0 = R0; p.T0 = T0; p.out_marker_b = out_marker_b; p.out_pelvis = out_pelvis; p.out_R = out_R;
+  p.delta_T = delta_T; p.R0 = R0; p.T0 = T0; p.R0_out = R0; p.T0_out = T0; p.beam_status = nullptr; p.out_marker_b = out_marker_b; p.out_pelvis = out_pelvis; p.out_R = out_R;
   p.out_T = out_T; p.out_seed = out_seed_params; p.out_x0 = out_x0; p.out_x1 = out_x1; p.out_params = nullptr; p.nonfinite = nonfinite;
   p.rf = reproj_factor; p.B = num_sequences; p.jpb = joints_per_body; p.x_ld = x_ld; p.out_x_ld = out_x_ld;
   hipLaunchKernelGGL(egx_primitive_advance_kernel, dim3(num_sequences), dim3(BLK), 0, static_cast<hipStream_t>(stream), p);
@@ -356,12 +522,102 @@ extern "C" int egx_primitive_advance_select(const float* pred_params, const floa
               "markers_proj and out_marker_b must be 16-byte aligned");
   AdvanceArgs p;
   p.pred_params = pred_params; p.Y_gen = Y_gen; p.x0 = x0; p.x1 = x1; p.joints = joints; p.markers_proj = markers_proj;
-  p.delta_T = delta_T; p.R0 = R0; p.T0 = T0; p.out_marker_b = out_marker_b; p.out_pelvis = out_pelvis; p.out_R = out_R;
+  p.delta_T = delta_T; p.R0 = R0; p.T0 = T0; p.R0_out = R0; p.T0_out = T0; p.beam_status = nullptr; p.out_marker_b = out_marker_b; p.out_pelvis = out_pelvis; p.out_R = out_R;
   p.out_T = out_T; p.out_seed = out_seed_params; p.out_x0 = out_x0; p.out_x1 = out_x1; p.out_params = out_params;
   p.nonfinite = nonfinite; p.rf = reproj_factor; p.B = num_sequences * num_candidates; p.jpb = joints_per_body; p.x_ld = x_ld;
   p.out_x_ld = out_x_ld;
   hipLaunchKernelGGL(egx_primitive_advance_select_kernel, dim3(num_sequences), dim3(BLK), 0, static_cast<hipStream_t>(stream), p,
                      choice, num_candidates);
+  EGX_HIP_CHECK(hipGetLastError());
+  return EGX_OK;
+}
+
+extern "C" int egx_primitive_beam_select(const float* Y_gen, const float* x0, const float* x1, int x_ld, const float* joints,
+                                         int joints_per_body, const float* markers_proj, const float* R0, const float* T0,
+                                         const int32_t* pene_count, const float* goal, const int32_t* feet_marker_idx,
+                                         const float* weights, float pene_thres, float goal_thresh, float reproj_factor,
+                                         int num_sequences, int beam_width, int num_candidates, const float* acc,
+                                         const int32_t* ncoll, float* cost, float* cost_terms, int32_t* colliding, int32_t* beam_row,
+                                         int32_t* parent, float* acc_out, int32_t* ncoll_out, float* path_cost, int32_t* beam_status,
+                                         float* goal_dist, int32_t* reached, void* stream) {
+  EGX_REQUIRE(Y_gen && x0 && x1 && joints && markers_proj && R0 && T0 && goal && feet_marker_idx && weights && acc && ncoll, "null input");
+  EGX_REQUIRE(cost && cost_terms && colliding && beam_row && parent && acc_out && ncoll_out && path_cost && beam_status && goal_dist &&
+                  reached, "null output");
+  EGX_REQUIRE(num_sequences > 0 && joints_per_body >= 3, "need a non-empty batch and >= 3 joints per body");
+  EGX_REQUIRE(beam_width >= 1 && beam_width <= EGX_MAX_BEAM, "beam_width must be in [1, EGX_MAX_BEAM]");
+  EGX_REQUIRE(num_candidates >= 1 && num_candidates <= MAXC && beam_width * num_candidates <= MAXC,
+              "beam_width * num_candidates must be in [1, EGX_MAX_CANDIDATES]");
+  EGX_REQUIRE(x_ld >= MD, "a seed frame holds 201 floats: the row stride cannot be smaller");
+  EGX_REQUIRE(acc != acc_out && ncoll != ncoll_out, "acc / ncoll are read from one buffer and written to another");
+  SelectArgs p;
+  p.Y_gen = Y_gen; p.x0 = x0; p.x1 = x1; p.joints = joints; p.markers_proj = markers_proj; p.R0 = R0; p.T0 = T0;
+  p.pene_count = pene_count; p.goal = goal; p.feet_marker_idx = feet_marker_idx;
+  p.w_goal = weights[0]; p.w_skate = weights[1]; p.w_floor = weights[2]; p.w_pene = weights[3]; p.w_face = weights[4];
+  p.pene_thres = pene_thres; p.goal_thresh = goal_thresh; p.rf = reproj_factor;
+  p.rows = num_sequences * beam_width * num_candidates; p.N = beam_width * num_candidates; p.jpb = joints_per_body; p.x_ld = x_ld;
+  p.choice = nullptr; p.status = nullptr; p.reached = nullptr; p.goal_dist = nullptr; p.cost = cost; p.terms = cost_terms;
+  p.colliding = colliding;
+  BeamArgs q;
+  q.acc = acc; q.ncoll = ncoll; q.beam_row = beam_row; q.parent = parent; q.acc_out = acc_out; q.ncoll_out = ncoll_out;
+  q.path_cost = path_cost; q.beam_status = beam_status; q.goal_dist = goal_dist; q.reached = reached; q.W = beam_width;
+  q.N = num_candidates;
+  hipLaunchKernelGGL(egx_primitive_beam_select_kernel, dim3(num_sequences), dim3(SEL_BLK), 0, static_cast<hipStream_t>(stream), p, q);
+  EGX_HIP_CHECK(hipGetLastError());
+  return EGX_OK;
+}
+
+extern "C" int egx_primitive_advance_beam(const float* pred_params, const float* Y_gen, const float* x0, const float* x1, int x_ld,
+                                          const float* joints, int joints_per_body, const float* markers_proj, const float* delta_T,
+                                          float reproj_factor, int num_sequences, int beam_width, int num_candidates,
+                                          const int32_t* beam_row, const float* R0, const float* T0, float* R0_out, float* T0_out,
+                                          float* out_marker_b, float* out_pelvis, float* out_R, float* out_T, float* out_params,
+                                          float* out_seed_params, float* out_x0, float* out_x1, int out_x_ld, int32_t* beam_status,
+                                          void* stream) {
+  EGX_REQUIRE(pred_params && Y_gen && x0 && x1 && joints && markers_proj && delta_T && R0 && T0 && beam_row, "null input");
+  EGX_REQUIRE(R0_out && T0_out && out_marker_b && out_pelvis && out_R && out_T && out_seed_params && out_x0 && out_x1 && beam_status,
+              "null output");
+  EGX_REQUIRE(num_sequences > 0 && joints_per_body >= 3, "need a non-empty batch and >= 3 joints per body");
+  EGX_REQUIRE(beam_width >= 1 && beam_width <= EGX_MAX_BEAM, "beam_width must be in [1, EGX_MAX_BEAM]");
+  EGX_REQUIRE(num_candidates >= 1 && num_candidates <= MAXC && beam_width * num_candidates <= MAXC,
+              "beam_width * num_candidates must be in [1, EGX_MAX_CANDIDATES]");
+  EGX_REQUIRE(x_ld >= MD && out_x_ld >= MD, "a seed frame holds 201 floats: the row strides cannot be smaller");
+  EGX_REQUIRE(((uintptr_t)markers_proj & 15) == 0 && ((uintptr_t)out_marker_b & 15) == 0,
+              "markers_proj and out_marker_b must be 16-byte aligned");
+  EGX_REQUIRE(R0 != R0_out && T0 != T0_out && x0 != out_x0 && x1 != out_x1,
+              "a slot may read a row another slot writes: R0 / T0 and the seed frames are written to other buffers");
+  AdvanceArgs p;
+  p.pred_params = pred_params; p.Y_gen = Y_gen; p.x0 = x0; p.x1 = x1; p.joints = joints; p.markers_proj = markers_proj;
+  p.delta_T = delta_T; p.R0 = R0; p.T0 = T0; p.R0_out = R0_out; p.T0_out = T0_out; p.beam_status = beam_status;
+  p.out_marker_b = out_marker_b; p.out_pelvis = out_pelvis; p.out_R = out_R; p.out_T = out_T; p.out_seed = out_seed_params;
+  p.out_x0 = out_x0; p.out_x1 = out_x1; p.out_params = out_params; p.nonfinite = nullptr; p.rf = reproj_factor;
+  p.B = num_sequences * beam_width * num_candidates; p.jpb = joints_per_body; p.x_ld = x_ld; p.out_x_ld = out_x_ld;
+  hipLaunchKernelGGL(egx_primitive_advance_beam_kernel, dim3(num_sequences * beam_width), dim3(BLK), 0,
+                     static_cast<hipStream_t>(stream), p, beam_row, beam_width, num_candidates);
+  EGX_HIP_CHECK(hipGetLastError());
+  return EGX_OK;
+}
+
+extern "C" int egx_beam_backtrack(const int32_t* parent, const int32_t* beam_row, const int32_t* beam_status, const float* goal_dist,
+                                  const int32_t* reached, const float* rec_marker_b, const float* rec_pelvis, const float* rec_R,
+                                  const float* rec_T, const float* rec_params, int num_primitives, int num_sequences, int beam_width,
+                                  int32_t* path_slot, int32_t* choice, int32_t* status, float* out_goal_dist, int32_t* out_reached,
+                                  float* out_marker_b, float* out_pelvis, float* out_R, float* out_T, float* out_params, void* stream) {
+  EGX_REQUIRE(parent && beam_row && beam_status && goal_dist && reached && rec_marker_b && rec_pelvis && rec_R && rec_T && rec_params,
+              "null input");
+  EGX_REQUIRE(path_slot && choice && status && out_goal_dist && out_reached && out_marker_b && out_pelvis && out_R && out_T && out_params,
+              "null output");
+  EGX_REQUIRE(num_primitives > 0 && num_sequences > 0, "need at least one primitive and one sequence");
+  EGX_REQUIRE(beam_width >= 1 && beam_width <= EGX_MAX_BEAM, "beam_width must be in [1, EGX_MAX_BEAM]");
+  EGX_REQUIRE((long long)num_primitives * num_sequences <= 0x7fffffffLL, "num_primitives * num_sequences workgroups exceed the grid");
+  EGX_REQUIRE(((uintptr_t)rec_marker_b & 15) == 0 && ((uintptr_t)out_marker_b & 15) == 0 && ((uintptr_t)rec_params & 15) == 0 &&
+                  ((uintptr_t)out_params & 15) == 0, "the marker and parameter records must be 16-byte aligned");
+  BacktrackArgs p;
+  p.parent = parent; p.beam_row = beam_row; p.beam_status = beam_status; p.goal_dist = goal_dist; p.reached = reached;
+  p.rec_marker_b = rec_marker_b; p.rec_pelvis = rec_pelvis; p.rec_R = rec_R; p.rec_T = rec_T; p.rec_params = rec_params;
+  p.K = num_primitives; p.b = num_sequences; p.W = beam_width; p.path_slot = path_slot; p.choice = choice; p.status = status;
+  p.out_goal_dist = out_goal_dist; p.out_reached = out_reached; p.out_marker_b = out_marker_b; p.out_pelvis = out_pelvis;
+  p.out_R = out_R; p.out_T = out_T; p.out_params = out_params;
+  hipLaunchKernelGGL(egx_beam_backtrack_kernel, dim3(num_primitives * num_sequences), dim3(BLK), 0, static_cast<hipStream_t>(stream), p);
   EGX_HIP_CHECK(hipGetLastError());
   return EGX_OK;
 }

@@ -5,7 +5,9 @@ primitives with the re-canonicalisation between them on the device (`generate_se
 motion-only part of `CrowdEnv.step` (crowd_ppo/crowd_env_2f.py:109-155, 238-265) without scene, rewards or egosensing; and
 `generate_sequence_to_goal`, the greedy best-of-N search over such a chain: per primitive N candidates are scored with the
 arguments of the env's reward terms (:171-235) against a goal and an SDF scene, and every candidate of the next primitive
-continues from the best one (kernels egx_primitive_select, egx_primitive_advance_select).
+continues from the best one (kernels egx_primitive_select, egx_primitive_advance_select); with `beam_width` W > 1 it is a beam
+search that keeps the best W partial paths per sequence (kernels egx_primitive_beam_select, egx_primitive_advance_beam,
+egx_beam_backtrack).
 
 Differences from the reference, all in `generate` unless noted:
   * `t_his=None` means the model's t_his (the reference computes `20 - None` and fails);
@@ -29,6 +31,7 @@ from .models import GAMMAPrimitiveCombo
 
 T_ALL, T_PRED, NM3, XB = 20, 18, 201, 93
 MAX_CANDIDATES = 256        # EGX_MAX_CANDIDATES of include/egogen_hip.h
+MAX_BEAM = 32               # EGX_MAX_BEAM
 SEARCH_WEIGHTS = {"goal": 1.0, "skate": 1.0, "floor": 1.0, "pene": 1.0, "face": 0.0}
 GENERATE_PPO_NOT_BUILT = ("generate_ppo is not built: nothing in the reference calls it, and its policy_model(X, obj_points=, "
                           "target_ori=, local_map=) signature belongs to no class in the tree")
@@ -57,8 +60,13 @@ class PrimitiveSequence:
     A result of `generate_sequence_to_goal` holds the chosen candidates in those fields and, in `search`, what the selection saw:
     goal [b,3], choice [K,b], cost [K,b,N], cost_terms [K,b,N,5] (dist, skate, floor, pene, face), colliding [K,b,N],
     status [K,b] (bit 0: the chosen candidate collides), goal_dist [K,b], n_valid [b] (primitives up to and including the first
-    whose chosen candidate ends within goal_thresh of the goal, K if none does); `primitives` and `save` stop at n_valid."""
+    whose chosen candidate ends within goal_thresh of the goal, K if none does); `primitives` and `save` stop at n_valid.
+    A beam result (beam_width W > 1) holds the returned path in the same fields: cost / cost_terms / colliding are [K,b,W*N(,5)],
+    choice [K,b] the path's row within its W*N, status [K,b] the path node's bits (0: collides, 1: non-finite row, 2: non-finite
+    hand-off); and beam_width, path_slot [K,b], parent / beam_row / path_cost / beam_status [K,b,W], which a greedy result has as
+    None."""
     SEARCH_FIELDS = ("goal", "choice", "cost", "cost_terms", "colliding", "status", "goal_dist", "n_valid")
+    BEAM_FIELDS = ("beam_width", "path_slot", "parent", "beam_row", "path_cost", "beam_status")
 
     def __init__(self, markers, params, rotmat, transl, pelvis, z, betas, gender, R0, T0, search: Optional[dict] = None):
         self.markers, self.params, self.rotmat, self.transl, self.pelvis, self.z = markers, params, rotmat, transl, pelvis, z
@@ -66,6 +74,8 @@ class PrimitiveSequence:
         self.search = search
         for k in self.SEARCH_FIELDS:
             setattr(self, k, None if search is None else search[k])
+        for k in self.BEAM_FIELDS:
+            setattr(self, k, None if search is None else search.get(k))
 
     def primitives(self, i: int) -> list:
         """Sequence i as the list of 8-item records `utils.save_rollout_results` takes (crowd_env_2f.py:155)."""
@@ -293,7 +303,8 @@ class GAMMAPrimitiveComboGenOP:
     # ------------------------------------------------------------------------------------------------------------------
     def generate_sequence_to_goal(self, data, bparams, betas, goal, n_primitives: int, n_candidates: int, scene=None,
                                   agent_scene=None, weights: Optional[dict] = None, pene_thres: float = 40, goal_thresh=None,
-                                  z=None, reproj_factor=None, to_numpy: bool = True, R0=None, T0=None) -> PrimitiveSequence:
+                                  z=None, reproj_factor=None, to_numpy: bool = True, R0=None, T0=None,
+                                  beam_width: int = 1) -> PrimitiveSequence:
         """`generate_sequence` steered to a goal through a scene by a greedy best-of-N search: for each of the `n_primitives`
         primitives, `n_candidates` candidates per sequence are generated, scored and the best one is kept; every candidate of the
         next primitive continues from it.  data / bparams / betas / reproj_factor / R0 / T0 as in `generate_sequence` (b seeds,
@@ -311,20 +322,32 @@ class GAMMAPrimitiveComboGenOP:
         Choice per sequence: candidates without a non-finite value first, then non-colliding, then the lower cost, then the lower
         index.  Per primitive: sample_prior_into -> egx_assemble_params -> BodyModelHandle.forward (with penetration counts in a
         scene) -> egx_primitive_select -> egx_primitive_advance_select; nothing in the loop waits for the device.
+            - beam_width: W in [1, 32] with W * N <= 256 (ValueError otherwise).  1 is the greedy search above.  With W > 1 every
+              sequence keeps W partial paths (slots); each slot is expanded into N candidates (row (i * W + s) * N + n is candidate n
+              of slot s; z is [n_primitives, b * W * N, 128]; at the first primitive all slots hold the seed) and the W rows with the
+              smallest path key (non-finite, colliding nodes on the path, accumulated cost, row) become the next slots, where the
+              accumulated cost is the row's cost plus the skate, floor, pene and face terms of its ancestors: the goal distance at
+              the path's end plus the motion quality along it.  Per primitive: ... -> egx_primitive_beam_select ->
+              egx_primitive_advance_beam; after the loop egx_beam_backtrack gathers the path that ends in the best slot.
         Raises FloatingPointError when a chosen hand-off, or every candidate of a sequence, held a non-finite value (read once,
-        after the loop)."""
+        after the loop); for a beam, when a node of the returned path did."""
         from .body_model import SdfScene, SdfSceneSet
         from . import synth
         if self.body_model is None:
             raise _lib.EgxError("generate_sequence_to_goal needs the body model: build_model(..., body_model=BodyModelHandle)")
-        K, N = int(n_primitives), int(n_candidates)
+        K, N, W = int(n_primitives), int(n_candidates), int(beam_width)
         if K < 1:
             raise ValueError("n_primitives must be >= 1")
         if N < 1 or N > MAX_CANDIDATES:
             raise ValueError(f"n_candidates must be in [1, {MAX_CANDIDATES}], got {N}")
+        if W < 1 or W > MAX_BEAM:
+            raise ValueError(f"beam_width must be in [1, {MAX_BEAM}], got {W}")
+        if W * N > MAX_CANDIDATES:
+            raise ValueError(f"beam_width * n_candidates must be at most {MAX_CANDIDATES}, got {W} * {N}")
+        M = W * N       # rows per sequence
         X, seed, bt = self._seed_inputs(data, bparams, betas, -1, None)
         b, dev, f32, i32 = X.shape[1], self.device, torch.float32, torch.int32
-        BN = b * N
+        BN = b * M
         goal = self._dev(goal, "goal")
         if goal.shape == (3,):
             goal = goal.reshape(1, 3).repeat(b, 1)
@@ -338,7 +361,7 @@ class GAMMAPrimitiveComboGenOP:
             idx = torch.as_tensor(agent_scene).reshape(-1).to("cpu", torch.int64)
             if idx.numel() != b or int(idx.min()) < 0 or int(idx.max()) >= len(scene):
                 raise ValueError(f"agent_scene must hold {b} indices in [0, {len(scene)}), got {idx.tolist()}")
-            rows_scene = idx.to(dev, i32).repeat_interleave(N).contiguous()
+            rows_scene = idx.to(dev, i32).repeat_interleave(M).contiguous()
         elif agent_scene is not None:
             raise ValueError("agent_scene needs an SdfSceneSet")
         elif scene is not None and not isinstance(scene, SdfScene):
@@ -366,7 +389,7 @@ class GAMMAPrimitiveComboGenOP:
         eye = torch.eye(3, device=dev, dtype=f32)
         R0 = eye.repeat(b, 1, 1) if R0 is None else self._dev(R0, "R0").reshape(b, 3, 3)
         T0 = torch.zeros(b, 3, device=dev, dtype=f32) if T0 is None else self._dev(T0, "T0").reshape(b, 3)
-        rep = lambda t, dim=0: t.repeat_interleave(N, dim=dim).contiguous()
+        rep = lambda t, dim=0: t.repeat_interleave(M, dim=dim).contiguous()
         bt_rows = rep(bt)
         s = {"rf": float(reproj_factor), "z": z, "bt": bt_rows, "R0": rep(R0), "T0": rep(T0), "goal": goal,
              "xs": [rep(X, 1), torch.empty(2, BN, NM3, device=dev, dtype=f32)],            # seed markers, ping-pong
@@ -384,30 +407,51 @@ class GAMMAPrimitiveComboGenOP:
              "pelvis": torch.empty(K, b, T_ALL, 3, device=dev, dtype=f32),
              "choice": torch.empty(K, b, device=dev, dtype=i32), "status": torch.empty(K, b, device=dev, dtype=i32),
              "reached": torch.empty(K, b, device=dev, dtype=i32), "goal_dist": torch.empty(K, b, device=dev, dtype=f32),
-             "cost": torch.empty(K, b, N, device=dev, dtype=f32), "cost_terms": torch.empty(K, b, N, 5, device=dev, dtype=f32),
-             "colliding": torch.empty(K, b, N, device=dev, dtype=i32),
+             "cost": torch.empty(K, b, M, device=dev, dtype=f32), "cost_terms": torch.empty(K, b, M, 5, device=dev, dtype=f32),
+             "colliding": torch.empty(K, b, M, device=dev, dtype=i32),
              "nonfinite": torch.zeros(1, device=dev, dtype=i32)}
         if scene is not None:
             s["lbs_out"]["pene_count"] = torch.empty(BN * T_ALL, device=dev, dtype=i32)
         # calc_calibrate_offset: joint 0 at zero orientation / translation (the body pose does not move the root)
         s["delta_T"] = bm.joints55(torch.zeros(BN, XB, device=dev, dtype=f32), bt_rows, 1)[:, 0].contiguous()
         bm.workspace(BN * T_ALL)
-        self._search_loop(K, b, N, s)
-        n = int(s["nonfinite"].item())
         status = s["status"]
-        n_all = int((status & 2).ne(0).sum().item())
-        if n or n_all:
-            raise FloatingPointError(f"the search produced non-finite values: {n} chosen hand-offs, {n_all} sequence steps whose "
-                                     f"candidates were all non-finite")
+        if W == 1:
+            self._search_loop(K, b, N, s)
+            n = int(s["nonfinite"].item())
+            n_all = int((status & 2).ne(0).sum().item())
+            if n or n_all:
+                raise FloatingPointError(f"the search produced non-finite values: {n} chosen hand-offs, {n_all} sequence steps whose "
+                                         f"candidates were all non-finite")
+            R0_end, T0_end = s["R0"], s["T0"]
+        else:
+            slot = lambda *tail, dtype=f32: torch.empty(K, b, W, *tail, device=dev, dtype=dtype)
+            s.update({"R0s": [s["R0"], torch.empty_like(s["R0"])], "T0s": [s["T0"], torch.empty_like(s["T0"])],      # ping-pong
+                      "acc": torch.zeros(K + 1, b, W, device=dev, dtype=f32), "ncoll": torch.zeros(K + 1, b, W, device=dev, dtype=i32),
+                      "rec_markers": slot(T_ALL, 67, 3), "rec_params": slot(T_ALL, XB), "rec_rotmat": slot(3, 3), "rec_transl": slot(3),
+                      "rec_pelvis": slot(T_ALL, 3), "beam_row": slot(dtype=i32), "parent": slot(dtype=i32), "path_cost": slot(),
+                      "beam_status": slot(dtype=i32), "slot_goal_dist": slot(), "slot_reached": slot(dtype=i32),
+                      "path_slot": torch.empty(K, b, device=dev, dtype=i32)})
+            self._beam_loop(K, b, W, N, s)
+            bad = (status & 6).ne(0)
+            n = int(bad.sum().item())
+            if n:
+                raise FloatingPointError(f"the beam search produced non-finite values: {n} nodes of the returned paths")
+            R0_end, T0_end = s["R0s"][K % 2], s["T0s"][K % 2]      # the rows of slot 0: where the path ends
         reached = s["reached"].ne(0)
         first = torch.where(reached.any(0), reached.int().argmax(0) + 1, torch.full((b,), K, device=dev, dtype=torch.int64))
-        zc = z.view(K, b, N, zd).gather(2, s["choice"].long().view(K, b, 1, 1).expand(K, b, 1, zd))[:, :, 0]
-        res = [s["markers"], s["params"], s["rotmat"], s["transl"], s["pelvis"], zc, bt, s["R0"][::N].reshape(b, 3, 3).contiguous(), s["T0"][::N].contiguous()]
+        zc = z.view(K, b, M, zd).gather(2, s["choice"].long().view(K, b, 1, 1).expand(K, b, 1, zd))[:, :, 0]
+        res = [s["markers"], s["params"], s["rotmat"], s["transl"], s["pelvis"], zc, bt, R0_end[::M].reshape(b, 3, 3).contiguous(),
+               T0_end[::M].contiguous()]
         search = {"goal": goal, "choice": s["choice"], "cost": s["cost"], "cost_terms": s["cost_terms"], "colliding": s["colliding"],
                   "status": status, "goal_dist": s["goal_dist"], "n_valid": first}
+        if W > 1:
+            search.update({k: s[k] for k in ("path_slot", "parent", "beam_row", "path_cost", "beam_status")})
         if to_numpy:
             res = [t.cpu().numpy() for t in res]
             search = {k: v.cpu().numpy() for k, v in search.items()}
+        if W > 1:
+            search["beam_width"] = W
         gender = str(_section(self.regressorcfg, "modelconfig").get("gender", "male"))
         return PrimitiveSequence(*res[:7], gender, res[7], res[8], search=search)
 
@@ -438,6 +482,45 @@ class GAMMAPrimitiveComboGenOP:
                 _lib.ptr(lbs["markers"]), _lib.ptr(s["delta_T"]), s["rf"], b, vp(s["choice"][k]), N, _lib.ptr(s["R0"]), _lib.ptr(s["T0"]),
                 vp(s["markers"][k]), vp(s["pelvis"][k]), vp(s["rotmat"][k]), vp(s["transl"][k]), vp(s["params"][k]), _lib.ptr(s["seed"]),
                 vp(nxt[0]), vp(nxt[1]), NM3, _lib.ptr(s["nonfinite"]), st), "egx_primitive_advance_select")
+
+    def _beam_loop(self, K, b, W, N, s):
+        """The primitive loop of the beam search and the backtrack after it: launches only, no allocation that depends on k, no
+        host wait.  R0 / T0 and the seed frames are read from one buffer and written to the other: a slot may continue from a row
+        of another slot of its sequence."""
+        lib, bm = _lib.load(), self.body_model
+        st = _lib.current_stream_ptr()
+        BN = b * W * N
+        lbs, scene = s["lbs_out"], s["scene"]
+        vp = lambda t: C.c_void_p(t.data_ptr())
+        for k in range(K):
+            cur, nxt = s["xs"][k % 2], s["xs"][(k + 1) % 2]
+            R0, T0, R0n, T0n = s["R0s"][k % 2], s["T0s"][k % 2], s["R0s"][(k + 1) % 2], s["T0s"][(k + 1) % 2]
+            self.model.sample_prior_into(cur[0], cur[1], NM3, s["bt"], s["z"][k], s["Y_gen"], s["Yb_gen"])
+            _lib.check(lib.egx_assemble_params(_lib.ptr(s["seed"]), _lib.ptr(s["Yb_gen"]), BN, _lib.ptr(s["pp"]), st), "egx_assemble_params")
+            if scene is None:
+                bm.forward(s["pp"].view(BN * T_ALL, XB), s["bt"], T_ALL, want_verts=False, want_joints=True, want_markers=True, out=lbs)
+            else:
+                bm.forward(s["pp"].view(BN * T_ALL, XB), s["bt"], T_ALL, want_verts=False, want_joints=True, want_markers=True, out=lbs,
+                           sdf=scene, R0=R0, T0=T0, agent_scene=s["rows_scene"])
+            _lib.check(lib.egx_primitive_beam_select(
+                _lib.ptr(s["Y_gen"]), vp(cur[0]), vp(cur[1]), NM3, _lib.ptr(lbs["joints"]), 127, _lib.ptr(lbs["markers"]),
+                _lib.ptr(R0), _lib.ptr(T0), _lib.ptr(lbs.get("pene_count")), _lib.ptr(s["goal"]), _lib.ptr(s["feet"]),
+                s["weights"], s["pene_thres"], s["goal_thresh"], s["rf"], b, W, N, vp(s["acc"][k]), vp(s["ncoll"][k]),
+                vp(s["cost"][k]), vp(s["cost_terms"][k]), vp(s["colliding"][k]), vp(s["beam_row"][k]), vp(s["parent"][k]),
+                vp(s["acc"][k + 1]), vp(s["ncoll"][k + 1]), vp(s["path_cost"][k]), vp(s["beam_status"][k]), vp(s["slot_goal_dist"][k]),
+                vp(s["slot_reached"][k]), st), "egx_primitive_beam_select")
+            _lib.check(lib.egx_primitive_advance_beam(
+                _lib.ptr(s["pp"]), _lib.ptr(s["Y_gen"]), vp(cur[0]), vp(cur[1]), NM3, _lib.ptr(lbs["joints"]), 127,
+                _lib.ptr(lbs["markers"]), _lib.ptr(s["delta_T"]), s["rf"], b, W, N, vp(s["beam_row"][k]), _lib.ptr(R0), _lib.ptr(T0),
+                _lib.ptr(R0n), _lib.ptr(T0n), vp(s["rec_markers"][k]), vp(s["rec_pelvis"][k]), vp(s["rec_rotmat"][k]),
+                vp(s["rec_transl"][k]), vp(s["rec_params"][k]), _lib.ptr(s["seed"]), vp(nxt[0]), vp(nxt[1]), NM3,
+                vp(s["beam_status"][k]), st), "egx_primitive_advance_beam")
+        _lib.check(lib.egx_beam_backtrack(
+            _lib.ptr(s["parent"]), _lib.ptr(s["beam_row"]), _lib.ptr(s["beam_status"]), _lib.ptr(s["slot_goal_dist"]),
+            _lib.ptr(s["slot_reached"]), _lib.ptr(s["rec_markers"]), _lib.ptr(s["rec_pelvis"]), _lib.ptr(s["rec_rotmat"]),
+            _lib.ptr(s["rec_transl"]), _lib.ptr(s["rec_params"]), K, b, W, _lib.ptr(s["path_slot"]), _lib.ptr(s["choice"]),
+            _lib.ptr(s["status"]), _lib.ptr(s["goal_dist"]), _lib.ptr(s["reached"]), _lib.ptr(s["markers"]), _lib.ptr(s["pelvis"]),
+            _lib.ptr(s["rotmat"]), _lib.ptr(s["transl"]), _lib.ptr(s["params"]), st), "egx_beam_backtrack")
 
     # ------------------------------------------------------------------------------------------------------------------
     def _compose_body_params_(self, data):

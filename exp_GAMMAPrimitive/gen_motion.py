@@ -7,6 +7,8 @@
 With `--goal x,y,z` (world coordinates) the variants are steered there by `generate_sequence_to_goal`: `--n-candidates N` candidates
 per primitive and variant, the best one kept (greedy best-of-N on the env's reward arguments), optionally through the SDF scene
 `--scene file.npz` (keys sdf, center, scale: the reference's sdf_dict); a file stops at the primitive that reaches the goal.
+`--beam-width W` (default 1: greedy) keeps the best W partial paths per variant instead of one, each expanded into N candidates
+(W <= 32, W * N <= 256), and writes the path that ends in the best one.
 
 `--cfg <name>` is the combo config (`crowd_ppo/cfg_samp20/<name>.yml` under the working directory, else the packaged copy): it
 names the predictor's and the regressor's configs, whose checkpoints are read from `results/crowd_ppo/<config>/checkpoints`
@@ -44,10 +46,13 @@ def main(argv=None):
     parser.add_argument("--start-frame", type=int, default=5)
     parser.add_argument("--goal", default=None, help="x,y,z in world coordinates: steer every variant there (best-of-N search)")
     parser.add_argument("--n-candidates", type=int, default=16, help="candidates per primitive and variant (with --goal)")
+    parser.add_argument("--beam-width", type=int, default=1, help="partial paths kept per variant (with --goal); 1 = greedy best-of-N")
     parser.add_argument("--scene", default=None, help="npz with sdf, center, scale: penalise and avoid penetration (with --goal)")
     args = parser.parse_args(argv)
     if args.goal is None and args.scene is not None:
         parser.error("--scene needs --goal")
+    if args.goal is None and args.beam_width != 1:
+        parser.error("--beam-width needs --goal")
     if not torch.cuda.is_available():
         raise SystemExit("gen_motion needs a HIP device: the MI355X path has no CPU fallback")
     np.random.seed(args.seed)
@@ -96,7 +101,8 @@ def main(argv=None):
             with np.load(args.scene) as f:
                 scene = SdfScene({k: f[k] for k in ("sdf", "center", "scale")})
         res = op.generate_sequence_to_goal(data.repeat(args.n_gens, 1), bparams.repeat(args.n_gens, 1), can["betas"].astype(np.float32),
-                                           goal, args.n_primitives, args.n_candidates, scene=scene, R0=R0, T0=T0)
+                                           goal, args.n_primitives, args.n_candidates, scene=scene, R0=R0, T0=T0,
+                                           beam_width=args.beam_width)
         for i in range(args.n_gens):
             print("[INFO] variant {}: {} primitives, final distance to the goal {:.3f} m, colliding choices {}".format(
                 i, int(res.n_valid[i]), float(res.goal_dist[int(res.n_valid[i]) - 1, i]), int((res.status[:int(res.n_valid[i]), i] & 1).sum())))

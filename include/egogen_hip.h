@@ -33,6 +33,7 @@ extern "C" {
 #define EGX_NUM_JOINTS_OUT 127 /* 55 + 21 vertex joints + 51 landmarks   */
 #define EGX_XB_DIM 93          /* transl3 glorot3 body63 lhand12 rhand12 */
 #define EGX_MAX_CANDIDATES 256 /* candidates per sequence of egx_primitive_select */
+#define EGX_MAX_BEAM 32        /* beam slots per sequence of egx_primitive_beam_select; slots * candidates <= EGX_MAX_CANDIDATES */
 #define EGX_NUM_BETAS 10
 #define EGX_POSE_FEAT 486
 #define EGX_BLEND_K 472        /* GEMM K: 10 betas + 9 x 51 movable joints = 469, padded to 8 (jaw/eyes are always identity here) */
@@ -842,6 +843,49 @@ int egx_primitive_advance_select(const float* pred_params, const float* Y_gen, c
                                  float* T0, float* out_marker_b, float* out_pelvis, float* out_R, float* out_T, float* out_params,
                                  float* out_seed_params, float* out_x0, float* out_x1, int out_x_ld, int32_t* nonfinite,
                                  void* stream);
+
+/* Beam search over motion primitives: per sequence i, beam_width (W) slots, each expanded into num_candidates (N) rows;
+ * row r = (i * W + s) * N + n is candidate n of slot s.  1 <= W <= EGX_MAX_BEAM and W * N <= EGX_MAX_CANDIDATES.
+ *
+ * egx_primitive_beam_select - one workgroup per sequence scores its W * N rows with the row scoring of egx_primitive_select (the
+ * same bits for cost [rows], cost_terms [rows,5], colliding [rows] on the same rows) and q = w_skate skate + w_floor floor + w_pene pene
+ * + w_face face (the cost without its goal term, summed on its own).  acc [b,W] / ncoll [b,W]: sum of q and number of colliding nodes
+ * on the path into each slot (zeros at depth 0).  Path key of a row with parent slot s = r / N: (nonfinite, ncoll[s] + colliding,
+ * acc[s] + cost, r), compared lexicographically, a total order; a row with a non-finite cost, term or acc[s] + cost has
+ * nonfinite = 1 and 0 for its cost in the key.  The W smallest keys go to slots 0 (best) .. W-1, per slot: beam_row (row within the
+ * sequence's W * N), parent = beam_row / N, acc_out = acc[parent] + q, ncoll_out = ncoll[parent] + colliding, path_cost (the key's
+ * cost), beam_status (bit 0: the node collides, bit 1: non-finite), goal_dist, reached = goal_dist < goal_thresh, all [b,W].  acc_out /
+ * ncoll_out must be other buffers than acc / ncoll.  No float atomics; a sequence's outputs are the same bits in any batch. */
+int egx_primitive_beam_select(const float* Y_gen, const float* x0, const float* x1, int x_ld, const float* joints,
+                              int joints_per_body, const float* markers_proj, const float* R0, const float* T0,
+                              const int32_t* pene_count, const float* goal, const int32_t* feet_marker_idx, const float* weights,
+                              float pene_thres, float goal_thresh, float reproj_factor, int num_sequences, int beam_width,
+                              int num_candidates, const float* acc, const int32_t* ncoll, float* cost, float* cost_terms,
+                              int32_t* colliding, int32_t* beam_row, int32_t* parent, float* acc_out, int32_t* ncoll_out,
+                              float* path_cost, int32_t* beam_status, float* goal_dist, int32_t* reached, void* stream);
+
+/* egx_primitive_advance_beam - the hand-off of egx_primitive_advance from every kept row: workgroup (i, s) reads the per-row inputs
+ * at row i * W * N + beam_row[i,s] (clamped into the sequence's rows), writes the records to row (i, s) of [b,W,...] buffers
+ * (out_params may be NULL) and the next state to the N rows of slot s.  Slot s' may read a row that slot s writes, so R0 / T0 are
+ * read from one pair of buffers and written to another (R0_out / T0_out), as the seed frames are (x0 / x1 -> out_x0 / out_x1); the
+ * caller swaps them from primitive to primitive.  A non-finite handed-on value sets bit 2 of beam_status[i,s]; there is no counter.
+ * With W = 1 the same bits as egx_primitive_advance_select. */
+int egx_primitive_advance_beam(const float* pred_params, const float* Y_gen, const float* x0, const float* x1, int x_ld,
+                               const float* joints, int joints_per_body, const float* markers_proj, const float* delta_T,
+                               float reproj_factor, int num_sequences, int beam_width, int num_candidates, const int32_t* beam_row,
+                               const float* R0, const float* T0, float* R0_out, float* T0_out, float* out_marker_b,
+                               float* out_pelvis, float* out_R, float* out_T, float* out_params, float* out_seed_params,
+                               float* out_x0, float* out_x1, int out_x_ld, int32_t* beam_status, void* stream);
+
+/* egx_beam_backtrack - the returned path: it ends in slot 0 of depth num_primitives - 1 and follows parent [K,b,W] back to depth 0.
+ * Workgroup (k, i) copies the records of the path's slot at depth k (per slot [K,b,W,...]: beam_row, beam_status, goal_dist, reached
+ * of the selection; marker_b, pelvis, R, T, params of the hand-off) into row (k, i) of the [K,b,...] outputs and writes
+ * path_slot [K,b].  The marker and parameter buffers must be 16-byte aligned. */
+int egx_beam_backtrack(const int32_t* parent, const int32_t* beam_row, const int32_t* beam_status, const float* goal_dist,
+                       const int32_t* reached, const float* rec_marker_b, const float* rec_pelvis, const float* rec_R,
+                       const float* rec_T, const float* rec_params, int num_primitives, int num_sequences, int beam_width,
+                       int32_t* path_slot, int32_t* choice, int32_t* status, float* out_goal_dist, int32_t* out_reached,
+                       float* out_marker_b, float* out_pelvis, float* out_R, float* out_T, float* out_params, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * PPO rollout glue

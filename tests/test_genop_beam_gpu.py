@@ -1,0 +1,657 @@
+"""GPU checks of the beam search over motion primitives: kernels egx_primitive_beam_select, egx_primitive_advance_beam and
+egx_beam_backtrack (csrc/genop.hip) and `GAMMAPrimitiveComboGenOP.generate_sequence_to_goal(..., beam_width=W)`.
+
+Yardsticks.  Values: `held()` of tests/test_genop_gpu.py (R = 3 against the float32 restatement's own distance from float64,
+tests/genop_beam_ref.py on tests/genop_search_ref.py::score), at least 64 rows pooled per case as in tests/test_genop_search_gpu.py.
+Slots: equal to the float64 selection for every DECIDABLE group - one in which every adjacent gap among the float64 top W + 1 keys
+of equal (nonfinite, ncoll) exceeds 6 x the group's largest |path_cost32 - path_cost64| (3 x for each of the two costs compared);
+at most 5 % of the groups are undecidable, a property of the inputs that is printed.  Everything else (flags, counts, parents,
+status bits, the hand-off against egx_primitive_advance, the backtrack against the host walk) is exact."""
+import ctypes as C
+import os
+import pickle
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+from tests import genop_beam_ref as bref, genop_search_ref as sref
+from tests.test_genop_beam_cpu import GOAL_ONLY, beam_cases
+from tests.test_genop_gpu import CFG_RF, ROOT, V_SMALL, _aa2R64, _inputs, _launch, emit, held, small_world  # noqa: F401
+from tests.test_genop_search_gpu import (MIN_GROUP, POOL, UNDECIDABLE_CAP, W_ORDER, W_TEST, _advance_select, _feet, _handmade, _restate,
+                                         _rows_inputs, _select, search_world)  # noqa: F401
+
+pytestmark = pytest.mark.gpu
+
+SELECT_CASES = [(1, 1, 1), (1, 2, 1), (1, 2, 3), (3, 4, 5), (2, 4, 64), (65, 2, 5), (1, 16, 16)]       # (b, W, N)
+SLOT_OUT = ("beam_row", "parent", "acc", "ncoll", "path_cost", "status", "goal_dist", "reached")
+
+
+def _slot_state(b, W, seed):
+    """random non-zero acc [b,W] (float32) and ncoll [b,W] of the paths into the slots"""
+    g = torch.Generator().manual_seed(seed)
+    return torch.rand(b, W, generator=g) * 2.0 + 0.01, torch.randint(0, 3, (b, W), generator=g).int()
+
+
+def _beam_select(x, W, N, jpb, acc=None, ncoll=None, rf=CFG_RF, weights=W_TEST, pene_thres=40.0, goal_thresh=0.1, nan_face_rows=(), b=None,
+                 group0=0):
+    """egx_primitive_beam_select on the groups [group0, group0 + b) of the row set x (W * N rows each) -> (outputs, inputs as
+    launched); the inputs are built as tests/test_genop_search_gpu.py::_select builds them"""
+    from egogen_amd import _lib
+    lib = _lib.load()
+    b = x["b"] if b is None else b
+    M = W * N
+    assert x["N"] == M
+    sl = slice(group0 * M, (group0 + b) * M)
+    rows = x["rows"][sl].cuda()
+    d = x["pool"]
+    n = b * M
+    per = lambda t: t.reshape(POOL, 20, *t.shape[1:])[rows].reshape(n * 20, *t.shape[1:]).contiguous()
+    Yg = d["Y_gen"][:, rows].contiguous()
+    X = d["X"][:, rows].contiguous()
+    J = per(d["j127"] if jpb == 127 else d["j55"])
+    for r in nan_face_rows:
+        J.view(n, 20, jpb, 3)[r, 19, 2, 0] = float("nan")
+    mp = per(d["mproj"])
+    R0, T0 = x["R0"][sl].cuda().contiguous(), x["T0"][sl].cuda().contiguous()
+    goal = x["goal"][group0:group0 + b].cuda().contiguous()
+    pene = None if x["pene"] is None else x["pene"][sl].cuda().reshape(-1).contiguous()
+    feet = torch.tensor(_feet(), dtype=torch.int32, device="cuda")
+    acc = torch.zeros(b, W) if acc is None else acc
+    ncoll = torch.zeros(b, W, dtype=torch.int32) if ncoll is None else ncoll
+    acc_d, ncoll_d = acc.float().cuda().contiguous(), ncoll.int().cuda().contiguous()
+    fi = lambda *s: torch.full(s, -7, dtype=torch.int32, device="cuda")
+    ff = lambda *s: torch.full(s, float("nan"), device="cuda")
+    o = {"cost": ff(b, M), "terms": ff(b, M, 5), "colliding": fi(b, M), "beam_row": fi(b, W), "parent": fi(b, W), "acc": ff(b, W),
+         "ncoll": fi(b, W), "path_cost": ff(b, W), "status": fi(b, W), "goal_dist": ff(b, W), "reached": fi(b, W)}
+    w = (C.c_float * 5)(*[weights[k] for k in W_ORDER])
+    _lib.check(lib.egx_primitive_beam_select(
+        _lib.ptr(Yg), C.c_void_p(X[0].data_ptr()), C.c_void_p(X[1].data_ptr()), 201, _lib.ptr(J), jpb, _lib.ptr(mp), _lib.ptr(R0),
+        _lib.ptr(T0), _lib.ptr(pene), _lib.ptr(goal), _lib.ptr(feet), w, float(pene_thres), float(goal_thresh), float(rf), b, W, N,
+        _lib.ptr(acc_d), _lib.ptr(ncoll_d), _lib.ptr(o["cost"]), _lib.ptr(o["terms"]), _lib.ptr(o["colliding"]), _lib.ptr(o["beam_row"]),
+        _lib.ptr(o["parent"]), _lib.ptr(o["acc"]), _lib.ptr(o["ncoll"]), _lib.ptr(o["path_cost"]), _lib.ptr(o["status"]),
+        _lib.ptr(o["goal_dist"]), _lib.ptr(o["reached"]), _lib.current_stream_ptr()), "egx_primitive_beam_select")
+    torch.cuda.synchronize()
+    i = {"Y_gen": Yg, "X": X, "J": J.reshape(n, 20, jpb, 3), "mp": mp.reshape(n, 20, 67, 3), "R0": R0, "T0": T0,
+         "goal_rows": goal.repeat_interleave(M, 0), "pene": None if pene is None else pene.reshape(n, 20)}
+    return {k: v.cpu() for k, v in o.items()}, i
+
+
+def beam_decidable(cost64, terms64, coll, acc, ncoll, W, N, cost32, acc64=None):
+    """[b] bool: among the float64 top W + 1 keys every adjacent pair of equal (nonfinite, ncoll) lies further apart than
+    6 x max_rows |path_cost32 - path_cost64|; acc is the float32 table (the float64 side reads the same values unless it has a
+    table of its own, acc64)"""
+    nf, nc, p64 = bref.path_keys(cost64, terms64, coll, acc.double() if acc64 is None else acc64, ncoll, W, N)
+    _, _, p32 = bref.path_keys(cost32, torch.zeros(*cost32.shape, 5), coll, acc.float(), ncoll, W, N)
+    b, M = cost64.shape
+    ok = torch.ones(b, dtype=torch.bool)
+    for g in range(b):
+        keys = sorted((int(nf[g, r]), int(nc[g, r]), float(p64[g, r]), r) for r in range(M))[:W + 1]
+        err = float((p32[g].double() - p64[g]).abs().max())
+        for a, c in zip(keys[:-1], keys[1:]):
+            if a[:2] == c[:2] and not a[0] and not (c[2] - a[2] > 6.0 * err):
+                ok[g] = False
+    return ok
+
+
+def _own_rules(o, acc, ncoll, W, N, weights=W_TEST):
+    """the kernel's slots are the rule applied to the kernel's own costs: exact"""
+    own = bref.beam_select(o["cost"], o["terms"], o["colliding"].bool(), acc, ncoll, W, N, weights)
+    for k in ("beam_row", "parent", "ncoll", "status"):
+        assert torch.equal(own[k], o[k].long()), (k, own[k], o[k])
+    assert torch.equal(own["path_cost"], o["path_cost"])
+    br = o["beam_row"].long()
+    assert int(br.min()) >= 0 and int(br.max()) < W * N
+    assert torch.equal(o["goal_dist"], o["terms"][..., 0].gather(1, br))
+    assert torch.equal(o["reached"].bool(), o["goal_dist"] < 0.1)
+
+
+@pytest.mark.parametrize("with_pene", [True, False])
+@pytest.mark.parametrize("jpb", [127, 55])
+@pytest.mark.parametrize("b,W,N", SELECT_CASES)
+def test_beam_select_kernel(small_world, b, W, N, jpb, with_pene):
+    M = W * N
+    name = f"beam select b={b} W={W} N={N} jpb={jpb} pene={int(with_pene)}"
+    got, r64, r32, oks = [], [], [], []
+    for draw in range(max(1, -(-MIN_GROUP // (b * M)))):
+        x = _rows_inputs(small_world, b, M, 200 + b * 7 + M + 1000 * draw, with_pene)
+        acc, ncoll = _slot_state(b, W, 5 + draw)
+        o, i = _beam_select(x, W, N, jpb, acc, ncoll)
+        c64, t64, coll = _restate(i, b, M, CFG_RF, W_TEST, 40.0, torch.float64)
+        c32, t32, coll32 = _restate(i, b, M, CFG_RF, W_TEST, 40.0, torch.float32)
+        assert torch.equal(o["colliding"].bool(), coll) and torch.equal(coll32, coll)
+        s64 = bref.beam_select(c64, t64, coll, acc.double(), ncoll, W, N, W_TEST)
+        s32 = bref.beam_select(c32, t32, coll, acc, ncoll, W, N, W_TEST)
+        ok = beam_decidable(c64, t64, coll, acc, ncoll, W, N, c32)
+        oks.append(ok)
+        for k in ("beam_row", "parent", "ncoll", "status"):
+            assert torch.equal(s32[k][ok], s64[k][ok]), k       # the float32 restatement itself decides those groups alike
+            assert torch.equal(o[k].long()[ok], s64[k][ok]), (name, draw, k, o[k], s64[k])
+        _own_rules(o, acc, ncoll, W, N)
+        # the carried values on the kernel's own slots, held like the terms
+        br = o["beam_row"].long()
+        on_slots = lambda c, t, a: (bref.path_keys(c, t, coll, a, ncoll, W, N)[2].gather(1, br),
+                                    a.gather(1, br // N) + bref.q_of(t, W_TEST).gather(1, br))
+        got.append((o["cost"], o["terms"], o["path_cost"], o["acc"]))
+        r64.append((c64, t64) + on_slots(c64, t64, acc.double()))
+        r32.append((c32, t32) + on_slots(c32, t32, acc))
+    cat = lambda lst, j: torch.cat([v[j] for v in lst], 0)
+    for k, term in enumerate(sref.TERMS):
+        held(name, term, cat(got, 1)[..., k], cat(r64, 1)[..., k], cat(r32, 1)[..., k])
+    for j, what in ((0, "cost"), (2, "path_cost"), (3, "acc")):
+        held(name, what, cat(got, j), cat(r64, j), cat(r32, j))
+    ok = torch.cat(oks)
+    share = 1.0 - float(ok.float().mean())
+    emit(f"| {name} | undecidable groups | {int((~ok).sum())} of {ok.numel()} | {share:.3f} | |")
+    assert share <= UNDECIDABLE_CAP, (name, share)
+
+
+@pytest.mark.parametrize("name", list(beam_cases()))
+def test_beam_select_handmade_cases(small_world, name):
+    W, N, costs, coll, nan_rows, acc, ncoll, want_rows, want_ncoll, want_status = beam_cases()[name]
+    x = _handmade(small_world, costs, coll)
+    acc, ncoll = torch.tensor([acc]), torch.tensor([ncoll], dtype=torch.int32)
+    o, _ = _beam_select(x, W, N, 127, acc, ncoll, weights=GOAL_ONLY, nan_face_rows=nan_rows)
+    assert o["colliding"][0].tolist() == list(coll)
+    _own_rules(o, acc, ncoll, W, N, GOAL_ONLY)
+    assert o["ncoll"][0].tolist() == [int(ncoll[0, r // N]) + coll[r] for r in o["beam_row"][0].tolist()]
+    if "tie across parents" not in name:        # there the table's tie is exact, the device's distances are rounded: rule only
+        assert o["beam_row"][0].tolist() == want_rows and o["ncoll"][0].tolist() == want_ncoll, (name, o["beam_row"], o["cost"])
+        assert o["status"][0].tolist() == want_status and o["parent"][0].tolist() == [r // N for r in want_rows]
+
+
+@pytest.mark.parametrize("with_pene", [True, False])
+@pytest.mark.parametrize("jpb", [127, 55])
+@pytest.mark.parametrize("b,N", [(3, 5), (2, 70)])
+def test_beam_select_with_one_slot_is_the_greedy_select(small_world, b, N, jpb, with_pene):
+    x = _rows_inputs(small_world, b, N, 77 + N, with_pene)
+    want, _ = _select(x, jpb)
+    got, _ = _beam_select(x, 1, N, jpb)
+    for k in ("cost", "terms", "colliding"):
+        assert torch.equal(got[k], want[k]), k
+    assert torch.equal(got["beam_row"][:, 0], want["choice"]) and torch.equal(got["status"][:, 0], want["status"])
+    assert torch.equal(got["goal_dist"][:, 0], want["goal_dist"]) and torch.equal(got["reached"][:, 0], want["reached"])
+    assert torch.equal(got["path_cost"][:, 0], want["cost"].gather(1, want["choice"].long()[:, None])[:, 0])
+    assert not got["parent"].any()
+
+
+def test_beam_select_group_does_not_depend_on_batch(small_world):
+    b, W, N = 65, 2, 5
+    x = _rows_inputs(small_world, b, W * N, 31, True)
+    acc, ncoll = _slot_state(b, W, 9)
+    full, _ = _beam_select(x, W, N, 127, acc, ncoll)
+    for g in (0, 33, 64):
+        one, _ = _beam_select(x, W, N, 127, acc[g:g + 1], ncoll[g:g + 1], b=1, group0=g)
+        for k in ("cost", "terms", "colliding") + SLOT_OUT:
+            assert torch.equal(one[k][0], full[k][g]), (g, k)
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+def _advance_beam(d, rows, beam_row, W, N, jpb, rf, status=None, nan_rows=()):
+    """egx_primitive_advance_beam on the rows `rows` (b * W * N pool rows) of the input set d; beam_row [b,W]"""
+    from egogen_amd import _lib
+    lib = _lib.load()
+    rows = torch.as_tensor(rows, device="cuda")
+    n = int(rows.numel())
+    b = n // (W * N)
+    sel = lambda t, per=1: t.reshape(-1, per, *t.shape[1:])[rows].reshape(n * per, *t.shape[1:]).contiguous()
+    pp, Yg, X = d["pp"][rows].contiguous(), d["Y_gen"][:, rows].contiguous(), d["X"][:, rows].contiguous()
+    J, mp, dT = sel(d["j127"] if jpb == 127 else d["j55"], 20), sel(d["mproj"], 20), d["delta_T"][rows].contiguous()
+    for r in nan_rows:
+        J.view(n, 20, jpb, 3)[r, 5, 0, 1] = float("nan")
+    R0, T0 = d["R0"][rows].clone().contiguous(), d["T0"][rows].clone().contiguous()
+    keep = (R0.clone(), T0.clone())
+    br = torch.as_tensor(beam_row, dtype=torch.int32, device="cuda").reshape(b, W).contiguous()
+    st = torch.zeros(b, W, dtype=torch.int32, device="cuda") if status is None else status.int().cuda().contiguous()
+    f = lambda *s: torch.full(s, float("nan"), device="cuda")
+    o = {"marker_b": f(b * W, 20, 67, 3), "pelvis": f(b * W, 20, 3), "R": f(b * W, 3, 3), "T": f(b * W, 3), "params": f(b * W, 20, 93),
+         "seed_params": f(n, 2, 93), "seed_markers": f(2, n, 201), "R0": f(n, 3, 3), "T0": f(n, 3)}
+    _lib.check(lib.egx_primitive_advance_beam(
+        _lib.ptr(pp), _lib.ptr(Yg), C.c_void_p(X[0].data_ptr()), C.c_void_p(X[1].data_ptr()), 201, _lib.ptr(J), jpb, _lib.ptr(mp),
+        _lib.ptr(dT), float(rf), b, W, N, _lib.ptr(br), _lib.ptr(R0), _lib.ptr(T0), _lib.ptr(o["R0"]), _lib.ptr(o["T0"]),
+        _lib.ptr(o["marker_b"]), _lib.ptr(o["pelvis"]), _lib.ptr(o["R"]), _lib.ptr(o["T"]), _lib.ptr(o["params"]), _lib.ptr(o["seed_params"]),
+        C.c_void_p(o["seed_markers"][0].data_ptr()), C.c_void_p(o["seed_markers"][1].data_ptr()), 201, _lib.ptr(st),
+        _lib.current_stream_ptr()), "egx_primitive_advance_beam")
+    torch.cuda.synchronize()
+    assert torch.equal(R0, keep[0]) and torch.equal(T0, keep[1])          # the input frames are only read
+    o.update(status=st, seed_markers=o["seed_markers"].permute(1, 0, 2).contiguous())
+    return o
+
+
+def _check_handoff(d, rows, beam_row, W, N, jpb):
+    rows = torch.as_tensor(rows)
+    b = rows.numel() // (W * N)
+    br = torch.as_tensor(beam_row).reshape(b, W)
+    chosen = rows.reshape(b, W * N).gather(1, br).reshape(-1)
+    want = _launch(d, chosen.tolist(), jpb, CFG_RF)
+    got = _advance_beam(d, rows.tolist(), br, W, N, jpb, CFG_RF)
+    for k in ("marker_b", "pelvis", "R", "T"):
+        assert torch.equal(got[k], want[k]), k
+    assert torch.equal(got["params"], d["pp"][chosen.cuda()])
+    for k in ("R0", "T0", "seed_params", "seed_markers"):       # every kept row's next state in the N rows of its slot
+        assert torch.equal(got[k], want[k].repeat_interleave(N, 0)), k
+    assert not got["status"].any()
+    return got
+
+
+@pytest.mark.parametrize("jpb", [127, 55])
+@pytest.mark.parametrize("N", [1, 3])
+@pytest.mark.parametrize("b", [1, 3])
+def test_advance_beam_slots_take_each_others_rows(small_world, b, N, jpb):
+    """Slot 0 continues from a row of slot 1 and slot 1 from a row of slot 0: with R0 / T0 updated in place the second to run would
+    read what the first wrote.  Then both slots from the same row."""
+    d = _inputs(small_world, POOL)
+    W = 2
+    rows = torch.randperm(POOL, generator=torch.Generator().manual_seed(b * 10 + N))[:b * W * N]      # R0 / T0 differ from row to row
+    crossed = [[N + (i % N), (i + N - 1) % N] for i in range(b)]
+    _check_handoff(d, rows, crossed, W, N, jpb)
+    _check_handoff(d, rows, [[(i + 1) % (W * N)] * 2 for i in range(b)], W, N, jpb)
+
+
+@pytest.mark.parametrize("jpb", [127, 55])
+def test_advance_beam_random_rows(small_world, jpb):
+    d = _inputs(small_world, POOL)
+    b, W, N = 13, 4, 1
+    g = torch.Generator().manual_seed(6)
+    rows = torch.randperm(POOL, generator=g)[:b * W * N]
+    br = torch.randint(0, W * N, (b, W), generator=g)
+    assert (br != torch.arange(W)).any() and any(len(set(r)) < W for r in br.tolist())
+    _check_handoff(d, rows, br, W, N, jpb)
+    # a row outside the sequence's rows is clamped, never followed
+    lo = _advance_beam(d, rows.tolist(), torch.full((b, W), -3), W, N, jpb, CFG_RF)
+    hi = _advance_beam(d, rows.tolist(), torch.full((b, W), W * N + 2), W, N, jpb, CFG_RF)
+    first, last = rows.reshape(b, W * N)[:, 0].repeat_interleave(W), rows.reshape(b, W * N)[:, -1].repeat_interleave(W)
+    assert torch.equal(lo["pelvis"], _launch(d, first.tolist(), jpb, CFG_RF)["pelvis"])
+    assert torch.equal(hi["pelvis"], _launch(d, last.tolist(), jpb, CFG_RF)["pelvis"])
+
+
+@pytest.mark.parametrize("jpb", [127, 55])
+def test_advance_beam_with_one_slot_is_the_advance_select(small_world, jpb):
+    d = _inputs(small_world, POOL)
+    N, b = 5, 13
+    g = torch.Generator().manual_seed(5)
+    choice = torch.randint(0, N, (b,), generator=g)
+    rows = torch.randperm(POOL, generator=g)
+    want = _advance_select(d, rows.tolist(), choice.tolist(), N, jpb, CFG_RF)
+    got = _advance_beam(d, rows.tolist(), choice[:, None], 1, N, jpb, CFG_RF)
+    for k in ("marker_b", "pelvis", "R", "T", "params", "R0", "T0", "seed_params", "seed_markers"):
+        assert torch.equal(got[k], want[k]), k
+
+
+def test_advance_beam_marks_the_nonfinite_slot_only(small_world):
+    d = _inputs(small_world, POOL)
+    b, W, N = 2, 3, 2
+    rows = list(range(b * W * N))
+    br = torch.tensor([[0, 3, 5], [4, 4, 1]])
+    before = torch.tensor([[1, 0, 2], [3, 0, 1]])                 # what the selection left: kept, bit 2 added
+    got = _advance_beam(d, rows, br, W, N, 127, CFG_RF, status=before, nan_rows=(W * N + 1, 3))       # rows of slots (1,2) and (0,1)
+    want = before.clone()
+    want[1, 2] |= 4
+    want[0, 1] |= 4
+    assert torch.equal(got["status"].cpu(), want.int())
+    clean = _advance_beam(d, rows, br, W, N, 127, CFG_RF, status=before)
+    assert torch.equal(clean["status"].cpu(), before.int())
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("b", [1, 5])
+@pytest.mark.parametrize("K", [1, 4])
+def test_beam_backtrack_kernel(K, b):
+    from egogen_amd import _lib
+    lib = _lib.load()
+    W = 3
+    g = torch.Generator().manual_seed(K * 10 + b)
+    parent = torch.randint(0, W, (K, b, W), generator=g).int()
+    ri = lambda: torch.randint(0, 1000, (K, b, W), generator=g).int()
+    rec = {"beam_row": ri(), "status": ri(), "goal_dist": torch.randn(K, b, W, generator=g), "reached": ri(),
+           "marker_b": torch.randn(K, b, W, 20, 67, 3, generator=g), "pelvis": torch.randn(K, b, W, 20, 3, generator=g),
+           "R": torch.randn(K, b, W, 3, 3, generator=g), "T": torch.randn(K, b, W, 3, generator=g), "params": torch.randn(K, b, W, 20, 93, generator=g)}
+    dv = {k: v.cuda().contiguous() for k, v in rec.items()}
+    par = parent.cuda().contiguous()
+    out = {k: torch.full((K, b) + tuple(v.shape[3:]), -7, dtype=v.dtype, device="cuda") for k, v in rec.items()}
+    slot = torch.full((K, b), -7, dtype=torch.int32, device="cuda")
+    p = _lib.ptr
+    _lib.check(lib.egx_beam_backtrack(p(par), p(dv["beam_row"]), p(dv["status"]), p(dv["goal_dist"]), p(dv["reached"]), p(dv["marker_b"]),
+                                      p(dv["pelvis"]), p(dv["R"]), p(dv["T"]), p(dv["params"]), K, b, W, p(slot), p(out["beam_row"]),
+                                      p(out["status"]), p(out["goal_dist"]), p(out["reached"]), p(out["marker_b"]), p(out["pelvis"]),
+                                      p(out["R"]), p(out["T"]), p(out["params"]), _lib.current_stream_ptr()), "egx_beam_backtrack")
+    torch.cuda.synchronize()
+    want = bref.backtrack(parent, K)
+    assert torch.equal(slot.cpu().long(), want)
+    if K > 1 and b > 1:
+        assert len(set(want[:-1].reshape(-1).tolist())) > 1
+    for k, v in rec.items():
+        idx = want.view(K, b, 1, *([1] * (v.dim() - 3))).expand(K, b, 1, *v.shape[3:])
+        assert torch.equal(out[k].cpu(), v.gather(2, idx)[:, :, 0]), k
+
+
+def test_beam_kernels_reject_bad_arguments(small_world):
+    """Rejected before anything is launched: every pointer may therefore be the same scratch buffer (two, where an entry wants its
+    output elsewhere than its input)."""
+    from egogen_amd import _lib
+    lib = _lib.load()
+    buf, buf2 = torch.zeros(16384, device="cuda"), torch.zeros(16384, device="cuda")
+    p, p2, off = C.c_void_p(buf.data_ptr()), C.c_void_p(buf2.data_ptr()), C.c_void_p(buf.data_ptr() + 4)
+    w = (C.c_float * 5)(1, 1, 1, 1, 0)
+    st = _lib.current_stream_ptr()
+
+    def sel(goal=p, jpb=127, x_ld=201, B=1, W=1, N=1, weights=w, acc=p, acc_out=p2, ncoll_out=p2, beam_row=p):
+        return lib.egx_primitive_beam_select(p, p, p, x_ld, p, jpb, p, p, p, None, goal, p, weights, 40.0, 0.1, 0.5, B, W, N, acc, p, p, p, p,
+                                             beam_row, p, acc_out, ncoll_out, p, p, p, p, st)
+
+    def adv(mproj=p, jpb=127, x_ld=201, B=1, W=1, N=1, out_marker=p, beam_row=p, R0_out=p2, T0_out=p2, x0_out=p2, x1_out=p2, status=p):
+        return lib.egx_primitive_advance_beam(p, p, p, p, x_ld, p, jpb, mproj, p, 0.5, B, W, N, beam_row, p, p, R0_out, T0_out, out_marker, p, p,
+                                              p, None, p, x0_out, x1_out, 201, status, st)
+
+    def back(parent=p, K=1, B=1, W=1, rec_marker=p, out_params=p, slot=p):
+        return lib.egx_beam_backtrack(parent, p, p, p, p, rec_marker, p, p, p, p, K, B, W, slot, p, p, p, p, p, p, p, p, out_params, st)
+    for fn, name, cases in (
+            (sel, "egx_primitive_beam_select",
+             ({"goal": None}, {"jpb": 2}, {"x_ld": 200}, {"B": 0}, {"W": 0}, {"W": 33}, {"N": 0}, {"W": 2, "N": 129}, {"W": 32, "N": 9},
+              {"weights": None}, {"acc": None}, {"acc_out": p}, {"ncoll_out": p}, {"beam_row": None})),
+            (adv, "egx_primitive_advance_beam",
+             ({"mproj": off}, {"out_marker": off}, {"jpb": 2}, {"x_ld": 200}, {"B": 0}, {"mproj": None}, {"W": 0}, {"W": 33}, {"N": 0},
+              {"W": 2, "N": 129}, {"beam_row": None}, {"R0_out": p}, {"T0_out": p}, {"x0_out": p}, {"x1_out": p}, {"status": None})),
+            (back, "egx_beam_backtrack",
+             ({"parent": None}, {"K": 0}, {"B": 0}, {"W": 0}, {"W": 33}, {"rec_marker": off}, {"out_params": off}, {"slot": None}))):
+        for kw in cases:
+            assert fn(**kw) != 0, (name, kw)
+            with pytest.raises(_lib.EgxError):
+                _lib.check(fn(**kw), name)
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+RESULT_FIELDS = ("markers", "params", "rotmat", "transl", "pelvis", "z", "betas", "R0", "T0", "goal", "choice", "cost", "cost_terms", "colliding",
+                 "status", "goal_dist", "n_valid")
+
+
+def test_beam_width_one_is_the_greedy_search(search_world):
+    from egogen_amd import synth
+    from egogen_amd.body_model import SdfScene
+    w = search_world
+    op, K, b, N = w["op"], 3, w["b"], 4
+    z = torch.randn(K, b * N, 128, generator=torch.Generator().manual_seed(2))
+    scene = SdfScene(synth.make_sdf_scene(32))
+    T0 = torch.tensor([[-1.0, -1.0, 0.0], [1.5, -0.2, 0.0], [1.5, -0.75, 0.0]])
+    kw = dict(z=z, reproj_factor=CFG_RF, weights=W_TEST, scene=scene, T0=T0)
+    want = op.generate_sequence_to_goal(w["data"], w["bparams"], w["betas"], w["goal"] + T0, K, N, **kw)
+    ran = []
+    real = op._search_loop
+    op._search_loop = lambda *a: (ran.append(a[:3]), real(*a))[1]
+    try:
+        got = op.generate_sequence_to_goal(w["data"], w["bparams"], w["betas"], w["goal"] + T0, K, N, beam_width=1, **kw)
+    finally:
+        op._search_loop = real
+    assert ran == [(K, b, N)]                                      # the greedy loop itself, not a beam of one
+    for k in RESULT_FIELDS:
+        assert np.array_equal(getattr(got, k), getattr(want, k)), k
+    for k in got.BEAM_FIELDS:
+        assert getattr(got, k) is None and k not in got.search, k
+
+
+def _spy_beam_loop(op, kept):
+    real = op._beam_loop
+
+    def spy(K, b, W, N, s):
+        real(K, b, W, N, s)
+        kept.update(s=s)
+    return real, spy
+
+
+def test_beam_chain_matches_float64(search_world, small_world):
+    """The operator against the float64 `beam_chain`.  Kept rows and parents: equal, depth by depth, until a sequence meets its first
+    undecidable selection (at most 5 % of the decisions).  The records of the returned path of every sequence that was decidable to
+    the end: `held()`, pooled per group over those path nodes - the device within R = 3 times the float32 chain's own distance from
+    the float64 one.  (The element-wise bars of tests/test_genop_search_gpu.py::test_search_chain_matches_float64, 1e-4 |ref| + 2e-5,
+    do not fit this chain: its seeded prior reaches poses of 11 rad at the second depth, where the float32 restatement itself is
+    6.1e-5 from float64 on elements near zero; the device was 4.3e-5 there.)"""
+    from oracle.smplx_lbs import BodyModel
+    w = search_world
+    op, K, b, N, W = w["op"], 3, w["b"], 4, 2
+    M = W * N
+    z = torch.randn(K, b * M, 128, generator=torch.Generator().manual_seed(12))
+    res = op.generate_sequence_to_goal(w["data"], w["bparams"], w["betas"], w["goal"], K, N, z=z, reproj_factor=CFG_RF, weights=W_TEST,
+                                       goal_thresh=0.0, beam_width=W)
+    assert res.beam_width == W and res.cost.shape == (K, b, M) and res.cost_terms.shape == (K, b, M, 5) and res.colliding.shape == (K, b, M)
+    assert res.parent.shape == res.beam_row.shape == res.path_cost.shape == res.beam_status.shape == (K, b, W)
+    assert res.path_slot.shape == res.choice.shape == res.status.shape == (K, b) and res.z.shape == (K, b, 128)
+    ref = {dt: bref.beam_chain(w["sd"], BodyModel(small_world["bm"], dtype=dt), small_world["mk"], _feet(), w["data"].permute(1, 0, 2),
+                               w["pp"][:, :2], torch.eye(3).repeat(b, 1, 1), torch.zeros(b, 3), w["betas"], z, w["goal"], W, N, CFG_RF, W_TEST,
+                               goal_thresh=0.0) for dt in (torch.float64, torch.float32)}
+    (s64, p64), (s32, p32) = ref[torch.float64], ref[torch.float32]
+    undecided, compared, pooled = 0, 0, {}
+    for i in range(b):
+        whole = True
+        for k in range(K):
+            one = lambda t: t[i:i + 1]
+            ok = beam_decidable(one(s64[k]["cost"]), one(s64[k]["terms"]), torch.zeros(1, M, dtype=torch.bool), one(s32[k]["acc_in"]),
+                                one(s64[k]["ncoll_in"]), W, N, one(s32[k]["cost"]), acc64=one(s64[k]["acc_in"]))
+            if not bool(ok[0]) or not torch.equal(s32[k]["beam_row"][i], s64[k]["beam_row"][i]):
+                undecided += 1       # from here on the float32 chain and the device may keep other rows
+                whole = False
+                break
+            assert res.beam_row[k, i].tolist() == s64[k]["beam_row"][i].tolist(), (i, k, res.beam_row[:, i], res.cost[k, i], s64[k]["cost"][i])
+            assert res.parent[k, i].tolist() == s64[k]["parent"][i].tolist() and not res.beam_status[k, i].any()
+            compared += 1
+        if not whole:
+            continue
+        for k in range(K):
+            assert int(res.path_slot[k, i]) == int(p64[k]["slot"][i]) and int(res.choice[k, i]) == int(p64[k]["choice"][i])
+            assert int(p32[k]["slot"][i]) == int(p64[k]["slot"][i])
+            for group, dev, of in (
+                    ("marker_b", res.markers[k, i], lambda p: p["marker_b"][i]), ("pelvis", res.pelvis[k, i], lambda p: p["pelvis"][i]),
+                    ("frame", np.concatenate([res.rotmat[k, i].reshape(9), res.transl[k, i]]), lambda p: torch.cat([p["R"][i].reshape(9), p["T"][i]])),
+                    ("transl", res.params[k, i, :, :3], lambda p: p["pred_params"][i, :, :3]),
+                    ("glorot as a matrix", _aa2R64(res.params[k, i, :, 3:6]), lambda p: _aa2R64(p["pred_params"][i, :, 3:6])),
+                    ("pose", res.params[k, i, :, 6:], lambda p: p["pred_params"][i, :, 6:]),
+                    ("goal_dist", res.goal_dist[k, i].reshape(1), lambda p: p["goal_dist"][i].reshape(1)),
+                    ("path_cost", res.path_cost[k, i], lambda p, k=k: (s64 if p is p64[k] else s32)[k]["path_cost"][i])):
+                pooled.setdefault(group, []).append([torch.as_tensor(dev).double().reshape(-1), of(p64[k]).double().reshape(-1),
+                                                     of(p32[k]).double().reshape(-1)])
+    name = f"beam chain b={b} W={W} N={N} K={K}"
+    assert pooled, "no sequence was decidable to the end: nothing was compared"
+    for group, v in pooled.items():
+        held(name, group, *[torch.cat([x[j] for x in v]) for j in range(3)])
+    share = undecided / (b * K)
+    emit(f"| beam chain b={b} W={W} N={N} K={K} | undecidable decisions | {undecided} of {b * K} | {share:.3f} | compared {compared} |")
+    assert share <= UNDECIDABLE_CAP, share
+    assert (res.parent[1:] != np.arange(W)).any()                 # some slot did continue from another slot's row
+    # the returned path is consistent with the per-slot records, exactly
+    slot = bref.backtrack(torch.as_tensor(res.parent), K).numpy()
+    assert np.array_equal(res.path_slot, slot)
+    take = lambda t: np.take_along_axis(t, slot[..., None], 2)[..., 0]
+    assert np.array_equal(res.choice, take(res.beam_row)) and np.array_equal(res.status, take(res.beam_status))
+    assert np.array_equal(res.goal_dist, np.take_along_axis(res.cost_terms[..., 0], res.choice[..., None].astype(np.int64), 2)[..., 0])
+    assert np.array_equal(res.z, np.take_along_axis(z.numpy().reshape(K, b, M, 128), res.choice[..., None, None].astype(np.int64), 2)[:, :, 0])
+    # ... and the node at depth k + 1 starts from what the path's node at depth k handed on: the seed's pose is a copy
+    assert np.array_equal(res.params[1:, :, :2, 6:], res.params[:-1, :, 18:20, 6:])
+
+
+def test_beam_path_starts_each_primitive_from_its_parent(search_world):
+    """Path consistency, exact, on the loop's own buffers: every slot's record at depth 1 starts from the state its parent slot
+    handed on at depth 0 (frame and pose seed), and the returned records are those of the path's slots.  K = 2, so that the
+    frames handed on at depth 0 are still in their buffer after the loop (depth 1 writes the other one)."""
+    w = search_world
+    op, K, b, N, W = w["op"], 2, w["b"], 2, 3
+    M = W * N
+    z = torch.randn(K, b * M, 128, generator=torch.Generator().manual_seed(14))
+    kept = {}
+    real, op._beam_loop = _spy_beam_loop(op, kept)
+    try:
+        res = op.generate_sequence_to_goal(w["data"], w["bparams"], w["betas"], w["goal"], K, N, z=z, reproj_factor=CFG_RF, beam_width=W,
+                                           to_numpy=False)
+    finally:
+        op._beam_loop = real
+    s = kept["s"]
+    rec, par, row = s["rec_params"], s["parent"].long(), s["beam_row"].long()
+    assert torch.equal(par, row // N) and (par[1] != torch.arange(W, device=par.device)).any()
+    handed_R, handed_T = s["R0s"][1].view(b, W, N, 3, 3), s["T0s"][1].view(b, W, N, 3)       # written by the hand-off of depth 0
+    assert all(torch.equal(handed_R[:, :, n], handed_R[:, :, 0]) for n in range(N))           # ... to every row of a slot alike
+    assert not torch.isnan(handed_R).any()
+    take = lambda t, idx: t.gather(1, idx.view(b, W, *([1] * (t.dim() - 2))).expand(b, W, *t.shape[2:]))
+    assert torch.equal(s["rec_rotmat"][1], take(handed_R[:, :, 0], par[1])) and torch.equal(s["rec_transl"][1], take(handed_T[:, :, 0], par[1]))
+    assert torch.equal(rec[1][:, :, :2, 6:], take(rec[0][:, :, 18:20, 6:], par[1]))           # the pose of the seed is a copy
+    slot = res.path_slot.long()
+    assert torch.equal(slot[K - 1], torch.zeros_like(slot[0])) and torch.equal(slot[0], par[1][:, 0])
+    for k in range(K):
+        for got, per_slot in ((res.params, rec), (res.markers, s["rec_markers"]), (res.rotmat, s["rec_rotmat"]), (res.transl, s["rec_transl"]),
+                              (res.pelvis, s["rec_pelvis"])):
+            at = slot[k].view(b, 1, *([1] * (per_slot.dim() - 3))).expand(b, 1, *per_slot.shape[3:])
+            assert torch.equal(got[k], per_slot[k].gather(1, at)[:, 0])
+    # the frame after the last primitive is the one handed to the rows of slot 0 at the last depth
+    end_R, end_T = s["R0s"][K % 2], s["T0s"][K % 2]
+    assert torch.equal(res.R0, end_R[::M]) and torch.equal(res.T0, end_T[::M])
+    assert all(torch.equal(end_R[n::M], end_R[::M]) for n in range(N))
+
+
+def test_beam_counts_the_colliding_nodes_of_its_path(search_world):
+    from egogen_amd import synth
+    from egogen_amd.body_model import SdfScene
+    w = search_world
+    op, b, N, K, W = w["op"], w["b"], 4, 3, 2
+    box = SdfScene(synth.make_sdf_scene(32))                                                   # box x 1..2, y -0.5..0.5, z 0..1
+    T0 = torch.tensor([[-1.0, -1.0, 0.0], [1.5, -0.2, 0.0], [1.5, -0.75, 0.0]])               # beside, inside, at its edge
+    z = torch.randn(K, b * W * N, 128, generator=torch.Generator().manual_seed(4))
+    kept = {}
+    real, op._beam_loop = _spy_beam_loop(op, kept)
+    try:
+        res = op.generate_sequence_to_goal(w["data"], w["bparams"], w["betas"], w["goal"] + T0, K, N, scene=box, z=z, reproj_factor=CFG_RF,
+                                           T0=T0, to_numpy=False, beam_width=W)
+    finally:
+        op._beam_loop = real
+    s = kept["s"]
+    coll = res.colliding.bool().cpu()
+    emit(f"| beam scene | colliding rows per (k, sequence) | {coll.sum(-1).tolist()} | | |")
+    assert coll.any() and not coll.all()
+    ncoll, acc = s["ncoll"].cpu(), s["acc"].cpu()
+    assert not ncoll[0].any() and not acc[0].any()
+    node = (res.status.cpu() & 1)
+    assert node.any()
+    assert torch.equal(node.bool(), coll.gather(2, res.choice.cpu().long()[..., None])[..., 0])
+    along = ncoll[1:].gather(2, res.path_slot.cpu().long()[..., None])[..., 0]
+    assert torch.equal(along, node.cumsum(0).int())
+    # every depth obeys the rule on the kernel's own costs, with the carried state of the depth before
+    for k in range(K):
+        own = bref.beam_select(res.cost[k].cpu(), res.cost_terms[k].cpu(), coll[k], acc[k], ncoll[k], W, N)
+        assert torch.equal(own["beam_row"], res.beam_row[k].cpu().long()) and torch.equal(own["ncoll"], ncoll[k + 1].long())
+        assert torch.equal(own["status"], res.beam_status[k].cpu().long()) and torch.equal(own["path_cost"], res.path_cost[k].cpu())
+
+
+def test_beam_result_truncates_saves_and_rolls_out(search_world, tmp_path):
+    from egogen_amd.utils import rollout_primitives
+    w = search_world
+    op, h, K, b, N, W = w["op"], w["handle"], 3, w["b"], 2, 2
+    z = torch.randn(K, b * W * N, 128, generator=torch.Generator().manual_seed(4))
+    wts = {"goal": 0.0, "skate": 1.0, "floor": 1.0}             # no key depends on the goal: both runs below keep the same rows
+    nowhere = np.asarray([40.0, 40.0, 0.9], np.float32)
+    far = op.generate_sequence_to_goal(w["data"], w["bparams"], w["betas"], nowhere, K, N, z=z, reproj_factor=CFG_RF, weights=wts, beam_width=W)
+    assert far.n_valid.tolist() == [K] * b and far.goal.shape == (b, 3)
+    goal = far.pelvis[0, :, 19].copy()                  # identity start frame: the path's first primitive ends there
+    goal[2] = nowhere
+    res = op.generate_sequence_to_goal(w["data"], w["bparams"], w["betas"], goal, K, N, z=z, reproj_factor=CFG_RF, weights=wts, beam_width=W)
+    assert np.array_equal(res.beam_row, far.beam_row) and np.array_equal(res.pelvis, far.pelvis)
+    assert res.n_valid.tolist() == [1, 1, K]
+    assert np.all(res.goal_dist[0, :2] < 0.1) and len(res.primitives(0)) == 1 and len(res.primitives(2)) == K
+    for i in (0, 2):
+        path = res.save(str(tmp_path), i, man_id=f"beam{i}")
+        with open(path, "rb") as fh:
+            node = pickle.load(fh)
+        assert len(node["motion"]) == int(res.n_valid[i])
+        assert np.allclose(node["wpath"][1], goal[i]) and np.allclose(node["wpath"][0], res.pelvis[0, i, 0], atol=1e-6)
+        seq = rollout_primitives(node["motion"], h)
+        assert seq.shape == (2 + 18 * int(res.n_valid[i]), 93) and np.isfinite(seq).all()
+
+
+def test_beam_loop_has_no_host_wait(search_world):
+    """torch-level synchronisation only, as tests/test_genop_search_gpu.py::test_search_loop_has_no_host_wait; the backtrack launch
+    is part of the guarded loop"""
+    if not hasattr(torch.cuda, "set_sync_debug_mode"):
+        pytest.skip("this torch build has no torch.cuda.set_sync_debug_mode")
+    from egogen_amd import synth
+    from egogen_amd.body_model import SdfScene
+    w = search_world
+    op = w["op"]
+    scene = SdfScene(synth.make_sdf_scene(32))
+    args = (w["data"], w["bparams"], w["betas"], w["goal"])
+    op.generate_sequence_to_goal(*args, 1, 2, scene=scene, beam_width=2)      # weight images, workspaces
+    real = op._beam_loop
+    ran = []
+
+    def guarded(*a):
+        old = torch.cuda.get_sync_debug_mode()
+        torch.cuda.set_sync_debug_mode("error")
+        try:
+            real(*a)
+            ran.append(a[:4])
+        finally:
+            torch.cuda.set_sync_debug_mode(old)
+    op._beam_loop = guarded
+    try:
+        res = op.generate_sequence_to_goal(*args, 3, 2, scene=scene, beam_width=2)
+    finally:
+        op._beam_loop = real
+    assert ran == [(3, w["b"], 2, 2)] and np.isfinite(res.markers).all()
+
+
+def test_beam_width_argument_handling(search_world):
+    w = search_world
+    op, b = w["op"], w["b"]
+    args = (w["data"], w["bparams"], w["betas"], w["goal"])
+    with pytest.raises(ValueError, match="beam_width"):
+        op.generate_sequence_to_goal(*args, 1, 2, beam_width=0)
+    with pytest.raises(ValueError, match="beam_width"):
+        op.generate_sequence_to_goal(*args, 1, 2, beam_width=33)
+    with pytest.raises(ValueError, match="256"):
+        op.generate_sequence_to_goal(*args, 1, 65, beam_width=4)
+    with pytest.raises(ValueError, match="z must be"):
+        op.generate_sequence_to_goal(*args, 2, 4, beam_width=2, z=torch.zeros(2, b * 4, 128))
+    one = op.generate_sequence_to_goal(w["data"], w["bparams"], w["betas"], w["goal"][0], 2, 8, beam_width=32, to_numpy=False)     # W * N = 256
+    assert one.markers.is_cuda and one.beam_width == 32 and one.parent.shape == (2, b, 32) and one.z.shape == (2, b, 128)
+    assert one.cost.shape == (2, b, 256) and int(one.beam_row.max()) < 256 and len(set(one.beam_row[0, 0].tolist())) == 32
+
+
+@pytest.mark.parametrize("bit", [2, 4])
+def test_beam_raises_on_a_nonfinite_path_node(search_world, bit):
+    """bit 1 (a non-finite row) or bit 2 (a non-finite hand-off) on a node of a returned path raises; on another slot it does not.
+    The bits themselves are the kernels' (the hand-made selection cases, test_advance_beam_marks_the_nonfinite_slot_only)."""
+    w = search_world
+    op, K, W = w["op"], 2, 2
+    args = (w["data"], w["bparams"], w["betas"], w["goal"], K, 2)
+    z = torch.randn(K, w["b"] * W * 2, 128, generator=torch.Generator().manual_seed(8))
+    real = op._beam_loop
+
+    def marked(on_path):
+        def loop(K_, b, W_, N, s):
+            real(K_, b, W_, N, s)
+            slot = s["path_slot"][1, 1].long()
+            s["beam_status"][1, 1, slot if on_path else 1 - slot] |= bit
+            s["status"][1, 1] = s["beam_status"][1, 1, slot]
+        return loop
+    try:
+        op._beam_loop = marked(False)
+        op.generate_sequence_to_goal(*args, z=z, beam_width=W)
+        op._beam_loop = marked(True)
+        with pytest.raises(FloatingPointError, match="non-finite"):
+            op.generate_sequence_to_goal(*args, z=z, beam_width=W)
+    finally:
+        op._beam_loop = real
+
+
+def test_gen_motion_driver_beam_search(tmp_path):
+    """The driver with --beam-width; its greedy path is tests/test_genop_search_gpu.py::test_gen_motion_driver_goal_search."""
+    env = dict(os.environ, PYTHONPATH=ROOT + os.pathsep + os.environ.get("PYTHONPATH", ""))
+    out = tmp_path / "beam"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "exp_GAMMAPrimitive", "gen_motion.py"), "--n-primitives", "2", "--seed", "3",
+                        "--num-verts", str(V_SMALL), "--n-gens", "2", "--goal", "40,40,0.9", "--n-candidates", "4", "--beam-width", "2",
+                        "--out", str(out)], cwd=str(tmp_path), env=env, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    files = sorted(f for f in os.listdir(out) if f.startswith("motion_") and f.endswith(".pkl"))
+    assert len(files) == 2, files
+    for f in files:
+        with open(out / f, "rb") as fh:
+            node = pickle.load(fh)
+        assert len(node["motion"]) == 2 and node["motion"][0]["smplx_params"].shape == (1, 20, 93)
+        assert np.allclose(node["wpath"][1], [40.0, 40.0, 0.9])
+    assert "frames: 38" in r.stdout, r.stdout[-500:]
