@@ -3,7 +3,9 @@
 // (egx_primitive_advance_select).  The beam search keeps W partial paths per sequence: egx_primitive_beam_select scores the W * N
 // rows of a sequence with the same row scoring and keeps the W best path keys, egx_primitive_advance_beam hands each kept row on
 // to the N rows of its slot (one workgroup per slot, R0 / T0 from one buffer into another), egx_beam_backtrack gathers the
-// records of the returned path.
+// records of the returned path.  Device code is shared (advance_body, score_group, key_before); so is the host side: the three
+// hand-off entries go through advance_entry and the two selection entries through select_entry (common checks, common fields,
+// launch check), and each entry states only the checks, fields and launch that are its own.
 //
 // Reference: the motion-only tail of CrowdEnv.step, motion/crowd_ppo/crowd_env_2f.py:144-155 (pelvis, blended markers) and
 // :238-265 (new canonical frame from the second-last body, accumulated world frame, seed parameters and seed markers in the new
@@ -226,16 +228,30 @@ __device__ __forceinline__ int wave_max(int v) {
   for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_down(v, o, 64));
   return v;
 }
-// the order of the choice: class (0 clean, 1 colliding, 2 / 3 the same with a non-finite value), then cost, then index
-__device__ __forceinline__ bool candidate_before(int ca, float xa, int ia, int cb, float xb, int ib) {
+// The order of both selections, a total one: key class, then cost, then row index.  Greedy: class 0 clean, 1 colliding, 2 / 3 the
+// same with a non-finite value, cost of the row.  Beam: class (non-finite, colliding nodes on the path), accumulated path cost.
+__device__ __forceinline__ bool key_before(int ca, float xa, int ia, int cb, float xb, int ib) {
   if (ca != cb) return ca < cb;
   if (xa != xb) return xa < xb;
   return ia < ib;
 }
 
-}  // namespace
+// the carried state of the beam's slots and what its selection writes per kept slot
+struct BeamArgs {
+  const float* acc;      // [b,W] sum of q along the path into each slot
+  const int* ncoll;      // [b,W] colliding nodes on it
+  int* beam_row;         // [b,W] outputs per kept slot
+  int* parent;
+  float* acc_out;
+  int* ncoll_out;
+  float* path_cost;
+  int* beam_status;
+  float* goal_dist;
+  int* reached;
+  int W, N;
+};
 
-namespace {
+constexpr int NONFINITE_KEY = 1 << 30;   // above any count of colliding nodes on a path
 
 // what lane 0 of the scoring wave knows of a row; q is the cost without its goal term, accumulated on its own
 struct RowScore {
@@ -322,11 +338,11 @@ __global__ __launch_bounds__(SEL_BLK) void egx_primitive_select_kernel(SelectArg
     int bc = 4, bi = 0x7fffffff;
     float bx = 0.f;
     for (int n = lane; n < N; n += 64)
-      if (candidate_before(s_cls[n], s_cost[n], n, bc, bx, bi)) { bc = s_cls[n]; bx = s_cost[n]; bi = n; }
+      if (key_before(s_cls[n], s_cost[n], n, bc, bx, bi)) { bc = s_cls[n]; bx = s_cost[n]; bi = n; }
     for (int o = 32; o > 0; o >>= 1) {
       const int oc = __shfl_xor(bc, o, 64), oi = __shfl_xor(bi, o, 64);
       const float ox = __shfl_xor(bx, o, 64);
-      if (candidate_before(oc, ox, oi, bc, bx, bi)) { bc = oc; bx = ox; bi = oi; }
+      if (key_before(oc, ox, oi, bc, bx, bi)) { bc = oc; bx = ox; bi = oi; }
     }
     if (lane == 0) {
       const float dist = s_dist[bi];
@@ -342,32 +358,6 @@ __global__ __launch_bounds__(SEL_BLK) void egx_primitive_select_kernel(SelectArg
 // One workgroup per sequence scores its W * N rows as above, then every row counts the rows whose path key precedes its own:
 // (non-finite, colliding nodes on the path, accumulated cost, row index) is a total order, so that count is the row's rank
 // whatever the order of the comparisons, and the rows of rank < W are the beam, slot = rank.
-namespace {
-
-struct BeamArgs {
-  const float* acc;      // [b,W] sum of q along the path into each slot
-  const int* ncoll;      // [b,W] colliding nodes on it
-  int* beam_row;         // [b,W] outputs per kept slot
-  int* parent;
-  float* acc_out;
-  int* ncoll_out;
-  float* path_cost;
-  int* beam_status;
-  float* goal_dist;
-  int* reached;
-  int W, N;
-};
-
-constexpr int NONFINITE_KEY = 1 << 30;   // above any count of colliding nodes
-
-__device__ __forceinline__ bool path_before(int ca, float xa, int ia, int cb, float xb, int ib) {
-  if (ca != cb) return ca < cb;
-  if (xa != xb) return xa < xb;
-  return ia < ib;
-}
-
-}  // namespace
-
 __global__ __launch_bounds__(SEL_BLK) void egx_primitive_beam_select_kernel(SelectArgs p, BeamArgs q) {
   __shared__ float s_feet[SEL_WAVES][NT][NF * 3];
   __shared__ float s_path[MAXC], s_q[MAXC], s_dist[MAXC];   // path cost (0 where non-finite), q and dist of every row
@@ -389,7 +379,7 @@ __global__ __launch_bounds__(SEL_BLK) void egx_primitive_beam_select_kernel(Sele
     const int kc = s_key[tid];
     const float kx = s_path[tid];
     int rank = 0;
-    for (int m = 0; m < M; ++m) rank += path_before(s_key[m], s_path[m], m, kc, kx, tid) ? 1 : 0;
+    for (int m = 0; m < M; ++m) rank += key_before(s_key[m], s_path[m], m, kc, kx, tid) ? 1 : 0;
     if (rank < W) {
       const int s = tid / N;
       const size_t o = (size_t)g * W + rank;
@@ -462,25 +452,68 @@ __global__ __launch_bounds__(BLK) void egx_beam_backtrack_kernel(BacktrackArgs p
   if (tid >= 128 && tid < 128 + 3) p.out_T[dst * 3 + (tid - 128)] = p.rec_T[src * 3 + (tid - 128)];
 }
 
-extern "C" int egx_primitive_advance(const float* pred_params, const float* Y_gen, const float* x0, const float* x1, int x_ld,
-                                     const float* joints, int joints_per_body, const float* markers_proj, const float* delta_T,
-                                     float reproj_factor, int num_sequences, float* R0, float* T0, float* out_marker_b,
-                                     float* out_pelvis, float* out_R, float* out_T, float* out_seed_params, float* out_x0,
-                                     float* out_x1, int out_x_ld, int32_t* nonfinite, void* stream) {
+// ---- host: one argument path per kernel family --------------------------------------------------------------------------
+namespace {
+
+// What the three hand-off entries share: the checks on their common arguments, the fields these fill, the launch check.  `launch`
+// sets what is the entry's own (R0_out / T0_out, out_params, nonfinite, beam_status: null unless set; B) and launches its kernel.
+// EGX_REQUIRE returns from the function it stands in: the entry checks its own arguments first, then returns this one's result.
+template <class Launch>
+int advance_entry(const float* pred_params, const float* Y_gen, const float* x0, const float* x1, int x_ld, const float* joints,
+                  int joints_per_body, const float* markers_proj, const float* delta_T, float reproj_factor, int num_sequences,
+                  const float* R0, const float* T0, float* out_marker_b, float* out_pelvis, float* out_R, float* out_T,
+                  float* out_seed_params, float* out_x0, float* out_x1, int out_x_ld, Launch launch) {
   EGX_REQUIRE(pred_params && Y_gen && x0 && x1 && joints && markers_proj && delta_T && R0 && T0, "null input");
   EGX_REQUIRE(out_marker_b && out_pelvis && out_R && out_T && out_seed_params && out_x0 && out_x1, "null output");
   EGX_REQUIRE(num_sequences > 0 && joints_per_body >= 3, "need a non-empty batch and >= 3 joints per body");
   EGX_REQUIRE(x_ld >= MD && out_x_ld >= MD, "a seed frame holds 201 floats: the row strides cannot be smaller");
   EGX_REQUIRE(((uintptr_t)markers_proj & 15) == 0 && ((uintptr_t)out_marker_b & 15) == 0,
               "markers_proj and out_marker_b must be 16-byte aligned");
-  AdvanceArgs p;
+  AdvanceArgs p{};
   p.pred_params = pred_params; p.Y_gen = Y_gen; p.x0 = x0; p.x1 = x1; p.joints = joints; p.markers_proj = markers_proj;
-  p.delta_T = delta_T; p.R0 = R0; p.T0 = T0; p.R0_out = R0; p.T0_out = T0; p.beam_status = nullptr; p.out_marker_b = out_marker_b; p.out_pelvis = out_pelvis; p.out_R = out_R;
-  p.out_T = out_T; p.out_seed = out_seed_params; p.out_x0 = out_x0; p.out_x1 = out_x1; p.out_params = nullptr; p.nonfinite = nonfinite;
-  p.rf = reproj_factor; p.B = num_sequences; p.jpb = joints_per_body; p.x_ld = x_ld; p.out_x_ld = out_x_ld;
-  hipLaunchKernelGGL(egx_primitive_advance_kernel, dim3(num_sequences), dim3(BLK), 0, static_cast<hipStream_t>(stream), p);
+  p.delta_T = delta_T; p.R0 = R0; p.T0 = T0; p.out_marker_b = out_marker_b; p.out_pelvis = out_pelvis; p.out_R = out_R;
+  p.out_T = out_T; p.out_seed = out_seed_params; p.out_x0 = out_x0; p.out_x1 = out_x1;
+  p.rf = reproj_factor; p.jpb = joints_per_body; p.x_ld = x_ld; p.out_x_ld = out_x_ld;
+  launch(p);
   EGX_HIP_CHECK(hipGetLastError());
   return EGX_OK;
+}
+
+// The same for the two selection entries, for num_sequences groups of `group_rows` rows; `launch` sets the per-group outputs of
+// the greedy selection (null unless set; the beam's are in BeamArgs) and launches.
+template <class Launch>
+int select_entry(const float* Y_gen, const float* x0, const float* x1, int x_ld, const float* joints, int joints_per_body,
+                 const float* markers_proj, const float* R0, const float* T0, const int32_t* pene_count, const float* goal,
+                 const int32_t* feet_marker_idx, const float* weights, float pene_thres, float goal_thresh, float reproj_factor,
+                 int num_sequences, int group_rows, float* cost, float* cost_terms, int32_t* colliding, Launch launch) {
+  EGX_REQUIRE(Y_gen && x0 && x1 && joints && markers_proj && R0 && T0 && goal && feet_marker_idx && weights, "null input");
+  EGX_REQUIRE(cost && cost_terms && colliding, "null output");
+  EGX_REQUIRE(num_sequences > 0 && joints_per_body >= 3, "need a non-empty batch and >= 3 joints per body");
+  EGX_REQUIRE(x_ld >= MD, "a seed frame holds 201 floats: the row stride cannot be smaller");
+  SelectArgs p{};
+  p.Y_gen = Y_gen; p.x0 = x0; p.x1 = x1; p.joints = joints; p.markers_proj = markers_proj; p.R0 = R0; p.T0 = T0;
+  p.pene_count = pene_count; p.goal = goal; p.feet_marker_idx = feet_marker_idx;
+  p.w_goal = weights[0]; p.w_skate = weights[1]; p.w_floor = weights[2]; p.w_pene = weights[3]; p.w_face = weights[4];
+  p.pene_thres = pene_thres; p.goal_thresh = goal_thresh; p.rf = reproj_factor;
+  p.rows = num_sequences * group_rows; p.N = group_rows; p.jpb = joints_per_body; p.x_ld = x_ld;
+  p.cost = cost; p.terms = cost_terms; p.colliding = colliding;
+  launch(p);
+  EGX_HIP_CHECK(hipGetLastError());
+  return EGX_OK;
+}
+
+}  // namespace
+
+extern "C" int egx_primitive_advance(const float* pred_params, const float* Y_gen, const float* x0, const float* x1, int x_ld,
+                                     const float* joints, int joints_per_body, const float* markers_proj, const float* delta_T,
+                                     float reproj_factor, int num_sequences, float* R0, float* T0, float* out_marker_b,
+                                     float* out_pelvis, float* out_R, float* out_T, float* out_seed_params, float* out_x0,
+                                     float* out_x1, int out_x_ld, int32_t* nonfinite, void* stream) {
+  return advance_entry(pred_params, Y_gen, x0, x1, x_ld, joints, joints_per_body, markers_proj, delta_T, reproj_factor, num_sequences,
+                       R0, T0, out_marker_b, out_pelvis, out_R, out_T, out_seed_params, out_x0, out_x1, out_x_ld, [&](AdvanceArgs& p) {
+    p.R0_out = R0; p.T0_out = T0; p.nonfinite = nonfinite; p.B = num_sequences;
+    hipLaunchKernelGGL(egx_primitive_advance_kernel, dim3(num_sequences), dim3(BLK), 0, static_cast<hipStream_t>(stream), p);
+  });
 }
 
 extern "C" int egx_primitive_select(const float* Y_gen, const float* x0, const float* x1, int x_ld, const float* joints,
@@ -489,22 +522,14 @@ extern "C" int egx_primitive_select(const float* Y_gen, const float* x0, const f
                                     const float* weights, float pene_thres, float goal_thresh, float reproj_factor,
                                     int num_sequences, int num_candidates, int32_t* choice, int32_t* status, int32_t* reached,
                                     float* goal_dist, float* cost, float* cost_terms, int32_t* colliding, void* stream) {
-  EGX_REQUIRE(Y_gen && x0 && x1 && joints && markers_proj && R0 && T0 && goal && feet_marker_idx && weights, "null input");
-  EGX_REQUIRE(choice && status && reached && goal_dist && cost && cost_terms && colliding, "null output");
-  EGX_REQUIRE(num_sequences > 0 && joints_per_body >= 3, "need a non-empty batch and >= 3 joints per body");
+  EGX_REQUIRE(choice && status && reached && goal_dist, "null output");
   EGX_REQUIRE(num_candidates >= 1 && num_candidates <= MAXC, "num_candidates must be in [1, EGX_MAX_CANDIDATES]");
-  EGX_REQUIRE(x_ld >= MD, "a seed frame holds 201 floats: the row stride cannot be smaller");
-  SelectArgs p;
-  p.Y_gen = Y_gen; p.x0 = x0; p.x1 = x1; p.joints = joints; p.markers_proj = markers_proj; p.R0 = R0; p.T0 = T0;
-  p.pene_count = pene_count; p.goal = goal; p.feet_marker_idx = feet_marker_idx;
-  p.w_goal = weights[0]; p.w_skate = weights[1]; p.w_floor = weights[2]; p.w_pene = weights[3]; p.w_face = weights[4];
-  p.pene_thres = pene_thres; p.goal_thresh = goal_thresh; p.rf = reproj_factor;
-  p.rows = num_sequences * num_candidates; p.N = num_candidates; p.jpb = joints_per_body; p.x_ld = x_ld;
-  p.choice = choice; p.status = status; p.reached = reached; p.goal_dist = goal_dist; p.cost = cost; p.terms = cost_terms;
-  p.colliding = colliding;
-  hipLaunchKernelGGL(egx_primitive_select_kernel, dim3(num_sequences), dim3(SEL_BLK), 0, static_cast<hipStream_t>(stream), p);
-  EGX_HIP_CHECK(hipGetLastError());
-  return EGX_OK;
+  return select_entry(Y_gen, x0, x1, x_ld, joints, joints_per_body, markers_proj, R0, T0, pene_count, goal, feet_marker_idx, weights,
+                      pene_thres, goal_thresh, reproj_factor, num_sequences, num_candidates, cost, cost_terms, colliding,
+                      [&](SelectArgs& p) {
+    p.choice = choice; p.status = status; p.reached = reached; p.goal_dist = goal_dist;
+    hipLaunchKernelGGL(egx_primitive_select_kernel, dim3(num_sequences), dim3(SEL_BLK), 0, static_cast<hipStream_t>(stream), p);
+  });
 }
 
 extern "C" int egx_primitive_advance_select(const float* pred_params, const float* Y_gen, const float* x0, const float* x1, int x_ld,
@@ -513,23 +538,14 @@ extern "C" int egx_primitive_advance_select(const float* pred_params, const floa
                                             int num_candidates, float* R0, float* T0, float* out_marker_b, float* out_pelvis,
                                             float* out_R, float* out_T, float* out_params, float* out_seed_params, float* out_x0,
                                             float* out_x1, int out_x_ld, int32_t* nonfinite, void* stream) {
-  EGX_REQUIRE(pred_params && Y_gen && x0 && x1 && joints && markers_proj && delta_T && R0 && T0 && choice, "null input");
-  EGX_REQUIRE(out_marker_b && out_pelvis && out_R && out_T && out_seed_params && out_x0 && out_x1, "null output");
-  EGX_REQUIRE(num_sequences > 0 && joints_per_body >= 3, "need a non-empty batch and >= 3 joints per body");
+  EGX_REQUIRE(choice, "null input");
   EGX_REQUIRE(num_candidates >= 1 && num_candidates <= MAXC, "num_candidates must be in [1, EGX_MAX_CANDIDATES]");
-  EGX_REQUIRE(x_ld >= MD && out_x_ld >= MD, "a seed frame holds 201 floats: the row strides cannot be smaller");
-  EGX_REQUIRE(((uintptr_t)markers_proj & 15) == 0 && ((uintptr_t)out_marker_b & 15) == 0,
-              "markers_proj and out_marker_b must be 16-byte aligned");
-  AdvanceArgs p;
-  p.pred_params = pred_params; p.Y_gen = Y_gen; p.x0 = x0; p.x1 = x1; p.joints = joints; p.markers_proj = markers_proj;
-  p.delta_T = delta_T; p.R0 = R0; p.T0 = T0; p.R0_out = R0; p.T0_out = T0; p.beam_status = nullptr; p.out_marker_b = out_marker_b; p.out_pelvis = out_pelvis; p.out_R = out_R;
-  p.out_T = out_T; p.out_seed = out_seed_params; p.out_x0 = out_x0; p.out_x1 = out_x1; p.out_params = out_params;
-  p.nonfinite = nonfinite; p.rf = reproj_factor; p.B = num_sequences * num_candidates; p.jpb = joints_per_body; p.x_ld = x_ld;
-  p.out_x_ld = out_x_ld;
-  hipLaunchKernelGGL(egx_primitive_advance_select_kernel, dim3(num_sequences), dim3(BLK), 0, static_cast<hipStream_t>(stream), p,
-                     choice, num_candidates);
-  EGX_HIP_CHECK(hipGetLastError());
-  return EGX_OK;
+  return advance_entry(pred_params, Y_gen, x0, x1, x_ld, joints, joints_per_body, markers_proj, delta_T, reproj_factor, num_sequences,
+                       R0, T0, out_marker_b, out_pelvis, out_R, out_T, out_seed_params, out_x0, out_x1, out_x_ld, [&](AdvanceArgs& p) {
+    p.R0_out = R0; p.T0_out = T0; p.out_params = out_params; p.nonfinite = nonfinite; p.B = num_sequences * num_candidates;
+    hipLaunchKernelGGL(egx_primitive_advance_select_kernel, dim3(num_sequences), dim3(BLK), 0, static_cast<hipStream_t>(stream), p,
+                       choice, num_candidates);
+  });
 }
 
 extern "C" int egx_primitive_beam_select(const float* Y_gen, const float* x0, const float* x1, int x_ld, const float* joints,
@@ -540,30 +556,18 @@ extern "C" int egx_primitive_beam_select(const float* Y_gen, const float* x0, co
                                          const int32_t* ncoll, float* cost, float* cost_terms, int32_t* colliding, int32_t* beam_row,
                                          int32_t* parent, float* acc_out, int32_t* ncoll_out, float* path_cost, int32_t* beam_status,
                                          float* goal_dist, int32_t* reached, void* stream) {
-  EGX_REQUIRE(Y_gen && x0 && x1 && joints && markers_proj && R0 && T0 && goal && feet_marker_idx && weights && acc && ncoll, "null input");
-  EGX_REQUIRE(cost && cost_terms && colliding && beam_row && parent && acc_out && ncoll_out && path_cost && beam_status && goal_dist &&
-                  reached, "null output");
-  EGX_REQUIRE(num_sequences > 0 && joints_per_body >= 3, "need a non-empty batch and >= 3 joints per body");
+  EGX_REQUIRE(acc && ncoll, "null input");
+  EGX_REQUIRE(beam_row && parent && acc_out && ncoll_out && path_cost && beam_status && goal_dist && reached, "null output");
   EGX_REQUIRE(beam_width >= 1 && beam_width <= EGX_MAX_BEAM, "beam_width must be in [1, EGX_MAX_BEAM]");
   EGX_REQUIRE(num_candidates >= 1 && num_candidates <= MAXC && beam_width * num_candidates <= MAXC,
               "beam_width * num_candidates must be in [1, EGX_MAX_CANDIDATES]");
-  EGX_REQUIRE(x_ld >= MD, "a seed frame holds 201 floats: the row stride cannot be smaller");
   EGX_REQUIRE(acc != acc_out && ncoll != ncoll_out, "acc / ncoll are read from one buffer and written to another");
-  SelectArgs p;
-  p.Y_gen = Y_gen; p.x0 = x0; p.x1 = x1; p.joints = joints; p.markers_proj = markers_proj; p.R0 = R0; p.T0 = T0;
-  p.pene_count = pene_count; p.goal = goal; p.feet_marker_idx = feet_marker_idx;
-  p.w_goal = weights[0]; p.w_skate = weights[1]; p.w_floor = weights[2]; p.w_pene = weights[3]; p.w_face = weights[4];
-  p.pene_thres = pene_thres; p.goal_thresh = goal_thresh; p.rf = reproj_factor;
-  p.rows = num_sequences * beam_width * num_candidates; p.N = beam_width * num_candidates; p.jpb = joints_per_body; p.x_ld = x_ld;
-  p.choice = nullptr; p.status = nullptr; p.reached = nullptr; p.goal_dist = nullptr; p.cost = cost; p.terms = cost_terms;
-  p.colliding = colliding;
-  BeamArgs q;
-  q.acc = acc; q.ncoll = ncoll; q.beam_row = beam_row; q.parent = parent; q.acc_out = acc_out; q.ncoll_out = ncoll_out;
-  q.path_cost = path_cost; q.beam_status = beam_status; q.goal_dist = goal_dist; q.reached = reached; q.W = beam_width;
-  q.N = num_candidates;
-  hipLaunchKernelGGL(egx_primitive_beam_select_kernel, dim3(num_sequences), dim3(SEL_BLK), 0, static_cast<hipStream_t>(stream), p, q);
-  EGX_HIP_CHECK(hipGetLastError());
-  return EGX_OK;
+  return select_entry(Y_gen, x0, x1, x_ld, joints, joints_per_body, markers_proj, R0, T0, pene_count, goal, feet_marker_idx, weights,
+                      pene_thres, goal_thresh, reproj_factor, num_sequences, beam_width * num_candidates, cost, cost_terms, colliding,
+                      [&](SelectArgs& p) {
+    const BeamArgs q{acc, ncoll, beam_row, parent, acc_out, ncoll_out, path_cost, beam_status, goal_dist, reached, beam_width, num_candidates};
+    hipLaunchKernelGGL(egx_primitive_beam_select_kernel, dim3(num_sequences), dim3(SEL_BLK), 0, static_cast<hipStream_t>(stream), p, q);
+  });
 }
 
 extern "C" int egx_primitive_advance_beam(const float* pred_params, const float* Y_gen, const float* x0, const float* x1, int x_ld,
@@ -573,28 +577,20 @@ extern "C" int egx_primitive_advance_beam(const float* pred_params, const float*
                                           float* out_marker_b, float* out_pelvis, float* out_R, float* out_T, float* out_params,
                                           float* out_seed_params, float* out_x0, float* out_x1, int out_x_ld, int32_t* beam_status,
                                           void* stream) {
-  EGX_REQUIRE(pred_params && Y_gen && x0 && x1 && joints && markers_proj && delta_T && R0 && T0 && beam_row, "null input");
-  EGX_REQUIRE(R0_out && T0_out && out_marker_b && out_pelvis && out_R && out_T && out_seed_params && out_x0 && out_x1 && beam_status,
-              "null output");
-  EGX_REQUIRE(num_sequences > 0 && joints_per_body >= 3, "need a non-empty batch and >= 3 joints per body");
+  EGX_REQUIRE(beam_row, "null input");
+  EGX_REQUIRE(R0_out && T0_out && beam_status, "null output");
   EGX_REQUIRE(beam_width >= 1 && beam_width <= EGX_MAX_BEAM, "beam_width must be in [1, EGX_MAX_BEAM]");
   EGX_REQUIRE(num_candidates >= 1 && num_candidates <= MAXC && beam_width * num_candidates <= MAXC,
               "beam_width * num_candidates must be in [1, EGX_MAX_CANDIDATES]");
-  EGX_REQUIRE(x_ld >= MD && out_x_ld >= MD, "a seed frame holds 201 floats: the row strides cannot be smaller");
-  EGX_REQUIRE(((uintptr_t)markers_proj & 15) == 0 && ((uintptr_t)out_marker_b & 15) == 0,
-              "markers_proj and out_marker_b must be 16-byte aligned");
   EGX_REQUIRE(R0 != R0_out && T0 != T0_out && x0 != out_x0 && x1 != out_x1,
               "a slot may read a row another slot writes: R0 / T0 and the seed frames are written to other buffers");
-  AdvanceArgs p;
-  p.pred_params = pred_params; p.Y_gen = Y_gen; p.x0 = x0; p.x1 = x1; p.joints = joints; p.markers_proj = markers_proj;
-  p.delta_T = delta_T; p.R0 = R0; p.T0 = T0; p.R0_out = R0_out; p.T0_out = T0_out; p.beam_status = beam_status;
-  p.out_marker_b = out_marker_b; p.out_pelvis = out_pelvis; p.out_R = out_R; p.out_T = out_T; p.out_seed = out_seed_params;
-  p.out_x0 = out_x0; p.out_x1 = out_x1; p.out_params = out_params; p.nonfinite = nullptr; p.rf = reproj_factor;
-  p.B = num_sequences * beam_width * num_candidates; p.jpb = joints_per_body; p.x_ld = x_ld; p.out_x_ld = out_x_ld;
-  hipLaunchKernelGGL(egx_primitive_advance_beam_kernel, dim3(num_sequences * beam_width), dim3(BLK), 0,
-                     static_cast<hipStream_t>(stream), p, beam_row, beam_width, num_candidates);
-  EGX_HIP_CHECK(hipGetLastError());
-  return EGX_OK;
+  return advance_entry(pred_params, Y_gen, x0, x1, x_ld, joints, joints_per_body, markers_proj, delta_T, reproj_factor, num_sequences,
+                       R0, T0, out_marker_b, out_pelvis, out_R, out_T, out_seed_params, out_x0, out_x1, out_x_ld, [&](AdvanceArgs& p) {
+    p.R0_out = R0_out; p.T0_out = T0_out; p.out_params = out_params; p.beam_status = beam_status;
+    p.B = num_sequences * beam_width * num_candidates;
+    hipLaunchKernelGGL(egx_primitive_advance_beam_kernel, dim3(num_sequences * beam_width), dim3(BLK), 0,
+                       static_cast<hipStream_t>(stream), p, beam_row, beam_width, num_candidates);
+  });
 }
 
 extern "C" int egx_beam_backtrack(const int32_t* parent, const int32_t* beam_row, const int32_t* beam_status, const float* goal_dist,

@@ -9,6 +9,12 @@ continues from the best one (kernels egx_primitive_select, egx_primitive_advance
 search that keeps the best W partial paths per sequence (kernels egx_primitive_beam_select, egx_primitive_advance_beam,
 egx_beam_backtrack).
 
+The three chains share their host path: `_chain_state` builds the state dict (checked inputs, defaults, the loop's buffers, the
+records) for b seeds of M rows each, `_primitive` launches what every primitive begins with (prior, parameter assembly, body
+model), `_handoff_lead` / `_select_lead` build the leading arguments common to the hand-off and to the selection entries once per
+loop, and `_result` turns the records into a `PrimitiveSequence`.  `_advance_loop(K, B, s)`, `_search_loop(K, b, N, s)` and
+`_beam_loop(K, b, W, N, s)` are launches only and differ in what follows the prefix.
+
 Differences from the reference, all in `generate` unless noted:
   * `t_his=None` means the model's t_his (the reference computes `20 - None` and fails);
   * only t_his == 2 is supported (egx_sample_prior takes two history frames): anything else raises ValueError;
@@ -40,6 +46,11 @@ GENERATE_PPO_NOT_BUILT = ("generate_ppo is not built: nothing in the reference c
 def _section(cfg, name):
     """`cfg.modelconfig` (OmegaConf / namespace) or `cfg['modelconfig']` (plain yaml)."""
     return cfg[name] if isinstance(cfg, dict) else getattr(cfg, name)
+
+
+def _vp(t):
+    """`_lib.ptr` without its checks, for the per-primitive slices of the records (contiguous by construction, never None)"""
+    return C.c_void_p(t.data_ptr())
 
 
 def _load_ckpt(candidates):
@@ -222,6 +233,77 @@ class GAMMAPrimitiveComboGenOP:
         raise NotImplementedError(GENERATE_PPO_NOT_BUILT)
 
     # ------------------------------------------------------------------------------------------------------------------
+    def _chain_state(self, X, seed, bt, K, M, z, reproj_factor, R0, T0) -> dict:
+        """What a chain of K primitives starts from, a plain dict: the b seeds of `_seed_inputs` repeated to M rows each (row
+        i * M + m continues seed i), the buffers the primitive loop works in over those b * M rows, and the [K,b,...] records of the
+        returned primitives.  z: None (drawn here) or [K, b * M, 128]; reproj_factor, R0 [b,3,3], T0 [b,3]: None takes the defaults
+        `generate_sequence` states.  No buffer aliases an input: the loop updates R0 / T0, the seed and the seed frames in place."""
+        bm, dev, f32 = self.body_model, self.device, torch.float32
+        if bm.M != 67:
+            raise ValueError(f"the body model carries {bm.M} markers, the motion prior works on 67")
+        b, rows, zd = X.shape[1], X.shape[1] * M, self.model.predictor.z_dim
+        if z is None:
+            z = torch.randn(K, rows, zd, device=dev)
+        else:
+            z = self._dev(z, "z").contiguous()
+            if z.shape != (K, rows, zd):
+                raise ValueError(f"z must be [{K},{rows},{zd}], got {tuple(z.shape)}")
+        if reproj_factor is None:
+            reproj_factor = _section(self.predictorcfg, "modelconfig").get("reproj_factor", 0.5)
+        R0 = torch.eye(3, device=dev, dtype=f32).repeat(b, 1, 1) if R0 is None else self._dev(R0, "R0").reshape(b, 3, 3)
+        T0 = torch.zeros(b, 3, device=dev, dtype=f32) if T0 is None else self._dev(T0, "T0").reshape(b, 3)
+        rep = lambda t, dim=0: t.repeat_interleave(M, dim=dim).contiguous()
+        new = lambda *shape: torch.empty(*shape, device=dev, dtype=f32)
+        bt = rep(bt)
+        s = {"rf": float(reproj_factor), "z": z, "bt": bt, "R0": rep(R0), "T0": rep(T0), "scene": None, "rows_scene": None,
+             "xs": [rep(X, 1), new(2, rows, NM3)],                  # seed markers [2,rows,201], ping-pong (no output aliases an input)
+             "seed": rep(seed.permute(1, 0, 2)),                    # [rows,2,93]
+             "Y_gen": new(T_PRED, rows, NM3), "Yb_gen": new(T_PRED, rows, XB),
+             "lbs_out": {"joints": new(rows * T_ALL, 127, 3), "markers": new(rows * T_ALL, bm.M, 3)},
+             "markers": new(K, b, T_ALL, 67, 3), "params": new(K, b, T_ALL, XB), "rotmat": new(K, b, 3, 3), "transl": new(K, b, 3),
+             "pelvis": new(K, b, T_ALL, 3), "nonfinite": torch.zeros(1, device=dev, dtype=torch.int32),
+             # calc_calibrate_offset: joint 0 at zero orientation / translation (the body pose does not move the root)
+             "delta_T": bm.joints55(torch.zeros(rows, XB, device=dev, dtype=f32), bt, 1)[:, 0].contiguous()}
+        bm.workspace(rows * T_ALL)
+        return s
+
+    def _result(self, s, z, betas, R0, T0, to_numpy, search=None) -> PrimitiveSequence:
+        res = [s["markers"], s["params"], s["rotmat"], s["transl"], s["pelvis"], z, betas, R0, T0]
+        if to_numpy:
+            res = [t.cpu().numpy() for t in res]
+            search = search and {k: v.cpu().numpy() if torch.is_tensor(v) else v for k, v in search.items()}
+        gender = str(_section(self.regressorcfg, "modelconfig").get("gender", "male"))
+        return PrimitiveSequence(*res[:7], gender, res[7], res[8], search=search)
+
+    def _primitive(self, s, k, dst, st, R0=None, T0=None):
+        """What every primitive begins with, over all rows of the state: sample_prior_into -> egx_assemble_params into `dst`
+        [rows,20,93] -> BodyModelHandle.forward into s["lbs_out"], with the penetration counts of the bodies in the frames R0 / T0
+        where the state holds a scene.  Launches only."""
+        cur, rows = s["xs"][k % 2], dst.shape[0]
+        self.model.sample_prior_into(cur[0], cur[1], NM3, s["bt"], s["z"][k], s["Y_gen"], s["Yb_gen"])
+        _lib.check(_lib.load().egx_assemble_params(_lib.ptr(s["seed"]), _lib.ptr(s["Yb_gen"]), rows, _lib.ptr(dst), st), "egx_assemble_params")
+        in_scene = {} if s["scene"] is None else {"sdf": s["scene"], "R0": R0, "T0": T0, "agent_scene": s["rows_scene"]}
+        self.body_model.forward(dst.view(rows * T_ALL, XB), s["bt"], T_ALL, want_verts=False, want_joints=True, want_markers=True,
+                                out=s["lbs_out"], **in_scene)
+
+    @staticmethod
+    def _handoff_lead(s):
+        """The nine arguments that follow pred_params in the three hand-off entries, built once per loop: only the seed frames
+        read depend on k, and they alternate, so `[k % 2]` of the result is the tuple of primitive k."""
+        lbs = s["lbs_out"]
+        return [(_lib.ptr(s["Y_gen"]), _vp(x[0]), _vp(x[1]), NM3, _lib.ptr(lbs["joints"]), 127, _lib.ptr(lbs["markers"]), _lib.ptr(s["delta_T"]),
+                 s["rf"]) for x in s["xs"]]
+
+    @staticmethod
+    def _select_lead(s, R0s, T0s):
+        """The sixteen leading arguments of the two selection entries, likewise `[k % 2]`; R0s / T0s: the frames of the rows at
+        even and at odd k."""
+        lbs = s["lbs_out"]
+        return [(_lib.ptr(s["Y_gen"]), _vp(x[0]), _vp(x[1]), NM3, _lib.ptr(lbs["joints"]), 127, _lib.ptr(lbs["markers"]), _lib.ptr(R0),
+                 _lib.ptr(T0), _lib.ptr(lbs.get("pene_count")), _lib.ptr(s["goal"]), _lib.ptr(s["feet"]), s["weights"], s["pene_thres"],
+                 s["goal_thresh"], s["rf"]) for x, R0, T0 in zip(s["xs"], R0s, T0s)]
+
+    # ------------------------------------------------------------------------------------------------------------------
     def generate_sequence(self, data, bparams, betas, n_primitives: int, n_gens: int = -1, z=None, reproj_factor=None,
                           to_numpy: bool = True, R0=None, T0=None) -> PrimitiveSequence:
         """A chain of `n_primitives` primitives from the motion seed (data [>=2,b,>=201], bparams [>=2,b,93] in the seed's
@@ -239,66 +321,23 @@ class GAMMAPrimitiveComboGenOP:
         if K < 1:
             raise ValueError("n_primitives must be >= 1")
         X, seed, bt = self._seed_inputs(data, bparams, betas, n_gens, None)
-        B, dev, f32 = X.shape[1], self.device, torch.float32
-        zd = self.model.predictor.z_dim
-        if z is None:
-            z = torch.randn(K, B, zd, device=dev)
-        else:
-            z = self._dev(z, "z").contiguous()
-            if z.shape != (K, B, zd):
-                raise ValueError(f"z must be [{K},{B},{zd}], got {tuple(z.shape)}")
-        if reproj_factor is None:
-            reproj_factor = _section(self.predictorcfg, "modelconfig").get("reproj_factor", 0.5)
-        rf = float(reproj_factor)
-        eye = torch.eye(3, device=dev, dtype=f32)
-        R0 = eye.repeat(B, 1, 1) if R0 is None else self._dev(R0, "R0").reshape(B, 3, 3).clone()
-        T0 = torch.zeros(B, 3, device=dev, dtype=f32) if T0 is None else self._dev(T0, "T0").reshape(B, 3).clone()
-        R0, T0 = R0.contiguous(), T0.contiguous()
-        markers = torch.empty(K, B, T_ALL, 67, 3, device=dev, dtype=f32)
-        params = torch.empty(K, B, T_ALL, XB, device=dev, dtype=f32)
-        rotmat = torch.empty(K, B, 3, 3, device=dev, dtype=f32)
-        transl = torch.empty(K, B, 3, device=dev, dtype=f32)
-        pelvis = torch.empty(K, B, T_ALL, 3, device=dev, dtype=f32)
-        xs = [X.contiguous(), torch.empty_like(X)]                  # seed markers [2,B,201], ping-pong (no output aliases an input)
-        seed = seed.permute(1, 0, 2).contiguous()                   # [B,2,93]
-        Y_gen = torch.empty(T_PRED, B, NM3, device=dev, dtype=f32)
-        Yb_gen = torch.empty(T_PRED, B, XB, device=dev, dtype=f32)
-        nonfinite = torch.zeros(1, device=dev, dtype=torch.int32)
-        bm = self.body_model
-        lbs_out = {"joints": torch.empty(B * T_ALL, 127, 3, device=dev, dtype=f32),
-                   "markers": torch.empty(B * T_ALL, bm.M, 3, device=dev, dtype=f32)}
-        if bm.M != 67:
-            raise ValueError(f"the body model carries {bm.M} markers, the motion prior works on 67")
-        # calc_calibrate_offset: joint 0 at zero orientation / translation (the body pose does not move the root)
-        delta_T = bm.joints55(torch.zeros(B, XB, device=dev, dtype=f32), bt, 1)[:, 0].contiguous()
-        bm.workspace(B * T_ALL)
-        self._advance_loop(K, B, rf, z, bt, xs, seed, Y_gen, Yb_gen, lbs_out, delta_T, R0, T0, markers, params, rotmat, transl,
-                           pelvis, nonfinite)
-        n = int(nonfinite.item())
+        s = self._chain_state(X, seed, bt, K, 1, z, reproj_factor, R0, T0)
+        self._advance_loop(K, X.shape[1], s)
+        n = int(s["nonfinite"].item())
         if n:
             raise FloatingPointError(f"{n} primitives of the chain produced non-finite values")
-        res = [markers, params, rotmat, transl, pelvis, z, bt, R0, T0]
-        if to_numpy:
-            res = [t.cpu().numpy() for t in res]
-        gender = str(_section(self.regressorcfg, "modelconfig").get("gender", "male"))
-        return PrimitiveSequence(*res[:7], gender, res[7], res[8])
+        return self._result(s, s["z"], bt, s["R0"], s["T0"], to_numpy)
 
-    def _advance_loop(self, K, B, rf, z, bt, xs, seed, Y_gen, Yb_gen, lbs_out, delta_T, R0, T0, markers, params, rotmat, transl,
-                      pelvis, nonfinite):
+    def _advance_loop(self, K, B, s):
         """The primitive loop of `generate_sequence`: launches only, no allocation that depends on k, no host wait."""
-        lib, bm = _lib.load(), self.body_model
-        st = _lib.current_stream_ptr()
+        lib, st, hand = _lib.load(), _lib.current_stream_ptr(), self._handoff_lead(s)
         for k in range(K):
-            cur, nxt = xs[k % 2], xs[(k + 1) % 2]
-            self.model.sample_prior_into(cur[0], cur[1], NM3, bt, z[k], Y_gen, Yb_gen)
-            pp = params[k]
-            _lib.check(lib.egx_assemble_params(_lib.ptr(seed), _lib.ptr(Yb_gen), B, _lib.ptr(pp), st), "egx_assemble_params")
-            bm.forward(pp.view(B * T_ALL, XB), bt, T_ALL, want_verts=False, want_joints=True, want_markers=True, out=lbs_out)
+            nxt, pp = s["xs"][(k + 1) % 2], s["params"][k]          # assembled straight into the record
+            self._primitive(s, k, pp, st)
             _lib.check(lib.egx_primitive_advance(
-                _lib.ptr(pp), _lib.ptr(Y_gen), C.c_void_p(cur[0].data_ptr()), C.c_void_p(cur[1].data_ptr()), NM3,
-                _lib.ptr(lbs_out["joints"]), 127, _lib.ptr(lbs_out["markers"]), _lib.ptr(delta_T), rf, B, _lib.ptr(R0), _lib.ptr(T0),
-                _lib.ptr(markers[k]), _lib.ptr(pelvis[k]), _lib.ptr(rotmat[k]), _lib.ptr(transl[k]), _lib.ptr(seed),
-                C.c_void_p(nxt[0].data_ptr()), C.c_void_p(nxt[1].data_ptr()), NM3, _lib.ptr(nonfinite), st), "egx_primitive_advance")
+                _vp(pp), *hand[k % 2], B, _lib.ptr(s["R0"]), _lib.ptr(s["T0"]), _vp(s["markers"][k]), _vp(s["pelvis"][k]),
+                _vp(s["rotmat"][k]), _vp(s["transl"][k]), _lib.ptr(s["seed"]), _vp(nxt[0]), _vp(nxt[1]), NM3, _lib.ptr(s["nonfinite"]), st),
+                "egx_primitive_advance")
 
     # ------------------------------------------------------------------------------------------------------------------
     def generate_sequence_to_goal(self, data, bparams, betas, goal, n_primitives: int, n_candidates: int, scene=None,
@@ -347,7 +386,6 @@ class GAMMAPrimitiveComboGenOP:
         M = W * N       # rows per sequence
         X, seed, bt = self._seed_inputs(data, bparams, betas, -1, None)
         b, dev, f32, i32 = X.shape[1], self.device, torch.float32, torch.int32
-        BN = b * M
         goal = self._dev(goal, "goal")
         if goal.shape == (3,):
             goal = goal.reshape(1, 3).repeat(b, 1)
@@ -374,47 +412,16 @@ class GAMMAPrimitiveComboGenOP:
             w.update({k: float(v) for k, v in weights.items()})
         if goal_thresh is None:
             goal_thresh = self.testconfig.get("goal_thresh", 0.1)
-        zd = self.model.predictor.z_dim
-        if z is None:
-            z = torch.randn(K, BN, zd, device=dev)
-        else:
-            z = self._dev(z, "z").contiguous()
-            if z.shape != (K, BN, zd):
-                raise ValueError(f"z must be [{K},{BN},{zd}], got {tuple(z.shape)}")
-        if reproj_factor is None:
-            reproj_factor = _section(self.predictorcfg, "modelconfig").get("reproj_factor", 0.5)
-        bm = self.body_model
-        if bm.M != 67:
-            raise ValueError(f"the body model carries {bm.M} markers, the motion prior works on 67")
-        eye = torch.eye(3, device=dev, dtype=f32)
-        R0 = eye.repeat(b, 1, 1) if R0 is None else self._dev(R0, "R0").reshape(b, 3, 3)
-        T0 = torch.zeros(b, 3, device=dev, dtype=f32) if T0 is None else self._dev(T0, "T0").reshape(b, 3)
-        rep = lambda t, dim=0: t.repeat_interleave(M, dim=dim).contiguous()
-        bt_rows = rep(bt)
-        s = {"rf": float(reproj_factor), "z": z, "bt": bt_rows, "R0": rep(R0), "T0": rep(T0), "goal": goal,
-             "xs": [rep(X, 1), torch.empty(2, BN, NM3, device=dev, dtype=f32)],            # seed markers, ping-pong
-             "seed": rep(seed.permute(1, 0, 2)),                                             # [BN,2,93]
-             "pp": torch.empty(BN, T_ALL, XB, device=dev, dtype=f32),
-             "Y_gen": torch.empty(T_PRED, BN, NM3, device=dev, dtype=f32), "Yb_gen": torch.empty(T_PRED, BN, XB, device=dev, dtype=f32),
-             "lbs_out": {"joints": torch.empty(BN * T_ALL, 127, 3, device=dev, dtype=f32),
-                         "markers": torch.empty(BN * T_ALL, bm.M, 3, device=dev, dtype=f32)},
-             "scene": scene, "rows_scene": rows_scene,
-             "feet": torch.tensor(synth.feet_marker_idx(), device=dev, dtype=i32),
-             "weights": (C.c_float * 5)(*[w[k] for k in ("goal", "skate", "floor", "pene", "face")]),
-             "pene_thres": float(pene_thres), "goal_thresh": float(goal_thresh),
-             "markers": torch.empty(K, b, T_ALL, 67, 3, device=dev, dtype=f32), "params": torch.empty(K, b, T_ALL, XB, device=dev, dtype=f32),
-             "rotmat": torch.empty(K, b, 3, 3, device=dev, dtype=f32), "transl": torch.empty(K, b, 3, device=dev, dtype=f32),
-             "pelvis": torch.empty(K, b, T_ALL, 3, device=dev, dtype=f32),
-             "choice": torch.empty(K, b, device=dev, dtype=i32), "status": torch.empty(K, b, device=dev, dtype=i32),
-             "reached": torch.empty(K, b, device=dev, dtype=i32), "goal_dist": torch.empty(K, b, device=dev, dtype=f32),
-             "cost": torch.empty(K, b, M, device=dev, dtype=f32), "cost_terms": torch.empty(K, b, M, 5, device=dev, dtype=f32),
-             "colliding": torch.empty(K, b, M, device=dev, dtype=i32),
-             "nonfinite": torch.zeros(1, device=dev, dtype=i32)}
+        s = self._chain_state(X, seed, bt, K, M, z, reproj_factor, R0, T0)
+        rec = lambda *tail, dtype=f32: torch.empty(K, b, *tail, device=dev, dtype=dtype)
+        s.update({"goal": goal, "scene": scene, "rows_scene": rows_scene, "pp": torch.empty(b * M, T_ALL, XB, device=dev, dtype=f32),
+                  "feet": torch.tensor(synth.feet_marker_idx(), device=dev, dtype=i32),
+                  "weights": (C.c_float * 5)(*[w[k] for k in ("goal", "skate", "floor", "pene", "face")]),
+                  "pene_thres": float(pene_thres), "goal_thresh": float(goal_thresh),
+                  "choice": rec(dtype=i32), "status": rec(dtype=i32), "reached": rec(dtype=i32), "goal_dist": rec(),
+                  "cost": rec(M), "cost_terms": rec(M, 5), "colliding": rec(M, dtype=i32)})
         if scene is not None:
-            s["lbs_out"]["pene_count"] = torch.empty(BN * T_ALL, device=dev, dtype=i32)
-        # calc_calibrate_offset: joint 0 at zero orientation / translation (the body pose does not move the root)
-        s["delta_T"] = bm.joints55(torch.zeros(BN, XB, device=dev, dtype=f32), bt_rows, 1)[:, 0].contiguous()
-        bm.workspace(BN * T_ALL)
+            s["lbs_out"]["pene_count"] = torch.empty(b * M * T_ALL, device=dev, dtype=i32)
         status = s["status"]
         if W == 1:
             self._search_loop(K, b, N, s)
@@ -425,96 +432,60 @@ class GAMMAPrimitiveComboGenOP:
                                          f"candidates were all non-finite")
             R0_end, T0_end = s["R0"], s["T0"]
         else:
-            slot = lambda *tail, dtype=f32: torch.empty(K, b, W, *tail, device=dev, dtype=dtype)
             s.update({"R0s": [s["R0"], torch.empty_like(s["R0"])], "T0s": [s["T0"], torch.empty_like(s["T0"])],      # ping-pong
                       "acc": torch.zeros(K + 1, b, W, device=dev, dtype=f32), "ncoll": torch.zeros(K + 1, b, W, device=dev, dtype=i32),
-                      "rec_markers": slot(T_ALL, 67, 3), "rec_params": slot(T_ALL, XB), "rec_rotmat": slot(3, 3), "rec_transl": slot(3),
-                      "rec_pelvis": slot(T_ALL, 3), "beam_row": slot(dtype=i32), "parent": slot(dtype=i32), "path_cost": slot(),
-                      "beam_status": slot(dtype=i32), "slot_goal_dist": slot(), "slot_reached": slot(dtype=i32),
-                      "path_slot": torch.empty(K, b, device=dev, dtype=i32)})
+                      "rec_markers": rec(W, T_ALL, 67, 3), "rec_params": rec(W, T_ALL, XB), "rec_rotmat": rec(W, 3, 3),
+                      "rec_transl": rec(W, 3), "rec_pelvis": rec(W, T_ALL, 3), "beam_row": rec(W, dtype=i32), "parent": rec(W, dtype=i32),
+                      "path_cost": rec(W), "beam_status": rec(W, dtype=i32), "slot_goal_dist": rec(W), "slot_reached": rec(W, dtype=i32),
+                      "path_slot": rec(dtype=i32)})
             self._beam_loop(K, b, W, N, s)
-            bad = (status & 6).ne(0)
-            n = int(bad.sum().item())
+            n = int((status & 6).ne(0).sum().item())
             if n:
                 raise FloatingPointError(f"the beam search produced non-finite values: {n} nodes of the returned paths")
             R0_end, T0_end = s["R0s"][K % 2], s["T0s"][K % 2]      # the rows of slot 0: where the path ends
-        reached = s["reached"].ne(0)
+        reached, zd = s["reached"].ne(0), s["z"].shape[-1]
         first = torch.where(reached.any(0), reached.int().argmax(0) + 1, torch.full((b,), K, device=dev, dtype=torch.int64))
-        zc = z.view(K, b, M, zd).gather(2, s["choice"].long().view(K, b, 1, 1).expand(K, b, 1, zd))[:, :, 0]
-        res = [s["markers"], s["params"], s["rotmat"], s["transl"], s["pelvis"], zc, bt, R0_end[::M].reshape(b, 3, 3).contiguous(),
-               T0_end[::M].contiguous()]
+        zc = s["z"].view(K, b, M, zd).gather(2, s["choice"].long().view(K, b, 1, 1).expand(K, b, 1, zd))[:, :, 0]
         search = {"goal": goal, "choice": s["choice"], "cost": s["cost"], "cost_terms": s["cost_terms"], "colliding": s["colliding"],
                   "status": status, "goal_dist": s["goal_dist"], "n_valid": first}
         if W > 1:
-            search.update({k: s[k] for k in ("path_slot", "parent", "beam_row", "path_cost", "beam_status")})
-        if to_numpy:
-            res = [t.cpu().numpy() for t in res]
-            search = {k: v.cpu().numpy() for k, v in search.items()}
-        if W > 1:
-            search["beam_width"] = W
-        gender = str(_section(self.regressorcfg, "modelconfig").get("gender", "male"))
-        return PrimitiveSequence(*res[:7], gender, res[7], res[8], search=search)
+            search.update({k: s[k] for k in ("path_slot", "parent", "beam_row", "path_cost", "beam_status")}, beam_width=W)
+        return self._result(s, zc, bt, R0_end[::M].reshape(b, 3, 3).contiguous(), T0_end[::M].contiguous(), to_numpy, search)
 
     def _search_loop(self, K, b, N, s):
         """The primitive loop of `generate_sequence_to_goal`: launches only, no allocation that depends on k, no host wait."""
-        lib, bm = _lib.load(), self.body_model
-        st = _lib.current_stream_ptr()
-        BN = b * N
-        lbs, scene = s["lbs_out"], s["scene"]
-        vp = lambda t: C.c_void_p(t.data_ptr())
+        lib, st, hand, pp = _lib.load(), _lib.current_stream_ptr(), self._handoff_lead(s), _lib.ptr(s["pp"])
+        sel = self._select_lead(s, [s["R0"]] * 2, [s["T0"]] * 2)
         for k in range(K):
-            cur, nxt = s["xs"][k % 2], s["xs"][(k + 1) % 2]
-            self.model.sample_prior_into(cur[0], cur[1], NM3, s["bt"], s["z"][k], s["Y_gen"], s["Yb_gen"])
-            _lib.check(lib.egx_assemble_params(_lib.ptr(s["seed"]), _lib.ptr(s["Yb_gen"]), BN, _lib.ptr(s["pp"]), st), "egx_assemble_params")
-            if scene is None:
-                bm.forward(s["pp"].view(BN * T_ALL, XB), s["bt"], T_ALL, want_verts=False, want_joints=True, want_markers=True, out=lbs)
-            else:
-                bm.forward(s["pp"].view(BN * T_ALL, XB), s["bt"], T_ALL, want_verts=False, want_joints=True, want_markers=True, out=lbs,
-                           sdf=scene, R0=s["R0"], T0=s["T0"], agent_scene=s["rows_scene"])
+            nxt = s["xs"][(k + 1) % 2]
+            self._primitive(s, k, s["pp"], st, s["R0"], s["T0"])
             _lib.check(lib.egx_primitive_select(
-                _lib.ptr(s["Y_gen"]), vp(cur[0]), vp(cur[1]), NM3, _lib.ptr(lbs["joints"]), 127, _lib.ptr(lbs["markers"]),
-                _lib.ptr(s["R0"]), _lib.ptr(s["T0"]), _lib.ptr(lbs.get("pene_count")), _lib.ptr(s["goal"]), _lib.ptr(s["feet"]),
-                s["weights"], s["pene_thres"], s["goal_thresh"], s["rf"], b, N, vp(s["choice"][k]), vp(s["status"][k]),
-                vp(s["reached"][k]), vp(s["goal_dist"][k]), vp(s["cost"][k]), vp(s["cost_terms"][k]), vp(s["colliding"][k]), st),
-                "egx_primitive_select")
+                *sel[k % 2], b, N, _vp(s["choice"][k]), _vp(s["status"][k]), _vp(s["reached"][k]),
+                _vp(s["goal_dist"][k]), _vp(s["cost"][k]), _vp(s["cost_terms"][k]), _vp(s["colliding"][k]), st), "egx_primitive_select")
             _lib.check(lib.egx_primitive_advance_select(
-                _lib.ptr(s["pp"]), _lib.ptr(s["Y_gen"]), vp(cur[0]), vp(cur[1]), NM3, _lib.ptr(lbs["joints"]), 127,
-                _lib.ptr(lbs["markers"]), _lib.ptr(s["delta_T"]), s["rf"], b, vp(s["choice"][k]), N, _lib.ptr(s["R0"]), _lib.ptr(s["T0"]),
-                vp(s["markers"][k]), vp(s["pelvis"][k]), vp(s["rotmat"][k]), vp(s["transl"][k]), vp(s["params"][k]), _lib.ptr(s["seed"]),
-                vp(nxt[0]), vp(nxt[1]), NM3, _lib.ptr(s["nonfinite"]), st), "egx_primitive_advance_select")
+                pp, *hand[k % 2], b, _vp(s["choice"][k]), N, _lib.ptr(s["R0"]), _lib.ptr(s["T0"]), _vp(s["markers"][k]),
+                _vp(s["pelvis"][k]), _vp(s["rotmat"][k]), _vp(s["transl"][k]), _vp(s["params"][k]), _lib.ptr(s["seed"]), _vp(nxt[0]),
+                _vp(nxt[1]), NM3, _lib.ptr(s["nonfinite"]), st), "egx_primitive_advance_select")
 
     def _beam_loop(self, K, b, W, N, s):
         """The primitive loop of the beam search and the backtrack after it: launches only, no allocation that depends on k, no
         host wait.  R0 / T0 and the seed frames are read from one buffer and written to the other: a slot may continue from a row
         of another slot of its sequence."""
-        lib, bm = _lib.load(), self.body_model
-        st = _lib.current_stream_ptr()
-        BN = b * W * N
-        lbs, scene = s["lbs_out"], s["scene"]
-        vp = lambda t: C.c_void_p(t.data_ptr())
+        lib, st, hand, pp = _lib.load(), _lib.current_stream_ptr(), self._handoff_lead(s), _lib.ptr(s["pp"])
+        sel = self._select_lead(s, s["R0s"], s["T0s"])
         for k in range(K):
-            cur, nxt = s["xs"][k % 2], s["xs"][(k + 1) % 2]
+            nxt = s["xs"][(k + 1) % 2]
             R0, T0, R0n, T0n = s["R0s"][k % 2], s["T0s"][k % 2], s["R0s"][(k + 1) % 2], s["T0s"][(k + 1) % 2]
-            self.model.sample_prior_into(cur[0], cur[1], NM3, s["bt"], s["z"][k], s["Y_gen"], s["Yb_gen"])
-            _lib.check(lib.egx_assemble_params(_lib.ptr(s["seed"]), _lib.ptr(s["Yb_gen"]), BN, _lib.ptr(s["pp"]), st), "egx_assemble_params")
-            if scene is None:
-                bm.forward(s["pp"].view(BN * T_ALL, XB), s["bt"], T_ALL, want_verts=False, want_joints=True, want_markers=True, out=lbs)
-            else:
-                bm.forward(s["pp"].view(BN * T_ALL, XB), s["bt"], T_ALL, want_verts=False, want_joints=True, want_markers=True, out=lbs,
-                           sdf=scene, R0=R0, T0=T0, agent_scene=s["rows_scene"])
+            self._primitive(s, k, s["pp"], st, R0, T0)
             _lib.check(lib.egx_primitive_beam_select(
-                _lib.ptr(s["Y_gen"]), vp(cur[0]), vp(cur[1]), NM3, _lib.ptr(lbs["joints"]), 127, _lib.ptr(lbs["markers"]),
-                _lib.ptr(R0), _lib.ptr(T0), _lib.ptr(lbs.get("pene_count")), _lib.ptr(s["goal"]), _lib.ptr(s["feet"]),
-                s["weights"], s["pene_thres"], s["goal_thresh"], s["rf"], b, W, N, vp(s["acc"][k]), vp(s["ncoll"][k]),
-                vp(s["cost"][k]), vp(s["cost_terms"][k]), vp(s["colliding"][k]), vp(s["beam_row"][k]), vp(s["parent"][k]),
-                vp(s["acc"][k + 1]), vp(s["ncoll"][k + 1]), vp(s["path_cost"][k]), vp(s["beam_status"][k]), vp(s["slot_goal_dist"][k]),
-                vp(s["slot_reached"][k]), st), "egx_primitive_beam_select")
+                *sel[k % 2], b, W, N, _vp(s["acc"][k]), _vp(s["ncoll"][k]), _vp(s["cost"][k]), _vp(s["cost_terms"][k]),
+                _vp(s["colliding"][k]), _vp(s["beam_row"][k]), _vp(s["parent"][k]), _vp(s["acc"][k + 1]), _vp(s["ncoll"][k + 1]),
+                _vp(s["path_cost"][k]), _vp(s["beam_status"][k]), _vp(s["slot_goal_dist"][k]), _vp(s["slot_reached"][k]), st),
+                "egx_primitive_beam_select")
             _lib.check(lib.egx_primitive_advance_beam(
-                _lib.ptr(s["pp"]), _lib.ptr(s["Y_gen"]), vp(cur[0]), vp(cur[1]), NM3, _lib.ptr(lbs["joints"]), 127,
-                _lib.ptr(lbs["markers"]), _lib.ptr(s["delta_T"]), s["rf"], b, W, N, vp(s["beam_row"][k]), _lib.ptr(R0), _lib.ptr(T0),
-                _lib.ptr(R0n), _lib.ptr(T0n), vp(s["rec_markers"][k]), vp(s["rec_pelvis"][k]), vp(s["rec_rotmat"][k]),
-                vp(s["rec_transl"][k]), vp(s["rec_params"][k]), _lib.ptr(s["seed"]), vp(nxt[0]), vp(nxt[1]), NM3,
-                vp(s["beam_status"][k]), st), "egx_primitive_advance_beam")
+                pp, *hand[k % 2], b, W, N, _vp(s["beam_row"][k]), _lib.ptr(R0), _lib.ptr(T0), _lib.ptr(R0n), _lib.ptr(T0n),
+                _vp(s["rec_markers"][k]), _vp(s["rec_pelvis"][k]), _vp(s["rec_rotmat"][k]), _vp(s["rec_transl"][k]), _vp(s["rec_params"][k]),
+                _lib.ptr(s["seed"]), _vp(nxt[0]), _vp(nxt[1]), NM3, _vp(s["beam_status"][k]), st), "egx_primitive_advance_beam")
         _lib.check(lib.egx_beam_backtrack(
             _lib.ptr(s["parent"]), _lib.ptr(s["beam_row"]), _lib.ptr(s["beam_status"]), _lib.ptr(s["slot_goal_dist"]),
             _lib.ptr(s["slot_reached"]), _lib.ptr(s["rec_markers"]), _lib.ptr(s["rec_pelvis"]), _lib.ptr(s["rec_rotmat"]),

@@ -96,7 +96,9 @@ def main():
     op._advance_loop = real
     assert bool(torch.isfinite(res.markers).all())
     la = kept["args"]
-    (_, _, rf, _, bt, xs, seed, Y_gen, Yb_gen, lbs_out, delta_T, R0, T0, markers, params, rotmat, transl, pelvis, nonfinite) = la
+    s = la[2]                       # the state dict of _advance_loop(K, B, s)
+    rf, xs, seed, Y_gen, lbs_out, delta_T, R0, T0 = (s[k] for k in ("rf", "xs", "seed", "Y_gen", "lbs_out", "delta_T", "R0", "T0"))
+    markers, params, rotmat, transl, pelvis, nonfinite = (s[k] for k in ("markers", "params", "rotmat", "transl", "pelvis", "nonfinite"))
     loop = lambda: real(*la)
 
     # ---- the kernel alone, on the buffers the loop left behind (primitive K - 1), and the torch-op composition of the same hand-off

@@ -1,7 +1,7 @@
 """GPU checks of the beam search over motion primitives: kernels egx_primitive_beam_select, egx_primitive_advance_beam and
 egx_beam_backtrack (csrc/genop.hip) and `GAMMAPrimitiveComboGenOP.generate_sequence_to_goal(..., beam_width=W)`.
 
-Yardsticks.  Values: `held()` of tests/test_genop_gpu.py (R = 3 against the float32 restatement's own distance from float64,
+Yardsticks.  Values: `held()` of tests/genop_gpu_helpers.py (R = 3 against the float32 restatement's own distance from float64,
 tests/genop_beam_ref.py on tests/genop_search_ref.py::score), at least 64 rows pooled per case as in tests/test_genop_search_gpu.py.
 Slots: equal to the float64 selection for every DECIDABLE group - one in which every adjacent gap among the float64 top W + 1 keys
 of equal (nonfinite, ncoll) exceeds 6 x the group's largest |path_cost32 - path_cost64| (3 x for each of the two costs compared);
@@ -19,9 +19,9 @@ import torch
 
 from tests import genop_beam_ref as bref, genop_search_ref as sref
 from tests.test_genop_beam_cpu import GOAL_ONLY, beam_cases
-from tests.test_genop_gpu import CFG_RF, ROOT, V_SMALL, _aa2R64, _inputs, _launch, emit, held, small_world  # noqa: F401
-from tests.test_genop_search_gpu import (MIN_GROUP, POOL, UNDECIDABLE_CAP, W_ORDER, W_TEST, _advance_select, _feet, _handmade, _restate,
-                                         _rows_inputs, _select, search_world)  # noqa: F401
+from tests.genop_gpu_helpers import (CFG_RF, MIN_GROUP, POOL, ROOT, UNDECIDABLE_CAP, V_SMALL, W_TEST, _aa2R64, _advance_beam, _advance_select,
+                                     _beam_select, _feet, _handmade, _inputs, _launch, _restate, _rows_inputs, _select, emit, held, patched_loop,
+                                     search_world, small_world)  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -33,50 +33,6 @@ def _slot_state(b, W, seed):
     """random non-zero acc [b,W] (float32) and ncoll [b,W] of the paths into the slots"""
     g = torch.Generator().manual_seed(seed)
     return torch.rand(b, W, generator=g) * 2.0 + 0.01, torch.randint(0, 3, (b, W), generator=g).int()
-
-
-def _beam_select(x, W, N, jpb, acc=None, ncoll=None, rf=CFG_RF, weights=W_TEST, pene_thres=40.0, goal_thresh=0.1, nan_face_rows=(), b=None,
-                 group0=0):
-    """egx_primitive_beam_select on the groups [group0, group0 + b) of the row set x (W * N rows each) -> (outputs, inputs as
-    launched); the inputs are built as tests/test_genop_search_gpu.py::_select builds them"""
-    from egogen_amd import _lib
-    lib = _lib.load()
-    b = x["b"] if b is None else b
-    M = W * N
-    assert x["N"] == M
-    sl = slice(group0 * M, (group0 + b) * M)
-    rows = x["rows"][sl].cuda()
-    d = x["pool"]
-    n = b * M
-    per = lambda t: t.reshape(POOL, 20, *t.shape[1:])[rows].reshape(n * 20, *t.shape[1:]).contiguous()
-    Yg = d["Y_gen"][:, rows].contiguous()
-    X = d["X"][:, rows].contiguous()
-    J = per(d["j127"] if jpb == 127 else d["j55"])
-    for r in nan_face_rows:
-        J.view(n, 20, jpb, 3)[r, 19, 2, 0] = float("nan")
-    mp = per(d["mproj"])
-    R0, T0 = x["R0"][sl].cuda().contiguous(), x["T0"][sl].cuda().contiguous()
-    goal = x["goal"][group0:group0 + b].cuda().contiguous()
-    pene = None if x["pene"] is None else x["pene"][sl].cuda().reshape(-1).contiguous()
-    feet = torch.tensor(_feet(), dtype=torch.int32, device="cuda")
-    acc = torch.zeros(b, W) if acc is None else acc
-    ncoll = torch.zeros(b, W, dtype=torch.int32) if ncoll is None else ncoll
-    acc_d, ncoll_d = acc.float().cuda().contiguous(), ncoll.int().cuda().contiguous()
-    fi = lambda *s: torch.full(s, -7, dtype=torch.int32, device="cuda")
-    ff = lambda *s: torch.full(s, float("nan"), device="cuda")
-    o = {"cost": ff(b, M), "terms": ff(b, M, 5), "colliding": fi(b, M), "beam_row": fi(b, W), "parent": fi(b, W), "acc": ff(b, W),
-         "ncoll": fi(b, W), "path_cost": ff(b, W), "status": fi(b, W), "goal_dist": ff(b, W), "reached": fi(b, W)}
-    w = (C.c_float * 5)(*[weights[k] for k in W_ORDER])
-    _lib.check(lib.egx_primitive_beam_select(
-        _lib.ptr(Yg), C.c_void_p(X[0].data_ptr()), C.c_void_p(X[1].data_ptr()), 201, _lib.ptr(J), jpb, _lib.ptr(mp), _lib.ptr(R0),
-        _lib.ptr(T0), _lib.ptr(pene), _lib.ptr(goal), _lib.ptr(feet), w, float(pene_thres), float(goal_thresh), float(rf), b, W, N,
-        _lib.ptr(acc_d), _lib.ptr(ncoll_d), _lib.ptr(o["cost"]), _lib.ptr(o["terms"]), _lib.ptr(o["colliding"]), _lib.ptr(o["beam_row"]),
-        _lib.ptr(o["parent"]), _lib.ptr(o["acc"]), _lib.ptr(o["ncoll"]), _lib.ptr(o["path_cost"]), _lib.ptr(o["status"]),
-        _lib.ptr(o["goal_dist"]), _lib.ptr(o["reached"]), _lib.current_stream_ptr()), "egx_primitive_beam_select")
-    torch.cuda.synchronize()
-    i = {"Y_gen": Yg, "X": X, "J": J.reshape(n, 20, jpb, 3), "mp": mp.reshape(n, 20, 67, 3), "R0": R0, "T0": T0,
-         "goal_rows": goal.repeat_interleave(M, 0), "pene": None if pene is None else pene.reshape(n, 20)}
-    return {k: v.cpu() for k, v in o.items()}, i
 
 
 def beam_decidable(cost64, terms64, coll, acc, ncoll, W, N, cost32, acc64=None):
@@ -189,37 +145,6 @@ def test_beam_select_group_does_not_depend_on_batch(small_world):
 
 
 # ----------------------------------------------------------------------------------------------------------------------
-def _advance_beam(d, rows, beam_row, W, N, jpb, rf, status=None, nan_rows=()):
-    """egx_primitive_advance_beam on the rows `rows` (b * W * N pool rows) of the input set d; beam_row [b,W]"""
-    from egogen_amd import _lib
-    lib = _lib.load()
-    rows = torch.as_tensor(rows, device="cuda")
-    n = int(rows.numel())
-    b = n // (W * N)
-    sel = lambda t, per=1: t.reshape(-1, per, *t.shape[1:])[rows].reshape(n * per, *t.shape[1:]).contiguous()
-    pp, Yg, X = d["pp"][rows].contiguous(), d["Y_gen"][:, rows].contiguous(), d["X"][:, rows].contiguous()
-    J, mp, dT = sel(d["j127"] if jpb == 127 else d["j55"], 20), sel(d["mproj"], 20), d["delta_T"][rows].contiguous()
-    for r in nan_rows:
-        J.view(n, 20, jpb, 3)[r, 5, 0, 1] = float("nan")
-    R0, T0 = d["R0"][rows].clone().contiguous(), d["T0"][rows].clone().contiguous()
-    keep = (R0.clone(), T0.clone())
-    br = torch.as_tensor(beam_row, dtype=torch.int32, device="cuda").reshape(b, W).contiguous()
-    st = torch.zeros(b, W, dtype=torch.int32, device="cuda") if status is None else status.int().cuda().contiguous()
-    f = lambda *s: torch.full(s, float("nan"), device="cuda")
-    o = {"marker_b": f(b * W, 20, 67, 3), "pelvis": f(b * W, 20, 3), "R": f(b * W, 3, 3), "T": f(b * W, 3), "params": f(b * W, 20, 93),
-         "seed_params": f(n, 2, 93), "seed_markers": f(2, n, 201), "R0": f(n, 3, 3), "T0": f(n, 3)}
-    _lib.check(lib.egx_primitive_advance_beam(
-        _lib.ptr(pp), _lib.ptr(Yg), C.c_void_p(X[0].data_ptr()), C.c_void_p(X[1].data_ptr()), 201, _lib.ptr(J), jpb, _lib.ptr(mp),
-        _lib.ptr(dT), float(rf), b, W, N, _lib.ptr(br), _lib.ptr(R0), _lib.ptr(T0), _lib.ptr(o["R0"]), _lib.ptr(o["T0"]),
-        _lib.ptr(o["marker_b"]), _lib.ptr(o["pelvis"]), _lib.ptr(o["R"]), _lib.ptr(o["T"]), _lib.ptr(o["params"]), _lib.ptr(o["seed_params"]),
-        C.c_void_p(o["seed_markers"][0].data_ptr()), C.c_void_p(o["seed_markers"][1].data_ptr()), 201, _lib.ptr(st),
-        _lib.current_stream_ptr()), "egx_primitive_advance_beam")
-    torch.cuda.synchronize()
-    assert torch.equal(R0, keep[0]) and torch.equal(T0, keep[1])          # the input frames are only read
-    o.update(status=st, seed_markers=o["seed_markers"].permute(1, 0, 2).contiguous())
-    return o
-
-
 def _check_handoff(d, rows, beam_row, W, N, jpb):
     rows = torch.as_tensor(rows)
     b = rows.numel() // (W * N)
@@ -377,27 +302,14 @@ def test_beam_width_one_is_the_greedy_search(search_world):
     T0 = torch.tensor([[-1.0, -1.0, 0.0], [1.5, -0.2, 0.0], [1.5, -0.75, 0.0]])
     kw = dict(z=z, reproj_factor=CFG_RF, weights=W_TEST, scene=scene, T0=T0)
     want = op.generate_sequence_to_goal(w["data"], w["bparams"], w["betas"], w["goal"] + T0, K, N, **kw)
-    ran = []
-    real = op._search_loop
-    op._search_loop = lambda *a: (ran.append(a[:3]), real(*a))[1]
-    try:
+    with patched_loop(op, "_search_loop") as seen:
         got = op.generate_sequence_to_goal(w["data"], w["bparams"], w["betas"], w["goal"] + T0, K, N, beam_width=1, **kw)
-    finally:
-        op._search_loop = real
+    ran = seen.calls
     assert ran == [(K, b, N)]                                      # the greedy loop itself, not a beam of one
     for k in RESULT_FIELDS:
         assert np.array_equal(getattr(got, k), getattr(want, k)), k
     for k in got.BEAM_FIELDS:
         assert getattr(got, k) is None and k not in got.search, k
-
-
-def _spy_beam_loop(op, kept):
-    real = op._beam_loop
-
-    def spy(K, b, W, N, s):
-        real(K, b, W, N, s)
-        kept.update(s=s)
-    return real, spy
 
 
 def test_beam_chain_matches_float64(search_world, small_world):
@@ -477,14 +389,10 @@ def test_beam_path_starts_each_primitive_from_its_parent(search_world):
     op, K, b, N, W = w["op"], 2, w["b"], 2, 3
     M = W * N
     z = torch.randn(K, b * M, 128, generator=torch.Generator().manual_seed(14))
-    kept = {}
-    real, op._beam_loop = _spy_beam_loop(op, kept)
-    try:
+    with patched_loop(op, "_beam_loop") as seen:
         res = op.generate_sequence_to_goal(w["data"], w["bparams"], w["betas"], w["goal"], K, N, z=z, reproj_factor=CFG_RF, beam_width=W,
                                            to_numpy=False)
-    finally:
-        op._beam_loop = real
-    s = kept["s"]
+    s = seen.s
     rec, par, row = s["rec_params"], s["parent"].long(), s["beam_row"].long()
     assert torch.equal(par, row // N) and (par[1] != torch.arange(W, device=par.device)).any()
     handed_R, handed_T = s["R0s"][1].view(b, W, N, 3, 3), s["T0s"][1].view(b, W, N, 3)       # written by the hand-off of depth 0
@@ -514,14 +422,10 @@ def test_beam_counts_the_colliding_nodes_of_its_path(search_world):
     box = SdfScene(synth.make_sdf_scene(32))                                                   # box x 1..2, y -0.5..0.5, z 0..1
     T0 = torch.tensor([[-1.0, -1.0, 0.0], [1.5, -0.2, 0.0], [1.5, -0.75, 0.0]])               # beside, inside, at its edge
     z = torch.randn(K, b * W * N, 128, generator=torch.Generator().manual_seed(4))
-    kept = {}
-    real, op._beam_loop = _spy_beam_loop(op, kept)
-    try:
+    with patched_loop(op, "_beam_loop") as seen:
         res = op.generate_sequence_to_goal(w["data"], w["bparams"], w["betas"], w["goal"] + T0, K, N, scene=box, z=z, reproj_factor=CFG_RF,
                                            T0=T0, to_numpy=False, beam_width=W)
-    finally:
-        op._beam_loop = real
-    s = kept["s"]
+    s = seen.s
     coll = res.colliding.bool().cpu()
     emit(f"| beam scene | colliding rows per (k, sequence) | {coll.sum(-1).tolist()} | | |")
     assert coll.any() and not coll.all()
@@ -576,22 +480,9 @@ def test_beam_loop_has_no_host_wait(search_world):
     scene = SdfScene(synth.make_sdf_scene(32))
     args = (w["data"], w["bparams"], w["betas"], w["goal"])
     op.generate_sequence_to_goal(*args, 1, 2, scene=scene, beam_width=2)      # weight images, workspaces
-    real = op._beam_loop
-    ran = []
-
-    def guarded(*a):
-        old = torch.cuda.get_sync_debug_mode()
-        torch.cuda.set_sync_debug_mode("error")
-        try:
-            real(*a)
-            ran.append(a[:4])
-        finally:
-            torch.cuda.set_sync_debug_mode(old)
-    op._beam_loop = guarded
-    try:
+    with patched_loop(op, "_beam_loop", no_host_wait=True) as seen:
         res = op.generate_sequence_to_goal(*args, 3, 2, scene=scene, beam_width=2)
-    finally:
-        op._beam_loop = real
+    ran = seen.calls
     assert ran == [(3, w["b"], 2, 2)] and np.isfinite(res.markers).all()
 
 
@@ -620,23 +511,18 @@ def test_beam_raises_on_a_nonfinite_path_node(search_world, bit):
     op, K, W = w["op"], 2, 2
     args = (w["data"], w["bparams"], w["betas"], w["goal"], K, 2)
     z = torch.randn(K, w["b"] * W * 2, 128, generator=torch.Generator().manual_seed(8))
-    real = op._beam_loop
 
-    def marked(on_path):
-        def loop(K_, b, W_, N, s):
-            real(K_, b, W_, N, s)
+    def mark(on_path):
+        def then(s):
             slot = s["path_slot"][1, 1].long()
             s["beam_status"][1, 1, slot if on_path else 1 - slot] |= bit
             s["status"][1, 1] = s["beam_status"][1, 1, slot]
-        return loop
-    try:
-        op._beam_loop = marked(False)
+        return then
+    with patched_loop(op, "_beam_loop", then=mark(False)):
         op.generate_sequence_to_goal(*args, z=z, beam_width=W)
-        op._beam_loop = marked(True)
+    with patched_loop(op, "_beam_loop", then=mark(True)):
         with pytest.raises(FloatingPointError, match="non-finite"):
             op.generate_sequence_to_goal(*args, z=z, beam_width=W)
-    finally:
-        op._beam_loop = real
 
 
 def test_gen_motion_driver_beam_search(tmp_path):

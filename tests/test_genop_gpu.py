@@ -16,120 +16,11 @@ import pytest
 import torch
 
 from tests import genop_ref
+from tests.genop_gpu_helpers import (CFG_RF, R, ROOT, V_SMALL, _aa2R64, _combo, _inputs, _launch, _op, _walkers, emit, held, patched_loop,
+                                     small_world)  # noqa: F401
 from tests.helpers import load_golden, max_abs, rebuild_state_dict, seeded_prior_state_dict
 
 pytestmark = pytest.mark.gpu
-
-R = 3.0
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-V_SMALL = 2048
-CFG_RF = 0.5        # modelconfig.reproj_factor of the packaged policy configs
-
-
-def emit(line):
-    print(line)
-    path = os.environ.get("EGX_GENOP_TABLE")
-    if path:
-        with open(path, "a") as fh:
-            fh.write(line + "\n")
-
-
-def held(name, group, got, truth64, f32):
-    t = torch.as_tensor(truth64, dtype=torch.float64)
-    err = float((torch.as_tensor(got).double().cpu() - t).abs().max())
-    e32 = float((torch.as_tensor(f32).double() - t).abs().max())
-    emit(f"| {name} | {group} | {e32:.3e} | {err:.3e} | {err / e32 if e32 > 0 else float(err > 0):.2f} |")
-    assert err <= R * e32, (name, group, err, e32)
-
-
-def _aa2R64(aa):
-    from oracle.rot import tgm_angle_axis_to_rotation_matrix as aa2R
-    return aa2R(torch.as_tensor(aa).detach().cpu().double().reshape(-1, 3))
-
-
-# ----------------------------------------------------------------------------------------------------------------------
-@pytest.fixture(scope="module")
-def small_world():
-    from egogen_amd import synth
-    from egogen_amd.body_model import BodyModelHandle
-    bm = synth.make_body_model(0, num_verts=V_SMALL)
-    mk = synth.marker_ids(V_SMALL)
-    return {"bm": bm, "mk": mk, "handle": BodyModelHandle(bm, mk, synth.feet_vids(V_SMALL))}
-
-
-def _walkers(B, seed):
-    """Walking-like primitives (scripts/gen_combo_golden.py::make_sequence) in their canonical frame: xb[B,20,93], betas[B,10].
-    Body 1 (B >= 3) is yawed by almost pi, so its hip axis points the other way along x; body 2 carries a global orientation
-    of 3.1 rad (frame 18) and 3.25 rad (frame 19) about x: the large-angle branch of rot -> aa with both signs of w."""
-    g = torch.Generator().manual_seed(seed)
-    xb = torch.zeros(20, B, 93)
-    step = torch.tensor([0.0, 0.02, 0.0]) + torch.randn(1, B, 3, generator=g) * 0.004
-    xb[:, :, :3] = torch.arange(20).view(20, 1, 1) * step + torch.tensor([0.0, 0.0, 0.9])
-    xb[:, :, 3:69] = torch.randn(1, B, 66, generator=g) * 0.08 + (torch.randn(20, B, 66, generator=g) * 0.02).cumsum(0)
-    xb[:, :, 69:] = torch.randn(1, B, 24, generator=g) * 0.1
-    if B >= 3:
-        xb[:, 1, 3:6] = torch.tensor([0.0, 0.0, np.pi - 0.05]) + torch.randn(20, 3, generator=g) * 0.01
-        xb[:, 2, 3:6] = torch.tensor([3.1, 0.0, 0.0]) + torch.randn(20, 3, generator=g) * 0.01
-        xb[19, 2, 3:6] = torch.tensor([3.25, 0.01, -0.01])
-    betas = torch.randn(B, 10, generator=g) * 0.5
-    return xb.permute(1, 0, 2).contiguous(), betas.contiguous(), g
-
-
-_INPUTS = {}
-
-
-def _inputs(world, B):
-    """Everything one launch reads, on the device, for B sequences (computed once per B)."""
-    if B in _INPUTS:
-        return _INPUTS[B]
-    h = world["handle"]
-    pp, betas, g = _walkers(B, 900 + B)
-    pp_d, bt_d = pp.cuda(), betas.cuda()
-    o = h.forward(pp_d.reshape(B * 20, 93), bt_d, 20, want_verts=False)
-    j127, mproj = o["joints"].clone(), o["markers"].clone()
-    j55 = h.joints55(pp_d.reshape(B * 20, 93), bt_d, 20)
-    m = mproj.reshape(B, 20, 201)
-    noisy = (m.cpu() + torch.randn(B, 20, 201, generator=g) * 0.01).permute(1, 0, 2).contiguous()
-    Rz = torch.randn(B, generator=g) * 2.0
-    R0 = torch.zeros(B, 3, 3)
-    R0[:, 0, 0], R0[:, 0, 1], R0[:, 1, 0], R0[:, 1, 1], R0[:, 2, 2] = torch.cos(Rz), -torch.sin(Rz), torch.sin(Rz), torch.cos(Rz), 1.0
-    T0 = torch.randn(B, 3, generator=g) * 2.0
-    delta_T = h.joints55(torch.zeros(B, 93, device="cuda"), bt_d, 1)[:, 0].contiguous()
-    torch.cuda.synchronize()
-    d = {"pp": pp_d, "X": noisy[:2].cuda().contiguous(), "Y_gen": noisy[2:].cuda().contiguous(), "j127": j127, "j55": j55,
-         "mproj": mproj, "delta_T": delta_T, "R0": R0.cuda(), "T0": T0.cuda()}
-    _INPUTS[B] = d
-    return d
-
-
-def _launch(d, rows, jpb, rf, nonfinite=None, Y_gen=None):
-    """egx_primitive_advance on the sequences `rows` of the input set d -> dict of outputs (device tensors)."""
-    import ctypes as C
-    from egogen_amd import _lib
-    lib = _lib.load()
-    rows = torch.as_tensor(rows, device="cuda")
-    B = int(rows.numel())
-    sel = lambda t, per=1: t.reshape(-1, per, *t.shape[1:])[rows].reshape(B * per, *t.shape[1:]).contiguous()
-    pp = d["pp"][rows].contiguous()
-    Yg = (d["Y_gen"] if Y_gen is None else Y_gen)[:, rows].contiguous()
-    X = d["X"][:, rows].contiguous()
-    J = sel(d["j127"] if jpb == 127 else d["j55"], 20)
-    mp = sel(d["mproj"], 20)
-    dT = d["delta_T"][rows].contiguous()
-    R0, T0 = d["R0"][rows].clone().contiguous(), d["T0"][rows].clone().contiguous()
-    f = lambda *s: torch.full(s, float("nan"), device="cuda")
-    o = {"marker_b": f(B, 20, 67, 3), "pelvis": f(B, 20, 3), "R": f(B, 3, 3), "T": f(B, 3), "seed_params": f(B, 2, 93),
-         "seed_markers": f(2, B, 201)}
-    _lib.check(lib.egx_primitive_advance(
-        _lib.ptr(pp), _lib.ptr(Yg), C.c_void_p(X[0].data_ptr()), C.c_void_p(X[1].data_ptr()), 201, _lib.ptr(J), jpb, _lib.ptr(mp),
-        _lib.ptr(dT), float(rf), B, _lib.ptr(R0), _lib.ptr(T0), _lib.ptr(o["marker_b"]), _lib.ptr(o["pelvis"]), _lib.ptr(o["R"]),
-        _lib.ptr(o["T"]), _lib.ptr(o["seed_params"]), C.c_void_p(o["seed_markers"][0].data_ptr()),
-        C.c_void_p(o["seed_markers"][1].data_ptr()), 201, _lib.ptr(nonfinite), _lib.current_stream_ptr()), "egx_primitive_advance")
-    torch.cuda.synchronize()
-    o.update(R0=R0, T0=T0, seed_markers=o["seed_markers"].permute(1, 0, 2).contiguous())
-    o["_in"] = {"pp": pp, "Y_gen": Yg, "X": X, "J": J.reshape(B, 20, jpb, 3), "mp": mp.reshape(B, 20, 67, 3), "dT": dT,
-                "R0": d["R0"][rows], "T0": d["T0"][rows]}
-    return o
 
 
 def _seed_group(r):
@@ -210,22 +101,6 @@ def test_primitive_advance_rejects_bad_arguments(small_world):
 
 
 # ----------------------------------------------------------------------------------------------------------------------
-def _op(model=None, body_model=None, cfg_extra=None):
-    from egogen_amd.genop import GAMMAPrimitiveComboGenOP
-    from egogen_amd.models import PREDICTOR_CFG, REGRESSOR_CFG
-    op = GAMMAPrimitiveComboGenOP({"modelconfig": dict(PREDICTOR_CFG, **(cfg_extra or {})), "trainconfig": {}},
-                                  {"modelconfig": dict(REGRESSOR_CFG), "trainconfig": {}}, {"gpu_index": 0})
-    op.model, op.body_model = model, body_model
-    return op
-
-
-def _combo(sd):
-    from egogen_amd.models import GAMMAPrimitiveCombo, PREDICTOR_CFG, REGRESSOR_CFG
-    combo = GAMMAPrimitiveCombo(PREDICTOR_CFG, REGRESSOR_CFG)
-    combo.load_state_dict(sd)
-    return combo.cuda().eval()
-
-
 @pytest.fixture(scope="module")
 def gen_world():
     g = load_golden("genop_ref.npz")
@@ -345,18 +220,10 @@ def test_generate_sequence_marker_seed_matches_reference_env_execution():
         R0, T0 = torch.as_tensor(g[pre + "reset_R0"]).cuda(), torch.as_tensor(g[pre + "reset_T0"]).cuda()
         for i in range(n):
             sp = f"{pre}s{i}_"
-            kept = {}
-            real = op._advance_loop
-
-            def spy(K, B, rf_, z, bt, xs, sd_, *rest, _kept=kept, _real=real):
-                _real(K, B, rf_, z, bt, xs, sd_, *rest)
-                _kept["X"], _kept["seed"] = xs[1].clone(), sd_.clone()
-            op._advance_loop = spy
-            try:
+            with patched_loop(op, "_advance_loop") as seen:
                 res = op.generate_sequence(X, seed, g[pre + "betas"], 1, z=g[pre + "z"][i].reshape(1, 1, 128), reproj_factor=rf, R0=R0,
                                            T0=T0, to_numpy=False)
-            finally:
-                op._advance_loop = real
+            kept = {"X": seen.s["xs"][1], "seed": seen.s["seed"]}       # what the one primitive handed on: the loop's own buffers
             _close(kept["X"][:, 0], g[sp + "after_state"][:, :201], "unit", sp + "marker seed")
             _close(kept["seed"][0, :, :3], g[sp + "after_seed"][:, :3], "m", sp + "seed transl")
             _aa_close(kept["seed"][0, :, 3:6], g[sp + "after_seed"][:, 3:6], sp + "seed glorot")
@@ -442,22 +309,9 @@ def test_generate_sequence_loop_has_no_host_wait(chain_world):
     w = chain_world
     op = w["op"]
     op.generate_sequence(w["data"], w["bparams"], w["betas"], 1, z=w["z"][:1])      # weight images, workspaces
-    real = op._advance_loop
-    ran = []
-
-    def guarded(*a):
-        old = torch.cuda.get_sync_debug_mode()
-        torch.cuda.set_sync_debug_mode("error")
-        try:
-            real(*a)
-            ran.append(a[0])
-        finally:
-            torch.cuda.set_sync_debug_mode(old)
-    op._advance_loop = guarded
-    try:
+    with patched_loop(op, "_advance_loop", no_host_wait=True) as seen:
         res = op.generate_sequence(w["data"], w["bparams"], w["betas"], 3, z=w["z"])
-    finally:
-        op._advance_loop = real
+    ran = [call[0] for call in seen.calls]
     assert ran == [3] and np.isfinite(res.markers).all()
     # ... and the mode does catch a wait in that place
     torch.cuda.set_sync_debug_mode("error")

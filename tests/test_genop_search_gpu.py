@@ -1,7 +1,7 @@
 """GPU checks of the primitive search: kernels egx_primitive_select and egx_primitive_advance_select (csrc/genop.hip) and
 `GAMMAPrimitiveComboGenOP.generate_sequence_to_goal` (egogen_amd/genop.py).
 
-Yardsticks.  Values: `held()` of tests/test_genop_gpu.py - the device within R = 3 times the distance of the float32 restatement
+Yardsticks.  Values: `held()` of tests/genop_gpu_helpers.py - the device within R = 3 times the distance of the float32 restatement
 (tests/genop_search_ref.py) from the float64 one, largest entry of a group.  A group is one term (or the cost) over the rows of a
 case; the statistic compares two maxima of rounding errors, which says nothing on a handful of values (one row: a restatement that
 happens to round to the truth admits no kernel at all), so a case with fewer than 64 rows is launched on as many independent
@@ -20,82 +20,12 @@ import numpy as np
 import pytest
 import torch
 
-from tests import genop_ref, genop_search_ref as sref
-from tests.helpers import seeded_prior_state_dict
-from tests.test_genop_gpu import CFG_RF, ROOT, V_SMALL, _combo, _inputs, _launch, _op, _walkers, emit, held, small_world  # noqa: F401
+from tests import genop_search_ref as sref
+from tests.genop_gpu_helpers import (CFG_RF, MIN_GROUP, POOL, ROOT, UNDECIDABLE_CAP, V_SMALL, W_TEST, _advance_select, _feet, _handmade, _inputs,
+                                     _launch, _restate, _rows_inputs, _select, emit, held, patched_loop, search_world, small_world)  # noqa: F401
 from tests.test_genop_search_cpu import selection_cases
 
 pytestmark = pytest.mark.gpu
-
-POOL = 65                   # rows of the walker pool (tests/test_genop_gpu.py::_inputs)
-W_TEST = {"goal": 1.0, "skate": 2.0, "floor": 0.5, "pene": 0.3, "face": 0.7}
-W_ORDER = ("goal", "skate", "floor", "pene", "face")
-UNDECIDABLE_CAP = 0.05
-MIN_GROUP = 64              # candidate rows pooled into one held() group (see the module docstring)
-
-
-def _feet():
-    from egogen_amd import synth
-    return synth.feet_marker_idx()
-
-
-def _rows_inputs(world, b, N, seed, with_pene):
-    """b * N candidate rows drawn from the walker pool, each in a frame (R0, T0) of its own, one goal per sequence."""
-    d = _inputs(world, POOL)
-    g = torch.Generator().manual_seed(seed)
-    rows = (torch.arange(b * N) * 7 + seed) % POOL
-    yaw = torch.randn(b * N, generator=g) * 2.0
-    R0 = torch.zeros(b * N, 3, 3)
-    R0[:, 0, 0], R0[:, 0, 1], R0[:, 1, 0], R0[:, 1, 1], R0[:, 2, 2] = torch.cos(yaw), -torch.sin(yaw), torch.sin(yaw), torch.cos(yaw), 1.0
-    T0 = torch.randn(b * N, 3, generator=g) * torch.tensor([2.0, 2.0, 0.05])
-    goal = torch.randn(b, 3, generator=g) * torch.tensor([3.0, 3.0, 0.0]) + torch.tensor([0.0, 0.0, 0.9])
-    pene = None
-    if with_pene:
-        top = torch.randint(0, 90, (b * N, 1), generator=g)
-        pene = (torch.rand(b * N, 20, generator=g) * (top + 1)).floor().int()
-    return {"rows": rows, "R0": R0, "T0": T0, "goal": goal, "pene": pene, "pool": d, "b": b, "N": N}
-
-
-def _select(x, jpb, rf=CFG_RF, weights=W_TEST, pene_thres=40.0, goal_thresh=0.1, nan_face_rows=(), b=None, N=None, group0=0):
-    """egx_primitive_select on the groups [group0, group0 + b) of the row set x -> (outputs, the inputs as launched)"""
-    from egogen_amd import _lib
-    lib = _lib.load()
-    b = x["b"] if b is None else b
-    N = x["N"] if N is None else N
-    sl = slice(group0 * N, (group0 + b) * N)
-    rows = x["rows"][sl].cuda()
-    d = x["pool"]
-    n = b * N
-    per = lambda t: t.reshape(POOL, 20, *t.shape[1:])[rows].reshape(n * 20, *t.shape[1:]).contiguous()
-    Yg = d["Y_gen"][:, rows].contiguous()
-    X = d["X"][:, rows].contiguous()
-    J = per(d["j127"] if jpb == 127 else d["j55"])
-    for r in nan_face_rows:         # joint 2 of the last body: the facing term of row r becomes NaN, its distance stays finite
-        J.view(n, 20, jpb, 3)[r, 19, 2, 0] = float("nan")
-    mp = per(d["mproj"])
-    R0, T0 = x["R0"][sl].cuda().contiguous(), x["T0"][sl].cuda().contiguous()
-    goal = x["goal"][group0:group0 + b].cuda().contiguous()
-    pene = None if x["pene"] is None else x["pene"][sl].cuda().reshape(-1).contiguous()
-    feet = torch.tensor(_feet(), dtype=torch.int32, device="cuda")
-    fi = lambda *s: torch.full(s, -7, dtype=torch.int32, device="cuda")
-    ff = lambda *s: torch.full(s, float("nan"), device="cuda")
-    o = {"choice": fi(b), "status": fi(b), "reached": fi(b), "goal_dist": ff(b), "cost": ff(b, N), "terms": ff(b, N, 5), "colliding": fi(b, N)}
-    w = (C.c_float * 5)(*[weights[k] for k in W_ORDER])
-    _lib.check(lib.egx_primitive_select(
-        _lib.ptr(Yg), C.c_void_p(X[0].data_ptr()), C.c_void_p(X[1].data_ptr()), 201, _lib.ptr(J), jpb, _lib.ptr(mp), _lib.ptr(R0),
-        _lib.ptr(T0), _lib.ptr(pene), _lib.ptr(goal), _lib.ptr(feet), w, float(pene_thres), float(goal_thresh), float(rf), b, N,
-        _lib.ptr(o["choice"]), _lib.ptr(o["status"]), _lib.ptr(o["reached"]), _lib.ptr(o["goal_dist"]), _lib.ptr(o["cost"]),
-        _lib.ptr(o["terms"]), _lib.ptr(o["colliding"]), _lib.current_stream_ptr()), "egx_primitive_select")
-    torch.cuda.synchronize()
-    i = {"Y_gen": Yg, "X": X, "J": J.reshape(n, 20, jpb, 3), "mp": mp.reshape(n, 20, 67, 3), "R0": R0, "T0": T0,
-         "goal_rows": goal.repeat_interleave(N, 0), "pene": None if pene is None else pene.reshape(n, 20)}
-    return {k: v.cpu() for k, v in o.items()}, i
-
-
-def _restate(i, b, N, rf, weights, pene_thres, dtype):
-    r = sref.score(i["Y_gen"], i["X"], i["J"], i["mp"], i["R0"], i["T0"], i["pene"], i["goal_rows"], _feet(), weights, pene_thres, rf, dtype)
-    terms = torch.stack([r[t] for t in sref.TERMS], -1).reshape(b, N, 5)
-    return r["cost"].reshape(b, N), terms, r["colliding"].reshape(b, N)
 
 
 def decidable(cost64, terms64, coll, cost32):
@@ -162,28 +92,6 @@ def test_primitive_select_kernel(small_world, b, N, jpb, with_pene):
     assert share <= UNDECIDABLE_CAP, (name, share)
 
 
-def _handmade(world, costs, coll):
-    """One group of len(costs) duplicates of pool row 0 whose cost (w_goal = 1, every other weight 0) is ordered like `costs`: the
-    goal sits `cost` metres beside the last pelvis; a non-finite cost is a NaN in the row's T0.  (A non-finite term is made in
-    `_select`: a NaN in a joint the facing term reads.  The skate and floor terms take minima over the feet markers with fminf, as
-    the env kernel does, which drops a NaN marker; such a row is caught by the hand-off's non-finite counter when it is chosen.)"""
-    N = len(costs)
-    d = _inputs(world, POOL)
-    pelvis = d["j127"].reshape(POOL, 20, 127, 3)[0, 19, 0].cpu()
-    goal = torch.tensor([[0.3, -0.2, 0.9]])
-    T0 = torch.zeros(N, 3)
-    for n, c in enumerate(costs):
-        T0[n] = goal[0] - pelvis - torch.tensor([c, 0.0, 0.0]) if np.isfinite(c) else torch.tensor([float("nan"), 0.0, 0.0])
-    pene = torch.zeros(N, 20, dtype=torch.int32)
-    pene[:, 3] = 39
-    for n, cflag in enumerate(coll):
-        if cflag:
-            pene[n, 11] = 40
-    x = {"rows": torch.zeros(N, dtype=torch.long), "R0": torch.eye(3).repeat(N, 1, 1), "T0": T0, "goal": goal, "pene": pene, "pool": d,
-         "b": 1, "N": N}
-    return x
-
-
 @pytest.mark.parametrize("name", list(selection_cases()))
 def test_primitive_select_handmade_cases(small_world, name):
     costs, coll, nan_rows, want, status = selection_cases()[name]
@@ -204,32 +112,6 @@ def test_primitive_select_group_does_not_depend_on_batch(small_world):
         one, _ = _select(x, 127, b=1, group0=g)
         for k in ("choice", "status", "reached", "goal_dist", "cost", "terms", "colliding"):
             assert torch.equal(one[k][0], full[k][g]), (g, k)
-
-
-# ----------------------------------------------------------------------------------------------------------------------
-def _advance_select(d, rows, choice, N, jpb, rf, nonfinite=None):
-    """egx_primitive_advance_select on the candidate rows `rows` (b * N pool rows) of the input set d"""
-    from egogen_amd import _lib
-    lib = _lib.load()
-    rows = torch.as_tensor(rows, device="cuda")
-    n = int(rows.numel())
-    b = n // N
-    sel = lambda t, per=1: t.reshape(-1, per, *t.shape[1:])[rows].reshape(n * per, *t.shape[1:]).contiguous()
-    pp, Yg, X = d["pp"][rows].contiguous(), d["Y_gen"][:, rows].contiguous(), d["X"][:, rows].contiguous()
-    J, mp, dT = sel(d["j127"] if jpb == 127 else d["j55"], 20), sel(d["mproj"], 20), d["delta_T"][rows].contiguous()
-    R0, T0 = d["R0"][rows].clone().contiguous(), d["T0"][rows].clone().contiguous()
-    ch = torch.as_tensor(choice, dtype=torch.int32, device="cuda")
-    f = lambda *s: torch.full(s, float("nan"), device="cuda")
-    o = {"marker_b": f(b, 20, 67, 3), "pelvis": f(b, 20, 3), "R": f(b, 3, 3), "T": f(b, 3), "params": f(b, 20, 93), "seed_params": f(n, 2, 93),
-         "seed_markers": f(2, n, 201)}
-    _lib.check(lib.egx_primitive_advance_select(
-        _lib.ptr(pp), _lib.ptr(Yg), C.c_void_p(X[0].data_ptr()), C.c_void_p(X[1].data_ptr()), 201, _lib.ptr(J), jpb, _lib.ptr(mp),
-        _lib.ptr(dT), float(rf), b, _lib.ptr(ch), N, _lib.ptr(R0), _lib.ptr(T0), _lib.ptr(o["marker_b"]), _lib.ptr(o["pelvis"]),
-        _lib.ptr(o["R"]), _lib.ptr(o["T"]), _lib.ptr(o["params"]), _lib.ptr(o["seed_params"]), C.c_void_p(o["seed_markers"][0].data_ptr()),
-        C.c_void_p(o["seed_markers"][1].data_ptr()), 201, _lib.ptr(nonfinite), _lib.current_stream_ptr()), "egx_primitive_advance_select")
-    torch.cuda.synchronize()
-    o.update(R0=R0, T0=T0, seed_markers=o["seed_markers"].permute(1, 0, 2).contiguous())
-    return o
 
 
 @pytest.mark.parametrize("jpb", [127, 55])
@@ -294,22 +176,6 @@ def test_search_kernels_reject_bad_arguments(small_world):
 
 
 # ----------------------------------------------------------------------------------------------------------------------
-@pytest.fixture(scope="module")
-def search_world(small_world):
-    """b = 3 walkers on the small synthetic body with a seeded prior: the operator and its inputs."""
-    h = small_world["handle"]
-    sd = seeded_prior_state_dict()
-    op = _op(_combo(sd), h)
-    b = 3
-    pp, betas, g = _walkers(b, 78)
-    pp[:, :, 3:6] = torch.randn(b, 1, 3, generator=g) * 0.05        # ordinary orientations for all three walkers
-    o = h.forward(pp.cuda().reshape(b * 20, 93), betas.cuda(), 20, want_verts=False)
-    data = o["markers"].reshape(b, 20, 201)[:, :2].permute(1, 0, 2).contiguous().cpu()
-    bparams = pp[:, :2].permute(1, 0, 2).contiguous()
-    goal = torch.tensor([[0.5, 2.0, 0.9], [-1.0, 1.0, 0.9], [0.0, 3.0, 0.9]])
-    return {"op": op, "sd": sd, "data": data, "bparams": bparams, "pp": pp, "betas": betas, "goal": goal, "handle": h, "g": g, "b": b}
-
-
 def test_one_candidate_without_scene_is_generate_sequence(search_world):
     w = search_world
     op, K, b = w["op"], 3, w["b"]
@@ -361,15 +227,6 @@ def test_search_chain_matches_float64(search_world, small_world):
 
 
 # ----------------------------------------------------------------------------------------------------------------------
-def _spy_loop(op, kept):
-    real = op._search_loop
-
-    def spy(K, b, N, s):
-        real(K, b, N, s)
-        kept.update(s=s)
-    return real, spy
-
-
 @pytest.mark.parametrize("scenes", [1, 2])
 def test_scene_invariants(search_world, scenes):
     from egogen_amd import synth
@@ -384,14 +241,10 @@ def test_scene_invariants(search_world, scenes):
         other = SdfScene(synth.make_sdf_scene(32, obstacle=([-1.5, -1.5, 0.0], [-0.5, -0.5, 1.0])))
         scene, agent_scene = SdfSceneSet([box, other]), [1, 1, 0]
     z = torch.randn(K, b * N, 128, generator=torch.Generator().manual_seed(3 + scenes))
-    kept = {}
-    real, op._search_loop = _spy_loop(op, kept)
-    try:
+    with patched_loop(op, "_search_loop") as seen:
         res = op.generate_sequence_to_goal(w["data"], w["bparams"], w["betas"], w["goal"] + T0, K, N, scene=scene, agent_scene=agent_scene,
                                            z=z, reproj_factor=CFG_RF, T0=T0, to_numpy=False)
-    finally:
-        op._search_loop = real
-    s = kept["s"]
+    s = seen.s
     # the counts the last selection consumed are BodyModelHandle.forward's for the same rows in the frame of that primitive
     rep = lambda t: t.repeat_interleave(N, 0).contiguous()
     kw = {} if scenes == 1 else {"agent_scene": s["rows_scene"]}
@@ -452,22 +305,9 @@ def test_search_loop_has_no_host_wait(search_world):
     scene = SdfScene(synth.make_sdf_scene(32))
     args = (w["data"], w["bparams"], w["betas"], w["goal"])
     op.generate_sequence_to_goal(*args, 1, 4, scene=scene)      # weight images, workspaces
-    real = op._search_loop
-    ran = []
-
-    def guarded(*a):
-        old = torch.cuda.get_sync_debug_mode()
-        torch.cuda.set_sync_debug_mode("error")
-        try:
-            real(*a)
-            ran.append(a[:3])
-        finally:
-            torch.cuda.set_sync_debug_mode(old)
-    op._search_loop = guarded
-    try:
+    with patched_loop(op, "_search_loop", no_host_wait=True) as seen:
         res = op.generate_sequence_to_goal(*args, 3, 4, scene=scene)
-    finally:
-        op._search_loop = real
+    ran = seen.calls
     assert ran == [(3, w["b"], 4)] and np.isfinite(res.markers).all()
 
 
