@@ -372,7 +372,7 @@ void run_table(hipStream_t st, const PackEntry* tab, int n, int frags, int nplan
 
 // carve every buffer of a handle; with ar.base == nullptr this only measures
 void layout(egx_policy_train* h) {
-  const int n = h->n, Sn = h->Sn;
+  const int n = h->n;
   Arena& ar = h->ar;
   ar.off = 0;
   auto img = [&](int rows, int red) { return static_cast<bf16x8*>(ar.take(d3_img_frags(rows, red) * D3_FRAG_BYTES)); };
@@ -398,7 +398,6 @@ void layout(egx_policy_train* h) {
     B.head = f32((size_t)n * B.nout); B.ghead = f32((size_t)n * B.nout);
     B.ghead_r = img(n, B.nout); B.gheadT = img(B.nout, n);
   }
-  (void)Sn;
 }
 
 // the all-ones row of a transposed activation image whose other rows are written by kernel epilogues
@@ -558,32 +557,30 @@ extern "C" int egx_policy_train_bind(egx_policy_train* h, const float* state, co
   return EGX_OK;
 }
 
-static int train_step_parts(egx_policy_train* h, const float* dist, const float* time, const float* act, const float* adv,
-                            const float* ret, const float* logp_old, const float* adv_stats, const float* scale, float adv_eps,
-                            float min_logvar, float max_logvar, float eps_clip, float vf_coef, float ent_coef, float* out_terms,
-                            void* stream_, int parts, const egx_update_head* hd = nullptr);
+namespace {
 
-extern "C" int egx_policy_train_step(egx_policy_train* h, const float* dist, const float* time, const float* act, const float* adv,
-                                     const float* ret, const float* logp_old, const float* adv_stats, const float* scale,
-                                     float adv_eps, float min_logvar, float max_logvar, float eps_clip, float vf_coef, float ent_coef,
-                                     float* out_terms, void* stream_) {
-  return train_step_parts(h, dist, time, act, adv, ret, logp_old, adv_stats, scale, adv_eps, min_logvar, max_logvar, eps_clip, vf_coef,
-                          ent_coef, out_terms, stream_, 3);
+constexpr int S_HD = HD / 32, S_CAT = CAT / 32, S_G = 3 * HD / 32;
+constexpr float LRELU_SLOPE = 0.01f;   // torch.nn.LeakyReLU() default (baseops.py:627-628)
+
+struct LossConsts {
+  float adv_eps = 0.f, min_logvar = 0.f, max_logvar = 0.f, eps_clip = 0.f, vf_coef = 0.f, ent_coef = 0.f;
+};
+// One minibatch as the entry points below describe it: its rows (compact, or with `hd` the head launch's outputs), the loss
+// normaliser and constants, where the six loss sums go, and the head launch (null: input table + positional encoding instead).
+struct StepIn {
+  const float *dist = nullptr, *time = nullptr, *act = nullptr, *adv = nullptr, *ret = nullptr, *logp_old = nullptr;
+  const float *adv_stats = nullptr, *scale = nullptr;
+  LossConsts c;
+  float* out_terms = nullptr;
+  const egx_update_head* hd = nullptr;
+};
+
+void launch_n(const egx_policy_train* h, hipStream_t st, D3Plain* ps, int cnt) {
+  for (int i = 0; i < cnt; ++i) ps[i].prec = h->prec;
+  egx_launch_dense3_n(st, ps, cnt);
 }
 
-// The same chain in two halves, for data-parallel training: `egx_policy_train_step_heads` ends when the last weight gradient of
-// the actor and critic blocks has been enqueued (forward, loss, their whole backward: the 10.3 M-parameter prefix of the flat
-// gradient is final), `egx_policy_train_step_encoders` runs the rest (the two GRU encoders' backward).  The caller all-reduces
-// the first bucket on a side stream while the second half runs (egogen_amd/ppo_policy.py).
-extern "C" int egx_policy_train_step_heads(egx_policy_train* h, const float* dist, const float* time, const float* act, const float* adv,
-                                           const float* ret, const float* logp_old, const float* adv_stats, const float* scale,
-                                           float adv_eps, float min_logvar, float max_logvar, float eps_clip, float vf_coef,
-                                           float ent_coef, float* out_terms, void* stream_) {
-  return train_step_parts(h, dist, time, act, adv, ret, logp_old, adv_stats, scale, adv_eps, min_logvar, max_logvar, eps_clip, vf_coef,
-                          ent_coef, out_terms, stream_, 1);
-}
-// ---- the same chain behind ONE head launch (egx_update_head_kernel): the minibatch is named by row indices into the rollout
-static int head_args_ok(const egx_policy_train* h, const egx_update_head* a) {
+int head_args_ok(const egx_policy_train* h, const egx_update_head* a) {
   EGX_REQUIRE(h && a, "null argument");
   EGX_REQUIRE(a->perm && a->state && a->egosensing && a->dist && a->time && a->act && a->adv && a->ret && a->logp_old &&
                   a->act_c && a->adv_c && a->ret_c && a->logp_old_c && a->stats && a->log, "null field in egx_update_head");
@@ -591,8 +588,9 @@ static int head_args_ok(const egx_policy_train* h, const egx_update_head* a) {
   EGX_REQUIRE(a->num_src_rows > 0 && a->max_cursor >= 0, "egx_update_head: num_src_rows must be positive, max_cursor non-negative");
   return EGX_OK;
 }
-static void launch_head(egx_policy_train* h, const egx_update_head* a, hipStream_t st) {
-  constexpr int S_HD = HD / 32, S_CAT = CAT / 32;
+
+// gather, statistics, input images, positional encoding, cleared loss sums: one launch
+void launch_head(egx_policy_train* h, const egx_update_head* a, hipStream_t st) {
   const int n = h->n, Sn = h->Sn;
   HeadArgs k;
   k.tab = h->tab_inputs; k.n_tab = h->n_inputs; k.frags_tab = h->frags_inputs; k.nplanes = d3_planes(h->prec);
@@ -612,6 +610,229 @@ static void launch_head(egx_policy_train* h, const egx_update_head* a, hipStream
   hipLaunchKernelGGL(egx_update_head_kernel, dim3(blocks), dim3(256), 0, st, k);
 }
 
+void step_inputs(egx_policy_train* h, const StepIn& in, hipStream_t st) {
+  if (in.hd) {
+    launch_head(h, in.hd, st);
+    return;
+  }
+  run_table(st, h->tab_inputs, h->n_inputs, h->frags_inputs, d3_planes(h->prec));
+  egx_launch_posenc3(st, in.dist, in.time, h->n, h->catf + 2 * HD, CAT, h->cat_r, S_CAT, 2 * S_HD, h->catT, h->Sn, 2 * HD,
+                     in.out_terms);   // also clears the loss sums
+}
+
+// 2 GRU steps of both encoders -> [hx | he | pe]; 4 layers and the output layer of both MLP blocks
+void step_forward(egx_policy_train* h, hipStream_t st) {
+  const int n = h->n, Sn = h->Sn;
+  D3Gru g[2];
+  for (int e = 0; e < 2; ++e) {   // step 1: zero previous state
+    Encoder& E = h->enc[e];
+    const int Sx = egx_ceil_div(E.in_dim, 32);
+    D3Gru& q = g[e];
+    q.prec = h->prec;
+    q.M = n; q.H = HD;
+    q.Ai = E.x0_r; q.SAi = Sx; q.Bi = E.Wih_r; q.Si = Sx; q.bias_i = E.bih; q.bias_h = E.bhh;
+    q.gi_out = E.gi1; q.h_out = E.h1f; q.ldo = HD; q.h_out3 = E.h1_r; q.S3 = S_HD;
+    q.h_out3T = E.hprevT; q.S3T = 2 * Sn; q.s3T0 = Sn; q.col0T = 0;
+  }
+  egx_launch_gru3_pair(st, g[0], g[1]);
+  for (int e = 0; e < 2; ++e) {   // step 2 -> [hx | he | pe]
+    Encoder& E = h->enc[e];
+    D3Gru& q = g[e];
+    q.Ai = E.x1_r; q.gi_out = E.gi2; q.gh_out = E.gh2;
+    q.Ah = E.h1_r; q.SAh = S_HD; q.Bh = E.Whh_r; q.Sh = S_HD; q.h_prev = E.h1f; q.ldh = HD;
+    q.h_out = h->catf + E.cat_off; q.ldo = CAT; q.h_out3 = h->cat_r; q.S3 = S_CAT; q.s30 = E.cat_off / 32;
+    q.h_out3T = h->catT; q.S3T = Sn; q.s3T0 = 0; q.col0T = E.cat_off;
+  }
+  egx_launch_gru3_pair(st, g[0], g[1]);
+
+  D3Plain L[2];
+  // h = hx; per unit: h = lrelu(fc2(lrelu(fc1(h)))) + h   (models_policy_ppo.py:24-39, baseops.py:615-641)
+  for (int l = 0; l < 4; ++l) {
+    for (int b = 0; b < 2; ++b) {   // layer l of both MLP blocks: in -> lrelu(W_l in + b_l) (+ res)
+      Branch& B = h->br[b];
+      const bf16x8* const in[4] = {h->cat_r, B.a1_r, B.u1_r, B.a3_r};
+      const float* const res[4] = {nullptr, h->catf, nullptr, B.u1f};   // the skip connection closes after fc2 of a unit
+      float* const outf[4] = {nullptr, B.u1f, nullptr, nullptr};        // unit 1's output in fp32: the skip of unit 2
+      bf16x8* const o3[4] = {B.a1_r, B.u1_r, B.a3_r, B.u2_r};           // images of the output: the next product's operand
+      bf16x8* const o3T[4] = {B.a1T, B.u1T, B.a3T, B.u2T};             // and its transpose for the next layer's weight gradient
+      D3Plain& q = L[b];
+      q = D3Plain();
+      q.M = n; q.N = CAT; q.A = in[l]; q.SA = S_CAT; q.S = S_CAT; q.B = B.W_r[l]; q.bias = B.b[l]; q.act = 3; q.slope = LRELU_SLOPE;
+      q.out_act = B.a[l]; q.ldact = CAT;   // the activation saved for backward
+      q.res = res[l]; q.ldr = CAT; q.out = outf[l]; q.ldo = CAT;
+      q.out3 = o3[l]; q.S3 = S_CAT; q.out3T = o3T[l]; q.S3T = Sn;
+    }
+    launch_n(h, st, L, 2);
+  }
+  for (int b = 0; b < 2; ++b) {   // heads: zp = [mu | logvar] and the value
+    Branch& B = h->br[b];
+    D3Plain& q = L[b];
+    q = D3Plain();
+    q.M = n; q.N = B.nout; q.A = B.u2_r; q.SA = S_CAT; q.S = S_CAT; q.B = B.Wout_r; q.bias = B.bout; q.out = B.head; q.ldo = B.nout;
+  }
+  launch_n(h, st, L, 2);
+}
+
+// the loss and its gradient w.r.t. the two heads (ppo_policy.py:189-241), then the images of that gradient
+int step_loss(egx_policy_train* h, const StepIn& in, hipStream_t st) {
+  const egx_update_head* hd = in.hd;
+  int rc = egx_ppo_loss_packed_precleared(h->br[0].head, h->br[1].head, in.act, in.adv, in.ret, in.logp_old, in.adv_stats, in.scale,
+                                          in.c.adv_eps, in.c.min_logvar, in.c.max_logvar, in.c.eps_clip, in.c.vf_coef, in.c.ent_coef, h->n,
+                                          h->br[0].ghead, h->br[1].ghead, in.out_terms, st, hd ? hd->cursor : nullptr,
+                                          hd ? hd->max_cursor : 0);
+  if (rc) return rc;
+  run_table(st, h->tab_loss, h->n_loss, h->frags_loss, d3_planes(h->prec));
+  return EGX_OK;
+}
+
+// Backward of the actor and critic blocks.  Input-gradient products form the dependent chain (out_fc -> unit 2 -> unit 1 -> GRU
+// cells); each layer's weight-gradient product follows the launch that left its gradient image behind.  (Weight gradients on a
+// second stream beside the chain, and fused into the input-gradient launches, were both measured and are not faster:
+// profiles/r03_update_experiments.md.)
+void step_blocks_bwd(egx_policy_train* h, hipStream_t st) {
+  const int n = h->n, Sn = h->Sn;
+  auto wgrad = [&](D3Plain& q, const bf16x8* gT, const bf16x8* xT, int rows, float* gW, float* gb) {
+    q = D3Plain();
+    q.M = rows; q.N = CAT + 1; q.A = gT; q.SA = Sn; q.S = Sn; q.B = xT; q.out = gW; q.ldo = CAT; q.n_split = CAT; q.bias_out = gb;
+  };
+  D3Plain W[2], D[2], WL[8];
+  for (int b = 0; b < 2; ++b) wgrad(W[b], h->br[b].gheadT, h->br[b].u2T, h->br[b].nout, h->br[b].gWout, h->br[b].gbout);
+  launch_n(h, st, W, 2);
+  // Layer l of both blocks, l = 4 being out_fc: the input gradient d = g_l W_l^T-image (+ skip) now, as fp32 `out` raw and as
+  // images gated by lrelu'(a_l) = g_(l-1).  Its weight gradient dW_l = g_l^T x_l only needs the images the previous launch left
+  // behind, so the eight weight-gradient products of the four layers go out afterwards as two four-product launches (fewer,
+  // fuller launches: ~10 us of every launch is fixed cost, profiles/r03_update_experiments.md).
+  //   4: du2 = g W_out -> g4    3: d(a3) = g4 W4 -> g3    2: du1 = g3 W3 + du2 -> g2    1: d(a1) = g2 W2 -> g1    0: dhx = g1 W1 + du1
+  for (int l = 4; l >= 0; --l) {
+    for (int b = 0; b < 2; ++b) {
+      Branch& B = h->br[b];
+      bf16x8* const xT[4] = {h->catT, B.a1T, B.u1T, B.a3T};
+      float* const res[5] = {B.du1, nullptr, B.du2, nullptr, nullptr};
+      float* const outf[5] = {B.dhx, nullptr, B.du1, nullptr, B.du2};
+      if (l < 4) wgrad(WL[2 * l + b], B.gT[l], xT[l], CAT, B.gW[l], B.gb[l]);
+      const int S_in = l < 4 ? S_CAT : egx_ceil_div(B.nout, 32), gate = l - 1;
+      D3Plain& d = D[b];
+      d = D3Plain();
+      d.M = n; d.N = CAT; d.A = l < 4 ? B.g_r[l] : B.ghead_r; d.SA = S_in; d.S = S_in; d.B = l < 4 ? B.W_t[l] : B.Wout_t;
+      d.res = res[l]; d.ldr = CAT; d.out = outf[l]; d.ldo = CAT;
+      if (gate >= 0) {
+        d.dact = B.a[gate]; d.lddact = CAT; d.dact_code = 3; d.dact_slope = LRELU_SLOPE;
+        d.out3 = B.g_r[gate]; d.S3 = S_CAT; d.out3T = B.gT[gate]; d.S3T = Sn;
+      }
+    }
+    launch_n(h, st, D, 2);
+  }
+  launch_n(h, st, WL, 4);
+  launch_n(h, st, WL + 4, 4);
+}
+
+// Backward of the two GRU encoders (dhx = actor's + critic's)
+void step_encoders_bwd(egx_policy_train* h, hipStream_t st) {
+  const int n = h->n, Sn = h->Sn;
+  GruBwd2 two;
+  const int blocks = (n / 32) * (HD / 32);
+  two.blocks0 = blocks;
+  GruBwd* gb[2] = {&two.a, &two.b};
+  for (int e = 0; e < 2; ++e) {   // step 2
+    Encoder& E = h->enc[e];
+    GruBwd& q = *gb[e];
+    q.gi = E.gi2; q.gh = E.gh2; q.bias_h = E.bhh; q.h_prev = E.h1f;
+    q.dh0 = h->br[0].dhx + E.cat_off; q.ld0 = CAT; q.dh1 = h->br[1].dhx + E.cat_off; q.ld1 = CAT;
+    q.dgiT = E.dgiT; q.dghT = E.dghT; q.ST = 2 * Sn; q.s0T = Sn; q.dgh_r = E.dgh_r; q.dhp = E.dhp; q.M = n; q.H = HD;
+  }
+  hipLaunchKernelGGL(egx_gru_bwd3_kernel, dim3(2 * blocks), dim3(256), 0, st, two);
+  D3Plain P[4];
+  for (int e = 0; e < 2; ++e) {   // dh1 = dh z + dgh2 W_hh
+    Encoder& E = h->enc[e];
+    D3Plain& d = P[e];
+    d = D3Plain();
+    d.M = n; d.N = HD; d.A = E.dgh_r; d.SA = S_G; d.S = S_G; d.B = E.Whh_t; d.res = E.dhp; d.ldr = HD; d.out = E.dh1; d.ldo = HD;
+  }
+  launch_n(h, st, P, 2);
+  for (int e = 0; e < 2; ++e) {   // step 1 (h0 = 0: gh = b_hh)
+    Encoder& E = h->enc[e];
+    GruBwd& q = *gb[e];
+    q.gi = E.gi1; q.gh = nullptr; q.h_prev = nullptr; q.dh0 = E.dh1; q.ld0 = HD; q.dh1 = nullptr; q.ld1 = 0;
+    q.s0T = 0; q.dgh_r = nullptr; q.dhp = nullptr;
+  }
+  hipLaunchKernelGGL(egx_gru_bwd3_kernel, dim3(2 * blocks), dim3(256), 0, st, two);
+  for (int e = 0; e < 2; ++e) {   // dW_ih = [dgi1; dgi2]^T [x0; x1], dW_hh = [dgh1; dgh2]^T [0; h1]; the ones rows give the biases
+    Encoder& E = h->enc[e];
+    D3Plain& a = P[2 * e];
+    a = D3Plain();
+    a.M = 3 * HD; a.N = E.in_dim + 1; a.A = E.dgiT; a.SA = 2 * Sn; a.S = 2 * Sn; a.B = E.xT; a.out = E.gWih; a.ldo = E.in_dim;
+    a.n_split = E.in_dim; a.bias_out = E.gbih;
+    D3Plain& c = P[2 * e + 1];
+    c = D3Plain();
+    c.M = 3 * HD; c.N = HD + 1; c.A = E.dghT; c.SA = 2 * Sn; c.S = 2 * Sn; c.B = E.hprevT; c.out = E.gWhh; c.ldo = HD;
+    c.n_split = HD; c.bias_out = E.gbhh;
+  }
+  launch_n(h, st, P, 4);
+}
+
+// Launches of one minibatch (parts = 3): 22 with `in.hd` - head 1 | GRU steps 2, layers 4, output layers 1 | loss 1, its images 1
+// | backward of the blocks 8 (output-layer weight gradients, 5 input gradients, 2 x four weight gradients) | GRU encoders 4 - and
+// 23 without (input images and positional encoding instead of the head; the caller's gather and statistics launches come on
+// top: 25).  parts = 1 ends after the blocks' backward (18 / 19), parts = 2 is the encoders' 4.
+int train_step_parts(egx_policy_train* h, const StepIn& in, void* stream_, int parts) {
+  {   // egx_last_error() quotes a failed condition: these names are part of its sentences
+    const float *dist = in.dist, *time = in.time, *act = in.act, *adv = in.adv, *ret = in.ret, *logp_old = in.logp_old,
+                *scale = in.scale, *out_terms = in.out_terms;
+    const egx_update_head* hd = in.hd;
+    EGX_REQUIRE(h && (!(parts & 1) || (dist && time && act && adv && ret && logp_old && scale && out_terms)), "null argument");
+    EGX_REQUIRE(hd || !(parts & 1) || h->bound_state, "egx_policy_train_bind has not been called");
+  }
+  hipStream_t st = static_cast<hipStream_t>(stream_);
+  if (parts & 1) {
+    step_inputs(h, in, st);
+    step_forward(h, st);
+    int rc = step_loss(h, in, st);
+    if (rc) return rc;
+    step_blocks_bwd(h, st);   // every gradient of the actor and critic blocks is enqueued
+  }
+  if (parts & 2) step_encoders_bwd(h, st);
+  EGX_HIP_CHECK(hipGetLastError());
+  return EGX_OK;
+}
+
+// the minibatch behind ONE head launch (egx_update_head_kernel): its rows are named by indices into the rollout, the loss reads
+// the compact copies the head leaves behind and writes row `cursor` of the head's log
+int train_step_head(egx_policy_train* h, const egx_update_head* head, const float* scale, const LossConsts& c, void* stream_,
+                    int parts) {
+  int rc = head_args_ok(h, head);
+  if (rc) return rc;
+  const StepIn in{head->dist, head->time, head->act_c, head->adv_c, head->ret_c, head->logp_old_c, head->stats, scale, c, head->log, head};
+  return train_step_parts(h, in, stream_, parts);
+}
+
+}  // namespace
+
+extern "C" int egx_policy_train_step(egx_policy_train* h, const float* dist, const float* time, const float* act, const float* adv,
+                                     const float* ret, const float* logp_old, const float* adv_stats, const float* scale,
+                                     float adv_eps, float min_logvar, float max_logvar, float eps_clip, float vf_coef, float ent_coef,
+                                     float* out_terms, void* stream_) {
+  const StepIn in{dist, time, act, adv, ret, logp_old, adv_stats, scale, {adv_eps, min_logvar, max_logvar, eps_clip, vf_coef, ent_coef},
+                  out_terms};
+  return train_step_parts(h, in, stream_, 3);
+}
+
+// The same chain in two halves, for data-parallel training: `egx_policy_train_step_heads` ends when the last weight gradient of
+// the actor and critic blocks has been enqueued (forward, loss, their whole backward: the 10.3 M-parameter prefix of the flat
+// gradient is final), `egx_policy_train_step_encoders` runs the rest (the two GRU encoders' backward).  The caller all-reduces
+// the first bucket on a side stream while the second half runs (egogen_amd/ppo_policy.py).
+extern "C" int egx_policy_train_step_heads(egx_policy_train* h, const float* dist, const float* time, const float* act, const float* adv,
+                                           const float* ret, const float* logp_old, const float* adv_stats, const float* scale,
+                                           float adv_eps, float min_logvar, float max_logvar, float eps_clip, float vf_coef,
+                                           float ent_coef, float* out_terms, void* stream_) {
+  const StepIn in{dist, time, act, adv, ret, logp_old, adv_stats, scale, {adv_eps, min_logvar, max_logvar, eps_clip, vf_coef, ent_coef},
+                  out_terms};
+  return train_step_parts(h, in, stream_, 1);
+}
+extern "C" int egx_policy_train_step_encoders(egx_policy_train* h, void* stream_) {
+  EGX_REQUIRE(h, "null handle");
+  return train_step_parts(h, StepIn(), stream_, 2);
+}
+
 extern "C" int egx_policy_train_head(egx_policy_train* h, const egx_update_head* head, void* stream_) {
   int rc = head_args_ok(h, head);
   if (rc) return rc;
@@ -622,228 +843,10 @@ extern "C" int egx_policy_train_head(egx_policy_train* h, const egx_update_head*
 extern "C" int egx_policy_train_step_cursor(egx_policy_train* h, const egx_update_head* head, const float* scale, float adv_eps,
                                             float min_logvar, float max_logvar, float eps_clip, float vf_coef, float ent_coef,
                                             void* stream_) {
-  int rc = head_args_ok(h, head);
-  if (rc) return rc;
-  return train_step_parts(h, head->dist, head->time, head->act_c, head->adv_c, head->ret_c, head->logp_old_c, head->stats, scale, adv_eps,
-                          min_logvar, max_logvar, eps_clip, vf_coef, ent_coef, head->log, stream_, 3, head);
+  return train_step_head(h, head, scale, {adv_eps, min_logvar, max_logvar, eps_clip, vf_coef, ent_coef}, stream_, 3);
 }
 extern "C" int egx_policy_train_step_heads_cursor(egx_policy_train* h, const egx_update_head* head, const float* scale, float adv_eps,
                                                   float min_logvar, float max_logvar, float eps_clip, float vf_coef, float ent_coef,
                                                   void* stream_) {
-  int rc = head_args_ok(h, head);
-  if (rc) return rc;
-  return train_step_parts(h, head->dist, head->time, head->act_c, head->adv_c, head->ret_c, head->logp_old_c, head->stats, scale, adv_eps,
-                          min_logvar, max_logvar, eps_clip, vf_coef, ent_coef, head->log, stream_, 1, head);
-}
-extern "C" int egx_policy_train_step_encoders(egx_policy_train* h, void* stream_) {
-  EGX_REQUIRE(h, "null handle");
-  return train_step_parts(h, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, nullptr,
-                          stream_, 2);
-}
-
-// Launches of one minibatch (parts = 3): 22 with `hd` - head 1 | GRU steps 2, layers 4, output layers 1 | loss 1, its images 1 |
-// backward of the blocks 8 (output-layer weight gradients, 5 input gradients, 2 x four weight gradients) | GRU encoders 4 - and
-// 23 without (input images and positional encoding instead of the head; the caller's gather and statistics launches come on
-// top: 25).  parts = 1 ends after the blocks' backward (18 / 19), parts = 2 is the encoders' 4.
-static int train_step_parts(egx_policy_train* h, const float* dist, const float* time, const float* act, const float* adv,
-                            const float* ret, const float* logp_old, const float* adv_stats, const float* scale, float adv_eps,
-                            float min_logvar, float max_logvar, float eps_clip, float vf_coef, float ent_coef, float* out_terms,
-                            void* stream_, int parts, const egx_update_head* hd) {
-  EGX_REQUIRE(h && (!(parts & 1) || (dist && time && act && adv && ret && logp_old && scale && out_terms)), "null argument");
-  EGX_REQUIRE(hd || !(parts & 1) || h->bound_state, "egx_policy_train_bind has not been called");
-  hipStream_t st = static_cast<hipStream_t>(stream_);
-  const int n = h->n, Sn = h->Sn;
-  constexpr int S_HD = HD / 32, S_CAT = CAT / 32, S_G = 3 * HD / 32;
-  const float slope = 0.01f;   // torch.nn.LeakyReLU() default (baseops.py:627-628)
-  const int prec = h->prec;
-  auto launch_n = [prec](hipStream_t s_, D3Plain* ps, int cnt) {
-    for (int i = 0; i < cnt; ++i) ps[i].prec = prec;
-    egx_launch_dense3_n(s_, ps, cnt);
-  };
-  auto launch_gru = [prec](hipStream_t s_, D3Gru& g0, D3Gru& g1) {
-    g0.prec = g1.prec = prec;
-    return egx_launch_gru3_pair(s_, g0, g1);
-  };
-
-  int rc = EGX_OK;
-  if (parts & 1) {
-  // ================= forward =================
-  if (hd) {
-    launch_head(h, hd, st);   // gather, statistics, input images, positional encoding, cleared loss sums: one launch
-  } else {
-    run_table(st, h->tab_inputs, h->n_inputs, h->frags_inputs, d3_planes(h->prec));
-    egx_launch_posenc3(st, dist, time, n, h->catf + 2 * HD, CAT, h->cat_r, S_CAT, 2 * S_HD, h->catT, Sn, 2 * HD, out_terms);   // also clears the loss sums
-  }
-  {
-    D3Gru g[2];
-    for (int e = 0; e < 2; ++e) {   // step 1: zero previous state
-      Encoder& E = h->enc[e];
-      const int Sx = egx_ceil_div(E.in_dim, 32);
-      D3Gru& q = g[e];
-      q.M = n; q.H = HD;
-      q.Ai = E.x0_r; q.SAi = Sx; q.Bi = E.Wih_r; q.Si = Sx; q.bias_i = E.bih; q.bias_h = E.bhh;
-      q.gi_out = E.gi1; q.h_out = E.h1f; q.ldo = HD; q.h_out3 = E.h1_r; q.S3 = S_HD;
-      q.h_out3T = E.hprevT; q.S3T = 2 * Sn; q.s3T0 = Sn; q.col0T = 0;
-    }
-    launch_gru(st, g[0], g[1]);
-    for (int e = 0; e < 2; ++e) {   // step 2 -> [hx | he | pe]
-      Encoder& E = h->enc[e];
-      D3Gru& q = g[e];
-      q.Ai = E.x1_r; q.gi_out = E.gi2; q.gh_out = E.gh2;
-      q.Ah = E.h1_r; q.SAh = S_HD; q.Bh = E.Whh_r; q.Sh = S_HD; q.h_prev = E.h1f; q.ldh = HD;
-      q.h_out = h->catf + E.cat_off; q.ldo = CAT; q.h_out3 = h->cat_r; q.S3 = S_CAT; q.s30 = E.cat_off / 32;
-      q.h_out3T = h->catT; q.S3T = Sn; q.s3T0 = 0; q.col0T = E.cat_off;
-    }
-    launch_gru(st, g[0], g[1]);
-  }
-  {
-    D3Plain L[2];
-    // one dense layer of both MLP blocks: in -> lrelu(W_l in + b_l) (+ res); saves the activation, writes the images of its output
-    auto fwd = [&](int l, const bf16x8* in_a, const bf16x8* in_c, const float* res_a, const float* res_c, float* outf_a, float* outf_c,
-                   bf16x8* o3_a, bf16x8* o3_c, bf16x8* o3T_a, bf16x8* o3T_c) {
-      const bf16x8* in[2] = {in_a, in_c};
-      const float* res[2] = {res_a, res_c};
-      float* outf[2] = {outf_a, outf_c};
-      bf16x8* o3[2] = {o3_a, o3_c};
-      bf16x8* o3T[2] = {o3T_a, o3T_c};
-      for (int b = 0; b < 2; ++b) {
-        Branch& B = h->br[b];
-        D3Plain& q = L[b];
-        q = D3Plain();
-        q.M = n; q.N = CAT; q.A = in[b]; q.SA = S_CAT; q.S = S_CAT; q.B = B.W_r[l]; q.bias = B.b[l]; q.act = 3; q.slope = slope;
-        q.out_act = B.a[l]; q.ldact = CAT;
-        q.res = res[b]; q.ldr = CAT; q.out = outf[b]; q.ldo = CAT;
-        q.out3 = o3[b]; q.S3 = S_CAT; q.out3T = o3T[b]; q.S3T = Sn;
-      }
-      launch_n(st, L, 2);
-    };
-    Branch &Ba = h->br[0], &Bc = h->br[1];
-    // h = hx; per unit: h = lrelu(fc2(lrelu(fc1(h)))) + h   (models_policy_ppo.py:24-39, baseops.py:615-641)
-    fwd(0, h->cat_r, h->cat_r, nullptr, nullptr, nullptr, nullptr, Ba.a1_r, Bc.a1_r, Ba.a1T, Bc.a1T);
-    fwd(1, Ba.a1_r, Bc.a1_r, h->catf, h->catf, Ba.u1f, Bc.u1f, Ba.u1_r, Bc.u1_r, Ba.u1T, Bc.u1T);
-    fwd(2, Ba.u1_r, Bc.u1_r, nullptr, nullptr, nullptr, nullptr, Ba.a3_r, Bc.a3_r, Ba.a3T, Bc.a3T);
-    fwd(3, Ba.a3_r, Bc.a3_r, Ba.u1f, Bc.u1f, nullptr, nullptr, Ba.u2_r, Bc.u2_r, Ba.u2T, Bc.u2T);
-    for (int b = 0; b < 2; ++b) {   // heads: zp = [mu | logvar] and the value
-      Branch& B = h->br[b];
-      D3Plain& q = L[b];
-      q = D3Plain();
-      q.M = n; q.N = B.nout; q.A = B.u2_r; q.SA = S_CAT; q.S = S_CAT; q.B = B.Wout_r; q.bias = B.bout; q.out = B.head; q.ldo = B.nout;
-    }
-    launch_n(st, L, 2);
-  }
-  // ================= loss and its gradient w.r.t. the two heads (ppo_policy.py:189-241) =================
-  rc = egx_ppo_loss_packed_precleared(h->br[0].head, h->br[1].head, act, adv, ret, logp_old, adv_stats, scale, adv_eps, min_logvar, max_logvar,
-                               eps_clip, vf_coef, ent_coef, n, h->br[0].ghead, h->br[1].ghead, out_terms, st, hd ? hd->cursor : nullptr,
-                               hd ? hd->max_cursor : 0);
-  if (rc) return rc;
-  run_table(st, h->tab_loss, h->n_loss, h->frags_loss, d3_planes(h->prec));
-  // ================= backward =================
-  // Input-gradient products form the dependent chain (out_fc -> unit 2 -> unit 1 -> GRU cells); each layer's weight-gradient
-  // product follows the launch that left its gradient image behind.  (Weight gradients on a second stream beside the chain,
-  // and fused into the input-gradient launches, were both measured and are not faster: profiles/r03_update_experiments.md.)
-  hipStream_t sw = st;
-  auto wgrad = [&](D3Plain& q, const bf16x8* gT, const bf16x8* xT, int rows, float* gW, float* gb) {
-    q = D3Plain();
-    q.M = rows; q.N = CAT + 1; q.A = gT; q.SA = Sn; q.S = Sn; q.B = xT; q.out = gW; q.ldo = CAT; q.n_split = CAT; q.bias_out = gb;
-  };
-  Branch &Ba = h->br[0], &Bc = h->br[1];
-  D3Plain W[4], D[2];
-  for (int b = 0; b < 2; ++b) wgrad(W[b], h->br[b].gheadT, h->br[b].u2T, h->br[b].nout, h->br[b].gWout, h->br[b].gbout);
-  launch_n(sw, W, 2);
-  // input gradient of one layer for both blocks: d = g_in W^T-image (+ skip) -> fp32 `out` raw, images gated by act'(a[gate])
-  auto dgrad = [&](const bf16x8* const (&gin)[2], const int (&S_in)[2], const bf16x8* const (&Wt)[2], float* const (&res)[2],
-                   float* const (&outf)[2], int gate, int lout) {
-    for (int b = 0; b < 2; ++b) {
-      Branch& B = h->br[b];
-      D3Plain& d = D[b];
-      d = D3Plain();
-      d.M = n; d.N = CAT; d.A = gin[b]; d.SA = S_in[b]; d.S = S_in[b]; d.B = Wt[b];
-      d.res = res[b]; d.ldr = CAT; d.out = outf[b]; d.ldo = CAT;
-      if (gate >= 0) {
-        d.dact = B.a[gate]; d.lddact = CAT; d.dact_code = 3; d.dact_slope = slope;
-        d.out3 = B.g_r[lout]; d.S3 = S_CAT; d.out3T = B.gT[lout]; d.S3T = Sn;
-      }
-    }
-    launch_n(st, D, 2);
-  };
-  const int S_head[2] = {egx_ceil_div(Ba.nout, 32), egx_ceil_div(Bc.nout, 32)}, S_full[2] = {S_CAT, S_CAT};
-  float* const none[2] = {nullptr, nullptr};
-  {   // out_fc: du2 = g W_out -> g4 = du2 x lrelu'(a4)
-    const bf16x8* const gin[2] = {Ba.ghead_r, Bc.ghead_r};
-    const bf16x8* const Wt[2] = {Ba.Wout_t, Bc.Wout_t};
-    float* const outf[2] = {Ba.du2, Bc.du2};
-    dgrad(gin, S_head, Wt, none, outf, 3, 3);
-  }
-  // layer l of both blocks: the input gradient now (the dependent chain); its weight gradient dW_l = g_l^T x_l only needs the
-  // images this launch leaves behind, so the eight weight-gradient products of the four layers go out afterwards as two
-  // four-product launches (fewer, fuller launches: ~10 us of every launch is fixed cost, profiles/r03_update_experiments.md)
-  D3Plain WL[8];
-  auto layer_bwd = [&](int l, bf16x8* const (&xT)[2], float* const (&res)[2], float* const (&outf)[2], int gate) {
-    for (int b = 0; b < 2; ++b) wgrad(WL[2 * l + b], h->br[b].gT[l], xT[b], CAT, h->br[b].gW[l], h->br[b].gb[l]);
-    const bf16x8* const gin[2] = {Ba.g_r[l], Bc.g_r[l]};
-    const bf16x8* const Wt[2] = {Ba.W_t[l], Bc.W_t[l]};
-    dgrad(gin, S_full, Wt, res, outf, gate, gate);
-    return EGX_OK;
-  };
-  {
-    bf16x8* const x3[2] = {Ba.a3T, Bc.a3T};
-    if ((rc = layer_bwd(3, x3, none, none, 2))) return rc;                    // d(a3) = g4 W4 -> g3
-    bf16x8* const x2[2] = {Ba.u1T, Bc.u1T};
-    float* const du2[2] = {Ba.du2, Bc.du2};
-    float* const du1[2] = {Ba.du1, Bc.du1};
-    if ((rc = layer_bwd(2, x2, du2, du1, 1))) return rc;                      // du1 = g3 W3 + du2 -> g2
-    bf16x8* const x1[2] = {Ba.a1T, Bc.a1T};
-    if ((rc = layer_bwd(1, x1, none, none, 0))) return rc;                    // d(a1) = g2 W2 -> g1
-    bf16x8* const x0[2] = {h->catT, h->catT};
-    float* const dhx[2] = {Ba.dhx, Bc.dhx};
-    if ((rc = layer_bwd(0, x0, du1, dhx, -1))) return rc;                     // dhx = g1 W1 + du1
-    launch_n(sw, WL, 4);
-    launch_n(sw, WL + 4, 4);
-  }
-  }   // parts & 1: every gradient of the actor and critic blocks is enqueued
-  // ---- the two GRU encoders (dhx = actor's + critic's)
-  if (parts & 2) {
-    hipStream_t sw = st;
-    GruBwd2 two;
-    const int blocks = (n / 32) * (HD / 32);
-    two.blocks0 = blocks;
-    GruBwd* gb[2] = {&two.a, &two.b};
-    for (int e = 0; e < 2; ++e) {   // step 2
-      Encoder& E = h->enc[e];
-      GruBwd& q = *gb[e];
-      q.gi = E.gi2; q.gh = E.gh2; q.bias_h = E.bhh; q.h_prev = E.h1f;
-      q.dh0 = h->br[0].dhx + E.cat_off; q.ld0 = CAT; q.dh1 = h->br[1].dhx + E.cat_off; q.ld1 = CAT;
-      q.dgiT = E.dgiT; q.dghT = E.dghT; q.ST = 2 * Sn; q.s0T = Sn; q.dgh_r = E.dgh_r; q.dhp = E.dhp; q.M = n; q.H = HD;
-    }
-    hipLaunchKernelGGL(egx_gru_bwd3_kernel, dim3(2 * blocks), dim3(256), 0, st, two);
-    D3Plain P[4];
-    for (int e = 0; e < 2; ++e) {   // dh1 = dh z + dgh2 W_hh
-      Encoder& E = h->enc[e];
-      D3Plain& d = P[e];
-      d = D3Plain();
-      d.M = n; d.N = HD; d.A = E.dgh_r; d.SA = S_G; d.S = S_G; d.B = E.Whh_t; d.res = E.dhp; d.ldr = HD; d.out = E.dh1; d.ldo = HD;
-    }
-    launch_n(st, P, 2);
-    for (int e = 0; e < 2; ++e) {   // step 1 (h0 = 0: gh = b_hh)
-      Encoder& E = h->enc[e];
-      GruBwd& q = *gb[e];
-      q.gi = E.gi1; q.gh = nullptr; q.h_prev = nullptr; q.dh0 = E.dh1; q.ld0 = HD; q.dh1 = nullptr; q.ld1 = 0;
-      q.s0T = 0; q.dgh_r = nullptr; q.dhp = nullptr;
-    }
-    hipLaunchKernelGGL(egx_gru_bwd3_kernel, dim3(2 * blocks), dim3(256), 0, st, two);
-      for (int e = 0; e < 2; ++e) {   // dW_ih = [dgi1; dgi2]^T [x0; x1], dW_hh = [dgh1; dgh2]^T [0; h1]; the ones rows give the biases
-      Encoder& E = h->enc[e];
-      D3Plain& a = P[2 * e];
-      a = D3Plain();
-      a.M = 3 * HD; a.N = E.in_dim + 1; a.A = E.dgiT; a.SA = 2 * Sn; a.S = 2 * Sn; a.B = E.xT; a.out = E.gWih; a.ldo = E.in_dim;
-      a.n_split = E.in_dim; a.bias_out = E.gbih;
-      D3Plain& c = P[2 * e + 1];
-      c = D3Plain();
-      c.M = 3 * HD; c.N = HD + 1; c.A = E.dghT; c.SA = 2 * Sn; c.S = 2 * Sn; c.B = E.hprevT; c.out = E.gWhh; c.ldo = HD;
-      c.n_split = HD; c.bias_out = E.gbhh;
-    }
-    launch_n(sw, P, 4);
-  }
-  EGX_HIP_CHECK(hipGetLastError());
-  return EGX_OK;
+  return train_step_head(h, head, scale, {adv_eps, min_logvar, max_logvar, eps_clip, vf_coef, ent_coef}, stream_, 1);
 }

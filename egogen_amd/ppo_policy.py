@@ -10,9 +10,11 @@ products) stays as the checker of the chain and serves minibatches that are not 
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import math
 import os
+import warnings
 from typing import Dict, List, Optional
 
 import numpy as np
@@ -26,6 +28,8 @@ from .models import ActorCritic, GAMMAActor, GAMMACritic, GAMMAPolicyBase, Polic
 _EPS = float(np.finfo(np.float32).eps)  # tianshou BasePolicy._eps
 _LOG_SQRT_2PI = math.log(math.sqrt(2 * math.pi))
 _UPDATE_PREC = {"f32": 0, "bf16x2": 2, "bf16": 1}
+# a train handle's compact copies of the minibatch's rows, by name: what the loss kernel reads, and the observations
+_LOSS_ROWS, _OBS_ROWS = ("act", "adv", "ret", "logp_old"), ("state", "egosensing", "dist", "time")
 
 
 class RunningMeanStd:
@@ -77,6 +81,22 @@ class RolloutBatch:
         k = self.n if upto is None else upto
         return {"state": self.state[:k].reshape(-1, 2, 402), "egosensing": self.ego[:k].reshape(-1, 2, 32),
                 "dist": self.dist[:k].reshape(-1), "time": self.time[:k].reshape(-1)}
+
+
+def rollout_rows(batch: RolloutBatch) -> List[torch.Tensor]:
+    """Eight [N, w] views of the rollout's rows: state 804, egosensing 64, dist 1, time 1, act 128, adv 1, returns 1, logp_old 1."""
+    N = batch.n * batch.A
+    obs = batch.obs_flat()
+    return [obs["state"].reshape(N, 804), obs["egosensing"].reshape(N, 64), obs["dist"].reshape(N, 1), obs["time"].reshape(N, 1),
+            batch.act.reshape(N, 128), batch.adv.reshape(N, 1), batch.returns.reshape(N, 1), batch.logp_old.reshape(N, 1)]
+
+
+def minibatch_spans(N: int, size: int) -> List[tuple]:
+    """Batch.split(size, merge_last=True) as (start, end) spans of N rows: a rest shorter than `size` joins the span before it."""
+    bounds = list(range(0, N, size))
+    if len(bounds) > 1 and N - bounds[-1] < size:
+        bounds.pop()
+    return list(zip(bounds, bounds[1:] + [N]))
 
 
 class GAMMAPPOPolicy(nn.Module):
@@ -305,10 +325,7 @@ class GAMMAPPOPolicy(nn.Module):
         obs_all = batch.obs_flat()
         if idx.is_cuda and self.use_fused_loss and all(v.dtype == torch.float32 for v in obs_all.values()):
             from .fused_ops import gather_rows  # eight row gathers in one launch
-            st, ego, di, ti, act, adv, ret, lpo = gather_rows(idx, [
-                obs_all["state"].reshape(N, 804), obs_all["egosensing"].reshape(N, 64), obs_all["dist"].reshape(N, 1),
-                obs_all["time"].reshape(N, 1), batch.act.reshape(N, 128), batch.adv.reshape(N, 1), batch.returns.reshape(N, 1),
-                batch.logp_old.reshape(N, 1)])
+            st, ego, di, ti, act, adv, ret, lpo = gather_rows(idx, rollout_rows(batch))
             n = idx.shape[0]
             obs = {"state": st.reshape(n, 2, 402), "egosensing": ego.reshape(n, 2, 32), "dist": di.reshape(n), "time": ti.reshape(n)}
             return obs, act, adv.reshape(n), ret.reshape(n), lpo.reshape(n)
@@ -351,26 +368,24 @@ class GAMMAPPOPolicy(nn.Module):
         h = C.c_void_p()
         _lib.check(lib.egx_policy_train_create(C.byref(w), C.byref(g), int(n), C.byref(h)), "egx_policy_train_create")
         _lib.check(lib.egx_policy_train_set_precision(h, _UPDATE_PREC[self.update_precision]), "egx_policy_train_set_precision")
-        dev = self._flat_grad.device
-        f = dict(dtype=torch.float32, device=dev)
+        f = dict(dtype=torch.float32, device=self._flat_grad.device)
         # EGX_UPDATE_HEAD=0: the minibatch's head as the five launches it used to be (gather, statistics, input images,
         # positional encoding; index copy and log clone around a replay) - the A/B switch of profiles/update_head.md
         head = os.environ.get("EGX_UPDATE_HEAD", "1") != "0"
         # compact copies of the minibatch's rows: with the head launch only what the loss kernel reads (act, adv, returns,
         # logp_old) - the observations are read from the rollout in place
-        bufs = [None if head else torch.empty(n, 804, **f), None if head else torch.empty(n, 64, **f),
-                None if head else torch.empty(n, 1, **f), None if head else torch.empty(n, 1, **f),
-                torch.empty(n, 128, **f), torch.empty(n, 1, **f), torch.empty(n, 1, **f), torch.empty(n, 1, **f)]
+        obs = [] if head else [torch.empty(n, k, **f) for k in (804, 64, 1, 1)]
+        loss = [torch.empty(n, k, **f) for k in (128, 1, 1, 1)]
         if not head:
-            _lib.check(lib.egx_policy_train_bind(h, _lib.ptr(bufs[0]), _lib.ptr(bufs[1])), "egx_policy_train_bind")
+            _lib.check(lib.egx_policy_train_bind(h, _lib.ptr(obs[0]), _lib.ptr(obs[1])), "egx_policy_train_bind")
         packed = _lib.PolicyPacked3()
         _lib.check(lib.egx_policy_train_packed(h, C.byref(packed)), "egx_policy_train_packed")
-        hs = {"h": h, "n": int(n), "bufs": bufs, "stats": torch.zeros(2, **f), "key": (w.x_enc_w_ih, g.x_enc_w_ih), "packed": packed,
-              "head": head}
+        # the handle: named fields; the compact observations exist only without the head launch, which reads the rollout in place
+        hs = {"h": h, "n": int(n), "head": head, "packed": packed, "stats": torch.zeros(2, **f),
+              **dict(zip(_LOSS_ROWS, loss)), **dict(zip(_OBS_ROWS, obs))}
         self._train_handles[n] = hs
         if len(self._train_handles) == 1:   # the rollout forward reads the images this handle keeps current
             self._runner.adopt_packed(packed, refresh=self._refresh_images)
-            self._images_owner = n
         self._refresh_images()
         return hs
 
@@ -438,63 +453,60 @@ class GAMMAPPOPolicy(nn.Module):
         bucket while "encoders" - the GRU encoders' backward - runs).
         `cursor` (head path): int32 device scalar k - the minibatch is rows idx[k n : (k + 1) n] and its loss terms go to row k
         of `log_out`; None: k = 0, idx is the minibatch."""
+        if part == "encoders":
+            _lib.check(_lib.load().egx_policy_train_step_encoders(hs["h"], _lib.current_stream_ptr()), "egx_policy_train_step_encoders")
+        elif hs["head"]:
+            self._train_step_head(hs, batch, idx, gstats, log_out, part, cursor)
+        else:
+            self._train_step_compact(hs, batch, idx, gstats, log_out, part)
+
+    def _normaliser(self, n: int, dev, gstats, out: Optional[torch.Tensor] = None):
+        """(stats, scale) of a minibatch's loss from `gstats` = (mean, std, n_global) of the GLOBAL minibatch, the statistics also
+        written to `out`; without them (None, the cached constant 1 / n): the caller computes the statistics of its own rows."""
+        if gstats is None:
+            if (n, dev) not in self._scale_cache:
+                self._scale_cache[(n, dev)] = torch.full((1,), 1.0 / n, dtype=torch.float32, device=dev)
+            return None, self._scale_cache[(n, dev)]
+        stats = torch.stack([gstats[0], gstats[1]]).float() if self._norm_adv else None
+        if out is not None:
+            stats = out.copy_(stats)
+        return stats, (1.0 / gstats[2]).reshape(1).float()
+
+    def _loss_consts(self):
+        return (float(_EPS), float(self.actor.min_logvar), float(self.actor.max_logvar), float(self._eps_clip), float(self._weight_vf),
+                float(self._weight_ent))
+
+    def _train_step_head(self, hs: dict, batch, idx, gstats, log_out, part, cursor):
+        n = hs["n"]
+        idx = idx.contiguous()
+        rows = int(idx.numel()) // n
+        assert idx.dtype == torch.long and rows >= 1 and (cursor is not None or int(idx.numel()) == n), (idx.dtype, idx.shape, n)
+        assert log_out.is_contiguous() and log_out.dtype == torch.float32 and log_out.numel() >= 6 * rows, log_out.shape
+        srcs = rollout_rows(batch)
+        assert all(t.dtype == torch.float32 and t.is_contiguous() for t in srcs)
+        _, scale = self._normaliser(n, hs["stats"].device, gstats, out=hs["stats"])
+        hd = _lib.UpdateHead()
+        hd.perm, hd.cursor = idx.data_ptr(), (cursor.data_ptr() if cursor is not None else None)
+        hd.max_cursor, hd.num_src_rows = rows - 1, batch.n * batch.A
+        (hd.state, hd.egosensing, hd.dist, hd.time, hd.act, hd.adv, hd.ret, hd.logp_old) = (t.data_ptr() for t in srcs)
+        hd.act_c, hd.adv_c, hd.ret_c, hd.logp_old_c = (hs[k].data_ptr() for k in _LOSS_ROWS)
+        hd.stats, hd.compute_stats, hd.log = hs["stats"].data_ptr(), int(gstats is None), log_out.data_ptr()
+        lib = _lib.load()
+        fn = lib.egx_policy_train_step_heads_cursor if part == "heads" else lib.egx_policy_train_step_cursor
+        _lib.check(fn(hs["h"], C.byref(hd), _lib.ptr(scale), *self._loss_consts(), _lib.current_stream_ptr()), "egx_policy_train_step_cursor")
+
+    def _train_step_compact(self, hs: dict, batch, idx, gstats, log_out, part):
+        """EGX_UPDATE_HEAD=0: row gather and advantage statistics as launches of their own in front of the chain."""
         from .fused_ops import gather_rows
         lib, st = _lib.load(), _lib.current_stream_ptr()
-        if part == "encoders":
-            _lib.check(lib.egx_policy_train_step_encoders(hs["h"], st), "egx_policy_train_step_encoders")
-            return
-        N = batch.n * batch.A
-        obs_all = batch.obs_flat()
-        b = hs["bufs"]
-        if hs["head"]:
-            n = hs["n"]
-            idx = idx.contiguous()
-            rows = int(idx.numel()) // n
-            assert idx.dtype == torch.long and rows >= 1 and (cursor is not None or int(idx.numel()) == n), (idx.dtype, idx.shape, n)
-            assert log_out.is_contiguous() and log_out.dtype == torch.float32 and log_out.numel() >= 6 * rows, log_out.shape
-            srcs = (obs_all["state"], obs_all["egosensing"], obs_all["dist"], obs_all["time"], batch.act, batch.adv, batch.returns,
-                    batch.logp_old)
-            assert all(t.dtype == torch.float32 and t.is_contiguous() for t in srcs)
-            dev = b[4].device
-            if gstats is None:
-                scale = self._scale_cache.get((n, dev))
-                if scale is None:
-                    scale = torch.full((1,), 1.0 / n, dtype=torch.float32, device=dev)
-                    self._scale_cache[(n, dev)] = scale
-            else:
-                hs["stats"].copy_(torch.stack([gstats[0], gstats[1]]).float())
-                scale = (1.0 / gstats[2]).reshape(1).float()
-            hd = _lib.UpdateHead()
-            hd.perm, hd.cursor = idx.data_ptr(), (cursor.data_ptr() if cursor is not None else None)
-            hd.max_cursor, hd.num_src_rows = rows - 1, N
-            (hd.state, hd.egosensing, hd.dist, hd.time, hd.act, hd.adv, hd.ret, hd.logp_old) = (t.data_ptr() for t in srcs)
-            hd.act_c, hd.adv_c, hd.ret_c, hd.logp_old_c = (b[i].data_ptr() for i in (4, 5, 6, 7))
-            hd.stats, hd.compute_stats, hd.log = hs["stats"].data_ptr(), int(gstats is None), log_out.data_ptr()
-            fn = lib.egx_policy_train_step_heads_cursor if part == "heads" else lib.egx_policy_train_step_cursor
-            rc = fn(hs["h"], C.byref(hd), _lib.ptr(scale), float(_EPS), float(self.actor.min_logvar), float(self.actor.max_logvar),
-                    float(self._eps_clip), float(self._weight_vf), float(self._weight_ent), st)
-            _lib.check(rc, "egx_policy_train_step_cursor")
-            return
-        gather_rows(idx, [obs_all["state"].reshape(N, 804), obs_all["egosensing"].reshape(N, 64), obs_all["dist"].reshape(N, 1),
-                          obs_all["time"].reshape(N, 1), batch.act.reshape(N, 128), batch.adv.reshape(N, 1), batch.returns.reshape(N, 1),
-                          batch.logp_old.reshape(N, 1)], out=b)
+        gather_rows(idx, rollout_rows(batch), out=[hs[k] for k in _OBS_ROWS + _LOSS_ROWS])
         n = int(idx.shape[0])
-        dev = b[0].device
         if gstats is None:
-            _lib.check(lib.egx_adv_stats(_lib.ptr(b[5]), n, _lib.ptr(hs["stats"]), st), "egx_adv_stats")
-            scale = self._scale_cache.get((n, dev))
-            if scale is None:
-                scale = torch.full((1,), 1.0 / n, dtype=torch.float32, device=dev)
-                self._scale_cache[(n, dev)] = scale
-        else:
-            hs["stats"].copy_(torch.stack([gstats[0], gstats[1]]).float())
-            scale = (1.0 / gstats[2]).reshape(1).float()
+            _lib.check(lib.egx_adv_stats(_lib.ptr(hs["adv"]), n, _lib.ptr(hs["stats"]), st), "egx_adv_stats")
+        _, scale = self._normaliser(n, hs["stats"].device, gstats, out=hs["stats"])
         fn = lib.egx_policy_train_step_heads if part == "heads" else lib.egx_policy_train_step
-        rc = fn(hs["h"], _lib.ptr(b[2]), _lib.ptr(b[3]), _lib.ptr(b[4]), _lib.ptr(b[5]), _lib.ptr(b[6]), _lib.ptr(b[7]),
-                _lib.ptr(hs["stats"]), _lib.ptr(scale), float(_EPS), float(self.actor.min_logvar),
-                float(self.actor.max_logvar), float(self._eps_clip), float(self._weight_vf), float(self._weight_ent),
-                _lib.ptr(log_out), st)
-        _lib.check(rc, "egx_policy_train_step")
+        _lib.check(fn(hs["h"], _lib.ptr(hs["dist"]), _lib.ptr(hs["time"]), *(_lib.ptr(hs[k]) for k in _LOSS_ROWS), _lib.ptr(hs["stats"]),
+                      _lib.ptr(scale), *self._loss_consts(), _lib.ptr(log_out), st), "egx_policy_train_step")
 
     def _fwd_bwd(self, batch, idx, gstats, log_out, cursor=None, n=None) -> str:
         """Forward, loss and backward of one minibatch into the flat gradient; returns which formulation ran ("chain": the
@@ -667,81 +679,93 @@ class GAMMAPPOPolicy(nn.Module):
             s = self._comm_s = torch.cuda.Stream()
         return s
 
-    def _graphs_for(self, batch: RolloutBatch, local_bs: int):
-        """Capture (gather + forward + loss + backward) and (clip + AdamW) for a fixed minibatch size.  With one rank
-        both halves live in one graph; with several, the RCCL all-reduces run eagerly between the two replays."""
-        key = (id(batch), local_bs)
-        g = self._graph_cache.get(key)
-        if g is not None:
-            return g
+    def _new_graph_state(self, batch: RolloutBatch, local_bs: int) -> dict:
+        """What the graphs of one (rollout, minibatch size) read and write.  With the head launch the epoch's permutation, the
+        minibatch cursor and one log row per minibatch live on the device: nothing is copied between two replays (learn() writes
+        the permutation and zeroes the cursor once per epoch); without it `idx` and one log row are copied around every replay."""
         dev = batch.act.device
-        st = {"gstats": torch.tensor([0.0, 1.0, float(local_bs * self.world_size)], device=dev), "use_gstats": self._dp}
-        hs0 = self._train_handle(local_bs) if dev.type == "cuda" else None
-        st["head"] = hs0 is not None and hs0["head"] and self.use_flat_optimizer and self._flat_opt_state == "ready"
-        if st["head"]:
-            # the epoch's permutation, the minibatch cursor and one log row per minibatch live on the device: nothing is copied
-            # between two replays (learn() writes the permutation and zeroes the cursor once per epoch)
-            rows = max(1, (batch.n * batch.A) // local_bs)
-            st.update(rows=rows, perm=torch.zeros(rows * local_bs, dtype=torch.long, device=dev), log=torch.zeros(rows, 6, device=dev),
-                      cursor=torch.zeros((), dtype=torch.int32, device=dev))
-            fb_args, fb_kw = (st["perm"], ), dict(cursor=st["cursor"], n=local_bs)
-        else:
-            st.update(idx=torch.zeros(local_bs, dtype=torch.long, device=dev), log=torch.zeros(6, device=dev))
-            fb_args, fb_kw = (st["idx"], ), {}
-        cur = st.get("cursor")
-        gs = (lambda: (st["gstats"][0], st["gstats"][1], st["gstats"][2])) if st["use_gstats"] else (lambda: None)
-        try:
-            # warm-up on a side stream (lazy library init, allocator pools) - it performs real optimiser steps on a
-            # throw-away copy of the state, which is restored afterwards
-            snap = {k: v.clone() for k, v in self.state_dict().items()}
-            params = [p_ for g_ in self.optim.param_groups for p_ in g_["params"]]
-            osnap = {id(p_): {k: v.clone() for k, v in self.optim.state.get(p_, {}).items() if torch.is_tensor(v)} for p_ in params}
-            side = torch.cuda.Stream()
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
-                for _ in range(3):
-                    self._fwd_bwd(batch, *fb_args, gs(), st["log"], **fb_kw)
-                    self._clip_and_step(cur)
-            torch.cuda.current_stream().wait_stream(side)
-            torch.cuda.synchronize()
-            g1 = torch.cuda.CUDAGraph()
-            g2 = None
-            if not self._dp:
-                with torch.cuda.graph(g1):
-                    st["path"] = self._fwd_bwd(batch, *fb_args, gs(), st["log"], **fb_kw)
-                    self._clip_and_step(cur)
+        gstats = torch.tensor([0.0, 1.0, float(local_bs * self.world_size)], device=dev)
+        hs = self._train_handle(local_bs) if dev.type == "cuda" else None
+        head = hs is not None and hs["head"] and self.use_flat_optimizer and self._flat_opt_state == "ready"
+        rows = max(1, (batch.n * batch.A) // local_bs) if head else None
+        return {"gstats": gstats, "use_gstats": self._dp, "head": head, "rows": rows,
+                "perm": torch.zeros(rows * local_bs, dtype=torch.long, device=dev) if head else None,
+                "idx": None if head else torch.zeros(local_bs, dtype=torch.long, device=dev),
+                "log": torch.zeros(rows, 6, device=dev) if head else torch.zeros(6, device=dev),
+                "cursor": torch.zeros((), dtype=torch.int32, device=dev) if head else None,
+                "g1": None, "g1b": None, "g2": None, "path": None, "prec_key": None, "failed": False}
+
+    def _graph_fwd_bwd(self, batch: RolloutBatch, local_bs: int, st: dict, part: Optional[str] = None) -> str:
+        """The minibatch the graphs of `st` are made from, or with `part` one half of its chain (_fwd_bwd_train_step)."""
+        ids = st["perm"] if st["head"] else st["idx"]
+        gs = (st["gstats"][0], st["gstats"][1], st["gstats"][2]) if st["use_gstats"] else None
+        if part is None:
+            return self._fwd_bwd(batch, ids, gs, st["log"], **(dict(cursor=st["cursor"], n=local_bs) if st["head"] else {}))
+        self._fwd_bwd_train_step(self._train_handle(local_bs), batch, ids, gs, st["log"], part=part, cursor=st["cursor"])
+        return "chain"
+
+    @contextlib.contextmanager
+    def _warmed_up(self, step):
+        """Three runs of `step` on a side stream (lazy library init, allocator pools) before the block's captures.  They are real
+        optimiser steps: model and optimiser state get their values back IN PLACE after it (the graphs hold the live addresses)."""
+        snap = {k: v.clone() for k, v in self.state_dict().items()}
+        params = [p for g in self.optim.param_groups for p in g["params"]]
+        osnap = {id(p): {k: v.clone() for k, v in self.optim.state.get(p, {}).items() if torch.is_tensor(v)} for p in params}
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            for _ in range(3):
+                step()
+        torch.cuda.current_stream().wait_stream(side)
+        torch.cuda.synchronize()
+        yield
+        self.load_state_dict(snap)
+        for p in params:
+            for k, v in self.optim.state.get(p, {}).items():
+                if torch.is_tensor(v):
+                    old_v = osnap[id(p)].get(k)
+                    v.copy_(old_v) if old_v is not None else v.zero_()
+
+    def _capture(self, fwd_bwd, clip_and_step, halves: bool) -> dict:
+        """One graph; with data parallelism two around the all-reduce (g1 | g2 = clip + AdamW); with `halves` three: after g1
+        (heads) the actor + critic bucket is final and its all-reduce runs on a side stream beside g1b (the encoders' backward)."""
+        g1, g1b, g2, path = torch.cuda.CUDAGraph(), None, None, "chain"
+        with torch.cuda.graph(g1):
+            if halves:
+                fwd_bwd(part="heads")
             else:
-                hs = self._train_handle(local_bs) if dev.type == "cuda" else None
-                if hs is not None and len(self._grad_buckets()) == 2 and self.overlap_allreduce:
-                    # the chain in two halves: after g1 (heads) the actor + critic bucket is final and its all-reduce runs on a
-                    # side stream beside g1b (the encoders' backward)
-                    with torch.cuda.graph(g1):
-                        self._fwd_bwd_train_step(hs, batch, *fb_args, gs(), st["log"], part="heads", cursor=cur)
-                    g1b = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(g1b, pool=g1.pool()):
-                        self._fwd_bwd_train_step(hs, batch, *fb_args, gs(), st["log"], part="encoders")
-                    st["g1b"], st["path"] = g1b, "chain"
-                else:
-                    with torch.cuda.graph(g1):
-                        st["path"] = self._fwd_bwd(batch, *fb_args, gs(), st["log"], **fb_kw)
-                g2 = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g2, pool=g1.pool()):
-                    self._clip_and_step(cur)
-            # capture does not execute, but the warm-up steps did: restore parameters and optimiser state IN PLACE
-            # (the graphs hold the addresses of the live tensors)
-            self.load_state_dict(snap)
-            for p_ in params:
-                for k, v in self.optim.state.get(p_, {}).items():
-                    if torch.is_tensor(v):
-                        old_v = osnap[id(p_)].get(k)
-                        v.copy_(old_v) if old_v is not None else v.zero_()
-            st["g1"], st["g2"] = g1, g2
+                path = fwd_bwd()
+            if not self._dp:
+                clip_and_step()
+        if halves:
+            g1b = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g1b, pool=g1.pool()):
+                fwd_bwd(part="encoders")
+        if self._dp:
+            g2 = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g2, pool=g1.pool()):
+                clip_and_step()
+        return {"g1": g1, "g1b": g1b, "g2": g2, "path": path}
+
+    def _graphs_for(self, batch: RolloutBatch, local_bs: int) -> dict:
+        """Capture (gather + forward + loss + backward) and (clip + AdamW) for a fixed minibatch size.  With one rank
+        both halves live in one graph; with several, the RCCL all-reduces run eagerly between the replays."""
+        key = (id(batch), local_bs)
+        st = self._graph_cache.get(key)
+        if st is not None:
+            return st
+        st = self._new_graph_state(batch, local_bs)
+        fwd_bwd = lambda part=None: self._graph_fwd_bwd(batch, local_bs, st, part)
+        clip_and_step = lambda: self._clip_and_step(st["cursor"])
+        try:
+            with self._warmed_up(lambda: (fwd_bwd(), clip_and_step())):
+                halves = self._dp and self.overlap_allreduce and len(self._grad_buckets()) == 2 and self._train_handle(local_bs) is not None
+                st.update(self._capture(fwd_bwd, clip_and_step, halves))
             st["prec_key"] = self._prec_key()   # the captured refresh writes the planes of these precisions
-            if cur is not None:
-                cur.zero_()          # the warm-up steps advanced it
+            if st["cursor"] is not None:
+                st["cursor"].zero_()            # the warm-up steps advanced it
             self._refresh_images()   # the packed weight images followed the warm-up steps: back to the restored parameters
         except Exception as e:  # capture unsupported for some op on this stack: run the same ops eagerly
-            import warnings
             warnings.warn(f"PPO update graph capture failed ({type(e).__name__}: {e}); running the update eagerly")
             st["g1"] = st["g2"] = None
             st["failed"] = True
@@ -764,22 +788,10 @@ class GAMMAPPOPolicy(nn.Module):
             hx = self.shared_net(obs)
             (mu, logvar), _ = self.actor(hx)
             value = self.critic(hx).flatten()
-        n_local = adv.shape[0]
-        dev = adv.device
-        stats = None
-        if self._norm_adv:
-            if global_stats is None:
-                from .fused_ops import adv_stats
-                stats = adv_stats(adv)
-            else:
-                stats = torch.stack([global_stats[0], global_stats[1]]).float()
-        if global_stats is None:
-            scale = self._scale_cache.get((n_local, dev))
-            if scale is None:  # constant: built once, outside any graph capture
-                scale = torch.full((1,), 1.0 / n_local, dtype=torch.float32, device=dev)
-                self._scale_cache[(n_local, dev)] = scale
-        else:
-            scale = (1.0 / global_stats[2]).reshape(1).float()
+        stats, scale = self._normaliser(adv.shape[0], adv.device, global_stats)
+        if stats is None and self._norm_adv:
+            from .fused_ops import adv_stats
+            stats = adv_stats(adv)
         if zp is not None:
             loss, terms = PPOLossPackedFn.apply(zp, value, act, adv, returns, logp_old, stats, scale, _EPS, self.actor.min_logvar,
                                                 self.actor.max_logvar, self._eps_clip, self._weight_vf, self._weight_ent)
@@ -789,6 +801,72 @@ class GAMMAPPOPolicy(nn.Module):
         return loss, {"loss": terms[0], "loss/clip": terms[1], "loss/vf": terms[2], "loss/ent": terms[3], "loss/kld": terms[4],
                       "approx_kl": terms[5], "_packed": terms}
 
+    def _recompute_advantages(self, batch: RolloutBatch):
+        self._recomputing = True   # ppo_policy.py:185-186: values of ALL observations with the current weights
+        try:
+            # replayed update graphs write the parameters by address (no tensor version changes, and the
+            # mark_dirty() inside _clip_and_step ran at capture time only): the packed images the value pass
+            # reads must be re-made from the CURRENT weights first
+            self._runner.mark_dirty()
+            self._refresh_images()
+            self.process_fn(batch)
+        finally:
+            self._recomputing = False
+
+    def _replay_minibatch(self, st: dict, idx: torch.Tensor, gstats_row) -> Optional[torch.Tensor]:
+        """One optimiser step as replayed graphs, the all-reduce between them.  Returns the six loss terms, or None with the head
+        launch: they are row `cursor` of the device log, copied once after the epoch's last replay."""
+        if not st["head"]:
+            st["idx"].copy_(idx)
+        if self._dp:
+            st["gstats"].copy_(gstats_row)
+        st["g1"].replay()
+        if self._dp:
+            if st["g1b"] is not None:
+                # bucket 0 (actor + critic: 78 % of the bytes) is reduced on the communication stream while the
+                # encoders' backward runs on this one; bucket 1 follows it there; clip + AdamW wait for both
+                main, comm = torch.cuda.current_stream(), self._comm_stream()
+                b0, b1 = self._grad_buckets()
+                comm.wait_stream(main)
+                with torch.cuda.stream(comm):
+                    self._all_reduce_grad(b0)
+                st["g1b"].replay()
+                comm.wait_stream(main)
+                with torch.cuda.stream(comm):
+                    self._all_reduce_grad(b1)
+                main.wait_stream(comm)
+            else:
+                self._all_reduce_grad()
+            st["g2"].replay()
+        return None if st["head"] else st["log"].clone()
+
+    def _eager_minibatch(self, batch: RolloutBatch, idx: torch.Tensor, gstats_row):
+        """One optimiser step launch by launch; returns its six loss terms and the formulation that ran."""
+        gstats = (gstats_row[0], gstats_row[1], gstats_row[2]) if self._dp else None
+        log = torch.zeros(6, device=idx.device)
+        path = self._fwd_bwd(batch, idx, gstats, log)
+        if self._dp:
+            self._all_reduce_grad()
+        self._clip_and_step()
+        return log, path
+
+    def _learn_stats(self, batch: RolloutBatch, logs: List[torch.Tensor], kld_rows: List[torch.Tensor]) -> Dict[str, List[float]]:
+        """learn()'s result from every optimiser step's six terms and rows.  `loss/kld` of ppo_policy.py:232 reads minibatch.z_mu -
+        the means the ROLLOUT stored, not the current network's: 0.5 mean(mu_rollout^2) over each minibatch's rows, all at once."""
+        names = ("loss", "loss/clip", "loss/vf", "loss/ent", "loss/kld")
+        if not logs:
+            return {k: [] for k in names}
+        L = torch.stack(logs)[:, :5].contiguous()
+        mu2 = batch.mu.reshape(batch.n * batch.A, -1).pow(2).mean(1)   # [N]: per-row mean of the rollout's mu^2
+        if len({int(r.shape[0]) for r in kld_rows}) == 1:
+            kld = 0.5 * mu2.index_select(0, torch.cat(kld_rows)).reshape(len(kld_rows), -1).mean(1)
+        else:
+            kld = torch.stack([0.5 * mu2.index_select(0, r).mean() for r in kld_rows])
+        L[:, 4] = kld / self.world_size if self._dp else kld          # summed over the ranks below: the global minibatch mean
+        if self._dp:
+            dist.all_reduce(L)
+        return dict(zip(names, L.cpu().t().tolist()))
+
     def learn(self, batch: RolloutBatch, batch_size: int, repeat: int) -> Dict[str, List[float]]:
         """ppo_policy.py:182-265.  `batch_size` is the GLOBAL minibatch size; each rank contributes batch_size/world."""
         self.train()
@@ -796,41 +874,19 @@ class GAMMAPPOPolicy(nn.Module):
         if self.use_flat_optimizer and batch.act.is_cuda:
             self._flat_optimizer_ready()  # (re-)points parameters / optimiser state BEFORE anything is captured
         self._refresh_images_if_stale("learn_top")   # whatever changed the parameters since the last refresh (load_state_dict, ...)
-        ws = self.world_size
-        dp = self._dp
-        N = batch.n * batch.A
-        dev = batch.act.device
-        local_bs = max(1, batch_size // ws)
-        names = ("loss", "loss/clip", "loss/vf", "loss/ent", "loss/kld")
-        stats = {k: [] for k in names}
-        logs = []
+        N, dev = batch.n * batch.A, batch.act.device
+        local_bs = max(1, batch_size // self.world_size)
         use_graph = self.use_update_graph and dev.type == "cuda"
-        kld_rows = []
+        logs, kld_rows = [], []   # per optimiser step: its six loss terms, the rows it used
         for step in range(repeat):
-            if self._recompute_adv and step > 0:    # ppo_policy.py:185-186: values of ALL observations with the current weights
-                self._recomputing = True
-                try:
-                    # replayed update graphs write the parameters by address (no tensor version changes, and the
-                    # mark_dirty() inside _clip_and_step ran at capture time only): the packed images the value pass
-                    # reads must be re-made from the CURRENT weights first
-                    self._runner.mark_dirty()
-                    self._refresh_images()
-                    self.process_fn(batch)
-                finally:
-                    self._recomputing = False
-            if getattr(self, "_perm_queue", None):        # parity tests: the row order the reference's Batch.split drew
-                perm = torch.as_tensor(self._perm_queue.pop(0), dtype=torch.long).to(dev)
-            else:
-                perm = torch.randperm(N, generator=self._perm_gen).to(dev)
-            # Batch.split(size, shuffle=True, merge_last=True)
-            bounds = list(range(0, N, local_bs))
-            if len(bounds) > 1 and N - bounds[-1] < local_bs:
-                bounds.pop()
-            last_log = None
-            spans = [(s, bounds[i + 1] if i + 1 < len(bounds) else N) for i, s in enumerate(bounds)]
-            gstats_all = self._global_adv_stats(batch, perm, spans) if dp else None
+            if self._recompute_adv and step > 0:
+                self._recompute_advantages(batch)
+            queued = getattr(self, "_perm_queue", None)   # parity tests: the row order the reference's Batch.split drew
+            perm = (torch.as_tensor(queued.pop(0), dtype=torch.long) if queued else torch.randperm(N, generator=self._perm_gen)).to(dev)
+            spans = minibatch_spans(N, local_bs)
+            gstats_all = self._global_adv_stats(batch, perm, spans) if self._dp else None
             gst = self._graphs_for(batch, local_bs) if (use_graph and spans[0][1] - spans[0][0] == local_bs) else None
-            if gst is not None and gst.get("g1") is None:
+            if gst is not None and gst["g1"] is None:
                 gst = None
             vsum = self._img_key_now()[0]   # replays write the parameters by address: no version changes under them
             head = gst is not None and gst["head"]
@@ -840,63 +896,26 @@ class GAMMAPPOPolicy(nn.Module):
                 gst["cursor"].zero_()
             for i, (s, e) in enumerate(spans):
                 idx = perm[s:e]
-                st = gst if e - s == local_bs else None
-                if st is not None:
-                    if not head:
-                        st["idx"].copy_(idx)
-                    if dp:
-                        st["gstats"].copy_(gstats_all[i])
-                    st["g1"].replay()
-                    if dp:
-                        if st.get("g1b") is not None:
-                            # bucket 0 (actor + critic: 78 % of the bytes) is reduced on the communication stream while the
-                            # encoders' backward runs on this one; bucket 1 follows it there; clip + AdamW wait for both
-                            main, comm = torch.cuda.current_stream(), self._comm_stream()
-                            b0, b1 = self._grad_buckets()
-                            comm.wait_stream(main)
-                            with torch.cuda.stream(comm):
-                                self._all_reduce_grad(b0)
-                            st["g1b"].replay()
-                            comm.wait_stream(main)
-                            with torch.cuda.stream(comm):
-                                self._all_reduce_grad(b1)
-                            main.wait_stream(comm)
-                        else:
-                            self._all_reduce_grad()
-                        st["g2"].replay()
+                gstats_row = gstats_all[i] if self._dp else None
+                if gst is not None and e - s == local_bs:
+                    log, path = self._replay_minibatch(gst, idx, gstats_row), gst["path"] + "+graph"
                     # the captured refresh re-made the images from the parameters this replay wrote, with the capture's precisions
-                    self._img_key = (vsum, st["prec_key"])
-                    if head:
-                        last_log = None        # row n_replayed of the device log: copied once, after the epoch's last replay
-                        n_replayed += 1
-                    else:
-                        last_log = st["log"].clone()
-                    self.update_paths[st["path"] + "+graph"] = self.update_paths.get(st["path"] + "+graph", 0) + 1
+                    self._img_key = (vsum, gst["prec_key"])
+                    n_replayed += head
                 else:
-                    gstats = None
-                    if dp:
-                        gstats = (gstats_all[i, 0], gstats_all[i, 1], gstats_all[i, 2])
-                    log = torch.zeros(6, device=dev)
-                    path = self._fwd_bwd(batch, idx, gstats, log)
-                    if dp:
-                        self._all_reduce_grad()
-                    self._clip_and_step()
-                    last_log = log
-                    self.update_paths[path] = self.update_paths.get(path, 0) + 1
-                logs.append(last_log)   # six terms (None: a replay's row, filled in below)
+                    log, path = self._eager_minibatch(batch, idx, gstats_row)
+                self.update_paths[path] = self.update_paths.get(path, 0) + 1
+                logs.append(log)
                 if self._after_minibatch is not None:   # parity tests: the flat gradient / clip coefficient of THIS optimiser step
                     self._after_minibatch(len(logs) - 1)
-                # `loss/kld` of ppo_policy.py:232 reads minibatch.z_mu - the means the ROLLOUT stored - not the current network's:
-                # 0.5 mean(mu_rollout^2) over the minibatch's rows, evaluated for all minibatches at once after the loop
                 kld_rows.append(idx)
             if n_replayed:   # the replays come first in an epoch (only its last, merged minibatch can be eager); the next epoch
                 snap = gst["log"][:n_replayed].clone()   # clears these rows again
                 logs[first_log:first_log + n_replayed] = list(snap)
-            last_log = logs[-1] if logs else None
             # early stop on the last minibatch's approximate KL (ppo_policy.py:252-257); inert at repeat=1
-            if repeat > 1 and last_log is not None:
-                kl = last_log[5].clone()
-                if dp:
+            if repeat > 1 and logs:
+                kl = logs[-1][5].clone()
+                if self._dp:
                     dist.all_reduce(kl)
                 if float(kl.item()) >= 0.02:
                     break
@@ -904,19 +923,4 @@ class GAMMAPPOPolicy(nn.Module):
         # a captured refresh writes the planes of the precision in force at capture time; where that is not the precision in
         # force NOW (e.g. egx_policy_set_precision(0) for an fp32 evaluation after bf16x2 training), one eager refresh here
         self._refresh_images_if_stale("learn_bottom")
-        if logs:
-            L = torch.stack(logs)[:, :5].contiguous()
-            mu2 = batch.mu.reshape(N, -1).pow(2).mean(1)               # [N]: per-row mean of the rollout's mu^2
-            if len({int(r.shape[0]) for r in kld_rows}) == 1:
-                kld = 0.5 * mu2.index_select(0, torch.cat(kld_rows)).reshape(len(kld_rows), -1).mean(1)
-            else:
-                kld = torch.stack([0.5 * mu2.index_select(0, r).mean() for r in kld_rows])
-            if dp:
-                kld = kld / ws                                          # summed over the ranks below: the global minibatch mean
-            L[:, 4] = kld
-            if dp:
-                dist.all_reduce(L)
-            for row in L.cpu().tolist():
-                for k, v in zip(names, row):
-                    stats[k].append(v)
-        return stats
+        return self._learn_stats(batch, logs, kld_rows)

@@ -149,6 +149,17 @@ def test_gae_oracle_handcase():
     np.testing.assert_allclose(ret, adv + v[:, :3])
 
 
+def test_minibatch_spans_follow_batch_split_with_merge_last():
+    """learn()'s minibatches are tianshou's Batch.split(size, merge_last=True): a rest shorter than `size` joins the last span."""
+    from egogen_amd.ppo_policy import minibatch_spans
+    assert minibatch_spans(96, 32) == [(0, 32), (32, 64), (64, 96)]
+    assert minibatch_spans(96, 48) == [(0, 48), (48, 96)]
+    assert minibatch_spans(96, 40) == [(0, 40), (40, 96)]
+    for size in (64, 96, 100):
+        assert minibatch_spans(96, size) == [(0, 96)], size
+    assert minibatch_spans(3, 1) == [(0, 1), (1, 2), (2, 3)]
+
+
 def _dp_worker(rank, world, port, n_local, out_path):
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
     dist.init_process_group("gloo", rank=rank, world_size=world)

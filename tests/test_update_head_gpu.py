@@ -171,7 +171,8 @@ def test_log_rows_land_in_minibatch_order(monkeypatch):
     # the persistent buffers of the graphs hold exactly the epoch: N / 32 minibatches of indices, log rows and no more
     assert st["perm"].shape == (N,) and st["perm"].dtype == torch.long and st["log"].shape == (N // 32, 6) and st["rows"] == N // 32
     (hs,) = new[0]._train_handles.values()
-    assert hs["bufs"][:4] == [None] * 4 and [tuple(b.shape) for b in hs["bufs"][4:]] == [(32, 128), (32, 1), (32, 1), (32, 1)]
+    assert not {"state", "egosensing", "dist", "time"} & set(hs)   # no compact observation buffer exists with the head
+    assert [tuple(hs[k].shape) for k in ("act", "adv", "ret", "logp_old")] == [(32, 128), (32, 1), (32, 1), (32, 1)]
 
 
 def test_cursor_counts_the_replays_of_an_epoch(monkeypatch):
