@@ -1,0 +1,5 @@
+def __getattr__(name):      # `from egogen_amd import GeodesicField` without importing torch with the package
+    if name == "GeodesicField":
+        from .geodesic import GeodesicField
+        return GeodesicField
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -207,6 +207,16 @@ SIGNATURES = {
     "egx_primitive_advance_beam": (C.c_int, [C.c_void_p] * 4 + [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_float,
                                              C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 13 + [C.c_int, C.c_void_p, C.c_void_p]),
     "egx_beam_backtrack": (C.c_int, [C.c_void_p] * 10 + [C.c_int] * 3 + [C.c_void_p] * 11),
+    "egx_geodesic_field": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 4 + [C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_int,
+                                     C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_void_p]),
+    "egx_geodesic_sample": (C.c_int, [C.c_void_p, C.c_void_p, C.c_float] + [C.c_int] * 3 + [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "egx_primitive_select_field": (C.c_int, [C.c_void_p] * 3 + [C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 6 +
+                                   [C.POINTER(C.c_float), C.c_float, C.c_float, C.c_float, C.c_int, C.c_int] + [C.c_void_p] * 7 +
+                                   [C.c_void_p, C.c_void_p, C.c_float, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "egx_primitive_beam_select_field": (C.c_int, [C.c_void_p] * 3 + [C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 6 +
+                                        [C.POINTER(C.c_float), C.c_float, C.c_float, C.c_float, C.c_int, C.c_int, C.c_int] +
+                                        [C.c_void_p] * 13 +
+                                        [C.c_void_p, C.c_void_p, C.c_float, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "egx_sample_action": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_int, C.c_int, C.c_void_p,
                                     C.c_void_p, C.c_void_p]),
     "egx_gae": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double, C.c_void_p,

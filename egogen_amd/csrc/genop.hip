@@ -3,9 +3,12 @@
 // (egx_primitive_advance_select).  The beam search keeps W partial paths per sequence: egx_primitive_beam_select scores the W * N
 // rows of a sequence with the same row scoring and keeps the W best path keys, egx_primitive_advance_beam hands each kept row on
 // to the N rows of its slot (one workgroup per slot, R0 / T0 from one buffer into another), egx_beam_backtrack gathers the
-// records of the returned path.  Device code is shared (advance_body, score_group, key_before); so is the host side: the three
-// hand-off entries go through advance_entry and the two selection entries through select_entry (common checks, common fields,
-// launch check), and each entry states only the checks, fields and launch that are its own.
+// records of the returned path.  With a geodesic field (egx_primitive_select_field, egx_primitive_beam_select_field; geodesic.hip
+// builds it) the goal term of both selections is the field's distance along the walkable raster (field_row_cost, a phase after
+// the scoring); the entries without a field launch the same kernels with a null field.  Device code is shared (advance_body,
+// score_group, key_before); so is the host side: the three hand-off entries go through advance_entry and the selection entries
+// through select_entry (common checks, common fields, launch check), and each entry states only the checks, fields and launch
+// that are its own.
 //
 // Reference: the motion-only tail of CrowdEnv.step, motion/crowd_ppo/crowd_env_2f.py:144-155 (pelvis, blended markers) and
 // :238-265 (new canonical frame from the second-last body, accumulated world frame, seed parameters and seed markers in the new
@@ -13,6 +16,7 @@
 // of the env's reward terms (:171-235, egx_reward.h).
 #include "egx_common.h"
 #include "egx_frame.h"
+#include "egx_geodesic.h"
 #include "egx_reward.h"
 
 namespace {
@@ -218,6 +222,7 @@ struct SelectArgs {
   float* cost;                // [B*N]
   float* terms;               // [B*N,5] dist, skate, floor, pene, face
   int* colliding;             // [B*N]
+  GeoFieldDev field;          // field.dist null: the goal term is the Euclidean distance
 };
 
 __device__ __forceinline__ float wave_sum(float v) {   // lane 0 holds the sum; fixed tree
@@ -321,6 +326,30 @@ __device__ __forceinline__ void score_group(const SelectArgs& p, int g, int M, f
   }
 }
 
+// The goal term of a launch with a field.  score_group scores every row with the Euclidean distance, exactly as in a launch without
+// a field; this then replaces, per row, terms[0] by the field of group g at the world xy of the row's last pelvis (R0 j19 + T0)
+// and the cost by the sum with that term, every rounding stated (four rounded products added in order, the facing term as one
+// fused multiply-add; the other terms are read back from `terms`), and returns the cost.  It is a phase of its own after
+// score_group's closing barrier, one row per thread, and not a branch inside the scoring: any code added to the block that
+// computes the distance, the facing term and the cost changes how the compiler vectorises and contracts THAT arithmetic (measured:
+// last-bit changes of dist, face and cost against the build before the field came, with the field term inlined, out of line, and
+// in a block of its own behind the scoring).
+__device__ __forceinline__ float field_row_cost(const SelectArgs& p, int g, size_t row) {
+  const float* R0 = p.R0 + row * 9;
+  const float* T0 = p.T0 + row * 3;
+  const float* j19 = p.joints + (row * NT + 19) * p.jpb * 3;
+  const float x = fmaf(R0[2], j19[2], fmaf(R0[1], j19[1], R0[0] * j19[0])) + T0[0];
+  const float y = fmaf(R0[5], j19[2], fmaf(R0[4], j19[1], R0[3] * j19[0])) + T0[1];
+  const float geo = egx_geodesic_sample_group(p.field, g, x, y);
+  float* tm = p.terms + row * 5;
+  const float sum4 = egx_add(egx_add(egx_add(egx_mul(p.w_goal, geo), egx_mul(p.w_skate, tm[1])), egx_mul(p.w_floor, tm[2])),
+                             egx_mul(p.w_pene, tm[3]));
+  const float cost = fmaf(p.w_face, tm[4], sum4);      // NaN for a NaN position: the row then ranks as non-finite
+  tm[0] = geo;
+  p.cost[row] = cost;
+  return cost;
+}
+
 }  // namespace
 
 __global__ __launch_bounds__(SEL_BLK) void egx_primitive_select_kernel(SelectArgs p) {
@@ -333,6 +362,15 @@ __global__ __launch_bounds__(SEL_BLK) void egx_primitive_select_kernel(SelectArg
     s_dist[n] = r.dist;
     s_cls[n] = (r.finite ? 0 : 2) | (r.collides ? 1 : 0);
   });
+  if (p.field.dist) {                          // workgroup-uniform; score_group ended on a barrier: the rows' terms are visible
+    for (int n = tid; n < N; n += SEL_BLK) {
+      const float c = field_row_cost(p, g, (size_t)g * N + n);
+      const bool finite = !(s_cls[n] & 2) && isfinite(c);
+      s_cost[n] = finite ? c : 0.f;
+      s_cls[n] = (finite ? 0 : 2) | (s_cls[n] & 1);
+    }
+    __syncthreads();
+  }
 
   if (w == 0) {
     int bc = 4, bi = 0x7fffffff;
@@ -374,6 +412,19 @@ __global__ __launch_bounds__(SEL_BLK) void egx_primitive_beam_select_kernel(Sele
     s_key[n] = finite ? min(max(nc, 0), NONFINITE_KEY - 1) : NONFINITE_KEY + min(max(nc, 0), NONFINITE_KEY - 1);
     s_flag[n] = (r.collides ? 1 : 0) | (finite ? 0 : 2);
   });
+  if (p.field.dist) {                          // as in the greedy kernel; the path key of every row again with the field's cost
+    for (int n = tid; n < M; n += SEL_BLK) {
+      const float c = field_row_cost(p, g, (size_t)g * M + n);
+      const bool row_finite = !(s_flag[n] & 2) && isfinite(c);
+      const float path = q.acc[(size_t)g * W + n / N] + (row_finite ? c : 0.f);
+      const bool finite = row_finite && isfinite(path);
+      const int nc = s_key[n] & (NONFINITE_KEY - 1);
+      s_path[n] = finite ? path : 0.f;
+      s_key[n] = finite ? nc : NONFINITE_KEY + nc;
+      s_flag[n] = (s_flag[n] & 1) | (finite ? 0 : 2);
+    }
+    __syncthreads();
+  }
 
   if (tid < M) {
     const int kc = s_key[tid];
@@ -485,11 +536,17 @@ template <class Launch>
 int select_entry(const float* Y_gen, const float* x0, const float* x1, int x_ld, const float* joints, int joints_per_body,
                  const float* markers_proj, const float* R0, const float* T0, const int32_t* pene_count, const float* goal,
                  const int32_t* feet_marker_idx, const float* weights, float pene_thres, float goal_thresh, float reproj_factor,
-                 int num_sequences, int group_rows, float* cost, float* cost_terms, int32_t* colliding, Launch launch) {
+                 int num_sequences, int group_rows, float* cost, float* cost_terms, int32_t* colliding, const GeoFieldDev& field,
+                 Launch launch) {
   EGX_REQUIRE(Y_gen && x0 && x1 && joints && markers_proj && R0 && T0 && goal && feet_marker_idx && weights, "null input");
   EGX_REQUIRE(cost && cost_terms && colliding, "null output");
   EGX_REQUIRE(num_sequences > 0 && joints_per_body >= 3, "need a non-empty batch and >= 3 joints per body");
   EGX_REQUIRE(x_ld >= MD, "a seed frame holds 201 floats: the row stride cannot be smaller");
+  if (field.dist) {
+    EGX_REQUIRE(field.origin && field.H >= 1 && field.W >= 1 && field.F >= 1, "a field needs its origin, size and count");
+    EGX_REQUIRE(field.cell > 0.f && field.cell < __builtin_inff(), "field_cell must be positive and finite");
+    EGX_REQUIRE((long long)field.F * field.H * field.W <= 0x7fffffffLL, "the fields must stay below 2^31 cells");
+  }
   SelectArgs p{};
   p.Y_gen = Y_gen; p.x0 = x0; p.x1 = x1; p.joints = joints; p.markers_proj = markers_proj; p.R0 = R0; p.T0 = T0;
   p.pene_count = pene_count; p.goal = goal; p.feet_marker_idx = feet_marker_idx;
@@ -497,6 +554,7 @@ int select_entry(const float* Y_gen, const float* x0, const float* x1, int x_ld,
   p.pene_thres = pene_thres; p.goal_thresh = goal_thresh; p.rf = reproj_factor;
   p.rows = num_sequences * group_rows; p.N = group_rows; p.jpb = joints_per_body; p.x_ld = x_ld;
   p.cost = cost; p.terms = cost_terms; p.colliding = colliding;
+  if (field.dist) p.field = field;
   launch(p);
   EGX_HIP_CHECK(hipGetLastError());
   return EGX_OK;
@@ -516,20 +574,33 @@ extern "C" int egx_primitive_advance(const float* pred_params, const float* Y_ge
   });
 }
 
+extern "C" int egx_primitive_select_field(const float* Y_gen, const float* x0, const float* x1, int x_ld, const float* joints,
+                                          int joints_per_body, const float* markers_proj, const float* R0, const float* T0,
+                                          const int32_t* pene_count, const float* goal, const int32_t* feet_marker_idx,
+                                          const float* weights, float pene_thres, float goal_thresh, float reproj_factor,
+                                          int num_sequences, int num_candidates, int32_t* choice, int32_t* status, int32_t* reached,
+                                          float* goal_dist, float* cost, float* cost_terms, int32_t* colliding, const float* field_dist,
+                                          const float* field_origin, float field_cell, int field_H, int field_W, int num_fields,
+                                          const int32_t* field_index, void* stream) {
+  EGX_REQUIRE(choice && status && reached && goal_dist, "null output");
+  EGX_REQUIRE(num_candidates >= 1 && num_candidates <= MAXC, "num_candidates must be in [1, EGX_MAX_CANDIDATES]");
+  return select_entry(Y_gen, x0, x1, x_ld, joints, joints_per_body, markers_proj, R0, T0, pene_count, goal, feet_marker_idx, weights,
+                      pene_thres, goal_thresh, reproj_factor, num_sequences, num_candidates, cost, cost_terms, colliding,
+                      GeoFieldDev{field_dist, field_origin, field_index, field_cell, field_H, field_W, num_fields}, [&](SelectArgs& p) {
+    p.choice = choice; p.status = status; p.reached = reached; p.goal_dist = goal_dist;
+    hipLaunchKernelGGL(egx_primitive_select_kernel, dim3(num_sequences), dim3(SEL_BLK), 0, static_cast<hipStream_t>(stream), p);
+  });
+}
+
 extern "C" int egx_primitive_select(const float* Y_gen, const float* x0, const float* x1, int x_ld, const float* joints,
                                     int joints_per_body, const float* markers_proj, const float* R0, const float* T0,
                                     const int32_t* pene_count, const float* goal, const int32_t* feet_marker_idx,
                                     const float* weights, float pene_thres, float goal_thresh, float reproj_factor,
                                     int num_sequences, int num_candidates, int32_t* choice, int32_t* status, int32_t* reached,
                                     float* goal_dist, float* cost, float* cost_terms, int32_t* colliding, void* stream) {
-  EGX_REQUIRE(choice && status && reached && goal_dist, "null output");
-  EGX_REQUIRE(num_candidates >= 1 && num_candidates <= MAXC, "num_candidates must be in [1, EGX_MAX_CANDIDATES]");
-  return select_entry(Y_gen, x0, x1, x_ld, joints, joints_per_body, markers_proj, R0, T0, pene_count, goal, feet_marker_idx, weights,
-                      pene_thres, goal_thresh, reproj_factor, num_sequences, num_candidates, cost, cost_terms, colliding,
-                      [&](SelectArgs& p) {
-    p.choice = choice; p.status = status; p.reached = reached; p.goal_dist = goal_dist;
-    hipLaunchKernelGGL(egx_primitive_select_kernel, dim3(num_sequences), dim3(SEL_BLK), 0, static_cast<hipStream_t>(stream), p);
-  });
+  return egx_primitive_select_field(Y_gen, x0, x1, x_ld, joints, joints_per_body, markers_proj, R0, T0, pene_count, goal, feet_marker_idx,
+                                    weights, pene_thres, goal_thresh, reproj_factor, num_sequences, num_candidates, choice, status, reached,
+                                    goal_dist, cost, cost_terms, colliding, nullptr, nullptr, 0.f, 0, 0, 0, nullptr, stream);
 }
 
 extern "C" int egx_primitive_advance_select(const float* pred_params, const float* Y_gen, const float* x0, const float* x1, int x_ld,
@@ -548,14 +619,16 @@ extern "C" int egx_primitive_advance_select(const float* pred_params, const floa
   });
 }
 
-extern "C" int egx_primitive_beam_select(const float* Y_gen, const float* x0, const float* x1, int x_ld, const float* joints,
-                                         int joints_per_body, const float* markers_proj, const float* R0, const float* T0,
-                                         const int32_t* pene_count, const float* goal, const int32_t* feet_marker_idx,
-                                         const float* weights, float pene_thres, float goal_thresh, float reproj_factor,
-                                         int num_sequences, int beam_width, int num_candidates, const float* acc,
-                                         const int32_t* ncoll, float* cost, float* cost_terms, int32_t* colliding, int32_t* beam_row,
-                                         int32_t* parent, float* acc_out, int32_t* ncoll_out, float* path_cost, int32_t* beam_status,
-                                         float* goal_dist, int32_t* reached, void* stream) {
+extern "C" int egx_primitive_beam_select_field(const float* Y_gen, const float* x0, const float* x1, int x_ld, const float* joints,
+                                               int joints_per_body, const float* markers_proj, const float* R0, const float* T0,
+                                               const int32_t* pene_count, const float* goal, const int32_t* feet_marker_idx,
+                                               const float* weights, float pene_thres, float goal_thresh, float reproj_factor,
+                                               int num_sequences, int beam_width, int num_candidates, const float* acc,
+                                               const int32_t* ncoll, float* cost, float* cost_terms, int32_t* colliding,
+                                               int32_t* beam_row, int32_t* parent, float* acc_out, int32_t* ncoll_out, float* path_cost,
+                                               int32_t* beam_status, float* goal_dist, int32_t* reached, const float* field_dist,
+                                               const float* field_origin, float field_cell, int field_H, int field_W, int num_fields,
+                                               const int32_t* field_index, void* stream) {
   EGX_REQUIRE(acc && ncoll, "null input");
   EGX_REQUIRE(beam_row && parent && acc_out && ncoll_out && path_cost && beam_status && goal_dist && reached, "null output");
   EGX_REQUIRE(beam_width >= 1 && beam_width <= EGX_MAX_BEAM, "beam_width must be in [1, EGX_MAX_BEAM]");
@@ -564,10 +637,24 @@ extern "C" int egx_primitive_beam_select(const float* Y_gen, const float* x0, co
   EGX_REQUIRE(acc != acc_out && ncoll != ncoll_out, "acc / ncoll are read from one buffer and written to another");
   return select_entry(Y_gen, x0, x1, x_ld, joints, joints_per_body, markers_proj, R0, T0, pene_count, goal, feet_marker_idx, weights,
                       pene_thres, goal_thresh, reproj_factor, num_sequences, beam_width * num_candidates, cost, cost_terms, colliding,
-                      [&](SelectArgs& p) {
+                      GeoFieldDev{field_dist, field_origin, field_index, field_cell, field_H, field_W, num_fields}, [&](SelectArgs& p) {
     const BeamArgs q{acc, ncoll, beam_row, parent, acc_out, ncoll_out, path_cost, beam_status, goal_dist, reached, beam_width, num_candidates};
     hipLaunchKernelGGL(egx_primitive_beam_select_kernel, dim3(num_sequences), dim3(SEL_BLK), 0, static_cast<hipStream_t>(stream), p, q);
   });
+}
+
+extern "C" int egx_primitive_beam_select(const float* Y_gen, const float* x0, const float* x1, int x_ld, const float* joints,
+                                         int joints_per_body, const float* markers_proj, const float* R0, const float* T0,
+                                         const int32_t* pene_count, const float* goal, const int32_t* feet_marker_idx,
+                                         const float* weights, float pene_thres, float goal_thresh, float reproj_factor,
+                                         int num_sequences, int beam_width, int num_candidates, const float* acc,
+                                         const int32_t* ncoll, float* cost, float* cost_terms, int32_t* colliding, int32_t* beam_row,
+                                         int32_t* parent, float* acc_out, int32_t* ncoll_out, float* path_cost, int32_t* beam_status,
+                                         float* goal_dist, int32_t* reached, void* stream) {
+  return egx_primitive_beam_select_field(Y_gen, x0, x1, x_ld, joints, joints_per_body, markers_proj, R0, T0, pene_count, goal,
+                                         feet_marker_idx, weights, pene_thres, goal_thresh, reproj_factor, num_sequences, beam_width,
+                                         num_candidates, acc, ncoll, cost, cost_terms, colliding, beam_row, parent, acc_out, ncoll_out,
+                                         path_cost, beam_status, goal_dist, reached, nullptr, nullptr, 0.f, 0, 0, 0, nullptr, stream);
 }
 
 extern "C" int egx_primitive_advance_beam(const float* pred_params, const float* Y_gen, const float* x0, const float* x1, int x_ld,

@@ -7,7 +7,9 @@ motion-only part of `CrowdEnv.step` (crowd_ppo/crowd_env_2f.py:109-155, 238-265)
 arguments of the env's reward terms (:171-235) against a goal and an SDF scene, and every candidate of the next primitive
 continues from the best one (kernels egx_primitive_select, egx_primitive_advance_select); with `beam_width` W > 1 it is a beam
 search that keeps the best W partial paths per sequence (kernels egx_primitive_beam_select, egx_primitive_advance_beam,
-egx_beam_backtrack).
+egx_beam_backtrack).  With `geodesic=` (a `GeodesicField`, egogen_amd/geodesic.py) the goal term of either search is the distance
+along the walkable raster of the scene instead of the straight line (entries egx_primitive_select_field,
+egx_primitive_beam_select_field).
 
 The three chains share their host path: `_chain_state` builds the state dict (checked inputs, defaults, the loop's buffers, the
 records) for b seeds of M rows each, `_primitive` launches what every primitive begins with (prior, parameter assembly, body
@@ -71,12 +73,14 @@ class PrimitiveSequence:
     A result of `generate_sequence_to_goal` holds the chosen candidates in those fields and, in `search`, what the selection saw:
     goal [b,3], choice [K,b], cost [K,b,N], cost_terms [K,b,N,5] (dist, skate, floor, pene, face), colliding [K,b,N],
     status [K,b] (bit 0: the chosen candidate collides), goal_dist [K,b], n_valid [b] (primitives up to and including the first
-    whose chosen candidate ends within goal_thresh of the goal, K if none does); `primitives` and `save` stop at n_valid.
+    whose chosen candidate ends within goal_thresh of the goal, K if none does); `primitives` and `save` stop at n_valid;
+    geo_dist [K,b], with a `geodesic=` field the field's value at the chosen candidate's last pelvis (cost_terms[..., 0] of the
+    chosen row, which then holds the field's value, not the Euclidean distance), else None.
     A beam result (beam_width W > 1) holds the returned path in the same fields: cost / cost_terms / colliding are [K,b,W*N(,5)],
     choice [K,b] the path's row within its W*N, status [K,b] the path node's bits (0: collides, 1: non-finite row, 2: non-finite
     hand-off); and beam_width, path_slot [K,b], parent / beam_row / path_cost / beam_status [K,b,W], which a greedy result has as
     None."""
-    SEARCH_FIELDS = ("goal", "choice", "cost", "cost_terms", "colliding", "status", "goal_dist", "n_valid")
+    SEARCH_FIELDS = ("goal", "choice", "cost", "cost_terms", "colliding", "status", "goal_dist", "n_valid", "geo_dist")
     BEAM_FIELDS = ("beam_width", "path_slot", "parent", "beam_row", "path_cost", "beam_status")
 
     def __init__(self, markers, params, rotmat, transl, pelvis, z, betas, gender, R0, T0, search: Optional[dict] = None):
@@ -343,7 +347,7 @@ class GAMMAPrimitiveComboGenOP:
     def generate_sequence_to_goal(self, data, bparams, betas, goal, n_primitives: int, n_candidates: int, scene=None,
                                   agent_scene=None, weights: Optional[dict] = None, pene_thres: float = 40, goal_thresh=None,
                                   z=None, reproj_factor=None, to_numpy: bool = True, R0=None, T0=None,
-                                  beam_width: int = 1) -> PrimitiveSequence:
+                                  beam_width: int = 1, geodesic=None) -> PrimitiveSequence:
         """`generate_sequence` steered to a goal through a scene by a greedy best-of-N search: for each of the `n_primitives`
         primitives, `n_candidates` candidates per sequence are generated, scored and the best one is kept; every candidate of the
         next primitive continues from it.  data / bparams / betas / reproj_factor / R0 / T0 as in `generate_sequence` (b seeds,
@@ -368,6 +372,11 @@ class GAMMAPrimitiveComboGenOP:
               accumulated cost is the row's cost plus the skate, floor, pene and face terms of its ancestors: the goal distance at
               the path's end plus the motion quality along it.  Per primitive: ... -> egx_primitive_beam_select ->
               egx_primitive_advance_beam; after the loop egx_beam_backtrack gathers the path that ends in the best slot.
+            - geodesic: None, or a `GeodesicField` (egogen_amd/geodesic.py) of 1 or b fields whose goals' xy equal `goal`'s
+              (ValueError otherwise).  The goal term of the cost, greedy or beam, is then the field's distance along the walkable
+              raster at the world xy of the candidate's last pelvis instead of the straight line, so the search goes round an
+              obstacle instead of at it; goal_dist, the reached test and n_valid stay Euclidean.  The field is built before the
+              loop (that build waits for the device); the loop stays launches only.
         Raises FloatingPointError when a chosen hand-off, or every candidate of a sequence, held a non-finite value (read once,
         after the loop); for a beam, when a node of the returned path did."""
         from .body_model import SdfScene, SdfSceneSet
@@ -392,6 +401,18 @@ class GAMMAPrimitiveComboGenOP:
         if goal.shape != (b, 3):
             raise ValueError(f"goal must be [3] or [{b},3], got {tuple(goal.shape)}")
         goal = goal.contiguous()
+        field_args = field_alive = None
+        if geodesic is not None:
+            from .geodesic import GeodesicField
+            if not isinstance(geodesic, GeodesicField):
+                raise TypeError(f"geodesic must be None or a GeodesicField, got {type(geodesic).__name__}")
+            if len(geodesic) not in (1, b):
+                raise ValueError(f"geodesic must hold 1 or {b} fields, got {len(geodesic)}")
+            if geodesic.dist.device != dev:
+                raise ValueError(f"geodesic lives on {geodesic.dist.device}, the operator on {dev}")
+            if not torch.equal(geodesic.goals[:, :2].to(dev).expand(b, 2), goal[:, :2]):
+                raise ValueError("the fields of `geodesic` were built for other goals than `goal` (their xy must be equal)")
+            field_args, field_alive = geodesic.select_args(b)
         rows_scene = None
         if isinstance(scene, SdfSceneSet):
             if agent_scene is None:
@@ -417,7 +438,7 @@ class GAMMAPrimitiveComboGenOP:
         s.update({"goal": goal, "scene": scene, "rows_scene": rows_scene, "pp": torch.empty(b * M, T_ALL, XB, device=dev, dtype=f32),
                   "feet": torch.tensor(synth.feet_marker_idx(), device=dev, dtype=i32),
                   "weights": (C.c_float * 5)(*[w[k] for k in ("goal", "skate", "floor", "pene", "face")]),
-                  "pene_thres": float(pene_thres), "goal_thresh": float(goal_thresh),
+                  "pene_thres": float(pene_thres), "goal_thresh": float(goal_thresh), "field": field_args, "field_alive": field_alive,
                   "choice": rec(dtype=i32), "status": rec(dtype=i32), "reached": rec(dtype=i32), "goal_dist": rec(),
                   "cost": rec(M), "cost_terms": rec(M, 5), "colliding": rec(M, dtype=i32)})
         if scene is not None:
@@ -447,7 +468,9 @@ class GAMMAPrimitiveComboGenOP:
         first = torch.where(reached.any(0), reached.int().argmax(0) + 1, torch.full((b,), K, device=dev, dtype=torch.int64))
         zc = s["z"].view(K, b, M, zd).gather(2, s["choice"].long().view(K, b, 1, 1).expand(K, b, 1, zd))[:, :, 0]
         search = {"goal": goal, "choice": s["choice"], "cost": s["cost"], "cost_terms": s["cost_terms"], "colliding": s["colliding"],
-                  "status": status, "goal_dist": s["goal_dist"], "n_valid": first}
+                  "status": status, "goal_dist": s["goal_dist"], "n_valid": first, "geo_dist": None}
+        if geodesic is not None:
+            search["geo_dist"] = s["cost_terms"][..., 0].gather(2, s["choice"].long().clamp(0, M - 1).unsqueeze(-1))[..., 0]
         if W > 1:
             search.update({k: s[k] for k in ("path_slot", "parent", "beam_row", "path_cost", "beam_status")}, beam_width=W)
         return self._result(s, zc, bt, R0_end[::M].reshape(b, 3, 3).contiguous(), T0_end[::M].contiguous(), to_numpy, search)
@@ -456,12 +479,15 @@ class GAMMAPrimitiveComboGenOP:
         """The primitive loop of `generate_sequence_to_goal`: launches only, no allocation that depends on k, no host wait."""
         lib, st, hand, pp = _lib.load(), _lib.current_stream_ptr(), self._handoff_lead(s), _lib.ptr(s["pp"])
         sel = self._select_lead(s, [s["R0"]] * 2, [s["T0"]] * 2)
+        field = s["field"] or ()                                    # with a field: the *_field entry, the field before the stream
+        name = "egx_primitive_select_field" if field else "egx_primitive_select"
+        select = getattr(lib, name)
         for k in range(K):
             nxt = s["xs"][(k + 1) % 2]
             self._primitive(s, k, s["pp"], st, s["R0"], s["T0"])
-            _lib.check(lib.egx_primitive_select(
+            _lib.check(select(
                 *sel[k % 2], b, N, _vp(s["choice"][k]), _vp(s["status"][k]), _vp(s["reached"][k]),
-                _vp(s["goal_dist"][k]), _vp(s["cost"][k]), _vp(s["cost_terms"][k]), _vp(s["colliding"][k]), st), "egx_primitive_select")
+                _vp(s["goal_dist"][k]), _vp(s["cost"][k]), _vp(s["cost_terms"][k]), _vp(s["colliding"][k]), *field, st), name)
             _lib.check(lib.egx_primitive_advance_select(
                 pp, *hand[k % 2], b, _vp(s["choice"][k]), N, _lib.ptr(s["R0"]), _lib.ptr(s["T0"]), _vp(s["markers"][k]),
                 _vp(s["pelvis"][k]), _vp(s["rotmat"][k]), _vp(s["transl"][k]), _vp(s["params"][k]), _lib.ptr(s["seed"]), _vp(nxt[0]),
@@ -473,15 +499,18 @@ class GAMMAPrimitiveComboGenOP:
         of another slot of its sequence."""
         lib, st, hand, pp = _lib.load(), _lib.current_stream_ptr(), self._handoff_lead(s), _lib.ptr(s["pp"])
         sel = self._select_lead(s, s["R0s"], s["T0s"])
+        field = s["field"] or ()
+        name = "egx_primitive_beam_select_field" if field else "egx_primitive_beam_select"
+        select = getattr(lib, name)
         for k in range(K):
             nxt = s["xs"][(k + 1) % 2]
             R0, T0, R0n, T0n = s["R0s"][k % 2], s["T0s"][k % 2], s["R0s"][(k + 1) % 2], s["T0s"][(k + 1) % 2]
             self._primitive(s, k, s["pp"], st, R0, T0)
-            _lib.check(lib.egx_primitive_beam_select(
+            _lib.check(select(
                 *sel[k % 2], b, W, N, _vp(s["acc"][k]), _vp(s["ncoll"][k]), _vp(s["cost"][k]), _vp(s["cost_terms"][k]),
                 _vp(s["colliding"][k]), _vp(s["beam_row"][k]), _vp(s["parent"][k]), _vp(s["acc"][k + 1]), _vp(s["ncoll"][k + 1]),
-                _vp(s["path_cost"][k]), _vp(s["beam_status"][k]), _vp(s["slot_goal_dist"][k]), _vp(s["slot_reached"][k]), st),
-                "egx_primitive_beam_select")
+                _vp(s["path_cost"][k]), _vp(s["beam_status"][k]), _vp(s["slot_goal_dist"][k]), _vp(s["slot_reached"][k]), *field, st),
+                name)
             _lib.check(lib.egx_primitive_advance_beam(
                 pp, *hand[k % 2], b, W, N, _vp(s["beam_row"][k]), _lib.ptr(R0), _lib.ptr(T0), _lib.ptr(R0n), _lib.ptr(T0n),
                 _vp(s["rec_markers"][k]), _vp(s["rec_pelvis"][k]), _vp(s["rec_rotmat"][k]), _vp(s["rec_transl"][k]), _vp(s["rec_params"][k]),

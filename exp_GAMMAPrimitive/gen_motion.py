@@ -8,7 +8,10 @@ With `--goal x,y,z` (world coordinates) the variants are steered there by `gener
 per primitive and variant, the best one kept (greedy best-of-N on the env's reward arguments), optionally through the SDF scene
 `--scene file.npz` (keys sdf, center, scale: the reference's sdf_dict); a file stops at the primitive that reaches the goal.
 `--beam-width W` (default 1: greedy) keeps the best W partial paths per variant instead of one, each expanded into N candidates
-(W <= 32, W * N <= 256), and writes the path that ends in the best one.
+(W <= 32, W * N <= 256), and writes the path that ends in the best one.  `--walkable file.npz` (a scene file of
+`scene_gen.save_scene` that carries its walkable raster; independent of `--scene`) makes the goal term the distance along that
+raster (`GeodesicField`), so the variants go round an obstacle instead of at it; the driver then prints that distance next to the
+straight-line one.
 
 `--cfg <name>` is the combo config (`crowd_ppo/cfg_samp20/<name>.yml` under the working directory, else the packaged copy): it
 names the predictor's and the regressor's configs, whose checkpoints are read from `results/crowd_ppo/<config>/checkpoints`
@@ -48,15 +51,31 @@ def main(argv=None):
     parser.add_argument("--n-candidates", type=int, default=16, help="candidates per primitive and variant (with --goal)")
     parser.add_argument("--beam-width", type=int, default=1, help="partial paths kept per variant (with --goal); 1 = greedy best-of-N")
     parser.add_argument("--scene", default=None, help="npz with sdf, center, scale: penalise and avoid penetration (with --goal)")
+    parser.add_argument("--walkable", default=None, help="scene file of scene_gen.save_scene with its walkable raster: the goal term "
+                        "becomes the distance along the raster, round obstacles (with --goal; independent of --scene)")
     args = parser.parse_args(argv)
     if args.goal is None and args.scene is not None:
         parser.error("--scene needs --goal")
+    if args.goal is None and args.walkable is not None:
+        parser.error("--walkable needs --goal")
     if args.goal is None and args.beam_width != 1:
         parser.error("--beam-width needs --goal")
     if not torch.cuda.is_available():
         raise SystemExit("gen_motion needs a HIP device: the MI355X path has no CPU fallback")
     np.random.seed(args.seed)
     torch.manual_seed(args.seed)
+    goal = field = None
+    if args.goal is not None:
+        goal = np.asarray([float(v) for v in args.goal.split(",")], np.float32)
+        if goal.shape != (3,):
+            raise SystemExit("--goal takes x,y,z")
+    if args.walkable:        # before the models: a file without a raster, or a goal off it, ends the run here
+        from egogen_amd.geodesic import GeodesicField
+        try:
+            field = GeodesicField.from_scene(sw.load_scene_file(args.walkable, raster=True), goal[None])
+        except ValueError as e:
+            raise SystemExit("--walkable {}: {}".format(args.walkable, e))
+        print("[INFO] geodesic field: {} x {} cells of {} m, {} passes".format(field.dist.shape[1], field.dist.shape[2], field.cell, field.passes))
 
     mc = sw._read_yaml(args.cfg + ".yml")["modelconfig"]
     pdir = os.path.join(sw.RESULTS_ROOT, mc["predictor_config"], "checkpoints")
@@ -93,19 +112,18 @@ def main(argv=None):
         res = op.generate_sequence(data, bparams, can["betas"].astype(np.float32), args.n_primitives, n_gens=args.n_gens, R0=R0, T0=T0)
     else:
         from egogen_amd.body_model import SdfScene
-        goal = np.asarray([float(v) for v in args.goal.split(",")], np.float32)
-        if goal.shape != (3,):
-            raise SystemExit("--goal takes x,y,z")
         scene = None
         if args.scene:
             with np.load(args.scene) as f:
                 scene = SdfScene({k: f[k] for k in ("sdf", "center", "scale")})
         res = op.generate_sequence_to_goal(data.repeat(args.n_gens, 1), bparams.repeat(args.n_gens, 1), can["betas"].astype(np.float32),
                                            goal, args.n_primitives, args.n_candidates, scene=scene, R0=R0, T0=T0,
-                                           beam_width=args.beam_width)
+                                           beam_width=args.beam_width, geodesic=field)
         for i in range(args.n_gens):
-            print("[INFO] variant {}: {} primitives, final distance to the goal {:.3f} m, colliding choices {}".format(
-                i, int(res.n_valid[i]), float(res.goal_dist[int(res.n_valid[i]) - 1, i]), int((res.status[:int(res.n_valid[i]), i] & 1).sum())))
+            last = int(res.n_valid[i]) - 1
+            along = "" if field is None else " ({:.3f} m along the walkable raster)".format(float(res.geo_dist[last, i]))
+            print("[INFO] variant {}: {} primitives, final distance to the goal {:.3f} m{}, colliding choices {}".format(
+                i, last + 1, float(res.goal_dist[last, i]), along, int((res.status[:last + 1, i] & 1).sum())))
     paths = [res.save(args.out, i, man_id="{}_{}".format(args.seed, i)) for i in range(args.n_gens)]
     for p in paths:
         print(p)

@@ -28,12 +28,15 @@ extern "C" {
 #define EGX_ERR_ARG (-1)
 #define EGX_ERR_HIP (-2)
 #define EGX_ERR_WORKSPACE (-3)
+#define EGX_ERR_CONVERGENCE (-4) /* egx_geodesic_field: the pass cap was reached while the field still changed */
 
 #define EGX_NUM_JOINTS 55      /* SMPL-X kinematic joints                */
 #define EGX_NUM_JOINTS_OUT 127 /* 55 + 21 vertex joints + 51 landmarks   */
 #define EGX_XB_DIM 93          /* transl3 glorot3 body63 lhand12 rhand12 */
 #define EGX_MAX_CANDIDATES 256 /* candidates per sequence of egx_primitive_select */
 #define EGX_MAX_BEAM 32        /* beam slots per sequence of egx_primitive_beam_select; slots * candidates <= EGX_MAX_CANDIDATES */
+#define EGX_GEODESIC_OFF 1.0e4f /* metres: what a geodesic field gives where none of the four surrounding cells holds a distance */
+#define EGX_GEODESIC_BATCH 8    /* passes egx_geodesic_field launches between two reads of its flag */
 #define EGX_NUM_BETAS 10
 #define EGX_POSE_FEAT 486
 #define EGX_BLEND_K 472        /* GEMM K: 10 betas + 9 x 51 movable joints = 469, padded to 8 (jaw/eyes are always identity here) */
@@ -886,6 +889,55 @@ int egx_beam_backtrack(const int32_t* parent, const int32_t* beam_row, const int
                        const float* rec_T, const float* rec_params, int num_primitives, int num_sequences, int beam_width,
                        int32_t* path_slot, int32_t* choice, int32_t* status, float* out_goal_dist, int32_t* out_reached,
                        float* out_marker_b, float* out_pelvis, float* out_R, float* out_T, float* out_params, void* stream);
+
+/* Geodesic distance to a goal on the walkable raster (free [nx,ny] = [H,W], origin[2], cell: scene_gen.walkable_grid, the scene
+ * files of scene_gen.save_scene), and the selection entries that read it as their goal term.
+ *
+ * egx_geodesic_field - num_fields distance fields dist [F,H,W] (metres) over the masks free_mask [num_scenes,H,W] (uint8, non-zero =
+ * free); field f lies on mask field_scene[f] (NULL: mask 0, needs num_scenes == 1).  Graph: the free cells, 8 neighbours, a diagonal
+ * step (di,dj) from (i,j) only where (i+di,j) and (i,j+dj) are free too; weights w1 (axis) and w2 (diagonal).  Seeds: seed_cell [n]
+ * (flat f*H*W + i*W + j) with seed_value [n] (>= 0, finite); a seed outside the buffer or on a blocked cell is ignored, of two on
+ * one cell the smaller holds.  Result: dist[c] = min(seed value of c, min over allowed neighbours n of dist[n] + w), one float32
+ * addition per edge: float32 Dijkstra, the same bits in any order of relaxation (rounding is monotone); blocked and unreachable
+ * cells hold +inf.  One launch is one pass of pull-form relaxation over 32 x 32 tiles held in LDS with a one-cell halo, iterated
+ * inside the tile until it stops changing; passes read one of dist / tmp and write the other; no float atomics, no waiting
+ * between workgroups.  The host launches EGX_GEODESIC_BATCH passes, then reads the flag of the last one: this entry SYNCHRONISES
+ * the stream (scene set-up, not the primitive loop).  It stops at the first batch whose last pass changed nothing; after H*W + 1
+ * passes (more than a shortest path has cells) it returns EGX_ERR_CONVERGENCE.  tmp [F,H,W] and flags [EGX_GEODESIC_BATCH] are
+ * device workspace; *passes_host (HOST, may be NULL) receives the number of passes launched.  F*H*W < 2^31. */
+int egx_geodesic_field(const uint8_t* free_mask, const int32_t* field_scene, int num_scenes, int num_fields, int H, int W, float w1,
+                       float w2, const int32_t* seed_cell, const float* seed_value, int num_seeds, float* dist, float* tmp,
+                       int32_t* flags, int32_t* passes_host, void* stream);
+
+/* egx_geodesic_sample - fields dist [F,H,W] with origin [F,2] at points [F,n,2] (world xy) -> out [F,n].  u = (x - origin_x) / cell
+ * - 0.5, v likewise: bilinear over the four surrounding cell centres, of which those outside the raster, holding +inf or of
+ * weight 0 drop out and the rest are renormalised; EGX_GEODESIC_OFF where none is left; NaN for a NaN coordinate.  Every
+ * operation rounds on its own (the device function of csrc/egx_geodesic.h, which the selection kernels call too). */
+int egx_geodesic_sample(const float* dist, const float* origin, float cell, int num_fields, int H, int W, const float* points,
+                        int num_points, float* out, void* stream);
+
+/* egx_primitive_select_field / egx_primitive_beam_select_field - egx_primitive_select / egx_primitive_beam_select (the same
+ * kernels, the same leading arguments) with the goal term read from a geodesic field: field_dist [num_fields,H,W], field_origin
+ * [num_fields,2], field_cell, and field_index [num_sequences] (clamped into [0, num_fields); NULL: every sequence reads field 0).
+ * The goal term of cost, and cost_terms[...,0], is then the field sampled (egx_geodesic_sample's function) at the world xy of the
+ * last pelvis, R0 joint 0 of body 19 + T0; goal_dist and reached stay the Euclidean distance.  field_dist NULL: the entry
+ * without a field, the same bits. */
+int egx_primitive_select_field(const float* Y_gen, const float* x0, const float* x1, int x_ld, const float* joints,
+                               int joints_per_body, const float* markers_proj, const float* R0, const float* T0,
+                               const int32_t* pene_count, const float* goal, const int32_t* feet_marker_idx, const float* weights,
+                               float pene_thres, float goal_thresh, float reproj_factor, int num_sequences, int num_candidates,
+                               int32_t* choice, int32_t* status, int32_t* reached, float* goal_dist, float* cost, float* cost_terms,
+                               int32_t* colliding, const float* field_dist, const float* field_origin, float field_cell, int field_H,
+                               int field_W, int num_fields, const int32_t* field_index, void* stream);
+int egx_primitive_beam_select_field(const float* Y_gen, const float* x0, const float* x1, int x_ld, const float* joints,
+                                    int joints_per_body, const float* markers_proj, const float* R0, const float* T0,
+                                    const int32_t* pene_count, const float* goal, const int32_t* feet_marker_idx,
+                                    const float* weights, float pene_thres, float goal_thresh, float reproj_factor,
+                                    int num_sequences, int beam_width, int num_candidates, const float* acc, const int32_t* ncoll,
+                                    float* cost, float* cost_terms, int32_t* colliding, int32_t* beam_row, int32_t* parent,
+                                    float* acc_out, int32_t* ncoll_out, float* path_cost, int32_t* beam_status, float* goal_dist,
+                                    int32_t* reached, const float* field_dist, const float* field_origin, float field_cell,
+                                    int field_H, int field_W, int num_fields, const int32_t* field_index, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * PPO rollout glue
