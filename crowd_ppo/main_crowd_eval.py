@@ -121,11 +121,7 @@ def main(args, num_scenes=1, num_agents=4, out_dir="log/eval_results/crowd-4huma
                     hist[k] = hist[k][lo:]
                     t_start[k] -= lo
             offload(k)
-            m.sample_candidates()
-            m._injected = True
-            m._launch_reset(m.terminated)
-            m._injected = False
-            obs[k] = m.obs()
+            obs[k] = m.reset(m.terminated)
     torch.cuda.synchronize()
     t_loop = time.time() - t_loop
     print(f'Final reward: {np.mean(done_ret)}, length: {np.mean(done_len)}')

@@ -305,6 +305,14 @@ def ptr(t):
     return C.c_void_p(t.data_ptr())
 
 
+def fill(struct, **fields):
+    """Set fields of a ctypes struct and return it: a tensor becomes its device pointer, None is NULL, numbers as they are."""
+    for name, v in fields.items():
+        getattr(type(struct), name)   # AttributeError for a name that is no field (setattr alone would accept it)
+        setattr(struct, name, v.data_ptr() if hasattr(v, "data_ptr") else v)
+    return struct
+
+
 def current_stream_ptr():
     import torch
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)

@@ -284,6 +284,8 @@ __global__ __launch_bounds__(BLK) void egx_env_step_post_kernel(StepArgs p) {
   __shared__ float s_newseed[2][6];
   __shared__ float s_frame[24];        // R_[9], T_[3], R0new[9], T0new[3]
   __shared__ float s_scal[16];
+  constexpr int FR_R = 0, FR_T = 9, FR_R0 = 12, FR_T0 = 21;                           // slots of s_frame
+  constexpr int SC_FACE = 0, SC_LOOK = 1, SC_TDIST = 2, SC_GOAL = 3, SC_D2T = 4;      // slots of s_scal
   const int a = blockIdx.x, tid = threadIdx.x;
   const EnvCfg& c = p.cfg;
   const float* R0 = p.R0 + (size_t)a * 9;
@@ -370,15 +372,15 @@ __global__ __launch_bounds__(BLK) void egx_env_step_post_kernel(StepArgs p) {
     const float delta[3] = {j18[0] - PP[18 * XB + 0], j18[1] - PP[18 * XB + 1], j18[2] - PP[18 * XB + 2]};
     update_transl_glorot(Rn, Tn, delta, PP + 18 * XB, s_newseed[0]);
     update_transl_glorot(Rn, Tn, delta, PP + 19 * XB, s_newseed[1]);
-    for (int e = 0; e < 9; ++e) { s_frame[e] = Rn[e]; s_frame[12 + e] = R0n[e]; }
-    for (int e = 0; e < 3; ++e) { s_frame[9 + e] = Tn[e]; s_frame[21 + e] = T0n[e]; }
-    s_scal[0] = r_face; s_scal[1] = r_look; s_scal[2] = r_td; s_scal[3] = r_goal; s_scal[4] = d2t;
+    for (int e = 0; e < 9; ++e) { s_frame[FR_R + e] = Rn[e]; s_frame[FR_R0 + e] = R0n[e]; }
+    for (int e = 0; e < 3; ++e) { s_frame[FR_T + e] = Tn[e]; s_frame[FR_T0 + e] = T0n[e]; }
+    s_scal[SC_FACE] = r_face; s_scal[SC_LOOK] = r_look; s_scal[SC_TDIST] = r_td; s_scal[SC_GOAL] = r_goal; s_scal[SC_D2T] = d2t;
   }
   __syncthreads();
   float Rn[9], Tn[3], R0n[9], T0n[3];
-  for (int e = 0; e < 9; ++e) { Rn[e] = s_frame[e]; R0n[e] = s_frame[12 + e]; }
-  for (int e = 0; e < 3; ++e) { Tn[e] = s_frame[9 + e]; T0n[e] = s_frame[21 + e]; }
-  const float r_face = s_scal[0], r_look = s_scal[1], r_td = s_scal[2], r_goal = s_scal[3], d2t = s_scal[4];
+  for (int e = 0; e < 9; ++e) { Rn[e] = s_frame[FR_R + e]; R0n[e] = s_frame[FR_R0 + e]; }
+  for (int e = 0; e < 3; ++e) { Tn[e] = s_frame[FR_T + e]; T0n[e] = s_frame[FR_T0 + e]; }
+  const float r_face = s_scal[SC_FACE], r_look = s_scal[SC_LOOK], r_td = s_scal[SC_TDIST], r_goal = s_scal[SC_GOAL], d2t = s_scal[SC_D2T];
 
   // target in the NEW frame (for the marker features)
   float tln[3];
@@ -526,6 +528,9 @@ struct ResetArgs {
 __global__ __launch_bounds__(BLK) void egx_env_reset_kernel(ResetArgs p) {
   __shared__ float s_red[BLK];
   __shared__ float s_f[64];
+  // slots of s_f: the new canonical frame, the two seed frames' final R[9] t[3] (SF_FRAME + f * 12), the path's start (pelvis)
+  // and target, and frame 0's rotated R, t before it is moved over the start
+  constexpr int SF_R0 = 0, SF_T0 = 9, SF_FRAME = 12, SF_W0 = 36, SF_WP = 39, SF_RG0 = 42, SF_TG0 = 51;
   const int a = blockIdx.x, tid = threadIdx.x;
   if (p.mask && p.mask[a] == 0) {
     if (tid == 0 && p.pending && p.pending != p.mask) p.pending[a] = 0;
@@ -593,16 +598,16 @@ __global__ __launch_bounds__(BLK) void egx_env_reset_kernel(ResetArgs p) {
         apply_rot(Rz);
       }
       // frame 0's placement for the whole block: the lowest of its 127 joints is found one joint per thread
-      for (int e = 0; e < 9; ++e) s_f[42 + e] = Rg[0][e];
-      for (int e = 0; e < 3; ++e) s_f[51 + e] = tg[0][e];
+      for (int e = 0; e < 9; ++e) s_f[SF_RG0 + e] = Rg[0][e];
+      for (int e = 0; e < 3; ++e) s_f[SF_TG0 + e] = tg[0][e];
     }
     __syncthreads();
     float zmin;
     {
       float zl = 3.4e38f;
       if (tid != 0) {
-        for (int e = 0; e < 9; ++e) Rg[0][e] = s_f[42 + e];
-        for (int e = 0; e < 3; ++e) tg[0][e] = s_f[51 + e];
+        for (int e = 0; e < 9; ++e) Rg[0][e] = s_f[SF_RG0 + e];
+        for (int e = 0; e < 3; ++e) tg[0][e] = s_f[SF_TG0 + e];
       }
       for (int j = tid; j < NJO; j += BLK) {
         float q[3];
@@ -627,24 +632,24 @@ __global__ __launch_bounds__(BLK) void egx_env_reset_kernel(ResetArgs p) {
       world_joint(0, 2, wj2);
       canonical_frame(w0, wj1, wj2, R0n, T0n);
       // stash: R0n, T0n, per-frame Rg / tg, wpath
-      for (int e = 0; e < 9; ++e) s_f[e] = R0n[e];
-      for (int e = 0; e < 3; ++e) s_f[9 + e] = T0n[e];
+      for (int e = 0; e < 9; ++e) s_f[SF_R0 + e] = R0n[e];
+      for (int e = 0; e < 3; ++e) s_f[SF_T0 + e] = T0n[e];
       for (int f = 0; f < 2; ++f) {
-        for (int e = 0; e < 9; ++e) s_f[12 + f * 12 + e] = Rg[f][e];
-        for (int e = 0; e < 3; ++e) s_f[12 + f * 12 + 9 + e] = tg[f][e];
+        for (int e = 0; e < 9; ++e) s_f[SF_FRAME + f * 12 + e] = Rg[f][e];
+        for (int e = 0; e < 3; ++e) s_f[SF_FRAME + f * 12 + 9 + e] = tg[f][e];
       }
-      s_f[36] = w0[0]; s_f[37] = w0[1]; s_f[38] = w0[2];
-      s_f[39] = target[0]; s_f[40] = target[1]; s_f[41] = w0[2];
+      s_f[SF_W0] = w0[0]; s_f[SF_W0 + 1] = w0[1]; s_f[SF_W0 + 2] = w0[2];
+      s_f[SF_WP] = target[0]; s_f[SF_WP + 1] = target[1]; s_f[SF_WP + 2] = w0[2];
     }
     __syncthreads();
     float R0n[9], T0n[3];   // Rg / tg: every thread now takes the final placement of both frames
-    for (int e = 0; e < 9; ++e) R0n[e] = s_f[e];
-    for (int e = 0; e < 3; ++e) T0n[e] = s_f[9 + e];
+    for (int e = 0; e < 9; ++e) R0n[e] = s_f[SF_R0 + e];
+    for (int e = 0; e < 3; ++e) T0n[e] = s_f[SF_T0 + e];
     for (int f = 0; f < 2; ++f) {
-      for (int e = 0; e < 9; ++e) Rg[f][e] = s_f[12 + f * 12 + e];
-      for (int e = 0; e < 3; ++e) tg[f][e] = s_f[12 + f * 12 + 9 + e];
+      for (int e = 0; e < 9; ++e) Rg[f][e] = s_f[SF_FRAME + f * 12 + e];
+      for (int e = 0; e < 3; ++e) tg[f][e] = s_f[SF_FRAME + f * 12 + 9 + e];
     }
-    const float wp[3] = {s_f[39], s_f[40], s_f[41]};
+    const float wp[3] = {s_f[SF_WP], s_f[SF_WP + 1], s_f[SF_WP + 2]};
     const float* J0 = TJ;
     auto to_canonical = [&](int f, const float* q, float* o) {
       const float d[3] = {q[0] - J0[0], q[1] - J0[1], q[2] - J0[2]};
@@ -745,7 +750,7 @@ __global__ __launch_bounds__(BLK) void egx_env_reset_kernel(ResetArgs p) {
       for (int e = 0; e < 9; ++e) p.R0[(size_t)a * 9 + e] = R0n[e];
       for (int e = 0; e < 3; ++e) p.T0[(size_t)a * 3 + e] = T0n[e];
       float* w = p.wpath + (size_t)a * 6;
-      w[0] = s_f[36]; w[1] = s_f[37]; w[2] = s_f[38]; w[3] = wp[0]; w[4] = wp[1]; w[5] = wp[2];
+      w[0] = s_f[SF_W0]; w[1] = s_f[SF_W0 + 1]; w[2] = s_f[SF_W0 + 2]; w[3] = wp[0]; w[4] = wp[1]; w[5] = wp[2];
       if (p.out_choice) p.out_choice[a] = k;
       if (p.cand_scene && p.scene_idx) p.scene_idx[a] = scene;
       if (p.pending) p.pending[a] = accept ? 0 : 1;
