@@ -21,6 +21,7 @@
 #include <atomic>
 #include <cstdlib>
 
+#include "egx_sdf.h"
 #include "lbs_pack.h"
 
 // the events egx_profile_next_lbs hands over: the next launch of this thread records them around its fused and fix-up launches
@@ -288,9 +289,9 @@ static int lbs_forward_launch(const egx_body_model* m, const float* xb, const fl
                               size_t workspace_bytes, void* stream_) {
   EGX_REQUIRE(m && xb && betas, "null model/xb/betas");
   EGX_REQUIRE(B > 0 && fpa > 0, "num_bodies and frames_per_agent must be positive");
-  EGX_REQUIRE(!sdf || (sdf->grid && out_pene_count && sdf->d0 > 0 && sdf->d1 > 0 && sdf->d2 > 0), "sdf needs grid + out_pene_count");
+  EGX_REQUIRE(!sdf || out_pene_count, "sdf needs out_pene_count");
+  EGX_REQUIRE(!sdf || egx_sdf_grid_ok(sdf), "sdf grid needs d2 >= 2 and fewer than 2^32 samples");
   EGX_REQUIRE(!sdf || sdf->coarse_minmax, "sdf needs its bracket table: call egx_sdf_build_coarse once per grid");
-  EGX_REQUIRE(!sdf || egx_sdf_dims_ok(sdf->d0, sdf->d1, sdf->d2), "sdf grid needs d2 >= 2 and fewer than 2^32 samples");
   const WsLayout wl = ws_layout(m, B);
   if (!workspace || workspace_bytes < wl.total) {
     egx_set_error("workspace too small: need " + std::to_string(wl.total) + " bytes");
@@ -314,10 +315,13 @@ static int lbs_forward_launch(const egx_body_model* m, const float* xb, const fl
                     (size_t)m->n_sdf_tiles * nbg_all >= 8;
   SdfDev sd = {};
   const float* mips = nullptr;
+  const float* aux = nullptr;
   if (sdf) {
+    const EgxSdfTables t(*sdf);
     sd = egx_sdf_dev(*sdf);
-    sd.coarse = static_cast<const float2*>(sdf->coarse_minmax);
-    mips = reinterpret_cast<const float*>(static_cast<const char*>(sdf->coarse_minmax) + egx_sdf_table_bytes(sd.c0, sd.c1, sd.c2));
+    sd.coarse = t.brackets();
+    mips = t.mips();
+    aux = t.aux();
   }
   const bool fix = split3 && mode == 3 && sdf;   // mixed blend with counts: the pose kernel also writes the per-body error bound
   int* order = cull ? reinterpret_cast<int*>(ws + wl.order) : nullptr;
@@ -378,7 +382,7 @@ static int lbs_forward_launch(const egx_body_model* m, const float* xb, const fl
     p.fixq = reinterpret_cast<int2*>(ws + wl.fixq); p.fixq_cap = g_fixq_cap.load() > 0 ? g_fixq_cap.load() : LBS_FIXQ_CAP;
     p.dirs_rm = m->dirs_rm; p.pc = m->pc; p.betas = betas;
     p.skinB = reinterpret_cast<const bf16x8*>(ws + wl.skinB); p.cinit = reinterpret_cast<const f32x4*>(ws + wl.cinit);
-    p.sdf_aux = (sdf && !ms) ? reinterpret_cast<const float*>(static_cast<const char*>(sdf->coarse_minmax) + egx_sdf_aux_offset(sd.c0, sd.c1, sd.c2)) : nullptr;
+    p.sdf_aux = ms ? nullptr : aux;
     p.scenes = scene_tab; p.agent_scene = agent_scene; p.n_scenes = n_scenes;
     // three body groups per block: features + joint transforms of a block (3 x 1.2 MB) still live in the XCD's 4 MiB L2 and the
     // bases stream through twice per XCD instead of three times (5 groups per XCD at 10 240 bodies): fabric-side traffic 1.77 ->

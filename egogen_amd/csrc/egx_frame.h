@@ -4,6 +4,53 @@
 #pragma once
 #include "egx_common.h"
 
+// ---- rotation helpers shared with the network kernels (torchgeometry 0.1.2 semantics) ----
+__device__ __forceinline__ void egx_tgm_rotmat_to_aa(const float* R /*row-major 3x3*/, float* aa) {
+  // rotation_matrix_to_quaternion works on R^T: m[a][b] = R[b][a]
+  const float m00 = R[0], m01 = R[3], m02 = R[6], m10 = R[1], m11 = R[4], m12 = R[7], m20 = R[2], m21 = R[5], m22 = R[8];
+  float q0, q1, q2, q3, t;
+  if (m22 < 1e-6f) {
+    if (m00 > m11) {
+      t = 1.f + m00 - m11 - m22;
+      q0 = m12 - m21; q1 = t; q2 = m01 + m10; q3 = m20 + m02;
+    } else {
+      t = 1.f - m00 + m11 - m22;
+      q0 = m20 - m02; q1 = m01 + m10; q2 = t; q3 = m12 + m21;
+    }
+  } else {
+    if (m00 < -m11) {
+      t = 1.f - m00 - m11 + m22;
+      q0 = m01 - m10; q1 = m20 + m02; q2 = m12 + m21; q3 = t;
+    } else {
+      t = 1.f + m00 + m11 + m22;
+      q0 = t; q1 = m12 - m21; q2 = m20 - m02; q3 = m01 - m10;
+    }
+  }
+  const float sc = 0.5f / sqrtf(t);
+  q0 *= sc; q1 *= sc; q2 *= sc; q3 *= sc;
+  const float sin_sq = q1 * q1 + q2 * q2 + q3 * q3;
+  const float sin_t = sqrtf(sin_sq);
+  const float two_theta = 2.f * ((q0 < 0.f) ? atan2f(-sin_t, -q0) : atan2f(sin_t, q0));
+  const float k = (sin_sq > 0.f) ? two_theta / sin_t : 2.f;
+  aa[0] = q1 * k; aa[1] = q2 * k; aa[2] = q3 * k;
+}
+
+__device__ __forceinline__ void egx_tgm_aa_to_rotmat(const float* aa, float* R) {
+  const float theta2 = aa[0] * aa[0] + aa[1] * aa[1] + aa[2] * aa[2];
+  if (theta2 > 1e-6f) {
+    const float theta = sqrtf(theta2);
+    const float wx = aa[0] / (theta + 1e-6f), wy = aa[1] / (theta + 1e-6f), wz = aa[2] / (theta + 1e-6f);
+    const float c = cosf(theta), s = sinf(theta), oc = 1.f - c;
+    R[0] = c + wx * wx * oc;      R[1] = wx * wy * oc - wz * s; R[2] = wy * s + wx * wz * oc;
+    R[3] = wz * s + wx * wy * oc; R[4] = c + wy * wy * oc;      R[5] = -wx * s + wy * wz * oc;
+    R[6] = -wy * s + wx * wz * oc; R[7] = wx * s + wy * wz * oc; R[8] = c + wz * wz * oc;
+  } else {
+    R[0] = 1.f; R[1] = -aa[2]; R[2] = aa[1];
+    R[3] = aa[2]; R[4] = 1.f; R[5] = -aa[0];
+    R[6] = -aa[1]; R[7] = aa[0]; R[8] = 1.f;
+  }
+}
+
 __device__ __forceinline__ void mat3_mul(const float* A, const float* B, float* C) {  // C = A B
   for (int r = 0; r < 3; ++r)
     for (int c = 0; c < 3; ++c) C[r * 3 + c] = A[r * 3 + 0] * B[0 * 3 + c] + A[r * 3 + 1] * B[1 * 3 + c] + A[r * 3 + 2] * B[2 * 3 + c];

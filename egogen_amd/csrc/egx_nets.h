@@ -1,6 +1,7 @@
 // Internal launch helpers shared by the network files (not part of the C ABI).  Device helpers of the dense3 kernels: d3.h.
 #pragma once
 #include "egx_common.h"
+#include "egx_frame.h"   // egx_tgm_rotmat_to_aa
 
 struct EgxSeg {
   const float* p;

@@ -7,6 +7,7 @@
 #include <mutex>
 
 #include "egx_common.h"
+#include "egx_sdf.h"
 
 namespace {
 

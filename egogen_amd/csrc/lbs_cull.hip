@@ -13,6 +13,7 @@
 //   egx_lbs_cull_kernel         the test per (tile, body), OR-reduced per item
 //   egx_lbs_compact_kernel      per-XCD item lists (non-picked tiles dealt by tile chunk: an XCD streams an eighth of the bases)
 // ------------------------------------------------------------------------------------------------
+#include "egx_sdf.h"
 #include "lbs.h"
 
 namespace {

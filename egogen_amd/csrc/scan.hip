@@ -3,6 +3,7 @@
 // (support + clearance per cell).  The host side (welding, pseudo-normals, BVH build, floor detection, erosion) is in
 // egogen_amd/scene_gen.py.
 #include "egx_common.h"
+#include "egx_sdf.h"   // egx_sdf_dims_ok
 
 namespace {
 

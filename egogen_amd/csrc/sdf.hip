@@ -3,6 +3,7 @@
 // coordinates and output: profiles/r06_sdf_sample.md (incl. the LDS-staged per-body variant that was built, measured slower and
 // removed).
 #include "egx_common.h"
+#include "egx_sdf.h"
 
 #include <cmath>
 #include <cstring>
@@ -10,67 +11,21 @@
 #ifndef EGX_SDF_PPT
 #define EGX_SDF_PPT 4   // points per lane and trip: their 4 x PPT corner-pair gathers are in flight together
 #endif
-__global__ __launch_bounds__(256) void egx_sdf_sample_kernel(SdfDev s, const float* __restrict__ pts, int64_t n,
-                                                            float* __restrict__ out) {
+// FROM_BRICKS: the same values from the bricked copy of the grid (egx_sdf.h: egx_sdf_bricks_offset; built by egx_sdf_build_coarse).
+// What bounds the row-major kernel is the number of 128-byte lines its corner gathers pull from L2, and a point's eight corners
+// span four lines of the row-major grid but 2.3 on average of the bricked one.  Same cell, same arithmetic: bit-identical values.
+template <bool FROM_BRICKS>
+__global__ __launch_bounds__(256) void egx_sdf_sample_kernel(SdfDev s, const float* __restrict__ bricks, const float* __restrict__ pts,
+                                                            int64_t n, float* __restrict__ out) {
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t i0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i0 < n; i0 += EGX_SDF_PPT * stride) {
     float r[EGX_SDF_PPT];
 #pragma unroll
     for (int u = 0; u < EGX_SDF_PPT; ++u) {
       const int64_t i = min(i0 + u * stride, n - 1);
-      r[u] = egx_sdf_neg_trilinear(s, pts[i * 3 + 0], pts[i * 3 + 1], pts[i * 3 + 2]);
-    }
-#pragma unroll
-    for (int u = 0; u < EGX_SDF_PPT; ++u)
-      if (i0 + u * stride < n) out[i0 + u * stride] = r[u];
-  }
-}
-
-// The same values from the bricked copy of the grid (egx_common.h: egx_sdf_bricks_offset; built by egx_sdf_build_coarse): what
-// bounds the kernel above is the number of 128-byte lines its corner gathers pull from L2, and a point's eight corners span four
-// lines of the row-major grid but 2.3 on average of the bricked one.  Same samples, same arithmetic: bit-identical values.
-__device__ __forceinline__ float egx_brick_at(const float* __restrict__ bricks, unsigned nb1, unsigned nb2, unsigned x, unsigned y, unsigned z) {
-  const unsigned b = ((x >> 2) * nb1 + (y >> 2)) * nb2 + (z >> 2);
-  return bricks[(size_t)b * 64 + ((x & 3) << 4) + ((y & 3) << 2) + (z & 3)];
-}
-__device__ __forceinline__ float egx_sdf_neg_trilinear_bricks(const SdfDev& s, const float* __restrict__ bricks, float x, float y, float z) {
-  float px, py, pz;
-  egx_sdf_voxel_coords(s, x, y, z, px, py, pz);
-  const float x0 = floorf(px), y0 = floorf(py), z0 = floorf(pz);
-  const float wx1 = egx_sub(px, x0), wy1 = egx_sub(py, y0), wz1 = egx_sub(pz, z0);
-  const float wx0 = egx_sub(egx_add(x0, 1.f), px), wy0 = egx_sub(egx_add(y0, 1.f), py), wz0 = egx_sub(egx_add(z0, 1.f), pz);
-  const unsigned ix0 = (unsigned)x0, iy0 = (unsigned)y0, iz0 = (unsigned)z0;
-  const bool x1_in = ix0 + 1 < (unsigned)s.d0, y1_in = iy0 + 1 < (unsigned)s.d1, z1_in = iz0 + 1 < (unsigned)s.d2;
-  const unsigned zb = z1_in ? iz0 : iz0 - 1;                      // pair (zb, zb+1) always inside the row
-  const unsigned ix1 = x1_in ? ix0 + 1 : ix0, iy1 = y1_in ? iy0 + 1 : iy0;   // off-grid corners: weight exactly 0, any valid sample
-  const unsigned nb1 = (unsigned)s.c1, nb2 = (unsigned)s.c2;
-  const float c00x = egx_brick_at(bricks, nb1, nb2, ix0, iy0, zb), c00y = egx_brick_at(bricks, nb1, nb2, ix0, iy0, zb + 1);
-  const float c01x = egx_brick_at(bricks, nb1, nb2, ix0, iy1, zb), c01y = egx_brick_at(bricks, nb1, nb2, ix0, iy1, zb + 1);
-  const float c10x = egx_brick_at(bricks, nb1, nb2, ix1, iy0, zb), c10y = egx_brick_at(bricks, nb1, nb2, ix1, iy0, zb + 1);
-  const float c11x = egx_brick_at(bricks, nb1, nb2, ix1, iy1, zb), c11y = egx_brick_at(bricks, nb1, nb2, ix1, iy1, zb + 1);
-  const float wx1e = x1_in ? wx1 : 0.f, wy1e = y1_in ? wy1 : 0.f, wz1e = z1_in ? wz1 : 0.f;
-  const float v000 = z1_in ? c00x : c00y, v010 = z1_in ? c01x : c01y, v100 = z1_in ? c10x : c10y, v110 = z1_in ? c11x : c11y;
-  const float a00 = egx_mul(wx0, wy0), a01 = egx_mul(wx0, wy1e), a10 = egx_mul(wx1e, wy0), a11 = egx_mul(wx1e, wy1e);
-  float acc;
-  acc = egx_mul(v000, egx_mul(a00, wz0));
-  acc = egx_add(acc, egx_mul(c00y, egx_mul(a00, wz1e)));
-  acc = egx_add(acc, egx_mul(v010, egx_mul(a01, wz0)));
-  acc = egx_add(acc, egx_mul(c01y, egx_mul(a01, wz1e)));
-  acc = egx_add(acc, egx_mul(v100, egx_mul(a10, wz0)));
-  acc = egx_add(acc, egx_mul(c10y, egx_mul(a10, wz1e)));
-  acc = egx_add(acc, egx_mul(v110, egx_mul(a11, wz0)));
-  acc = egx_add(acc, egx_mul(c11y, egx_mul(a11, wz1e)));
-  return -acc;
-}
-__global__ __launch_bounds__(256) void egx_sdf_sample_bricks_kernel(SdfDev s, const float* __restrict__ bricks, const float* __restrict__ pts,
-                                                                   int64_t n, float* __restrict__ out) {
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t i0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i0 < n; i0 += EGX_SDF_PPT * stride) {
-    float r[EGX_SDF_PPT];
-#pragma unroll
-    for (int u = 0; u < EGX_SDF_PPT; ++u) {
-      const int64_t i = min(i0 + u * stride, n - 1);
-      r[u] = egx_sdf_neg_trilinear_bricks(s, bricks, pts[i * 3 + 0], pts[i * 3 + 1], pts[i * 3 + 2]);
+      float px, py, pz;
+      egx_sdf_voxel_coords(s, pts[i * 3 + 0], pts[i * 3 + 1], pts[i * 3 + 2], px, py, pz);
+      r[u] = egx_sdf_cell_neg_value(egx_sdf_cell<FROM_BRICKS>(s, bricks, px, py, pz));
     }
 #pragma unroll
     for (int u = 0; u < EGX_SDF_PPT; ++u)
@@ -119,7 +74,7 @@ __global__ void egx_sdf_build_coarse_kernel(const float* __restrict__ grid, int 
   out[idx] = make_float2(mn, mx);
 }
 
-// free-space pyramid (egx_common.h): level l entry = max over its 2^l-cubed block of padded bracket cells of their `max`
+// free-space pyramid (egx_sdf.h): level l entry = max over its 2^l-cubed block of padded bracket cells of their `max`
 __global__ void egx_sdf_build_mip_kernel(const float2* __restrict__ table, int c0, int c1, int c2, int l, float* __restrict__ out) {
   const int idx = blockIdx.x * blockDim.x + threadIdx.x;
   const int e0 = egx_sdf_mip_dim(c0, l), e1 = egx_sdf_mip_dim(c1, l), e2 = egx_sdf_mip_dim(c2, l);
@@ -133,7 +88,7 @@ __global__ void egx_sdf_build_mip_kernel(const float2* __restrict__ table, int c
   out[idx] = mx;
 }
 
-// aux[0..2] (egx_common.h): largest |difference| of neighbouring samples along each axis; aux[3]: the steepest slope of the
+// aux[0..2] (egx_sdf.h): largest |difference| of neighbouring samples along each axis; aux[3]: the steepest slope of the
 // interpolated field in value per METRE.  Inside a cell every component of the trilinear gradient is a convex combination of the
 // cell's four edge differences along that axis, so |gradient| <= sqrt(sum_a (k_a max edge_a)^2) per cell, k_a = samples per
 // metre; outside the cube the border clamp only removes components.  Non-negative floats order like their bit patterns, so the
@@ -165,52 +120,48 @@ __global__ __launch_bounds__(256) void egx_sdf_axis_steps_kernel(const float* __
 
 extern "C" size_t egx_sdf_coarse_bytes(int d0, int d1, int d2) {
   if (d0 <= 0 || d1 <= 0 || d2 <= 0) return 0;
-  const int c0 = egx_ceil_div(d0, 4), c1 = egx_ceil_div(d1, 4), c2 = egx_ceil_div(d2, 4);
-  return egx_sdf_bricks_offset(c0, c1, c2) + (size_t)c0 * c1 * c2 * 64 * sizeof(float);
+  return EgxSdfTables(d0, d1, d2).bytes();
 }
 
 extern "C" int egx_sdf_build_coarse(const egx_sdf_grid* sdf, void* coarse_out, void* stream_) {
   EGX_REQUIRE(sdf && sdf->grid && coarse_out && sdf->d0 > 0 && sdf->d1 > 0 && sdf->d2 > 0, "bad arguments");
-  const int c0 = egx_ceil_div(sdf->d0, 4), c1 = egx_ceil_div(sdf->d1, 4), c2 = egx_ceil_div(sdf->d2, 4);
+  const EgxSdfTables t(sdf->d0, sdf->d1, sdf->d2, coarse_out);
+  const int c0 = t.c0, c1 = t.c1, c2 = t.c2;
+  hipStream_t st = static_cast<hipStream_t>(stream_);
   const int n = (c0 + 2) * (c1 + 2) * (c2 + 2);
-  hipLaunchKernelGGL(egx_sdf_build_coarse_kernel, dim3(egx_ceil_div(n, 256)), dim3(256), 0, static_cast<hipStream_t>(stream_),
-                     sdf->grid, sdf->d0, sdf->d1, sdf->d2, c0, c1, c2, static_cast<float2*>(coarse_out));
-  float* mips = reinterpret_cast<float*>(static_cast<char*>(coarse_out) + egx_sdf_table_bytes(c0, c1, c2));
+  hipLaunchKernelGGL(egx_sdf_build_coarse_kernel, dim3(egx_ceil_div(n, 256)), dim3(256), 0, st, sdf->grid, sdf->d0, sdf->d1, sdf->d2, c0, c1, c2,
+                     t.brackets());
   for (int l = 1; l <= EGX_SDF_MIP_LEVELS; ++l) {
     const int ne = egx_sdf_mip_dim(c0, l) * egx_sdf_mip_dim(c1, l) * egx_sdf_mip_dim(c2, l);
-    hipLaunchKernelGGL(egx_sdf_build_mip_kernel, dim3(egx_ceil_div(ne, 128)), dim3(128), 0, static_cast<hipStream_t>(stream_),
-                       static_cast<const float2*>(coarse_out), c0, c1, c2, l, mips + egx_sdf_mip_offset(c0, c1, c2, l));
+    hipLaunchKernelGGL(egx_sdf_build_mip_kernel, dim3(egx_ceil_div(ne, 128)), dim3(128), 0, st, t.brackets(), c0, c1, c2, l, t.mip(l));
   }
-  hipLaunchKernelGGL(egx_sdf_build_bricks_kernel, dim3(2048), dim3(256), 0, static_cast<hipStream_t>(stream_), sdf->grid, sdf->d0, sdf->d1, sdf->d2,
-                     c0, c1, c2, reinterpret_cast<float*>(static_cast<char*>(coarse_out) + egx_sdf_bricks_offset(c0, c1, c2)));
-  unsigned* aux = reinterpret_cast<unsigned*>(static_cast<char*>(coarse_out) + egx_sdf_aux_offset(c0, c1, c2));
-  EGX_HIP_CHECK(hipMemsetAsync(aux, 0, EGX_SDF_AUX_FLOATS * sizeof(float), static_cast<hipStream_t>(stream_)));
-  hipLaunchKernelGGL(egx_sdf_axis_steps_kernel, dim3(1024), dim3(256), 0, static_cast<hipStream_t>(stream_), sdf->grid, sdf->d0, sdf->d1,
-                     sdf->d2, sdf->scale * (float)sdf->d0 * 0.5f, sdf->scale * (float)sdf->d1 * 0.5f, sdf->scale * (float)sdf->d2 * 0.5f, aux);
+  hipLaunchKernelGGL(egx_sdf_build_bricks_kernel, dim3(2048), dim3(256), 0, st, sdf->grid, sdf->d0, sdf->d1, sdf->d2, c0, c1, c2, t.bricks());
+  EGX_HIP_CHECK(hipMemsetAsync(t.aux(), 0, EGX_SDF_AUX_FLOATS * sizeof(float), st));
+  hipLaunchKernelGGL(egx_sdf_axis_steps_kernel, dim3(1024), dim3(256), 0, st, sdf->grid, sdf->d0, sdf->d1, sdf->d2,
+                     sdf->scale * (float)sdf->d0 * 0.5f, sdf->scale * (float)sdf->d1 * 0.5f, sdf->scale * (float)sdf->d2 * 0.5f,
+                     reinterpret_cast<unsigned*>(t.aux()));
   EGX_HIP_CHECK(hipGetLastError());
   return EGX_OK;
 }
 
 extern "C" int egx_sdf_sample(const egx_sdf_grid* sdf, const float* pts, int64_t n, float* out, void* stream_) {
-  EGX_REQUIRE(sdf && sdf->grid && sdf->d0 > 0 && sdf->d1 > 0 && sdf->d2 > 0, "bad sdf grid");
-  EGX_REQUIRE(egx_sdf_dims_ok(sdf->d0, sdf->d1, sdf->d2), "sdf grid needs d2 >= 2 and fewer than 2^32 samples");
+  EGX_REQUIRE(egx_sdf_grid_ok(sdf), "sdf grid needs d2 >= 2 and fewer than 2^32 samples");
   if (n == 0) return EGX_OK;  // empty input is legal
   EGX_REQUIRE(pts && out && n > 0, "null points / output");
   const SdfDev s = egx_sdf_dev(*sdf);
   const int64_t blocks = (n + 256 * EGX_SDF_PPT - 1) / (256 * EGX_SDF_PPT);
   const int grid = (int)(blocks < 8192 ? blocks : 8192);
-  if (sdf->coarse_minmax) {   // the tables of egx_sdf_build_coarse are there: gather from the bricked copy
-    const float* bricks = reinterpret_cast<const float*>(static_cast<const char*>(sdf->coarse_minmax) + egx_sdf_bricks_offset(s.c0, s.c1, s.c2));
-    hipLaunchKernelGGL(egx_sdf_sample_bricks_kernel, dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream_), s, bricks, pts, n, out);
-  } else {
-    hipLaunchKernelGGL(egx_sdf_sample_kernel, dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream_), s, pts, n, out);
-  }
+  const float* bricks = egx_sdf_bricks(*sdf);   // the tables of egx_sdf_build_coarse are there: gather from the bricked copy
+  if (bricks)
+    hipLaunchKernelGGL(egx_sdf_sample_kernel<true>, dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream_), s, bricks, pts, n, out);
+  else
+    hipLaunchKernelGGL(egx_sdf_sample_kernel<false>, dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream_), s, bricks, pts, n, out);
   EGX_HIP_CHECK(hipGetLastError());
   return EGX_OK;
 }
 
 // ------------------------------------------------------------------------------------------------
-// SDF scene sets: the per-scene records of egx_lbs_forward_scenes, made once (struct egx_sdf_scene_set: egx_common.h)
+// SDF scene sets: the per-scene records of egx_lbs_forward_scenes, made once (struct egx_sdf_scene_set: egx_sdf.h)
 // ------------------------------------------------------------------------------------------------
 
 extern "C" int egx_sdf_scene_set_create(const egx_sdf_grid* scenes, int num_scenes, egx_sdf_scene_set** out) {
@@ -230,7 +181,7 @@ extern "C" int egx_sdf_scene_set_create(const egx_sdf_grid* scenes, int num_scen
   }
   for (int i = 0; i < num_scenes; ++i) {
     const egx_sdf_grid& g = scenes[i];
-    if (!g.grid || !g.coarse_minmax || !egx_sdf_dims_ok(g.d0, g.d1, g.d2) || g.d0 <= 0 || g.d1 <= 0) {
+    if (!egx_sdf_grid_ok(&g) || !g.coarse_minmax) {
       egx_set_error("egx_sdf_scene_set_create: scene " + std::to_string(i) +
                     " needs a grid with d2 >= 2 and fewer than 2^32 samples and its bracket table (egx_sdf_build_coarse)");
       return EGX_ERR_ARG;
@@ -238,15 +189,14 @@ extern "C" int egx_sdf_scene_set_create(const egx_sdf_grid* scenes, int num_scen
   }
   // the slopes (aux[3] of each table) were written by egx_sdf_build_coarse on some stream: wait for it, then read them once
   EGX_HIP_CHECK(hipDeviceSynchronize());
-  const int c0 = egx_ceil_div(s0.d0, 4), c1 = egx_ceil_div(s0.d1, 4), c2 = egx_ceil_div(s0.d2, 4);
   for (int i = 0; i < num_scenes; ++i) {
     const egx_sdf_grid& g = scenes[i];
     SdfSceneDev& r = rec[(size_t)i];
     r.grid = g.grid;
-    r.coarse = static_cast<const float2*>(g.coarse_minmax);
+    const EgxSdfTables t(g);
+    r.coarse = t.brackets();
     r.cx = g.center[0]; r.cy = g.center[1]; r.cz = g.center[2]; r.scale = g.scale;
-    EGX_HIP_CHECK(hipMemcpy(&r.slope, static_cast<const char*>(g.coarse_minmax) + egx_sdf_aux_offset(c0, c1, c2) + 3 * sizeof(float),
-                            sizeof(float), hipMemcpyDeviceToHost));
+    EGX_HIP_CHECK(hipMemcpy(&r.slope, t.aux() + 3, sizeof(float), hipMemcpyDeviceToHost));
     r.pad = 0.f;
   }
   auto* set = new egx_sdf_scene_set();

@@ -4,8 +4,10 @@
 // bricked copy of the grid when the descriptor carries the tables of egx_sdf_build_coarse.  Resources, errors against float64
 // and timings: profiles/sdf_grad.md.
 #include "egx_common.h"
+#include "egx_sdf.h"
 
 #include <cmath>
+#include <type_traits>
 
 #ifndef EGX_SDF_GRAD_PPT
 #define EGX_SDF_GRAD_PPT 4   // points per lane and trip
@@ -36,13 +38,8 @@ __device__ __forceinline__ double voxel_coord_f64(float w, float c, float scale,
   return fmin(fmax(p, 0.0), (double)(d - 1));
 }
 
-__device__ __forceinline__ float brick_at(const float* __restrict__ bricks, unsigned nb1, unsigned nb2, unsigned x, unsigned y, unsigned z) {
-  const unsigned b = ((x >> 2) * nb1 + (y >> 2)) * nb2 + (z >> 2);
-  return bricks[(size_t)b * 64 + ((x & 3) << 4) + ((y & 3) << 2) + (z & 3)];
-}
-
-// s = -trilinear and g = d s / d (x, y, z).  The value repeats egx_sdf_neg_trilinear_at (egx_common.h) operation by operation -
-// same coordinates, weights, corner substitution and accumulation order - so it has the bits of egx_sdf_sample.  The gradient
+// s = -trilinear and g = d s / d (x, y, z) from the cell of the point (egx_sdf.h).  The value is the shared accumulation
+// egx_sdf_cell_neg_value, so it has the bits of egx_sdf_sample and of the LBS count.  The gradient
 // takes the four corner differences along each axis first and combines them with the other two axes' weights (the differences
 // of neighbouring samples are small and exact to a rounding; eight signed products would cancel instead), then multiplies by
 // d voxel / d metre = scale * d_a / 2.  An axis whose clamped coordinate sits on the first or last sample plane has an
@@ -56,66 +53,34 @@ __device__ __forceinline__ SdfValGrad sdf_value_grad_at(const SdfDev& s, const f
 #pragma clang fp contract(off)
   float px, py, pz;
   egx_sdf_voxel_coords(s, x, y, z, px, py, pz);
-  const float x0 = floorf(px), y0 = floorf(py), z0 = floorf(pz);
-  const float wx1 = egx_sub(px, x0), wy1 = egx_sub(py, y0), wz1 = egx_sub(pz, z0);
-  const float wx0 = egx_sub(egx_add(x0, 1.f), px), wy0 = egx_sub(egx_add(y0, 1.f), py), wz0 = egx_sub(egx_add(z0, 1.f), pz);
-  const unsigned ix0 = (unsigned)x0, iy0 = (unsigned)y0, iz0 = (unsigned)z0;
-  const bool x1_in = ix0 + 1 < (unsigned)s.d0, y1_in = iy0 + 1 < (unsigned)s.d1, z1_in = iz0 + 1 < (unsigned)s.d2;
-  const unsigned zb = z1_in ? iz0 : iz0 - 1;                      // pair (zb, zb+1) always inside the row
-  float c00x, c00y, c01x, c01y, c10x, c10y, c11x, c11y;
-  if (FROM_BRICKS) {
-    const unsigned ix1 = x1_in ? ix0 + 1 : ix0, iy1 = y1_in ? iy0 + 1 : iy0;   // off-grid corners: weight exactly 0, any valid sample
-    const unsigned nb1 = (unsigned)s.c1, nb2 = (unsigned)s.c2;
-    c00x = brick_at(bricks, nb1, nb2, ix0, iy0, zb); c00y = brick_at(bricks, nb1, nb2, ix0, iy0, zb + 1);
-    c01x = brick_at(bricks, nb1, nb2, ix0, iy1, zb); c01y = brick_at(bricks, nb1, nb2, ix0, iy1, zb + 1);
-    c10x = brick_at(bricks, nb1, nb2, ix1, iy0, zb); c10y = brick_at(bricks, nb1, nb2, ix1, iy0, zb + 1);
-    c11x = brick_at(bricks, nb1, nb2, ix1, iy1, zb); c11y = brick_at(bricks, nb1, nb2, ix1, iy1, zb + 1);
-  } else {
-    const unsigned i00 = (ix0 * (unsigned)s.d1 + iy0) * (unsigned)s.d2 + zb;
-    const unsigned sy = y1_in ? (unsigned)s.d2 : 0u, sx = x1_in ? (unsigned)s.d1 * (unsigned)s.d2 : 0u;
-    const EgxF2 c00 = *reinterpret_cast<const EgxF2*>(s.grid + i00), c01 = *reinterpret_cast<const EgxF2*>(s.grid + (i00 + sy)),
-                c10 = *reinterpret_cast<const EgxF2*>(s.grid + (i00 + sx)), c11 = *reinterpret_cast<const EgxF2*>(s.grid + (i00 + sx + sy));
-    c00x = c00.x; c00y = c00.y; c01x = c01.x; c01y = c01.y; c10x = c10.x; c10y = c10.y; c11x = c11.x; c11y = c11.y;
-  }
-  const float wx1e = x1_in ? wx1 : 0.f, wy1e = y1_in ? wy1 : 0.f, wz1e = z1_in ? wz1 : 0.f;
-  const float v000 = z1_in ? c00x : c00y, v010 = z1_in ? c01x : c01y, v100 = z1_in ? c10x : c10y, v110 = z1_in ? c11x : c11y;
-  const float a00 = egx_mul(wx0, wy0), a01 = egx_mul(wx0, wy1e), a10 = egx_mul(wx1e, wy0), a11 = egx_mul(wx1e, wy1e);
-  float acc;
-  acc = egx_mul(v000, egx_mul(a00, wz0));
-  acc = egx_add(acc, egx_mul(c00y, egx_mul(a00, wz1e)));
-  acc = egx_add(acc, egx_mul(v010, egx_mul(a01, wz0)));
-  acc = egx_add(acc, egx_mul(c01y, egx_mul(a01, wz1e)));
-  acc = egx_add(acc, egx_mul(v100, egx_mul(a10, wz0)));
-  acc = egx_add(acc, egx_mul(c10y, egx_mul(a10, wz1e)));
-  acc = egx_add(acc, egx_mul(v110, egx_mul(a11, wz0)));
-  acc = egx_add(acc, egx_mul(c11y, egx_mul(a11, wz1e)));
+  const EgxSdfCell c = egx_sdf_cell<FROM_BRICKS>(s, bricks, px, py, pz);
   // gradient in voxel units: corner (i, j, k) is v{i}{j}0 for k = 0 and c{i}{j}y for k = 1
-  const float b00 = egx_mul(wy0, wz0), b01 = egx_mul(wy0, wz1e), b10 = egx_mul(wy1e, wz0), b11 = egx_mul(wy1e, wz1e);   // (y, z)
-  const float e00 = egx_mul(wx0, wz0), e01 = egx_mul(wx0, wz1e), e10 = egx_mul(wx1e, wz0), e11 = egx_mul(wx1e, wz1e);   // (x, z)
-  float dx = egx_mul(egx_sub(v100, v000), b00);
-  dx = __builtin_fmaf(egx_sub(c10y, c00y), b01, dx);
-  dx = __builtin_fmaf(egx_sub(v110, v010), b10, dx);
-  dx = __builtin_fmaf(egx_sub(c11y, c01y), b11, dx);
-  float dy = egx_mul(egx_sub(v010, v000), e00);
-  dy = __builtin_fmaf(egx_sub(c01y, c00y), e01, dy);
-  dy = __builtin_fmaf(egx_sub(v110, v100), e10, dy);
-  dy = __builtin_fmaf(egx_sub(c11y, c10y), e11, dy);
-  float dz = egx_mul(egx_sub(c00y, v000), a00);
-  dz = __builtin_fmaf(egx_sub(c01y, v010), a01, dz);
-  dz = __builtin_fmaf(egx_sub(c10y, v100), a10, dz);
-  dz = __builtin_fmaf(egx_sub(c11y, v110), a11, dz);
+  const float b00 = egx_mul(c.wy0, c.wz0), b01 = egx_mul(c.wy0, c.wz1e), b10 = egx_mul(c.wy1e, c.wz0), b11 = egx_mul(c.wy1e, c.wz1e);   // (y, z)
+  const float e00 = egx_mul(c.wx0, c.wz0), e01 = egx_mul(c.wx0, c.wz1e), e10 = egx_mul(c.wx1e, c.wz0), e11 = egx_mul(c.wx1e, c.wz1e);   // (x, z)
+  float dx = egx_mul(egx_sub(c.v100, c.v000), b00);
+  dx = __builtin_fmaf(egx_sub(c.c10y, c.c00y), b01, dx);
+  dx = __builtin_fmaf(egx_sub(c.v110, c.v010), b10, dx);
+  dx = __builtin_fmaf(egx_sub(c.c11y, c.c01y), b11, dx);
+  float dy = egx_mul(egx_sub(c.v010, c.v000), e00);
+  dy = __builtin_fmaf(egx_sub(c.c01y, c.c00y), e01, dy);
+  dy = __builtin_fmaf(egx_sub(c.v110, c.v100), e10, dy);
+  dy = __builtin_fmaf(egx_sub(c.c11y, c.c10y), e11, dy);
+  float dz = egx_mul(egx_sub(c.c00y, c.v000), c.a00);
+  dz = __builtin_fmaf(egx_sub(c.c01y, c.v010), c.a01, dz);
+  dz = __builtin_fmaf(egx_sub(c.c10y, c.v100), c.a10, dz);
+  dz = __builtin_fmaf(egx_sub(c.c11y, c.v110), c.a11, dz);
   const float kx = egx_mul(egx_mul((float)s.d0, 0.5f), s.scale), ky = egx_mul(egx_mul((float)s.d1, 0.5f), s.scale),
               kz = egx_mul(egx_mul((float)s.d2, 0.5f), s.scale);
   SdfValGrad r;
-  r.v = -acc;
+  r.v = egx_sdf_cell_neg_value(c);
   r.v64 = 0.0;
   if (WITH_F64) {
     const double qx = voxel_coord_f64(x, s.cx, s.scale, s.d0), qy = voxel_coord_f64(y, s.cy, s.scale, s.d1),
                  qz = voxel_coord_f64(z, s.cz, s.scale, s.d2);
-    const double ux1 = x1_in ? d_sub(qx, (double)x0) : 0.0, uy1 = y1_in ? d_sub(qy, (double)y0) : 0.0, uz1 = z1_in ? d_sub(qz, (double)z0) : 0.0;
-    const double ux0 = x1_in ? d_sub(1.0, ux1) : 1.0, uy0 = y1_in ? d_sub(1.0, uy1) : 1.0, uz0 = z1_in ? d_sub(1.0, uz1) : 1.0;
-    const double lo0 = d_add(d_mul((double)v000, uz0), d_mul((double)c00y, uz1)), lo1 = d_add(d_mul((double)v010, uz0), d_mul((double)c01y, uz1));
-    const double hi0 = d_add(d_mul((double)v100, uz0), d_mul((double)c10y, uz1)), hi1 = d_add(d_mul((double)v110, uz0), d_mul((double)c11y, uz1));
+    const double ux1 = c.x1_in ? d_sub(qx, (double)c.x0) : 0.0, uy1 = c.y1_in ? d_sub(qy, (double)c.y0) : 0.0, uz1 = c.z1_in ? d_sub(qz, (double)c.z0) : 0.0;
+    const double ux0 = c.x1_in ? d_sub(1.0, ux1) : 1.0, uy0 = c.y1_in ? d_sub(1.0, uy1) : 1.0, uz0 = c.z1_in ? d_sub(1.0, uz1) : 1.0;
+    const double lo0 = d_add(d_mul((double)c.v000, uz0), d_mul((double)c.c00y, uz1)), lo1 = d_add(d_mul((double)c.v010, uz0), d_mul((double)c.c01y, uz1));
+    const double hi0 = d_add(d_mul((double)c.v100, uz0), d_mul((double)c.c10y, uz1)), hi1 = d_add(d_mul((double)c.v110, uz0), d_mul((double)c.c11y, uz1));
     const double lo = d_add(d_mul(lo0, uy0), d_mul(lo1, uy1)), hi = d_add(d_mul(hi0, uy0), d_mul(hi1, uy1));
     r.v64 = -d_add(d_mul(lo, ux0), d_mul(hi, ux1));
   }
@@ -281,17 +246,6 @@ __global__ __launch_bounds__(256) void egx_sdf_penalty_backward_kernel(PenaltyFi
   }
 }
 
-bool grid_ok(const egx_sdf_grid* g) {
-  return g && g->grid && g->d0 > 0 && g->d1 > 0 && g->d2 > 0 && egx_sdf_dims_ok(g->d0, g->d1, g->d2);
-}
-
-SdfDev dev_of(const egx_sdf_grid& g, const float** bricks) {
-  const SdfDev s = egx_sdf_dev(g);
-  // the tables of egx_sdf_build_coarse are there: gather from the bricked copy
-  *bricks = g.coarse_minmax ? reinterpret_cast<const float*>(static_cast<const char*>(g.coarse_minmax) + egx_sdf_bricks_offset(s.c0, s.c1, s.c2)) : nullptr;
-  return s;
-}
-
 constexpr int MAX_POINTS_PER_BODY = 1 << 20;
 
 // shared argument checks of the two penalty calls; fills the field and the instantiation to launch
@@ -304,13 +258,13 @@ int penalty_field(const egx_sdf_grid* sdf, const egx_sdf_scene_set* scenes, cons
   *f = PenaltyField{};
   f->fpa = fpa;
   if (sdf) {
-    EGX_REQUIRE(grid_ok(sdf), "sdf grid needs d2 >= 2 and fewer than 2^32 samples");
-    f->s = dev_of(*sdf, &f->bricks);
+    EGX_REQUIRE(egx_sdf_grid_ok(sdf), "sdf grid needs d2 >= 2 and fewer than 2^32 samples");
+    f->s = egx_sdf_dev(*sdf);
+    f->bricks = egx_sdf_bricks(*sdf);   // the tables of egx_sdf_build_coarse are there: gather from the bricked copy
     *mode = f->bricks ? BRICKS : ROWMAJOR;
   } else {
     EGX_REQUIRE(agent_scene && scenes->S >= 1 && scenes->table, "a scene set needs agent_scene");
-    const float* unused;
-    f->s = dev_of(scenes->dims, &unused);   // the scenes of a set carry their tables (egx_sdf_scene_set_create)
+    f->s = egx_sdf_dev(scenes->dims);   // the scenes of a set carry their tables (egx_sdf_scene_set_create)
     f->table = scenes->table;
     f->agent_scene = agent_scene;
     f->n_scenes = scenes->S;
@@ -319,15 +273,23 @@ int penalty_field(const egx_sdf_grid* sdf, const egx_sdf_scene_set* scenes, cons
   }
   return EGX_OK;
 }
+
+// launch(mode as an std::integral_constant) for the mode penalty_field chose: the three instantiations of a penalty kernel
+template <typename Launch>
+void with_penalty_mode(int mode, Launch&& launch) {
+  if (mode == ROWMAJOR) launch(std::integral_constant<int, ROWMAJOR>{});
+  else if (mode == BRICKS) launch(std::integral_constant<int, BRICKS>{});
+  else launch(std::integral_constant<int, SCENE_SET>{});
+}
 }  // namespace
 
 extern "C" int egx_sdf_value_grad(const egx_sdf_grid* sdf, const float* pts, int64_t n, const float* cotangent, float* out_val,
                                   float* out_grad, void* stream_) {
-  EGX_REQUIRE(grid_ok(sdf), "sdf grid needs d2 >= 2 and fewer than 2^32 samples");
+  EGX_REQUIRE(egx_sdf_grid_ok(sdf), "sdf grid needs d2 >= 2 and fewer than 2^32 samples");
   if (n == 0) return EGX_OK;  // empty input is legal
   EGX_REQUIRE(pts && out_grad && n > 0, "null points / gradient output");
-  const float* bricks;
-  const SdfDev s = dev_of(*sdf, &bricks);
+  const SdfDev s = egx_sdf_dev(*sdf);
+  const float* bricks = egx_sdf_bricks(*sdf);
   const int64_t blocks = (n + 256 * EGX_SDF_GRAD_PPT - 1) / (256 * EGX_SDF_GRAD_PPT);
   const int grid = (int)(blocks < 8192 ? blocks : 8192);
   hipStream_t st = static_cast<hipStream_t>(stream_);
@@ -348,15 +310,10 @@ extern "C" int egx_sdf_penalty_forward(const egx_sdf_grid* sdf, const egx_sdf_sc
   EGX_REQUIRE(out_penalty, "null penalty output");
   hipStream_t st = static_cast<hipStream_t>(stream_);
   const dim3 grid(num_bodies), block(256);
-  if (mode == ROWMAJOR)
-    hipLaunchKernelGGL(egx_sdf_penalty_forward_kernel<ROWMAJOR>, grid, block, 0, st, f, pts, points_per_body, weights, margin, power,
+  with_penalty_mode(mode, [&](auto m) {
+    hipLaunchKernelGGL(egx_sdf_penalty_forward_kernel<decltype(m)::value>, grid, block, 0, st, f, pts, points_per_body, weights, margin, power,
                        out_penalty, out_count);
-  else if (mode == BRICKS)
-    hipLaunchKernelGGL(egx_sdf_penalty_forward_kernel<BRICKS>, grid, block, 0, st, f, pts, points_per_body, weights, margin, power,
-                       out_penalty, out_count);
-  else
-    hipLaunchKernelGGL(egx_sdf_penalty_forward_kernel<SCENE_SET>, grid, block, 0, st, f, pts, points_per_body, weights, margin, power,
-                       out_penalty, out_count);
+  });
   EGX_HIP_CHECK(hipGetLastError());
   return EGX_OK;
 }
@@ -372,15 +329,10 @@ extern "C" int egx_sdf_penalty_backward(const egx_sdf_grid* sdf, const egx_sdf_s
   const int runs = egx_ceil_div(points_per_body, EGX_SDF_GRAD_PPT * 256);
   const int64_t items = (int64_t)num_bodies * runs;
   const dim3 grid((unsigned)(items < 16384 ? items : 16384)), block(256);
-  if (mode == ROWMAJOR)
-    hipLaunchKernelGGL(egx_sdf_penalty_backward_kernel<ROWMAJOR>, grid, block, 0, st, f, pts, points_per_body, runs, items, weights, margin,
-                       power, grad_penalty, grad_pts);
-  else if (mode == BRICKS)
-    hipLaunchKernelGGL(egx_sdf_penalty_backward_kernel<BRICKS>, grid, block, 0, st, f, pts, points_per_body, runs, items, weights, margin,
-                       power, grad_penalty, grad_pts);
-  else
-    hipLaunchKernelGGL(egx_sdf_penalty_backward_kernel<SCENE_SET>, grid, block, 0, st, f, pts, points_per_body, runs, items, weights, margin,
-                       power, grad_penalty, grad_pts);
+  with_penalty_mode(mode, [&](auto m) {
+    hipLaunchKernelGGL(egx_sdf_penalty_backward_kernel<decltype(m)::value>, grid, block, 0, st, f, pts, points_per_body, runs, items, weights,
+                       margin, power, grad_penalty, grad_pts);
+  });
   EGX_HIP_CHECK(hipGetLastError());
   return EGX_OK;
 }

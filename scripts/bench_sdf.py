@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""K2 of SURVEY 8(d): the standalone `calc_sdf` (crowd_ppo/utils.py:54-84 -> egogen_amd.utils.calc_sdf -> egx_sdf_sample_kernel)
+"""K2 of SURVEY 8(d): the standalone `calc_sdf` (crowd_ppo/utils.py:54-84 -> egogen_amd.utils.calc_sdf -> egx_sdf_sample_kernel<FROM_BRICKS>)
 at configs[1] scale - 64 agents x 20 frames x 10 475 vertices = 13.4 M points in the 256^3 single-box grid.
 
 Algorithmic bytes: 16 B / point (12 B of coordinates in, 4 B of value out); the 64 MiB grid is a gather target that mostly lives
@@ -53,7 +53,7 @@ def bricks(pts, out):
 for name, pts in (("bodies", verts), ("uniform", uni)):
     n = pts.shape[0] * pts.shape[1]
     ref = None
-    for kname, fn in (("row-major grid (egx_sdf_sample_kernel)", gather), ("4x4x4 bricks (egx_sdf_sample_bricks_kernel)", bricks)):
+    for kname, fn in (("row-major grid (egx_sdf_sample_kernel<false>)", gather), ("4x4x4 bricks (egx_sdf_sample_kernel<true>)", bricks)):
         out = torch.empty(pts.shape[0], pts.shape[1], device="cuda")
         for _ in range(5):
             fn(pts, out)

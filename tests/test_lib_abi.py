@@ -26,6 +26,17 @@ def test_header_symbols_all_bound_and_exported():
     assert lib.egx_version() >= 1
 
 
+@pytest.mark.parametrize("dims,nbytes", [((7, 5, 2), 2048), ((9, 6, 5), 4352), ((37, 50, 23), 212480), ((256, 256, 256), 69576192),
+                                         ((0, 5, 2), 0), ((7, -1, 2), 0), ((7, 5, 0), 0)])
+def test_sdf_table_layout_is_pinned(dims, nbytes):
+    """egx_sdf_coarse_bytes (a host function: no device needed) is the end of the last part of a grid's tables - brackets,
+    pyramid, aux floats, bricks, each 256-byte aligned - so its value moves with any change of that layout.  The literals were
+    recorded from the library before the layout got its one host view; (7, 5, 2) by hand: 4*4*3 brackets of 8 bytes -> 512,
+    8+1+1+1 pyramid floats -> 768, 64 aux floats -> 1024, 2*2*1 bricks of 256 bytes -> 2048.  A non-positive dimension has no tables."""
+    from egogen_amd import _lib
+    assert _lib.load().egx_sdf_coarse_bytes(*dims) == nbytes
+
+
 def test_product_does_not_import_oracle():
     """The oracle is test infrastructure: nothing under egogen_amd/ or crowd_ppo/ may reference it."""
     bad = []
