@@ -256,6 +256,7 @@ SIGNATURES = {
     "egx_policy_train_step_heads": (C.c_int, [C.c_void_p] * 9 + [C.c_float] * 6 + [C.c_void_p, C.c_void_p]),
     "egx_policy_train_step_encoders": (C.c_int, [C.c_void_p, C.c_void_p]),
     "egx_policy_train_set_precision": (C.c_int, [C.c_void_p, C.c_int]),
+    "egx_policy_train_dense3_launches": (C.c_int, [C.c_void_p]),
     "egx_policy_train_head": (C.c_int, [C.c_void_p, C.POINTER(UpdateHead), C.c_void_p]),
     "egx_policy_train_step_cursor": (C.c_int, [C.c_void_p, C.POINTER(UpdateHead), C.c_void_p] + [C.c_float] * 6 + [C.c_void_p]),
     "egx_policy_train_step_heads_cursor": (C.c_int, [C.c_void_p, C.POINTER(UpdateHead), C.c_void_p] + [C.c_float] * 6 + [C.c_void_p]),

@@ -121,8 +121,8 @@ static __device__ __forceinline__ void d3_mma_tiles(const bf16x8 (&fa)[MI][NPL],
 template <class T>
 static __device__ __forceinline__ D3_GLOBAL T* d3_g(T* p) { return (D3_GLOBAL T*)p; }
 
-// The layer a block works on, of the several a launch carries (D3Args4, D3Gru2).  Picking one of the structs by reference
-// (`which == 0 ? four.p0 : ...`) makes the compiler copy all of the kernel arguments to scratch in every wave and read the
+// The layer a block works on, of the several a launch carries (D3ArgsN, D3Gru2).  Picking one of the structs by reference
+// (`which == 0 ? args.p[0] : ...`, or `args.p[which]`) makes the compiler copy all of the kernel arguments to scratch in every wave and read the
 // fields back with vector loads; selecting field by field keeps them in SGPRs but loads all of the structs, or reads each field
 // where it is first used - a scalar round trip in the middle of the epilogue.  Reading the one struct straight from the
 // kernel-argument segment (constant address space, uniform offset: scalar loads, all at the top of the kernel) touches only

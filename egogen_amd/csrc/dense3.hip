@@ -67,31 +67,40 @@ __device__ __forceinline__ void d3_write_packed(const D3Plain& a, const float* t
 
 // ---------------------------------------------------------------------------------------------------------
 // plain layer: out = act(A B^T + bias) + res for a 32 x 32 output tile per workgroup, the reduction split over the four
-// waves; up to three independent layers may share a launch.
+// waves; up to EGX_DENSE3_MAX independent layers may share a launch.
 // ---------------------------------------------------------------------------------------------------------
-struct D3Args4 {
-  D3Plain p0, p1, p2, p3;
-  int end0, end1, end2;   // blocks [0, end0) work on p0, [end0, end1) on p1, [end1, end2) on p2, the rest on p3
+struct D3ArgsN {
+  D3Plain p[EGX_DENSE3_MAX];
+  int end[EGX_DENSE3_MAX];   // blocks [end[i - 1], end[i]) work on p[i] (from 0 for p[0]); unused slots end where the grid ends
   int rowmap;
 };
 
 // d3_kernarg reads the block's layer as element `which` of an array of D3Plain at the start of the kernel-argument segment
-static_assert(offsetof(D3Args4, p0) == 0 && offsetof(D3Args4, p1) == sizeof(D3Plain), "layout");
+static_assert(offsetof(D3ArgsN, p) == 0 && sizeof(D3Plain) % 8 == 0, "layout");
+static_assert(sizeof(D3ArgsN) <= 4096, "kernel-argument segment limit");
 
 // MI x NI MFMA tiles of 16 x 16 per workgroup of NW waves (instantiated: 2 x 2 tiles; four waves, eight for 9..16 k-steps).
 template <int TRIP, int MI, int NI, int NW, int NPL>
-__global__ __launch_bounds__(64 * NW) void egx_dense3_kernel(D3Args4 four) {
+__global__ __launch_bounds__(64 * NW) void egx_dense3_kernel(D3ArgsN args) {
   constexpr int TM = 16 * MI, TN = 16 * NI, NACC = MI * NI * 4, PITCH = TN + 4;
   const int bx = (int)blockIdx.x;
-  const int which = bx < four.end0 ? 0 : (bx < four.end1 ? 1 : (bx < four.end2 ? 2 : 3));
+  // the ends are constant-indexed fields of the argument block: scalar loads and scalar compares, nothing per lane.  (Leaving
+  // after the first three ends when the block lies before the fourth - every launch of up to four layers - was measured and
+  // is not faster: profiles/update_tail.md.)
+  int which = 0, first = 0;
+#pragma unroll
+  for (int i = 0; i + 1 < EGX_DENSE3_MAX; ++i) {
+    const int e = args.end[i];
+    if (bx >= e) { which = i + 1; first = e; }
+  }
   const D3Plain a = d3_kernarg<D3Plain>(which);
-  const int bid = bx - (which == 0 ? 0 : (which == 1 ? four.end0 : (which == 2 ? four.end1 : four.end2)));
+  const int bid = bx - first;
   extern __shared__ __attribute__((aligned(16))) float d3_smem[];
   float* red = d3_smem;                      // [NW waves][NACC][64]
   float* tile = d3_smem + NW * NACC * 64;    // [TM][PITCH]
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int MT = (a.M + TM - 1) / TM, NT = (a.N + TN - 1) / TN;
-  const int rowmap = d3_rowmap(four.rowmap, a.M, a.N);
+  const int rowmap = d3_rowmap(args.rowmap, a.M, a.N);
   const int per_batch = d3_blocks(MT, NT, rowmap);
   const int batch = bid / per_batch;
   int mt, nt;
@@ -207,16 +216,14 @@ void d3_launch_cfg(hipStream_t st, const D3Plain* ps, int n) {
   constexpr int TM = 16 * MI, TN = 16 * NI;
   constexpr size_t lds = (size_t)(NW * MI * NI * 4 * 64 + TM * (TN + 4)) * sizeof(float);
   static_assert(lds <= 64 * 1024, "within the default dynamic-LDS cap (above it: d3_raise_lds_cap)");
-  D3Args4 f;
+  D3ArgsN f;
   f.rowmap = -1;   // the M >= N rule of d3_rowmap
-  D3Plain* dst[4] = {&f.p0, &f.p1, &f.p2, &f.p3};
-  int ends[4] = {0, 0, 0, 0}, total = 0;
-  for (int i = 0; i < 4; ++i) {
-    *dst[i] = ps[i < n ? i : n - 1];
+  int total = 0;
+  for (int i = 0; i < EGX_DENSE3_MAX; ++i) {
+    f.p[i] = ps[i < n ? i : n - 1];
     if (i < n) total += d3_blocks(egx_ceil_div(ps[i].M, TM), egx_ceil_div(ps[i].N, TN), d3_rowmap(-1, ps[i].M, ps[i].N)) * std::max(1, ps[i].batches);
-    ends[i] = total;
+    f.end[i] = total;
   }
-  f.end0 = ends[0]; f.end1 = ends[1]; f.end2 = ends[2];
   hipLaunchKernelGGL((egx_dense3_kernel<TRIP, MI, NI, NW, NPL>), dim3(total), dim3(64 * NW), lds, st, f);
 }
 // the three configurations of one arithmetic mode; DEEP_TRIP: k-steps per operand round trip of the deep one
@@ -233,21 +240,30 @@ void d3_launch_mode(hipStream_t st, const D3Plain* ps, int n, bool wide, bool de
 // (Measured for the update's 1152-deep layers, profiles/r03_update_experiments.md: 64 x 64 and 64 x 32 tiles, eight-wave
 // split-K, a software-pipelined loop and two k-steps per trip all land within a few per cent of this form or behind it.)
 // All layers of a launch share the arithmetic mode of the first (the callers build them from one setting).
-void egx_launch_dense3_n(hipStream_t st, const D3Plain* ps, int n) {
+// The configuration follows from the launch as a whole (its deepest reduction, its tile count), so a product's kernel - and with
+// it the split of its reduction over the waves, i.e. its bits - depends on its companions: a caller that merges launches and
+// must keep results asks here first (update3.hip).
+int egx_dense3_config(const D3Plain* ps, int n) {
   int smax = 0, tiles = 0;
   for (int i = 0; i < n; ++i) {
     smax = std::max(smax, ps[i].S);
     tiles += egx_ceil_div(ps[i].M, 32) * egx_ceil_div(ps[i].N, 32) * std::max(1, ps[i].batches);
   }
-  const bool deep = smax > 16;
+  if (smax > 16) return EGX_DENSE3_DEEP;
   // 9..16 k-steps: eight waves take two k-steps each, ONE operand round trip (four waves need two) - for a latency-bound launch:
   // at most two workgroups per CU
-  const bool wide = smax > 8 && !deep && tiles <= 512;
+  return smax > 8 && tiles <= 512 ? EGX_DENSE3_WIDE : EGX_DENSE3_BASE;
+}
+int egx_launch_dense3_n(hipStream_t st, const D3Plain* ps, int n) {
+  EGX_REQUIRE(ps && n >= 1 && n <= EGX_DENSE3_MAX, "1 to EGX_DENSE3_MAX products per launch");
+  const int cfg = egx_dense3_config(ps, n);
+  const bool deep = cfg == EGX_DENSE3_DEEP, wide = cfg == EGX_DENSE3_WIDE;
   switch (ps[0].prec) {
     case 2: d3_launch_mode<2, 3>(st, ps, n, wide, deep); break;
     case 1: d3_launch_mode<1, 5>(st, ps, n, wide, deep); break;
     default: d3_launch_mode<3, 3>(st, ps, n, wide, deep);
   }
+  return EGX_OK;
 }
 void egx_launch_dense3(hipStream_t st, const D3Plain& p) { egx_launch_dense3_n(st, &p, 1); }
 void egx_launch_dense3_pair(hipStream_t st, const D3Plain& p, const D3Plain& q) {

@@ -66,7 +66,11 @@ struct D3Plain {
   float* bias_out = nullptr;      // n_split > 0: columns >= n_split are not stored to `out`; column n_split goes to bias_out[m]
   int n_split = 0;
 };
-void egx_launch_dense3_n(hipStream_t st, const D3Plain* ps, int n);   // up to four independent layers, one launch
+constexpr int EGX_DENSE3_MAX = 12;   // independent layers per launch (their D3Plain travel in the kernel-argument segment)
+int egx_launch_dense3_n(hipStream_t st, const D3Plain* ps, int n);   // 1 .. EGX_DENSE3_MAX independent layers, one launch
+// the kernel configuration egx_launch_dense3_n picks for these layers as ONE launch
+enum { EGX_DENSE3_BASE = 0, EGX_DENSE3_DEEP = 1, EGX_DENSE3_WIDE = 2 };
+int egx_dense3_config(const D3Plain* ps, int n);
 void egx_launch_dense3(hipStream_t st, const D3Plain& p);
 void egx_launch_dense3_pair(hipStream_t st, const D3Plain& p, const D3Plain& q);  // two independent layers, one launch
 void egx_launch_dense3_triple(hipStream_t st, const D3Plain& p, const D3Plain& q, const D3Plain& r);

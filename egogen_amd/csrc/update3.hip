@@ -9,9 +9,10 @@
 //             gradient one more output column; input- and weight-gradient products of the actor AND the critic share a launch;
 //   GRU       cell forward = one launch per time step for both encoders (dense3 gru kernel), cell backward = one launch per
 //             step producing the gate gradients directly as packed images.
-// 22 launches per minibatch (egx_update_head_kernel first) instead of ~85.  Gradients are WRITTEN (not accumulated) into the flat
+// 19 launches per minibatch (egx_update_head_kernel first) instead of ~85.  Gradients are WRITTEN (not accumulated) into the flat
 // gradient buffer - every parameter is used exactly once per minibatch - so the buffer needs no zero fill.
 #include <algorithm>
+#include <cstdlib>
 #include <cstring>
 #include <vector>
 #include "d3.h"
@@ -345,6 +346,8 @@ struct egx_policy_train {
   std::vector<PackEntry> h_inputs;   // host copy: the source pointers of the observation change per call
   const float* bound_state = nullptr; const float* bound_ego = nullptr;
   int prec = 0;   // arithmetic of every product of the chain (D3Plain::prec): egx_policy_train_set_precision
+  int dense3_launches = 0;   // egx_dense3_kernel launches of the last step call (egx_policy_train_dense3_launches)
+  bool merge = true;   // independent products of the backward pass share launches (EGX_UPDATE_MERGE=0 at creation: the old sequence)
 };
 
 namespace {
@@ -418,6 +421,7 @@ extern "C" int egx_policy_train_create(const egx_policy_weights* w, const egx_po
   EGX_REQUIRE(num_rows > 0 && num_rows % 32 == 0, "the minibatch must be a multiple of 32 rows");
   auto* h = new egx_policy_train();
   h->n = num_rows; h->Sn = num_rows / 32;
+  if (const char* e = getenv("EGX_UPDATE_MERGE")) h->merge = !(e[0] == '0' && e[1] == 0);
   Encoder& X = h->enc[0];
   X.Wih = w->x_enc_w_ih; X.Whh = w->x_enc_w_hh; X.bih = w->x_enc_b_ih; X.bhh = w->x_enc_b_hh;
   X.gWih = g->x_enc_w_ih; X.gWhh = g->x_enc_w_hh; X.gbih = g->x_enc_b_ih; X.gbhh = g->x_enc_b_hh;
@@ -537,6 +541,8 @@ extern "C" int egx_policy_train_set_precision(egx_policy_train* h, int prec) {
   return EGX_OK;
 }
 
+extern "C" int egx_policy_train_dense3_launches(const egx_policy_train* h) { return h ? h->dense3_launches : -1; }
+
 extern "C" int egx_policy_train_packed(const egx_policy_train* h, egx_policy_packed3* out) {
   EGX_REQUIRE(h && out, "null argument");
   out->x_enc_w_ih = h->enc[0].Wih_r; out->x_enc_w_hh = h->enc[0].Whh_r;
@@ -575,9 +581,26 @@ struct StepIn {
   const egx_update_head* hd = nullptr;
 };
 
-void launch_n(const egx_policy_train* h, hipStream_t st, D3Plain* ps, int cnt) {
+void launch_n(egx_policy_train* h, hipStream_t st, D3Plain* ps, int cnt) {
   for (int i = 0; i < cnt; ++i) ps[i].prec = h->prec;
-  egx_launch_dense3_n(st, ps, cnt);
+  ++h->dense3_launches;
+  (void)egx_launch_dense3_n(st, ps, cnt);   // cnt <= EGX_DENSE3_MAX by the sizes of the callers' arrays
+}
+// Consecutive groups of independent products, cnt[g] each, as few launches as keep the results: a product's kernel configuration -
+// its split of the reduction over the waves, hence its bits - is chosen per launch (egx_dense3_config), so a group joins the launch
+// of the groups before it only where its own launch and the joint one pick the same configuration (at 256 rows every one does; from
+// 288 rows on the GRU weight gradients run the deep configuration and stay a launch of their own).  Without h->merge: one launch per
+// group, the sequence before the merge.
+void launch_groups(egx_policy_train* h, hipStream_t st, D3Plain* ps, const int* cnt, int groups) {
+  for (int g = 0; g < groups;) {
+    int len = cnt[g++];
+    const int cfg = egx_dense3_config(ps, len);
+    while (h->merge && g < groups && len + cnt[g] <= EGX_DENSE3_MAX && egx_dense3_config(ps + len, cnt[g]) == cfg &&
+           egx_dense3_config(ps, len + cnt[g]) == cfg)
+      len += cnt[g++];
+    launch_n(h, st, ps, len);
+    ps += len;
+  }
 }
 
 int head_args_ok(const egx_policy_train* h, const egx_update_head* a) {
@@ -689,19 +712,21 @@ int step_loss(egx_policy_train* h, const StepIn& in, hipStream_t st) {
 // cells); each layer's weight-gradient product follows the launch that left its gradient image behind.  (Weight gradients on a
 // second stream beside the chain, and fused into the input-gradient launches, were both measured and are not faster:
 // profiles/r03_update_experiments.md.)
-void step_blocks_bwd(egx_policy_train* h, hipStream_t st) {
+// `WL`: the eight weight-gradient products of the layers, left to the caller with `defer_wl` (train_step_parts).
+void step_blocks_bwd(egx_policy_train* h, hipStream_t st, D3Plain* WL, bool defer_wl) {
   const int n = h->n, Sn = h->Sn;
   auto wgrad = [&](D3Plain& q, const bf16x8* gT, const bf16x8* xT, int rows, float* gW, float* gb) {
     q = D3Plain();
     q.M = rows; q.N = CAT + 1; q.A = gT; q.SA = Sn; q.S = Sn; q.B = xT; q.out = gW; q.ldo = CAT; q.n_split = CAT; q.bias_out = gb;
   };
-  D3Plain W[2], D[2], WL[8];
+  // the output layer's weight gradients and the l = 4 input gradients below both read only the images of `ghead`: one launch
+  D3Plain first[4];
+  D3Plain *W = first, *D = first + 2;
   for (int b = 0; b < 2; ++b) wgrad(W[b], h->br[b].gheadT, h->br[b].u2T, h->br[b].nout, h->br[b].gWout, h->br[b].gbout);
-  launch_n(h, st, W, 2);
   // Layer l of both blocks, l = 4 being out_fc: the input gradient d = g_l W_l^T-image (+ skip) now, as fp32 `out` raw and as
   // images gated by lrelu'(a_l) = g_(l-1).  Its weight gradient dW_l = g_l^T x_l only needs the images the previous launch left
-  // behind, so the eight weight-gradient products of the four layers go out afterwards as two four-product launches (fewer,
-  // fuller launches: ~10 us of every launch is fixed cost, profiles/r03_update_experiments.md).
+  // behind, so the eight weight-gradient products of the four layers go out afterwards in one launch (fewer, fuller launches:
+  // ~10 us of every launch is fixed cost, profiles/r03_update_experiments.md).
   //   4: du2 = g W_out -> g4    3: d(a3) = g4 W4 -> g3    2: du1 = g3 W3 + du2 -> g2    1: d(a1) = g2 W2 -> g1    0: dhx = g1 W1 + du1
   for (int l = 4; l >= 0; --l) {
     for (int b = 0; b < 2; ++b) {
@@ -720,14 +745,17 @@ void step_blocks_bwd(egx_policy_train* h, hipStream_t st) {
         d.out3 = B.g_r[gate]; d.S3 = S_CAT; d.out3T = B.gT[gate]; d.S3T = Sn;
       }
     }
-    launch_n(h, st, D, 2);
+    const int two[2] = {2, 2};
+    if (l == 4) launch_groups(h, st, first, two, 2);
+    else launch_n(h, st, D, 2);
   }
-  launch_n(h, st, WL, 4);
-  launch_n(h, st, WL + 4, 4);
+  const int four[2] = {4, 4};
+  if (!defer_wl) launch_groups(h, st, WL, four, 2);
 }
 
-// Backward of the two GRU encoders (dhx = actor's + critic's)
-void step_encoders_bwd(egx_policy_train* h, hipStream_t st) {
+// Backward of the two GRU encoders (dhx = actor's + critic's).  `tail`: twelve products, the last four the encoders' weight
+// gradients built here; with `with_wl` the first eight (step_blocks_bwd's deferred ones) go out with them.
+void step_encoders_bwd(egx_policy_train* h, hipStream_t st, D3Plain* tail, bool with_wl) {
   const int n = h->n, Sn = h->Sn;
   GruBwd2 two;
   const int blocks = (n / 32) * (HD / 32);
@@ -741,7 +769,7 @@ void step_encoders_bwd(egx_policy_train* h, hipStream_t st) {
     q.dgiT = E.dgiT; q.dghT = E.dghT; q.ST = 2 * Sn; q.s0T = Sn; q.dgh_r = E.dgh_r; q.dhp = E.dhp; q.M = n; q.H = HD;
   }
   hipLaunchKernelGGL(egx_gru_bwd3_kernel, dim3(2 * blocks), dim3(256), 0, st, two);
-  D3Plain P[4];
+  D3Plain P[2];
   for (int e = 0; e < 2; ++e) {   // dh1 = dh z + dgh2 W_hh
     Encoder& E = h->enc[e];
     D3Plain& d = P[e];
@@ -758,22 +786,27 @@ void step_encoders_bwd(egx_policy_train* h, hipStream_t st) {
   hipLaunchKernelGGL(egx_gru_bwd3_kernel, dim3(2 * blocks), dim3(256), 0, st, two);
   for (int e = 0; e < 2; ++e) {   // dW_ih = [dgi1; dgi2]^T [x0; x1], dW_hh = [dgh1; dgh2]^T [0; h1]; the ones rows give the biases
     Encoder& E = h->enc[e];
-    D3Plain& a = P[2 * e];
+    D3Plain& a = tail[8 + 2 * e];
     a = D3Plain();
     a.M = 3 * HD; a.N = E.in_dim + 1; a.A = E.dgiT; a.SA = 2 * Sn; a.S = 2 * Sn; a.B = E.xT; a.out = E.gWih; a.ldo = E.in_dim;
     a.n_split = E.in_dim; a.bias_out = E.gbih;
-    D3Plain& c = P[2 * e + 1];
+    D3Plain& c = tail[8 + 2 * e + 1];
     c = D3Plain();
     c.M = 3 * HD; c.N = HD + 1; c.A = E.dghT; c.SA = 2 * Sn; c.S = 2 * Sn; c.B = E.hprevT; c.out = E.gWhh; c.ldo = HD;
     c.n_split = HD; c.bias_out = E.gbhh;
   }
-  launch_n(h, st, P, 4);
+  const int four[3] = {4, 4, 4};
+  if (with_wl) launch_groups(h, st, tail, four, 3);
+  else launch_n(h, st, tail + 8, 4);
 }
 
-// Launches of one minibatch (parts = 3): 22 with `in.hd` - head 1 | GRU steps 2, layers 4, output layers 1 | loss 1, its images 1
-// | backward of the blocks 8 (output-layer weight gradients, 5 input gradients, 2 x four weight gradients) | GRU encoders 4 - and
-// 23 without (input images and positional encoding instead of the head; the caller's gather and statistics launches come on
-// top: 25).  parts = 1 ends after the blocks' backward (18 / 19), parts = 2 is the encoders' 4.
+// Launches of one minibatch (parts = 3): 19 with `in.hd` - head 1 | GRU steps 2, layers 4, output layers 1 | loss 1, its images 1
+// | backward of the blocks 5 (output-layer weight gradients with the first of 5 input gradients) | GRU encoders 4, the last of
+// them all twelve weight gradients of the layers and the encoders - and 20 without (input images and positional encoding instead
+// of the head; the caller's gather and statistics launches come on top: 22).  parts = 1 ends after the blocks' backward and their
+// eight weight gradients in one launch (16 / 17) - the heads' half leaves exactly the actor's and the critic's part of the flat
+// gradient final - and parts = 2 is the encoders' 4.  Without h->merge (EGX_UPDATE_MERGE=0, the checker of the merged sequence):
+// 22 / 23, the output-layer weight gradients and the layers' 2 x four as launches of their own, parts = 1 18 / 19.
 int train_step_parts(egx_policy_train* h, const StepIn& in, void* stream_, int parts) {
   {   // egx_last_error() quotes a failed condition: these names are part of its sentences
     const float *dist = in.dist, *time = in.time, *act = in.act, *adv = in.adv, *ret = in.ret, *logp_old = in.logp_old,
@@ -783,14 +816,18 @@ int train_step_parts(egx_policy_train* h, const StepIn& in, void* stream_, int p
     EGX_REQUIRE(hd || !(parts & 1) || h->bound_state, "egx_policy_train_bind has not been called");
   }
   hipStream_t st = static_cast<hipStream_t>(stream_);
+  h->dense3_launches = 0;
   if (parts & 1) {
     step_inputs(h, in, st);
     step_forward(h, st);
     int rc = step_loss(h, in, st);
     if (rc) return rc;
-    step_blocks_bwd(h, st);   // every gradient of the actor and critic blocks is enqueued
   }
-  if (parts & 2) step_encoders_bwd(h, st);
+  static_assert(8 + 4 <= EGX_DENSE3_MAX, "the weight gradients of one launch");
+  D3Plain tail[12];
+  const bool defer_wl = h->merge && parts == 3;
+  if (parts & 1) step_blocks_bwd(h, st, tail, defer_wl);   // parts = 1: every gradient of the actor and critic blocks is enqueued
+  if (parts & 2) step_encoders_bwd(h, st, tail, defer_wl);
   EGX_HIP_CHECK(hipGetLastError());
   return EGX_OK;
 }

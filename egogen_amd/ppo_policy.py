@@ -446,9 +446,10 @@ class GAMMAPPOPolicy(nn.Module):
             self.refresh_counts[who] += 1
 
     def _fwd_bwd_train_step(self, hs, batch, idx, gstats, log_out, part: str = "all", cursor=None):
-        """head + forward + loss + backward of one minibatch: 1 + 21 launches (head | 2 GRU steps, 4 layers, output layers | loss,
-        its images | 12 of the backward), gradients written into the flat buffer; with EGX_UPDATE_HEAD=0 the head is the four
-        launches it used to be (gather, statistics, input images, positional encoding).
+        """head + forward + loss + backward of one minibatch: 1 + 18 launches (head | 2 GRU steps, 4 layers, output layers | loss,
+        its images | 9 of the backward; 12 with EGX_UPDATE_MERGE=0, read by egx_policy_train_create), gradients written into the
+        flat buffer; with EGX_UPDATE_HEAD=0 the head is the four launches it used to be (gather, statistics, input images,
+        positional encoding).
         `part`: "all"; "heads" = everything up to the last actor / critic weight gradient (data-parallel training all-reduces that
         bucket while "encoders" - the GRU encoders' backward - runs).
         `cursor` (head path): int32 device scalar k - the minibatch is rows idx[k n : (k + 1) n] and its loss terms go to row k

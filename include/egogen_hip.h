@@ -627,6 +627,10 @@ int egx_policy_train_step_heads_cursor(egx_policy_train* h, const egx_update_hea
  * of north_star).  fp32 accumulation, biases, activations, loss and all gradients OUTPUTS are fp32 in every mode.  Measured
  * against a float64 evaluation of crowd_ppo/ppo_policy.py:189-241 in tests/test_trainer_gpu.py (profiles/r04_p3_yardstick.txt). */
 int egx_policy_train_set_precision(egx_policy_train* h, int prec);
+/* How many dense-layer launches (egx_dense3_kernel) the handle's last step call enqueued: 12 for a whole minibatch, 15 with
+ * EGX_UPDATE_MERGE=0 in the environment when the handle was created - the sequence before independent products of the backward
+ * pass shared launches, kept as the checker of the merged one (both leave the same bits everywhere). */
+int egx_policy_train_dense3_launches(const egx_policy_train* h);
 
 /* Arithmetic of the dense layers inside egx_policy_forward (process-wide): 0 = fp32-equivalent (default; 1e-4 parity with the
  * reference's fp32 policy), 2 = operands as two bf16 terms (16 significant bits, three partial products), 1 = operands
