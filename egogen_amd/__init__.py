@@ -2,4 +2,7 @@ def __getattr__(name):      # `from egogen_amd import GeodesicField` without imp
     if name == "GeodesicField":
         from .geodesic import GeodesicField
         return GeodesicField
+    if name == "MovingObstacles":
+        from .obstacles import MovingObstacles
+        return MovingObstacles
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

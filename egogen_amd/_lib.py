@@ -217,6 +217,17 @@ SIGNATURES = {
                                         [C.POINTER(C.c_float), C.c_float, C.c_float, C.c_float, C.c_int, C.c_int, C.c_int] +
                                         [C.c_void_p] * 13 +
                                         [C.c_void_p, C.c_void_p, C.c_float, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    # the *_field entries' arguments up to field_index, then: obs_xy, obs_radius, obs_count, obs_index, num_sets, max_obstacles,
+    # num_frames, frame0, obstacle_weight, margin, body_radius, obs_term, obs_clearance, obs_hit, stream
+    "egx_primitive_select_obstacles": (C.c_int, [C.c_void_p] * 3 + [C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 6 +
+                                       [C.POINTER(C.c_float), C.c_float, C.c_float, C.c_float, C.c_int, C.c_int] + [C.c_void_p] * 7 +
+                                       [C.c_void_p, C.c_void_p, C.c_float, C.c_int, C.c_int, C.c_int, C.c_void_p] +
+                                       [C.c_void_p] * 4 + [C.c_int] * 4 + [C.c_float] * 3 + [C.c_void_p] * 4),
+    "egx_primitive_beam_select_obstacles": (C.c_int, [C.c_void_p] * 3 + [C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 6 +
+                                            [C.POINTER(C.c_float), C.c_float, C.c_float, C.c_float, C.c_int, C.c_int, C.c_int] +
+                                            [C.c_void_p] * 13 +
+                                            [C.c_void_p, C.c_void_p, C.c_float, C.c_int, C.c_int, C.c_int, C.c_void_p] +
+                                            [C.c_void_p] * 4 + [C.c_int] * 4 + [C.c_float] * 3 + [C.c_void_p] * 4),
     "egx_sample_action": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_int, C.c_int, C.c_void_p,
                                     C.c_void_p, C.c_void_p]),
     "egx_gae": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double, C.c_void_p,

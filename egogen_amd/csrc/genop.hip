@@ -5,8 +5,10 @@
 // to the N rows of its slot (one workgroup per slot, R0 / T0 from one buffer into another), egx_beam_backtrack gathers the
 // records of the returned path.  With a geodesic field (egx_primitive_select_field, egx_primitive_beam_select_field; geodesic.hip
 // builds it) the goal term of both selections is the field's distance along the walkable raster (field_row_cost, a phase after
-// the scoring); the entries without a field launch the same kernels with a null field.  Device code is shared (advance_body,
-// score_group, key_before); so is the host side: the three hand-off entries go through advance_entry and the selection entries
+// the scoring); the entries without a field launch the same kernels with a null field.  With moving obstacles
+// (egx_primitive_select_obstacles, egx_primitive_beam_select_obstacles; egx_obstacles.h) a third phase adds the obstacle term to
+// the cost and the hit to the collision of every row (obstacle_group); the other entries launch the same kernels with a null
+// obstacle descriptor.  Device code is shared (advance_body, score_group, field_row_cost, obstacle_group, key_before); so is the host side: the three hand-off entries go through advance_entry and the selection entries
 // through select_entry (common checks, common fields, launch check), and each entry states only the checks, fields and launch
 // that are its own.
 //
@@ -17,6 +19,7 @@
 #include "egx_common.h"
 #include "egx_frame.h"
 #include "egx_geodesic.h"
+#include "egx_obstacles.h"
 #include "egx_reward.h"
 
 namespace {
@@ -350,9 +353,59 @@ __device__ __forceinline__ float field_row_cost(const SelectArgs& p, int g, size
   return cost;
 }
 
+__device__ __forceinline__ float wave_min(float v) {   // every lane's partner chain ends in lane 0; min is order-free
+  for (int o = 32; o > 0; o >>= 1) v = fminf(v, __shfl_down(v, o, 64));
+  return v;
+}
+
+// The obstacle term and veto of a launch with obstacles: a phase of its own after score_group's closing barrier and after the
+// field phase, for the reason field_row_cost states.  The workgroup stages the window of group g's set into LDS once (every row
+// of a group shares the time window and the set), then a wave takes one row at a time: lanes 0..17 one predicted frame each
+// (t = lane + 2; the world xy of the frame's pelvis with field_row_cost's nesting, then the obstacles in LDS), the frame sum by
+// the fixed wave_sum tree, divided by 18; clearance by wave_min.  Lane 0 writes obs_term / obs_clearance / obs_hit and the row's
+// cost = cost_prev + w_obs * term (cost_prev read back: what the launch wrote so far), both rounded on their own, and hands
+// (n, row, term, cost, hit) to update(), which redoes the LDS key tables of the row.  Ends on a barrier.
+template <class Update>
+__device__ __forceinline__ void obstacle_group(const SelectArgs& p, const ObstaclesDev& ob, int g, int M, Update update) {
+  __shared__ float s_ox[EGX_OBS_FRAMES][EGX_MAX_OBSTACLES], s_oy[EGX_OBS_FRAMES][EGX_MAX_OBSTACLES], s_rr[EGX_MAX_OBSTACLES];
+  const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
+  const int cnt = egx_obstacles_stage(ob, g, s_ox, s_oy, s_rr);
+  __syncthreads();
+  for (int n = w; n < M; n += SEL_WAVES) {
+    const size_t row = (size_t)g * M + n;
+    float c = __builtin_inff(), pen = 0.f;
+    int bad = 0;
+    if (lane < EGX_OBS_FRAMES) {
+      const float* R0 = p.R0 + row * 9;
+      const float* T0 = p.T0 + row * 3;
+      const float* j = p.joints + (row * NT + THIS + lane) * p.jpb * 3;
+      const float x = fmaf(R0[2], j[2], fmaf(R0[1], j[1], R0[0] * j[0])) + T0[0];
+      const float y = fmaf(R0[5], j[2], fmaf(R0[4], j[1], R0[3] * j[0])) + T0[1];
+      c = egx_obstacle_clearance(x, y, cnt, s_ox[lane], s_oy[lane], s_rr);
+      bad = isnan(c) ? 1 : 0;
+      pen = bad ? c : fmaxf(0.f, egx_sub(ob.margin, c));
+    }
+    const float sum = wave_sum(pen);                       // NaN where a frame is NaN
+    const float cmin = wave_min(bad ? __builtin_inff() : c);
+    const int any_bad = wave_max(bad);
+    if (lane == 0) {
+      const float term = sum / (float)EGX_OBS_FRAMES;
+      const float clearance = any_bad ? __builtin_nanf("") : cmin;
+      const bool hit = clearance < 0.f;                    // false for NaN
+      const float cost = egx_add(p.cost[row], egx_mul(ob.w, term));
+      ob.term[row] = term;
+      ob.clearance[row] = clearance;
+      ob.hit[row] = hit ? 1 : 0;
+      p.cost[row] = cost;
+      update(n, row, term, cost, hit);
+    }
+  }
+  __syncthreads();
+}
+
 }  // namespace
 
-__global__ __launch_bounds__(SEL_BLK) void egx_primitive_select_kernel(SelectArgs p) {
+__global__ __launch_bounds__(SEL_BLK) void egx_primitive_select_kernel(SelectArgs p, ObstaclesDev ob) {
   __shared__ float s_feet[SEL_WAVES][NT][NF * 3];   // blended feet markers of the row a wave is scoring
   __shared__ float s_cost[MAXC], s_dist[MAXC];
   __shared__ int s_cls[MAXC];
@@ -371,6 +424,14 @@ __global__ __launch_bounds__(SEL_BLK) void egx_primitive_select_kernel(SelectArg
     }
     __syncthreads();
   }
+  if (ob.term)                                 // workgroup-uniform; the costs of the rows are visible: a barrier precedes
+    obstacle_group(p, ob, g, N, [&](int n, size_t row, float term, float c, bool hit) {
+      const bool finite = !(s_cls[n] & 2) && isfinite(term) && isfinite(c);
+      const int coll = (s_cls[n] & 1) | (hit ? 1 : 0);
+      p.colliding[row] = coll;
+      s_cost[n] = finite ? c : 0.f;
+      s_cls[n] = (finite ? 0 : 2) | coll;
+    });
 
   if (w == 0) {
     int bc = 4, bi = 0x7fffffff;
@@ -396,7 +457,7 @@ __global__ __launch_bounds__(SEL_BLK) void egx_primitive_select_kernel(SelectArg
 // One workgroup per sequence scores its W * N rows as above, then every row counts the rows whose path key precedes its own:
 // (non-finite, colliding nodes on the path, accumulated cost, row index) is a total order, so that count is the row's rank
 // whatever the order of the comparisons, and the rows of rank < W are the beam, slot = rank.
-__global__ __launch_bounds__(SEL_BLK) void egx_primitive_beam_select_kernel(SelectArgs p, BeamArgs q) {
+__global__ __launch_bounds__(SEL_BLK) void egx_primitive_beam_select_kernel(SelectArgs p, BeamArgs q, ObstaclesDev ob) {
   __shared__ float s_feet[SEL_WAVES][NT][NF * 3];
   __shared__ float s_path[MAXC], s_q[MAXC], s_dist[MAXC];   // path cost (0 where non-finite), q and dist of every row
   __shared__ int s_key[MAXC], s_flag[MAXC];                 // (non-finite, colliding nodes) in one int; bit 0 collides, bit 1 non-finite
@@ -425,6 +486,19 @@ __global__ __launch_bounds__(SEL_BLK) void egx_primitive_beam_select_kernel(Sele
     }
     __syncthreads();
   }
+  if (ob.term)                                 // as in the greedy kernel; q gains the product the cost gained, a hit is a colliding node
+    obstacle_group(p, ob, g, M, [&](int n, size_t row, float term, float c, bool hit) {
+      const bool row_finite = !(s_flag[n] & 2) && isfinite(term) && isfinite(c);
+      const float path = q.acc[(size_t)g * W + n / N] + (row_finite ? c : 0.f);
+      const bool finite = row_finite && isfinite(path);
+      const int coll = (s_flag[n] & 1) | (hit ? 1 : 0);
+      const int nc = min(max(q.ncoll[(size_t)g * W + n / N] + coll, 0), NONFINITE_KEY - 1);
+      p.colliding[row] = coll;
+      s_q[n] = egx_add(s_q[n], egx_mul(ob.w, term));
+      s_path[n] = finite ? path : 0.f;
+      s_key[n] = finite ? nc : NONFINITE_KEY + nc;
+      s_flag[n] = coll | (finite ? 0 : 2);
+    });
 
   if (tid < M) {
     const int kc = s_key[tid];
@@ -530,14 +604,15 @@ int advance_entry(const float* pred_params, const float* Y_gen, const float* x0,
   return EGX_OK;
 }
 
-// The same for the two selection entries, for num_sequences groups of `group_rows` rows; `launch` sets the per-group outputs of
-// the greedy selection (null unless set; the beam's are in BeamArgs) and launches.
+// The same for the selection entries, for num_sequences groups of `group_rows` rows; `launch` sets the per-group outputs of
+// the greedy selection (null unless set; the beam's are in BeamArgs) and launches with the obstacle descriptor it is handed: `obs`
+// checked, or a null one (no phase) where obs is null.
 template <class Launch>
 int select_entry(const float* Y_gen, const float* x0, const float* x1, int x_ld, const float* joints, int joints_per_body,
                  const float* markers_proj, const float* R0, const float* T0, const int32_t* pene_count, const float* goal,
                  const int32_t* feet_marker_idx, const float* weights, float pene_thres, float goal_thresh, float reproj_factor,
                  int num_sequences, int group_rows, float* cost, float* cost_terms, int32_t* colliding, const GeoFieldDev& field,
-                 Launch launch) {
+                 const ObstaclesDev* obs, Launch launch) {
   EGX_REQUIRE(Y_gen && x0 && x1 && joints && markers_proj && R0 && T0 && goal && feet_marker_idx && weights, "null input");
   EGX_REQUIRE(cost && cost_terms && colliding, "null output");
   EGX_REQUIRE(num_sequences > 0 && joints_per_body >= 3, "need a non-empty batch and >= 3 joints per body");
@@ -555,9 +630,56 @@ int select_entry(const float* Y_gen, const float* x0, const float* x1, int x_ld,
   p.rows = num_sequences * group_rows; p.N = group_rows; p.jpb = joints_per_body; p.x_ld = x_ld;
   p.cost = cost; p.terms = cost_terms; p.colliding = colliding;
   if (field.dist) p.field = field;
-  launch(p);
+  ObstaclesDev ob{};
+  if (obs) {
+    EGX_REQUIRE(obs->term && obs->clearance && obs->hit, "null obstacle output");
+    EGX_REQUIRE(obs->O_max >= 0 && obs->O_max <= EGX_MAX_OBSTACLES, "max_obstacles must be in [0, EGX_MAX_OBSTACLES]");
+    EGX_REQUIRE(obs->O_max == 0 || (obs->xy && obs->radius && obs->count), "obstacles need obs_xy, obs_radius and obs_count");
+    EGX_REQUIRE(obs->T >= 1 && obs->S >= 1, "num_frames and num_sets must be at least 1");
+    EGX_REQUIRE(obs->margin >= 0.f && obs->body_radius >= 0.f, "margin and body_radius must not be negative");
+    ob = *obs;
+  }
+  launch(p, ob);
   EGX_HIP_CHECK(hipGetLastError());
   return EGX_OK;
+}
+
+// the greedy selection behind egx_primitive_select, _select_field and _select_obstacles: its own checks, then select_entry
+int greedy_select(const float* Y_gen, const float* x0, const float* x1, int x_ld, const float* joints, int joints_per_body,
+                  const float* markers_proj, const float* R0, const float* T0, const int32_t* pene_count, const float* goal,
+                  const int32_t* feet_marker_idx, const float* weights, float pene_thres, float goal_thresh, float reproj_factor,
+                  int num_sequences, int num_candidates, int32_t* choice, int32_t* status, int32_t* reached, float* goal_dist, float* cost,
+                  float* cost_terms, int32_t* colliding, const GeoFieldDev& field, const ObstaclesDev* obs, void* stream) {
+  EGX_REQUIRE(choice && status && reached && goal_dist, "null output");
+  EGX_REQUIRE(num_candidates >= 1 && num_candidates <= MAXC, "num_candidates must be in [1, EGX_MAX_CANDIDATES]");
+  return select_entry(Y_gen, x0, x1, x_ld, joints, joints_per_body, markers_proj, R0, T0, pene_count, goal, feet_marker_idx, weights,
+                      pene_thres, goal_thresh, reproj_factor, num_sequences, num_candidates, cost, cost_terms, colliding, field, obs,
+                      [&](SelectArgs& p, const ObstaclesDev& ob) {
+    p.choice = choice; p.status = status; p.reached = reached; p.goal_dist = goal_dist;
+    hipLaunchKernelGGL(egx_primitive_select_kernel, dim3(num_sequences), dim3(SEL_BLK), 0, static_cast<hipStream_t>(stream), p, ob);
+  });
+}
+
+// the beam selection behind egx_primitive_beam_select, _beam_select_field and _beam_select_obstacles
+int beam_select(const float* Y_gen, const float* x0, const float* x1, int x_ld, const float* joints, int joints_per_body,
+                const float* markers_proj, const float* R0, const float* T0, const int32_t* pene_count, const float* goal,
+                const int32_t* feet_marker_idx, const float* weights, float pene_thres, float goal_thresh, float reproj_factor,
+                int num_sequences, int beam_width, int num_candidates, const float* acc, const int32_t* ncoll, float* cost,
+                float* cost_terms, int32_t* colliding, int32_t* beam_row, int32_t* parent, float* acc_out, int32_t* ncoll_out,
+                float* path_cost, int32_t* beam_status, float* goal_dist, int32_t* reached, const GeoFieldDev& field,
+                const ObstaclesDev* obs, void* stream) {
+  EGX_REQUIRE(acc && ncoll, "null input");
+  EGX_REQUIRE(beam_row && parent && acc_out && ncoll_out && path_cost && beam_status && goal_dist && reached, "null output");
+  EGX_REQUIRE(beam_width >= 1 && beam_width <= EGX_MAX_BEAM, "beam_width must be in [1, EGX_MAX_BEAM]");
+  EGX_REQUIRE(num_candidates >= 1 && num_candidates <= MAXC && beam_width * num_candidates <= MAXC,
+              "beam_width * num_candidates must be in [1, EGX_MAX_CANDIDATES]");
+  EGX_REQUIRE(acc != acc_out && ncoll != ncoll_out, "acc / ncoll are read from one buffer and written to another");
+  return select_entry(Y_gen, x0, x1, x_ld, joints, joints_per_body, markers_proj, R0, T0, pene_count, goal, feet_marker_idx, weights,
+                      pene_thres, goal_thresh, reproj_factor, num_sequences, beam_width * num_candidates, cost, cost_terms, colliding,
+                      field, obs, [&](SelectArgs& p, const ObstaclesDev& ob) {
+    const BeamArgs q{acc, ncoll, beam_row, parent, acc_out, ncoll_out, path_cost, beam_status, goal_dist, reached, beam_width, num_candidates};
+    hipLaunchKernelGGL(egx_primitive_beam_select_kernel, dim3(num_sequences), dim3(SEL_BLK), 0, static_cast<hipStream_t>(stream), p, q, ob);
+  });
 }
 
 }  // namespace
@@ -582,14 +704,30 @@ extern "C" int egx_primitive_select_field(const float* Y_gen, const float* x0, c
                                           float* goal_dist, float* cost, float* cost_terms, int32_t* colliding, const float* field_dist,
                                           const float* field_origin, float field_cell, int field_H, int field_W, int num_fields,
                                           const int32_t* field_index, void* stream) {
-  EGX_REQUIRE(choice && status && reached && goal_dist, "null output");
-  EGX_REQUIRE(num_candidates >= 1 && num_candidates <= MAXC, "num_candidates must be in [1, EGX_MAX_CANDIDATES]");
-  return select_entry(Y_gen, x0, x1, x_ld, joints, joints_per_body, markers_proj, R0, T0, pene_count, goal, feet_marker_idx, weights,
-                      pene_thres, goal_thresh, reproj_factor, num_sequences, num_candidates, cost, cost_terms, colliding,
-                      GeoFieldDev{field_dist, field_origin, field_index, field_cell, field_H, field_W, num_fields}, [&](SelectArgs& p) {
-    p.choice = choice; p.status = status; p.reached = reached; p.goal_dist = goal_dist;
-    hipLaunchKernelGGL(egx_primitive_select_kernel, dim3(num_sequences), dim3(SEL_BLK), 0, static_cast<hipStream_t>(stream), p);
-  });
+  return greedy_select(Y_gen, x0, x1, x_ld, joints, joints_per_body, markers_proj, R0, T0, pene_count, goal, feet_marker_idx, weights,
+                       pene_thres, goal_thresh, reproj_factor, num_sequences, num_candidates, choice, status, reached, goal_dist, cost,
+                       cost_terms, colliding, GeoFieldDev{field_dist, field_origin, field_index, field_cell, field_H, field_W, num_fields},
+                       nullptr, stream);
+}
+
+// extends egx_primitive_select_field
+extern "C" int egx_primitive_select_obstacles(const float* Y_gen, const float* x0, const float* x1, int x_ld, const float* joints,
+                                              int joints_per_body, const float* markers_proj, const float* R0, const float* T0,
+                                              const int32_t* pene_count, const float* goal, const int32_t* feet_marker_idx,
+                                              const float* weights, float pene_thres, float goal_thresh, float reproj_factor,
+                                              int num_sequences, int num_candidates, int32_t* choice, int32_t* status, int32_t* reached,
+                                              float* goal_dist, float* cost, float* cost_terms, int32_t* colliding,
+                                              const float* field_dist, const float* field_origin, float field_cell, int field_H,
+                                              int field_W, int num_fields, const int32_t* field_index, const float* obs_xy,
+                                              const float* obs_radius, const int32_t* obs_count, const int32_t* obs_index, int num_sets,
+                                              int max_obstacles, int num_frames, int frame0, float obstacle_weight, float margin,
+                                              float body_radius, float* obs_term, float* obs_clearance, int32_t* obs_hit, void* stream) {
+  const ObstaclesDev obs{obs_xy, obs_radius, obs_count, obs_index, num_sets, max_obstacles, num_frames, frame0, obstacle_weight, margin,
+                         body_radius, obs_term, obs_clearance, obs_hit};
+  return greedy_select(Y_gen, x0, x1, x_ld, joints, joints_per_body, markers_proj, R0, T0, pene_count, goal, feet_marker_idx, weights,
+                       pene_thres, goal_thresh, reproj_factor, num_sequences, num_candidates, choice, status, reached, goal_dist, cost,
+                       cost_terms, colliding, GeoFieldDev{field_dist, field_origin, field_index, field_cell, field_H, field_W, num_fields},
+                       &obs, stream);
 }
 
 extern "C" int egx_primitive_select(const float* Y_gen, const float* x0, const float* x1, int x_ld, const float* joints,
@@ -629,18 +767,33 @@ extern "C" int egx_primitive_beam_select_field(const float* Y_gen, const float* 
                                                int32_t* beam_status, float* goal_dist, int32_t* reached, const float* field_dist,
                                                const float* field_origin, float field_cell, int field_H, int field_W, int num_fields,
                                                const int32_t* field_index, void* stream) {
-  EGX_REQUIRE(acc && ncoll, "null input");
-  EGX_REQUIRE(beam_row && parent && acc_out && ncoll_out && path_cost && beam_status && goal_dist && reached, "null output");
-  EGX_REQUIRE(beam_width >= 1 && beam_width <= EGX_MAX_BEAM, "beam_width must be in [1, EGX_MAX_BEAM]");
-  EGX_REQUIRE(num_candidates >= 1 && num_candidates <= MAXC && beam_width * num_candidates <= MAXC,
-              "beam_width * num_candidates must be in [1, EGX_MAX_CANDIDATES]");
-  EGX_REQUIRE(acc != acc_out && ncoll != ncoll_out, "acc / ncoll are read from one buffer and written to another");
-  return select_entry(Y_gen, x0, x1, x_ld, joints, joints_per_body, markers_proj, R0, T0, pene_count, goal, feet_marker_idx, weights,
-                      pene_thres, goal_thresh, reproj_factor, num_sequences, beam_width * num_candidates, cost, cost_terms, colliding,
-                      GeoFieldDev{field_dist, field_origin, field_index, field_cell, field_H, field_W, num_fields}, [&](SelectArgs& p) {
-    const BeamArgs q{acc, ncoll, beam_row, parent, acc_out, ncoll_out, path_cost, beam_status, goal_dist, reached, beam_width, num_candidates};
-    hipLaunchKernelGGL(egx_primitive_beam_select_kernel, dim3(num_sequences), dim3(SEL_BLK), 0, static_cast<hipStream_t>(stream), p, q);
-  });
+  return beam_select(Y_gen, x0, x1, x_ld, joints, joints_per_body, markers_proj, R0, T0, pene_count, goal, feet_marker_idx, weights,
+                     pene_thres, goal_thresh, reproj_factor, num_sequences, beam_width, num_candidates, acc, ncoll, cost, cost_terms,
+                     colliding, beam_row, parent, acc_out, ncoll_out, path_cost, beam_status, goal_dist, reached,
+                     GeoFieldDev{field_dist, field_origin, field_index, field_cell, field_H, field_W, num_fields}, nullptr, stream);
+}
+
+// extends egx_primitive_beam_select_field
+extern "C" int egx_primitive_beam_select_obstacles(const float* Y_gen, const float* x0, const float* x1, int x_ld, const float* joints,
+                                                   int joints_per_body, const float* markers_proj, const float* R0, const float* T0,
+                                                   const int32_t* pene_count, const float* goal, const int32_t* feet_marker_idx,
+                                                   const float* weights, float pene_thres, float goal_thresh, float reproj_factor,
+                                                   int num_sequences, int beam_width, int num_candidates, const float* acc,
+                                                   const int32_t* ncoll, float* cost, float* cost_terms, int32_t* colliding,
+                                                   int32_t* beam_row, int32_t* parent, float* acc_out, int32_t* ncoll_out,
+                                                   float* path_cost, int32_t* beam_status, float* goal_dist, int32_t* reached,
+                                                   const float* field_dist, const float* field_origin, float field_cell, int field_H,
+                                                   int field_W, int num_fields, const int32_t* field_index, const float* obs_xy,
+                                                   const float* obs_radius, const int32_t* obs_count, const int32_t* obs_index,
+                                                   int num_sets, int max_obstacles, int num_frames, int frame0, float obstacle_weight,
+                                                   float margin, float body_radius, float* obs_term, float* obs_clearance,
+                                                   int32_t* obs_hit, void* stream) {
+  const ObstaclesDev obs{obs_xy, obs_radius, obs_count, obs_index, num_sets, max_obstacles, num_frames, frame0, obstacle_weight, margin,
+                         body_radius, obs_term, obs_clearance, obs_hit};
+  return beam_select(Y_gen, x0, x1, x_ld, joints, joints_per_body, markers_proj, R0, T0, pene_count, goal, feet_marker_idx, weights,
+                     pene_thres, goal_thresh, reproj_factor, num_sequences, beam_width, num_candidates, acc, ncoll, cost, cost_terms,
+                     colliding, beam_row, parent, acc_out, ncoll_out, path_cost, beam_status, goal_dist, reached,
+                     GeoFieldDev{field_dist, field_origin, field_index, field_cell, field_H, field_W, num_fields}, &obs, stream);
 }
 
 extern "C" int egx_primitive_beam_select(const float* Y_gen, const float* x0, const float* x1, int x_ld, const float* joints,

@@ -9,7 +9,9 @@ continues from the best one (kernels egx_primitive_select, egx_primitive_advance
 search that keeps the best W partial paths per sequence (kernels egx_primitive_beam_select, egx_primitive_advance_beam,
 egx_beam_backtrack).  With `geodesic=` (a `GeodesicField`, egogen_amd/geodesic.py) the goal term of either search is the distance
 along the walkable raster of the scene instead of the straight line (entries egx_primitive_select_field,
-egx_primitive_beam_select_field).
+egx_primitive_beam_select_field).  With `obstacles=` (a `MovingObstacles`, egogen_amd/obstacles.py) either search also avoids
+other people's recorded tracks: a clearance term in the cost and a veto on overlap (entries egx_primitive_select_obstacles,
+egx_primitive_beam_select_obstacles).
 
 The three chains share their host path: `_chain_state` builds the state dict (checked inputs, defaults, the loop's buffers, the
 records) for b seeds of M rows each, `_primitive` launches what every primitive begins with (prior, parameter assembly, body
@@ -40,6 +42,7 @@ from .models import GAMMAPrimitiveCombo
 T_ALL, T_PRED, NM3, XB = 20, 18, 201, 93
 MAX_CANDIDATES = 256        # EGX_MAX_CANDIDATES of include/egogen_hip.h
 MAX_BEAM = 32               # EGX_MAX_BEAM
+NULL_FIELD = (None, None, 0.0, 0, 0, 0, None)      # the field arguments of a selection entry without a field
 SEARCH_WEIGHTS = {"goal": 1.0, "skate": 1.0, "floor": 1.0, "pene": 1.0, "face": 0.0}
 GENERATE_PPO_NOT_BUILT = ("generate_ppo is not built: nothing in the reference calls it, and its policy_model(X, obj_points=, "
                           "target_ori=, local_map=) signature belongs to no class in the tree")
@@ -79,9 +82,11 @@ class PrimitiveSequence:
     A beam result (beam_width W > 1) holds the returned path in the same fields: cost / cost_terms / colliding are [K,b,W*N(,5)],
     choice [K,b] the path's row within its W*N, status [K,b] the path node's bits (0: collides, 1: non-finite row, 2: non-finite
     hand-off); and beam_width, path_slot [K,b], parent / beam_row / path_cost / beam_status [K,b,W], which a greedy result has as
-    None."""
+    None.  With `obstacles=`: obstacle_term [K,b,M] (metres), clearance [K,b,M] (metres, +inf for an empty set) and obstacle_hit
+    [K,b,M] of every row (M = N, or W*N for a beam), colliding then includes the hits; None without obstacles."""
     SEARCH_FIELDS = ("goal", "choice", "cost", "cost_terms", "colliding", "status", "goal_dist", "n_valid", "geo_dist")
     BEAM_FIELDS = ("beam_width", "path_slot", "parent", "beam_row", "path_cost", "beam_status")
+    OBSTACLE_FIELDS = ("obstacle_term", "clearance", "obstacle_hit")
 
     def __init__(self, markers, params, rotmat, transl, pelvis, z, betas, gender, R0, T0, search: Optional[dict] = None):
         self.markers, self.params, self.rotmat, self.transl, self.pelvis, self.z = markers, params, rotmat, transl, pelvis, z
@@ -89,7 +94,7 @@ class PrimitiveSequence:
         self.search = search
         for k in self.SEARCH_FIELDS:
             setattr(self, k, None if search is None else search[k])
-        for k in self.BEAM_FIELDS:
+        for k in self.BEAM_FIELDS + self.OBSTACLE_FIELDS:
             setattr(self, k, None if search is None else search.get(k))
 
     def primitives(self, i: int) -> list:
@@ -307,6 +312,17 @@ class GAMMAPrimitiveComboGenOP:
                  _lib.ptr(T0), _lib.ptr(lbs.get("pene_count")), _lib.ptr(s["goal"]), _lib.ptr(s["feet"]), s["weights"], s["pene_thres"],
                  s["goal_thresh"], s["rf"]) for x, R0, T0 in zip(s["xs"], R0s, T0s)]
 
+    @staticmethod
+    def _select_tail(s, K, base):
+        """What follows the outputs of a selection entry, built once per loop -> (entry name, field arguments, per primitive the
+        obstacle arguments): `base` and nothing; with a field `base`_field and the field; with obstacles `base`_obstacles, the field
+        (a null one without) and, for primitive k, the obstacles with frame0 = obstacle_frame0 + 18 k and the outputs' row k."""
+        if s["obstacles"] is None:
+            return (base + "_field", s["field"], [()] * K) if s["field"] else (base, (), [()] * K)
+        obs = [(*s["obstacles"], s["obs_frame0"] + T_PRED * k, *s["obs_scalars"], _vp(s["obstacle_term"][k]), _vp(s["clearance"][k]),
+                _vp(s["obstacle_hit"][k])) for k in range(K)]
+        return base + "_obstacles", s["field"] or NULL_FIELD, obs
+
     # ------------------------------------------------------------------------------------------------------------------
     def generate_sequence(self, data, bparams, betas, n_primitives: int, n_gens: int = -1, z=None, reproj_factor=None,
                           to_numpy: bool = True, R0=None, T0=None) -> PrimitiveSequence:
@@ -347,7 +363,9 @@ class GAMMAPrimitiveComboGenOP:
     def generate_sequence_to_goal(self, data, bparams, betas, goal, n_primitives: int, n_candidates: int, scene=None,
                                   agent_scene=None, weights: Optional[dict] = None, pene_thres: float = 40, goal_thresh=None,
                                   z=None, reproj_factor=None, to_numpy: bool = True, R0=None, T0=None,
-                                  beam_width: int = 1, geodesic=None) -> PrimitiveSequence:
+                                  beam_width: int = 1, geodesic=None, obstacles=None, obstacle_weight: float = 1.0,
+                                  obstacle_margin: float = 0.5, body_radius: float = 0.3,
+                                  obstacle_frame0: int = 0) -> PrimitiveSequence:
         """`generate_sequence` steered to a goal through a scene by a greedy best-of-N search: for each of the `n_primitives`
         primitives, `n_candidates` candidates per sequence are generated, scored and the best one is kept; every candidate of the
         next primitive continues from it.  data / bparams / betas / reproj_factor / R0 / T0 as in `generate_sequence` (b seeds,
@@ -377,6 +395,17 @@ class GAMMAPrimitiveComboGenOP:
               raster at the world xy of the candidate's last pelvis instead of the straight line, so the search goes round an
               obstacle instead of at it; goal_dist, the reached test and n_valid stay Euclidean.  The field is built before the
               loop (that build waits for the device); the loop stays launches only.
+            - obstacles: None, or a `MovingObstacles` (egogen_amd/obstacles.py) of 1 or b sets (or with an index of b entries;
+              ValueError otherwise) on the operator's device (one not yet on a device is moved there).  Other people as vertical
+              cylinders on recorded tracks.  Over the 18 predicted frames of a candidate (frames 0 and 1 are the seed all
+              candidates share) c_t is the distance in the plane from the candidate's pelvis to the nearest obstacle at that
+              absolute frame, minus both radii; the cost, greedy or beam, gains obstacle_weight * mean_t max(0, obstacle_margin -
+              c_t), accumulated along a beam's path like the other quality terms, and a candidate with min_t c_t < 0 (the
+              cylinders overlap) counts as colliding: it is chosen only where every candidate collides, and status bit 0 says so.
+              Primitive k is scored against the absolute frames obstacle_frame0 + 18 k + t; outside a track's frames an obstacle
+              stands at its first or last position.  The loop stays launches only.
+            - obstacle_weight (1.0), obstacle_margin (0.5 m), body_radius (0.3 m, the searching body's own cylinder): stated
+              choices, like the weights above: nobody has measured motion quality with them.
         Raises FloatingPointError when a chosen hand-off, or every candidate of a sequence, held a non-finite value (read once,
         after the loop); for a beam, when a node of the returned path did."""
         from .body_model import SdfScene, SdfSceneSet
@@ -413,6 +442,21 @@ class GAMMAPrimitiveComboGenOP:
             if not torch.equal(geodesic.goals[:, :2].to(dev).expand(b, 2), goal[:, :2]):
                 raise ValueError("the fields of `geodesic` were built for other goals than `goal` (their xy must be equal)")
             field_args, field_alive = geodesic.select_args(b)
+        obs_args = obs_alive = None
+        if obstacles is not None:
+            from .obstacles import MovingObstacles
+            if not isinstance(obstacles, MovingObstacles):
+                raise TypeError(f"obstacles must be None or a MovingObstacles, got {type(obstacles).__name__}")
+            if obstacles.index is None and len(obstacles) not in (1, b):
+                raise ValueError(f"obstacles must hold 1 or {b} sets, got {len(obstacles)}")
+            if obstacles.device is None:
+                obstacles.to(dev)
+            if obstacles.device != dev:
+                raise ValueError(f"obstacles live on {obstacles.device}, the operator on {dev}")
+            if not (float(obstacle_margin) >= 0 and float(body_radius) >= 0 and np.isfinite(float(obstacle_weight))):
+                raise ValueError(f"obstacle_margin and body_radius must not be negative and obstacle_weight finite, got "
+                                 f"{obstacle_margin}, {body_radius}, {obstacle_weight}")
+            obs_args, obs_alive = obstacles.select_args(b)
         rows_scene = None
         if isinstance(scene, SdfSceneSet):
             if agent_scene is None:
@@ -440,7 +484,10 @@ class GAMMAPrimitiveComboGenOP:
                   "weights": (C.c_float * 5)(*[w[k] for k in ("goal", "skate", "floor", "pene", "face")]),
                   "pene_thres": float(pene_thres), "goal_thresh": float(goal_thresh), "field": field_args, "field_alive": field_alive,
                   "choice": rec(dtype=i32), "status": rec(dtype=i32), "reached": rec(dtype=i32), "goal_dist": rec(),
-                  "cost": rec(M), "cost_terms": rec(M, 5), "colliding": rec(M, dtype=i32)})
+                  "cost": rec(M), "cost_terms": rec(M, 5), "colliding": rec(M, dtype=i32), "obstacles": obs_args, "obs_alive": obs_alive})
+        if obs_args is not None:
+            s.update({"obs_scalars": (float(obstacle_weight), float(obstacle_margin), float(body_radius)), "obs_frame0": int(obstacle_frame0),
+                      "obstacle_term": rec(M), "clearance": rec(M), "obstacle_hit": rec(M, dtype=i32)})
         if scene is not None:
             s["lbs_out"]["pene_count"] = torch.empty(b * M * T_ALL, device=dev, dtype=i32)
         status = s["status"]
@@ -473,21 +520,22 @@ class GAMMAPrimitiveComboGenOP:
             search["geo_dist"] = s["cost_terms"][..., 0].gather(2, s["choice"].long().clamp(0, M - 1).unsqueeze(-1))[..., 0]
         if W > 1:
             search.update({k: s[k] for k in ("path_slot", "parent", "beam_row", "path_cost", "beam_status")}, beam_width=W)
+        if obs_args is not None:
+            search.update({k: s[k] for k in PrimitiveSequence.OBSTACLE_FIELDS})
         return self._result(s, zc, bt, R0_end[::M].reshape(b, 3, 3).contiguous(), T0_end[::M].contiguous(), to_numpy, search)
 
     def _search_loop(self, K, b, N, s):
         """The primitive loop of `generate_sequence_to_goal`: launches only, no allocation that depends on k, no host wait."""
         lib, st, hand, pp = _lib.load(), _lib.current_stream_ptr(), self._handoff_lead(s), _lib.ptr(s["pp"])
         sel = self._select_lead(s, [s["R0"]] * 2, [s["T0"]] * 2)
-        field = s["field"] or ()                                    # with a field: the *_field entry, the field before the stream
-        name = "egx_primitive_select_field" if field else "egx_primitive_select"
+        name, field, obs = self._select_tail(s, K, "egx_primitive_select")
         select = getattr(lib, name)
         for k in range(K):
             nxt = s["xs"][(k + 1) % 2]
             self._primitive(s, k, s["pp"], st, s["R0"], s["T0"])
             _lib.check(select(
                 *sel[k % 2], b, N, _vp(s["choice"][k]), _vp(s["status"][k]), _vp(s["reached"][k]),
-                _vp(s["goal_dist"][k]), _vp(s["cost"][k]), _vp(s["cost_terms"][k]), _vp(s["colliding"][k]), *field, st), name)
+                _vp(s["goal_dist"][k]), _vp(s["cost"][k]), _vp(s["cost_terms"][k]), _vp(s["colliding"][k]), *field, *obs[k], st), name)
             _lib.check(lib.egx_primitive_advance_select(
                 pp, *hand[k % 2], b, _vp(s["choice"][k]), N, _lib.ptr(s["R0"]), _lib.ptr(s["T0"]), _vp(s["markers"][k]),
                 _vp(s["pelvis"][k]), _vp(s["rotmat"][k]), _vp(s["transl"][k]), _vp(s["params"][k]), _lib.ptr(s["seed"]), _vp(nxt[0]),
@@ -499,8 +547,7 @@ class GAMMAPrimitiveComboGenOP:
         of another slot of its sequence."""
         lib, st, hand, pp = _lib.load(), _lib.current_stream_ptr(), self._handoff_lead(s), _lib.ptr(s["pp"])
         sel = self._select_lead(s, s["R0s"], s["T0s"])
-        field = s["field"] or ()
-        name = "egx_primitive_beam_select_field" if field else "egx_primitive_beam_select"
+        name, field, obs = self._select_tail(s, K, "egx_primitive_beam_select")
         select = getattr(lib, name)
         for k in range(K):
             nxt = s["xs"][(k + 1) % 2]
@@ -509,7 +556,7 @@ class GAMMAPrimitiveComboGenOP:
             _lib.check(select(
                 *sel[k % 2], b, W, N, _vp(s["acc"][k]), _vp(s["ncoll"][k]), _vp(s["cost"][k]), _vp(s["cost_terms"][k]),
                 _vp(s["colliding"][k]), _vp(s["beam_row"][k]), _vp(s["parent"][k]), _vp(s["acc"][k + 1]), _vp(s["ncoll"][k + 1]),
-                _vp(s["path_cost"][k]), _vp(s["beam_status"][k]), _vp(s["slot_goal_dist"][k]), _vp(s["slot_reached"][k]), *field, st),
+                _vp(s["path_cost"][k]), _vp(s["beam_status"][k]), _vp(s["slot_goal_dist"][k]), _vp(s["slot_reached"][k]), *field, *obs[k], st),
                 name)
             _lib.check(lib.egx_primitive_advance_beam(
                 pp, *hand[k % 2], b, W, N, _vp(s["beam_row"][k]), _lib.ptr(R0), _lib.ptr(T0), _lib.ptr(R0n), _lib.ptr(T0n),

@@ -11,7 +11,12 @@ per primitive and variant, the best one kept (greedy best-of-N on the env's rewa
 (W <= 32, W * N <= 256), and writes the path that ends in the best one.  `--walkable file.npz` (a scene file of
 `scene_gen.save_scene` that carries its walkable raster; independent of `--scene`) makes the goal term the distance along that
 raster (`GeodesicField`), so the variants go round an obstacle instead of at it; the driver then prints that distance next to the
-straight-line one.
+straight-line one.  `--avoid a.pkl,b.pkl` (with `--goal`) makes the people of earlier `motion_*.pkl` files moving obstacles
+(`MovingObstacles.from_rollout_files`: a vertical cylinder of 0.3 m round each recorded pelvis track, frame 0 of every file being
+frame 0 of this run): a candidate pays for coming within 0.5 m of one and is vetoed where the cylinders overlap, so a crowd is
+composed by prioritised planning, one run per person; the driver prints the minimum clearance along each written path.
+`--start x,y,yaw_deg` places the seed's world frame (the origin, facing +y, without it): two runs without it start inside each
+other.
 
 `--cfg <name>` is the combo config (`crowd_ppo/cfg_samp20/<name>.yml` under the working directory, else the packaged copy): it
 names the predictor's and the regressor's configs, whose checkpoints are read from `results/crowd_ppo/<config>/checkpoints`
@@ -53,6 +58,9 @@ def main(argv=None):
     parser.add_argument("--scene", default=None, help="npz with sdf, center, scale: penalise and avoid penetration (with --goal)")
     parser.add_argument("--walkable", default=None, help="scene file of scene_gen.save_scene with its walkable raster: the goal term "
                         "becomes the distance along the raster, round obstacles (with --goal; independent of --scene)")
+    parser.add_argument("--avoid", default=None, help="comma-separated motion_*.pkl files of earlier runs: their people are moving "
+                        "obstacles of this one (with --goal)")
+    parser.add_argument("--start", default=None, help="x,y,yaw_deg: where the seed stands in the world and which way it faces")
     args = parser.parse_args(argv)
     if args.goal is None and args.scene is not None:
         parser.error("--scene needs --goal")
@@ -60,6 +68,24 @@ def main(argv=None):
         parser.error("--walkable needs --goal")
     if args.goal is None and args.beam_width != 1:
         parser.error("--beam-width needs --goal")
+    if args.goal is None and args.avoid is not None:
+        parser.error("--avoid needs --goal")
+    start = None
+    if args.start is not None:
+        try:
+            start = [float(v) for v in args.start.split(",")]
+        except ValueError:
+            start = []
+        if len(start) != 3 or not np.isfinite(start).all():
+            parser.error("--start takes x,y,yaw_deg")
+    obstacles = None
+    if args.avoid:          # before the models and the device: a bad file ends the run here
+        from egogen_amd.obstacles import MovingObstacles
+        try:
+            obstacles = MovingObstacles.from_rollout_files([f for f in args.avoid.split(",") if f])
+        except (OSError, ValueError, KeyError, pickle.UnpicklingError, EOFError, AttributeError) as e:
+            raise SystemExit("--avoid {}: {!r}".format(args.avoid, e))
+        print("[INFO] avoiding {} people over {} frames".format(int(obstacles.count[0]), obstacles.num_frames))
     if not torch.cuda.is_available():
         raise SystemExit("gen_motion needs a HIP device: the MI355X path has no CPU fallback")
     np.random.seed(args.seed)
@@ -108,6 +134,11 @@ def main(argv=None):
     bparams[:, 0, :3], bparams[:, 0, 3:69] = can["trans"], can["poses"][:, :66]
     R0 = can["transf_rotmat"].astype(np.float32)[None].repeat(args.n_gens, 0)
     T0 = can["transf_transl"].astype(np.float32).reshape(1, 3).repeat(args.n_gens, 0)
+    if start is not None:   # the seed's world frame turned by yaw about z and moved so that its origin stands at (x, y)
+        yaw = np.deg2rad(start[2])
+        Rz = np.array([[np.cos(yaw), -np.sin(yaw), 0.0], [np.sin(yaw), np.cos(yaw), 0.0], [0.0, 0.0, 1.0]])
+        R0 = (Rz @ R0.astype(np.float64)).astype(np.float32)
+        T0 = (T0.astype(np.float64) @ Rz.T + np.array([start[0], start[1], 0.0])).astype(np.float32)
     if args.goal is None:
         res = op.generate_sequence(data, bparams, can["betas"].astype(np.float32), args.n_primitives, n_gens=args.n_gens, R0=R0, T0=T0)
     else:
@@ -118,12 +149,17 @@ def main(argv=None):
                 scene = SdfScene({k: f[k] for k in ("sdf", "center", "scale")})
         res = op.generate_sequence_to_goal(data.repeat(args.n_gens, 1), bparams.repeat(args.n_gens, 1), can["betas"].astype(np.float32),
                                            goal, args.n_primitives, args.n_candidates, scene=scene, R0=R0, T0=T0,
-                                           beam_width=args.beam_width, geodesic=field)
+                                           beam_width=args.beam_width, geodesic=field, obstacles=obstacles)
         for i in range(args.n_gens):
             last = int(res.n_valid[i]) - 1
             along = "" if field is None else " ({:.3f} m along the walkable raster)".format(float(res.geo_dist[last, i]))
             print("[INFO] variant {}: {} primitives, final distance to the goal {:.3f} m{}, colliding choices {}".format(
                 i, last + 1, float(res.goal_dist[last, i]), along, int((res.status[:last + 1, i] & 1).sum())))
+            if obstacles is not None:
+                ch = np.asarray(res.choice[:last + 1, i], np.int64)
+                clear = np.asarray(res.clearance)[np.arange(last + 1), i, ch]
+                hits = np.asarray(res.obstacle_hit)[np.arange(last + 1), i, ch]
+                print("[INFO] variant {}: minimum clearance {:.3f} m, chosen hits {}".format(i, float(clear.min()), int(hits.sum())))
     paths = [res.save(args.out, i, man_id="{}_{}".format(args.seed, i)) for i in range(args.n_gens)]
     for p in paths:
         print(p)

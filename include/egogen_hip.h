@@ -35,6 +35,8 @@ extern "C" {
 #define EGX_XB_DIM 93          /* transl3 glorot3 body63 lhand12 rhand12 */
 #define EGX_MAX_CANDIDATES 256 /* candidates per sequence of egx_primitive_select */
 #define EGX_MAX_BEAM 32        /* beam slots per sequence of egx_primitive_beam_select; slots * candidates <= EGX_MAX_CANDIDATES */
+#define EGX_MAX_OBSTACLES 32   /* tracks per obstacle set of egx_primitive_select_obstacles: a choice, the 18-frame window of a set
+                                  (18 x 32 xy and 32 radii, 4.7 KB) is staged into one workgroup's LDS */
 #define EGX_GEODESIC_OFF 1.0e4f /* metres: what a geodesic field gives where none of the four surrounding cells holds a distance */
 #define EGX_GEODESIC_BATCH 8    /* passes egx_geodesic_field launches between two reads of its flag */
 #define EGX_NUM_BETAS 10
@@ -942,6 +944,50 @@ int egx_primitive_beam_select_field(const float* Y_gen, const float* x0, const f
                                     float* acc_out, int32_t* ncoll_out, float* path_cost, int32_t* beam_status, float* goal_dist,
                                     int32_t* reached, const float* field_dist, const float* field_origin, float field_cell,
                                     int field_H, int field_W, int num_fields, const int32_t* field_index, void* stream);
+
+/* egx_primitive_select_obstacles / egx_primitive_beam_select_obstacles - egx_primitive_select_field /
+ * egx_primitive_beam_select_field (the same kernels, the same arguments up to field_index; field_dist may be NULL: the Euclidean
+ * goal term) with moving obstacles: num_sets sets of up to max_obstacles <= EGX_MAX_OBSTACLES tracks, obs_xy
+ * [num_sets,max_obstacles,num_frames,2] the world xy of each track per absolute frame (finite), obs_radius
+ * [num_sets,max_obstacles] metres, obs_count [num_sets] the live tracks of each set, obs_index [num_sequences] the set of each
+ * sequence (clamped into [0, num_sets); NULL: every sequence reads set 0).  A person is a vertical cylinder: z is not read.  The
+ * rows of this launch are the primitive that starts at absolute frame frame0; its frames 0 and 1 are the seed every candidate
+ * shares and are not scored.  Per row, over the predicted frames t = 2..19, with p_t the world xy of joint 0 of body t
+ * (x = fma(R0[2], j.z, fma(R0[1], j.y, R0[0] j.x)) + T0.x, y likewise) and a_t = clamp(frame0 + t, 0, num_frames - 1) (before its
+ * track an obstacle stands at its first position, after it where it stopped):
+ *   c_t       = min_o sqrt((p_t.x - o.x)^2 + (p_t.y - o.y)^2) - (r_o + body_radius) over the live obstacles at frame a_t; +inf for none
+ *   clearance = min_t c_t;  term = (sum_t max(0, margin - c_t)) / 18 (metres);  hit = clearance < 0
+ * Every operation rounds on its own (no contraction); min is order-free; the frame sum is the fixed tree of the wave reduction
+ * (lane t - 2 holds frame t, partners 32, 16, 8, 4, 2, 1 lanes up).  A NaN pelvis gives a NaN term and clearance: the row ranks as
+ * non-finite and is not a hit.  cost = cost_prev + obstacle_weight * term, one rounded product and one rounded addition on what
+ * the launch would have written without obstacles (the Euclidean cost, or the field's); the beam's q gains the same product, so
+ * acc_out accumulates the term along the path.  colliding = the SDF collision OR hit: a hit row is in the colliding class of the
+ * greedy order and a colliding node of the beam's path key; status bit 0 follows.  Outputs per row: obs_term, obs_clearance
+ * (float), obs_hit (int32), [rows].  A phase of its own after the scoring and the field: the set's 18-frame window is staged into
+ * LDS once per workgroup, then one wave per row.  EGX_ERR_ARG for a NULL output, max_obstacles outside [0, EGX_MAX_OBSTACLES], a NULL
+ * obs_xy / obs_radius / obs_count with max_obstacles > 0, num_frames < 1, num_sets < 1, a negative or NaN margin or body_radius. */
+int egx_primitive_select_obstacles(const float* Y_gen, const float* x0, const float* x1, int x_ld, const float* joints,
+                                   int joints_per_body, const float* markers_proj, const float* R0, const float* T0,
+                                   const int32_t* pene_count, const float* goal, const int32_t* feet_marker_idx, const float* weights,
+                                   float pene_thres, float goal_thresh, float reproj_factor, int num_sequences, int num_candidates,
+                                   int32_t* choice, int32_t* status, int32_t* reached, float* goal_dist, float* cost,
+                                   float* cost_terms, int32_t* colliding, const float* field_dist, const float* field_origin,
+                                   float field_cell, int field_H, int field_W, int num_fields, const int32_t* field_index,
+                                   const float* obs_xy, const float* obs_radius, const int32_t* obs_count, const int32_t* obs_index,
+                                   int num_sets, int max_obstacles, int num_frames, int frame0, float obstacle_weight, float margin,
+                                   float body_radius, float* obs_term, float* obs_clearance, int32_t* obs_hit, void* stream);
+int egx_primitive_beam_select_obstacles(const float* Y_gen, const float* x0, const float* x1, int x_ld, const float* joints,
+                                        int joints_per_body, const float* markers_proj, const float* R0, const float* T0,
+                                        const int32_t* pene_count, const float* goal, const int32_t* feet_marker_idx,
+                                        const float* weights, float pene_thres, float goal_thresh, float reproj_factor,
+                                        int num_sequences, int beam_width, int num_candidates, const float* acc, const int32_t* ncoll,
+                                        float* cost, float* cost_terms, int32_t* colliding, int32_t* beam_row, int32_t* parent,
+                                        float* acc_out, int32_t* ncoll_out, float* path_cost, int32_t* beam_status, float* goal_dist,
+                                        int32_t* reached, const float* field_dist, const float* field_origin, float field_cell,
+                                        int field_H, int field_W, int num_fields, const int32_t* field_index, const float* obs_xy,
+                                        const float* obs_radius, const int32_t* obs_count, const int32_t* obs_index, int num_sets,
+                                        int max_obstacles, int num_frames, int frame0, float obstacle_weight, float margin,
+                                        float body_radius, float* obs_term, float* obs_clearance, int32_t* obs_hit, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * PPO rollout glue
