@@ -273,6 +273,11 @@ SIGNATURES = {
     "egx_policy_train_step_heads_cursor": (C.c_int, [C.c_void_p, C.POINTER(UpdateHead), C.c_void_p] + [C.c_float] * 6 + [C.c_void_p]),
     "egx_adamw_clip_step_cursor": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_float] +
                                    [C.c_double] * 5 + [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "egx_policy_train_bind_flat": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    "egx_policy_train_fused_tail": (C.c_int, [C.c_void_p]),
+    "egx_adamw_clip_step_train": (C.c_int, [C.c_void_p] * 5 + [C.c_size_t, C.c_size_t, C.c_float] + [C.c_double] * 5 + [C.c_void_p] * 3),
+    "egx_adamw_clip_step_train_cursor": (C.c_int, [C.c_void_p] * 5 + [C.c_size_t, C.c_size_t, C.c_float] + [C.c_double] * 5 +
+                                         [C.c_void_p] * 4),
     "egx_pack3_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "egx_pack3": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "egx_gemm3_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),

@@ -80,6 +80,15 @@ int egx_ppo_loss_packed_precleared(const float* zp, const float* value, const fl
                                    float max_logvar, float eps_clip, float vf_coef, float ent_coef, int num_rows, float* g_zp,
                                    float* g_value, float* out_terms, void* stream_, const int* cursor = nullptr, int max_cursor = 0);
 // (cursor != null: the sums go to row min(*cursor, max_cursor) of out_terms, six floats a row - the update's per-epoch log)
+// The optimiser step's launches (ppo.hip).  egx_adamw_launch_consts: egx_sumsq_partial_kernel (norm partials, step += 1) and
+// egx_adamw_consts_kernel (workspace[EGX_ADAMW_CONSTS ..] = clip coefficient, step size, sqrt(bias correction 2); *cursor += 1);
+// egx_adamw_clip_step_launches: those two and egx_adamw_flat_kernel - what egx_adamw_clip_step / _cursor enqueue.
+constexpr int EGX_ADAMW_CONSTS = 1024;
+int egx_adamw_launch_consts(const float* grad, size_t n_clip, float max_norm, double lr, double beta1, double beta2, float* step,
+                            float* workspace, int* cursor, hipStream_t st);
+int egx_adamw_clip_step_launches(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, size_t n, size_t n_clip,
+                                 float max_norm, double lr, double beta1, double beta2, double eps, double weight_decay, float* step,
+                                 float* workspace, int* cursor, void* stream_);
 void egx_launch_posenc3(hipStream_t st, const float* dist, const float* time, int n, float* out, int ld, void* out3, int S3, int s0,
                         void* out3T = nullptr, int S3T = 0, int col0T = 0, float* zero6 = nullptr /* six floats cleared by the launch */);
 

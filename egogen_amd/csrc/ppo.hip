@@ -2,6 +2,7 @@
 // policy's two encoders, so that the autograd graph of one minibatch is ~40 kernels instead of ~300 tiny elementwise ones.
 #include <algorithm>
 #include <cstring>
+#include "adamw.h"
 #include "egx_nets.h"
 
 namespace {
@@ -318,7 +319,7 @@ __global__ __launch_bounds__(256) void egx_adamw_flat_kernel(float* __restrict__
                                                              float* __restrict__ v, size_t n, size_t n_clip,
                                                              const float* __restrict__ consts /* clip coef, step size, sqrt(bc2) */,
                                                              double lr, double b1, double b2, double eps, double wd) {
-  const float coef = consts[0], step_size = consts[1], bc2s = consts[2];
+  const EgxAdamwK k(consts, lr, b1, b2, eps, wd);
   const size_t i0 = ((size_t)blockIdx.x * 256 + threadIdx.x) * 4;
   if (i0 >= n) return;
   const int cnt = (int)((n - i0 < 4) ? (n - i0) : 4);
@@ -331,20 +332,9 @@ __global__ __launch_bounds__(256) void egx_adamw_flat_kernel(float* __restrict__
   } else {
     for (int e = 0; e < cnt; ++e) { gr[e] = g[i0 + e]; pv[e] = p[i0 + e]; mv[e] = m[i0 + e]; vv[e] = v[i0 + e]; }
   }
-  const double omb1 = 1.0 - b1, omb2 = 1.0 - b2, lrwd = lr * wd;
 #pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    if (e < cnt) {
-      // operand types as in torch's functor: fp32 state, double hyper-parameters (the mixed expressions run in double)
-      float gg = gr[e];
-      if (i0 + e < n_clip) gg *= coef;
-      pv[e] = (float)((double)pv[e] - lrwd * (double)pv[e]);
-      mv[e] = (float)((double)mv[e] + omb1 * ((double)gg - (double)mv[e]));
-      vv[e] = (float)(b2 * (double)vv[e] + omb2 * (double)gg * (double)gg);
-      const float denom = (float)((double)(sqrtf(vv[e]) / bc2s) + eps);
-      pv[e] -= step_size * mv[e] / denom;
-    }
-  }
+  for (int e = 0; e < 4; ++e)
+    if (e < cnt) egx_adamw_elem(pv[e], gr[e], mv[e], vv[e], i0 + e < n_clip, k);   // the arithmetic: adamw.h
   if (cnt == 4) {
     *reinterpret_cast<float4*>(p + i0) = *reinterpret_cast<const float4*>(pv);
     *reinterpret_cast<float4*>(m + i0) = *reinterpret_cast<const float4*>(mv);
@@ -489,19 +479,28 @@ extern "C" int egx_rollout_store(const float* state, const float* egosensing, co
 
 extern "C" size_t egx_adamw_workspace_floats(void) { return 1024 + 8; }
 
-static int adamw_clip_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, size_t n, size_t n_clip,
-                           float max_norm, double lr, double beta1, double beta2, double eps, double weight_decay,
-                           float* step, float* workspace, int* cursor, void* stream_) {
-  EGX_REQUIRE(param && grad && exp_avg && exp_avg_sq && step && workspace && n > 0 && n_clip <= n, "bad arguments");
-  hipStream_t st = static_cast<hipStream_t>(stream_);
+// the two launches in front of AdamW's pass over the elements: norm partials (and step += 1), then the constants (and the cursor)
+int egx_adamw_launch_consts(const float* grad, size_t n_clip, float max_norm, double lr, double beta1, double beta2, float* step,
+                            float* workspace, int* cursor, hipStream_t st) {
   const int nb = 1024;
   const bool do_clip = max_norm > 0.f && n_clip > 0;
   hipLaunchKernelGGL(egx_sumsq_partial_kernel, dim3(nb), dim3(256), 0, st, grad, do_clip ? n_clip : (size_t)0, workspace, step);
   hipLaunchKernelGGL(egx_adamw_consts_kernel, dim3(1), dim3(256), 0, st, workspace, nb, do_clip ? 1 : 0, max_norm, lr, beta1, beta2,
                      step, workspace + nb, cursor);
+  EGX_HIP_CHECK(hipGetLastError());
+  return EGX_OK;
+}
+
+int egx_adamw_clip_step_launches(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, size_t n, size_t n_clip,
+                                 float max_norm, double lr, double beta1, double beta2, double eps, double weight_decay,
+                                 float* step, float* workspace, int* cursor, void* stream_) {
+  EGX_REQUIRE(param && grad && exp_avg && exp_avg_sq && step && workspace && n > 0 && n_clip <= n, "bad arguments");
+  hipStream_t st = static_cast<hipStream_t>(stream_);
+  const int rc = egx_adamw_launch_consts(grad, n_clip, max_norm, lr, beta1, beta2, step, workspace, cursor, st);
+  if (rc) return rc;
   const size_t blocks = (n + 1023) / 1024;
   hipLaunchKernelGGL(egx_adamw_flat_kernel, dim3((unsigned)blocks), dim3(256), 0, st, param, grad, exp_avg, exp_avg_sq, n, n_clip,
-                     workspace + nb, lr, beta1, beta2, eps, weight_decay);
+                     workspace + EGX_ADAMW_CONSTS, lr, beta1, beta2, eps, weight_decay);
   EGX_HIP_CHECK(hipGetLastError());
   return EGX_OK;
 }
@@ -509,13 +508,13 @@ static int adamw_clip_step(float* param, const float* grad, float* exp_avg, floa
 extern "C" int egx_adamw_clip_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, size_t n, size_t n_clip,
                                    float max_norm, double lr, double beta1, double beta2, double eps, double weight_decay,
                                    float* step, float* workspace, void* stream_) {
-  return adamw_clip_step(param, grad, exp_avg, exp_avg_sq, n, n_clip, max_norm, lr, beta1, beta2, eps, weight_decay, step, workspace,
-                         nullptr, stream_);
+  return egx_adamw_clip_step_launches(param, grad, exp_avg, exp_avg_sq, n, n_clip, max_norm, lr, beta1, beta2, eps, weight_decay, step,
+                                      workspace, nullptr, stream_);
 }
 
 extern "C" int egx_adamw_clip_step_cursor(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, size_t n, size_t n_clip,
                                           float max_norm, double lr, double beta1, double beta2, double eps, double weight_decay,
                                           float* step, float* workspace, int32_t* cursor, void* stream_) {
-  return adamw_clip_step(param, grad, exp_avg, exp_avg_sq, n, n_clip, max_norm, lr, beta1, beta2, eps, weight_decay, step, workspace,
-                         cursor, stream_);
+  return egx_adamw_clip_step_launches(param, grad, exp_avg, exp_avg_sq, n, n_clip, max_norm, lr, beta1, beta2, eps, weight_decay, step,
+                                      workspace, cursor, stream_);
 }

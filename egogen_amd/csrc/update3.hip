@@ -11,10 +11,16 @@
 //             step producing the gate gradients directly as packed images.
 // 19 launches per minibatch (egx_update_head_kernel first) instead of ~85.  Gradients are WRITTEN (not accumulated) into the flat
 // gradient buffer - every parameter is used exactly once per minibatch - so the buffer needs no zero fill.
+//   optimiser  the step that follows a minibatch (egx_adamw_clip_step_train): norm partials and constants as in ppo.hip, then ONE
+//             pass over the weights, egx_adamw_table_kernel - AdamW inside the blocks that make the weight images, the biases in
+//             blocks of their own - instead of egx_adamw_flat_kernel and a weight-image launch that reads back what it wrote.
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
+#include <string>
+#include <utility>
 #include <vector>
+#include "adamw.h"
 #include "d3.h"
 
 namespace {
@@ -126,6 +132,188 @@ __global__ __launch_bounds__(256) void egx_pack3_table_kernel(const PackEntry* _
     return;
   }
   u3_pack_fragment(e, e.src, frag, lane, nplanes, EgxRowsIdentity());
+}
+
+// ---- the optimiser step's pass over the weights: AdamW and both weight images from ONE read of every parameter.  In the flat
+// parameter buffer every weight matrix is an entry of the weight table (each exactly once) and the rest is biases and alignment
+// padding, so AdamW can run in egx_pack3_table_kernel's own blocks: the wave that holds a 32 x 32 block (or a 16 x 32 fragment)
+// of p loads the same elements of g, m and v, updates them (egx_adamw_elem, adamw.h: egx_adamw_flat_kernel's arithmetic), stores
+// p, m and v and writes the images from the updated values in its registers - instead of a second launch that reads back what
+// the first has just written.  The grid is partitioned by role; no role reads what another one writes (no fence, no ticket):
+//   [0, b_tab)       table role: egx_pack3_table_kernel's work on the weight table, same fragment order, search and LDS strip
+//   [.., + n_rem)    remainder role: egx_adamw_flat_kernel's body on the spans of [0, n) no table entry owns, <= 1024 elements
+//                    a block (`rem`, made by the host from the entries' offsets: egx_policy_train_bind_flat)
+// The host has checked that every entry is a whole contiguous matrix inside [0, n) and that no two overlap: no element is
+// updated twice, and no index leaves the flat buffers.
+struct RemBlock { size_t start, end; };   // flat elements [start, end), end - start <= 1024
+struct AdamwTabArgs {
+  const PackEntry* tab;
+  int n_tab, frags_tab, nplanes;
+  float* p; const float* g; float* m; float* v;
+  size_t n_clip;
+  const float* consts;   // egx_adamw_consts_kernel's: clip coefficient, step size, sqrt(bias correction 2)
+  double lr, b1, b2, eps, wd;
+  const RemBlock* rem;
+  int b_tab, n_rem;
+};
+
+__device__ __forceinline__ bool u3_aligned16(const void* a, const void* b, const void* c, const void* d) {
+  return ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(c) | reinterpret_cast<uintptr_t>(d)) & 15) == 0;
+}
+// p, g, m and v move with nontemporal accesses: each is touched once per optimiser step and by nothing else before the next one,
+// while the images written beside them are what the next launches read.  With plain accesses the 369 MB of this pass push the
+// images out of the last-level cache and the launches that follow pay for it (profiles/update_fused_tail.md).
+__device__ __forceinline__ void u3_load8(const float* s, float (&x)[8]) {
+  const f32x4 x0 = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(s));
+  const f32x4 x1 = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(s + 4));
+  x[0] = x0[0]; x[1] = x0[1]; x[2] = x0[2]; x[3] = x0[3]; x[4] = x1[0]; x[5] = x1[1]; x[6] = x1[2]; x[7] = x1[3];
+}
+__device__ __forceinline__ void u3_store8(float* d, const float (&x)[8]) {
+  __builtin_nontemporal_store(f32x4{x[0], x[1], x[2], x[3]}, reinterpret_cast<f32x4*>(d));
+  __builtin_nontemporal_store(f32x4{x[4], x[5], x[6], x[7]}, reinterpret_cast<f32x4*>(d + 4));
+}
+// AdamW on the flat elements fi .. fi + valid - 1 (valid <= 8: a row's in-range columns of a fragment lane) in two steps, so that
+// a wave can have the loads of both halves of its block in flight before it computes: load (x = p), then update and store (x = the
+// updated parameters, zero from `valid` on).  The interior - eight elements, 16-byte aligned in all four buffers - moves as two
+// 16-byte accesses per array, ragged or unaligned rows element by element; nothing outside [fi, fi + valid) is read or written.
+struct U3Adamw8 {
+  size_t fi;
+  int valid;
+  bool fast;
+  float x[8], gr[8], mv[8], vv[8];
+};
+__device__ __forceinline__ void u3_adamw8_load(const AdamwTabArgs& a, size_t fi, int valid, U3Adamw8& w) {
+  const float *pp = a.p + fi, *gp = a.g + fi, *mp = a.m + fi, *vp = a.v + fi;
+  w.fi = fi; w.valid = valid;
+  w.fast = valid == 8 && u3_aligned16(pp, gp, mp, vp);
+  if (w.fast) {
+    u3_load8(pp, w.x); u3_load8(gp, w.gr); u3_load8(mp, w.mv); u3_load8(vp, w.vv);
+  } else {
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+      const bool in = q < valid;
+      w.x[q] = in ? pp[q] : 0.f; w.gr[q] = in ? gp[q] : 0.f; w.mv[q] = in ? mp[q] : 0.f; w.vv[q] = in ? vp[q] : 0.f;
+    }
+  }
+}
+__device__ __forceinline__ void u3_adamw8_step(const AdamwTabArgs& a, const EgxAdamwK& k, U3Adamw8& w) {
+#pragma unroll
+  for (int q = 0; q < 8; ++q)
+    if (q < w.valid) egx_adamw_elem(w.x[q], w.gr[q], w.mv[q], w.vv[q], w.fi + q < a.n_clip, k);
+  float *pp = a.p + w.fi, *mp = a.m + w.fi, *vp = a.v + w.fi;
+  if (w.fast) {
+    u3_store8(pp, w.x); u3_store8(mp, w.mv); u3_store8(vp, w.vv);
+  } else {
+#pragma unroll
+    for (int q = 0; q < 8; ++q)
+      if (q < w.valid) { pp[q] = w.x[q]; mp[q] = w.mv[q]; vp[q] = w.vv[q]; }
+  }
+}
+
+__global__ __launch_bounds__(256) void egx_adamw_table_kernel(AdamwTabArgs a) {
+  const EgxAdamwK k(a.consts, a.lr, a.b1, a.b2, a.eps, a.wd);
+  if ((int)blockIdx.x >= a.b_tab) {   // ---- remainder role: egx_adamw_flat_kernel's body on one block of a span
+    const int rb = (int)blockIdx.x - a.b_tab;
+    if (rb >= a.n_rem) return;
+    const RemBlock blk = a.rem[rb];
+    const size_t i0 = blk.start + 4 * (size_t)threadIdx.x;
+    if (i0 >= blk.end) return;
+    const int cnt = (int)((blk.end - i0 < 4) ? (blk.end - i0) : 4);
+    float gr[4], pv[4], mv[4], vv[4];
+    const bool vec = cnt == 4 && u3_aligned16(a.p + i0, a.g + i0, a.m + i0, a.v + i0);
+    if (vec) {
+      *reinterpret_cast<f32x4*>(gr) = *reinterpret_cast<const f32x4*>(a.g + i0);
+      *reinterpret_cast<f32x4*>(pv) = *reinterpret_cast<const f32x4*>(a.p + i0);
+      *reinterpret_cast<f32x4*>(mv) = *reinterpret_cast<const f32x4*>(a.m + i0);
+      *reinterpret_cast<f32x4*>(vv) = *reinterpret_cast<const f32x4*>(a.v + i0);
+    } else {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const bool in = e < cnt;
+        gr[e] = in ? a.g[i0 + e] : 0.f; pv[e] = in ? a.p[i0 + e] : 0.f; mv[e] = in ? a.m[i0 + e] : 0.f; vv[e] = in ? a.v[i0 + e] : 0.f;
+      }
+    }
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+      if (e < cnt) egx_adamw_elem(pv[e], gr[e], mv[e], vv[e], i0 + e < a.n_clip, k);
+    if (vec) {
+      *reinterpret_cast<f32x4*>(a.p + i0) = *reinterpret_cast<const f32x4*>(pv);
+      *reinterpret_cast<f32x4*>(a.m + i0) = *reinterpret_cast<const f32x4*>(mv);
+      *reinterpret_cast<f32x4*>(a.v + i0) = *reinterpret_cast<const f32x4*>(vv);
+    } else {
+#pragma unroll
+      for (int e = 0; e < 4; ++e)
+        if (e < cnt) { a.p[i0 + e] = pv[e]; a.m[i0 + e] = mv[e]; a.v[i0 + e] = vv[e]; }
+    }
+    return;
+  }
+  // ---- table role: egx_pack3_table_kernel on the weight table, AdamW in place of the plain loads
+  const PackEntry* __restrict__ tab = a.tab;
+  int frag = blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63, nplanes = a.nplanes;
+  if (frag >= a.frags_tab) return;
+  int lo = 0, hi = a.n_tab - 1;   // first entry whose running count exceeds `frag`
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (frag >= tab[mid].frag_end) lo = mid + 1; else hi = mid;
+  }
+  const PackEntry e = tab[lo];
+  frag -= lo > 0 ? tab[lo - 1].frag_end : 0;
+  const size_t base = (size_t)(e.src - a.p) + e.col0;   // flat index of the matrix's element (0, 0)
+  float x[8];
+  if (e.transpose == 2) {
+    __shared__ float sblk[4][32][33];
+    float (*sb)[33] = sblk[threadIdx.x >> 6];
+    const int BJ = (e.cols + 31) >> 5;
+    const int bi = frag / BJ, bj = frag % BJ;
+    const int r = lane & 15, kg = lane >> 4;
+    U3Adamw8 w[2];
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {   // the loads of the whole block first
+      const int row = 32 * bi + 16 * t + r, k0 = 32 * bj + 8 * kg;
+      const int valid = row < e.red ? min(max(e.cols - k0, 0), 8) : 0;
+      u3_adamw8_load(a, valid ? base + (size_t)row * e.ld + k0 : 0, valid, w[t]);
+    }
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+      u3_adamw8_step(a, k, w[t]);
+#pragma unroll
+      for (int q = 0; q < 8; ++q) sb[16 * t + r][8 * kg + q] = w[t].x[q];
+      bf16x8 pl[3];
+      d3_split(w[t].x, pl);
+      bf16x8* o = e.dst + ((size_t)(2 * bi + t) * e.S_total + e.s0 + bj) * 3 * 64 + lane;
+#pragma unroll
+      for (int p = 0; p < 3; ++p)
+        if (p < nplanes) o[p * 64] = pl[p];
+    }
+    __builtin_amdgcn_wave_barrier();
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+#pragma unroll
+      for (int q = 0; q < 8; ++q) x[q] = sb[8 * kg + q][16 * t + r];
+      bf16x8 pl[3];
+      d3_split(x, pl);
+      bf16x8* o = e.dst2 + ((size_t)(2 * bj + t) * e.S_total2 + bi) * 3 * 64 + lane;
+#pragma unroll
+      for (int p = 0; p < 3; ++p)
+        if (p < nplanes) o[p * 64] = pl[p];
+    }
+    return;
+  }
+  // transpose 0 (the host admits no other): u3_pack_fragment's fragment with rows as they are
+  const int S = (e.cols + 31) >> 5;
+  const int rt = frag / S, s = frag % S;
+  const int row = rt * 16 + (lane & 15), k0 = s * 32 + 8 * (lane >> 4);
+  const int valid = row < e.red ? min(max(e.cols - k0, 0), 8) : 0;
+  U3Adamw8 w;
+  u3_adamw8_load(a, valid ? base + (size_t)row * e.ld + k0 : 0, valid, w);
+  u3_adamw8_step(a, k, w);
+  bf16x8 pl[3];
+  d3_split(w.x, pl);
+  bf16x8* o = e.dst + ((size_t)rt * e.S_total + e.s0 + s) * 3 * 64 + lane;
+#pragma unroll
+  for (int p = 0; p < 3; ++p)
+    if (p < nplanes) o[p * 64] = pl[p];
 }
 
 // ---- the head of a minibatch: ONE launch for what used to be five (index copy aside): the row gather, the advantage
@@ -348,6 +536,12 @@ struct egx_policy_train {
   int prec = 0;   // arithmetic of every product of the chain (D3Plain::prec): egx_policy_train_set_precision
   int dense3_launches = 0;   // egx_dense3_kernel launches of the last step call (egx_policy_train_dense3_launches)
   bool merge = true;   // independent products of the backward pass share launches (EGX_UPDATE_MERGE=0 at creation: the old sequence)
+  // the optimiser step's fused tail (egx_adamw_table_kernel): wanted unless EGX_UPDATE_FUSED_TAIL=0 at creation, in force once
+  // egx_policy_train_bind_flat has found every table entry a matrix of its own inside the flat buffer it was given
+  bool fused_wanted = true, fused = false;
+  std::vector<PackEntry> h_weights;
+  const float* flat_p = nullptr; size_t flat_n = 0;
+  RemBlock* rem = nullptr; int n_rem = 0;
 };
 
 namespace {
@@ -422,6 +616,7 @@ extern "C" int egx_policy_train_create(const egx_policy_weights* w, const egx_po
   auto* h = new egx_policy_train();
   h->n = num_rows; h->Sn = num_rows / 32;
   if (const char* e = getenv("EGX_UPDATE_MERGE")) h->merge = !(e[0] == '0' && e[1] == 0);
+  if (const char* e = getenv("EGX_UPDATE_FUSED_TAIL")) h->fused_wanted = !(e[0] == '0' && e[1] == 0);
   Encoder& X = h->enc[0];
   X.Wih = w->x_enc_w_ih; X.Whh = w->x_enc_w_hh; X.bih = w->x_enc_b_ih; X.bhh = w->x_enc_b_hh;
   X.gWih = g->x_enc_w_ih; X.gWhh = g->x_enc_w_hh; X.gbih = g->x_enc_b_ih; X.gbhh = g->x_enc_b_hh;
@@ -491,6 +686,7 @@ extern "C" int egx_policy_train_create(const egx_policy_weights* w, const egx_po
   h->n_weights = (int)tw.size();
   int rc = upload_table(tw, &h->tab_weights, &h->frags_weights);
   if (rc) return fail(rc);
+  h->h_weights = tw;
   // inputs: the two frames of every encoder as operands, and [frame 0; frame 1]^T (+ ones) for the weight gradient of W_ih
   for (int e = 0; e < 2; ++e) {
     Encoder& En = h->enc[e];
@@ -521,8 +717,54 @@ extern "C" int egx_policy_train_create(const egx_policy_weights* w, const egx_po
 extern "C" void egx_policy_train_destroy(egx_policy_train* h) {
   if (!h) return;
   (void)hipFree(h->ar.base); (void)hipFree(h->tab_weights); (void)hipFree(h->tab_inputs); (void)hipFree(h->tab_loss);
+  (void)hipFree(h->rem);
   delete h;
 }
+
+// The flat buffers the optimiser steps this handle's weights in: `param` (n floats; gradient and both moments have its layout).
+// Decides whether egx_adamw_clip_step_train may run the fused kernel: every entry of the weight table must be a whole contiguous
+// matrix inside [param, param + n) and no two may overlap - then the spans between them (biases, padding, any parameter without an
+// image) are cut into the remainder role's blocks.  Otherwise the handle keeps the two-launch tail and egx_last_error() says why.
+extern "C" int egx_policy_train_bind_flat(egx_policy_train* h, const float* param, size_t n) {
+  EGX_REQUIRE(h && param && n > 0, "bad arguments");
+  h->fused = false; h->flat_p = param; h->flat_n = n;
+  auto off_tail = [&](const std::string& why) {
+    egx_set_error("egx_policy_train_bind_flat: the optimiser step keeps its two-launch tail - " + why);
+    return EGX_OK;
+  };
+  if (!h->fused_wanted) return EGX_OK;   // EGX_UPDATE_FUSED_TAIL=0: asked for, nothing to report
+  std::vector<std::pair<size_t, size_t>> own;   // [start, end) of every entry, in flat elements
+  const uintptr_t p0 = reinterpret_cast<uintptr_t>(param);
+  for (size_t i = 0; i < h->h_weights.size(); ++i) {
+    const PackEntry& e = h->h_weights[i];
+    const std::string which = "weight table entry " + std::to_string(i);
+    if (e.transpose != 0 && e.transpose != 2) return off_tail(which + " is a transposed view");
+    if (e.col0 != 0 || e.ld != e.cols || e.red <= 0 || e.cols <= 0) return off_tail(which + " is not a whole contiguous matrix");
+    const uintptr_t s = reinterpret_cast<uintptr_t>(e.src);
+    const size_t cnt = (size_t)e.red * e.cols;
+    if (s < p0 || (s - p0) % sizeof(float) != 0 || (s - p0) / sizeof(float) > n || cnt > n - (s - p0) / sizeof(float))
+      return off_tail(which + " does not lie wholly inside the flat parameter buffer");
+    own.emplace_back((s - p0) / sizeof(float), (s - p0) / sizeof(float) + cnt);
+  }
+  std::sort(own.begin(), own.end());
+  for (size_t i = 1; i < own.size(); ++i)
+    if (own[i].first < own[i - 1].second) return off_tail("two weight table entries overlap");
+  std::vector<RemBlock> rem;
+  size_t at = 0;
+  auto span = [&](size_t lo, size_t hi) {
+    for (; lo < hi; lo += 1024) rem.push_back({lo, std::min(lo + 1024, hi)});
+  };
+  for (const auto& o : own) { span(at, o.first); at = o.second; }
+  span(at, n);
+  (void)hipFree(h->rem);
+  h->rem = nullptr; h->n_rem = (int)rem.size();
+  EGX_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&h->rem), std::max<size_t>(1, rem.size()) * sizeof(RemBlock)));
+  if (!rem.empty()) EGX_HIP_CHECK(hipMemcpy(h->rem, rem.data(), rem.size() * sizeof(RemBlock), hipMemcpyHostToDevice));
+  h->fused = true;
+  return EGX_OK;
+}
+
+extern "C" int egx_policy_train_fused_tail(const egx_policy_train* h) { return h ? (h->fused ? 1 : 0) : -1; }
 
 extern "C" int egx_policy_train_refresh(egx_policy_train* h, void* stream) {
   EGX_REQUIRE(h, "null handle");
@@ -532,6 +774,45 @@ extern "C" int egx_policy_train_refresh(egx_policy_train* h, void* stream) {
   run_table(static_cast<hipStream_t>(stream), h->tab_weights, h->n_weights, h->frags_weights, planes);
   EGX_HIP_CHECK(hipGetLastError());
   return EGX_OK;
+}
+
+// The optimiser step of the policy this handle trains, its weight images included: egx_sumsq_partial_kernel, egx_adamw_consts_kernel
+// and egx_adamw_table_kernel - three launches for the four of egx_adamw_clip_step + egx_policy_train_refresh, which is what runs
+// where the fused kernel does not apply (EGX_UPDATE_FUSED_TAIL=0, a table that failed egx_policy_train_bind_flat, other buffers
+// than the bound ones).  Either way p, m, v and this handle's images are those of the four launches, bit for bit.
+static int adamw_clip_step_train(egx_policy_train* h, float* param, const float* grad, float* exp_avg, float* exp_avg_sq, size_t n,
+                                 size_t n_clip, float max_norm, double lr, double beta1, double beta2, double eps, double weight_decay,
+                                 float* step, float* workspace, int* cursor, void* stream_) {
+  EGX_REQUIRE(h && param && grad && exp_avg && exp_avg_sq && step && workspace && n > 0 && n_clip <= n, "bad arguments");
+  if (!(h->fused && param == h->flat_p && n == h->flat_n && h->frags_weights > 0)) {
+    const int rc = egx_adamw_clip_step_launches(param, grad, exp_avg, exp_avg_sq, n, n_clip, max_norm, lr, beta1, beta2, eps, weight_decay,
+                                                step, workspace, cursor, stream_);
+    return rc ? rc : egx_policy_train_refresh(h, stream_);
+  }
+  hipStream_t st = static_cast<hipStream_t>(stream_);
+  const int rc = egx_adamw_launch_consts(grad, n_clip, max_norm, lr, beta1, beta2, step, workspace, cursor, st);
+  if (rc) return rc;
+  AdamwTabArgs a;
+  a.tab = h->tab_weights; a.n_tab = h->n_weights; a.frags_tab = h->frags_weights;
+  a.nplanes = std::max(d3_planes(h->prec), d3_planes(egx_policy_get_precision()));   // egx_policy_train_refresh's rule
+  a.p = param; a.g = grad; a.m = exp_avg; a.v = exp_avg_sq; a.n_clip = n_clip; a.consts = workspace + EGX_ADAMW_CONSTS;
+  a.lr = lr; a.b1 = beta1; a.b2 = beta2; a.eps = eps; a.wd = weight_decay;
+  a.rem = h->rem; a.b_tab = egx_ceil_div(h->frags_weights, 4); a.n_rem = h->n_rem;
+  hipLaunchKernelGGL(egx_adamw_table_kernel, dim3(a.b_tab + a.n_rem), dim3(256), 0, st, a);
+  EGX_HIP_CHECK(hipGetLastError());
+  return EGX_OK;
+}
+extern "C" int egx_adamw_clip_step_train(egx_policy_train* h, float* param, const float* grad, float* exp_avg, float* exp_avg_sq, size_t n,
+                                         size_t n_clip, float max_norm, double lr, double beta1, double beta2, double eps,
+                                         double weight_decay, float* step, float* workspace, void* stream) {
+  return adamw_clip_step_train(h, param, grad, exp_avg, exp_avg_sq, n, n_clip, max_norm, lr, beta1, beta2, eps, weight_decay, step,
+                               workspace, nullptr, stream);
+}
+extern "C" int egx_adamw_clip_step_train_cursor(egx_policy_train* h, float* param, const float* grad, float* exp_avg, float* exp_avg_sq,
+                                                size_t n, size_t n_clip, float max_norm, double lr, double beta1, double beta2, double eps,
+                                                double weight_decay, float* step, float* workspace, int32_t* cursor, void* stream) {
+  return adamw_clip_step_train(h, param, grad, exp_avg, exp_avg_sq, n, n_clip, max_norm, lr, beta1, beta2, eps, weight_decay, step,
+                               workspace, cursor, stream);
 }
 
 extern "C" int egx_policy_train_set_precision(egx_policy_train* h, int prec) {

@@ -368,6 +368,11 @@ class GAMMAPPOPolicy(nn.Module):
         h = C.c_void_p()
         _lib.check(lib.egx_policy_train_create(C.byref(w), C.byref(g), int(n), C.byref(h)), "egx_policy_train_create")
         _lib.check(lib.egx_policy_train_set_precision(h, _UPDATE_PREC[self.update_precision]), "egx_policy_train_set_precision")
+        # the optimiser step of this handle's minibatches runs AdamW inside the launch that re-makes its weight images
+        # (egx_adamw_clip_step_train) where every weight matrix is a span of its own in the flat buffer; EGX_UPDATE_FUSED_TAIL=0,
+        # read by egx_policy_train_create: AdamW and the refresh as two launches
+        _lib.check(lib.egx_policy_train_bind_flat(h, _lib.ptr(self._flat_p), self._flat_p.numel()), "egx_policy_train_bind_flat")
+        fused_tail = lib.egx_policy_train_fused_tail(h) == 1
         f = dict(dtype=torch.float32, device=self._flat_grad.device)
         # EGX_UPDATE_HEAD=0: the minibatch's head as the five launches it used to be (gather, statistics, input images,
         # positional encoding; index copy and log clone around a replay) - the A/B switch of profiles/update_head.md
@@ -381,7 +386,7 @@ class GAMMAPPOPolicy(nn.Module):
         packed = _lib.PolicyPacked3()
         _lib.check(lib.egx_policy_train_packed(h, C.byref(packed)), "egx_policy_train_packed")
         # the handle: named fields; the compact observations exist only without the head launch, which reads the rollout in place
-        hs = {"h": h, "n": int(n), "head": head, "packed": packed, "stats": torch.zeros(2, **f),
+        hs = {"h": h, "n": int(n), "head": head, "fused_tail": fused_tail, "packed": packed, "stats": torch.zeros(2, **f),
               **dict(zip(_LOSS_ROWS, loss)), **dict(zip(_OBS_ROWS, obs))}
         self._train_handles[n] = hs
         if len(self._train_handles) == 1:   # the rollout forward reads the images this handle keeps current
@@ -427,14 +432,16 @@ class GAMMAPPOPolicy(nn.Module):
         refresh of their own."""
         return (sum(int(p._version) for p in self.parameters()), self._prec_key())
 
-    def _refresh_images(self):
+    def _refresh_images(self, fresh=None):
         """Re-make the packed weight images of every update handle (one launch each) - after anything that changed the
-        parameters."""
+        parameters.  `fresh`: the handle whose optimiser step has just re-made its own images in its AdamW launch
+        (egx_adamw_clip_step_train) - that step counts as the refresh it contains."""
         if not self._train_handles:
             return
         lib, st = _lib.load(), _lib.current_stream_ptr()
         for hs in self._train_handles.values():
-            _lib.check(lib.egx_policy_train_refresh(hs["h"], st), "egx_policy_train_refresh")
+            if hs is not fresh:
+                _lib.check(lib.egx_policy_train_refresh(hs["h"], st), "egx_policy_train_refresh")
         self._img_key = self._img_key_now()
         self.refresh_counts["total"] += 1
 
@@ -537,8 +544,10 @@ class GAMMAPPOPolicy(nn.Module):
             log_out.copy_(torch.stack([terms[k].detach() for k in ("loss", "loss/clip", "loss/vf", "loss/ent", "loss/kld", "approx_kl")]))
         return "autograd"
 
-    def _clip_and_step(self, cursor=None):
-        """`cursor`: the update's minibatch cursor (int32 device scalar), advanced by the optimiser's single-block launch."""
+    def _clip_and_step(self, cursor=None, n=None):
+        """`cursor`: the update's minibatch cursor (int32 device scalar), advanced by the optimiser's single-block launch.
+        `n`: rows of the minibatch being stepped - where its train handle has the fused tail, AdamW runs in the launch that
+        re-makes that handle's weight images (three launches instead of four); other live handles keep a refresh of their own."""
         if self.use_flat_optimizer and self._flat_opt_state == "ready":
             g = self.optim.param_groups[0]
             lib = _lib.load()
@@ -546,13 +555,16 @@ class GAMMAPPOPolicy(nn.Module):
             args = (_lib.ptr(self._flat_p), _lib.ptr(self._flat_grad), _lib.ptr(self._flat_m), _lib.ptr(self._flat_v),
                     self._flat_p.numel(), self._n_clip, float(self._grad_norm or 0.0), float(g["lr"]), float(b1),
                     float(b2), float(g["eps"]), float(g["weight_decay"]), _lib.ptr(self._step_t), _lib.ptr(self._adamw_ws))
-            if cursor is None:
-                rc = lib.egx_adamw_clip_step(*args, _lib.current_stream_ptr())
-            else:
-                rc = lib.egx_adamw_clip_step_cursor(*args, _lib.ptr(cursor), _lib.current_stream_ptr())
-            _lib.check(rc, "egx_adamw_clip_step")
-            self._runner.mark_dirty()   # parameters written by address: the rollout runner's packed images are stale
-            self._refresh_images()      # ... and so are the update's own (re-made by one launch, inside the captured graph too)
+            hs = self._train_handles.get(int(n)) if n is not None else None
+            if hs is not None and not hs["fused_tail"]:
+                hs = None
+            if hs is not None:
+                args = (hs["h"],) + args
+            tail = (_lib.current_stream_ptr(),) if cursor is None else (_lib.ptr(cursor), _lib.current_stream_ptr())
+            name = "egx_adamw_clip_step" + ("_train" if hs is not None else "") + ("" if cursor is None else "_cursor")
+            _lib.check(getattr(lib, name)(*args, *tail), name)
+            self._runner.mark_dirty()       # parameters written by address: the rollout runner's packed images are stale
+            self._refresh_images(fresh=hs)  # ... and so are the update's own (re-made inside the captured graph too)
             return
         if cursor is not None:
             raise _lib.EgxError("a minibatch cursor needs the flat optimiser")
@@ -757,7 +769,7 @@ class GAMMAPPOPolicy(nn.Module):
             return st
         st = self._new_graph_state(batch, local_bs)
         fwd_bwd = lambda part=None: self._graph_fwd_bwd(batch, local_bs, st, part)
-        clip_and_step = lambda: self._clip_and_step(st["cursor"])
+        clip_and_step = lambda: self._clip_and_step(st["cursor"], n=local_bs)
         try:
             with self._warmed_up(lambda: (fwd_bwd(), clip_and_step())):
                 halves = self._dp and self.overlap_allreduce and len(self._grad_buckets()) == 2 and self._train_handle(local_bs) is not None
@@ -848,7 +860,7 @@ class GAMMAPPOPolicy(nn.Module):
         path = self._fwd_bwd(batch, idx, gstats, log)
         if self._dp:
             self._all_reduce_grad()
-        self._clip_and_step()
+        self._clip_and_step(n=int(idx.shape[0]))
         return log, path
 
     def _learn_stats(self, batch: RolloutBatch, logs: List[torch.Tensor], kld_rows: List[torch.Tensor]) -> Dict[str, List[float]]:

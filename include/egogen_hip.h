@@ -1081,6 +1081,24 @@ int egx_adamw_clip_step(float* param, const float* grad, float* exp_avg, float* 
 int egx_adamw_clip_step_cursor(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, size_t n, size_t n_clip,
                                float max_norm, double lr, double beta1, double beta2, double eps, double weight_decay, float* step,
                                float* workspace, int32_t* cursor, void* stream);
+/* The optimiser step of the policy a train handle belongs to, the handle's weight images included: the two small launches of
+ * egx_adamw_clip_step (norm partials, constants - the cursor advance with _cursor) and ONE pass over the weights, in which the
+ * blocks that make the images of a weight matrix also run AdamW on it (p, g, m, v read once, the images written from the updated
+ * values) and further blocks cover the biases: three launches for the four of egx_adamw_clip_step + egx_policy_train_refresh,
+ * the same bits everywhere.  Images of OTHER handles still need their egx_policy_train_refresh.
+ * egx_policy_train_bind_flat names the flat parameter buffer (n floats) once, outside graph capture: the fused pass is used for
+ * calls with that buffer when every entry of the handle's weight table is a whole matrix inside it and no two overlap, and not
+ * with EGX_UPDATE_FUSED_TAIL=0 in the environment when the handle was created; otherwise the calls below enqueue the four
+ * launches and egx_policy_train_fused_tail() returns 0.  A table that breaks the rule is reported through egx_last_error() after
+ * the bind, which still returns 0; the environment switch, being asked for, leaves no message. */
+int egx_policy_train_bind_flat(egx_policy_train* h, const float* param, size_t n);
+int egx_policy_train_fused_tail(const egx_policy_train* h);
+int egx_adamw_clip_step_train(egx_policy_train* h, float* param, const float* grad, float* exp_avg, float* exp_avg_sq, size_t n,
+                              size_t n_clip, float max_norm, double lr, double beta1, double beta2, double eps, double weight_decay,
+                              float* step, float* workspace, void* stream);
+int egx_adamw_clip_step_train_cursor(egx_policy_train* h, float* param, const float* grad, float* exp_avg, float* exp_avg_sq, size_t n,
+                                     size_t n_clip, float max_norm, double lr, double beta1, double beta2, double eps,
+                                     double weight_decay, float* step, float* workspace, int32_t* cursor, void* stream);
 
 #ifdef __cplusplus
 }
