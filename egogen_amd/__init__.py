@@ -5,4 +5,7 @@ def __getattr__(name):      # `from egogen_amd import GeodesicField` without imp
     if name == "MovingObstacles":
         from .obstacles import MovingObstacles
         return MovingObstacles
+    if name == "PersonGroups":
+        from .crowd import PersonGroups
+        return PersonGroups
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

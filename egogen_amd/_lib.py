@@ -228,6 +228,10 @@ SIGNATURES = {
                                             [C.c_void_p] * 13 +
                                             [C.c_void_p, C.c_void_p, C.c_float, C.c_int, C.c_int, C.c_int, C.c_void_p] +
                                             [C.c_void_p] * 4 + [C.c_int] * 4 + [C.c_float] * 3 + [C.c_void_p] * 4),
+    # joints, joints_per_body, R0, T0, goal, cost, cost_terms, colliding, num_sequences, num_candidates, group_start, group_member,
+    # num_groups, sweeps, pair_weight, margin, body_radius, goal_thresh, then the twelve outputs and the stream
+    "egx_primitive_select_joint": (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 6 + [C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                             C.c_int, C.c_int] + [C.c_float] * 4 + [C.c_void_p] * 13),
     "egx_sample_action": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_int, C.c_int, C.c_void_p,
                                     C.c_void_p, C.c_void_p]),
     "egx_gae": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double, C.c_void_p,

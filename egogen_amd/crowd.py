@@ -1,0 +1,61 @@
+"""The people of one call of `generate_sequence_to_goal` who see each other: `PersonGroups`, the partition of the b sequences into
+groups that the joint step of the greedy search (entry egx_primitive_select_joint, csrc/genop_joint.hip) reads as CSR tensors on
+the device.  A group is the people who share a scene and a time line; within a group every member chooses its next primitive
+against the others' current choices."""
+from __future__ import annotations
+
+import numpy as np
+import torch
+
+MAX_GROUP = 32          # EGX_MAX_GROUP of include/egogen_hip.h
+MAX_SWEEPS = 8          # EGX_MAX_SWEEPS
+
+
+class PersonGroups:
+    """ids [b] the group of every sequence as given; start [G+1] / member [b] the CSR form: group g holds the sequences
+    member[start[g]:start[g+1]] in ascending order, the groups in order of first appearance.  Built on the host (`from_ids`, no
+    device needed); `to(device)` makes the int32 tensors `group_start` / `group_member` the kernel reads."""
+
+    def __init__(self, ids, start, member):
+        self.ids, self.start, self.member = ids, start, member
+        self.device = self.group_start = self.group_member = None
+
+    def __len__(self):
+        return len(self.start) - 1
+
+    @property
+    def sizes(self):
+        return np.diff(self.start)
+
+    @classmethod
+    def from_ids(cls, groups, b: int) -> "PersonGroups":
+        """groups: [b] integers; sequences with equal ids are one group.  ValueError for another length, values that are no
+        integers, or a group of more than 32 members."""
+        if torch.is_tensor(groups):
+            groups = groups.detach().cpu().numpy()
+        g = np.asarray(groups)
+        if g.ndim != 1 or g.shape[0] != int(b):
+            raise ValueError(f"groups must hold {int(b)} ids, one per sequence, got shape {tuple(g.shape)}")
+        if g.dtype == bool or not (np.issubdtype(g.dtype, np.integer) or
+                                   (np.issubdtype(g.dtype, np.floating) and np.isfinite(g).all() and (g == np.round(g)).all())):
+            raise ValueError(f"groups must be integers, got {g.dtype}: {g.tolist()}")
+        g = g.astype(np.int64)
+        order, members = [], {}
+        for i, v in enumerate(g.tolist()):
+            if v not in members:
+                members[v] = []
+                order.append(v)
+            members[v].append(i)
+        for v in order:
+            if len(members[v]) > MAX_GROUP:
+                raise ValueError(f"group {v} has {len(members[v])} members, at most {MAX_GROUP} people can see each other")
+        start = np.cumsum([0] + [len(members[v]) for v in order]).astype(np.int32)
+        member = np.asarray([i for v in order for i in members[v]], np.int32)
+        return cls(g, start, member)
+
+    def to(self, device) -> "PersonGroups":
+        device = torch.device(device)
+        self.group_start = torch.from_numpy(self.start).to(device)
+        self.group_member = torch.from_numpy(self.member).to(device)
+        self.device = device
+        return self

@@ -53,3 +53,20 @@ __device__ __forceinline__ float egx_obstacle_clearance(float x, float y, int cn
   }
   return m;
 }
+
+// The same against the members of a group of the joint search (genop_joint.hip): the cnt columns of one frame of the group's table
+// except column `skip` (the member itself), every member the same cylinder, rr = body_radius + body_radius rounded once by the
+// caller.  The same roundings in the same order.  +inf where no other member is left; NaN for a NaN x / y; another member's NaN
+// coordinate gives a NaN distance, which fminf drops: that member is not there in this frame.
+__device__ __forceinline__ float egx_pair_clearance(float x, float y, int cnt, int skip, const float* s_x, const float* s_y, float rr) {
+#pragma clang fp contract(off)
+  if (isnan(x) || isnan(y)) return __builtin_nanf("");
+  float m = __builtin_inff();
+  for (int o = 0; o < cnt; ++o) {
+    if (o == skip) continue;
+    const float dx = egx_sub(x, s_x[o]), dy = egx_sub(y, s_y[o]);
+    const float d = sqrtf(egx_add(egx_mul(dx, dx), egx_mul(dy, dy)));
+    m = fminf(m, egx_sub(d, rr));
+  }
+  return m;
+}

@@ -11,7 +11,9 @@ egx_beam_backtrack).  With `geodesic=` (a `GeodesicField`, egogen_amd/geodesic.p
 along the walkable raster of the scene instead of the straight line (entries egx_primitive_select_field,
 egx_primitive_beam_select_field).  With `obstacles=` (a `MovingObstacles`, egogen_amd/obstacles.py) either search also avoids
 other people's recorded tracks: a clearance term in the cost and a veto on overlap (entries egx_primitive_select_obstacles,
-egx_primitive_beam_select_obstacles).
+egx_primitive_beam_select_obstacles).  With `groups=` (ids, or a `PersonGroups`, egogen_amd/crowd.py) the sequences of one group of the
+greedy search see each other: after the selection the members choose again against each other's current choices (entry
+egx_primitive_select_joint, csrc/genop_joint.hip), and the hand-off continues from that joint choice.
 
 The three chains share their host path: `_chain_state` builds the state dict (checked inputs, defaults, the loop's buffers, the
 records) for b seeds of M rows each, `_primitive` launches what every primitive begins with (prior, parameter assembly, body
@@ -69,6 +71,32 @@ def _load_ckpt(candidates):
     raise FileNotFoundError(f"none of {list(candidates)} could be read: {err}")
 
 
+def _person_groups(groups, data, beam_width, pair_weight, pair_margin, body_radius, joint_sweeps):
+    """The `groups=` argument of `generate_sequence_to_goal` checked on the host, before any device work -> a `PersonGroups` not yet
+    on a device (None without groups).  ValueError: groups with a beam, ids of another length than the b seeds of `data`, a group
+    of more than 32, sweeps outside [1, 8], a negative margin or radius, a non-finite weight."""
+    if groups is None:
+        return None
+    from .crowd import MAX_SWEEPS, PersonGroups
+    if beam_width > 1:
+        raise ValueError(f"groups= is the greedy search only: beam_width must be 1 with it, got {beam_width}")
+    shape = tuple(np.shape(data))
+    if len(shape) != 3:
+        raise ValueError(f"data must be [>=2,b,>=201], got {shape}")
+    b = shape[1]
+    if isinstance(groups, PersonGroups):
+        if len(groups.ids) != b:
+            raise ValueError(f"groups must hold {b} ids, one per sequence, got {len(groups.ids)}")
+    else:
+        groups = PersonGroups.from_ids(groups, b)
+    if int(joint_sweeps) != joint_sweeps or not 1 <= int(joint_sweeps) <= MAX_SWEEPS:
+        raise ValueError(f"joint_sweeps must be an integer in [1, {MAX_SWEEPS}], got {joint_sweeps}")
+    if not (float(pair_margin) >= 0 and float(body_radius) >= 0 and np.isfinite(float(pair_weight))):
+        raise ValueError(f"pair_margin and body_radius must not be negative and pair_weight finite, got {pair_margin}, {body_radius}, "
+                         f"{pair_weight}")
+    return groups
+
+
 class PrimitiveSequence:
     """What `generate_sequence` returns: K primitives of b sequences.
     markers [K,b,20,67,3] blended markers, params [K,b,20,93], rotmat [K,b,3,3] / transl [K,b,3] the world frame each primitive
@@ -83,10 +111,18 @@ class PrimitiveSequence:
     choice [K,b] the path's row within its W*N, status [K,b] the path node's bits (0: collides, 1: non-finite row, 2: non-finite
     hand-off); and beam_width, path_slot [K,b], parent / beam_row / path_cost / beam_status [K,b,W], which a greedy result has as
     None.  With `obstacles=`: obstacle_term [K,b,M] (metres), clearance [K,b,M] (metres, +inf for an empty set) and obstacle_hit
-    [K,b,M] of every row (M = N, or W*N for a beam), colliding then includes the hits; None without obstacles."""
+    [K,b,M] of every row (M = N, or W*N for a beam), colliding then includes the hits; None without obstacles.
+    With `groups=` (S = joint_sweeps, G groups): groups [b] the ids; individual_choice [K,b] what the selection chose before the
+    members saw each other (choice is the joint choice, choice_trace[:, -1]); pair_term / pair_clearance / joint_cost (metres, metres,
+    cost) and pair_hit [K,S,b,N] of every row as evaluated in each sweep; choice_trace [K,S,b] the choices after each sweep;
+    joint_changed [K,S,G] the members of a group that changed their choice in a sweep (0: a fixed point); crowd_clearance [K,b] the
+    clearance of the chosen track against the other members' chosen tracks and crowd_hit [K,b] = crowd_clearance < 0: did the crowd
+    as written overlap.  cost / colliding stay what the selection wrote; status follows the joint choice.  None without groups."""
     SEARCH_FIELDS = ("goal", "choice", "cost", "cost_terms", "colliding", "status", "goal_dist", "n_valid", "geo_dist")
     BEAM_FIELDS = ("beam_width", "path_slot", "parent", "beam_row", "path_cost", "beam_status")
     OBSTACLE_FIELDS = ("obstacle_term", "clearance", "obstacle_hit")
+    JOINT_FIELDS = ("individual_choice", "pair_term", "pair_clearance", "pair_hit", "joint_cost", "choice_trace", "joint_changed",
+                    "crowd_clearance", "crowd_hit", "groups")
 
     def __init__(self, markers, params, rotmat, transl, pelvis, z, betas, gender, R0, T0, search: Optional[dict] = None):
         self.markers, self.params, self.rotmat, self.transl, self.pelvis, self.z = markers, params, rotmat, transl, pelvis, z
@@ -94,7 +130,7 @@ class PrimitiveSequence:
         self.search = search
         for k in self.SEARCH_FIELDS:
             setattr(self, k, None if search is None else search[k])
-        for k in self.BEAM_FIELDS + self.OBSTACLE_FIELDS:
+        for k in self.BEAM_FIELDS + self.OBSTACLE_FIELDS + self.JOINT_FIELDS:
             setattr(self, k, None if search is None else search.get(k))
 
     def primitives(self, i: int) -> list:
@@ -365,7 +401,8 @@ class GAMMAPrimitiveComboGenOP:
                                   z=None, reproj_factor=None, to_numpy: bool = True, R0=None, T0=None,
                                   beam_width: int = 1, geodesic=None, obstacles=None, obstacle_weight: float = 1.0,
                                   obstacle_margin: float = 0.5, body_radius: float = 0.3,
-                                  obstacle_frame0: int = 0) -> PrimitiveSequence:
+                                  obstacle_frame0: int = 0, groups=None, pair_weight: float = 1.0, pair_margin: float = 0.5,
+                                  joint_sweeps: int = 2) -> PrimitiveSequence:
         """`generate_sequence` steered to a goal through a scene by a greedy best-of-N search: for each of the `n_primitives`
         primitives, `n_candidates` candidates per sequence are generated, scored and the best one is kept; every candidate of the
         next primitive continues from it.  data / bparams / betas / reproj_factor / R0 / T0 as in `generate_sequence` (b seeds,
@@ -406,6 +443,22 @@ class GAMMAPrimitiveComboGenOP:
               stands at its first or last position.  The loop stays launches only.
             - obstacle_weight (1.0), obstacle_margin (0.5 m), body_radius (0.3 m, the searching body's own cylinder): stated
               choices, like the weights above: nobody has measured motion quality with them.
+            - groups: None, or [b] integer ids (or a `PersonGroups`, egogen_amd/crowd.py): sequences with equal ids are the people of
+              one scene and time line, at most 32 of them, and see each other.  The greedy search only (ValueError with beam_width
+              > 1).  Per primitive, after the selection (plain, with a field or with obstacles), one more launch
+              (egx_primitive_select_joint) runs `joint_sweeps` Gauss-Seidel sweeps over the members of every group in order of
+              their sequence index: member i scores each of its N candidates against the others' CURRENTLY chosen tracks with the
+              obstacle term's arithmetic - c_t the distance in the plane between the two pelvises at predicted frame t minus 2 *
+              body_radius, the cost gains pair_weight * mean_t max(0, pair_margin - c_t), a candidate with min_t c_t < 0 is in
+              the colliding class - takes the best by the selection's order, and the next member sees that choice.  The hand-off
+              continues from the joint choice; `crowd_clearance` / `crowd_hit` say whether the chosen tracks of a primitive
+              overlap.  The model and its limits: a person is a cylinder of body_radius round the pelvis; the horizon is one
+              primitive and the others' tracks are their current choices, not predictions; everybody starts from the own best and
+              two sweeps need not reach a fixed point (`joint_changed` of the last sweep says whether one did); a member that has
+              reached its goal keeps walking, and stays an obstacle, after the primitive at which its file stops.  A group of
+              one is the search without groups.  The loop stays launches only.
+            - pair_weight (1.0), pair_margin (0.5 m), joint_sweeps (2, in [1, 8]): stated choices like the others, informed by a
+              toy on the CPU only: nobody has measured motion quality with them.
         Raises FloatingPointError when a chosen hand-off, or every candidate of a sequence, held a non-finite value (read once,
         after the loop); for a beam, when a node of the returned path did."""
         from .body_model import SdfScene, SdfSceneSet
@@ -422,6 +475,7 @@ class GAMMAPrimitiveComboGenOP:
         if W * N > MAX_CANDIDATES:
             raise ValueError(f"beam_width * n_candidates must be at most {MAX_CANDIDATES}, got {W} * {N}")
         M = W * N       # rows per sequence
+        people = _person_groups(groups, data, W, pair_weight, pair_margin, body_radius, joint_sweeps)
         X, seed, bt = self._seed_inputs(data, bparams, betas, -1, None)
         b, dev, f32, i32 = X.shape[1], self.device, torch.float32, torch.int32
         goal = self._dev(goal, "goal")
@@ -488,6 +542,15 @@ class GAMMAPrimitiveComboGenOP:
         if obs_args is not None:
             s.update({"obs_scalars": (float(obstacle_weight), float(obstacle_margin), float(body_radius)), "obs_frame0": int(obstacle_frame0),
                       "obstacle_term": rec(M), "clearance": rec(M), "obstacle_hit": rec(M, dtype=i32)})
+        if people is not None:
+            S, G = int(joint_sweeps), len(people.to(dev))
+            trace = lambda *tail, dtype=f32: torch.empty(K, S, *tail, device=dev, dtype=dtype)
+            s.update({"joint": (_lib.ptr(people.group_start), _lib.ptr(people.group_member), G, S, float(pair_weight), float(pair_margin),
+                                float(body_radius), float(goal_thresh)), "joint_alive": people,
+                      "individual_choice": rec(dtype=i32), "pair_term": trace(b, N), "pair_clearance": trace(b, N),
+                      "joint_cost": trace(b, N), "pair_hit": trace(b, N, dtype=i32), "choice_trace": trace(b, dtype=i32),
+                      "joint_changed": trace(G, dtype=i32), "crowd_clearance": rec(), "crowd_hit": rec(dtype=i32),
+                      "groups": torch.as_tensor(people.ids)})
         if scene is not None:
             s["lbs_out"]["pene_count"] = torch.empty(b * M * T_ALL, device=dev, dtype=i32)
         status = s["status"]
@@ -522,20 +585,34 @@ class GAMMAPrimitiveComboGenOP:
             search.update({k: s[k] for k in ("path_slot", "parent", "beam_row", "path_cost", "beam_status")}, beam_width=W)
         if obs_args is not None:
             search.update({k: s[k] for k in PrimitiveSequence.OBSTACLE_FIELDS})
+        if people is not None:
+            search.update({k: s[k] for k in PrimitiveSequence.JOINT_FIELDS})
         return self._result(s, zc, bt, R0_end[::M].reshape(b, 3, 3).contiguous(), T0_end[::M].contiguous(), to_numpy, search)
 
     def _search_loop(self, K, b, N, s):
-        """The primitive loop of `generate_sequence_to_goal`: launches only, no allocation that depends on k, no host wait."""
+        """The primitive loop of `generate_sequence_to_goal`: launches only, no allocation that depends on k, no host wait.  With
+        groups (s["joint"]) the joint launch stands between the selection and the hand-off; a device copy keeps what the selection
+        chose."""
         lib, st, hand, pp = _lib.load(), _lib.current_stream_ptr(), self._handoff_lead(s), _lib.ptr(s["pp"])
         sel = self._select_lead(s, [s["R0"]] * 2, [s["T0"]] * 2)
         name, field, obs = self._select_tail(s, K, "egx_primitive_select")
         select = getattr(lib, name)
+        joint = s.get("joint")
+        if joint is not None:
+            joint_in = (_lib.ptr(s["lbs_out"]["joints"]), 127, _lib.ptr(s["R0"]), _lib.ptr(s["T0"]), _lib.ptr(s["goal"]))
         for k in range(K):
             nxt = s["xs"][(k + 1) % 2]
             self._primitive(s, k, s["pp"], st, s["R0"], s["T0"])
             _lib.check(select(
                 *sel[k % 2], b, N, _vp(s["choice"][k]), _vp(s["status"][k]), _vp(s["reached"][k]),
                 _vp(s["goal_dist"][k]), _vp(s["cost"][k]), _vp(s["cost_terms"][k]), _vp(s["colliding"][k]), *field, *obs[k], st), name)
+            if joint is not None:
+                s["individual_choice"][k].copy_(s["choice"][k])
+                _lib.check(lib.egx_primitive_select_joint(
+                    *joint_in, _vp(s["cost"][k]), _vp(s["cost_terms"][k]), _vp(s["colliding"][k]), b, N, *joint,
+                    _vp(s["choice"][k]), _vp(s["status"][k]), _vp(s["reached"][k]), _vp(s["goal_dist"][k]), _vp(s["pair_term"][k]),
+                    _vp(s["pair_clearance"][k]), _vp(s["joint_cost"][k]), _vp(s["pair_hit"][k]), _vp(s["choice_trace"][k]),
+                    _vp(s["joint_changed"][k]), _vp(s["crowd_clearance"][k]), _vp(s["crowd_hit"][k]), st), "egx_primitive_select_joint")
             _lib.check(lib.egx_primitive_advance_select(
                 pp, *hand[k % 2], b, _vp(s["choice"][k]), N, _lib.ptr(s["R0"]), _lib.ptr(s["T0"]), _vp(s["markers"][k]),
                 _vp(s["pelvis"][k]), _vp(s["rotmat"][k]), _vp(s["transl"][k]), _vp(s["params"][k]), _lib.ptr(s["seed"]), _vp(nxt[0]),

@@ -16,7 +16,13 @@ straight-line one.  `--avoid a.pkl,b.pkl` (with `--goal`) makes the people of ea
 frame 0 of this run): a candidate pays for coming within 0.5 m of one and is vetoed where the cylinders overlap, so a crowd is
 composed by prioritised planning, one run per person; the driver prints the minimum clearance along each written path.
 `--start x,y,yaw_deg` places the seed's world frame (the origin, facing +y, without it): two runs without it start inside each
-other.
+other.  `--people "x,y,yaw_deg:gx,gy,gz;..."` generates P people TOGETHER instead: each starts at its x,y,yaw_deg and walks to its own
+goal, and every variant of `--n-gens` is one group of those P people (`generate_sequence_to_goal(groups=)`, b = n_gens * P
+sequences) who choose each primitive against each other's current choices, so nobody has priority; one
+`motion_<seed>_<variant>_p<person>.pkl` per person, and per variant the minimum crowd clearance, the number of overlapping
+primitives along the written paths and whether the members still changed their minds in a last sweep.  It stands in for
+`--start` and `--goal` and is the greedy search (`--beam-width 1`); `--scene`, `--walkable` (one field per distinct goal) and
+`--avoid` keep working with it.
 
 `--cfg <name>` is the combo config (`crowd_ppo/cfg_samp20/<name>.yml` under the working directory, else the packaged copy): it
 names the predictor's and the regressor's configs, whose checkpoints are read from `results/crowd_ppo/<config>/checkpoints`
@@ -61,7 +67,21 @@ def main(argv=None):
     parser.add_argument("--avoid", default=None, help="comma-separated motion_*.pkl files of earlier runs: their people are moving "
                         "obstacles of this one (with --goal)")
     parser.add_argument("--start", default=None, help="x,y,yaw_deg: where the seed stands in the world and which way it faces")
+    parser.add_argument("--people", default=None, help='"x,y,yaw_deg:gx,gy,gz;...": P people with a start and a goal each, generated together; '
+                        "every variant is one group who avoid each other (instead of --start / --goal; greedy search)")
     args = parser.parse_args(argv)
+    people = None
+    if args.people is not None:
+        if args.start is not None or args.goal is not None or args.beam_width != 1:
+            parser.error("--people stands in for --start and --goal and is the greedy search (--beam-width 1)")
+        try:
+            people = np.asarray([[float(v) for half in one.split(":") for v in half.split(",")] for one in args.people.split(";") if one], np.float64)
+        except ValueError:
+            people = np.zeros((0, 6))
+        if people.ndim != 2 or people.shape[1] != 6 or not 1 <= people.shape[0] <= 32 or not np.isfinite(people).all() or \
+                any(len(one.split(":")) != 2 or len(one.split(":")[0].split(",")) != 3 for one in args.people.split(";") if one):
+            parser.error('--people takes "x,y,yaw_deg:gx,gy,gz" for 1 to 32 people, separated by ";"')
+        args.goal = ",".join(str(v) for v in people[0, 3:])          # the goal-steered path; the goals themselves follow below
     if args.goal is None and args.scene is not None:
         parser.error("--scene needs --goal")
     if args.goal is None and args.walkable is not None:
@@ -91,14 +111,22 @@ def main(argv=None):
     np.random.seed(args.seed)
     torch.manual_seed(args.seed)
     goal = field = None
-    if args.goal is not None:
+    P = 1 if people is None else people.shape[0]
+    if people is not None:          # sequence v * P + p is person p of variant v
+        goal = np.tile(people[:, 3:].astype(np.float32), (args.n_gens, 1))
+    elif args.goal is not None:
         goal = np.asarray([float(v) for v in args.goal.split(",")], np.float32)
         if goal.shape != (3,):
             raise SystemExit("--goal takes x,y,z")
     if args.walkable:        # before the models: a file without a raster, or a goal off it, ends the run here
         from egogen_amd.geodesic import GeodesicField
         try:
-            field = GeodesicField.from_scene(sw.load_scene_file(args.walkable, raster=True), goal[None])
+            distinct, of_row = np.unique(goal.reshape(-1, 3), axis=0, return_inverse=True)
+            field = GeodesicField.from_scene(sw.load_scene_file(args.walkable, raster=True), distinct)
+            if people is not None:          # one field per distinct goal is computed, every sequence then reads its own copy
+                idx = torch.as_tensor(of_row.reshape(-1), device=field.dist.device)
+                field = GeodesicField(field.dist[idx].contiguous(), field.origin[idx].contiguous(), field.cell, field.goals[idx].contiguous(),
+                                      field.passes)
         except ValueError as e:
             raise SystemExit("--walkable {}: {}".format(args.walkable, e))
         print("[INFO] geodesic field: {} x {} cells of {} m, {} passes".format(field.dist.shape[1], field.dist.shape[2], field.cell, field.passes))
@@ -132,13 +160,17 @@ def main(argv=None):
     data = can["marker_ssm2_67"].reshape(2, 1, 201).astype(np.float32)
     bparams = np.zeros((2, 1, 93), np.float32)
     bparams[:, 0, :3], bparams[:, 0, 3:69] = can["trans"], can["poses"][:, :66]
-    R0 = can["transf_rotmat"].astype(np.float32)[None].repeat(args.n_gens, 0)
-    T0 = can["transf_transl"].astype(np.float32).reshape(1, 3).repeat(args.n_gens, 0)
-    if start is not None:   # the seed's world frame turned by yaw about z and moved so that its origin stands at (x, y)
-        yaw = np.deg2rad(start[2])
+    nseq = args.n_gens * P
+    R0 = can["transf_rotmat"].astype(np.float32)[None].repeat(nseq, 0)
+    T0 = can["transf_transl"].astype(np.float32).reshape(1, 3).repeat(nseq, 0)
+    starts = [start] * nseq if people is None else [people[i % P, :3] for i in range(nseq)]
+    for i, st in enumerate(starts):
+        if st is None:
+            continue        # the seed's world frame turned by yaw about z and moved so that its origin stands at (x, y)
+        yaw = np.deg2rad(st[2])
         Rz = np.array([[np.cos(yaw), -np.sin(yaw), 0.0], [np.sin(yaw), np.cos(yaw), 0.0], [0.0, 0.0, 1.0]])
-        R0 = (Rz @ R0.astype(np.float64)).astype(np.float32)
-        T0 = (T0.astype(np.float64) @ Rz.T + np.array([start[0], start[1], 0.0])).astype(np.float32)
+        R0[i] = (Rz @ R0[i].astype(np.float64)).astype(np.float32)
+        T0[i] = (T0[i].astype(np.float64) @ Rz.T + np.array([st[0], st[1], 0.0])).astype(np.float32)
     if args.goal is None:
         res = op.generate_sequence(data, bparams, can["betas"].astype(np.float32), args.n_primitives, n_gens=args.n_gens, R0=R0, T0=T0)
     else:
@@ -147,20 +179,28 @@ def main(argv=None):
         if args.scene:
             with np.load(args.scene) as f:
                 scene = SdfScene({k: f[k] for k in ("sdf", "center", "scale")})
-        res = op.generate_sequence_to_goal(data.repeat(args.n_gens, 1), bparams.repeat(args.n_gens, 1), can["betas"].astype(np.float32),
+        groups = None if people is None else np.arange(nseq) // P
+        res = op.generate_sequence_to_goal(data.repeat(nseq, 1), bparams.repeat(nseq, 1), can["betas"].astype(np.float32),
                                            goal, args.n_primitives, args.n_candidates, scene=scene, R0=R0, T0=T0,
-                                           beam_width=args.beam_width, geodesic=field, obstacles=obstacles)
-        for i in range(args.n_gens):
+                                           beam_width=args.beam_width, geodesic=field, obstacles=obstacles, groups=groups)
+        for v in range(args.n_gens if people is not None else 0):
+            mine = range(v * P, (v + 1) * P)
+            written = np.stack([np.arange(args.n_primitives) < int(res.n_valid[i]) for i in mine], 1)          # [K,P]: the primitives the files hold
+            clear, hits = np.asarray(res.crowd_clearance)[:, mine], np.asarray(res.crowd_hit)[:, mine]
+            print("[INFO] variant {}: minimum crowd clearance {:.3f} m, crowd hits {}, members still changing in a last sweep {}".format(
+                v, float(clear[written].min()), int(hits[written].sum()), int(np.asarray(res.joint_changed)[:, -1, v].max())))
+        for i in range(nseq):
             last = int(res.n_valid[i]) - 1
             along = "" if field is None else " ({:.3f} m along the walkable raster)".format(float(res.geo_dist[last, i]))
-            print("[INFO] variant {}: {} primitives, final distance to the goal {:.3f} m{}, colliding choices {}".format(
-                i, last + 1, float(res.goal_dist[last, i]), along, int((res.status[:last + 1, i] & 1).sum())))
+            print("[INFO] {}: {} primitives, final distance to the goal {:.3f} m{}, colliding choices {}".format(
+                "variant {}".format(i) if people is None else "variant {} person {}".format(i // P, i % P), last + 1, float(res.goal_dist[last, i]), along, int((res.status[:last + 1, i] & 1).sum())))
             if obstacles is not None:
                 ch = np.asarray(res.choice[:last + 1, i], np.int64)
                 clear = np.asarray(res.clearance)[np.arange(last + 1), i, ch]
                 hits = np.asarray(res.obstacle_hit)[np.arange(last + 1), i, ch]
                 print("[INFO] variant {}: minimum clearance {:.3f} m, chosen hits {}".format(i, float(clear.min()), int(hits.sum())))
-    paths = [res.save(args.out, i, man_id="{}_{}".format(args.seed, i)) for i in range(args.n_gens)]
+    name = (lambda i: "{}_{}".format(args.seed, i)) if people is None else (lambda i: "{}_{}_p{}".format(args.seed, i // P, i % P))
+    paths = [res.save(args.out, i, man_id=name(i)) for i in range(args.n_gens * P)]
     for p in paths:
         print(p)
     with open(paths[0], "rb") as fh:

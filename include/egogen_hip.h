@@ -37,6 +37,9 @@ extern "C" {
 #define EGX_MAX_BEAM 32        /* beam slots per sequence of egx_primitive_beam_select; slots * candidates <= EGX_MAX_CANDIDATES */
 #define EGX_MAX_OBSTACLES 32   /* tracks per obstacle set of egx_primitive_select_obstacles: a choice, the 18-frame window of a set
                                   (18 x 32 xy and 32 radii, 4.7 KB) is staged into one workgroup's LDS */
+#define EGX_MAX_GROUP 32       /* people of one group of egx_primitive_select_joint: their chosen tracks (18 x 32 xy, 4.6 KB) are one
+                                  workgroup's table in LDS */
+#define EGX_MAX_SWEEPS 8       /* Gauss-Seidel sweeps of egx_primitive_select_joint */
 #define EGX_GEODESIC_OFF 1.0e4f /* metres: what a geodesic field gives where none of the four surrounding cells holds a distance */
 #define EGX_GEODESIC_BATCH 8    /* passes egx_geodesic_field launches between two reads of its flag */
 #define EGX_NUM_BETAS 10
@@ -988,6 +991,52 @@ int egx_primitive_beam_select_obstacles(const float* Y_gen, const float* x0, con
                                         const float* obs_radius, const int32_t* obs_count, const int32_t* obs_index, int num_sets,
                                         int max_obstacles, int num_frames, int frame0, float obstacle_weight, float margin,
                                         float body_radius, float* obs_term, float* obs_clearance, int32_t* obs_hit, void* stream);
+
+/* egx_primitive_select_joint - the joint step of the greedy search: the people of one scene and time line choose again against
+ * each other's CURRENT choices.  One launch between a greedy selection entry (egx_primitive_select, _field or _obstacles, whose
+ * cost [rows], cost_terms [rows,5], colliding [rows] it reads and whose choice / status / reached / goal_dist [num_sequences] it
+ * updates) and egx_primitive_advance_select; rows = num_sequences * num_candidates, joints / R0 / T0 / goal as the selection read
+ * them.  The sequences are partitioned into num_groups groups in CSR form on the device: group g holds the sequences
+ * group_member[group_start[g] .. group_start[g+1]) in that order (group_start [num_groups+1], group_member [group_start[num_groups]];
+ * an index is clamped into [0, num_sequences), a group's size to EGX_MAX_GROUP).  A sequence of no group is not touched in any
+ * output; a sequence may be in one group only.  One workgroup per group:
+ *   start   c_j = choice[j] of every member j (clamped into [0, num_candidates))
+ *   table   per member j and predicted frame t = 2..19 the world xy of joint 0 of body t of row j * N + c_j,
+ *           x = fma(R0[2], j.z, fma(R0[1], j.y, R0[0] j.x)) + T0.x, y likewise (the obstacle entries' nesting)
+ *   sweeps  `sweeps` in [1, EGX_MAX_SWEEPS] Gauss-Seidel sweeps, all of them always, members in order.  For every row n of member i,
+ *           with p_t its own world xy:
+ *             c_t = min over the members j != i of sqrt((p_t.x - x_j)^2 + (p_t.y - y_j)^2) - rr,  rr = body_radius + body_radius
+ *                   rounded once; +inf for a group of one.  Two rounded differences, two rounded squares, their rounded sum, the
+ *                   correctly rounded root, one rounded difference, no contraction (the obstacle entries' clearance).  The min
+ *                   drops a NaN distance (another member's non-finite track is not there in that frame); a NaN p_t gives NaN.
+ *             pair_clearance = min_t c_t;  pair_term = (sum_t max(0, margin - c_t)) / 18, one rounded difference per frame, the frame
+ *                   sum by the fixed tree of the wave reduction (lane t - 2 holds frame t, partners 32, 16, 8, 4, 2, 1 lanes up);
+ *                   pair_hit = pair_clearance < 0.  A NaN frame makes term and clearance NaN, and the row is not a hit.
+ *             joint_cost = cost[row] + pair_weight * pair_term, one rounded product and one rounded addition
+ *             class = (finite ? 0 : 2) | colliding[row] | pair_hit, finite = cost[row], the five cost_terms of the row, pair_term
+ *                   and joint_cost are all finite.  (With a field the selection also asks for a finite Euclidean distance, which
+ *                   cost_terms no longer holds: such a row counts as finite here.)
+ *           Member i's choice becomes the first row in the selection's order (class, joint_cost (0 where non-finite), n); column
+ *           i of the table is rewritten from it before member i + 1 is visited.
+ *   after the last sweep  crowd_clearance[i] = min_t c_t of member i's final track against the other members' final tracks (the
+ *           same arithmetic), crowd_hit[i] = crowd_clearance[i] < 0, both [num_sequences]: did the crowd as written overlap.
+ * choice is overwritten; status is rewritten: bit 0 = bit 0 of the chosen row's class, bit 1 = that class >= 2, both as evaluated
+ * in the last sweep; goal_dist / reached are rewritten ONLY where the choice changed (the selection's Euclidean distance
+ * arithmetic on the new row, reached = dist < goal_thresh) and keep the selection's bits elsewhere; cost, cost_terms and colliding are
+ * only read.  Traces: pair_term, pair_clearance, joint_cost (float), pair_hit (int32), all [sweeps,rows], every row's values as
+ * evaluated in that sweep; choice_trace [sweeps,num_sequences] the choices after each sweep; changed [sweeps,num_groups] the members
+ * that changed their choice in that sweep (0: a fixed point).  A group of one keeps the selection's choice, status, goal_dist and
+ * reached: its pair_term is 0.  512 threads per group, a wave per row with lanes 0..17 one frame each; no float atomics, no
+ * waiting, nothing between workgroups: a group's outputs are the same bits in any batch.  EGX_ERR_ARG for a NULL output,
+ * num_candidates outside [1, EGX_MAX_CANDIDATES], sweeps outside [1, EGX_MAX_SWEEPS], num_groups < 1, a negative or NaN margin or
+ * body_radius, a non-finite pair_weight. */
+int egx_primitive_select_joint(const float* joints, int joints_per_body, const float* R0, const float* T0, const float* goal,
+                               const float* cost, const float* cost_terms, const int32_t* colliding, int num_sequences,
+                               int num_candidates, const int32_t* group_start, const int32_t* group_member, int num_groups, int sweeps,
+                               float pair_weight, float margin, float body_radius, float goal_thresh, int32_t* choice,
+                               int32_t* status, int32_t* reached, float* goal_dist, float* pair_term, float* pair_clearance,
+                               float* joint_cost, int32_t* pair_hit, int32_t* choice_trace, int32_t* changed,
+                               float* crowd_clearance, int32_t* crowd_hit, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * PPO rollout glue

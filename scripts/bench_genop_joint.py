@@ -1,0 +1,176 @@
+#!/usr/bin/env python3
+"""The joint step of the greedy primitive search (egx_primitive_select_joint, `generate_sequence_to_goal(groups=)`): what it costs,
+and that the entries that existed before did not move.  GPU only.
+
+    python scripts/bench_genop_joint.py [--iters 20] [--out-dir profiles]
+    python scripts/bench_genop_joint.py --lib <parent .so> --dump outputs.pt        (once, on the parent build)
+    python scripts/bench_genop_joint.py --compare outputs.pt [--out-dir profiles]   (once, on this build)
+
+Timing, in one process: G groups of P people swap places on a circle of 2 m, N candidates each, S = 2 sweeps, at the driver's shape
+(4 variants of 4 people, N = 16) and at 8 groups x 8 people x N = 32.  Device events around --iters passes of the whole primitive
+loop (K = 4, body of --num-verts vertices, no scene) with and without `groups`, and around ten times as many single launches of
+the selection and of the joint step on the same rows; the legs alternate, three windows per leg after --warmup, median and range.
+The joint launch rewrites `choice` in place, so a repeated launch starts from its own last choice; its work does not depend on
+that: all sweeps always run over all rows.
+
+Bit identity: `--dump` writes every output of the selection entries that existed before (scripts/bench_genop_obstacles.py's
+inputs for egx_primitive_select, _select_field, _beam_select, _beam_select_field, and the obstacle entries on two of the obstacle
+tests' constructed cases); `--compare` recomputes them and compares bit for bit.
+Writes the sections between the `timings` and the `identity` markers of `<out-dir>/genop_joint.md`."""
+import argparse
+import ctypes as C
+import os
+import sys
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "scripts"))
+
+from egogen_amd import _lib  # noqa: E402
+
+MARKS = {"timings": ("<!-- timings:begin -->", "<!-- timings:end -->"), "identity": ("<!-- identity:begin -->", "<!-- identity:end -->")}
+NEW = ("egx_primitive_select_joint",)
+SHAPES = ((4, 4, 16), (8, 8, 32))       # G, P, N
+K, S = 4, 2
+
+
+def use_library(path):
+    """every later `_lib.load()` opens `path`; a build from before the joint entry simply lacks its symbol"""
+    _lib.LIB_PATH = os.path.abspath(path)
+    probe = C.CDLL(_lib.LIB_PATH)
+    for name in NEW:
+        if not hasattr(probe, name):
+            _lib.SIGNATURES.pop(name, None)
+
+
+def write_section(out_dir, which, lines):
+    begin, end = MARKS[which]
+    md = os.path.join(out_dir, "genop_joint.md")
+    os.makedirs(out_dir, exist_ok=True)
+    txt = open(md).read() if os.path.exists(md) else "# The joint primitive search\n"
+    body = "\n".join([begin] + lines + [end])
+    if begin in txt and end in txt:
+        txt = txt[:txt.index(begin)] + body + txt[txt.index(end) + len(end):]
+    else:
+        txt += "\n" + body + "\n"
+    with open(md, "w") as fh:
+        fh.write(txt)
+
+
+# ---- bit identity of the entries that existed before -----------------------------------------------------------------------
+def existing_outputs():
+    from bench_genop_obstacles import existing_outputs as without_obstacles
+    from tests import genop_gpu_helpers as gh
+    from tests import test_genop_obstacles_gpu as to
+    out = without_obstacles()
+    from egogen_amd import synth
+    from egogen_amd.body_model import BodyModelHandle
+    V = gh.V_SMALL
+    world = {"handle": BodyModelHandle(synth.make_body_model(0, num_verts=V), synth.marker_ids(V), synth.feet_vids(V))}
+    for b, N, O, T, beam in ((3, 5, 2, 19, None), (65, 5, 32, 200, None), (3, 6, 6, 40, (2, 3))):
+        x = to._lattice(gh._rows_inputs(world, b, N, 400 + b * 7 + N, True), b, N)
+        ob = to._obs(to._tracks(to._pelvis64(x, 127, b, N), b, N, O, T, 3, True, 0, list(range(b))), to.RADIUS, index=list(range(b)), frame0=3)
+        for k, v in to._select_obs(x, 127, ob, beam=beam)[0].items():
+            out[f"select_obstacles b={b} N={N} O={O} beam={beam} {k}"] = v
+    return out
+
+
+def same_bits(a, b):
+    return a.shape == b.shape and a.dtype == b.dtype and bool((a.contiguous().view(torch.int32) == b.contiguous().view(torch.int32)).all())
+
+
+# ---- timing ---------------------------------------------------------------------------------------------------------------------
+def timings(args):
+    from bench_genop import alternate
+    from bench_genop_search import build_op, captured, seeds
+    lib = _lib.load()
+    op, body = build_op(args.num_verts)
+    g = torch.Generator().manual_seed(1)
+    vp = lambda t: C.c_void_p(t.data_ptr())
+    fmt = lambda v: f"{v['median_us']:.1f} ({v['min_us']:.1f} .. {v['max_us']:.1f})"
+    lines = [f"Device: {torch.cuda.get_device_name(0)}; K = {K} primitives, body of {args.num_verts} vertices, no scene, S = {S} sweeps; one "
+             f"process, {args.iters} loop passes or {10 * args.iters} launches per window, three windows per leg, the legs taking turns.  "
+             "Microseconds: median (range of the windows); loops per primitive.", "",
+             "| shape | leg | us |", "|---|---|---|"]
+    notes = []
+    for G, P, N in SHAPES:
+        b = G * P
+        data, xb, betas = seeds(body, b, g)
+        z = torch.randn(K, b * N, 128, generator=g).cuda()
+        ang = 2 * np.pi * (np.arange(b) % P) / P                      # the P people of a group swap places on a circle of 2 m
+        T0 = torch.tensor(np.stack([2.0 * np.cos(ang), 2.0 * np.sin(ang), np.zeros(b)], -1), dtype=torch.float32)
+        yaw = ang + np.pi / 2                                         # the seed walks along +y: turned to face the centre
+        R0 = torch.tensor(np.stack([np.stack([np.cos(yaw), -np.sin(yaw), 0 * yaw], -1), np.stack([np.sin(yaw), np.cos(yaw), 0 * yaw], -1),
+                                    np.stack([0 * yaw, 0 * yaw, 1 + 0 * yaw], -1)], 1), dtype=torch.float32)
+        goal = -T0 + torch.tensor([0.0, 0.0, 0.9])
+        kw = dict(z=z, T0=T0, R0=R0, to_numpy=False)
+        groups = np.arange(b) // P
+        plain, _ = captured(op, "_search_loop", lambda: op.generate_sequence_to_goal(data, xb, betas, goal, K, N, **kw))
+        res = {}
+        joint, sf = captured(op, "_search_loop",
+                             lambda: res.update(r=op.generate_sequence_to_goal(data, xb, betas, goal, K, N, groups=groups, joint_sweeps=S, **kw)))
+        s, st = sf[3], _lib.current_stream_ptr()
+        cur, lbs, k = s["xs"][(K - 1) % 2], s["lbs_out"], K - 1
+        outs = (vp(s["choice"][k]), vp(s["status"][k]), vp(s["reached"][k]), vp(s["goal_dist"][k]))
+        rows = (vp(s["cost"][k]), vp(s["cost_terms"][k]), vp(s["colliding"][k]))
+        lead = (_lib.ptr(s["Y_gen"]), vp(cur[0]), vp(cur[1]), 201, _lib.ptr(lbs["joints"]), 127, _lib.ptr(lbs["markers"]), _lib.ptr(s["R0"]),
+                _lib.ptr(s["T0"]), None, _lib.ptr(s["goal"]), _lib.ptr(s["feet"]), s["weights"], s["pene_thres"], s["goal_thresh"], s["rf"], b, N)
+        jargs = (_lib.ptr(lbs["joints"]), 127, _lib.ptr(s["R0"]), _lib.ptr(s["T0"]), _lib.ptr(s["goal"]), *rows, b, N, *s["joint"], *outs,
+                 vp(s["pair_term"][k]), vp(s["pair_clearance"][k]), vp(s["joint_cost"][k]), vp(s["pair_hit"][k]), vp(s["choice_trace"][k]),
+                 vp(s["joint_changed"][k]), vp(s["crowd_clearance"][k]), vp(s["crowd_hit"][k]))
+        launches = {"select launch": lambda: _lib.check(lib.egx_primitive_select(*lead, *outs, *rows, st), "egx_primitive_select"),
+                    "joint launch": lambda: _lib.check(lib.egx_primitive_select_joint(*jargs, st), "egx_primitive_select_joint")}
+        t = alternate({"loop without groups": plain, "loop with groups": joint}, args.iters, args.warmup)
+        for v in t.values():
+            for q in ("median_us", "min_us", "max_us"):
+                v[q] /= K
+        t.update(alternate(launches, 10 * args.iters, args.warmup))
+        for name, v in t.items():
+            lines.append(f"| G={G} P={P} N={N} (b={b}) | {name} | {fmt(v)} |")
+        r = res["r"]
+        notes.append(f"G={G} P={P} N={N}: members that changed their choice per primitive, first / last sweep: "
+                     f"{r.joint_changed[:, 0].sum(1).tolist()} / {r.joint_changed[:, -1].sum(1).tolist()}; crowd hits per primitive "
+                     f"{r.crowd_hit.sum(1).tolist()}.")
+    lines += [""] + notes
+    write_section(args.out_dir, "timings", lines)
+    print("\n".join(lines))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out-dir", default=os.path.join(ROOT, "profiles"))
+    ap.add_argument("--lib", default=None, help="run on this build of libegogen_hip.so instead of the package's")
+    ap.add_argument("--dump", default=None)
+    ap.add_argument("--compare", default=None)
+    ap.add_argument("--iters", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--num-verts", type=int, default=None)
+    args = ap.parse_args()
+    if args.num_verts is None:
+        from egogen_amd import synth
+        args.num_verts = synth.NUM_VERTS
+    if args.lib:
+        use_library(args.lib)
+    if not torch.cuda.is_available():
+        sys.exit("bench_genop_joint.py measures on the GPU; no device is visible")
+    if args.dump:
+        torch.save(existing_outputs(), args.dump)
+        print(f"wrote {args.dump}")
+    elif args.compare:
+        want, got = torch.load(args.compare), existing_outputs()
+        differ = sorted(k for k in want if k not in got or not same_bits(want[k], got[k])) + sorted(k for k in got if k not in want)
+        lines = [f"{len(want)} outputs of egx_primitive_select, _select_field, _beam_select, _beam_select_field, _select_obstacles and "
+                 f"_beam_select_obstacles on the pooled test inputs, dumped by the parent commit's build and recomputed by this one: "
+                 + ("every one bit-identical." if not differ else f"{len(differ)} differ: " + "; ".join(differ[:20]) + ".")]
+        write_section(args.out_dir, "identity", lines)
+        print(lines[0])
+        sys.exit(1 if differ else 0)
+    else:
+        timings(args)
+
+
+if __name__ == "__main__":
+    main()
