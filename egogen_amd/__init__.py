@@ -8,4 +8,7 @@ def __getattr__(name):      # `from egogen_amd import GeodesicField` without imp
     if name == "PersonGroups":
         from .crowd import PersonGroups
         return PersonGroups
+    if name == "PolicyProposal":
+        from .proposal import PolicyProposal
+        return PolicyProposal
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

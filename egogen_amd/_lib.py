@@ -232,6 +232,12 @@ SIGNATURES = {
     # num_groups, sweeps, pair_weight, margin, body_radius, goal_thresh, then the twelve outputs and the stream
     "egx_primitive_select_joint": (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 6 + [C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                              C.c_int, C.c_int] + [C.c_float] * 4 + [C.c_void_p] * 13),
+    # joints, frames_per_row, first_frame, choice, num_candidates, R_prev, T_prev, R0, T0, x0, x1, x_ld, goal, edges, edge_off, scene_idx,
+    # num_scenes, ray_len, step, max_depth, num_sequences, state, egosensing, dist, time, stream
+    "egx_primitive_observe": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 6 + [C.c_int] +
+                              [C.c_void_p] * 4 + [C.c_int, C.c_float, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 5),
+    "egx_policy_propose": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int,
+                                     C.c_float, C.c_void_p, C.c_void_p]),
     "egx_sample_action": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_int, C.c_int, C.c_void_p,
                                     C.c_void_p, C.c_void_p]),
     "egx_gae": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double, C.c_void_p,

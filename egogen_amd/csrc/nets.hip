@@ -7,6 +7,7 @@
 // builds them with torch.cat: models_GAMMA_primitive.py:93,257; models_policy_ppo.py:305) - no copy is made.
 // Weights are read in torch's own [N,K] layout so the same storage serves the autograd update path.
 #include <mutex>
+#include "egx_action.h"
 #include "egx_nets.h"
 
 namespace {
@@ -342,11 +343,11 @@ __global__ void egx_sample_action_kernel(const float* __restrict__ mu, float* __
   const int c = threadIdx.x;
   __shared__ float sh[128];
   const size_t i = (size_t)row * 128 + c;
-  const float lv = fminf(fmaxf(logvar[i], min_lv), max_lv);
+  const float lv = egx_action_clamp_logvar(logvar[i], min_lv, max_lv);
   logvar[i] = lv;
-  const float sigma = sqrtf(expf(lv));
+  const float sigma = egx_action_sigma(lv);
   const float e = deterministic ? 0.f : eps[i];
-  const float a = mu[i] + sigma * e;
+  const float a = egx_action_sample(mu[i], sigma, e);
   act[i] = a;
   const float d = a - mu[i];
   sh[c] = -(d * d) / (2.f * sigma * sigma) - logf(sigma) - 0.91893853320467274178f;

@@ -13,7 +13,11 @@ egx_primitive_beam_select_field).  With `obstacles=` (a `MovingObstacles`, egoge
 other people's recorded tracks: a clearance term in the cost and a veto on overlap (entries egx_primitive_select_obstacles,
 egx_primitive_beam_select_obstacles).  With `groups=` (ids, or a `PersonGroups`, egogen_amd/crowd.py) the sequences of one group of the
 greedy search see each other: after the selection the members choose again against each other's current choices (entry
-egx_primitive_select_joint, csrc/genop_joint.hip), and the hand-off continues from that joint choice.
+egx_primitive_select_joint, csrc/genop_joint.hip), and the hand-off continues from that joint choice.  With `policy=` (a
+`PolicyProposal`, egogen_amd/proposal.py) the candidates of the greedy search are no longer all drawn from N(0, I): per primitive
+every sequence senses its surroundings (entry egx_primitive_observe, csrc/genop_policy.hip), the trained policy's actor proposes
+mu, logvar over the latent, and the candidate rows become mu, samples round it and a share of prior samples (entry
+egx_policy_propose); the selection scores them as before.
 
 The three chains share their host path: `_chain_state` builds the state dict (checked inputs, defaults, the loop's buffers, the
 records) for b seeds of M rows each, `_primitive` launches what every primitive begins with (prior, parameter assembly, body
@@ -123,6 +127,8 @@ class PrimitiveSequence:
     OBSTACLE_FIELDS = ("obstacle_term", "clearance", "obstacle_hit")
     JOINT_FIELDS = ("individual_choice", "pair_term", "pair_clearance", "pair_hit", "joint_cost", "choice_trace", "joint_changed",
                     "crowd_clearance", "crowd_hit", "groups")
+    POLICY_FIELDS = ("policy_mu", "policy_logvar", "obs_state", "obs_egosensing", "obs_dist", "obs_time", "policy_temperature",
+                     "policy_n_mean", "policy_n_policy", "policy_ray_len", "policy_max_depth")
 
     def __init__(self, markers, params, rotmat, transl, pelvis, z, betas, gender, R0, T0, search: Optional[dict] = None):
         self.markers, self.params, self.rotmat, self.transl, self.pelvis, self.z = markers, params, rotmat, transl, pelvis, z
@@ -130,7 +136,7 @@ class PrimitiveSequence:
         self.search = search
         for k in self.SEARCH_FIELDS:
             setattr(self, k, None if search is None else search[k])
-        for k in self.BEAM_FIELDS + self.OBSTACLE_FIELDS + self.JOINT_FIELDS:
+        for k in self.BEAM_FIELDS + self.OBSTACLE_FIELDS + self.JOINT_FIELDS + self.POLICY_FIELDS:
             setattr(self, k, None if search is None else search.get(k))
 
     def primitives(self, i: int) -> list:
@@ -402,7 +408,7 @@ class GAMMAPrimitiveComboGenOP:
                                   beam_width: int = 1, geodesic=None, obstacles=None, obstacle_weight: float = 1.0,
                                   obstacle_margin: float = 0.5, body_radius: float = 0.3,
                                   obstacle_frame0: int = 0, groups=None, pair_weight: float = 1.0, pair_margin: float = 0.5,
-                                  joint_sweeps: int = 2) -> PrimitiveSequence:
+                                  joint_sweeps: int = 2, policy=None) -> PrimitiveSequence:
         """`generate_sequence` steered to a goal through a scene by a greedy best-of-N search: for each of the `n_primitives`
         primitives, `n_candidates` candidates per sequence are generated, scored and the best one is kept; every candidate of the
         next primitive continues from it.  data / bparams / betas / reproj_factor / R0 / T0 as in `generate_sequence` (b seeds,
@@ -459,6 +465,16 @@ class GAMMAPrimitiveComboGenOP:
               one is the search without groups.  The loop stays launches only.
             - pair_weight (1.0), pair_margin (0.5 m), joint_sweeps (2, in [1, 8]): stated choices like the others, informed by a
               toy on the CPU only: nobody has measured motion quality with them.
+            - policy: None, or a `PolicyProposal` (egogen_amd/proposal.py): the trained policy as the proposal distribution.  The
+              greedy search only (ValueError with beam_width > 1).  `z` (supplied or drawn up front) becomes the eps of the
+              proposal.  Before the loop one body-model forward of the b x 2 seed bodies gives the first observation its joints;
+              per primitive, ahead of the prefix above: egx_primitive_observe (the observation the env would hand the policy after
+              the chosen primitive, from the hand-off's records) -> the policy's actor into the records -> egx_policy_propose,
+              which rewrites the rows of z[k]: the first n_mean of a sequence become mu, the rows up to n_policy mu + temperature
+              * sigma * eps, the rest stay eps, the prior's samples.  scene, geodesic, obstacles and groups act after the proposal
+              and work as without it.  The returned z is the chosen row of the rewritten candidates.  The loop stays launches
+              only.  The proposal's parameters are stated choices (see `PolicyProposal`): nobody has measured motion quality with
+              them.
         Raises FloatingPointError when a chosen hand-off, or every candidate of a sequence, held a non-finite value (read once,
         after the loop); for a beam, when a node of the returned path did."""
         from .body_model import SdfScene, SdfSceneSet
@@ -475,6 +491,12 @@ class GAMMAPrimitiveComboGenOP:
         if W * N > MAX_CANDIDATES:
             raise ValueError(f"beam_width * n_candidates must be at most {MAX_CANDIDATES}, got {W} * {N}")
         M = W * N       # rows per sequence
+        if policy is not None:
+            from .proposal import PolicyProposal, check_beam
+            if not isinstance(policy, PolicyProposal):
+                raise TypeError(f"policy must be None or a PolicyProposal, got {type(policy).__name__}")
+            check_beam(W)
+            policy.counts(N)
         people = _person_groups(groups, data, W, pair_weight, pair_margin, body_radius, joint_sweeps)
         X, seed, bt = self._seed_inputs(data, bparams, betas, -1, None)
         b, dev, f32, i32 = X.shape[1], self.device, torch.float32, torch.int32
@@ -553,6 +575,11 @@ class GAMMAPrimitiveComboGenOP:
                       "groups": torch.as_tensor(people.ids)})
         if scene is not None:
             s["lbs_out"]["pene_count"] = torch.empty(b * M * T_ALL, device=dev, dtype=i32)
+        s["policy"] = policy
+        if policy is not None:
+            if z is not None:
+                s["z"] = s["z"].clone()         # the proposal overwrites its eps in place: never the caller's tensor
+            policy.prepare(self, s, K, b, N)
         status = s["status"]
         if W == 1:
             self._search_loop(K, b, N, s)
@@ -587,6 +614,8 @@ class GAMMAPrimitiveComboGenOP:
             search.update({k: s[k] for k in PrimitiveSequence.OBSTACLE_FIELDS})
         if people is not None:
             search.update({k: s[k] for k in PrimitiveSequence.JOINT_FIELDS})
+        if policy is not None:
+            search.update(policy.record(s))
         return self._result(s, zc, bt, R0_end[::M].reshape(b, 3, 3).contiguous(), T0_end[::M].contiguous(), to_numpy, search)
 
     def _search_loop(self, K, b, N, s):
@@ -597,11 +626,13 @@ class GAMMAPrimitiveComboGenOP:
         sel = self._select_lead(s, [s["R0"]] * 2, [s["T0"]] * 2)
         name, field, obs = self._select_tail(s, K, "egx_primitive_select")
         select = getattr(lib, name)
-        joint = s.get("joint")
+        joint, policy = s.get("joint"), s.get("policy")
         if joint is not None:
             joint_in = (_lib.ptr(s["lbs_out"]["joints"]), 127, _lib.ptr(s["R0"]), _lib.ptr(s["T0"]), _lib.ptr(s["goal"]))
         for k in range(K):
             nxt = s["xs"][(k + 1) % 2]
+            if policy is not None:
+                policy.launch(s, k, b, N, st)
             self._primitive(s, k, s["pp"], st, s["R0"], s["T0"])
             _lib.check(select(
                 *sel[k % 2], b, N, _vp(s["choice"][k]), _vp(s["status"][k]), _vp(s["reached"][k]),

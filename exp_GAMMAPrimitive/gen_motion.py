@@ -22,7 +22,12 @@ sequences) who choose each primitive against each other's current choices, so no
 `motion_<seed>_<variant>_p<person>.pkl` per person, and per variant the minimum crowd clearance, the number of overlapping
 primitives along the written paths and whether the members still changed their minds in a last sweep.  It stands in for
 `--start` and `--goal` and is the greedy search (`--beam-width 1`); `--scene`, `--walkable` (one field per distinct goal) and
-`--avoid` keep working with it.
+`--avoid` keep working with it.  `--policy CKPT` (with `--goal` or `--people`; the greedy search) makes a trained policy the proposal
+distribution of the search (`PolicyProposal`, egogen_amd/proposal.py): the checkpoint main_ppo.py writes (key `model`) is loaded into
+`setup_world.build_policy`'s networks, and per primitive every sequence's observation, with its 32 egosensing rays cast against the
+walkable polygon `--polygon FILE` (default: the file given to `--walkable` or `--scene` where that file holds `edges`; else no
+polygon, every ray reads +1), gives mu, sigma over the latent; the candidates are mu, samples round it (`--policy-temperature`
+scales sigma) and a share `--policy-prior-fraction` of prior samples.  Nobody has measured motion quality with these defaults.
 
 `--cfg <name>` is the combo config (`crowd_ppo/cfg_samp20/<name>.yml` under the working directory, else the packaged copy): it
 names the predictor's and the regressor's configs, whose checkpoints are read from `results/crowd_ppo/<config>/checkpoints`
@@ -69,6 +74,12 @@ def main(argv=None):
     parser.add_argument("--start", default=None, help="x,y,yaw_deg: where the seed stands in the world and which way it faces")
     parser.add_argument("--people", default=None, help='"x,y,yaw_deg:gx,gy,gz;...": P people with a start and a goal each, generated together; '
                         "every variant is one group who avoid each other (instead of --start / --goal; greedy search)")
+    parser.add_argument("--policy", default=None, help="checkpoint of a trained policy (main_ppo.py, key 'model'): the proposal distribution "
+                        "of the search (with --goal or --people; greedy search)")
+    parser.add_argument("--policy-temperature", type=float, default=1.0, help="scale of the policy's sigma (with --policy)")
+    parser.add_argument("--policy-prior-fraction", type=float, default=0.25, help="share of the candidates left as prior samples (with --policy)")
+    parser.add_argument("--polygon", default=None, help="scene file with the walkable polygon (`edges`) the egosensing rays are cast against, or "
+                        "room0 (with --policy); default: the --walkable or --scene file where it holds edges")
     args = parser.parse_args(argv)
     people = None
     if args.people is not None:
@@ -90,6 +101,27 @@ def main(argv=None):
         parser.error("--beam-width needs --goal")
     if args.goal is None and args.avoid is not None:
         parser.error("--avoid needs --goal")
+    if args.policy is None and (args.polygon is not None or args.policy_temperature != 1.0 or args.policy_prior_fraction != 0.25):
+        parser.error("--polygon, --policy-temperature and --policy-prior-fraction need --policy")
+    if args.policy is not None and (args.goal is None or args.beam_width != 1):
+        parser.error("--policy needs --goal (or --people) and is the greedy search (--beam-width 1)")
+    polygon = None
+    if args.policy is not None:          # before the models and the device: a bad file ends the run here
+        from egogen_amd.proposal import scene_file_edges
+        if not os.path.exists(args.policy):
+            raise SystemExit("--policy {}: no such file".format(args.policy))
+        for f in [args.polygon] if args.polygon else [args.walkable, args.scene]:
+            if f is None:
+                continue
+            try:
+                polygon = scene_file_edges(f)
+                print("[INFO] egosensing against the {} edges of {}".format(len(polygon), f))
+                break
+            except (OSError, ValueError, KeyError) as e:
+                if args.polygon:
+                    raise SystemExit("--polygon {}: {}".format(f, e))
+        if polygon is None:
+            print("[INFO] no walkable polygon: every egosensing ray reads +1")
     start = None
     if args.start is not None:
         try:
@@ -180,9 +212,21 @@ def main(argv=None):
             with np.load(args.scene) as f:
                 scene = SdfScene({k: f[k] for k in ("sdf", "center", "scale")})
         groups = None if people is None else np.arange(nseq) // P
+        proposal = None
+        if args.policy is not None:
+            from egogen_amd.proposal import PolicyProposal
+            pargs = argparse.Namespace(seed=args.seed, lr=3e-4, gamma=0.99, gae_lambda=0.95, max_grad_norm=0.1, vf_coef=1.0, ent_coef=0.01,
+                                       weight_kld=0.0, rew_norm=False, eps_clip=0.1, value_clip=0, dual_clip=None, norm_adv=1, recompute_adv=0,
+                                       deterministic_eval=True)
+            policy = sw.build_policy(pargs)
+            policy.load_state_dict(torch.load(args.policy, map_location="cuda")["model"])
+            policy.eval()
+            proposal = PolicyProposal(policy, edges=polygon, temperature=args.policy_temperature, prior_fraction=args.policy_prior_fraction)
+            print("[INFO] policy {}: {} of {} candidates from the policy, {} of them its mean".format(
+                args.policy, proposal.counts(args.n_candidates)[1], args.n_candidates, proposal.counts(args.n_candidates)[0]))
         res = op.generate_sequence_to_goal(data.repeat(nseq, 1), bparams.repeat(nseq, 1), can["betas"].astype(np.float32),
                                            goal, args.n_primitives, args.n_candidates, scene=scene, R0=R0, T0=T0,
-                                           beam_width=args.beam_width, geodesic=field, obstacles=obstacles, groups=groups)
+                                           beam_width=args.beam_width, geodesic=field, obstacles=obstacles, groups=groups, policy=proposal)
         for v in range(args.n_gens if people is not None else 0):
             mine = range(v * P, (v + 1) * P)
             written = np.stack([np.arange(args.n_primitives) < int(res.n_valid[i]) for i in mine], 1)          # [K,P]: the primitives the files hold

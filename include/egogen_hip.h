@@ -1038,6 +1038,50 @@ int egx_primitive_select_joint(const float* joints, int joints_per_body, const f
                                float* joint_cost, int32_t* pair_hit, int32_t* choice_trace, int32_t* changed,
                                float* crowd_clearance, int32_t* crowd_hit, void* stream);
 
+/* egx_primitive_observe - the observation of every sequence of the search as the env would have it after the chosen primitive
+ * (crowd_ppo/crowd_env_2f.py:311-312 what step() returns; _calc_egosensing :524-613; _get_feature :680-727): the values
+ * egx_env_step_post writes to state, obs_ego, obs_dist and obs_time, through the same device functions (csrc/egx_egosense.h,
+ * egx_reward.h, egx_frame.h), from what a hand-off entry left on the device.  One launch ahead of egx_policy_forward.
+ *   joints [rows * frames_per_row, joints 127, 3], rows = num_sequences * num_candidates; the two seed bodies of sequence i are the
+ *          frames first_frame and first_frame + 1 (18 of 20 for a primitive, 0 of 2 for the start) of row i * N + c_i, c_i =
+ *          choice[i] clamped into [0, num_candidates), 0 where choice is NULL
+ *   R_prev [num_sequences,9] / T_prev [num_sequences,3]  the frame those joints are expressed in (the rotmat / transl record of the
+ *          hand-off); R0 [rows,9] / T0 [rows,3] the new frame and x0 / x1 the new seed frames (201 values a row, row stride x_ld
+ *          floats), all read at row i * N: the hand-off writes the same values to the N rows of a sequence
+ *   goal [num_sequences,3] world;  edges [E,4] (x0,y0,x1,y1) / edge_off [num_scenes+1] / scene_idx [num_sequences] (clamped into
+ *          [0, num_scenes)) the walkable polygons as ring edges, all three NULL for no polygon
+ * Outputs, row i from sequence i's inputs alone:
+ *   state [num_sequences,2,402]   per seed frame the 201 marker coordinates of x0 / x1 as they are, then for every marker the unit
+ *          vector to target_l = R0^T (goal - T0) (marker_target_feature)
+ *   egosensing [num_sequences,2,32]  per seed body -1 + 2 d / ray_len over 32 rays about the look-at direction, from the world
+ *          positions R_prev j + T_prev of joints 23, 24, 56, 57 (egosensing_frame, float64); an eye outside the polygon reads -1 in
+ *          every ray; without a polygon every ray reads +1 (the eye is inside an unbounded plane, d = ray_len)
+ *   dist [num_sequences] = 1 / (d + 1), d = |R_prev^T (goal - T_prev) - joint 0 of the second seed body| clipped at 1e-12
+ *          (target_to_local, target_distance);  time [num_sequences] = 1 - min(step, max_depth) / max_depth: the policy never saw a
+ *          step above max_depth
+ * 256 threads per sequence: wave 0 holds the 64 (frame, ray) pairs, the other waves the markers; a scene of up to 1024 edges is
+ * staged in LDS once per workgroup.  No atomics, no waiting.  The outputs must not alias the inputs.  EGX_ERR_ARG for a NULL
+ * argument, num_candidates outside [1, EGX_MAX_CANDIDATES], seed bodies outside a row, x_ld < 201, some but not all of the polygon
+ * arrays, ray_len <= 0, step < 0, max_depth < 1. */
+int egx_primitive_observe(const float* joints, int frames_per_row, int first_frame, const int32_t* choice, int num_candidates,
+                          const float* R_prev, const float* T_prev, const float* R0, const float* T0, const float* x0, const float* x1,
+                          int x_ld, const float* goal, const float* edges, const int32_t* edge_off, const int32_t* scene_idx,
+                          int num_scenes, float ray_len, int step, int max_depth, int num_sequences, float* state, float* egosensing,
+                          float* dist, float* time, void* stream);
+
+/* egx_policy_propose - the candidate latents of every sequence from the policy's distribution (crowd_ppo/ppo_policy.py:169-178, the
+ * arithmetic of egx_sample_action through the same device functions, csrc/egx_action.h).  mu / logvar [num_sequences,128] as
+ * egx_policy_forward returns them (logvar unclamped), eps / z [num_sequences * num_candidates, 128]; z may be eps.  Row n of
+ * sequence i:
+ *   n < n_mean              z = mu[i], its bits
+ *   n_mean <= n < n_policy  z = mu[i] + (temperature * exp(clamp(logvar[i], min_logvar, max_logvar))^0.5) * eps, the product in
+ *                           brackets rounded once; temperature 0 gives mu[i]
+ *   n >= n_policy           z = eps, bit for bit: the prior's sample
+ * One thread per four values, 16-byte accesses.  EGX_ERR_ARG for a NULL or misaligned argument, num_candidates outside
+ * [1, EGX_MAX_CANDIDATES], not 0 <= n_mean <= n_policy <= num_candidates, a negative or NaN temperature, min_logvar > max_logvar. */
+int egx_policy_propose(const float* mu, const float* logvar, const float* eps, float min_logvar, float max_logvar, int num_sequences,
+                       int num_candidates, int n_mean, int n_policy, float temperature, float* z, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * PPO rollout glue
  * ------------------------------------------------------------------------------------------- */

@@ -1,0 +1,151 @@
+"""The policy proposal of the primitive search without a device: the restatement of tests/genop_policy_ref.py against the oracle's
+functions on the polygons the GPU test uses, the share of undecidable rays of those cases, and the argument checks of
+`PolicyProposal` / `generate_sequence_to_goal(policy=)`."""
+import types
+
+import numpy as np
+import pytest
+import torch
+
+from oracle.env import calc_egosensing, get_feature
+from tests import genop_policy_ref as ref
+from tests.genop_gpu_helpers import UNDECIDABLE_CAP
+
+RAY_LEN = 7.0
+
+
+@pytest.mark.parametrize("kind", ["square", "two"])
+def test_restatement_equals_oracle_functions(kind):
+    """Square with one hole, and room0 (6 rings, 89 edges) as scene 1 of two: rays = calc_egosensing on the world joints, directions =
+    get_feature's fea_marker_3d_n against the new frame, dist = 1 / (1 + dist_xyz) of the second seed body in the joints' frame."""
+    poly = ref.polygon(kind)
+    edges, off, idx, eyes = poly
+    d = ref.observe_inputs(5, 20, 18, eyes)
+    state, ego, dist, time = ref.observe_case(d, poly, RAY_LEN, 4, 13, torch.float64)
+    j2 = ref.seed_bodies(d).double()
+    N = d["N"]
+    R_prev, T_prev = d["R_prev"].double(), d["T_prev"].double()
+    jw = torch.einsum("bij,btkj->btki", R_prev, j2) + T_prev[:, None, None]
+    for i in range(ref.B):
+        e = edges.astype(np.float64)[off[idx[i]]:off[idx[i] + 1]]
+        assert torch.equal(ego[i], calc_egosensing(jw[i], e, RAY_LEN))
+    Y = torch.stack([d["x0"][::N], d["x1"][::N]], 1).double()
+    fea = get_feature(Y, j2[:, :, 0], d["R0"][::N].double(), d["T0"][::N].double()[:, None], d["goal"].double()[:, None])[3]
+    assert torch.equal(state[..., :201], Y) and torch.equal(state[..., 201:], fea)
+    dxyz = get_feature(Y, j2[:, :, 0], R_prev, T_prev[:, None], d["goal"].double()[:, None])[1]
+    assert torch.equal(dist, 1.0 / (dxyz[:, 1, 0] + 1.0))
+    assert torch.equal(time, torch.full((ref.B,), 1.0 - 4.0 / 13.0, dtype=torch.float64))
+    assert float(ego.min()) == -1.0 and float(ego.max()) > -0.5         # one start outside its polygon, the others see walls
+
+
+def test_time_is_clamped_and_no_polygon_reads_one():
+    d = ref.observe_inputs(1, 2, 0, None)
+    _, ego, _, time = ref.observe_case(d, None, RAY_LEN, 40, 13, torch.float32)
+    assert torch.equal(time, torch.zeros(ref.B)) and torch.equal(ego, torch.ones(ref.B, 2, 32))
+
+
+def test_undecidable_rays_stay_under_the_cap():
+    """The eye positions of the GPU test's cases: the float64 restatement alone leaves out at most UNDECIDABLE_CAP of all rays."""
+    left_out = total = 0
+    for kind, N, (fpr, first) in ref.OBSERVE_CASES:
+        poly = ref.polygon(kind)
+        if poly is None:
+            continue
+        u = ref.undecidable(ref.observe_inputs(N, fpr, first, poly[3]), poly, RAY_LEN)
+        left_out, total = left_out + int(u.sum()), total + u.numel()
+    assert total > 0 and left_out / total <= UNDECIDABLE_CAP, (left_out, total)
+
+
+def test_outside_start_reads_minus_one():
+    poly = ref.polygon("square")
+    d = ref.observe_inputs(1, 20, 18, poly[3])
+    ego = ref.observe_case(d, poly, RAY_LEN, 0, 13, torch.float64)[1]
+    assert torch.equal(ego[2], -torch.ones(2, 32)) and float(ego[:2].min()) > -1.0
+
+
+@pytest.mark.parametrize("n_mean,n_policy,temperature", [(0, 0, 1.0), (1, 5, 0.5), (5, 5, 1.0), (1, 4, 0.0)])
+def test_propose_restatement(n_mean, n_policy, temperature):
+    N = 5
+    mu, logvar, eps = ref.propose_inputs(N)
+    z = ref.propose(mu, logvar, eps, -2.5, 2.5, N, n_mean, n_policy, temperature, torch.float64).reshape(ref.B, N, 128)
+    e = eps.double().reshape(ref.B, N, 128)
+    assert torch.equal(z[:, :n_mean], mu.double()[:, None].expand(ref.B, n_mean, 128))
+    assert torch.equal(z[:, n_policy:], e[:, n_policy:])
+    sigma = torch.exp(logvar.double().clamp(-2.5, 2.5)) ** 0.5
+    assert torch.equal(z[:, n_mean:n_policy], (mu.double()[:, None] + (temperature * sigma)[:, None] * e)[:, n_mean:n_policy])
+    lo, hi = torch.exp(torch.tensor([-2.5, 2.5], dtype=torch.float64)) ** 0.5
+    assert bool((sigma[0] == lo).all()) and bool((sigma[1] == hi).all())        # both rows wholly clamped
+    if temperature == 0.0:
+        assert torch.equal(z[:, :n_policy], mu.double()[:, None].expand(ref.B, n_policy, 128))
+
+
+# ---- argument checks -------------------------------------------------------------------------------------------------
+def _runner():
+    return types.SimpleNamespace(forward=lambda *a, **k: None, actor=types.SimpleNamespace(min_logvar=-2.5, max_logvar=2.5))
+
+
+def test_policy_proposal_argument_checks():
+    from egogen_amd.proposal import PolicyProposal
+    sq = ref.square_hole_edges()
+    with pytest.raises(ValueError, match="temperature"):
+        PolicyProposal(_runner(), temperature=-0.1)
+    with pytest.raises(ValueError, match="temperature"):
+        PolicyProposal(_runner(), temperature=float("nan"))
+    for bad in (-0.01, 1.01):
+        with pytest.raises(ValueError, match="prior_fraction"):
+            PolicyProposal(_runner(), prior_fraction=bad)
+    with pytest.raises(ValueError, match="scene_idx"):
+        PolicyProposal(_runner(), edges=sq, scene_idx=[0, 1, 0])
+    with pytest.raises(ValueError, match="scene_idx"):
+        PolicyProposal(_runner(), edges=sq, scene_idx=[0, -1, 0])
+    for off in ([0, 5], [0, 5, 3, 8], [1, 8], [0]):         # does not end at E, falls, does not start at 0, no scene
+        with pytest.raises(ValueError, match="edge_off"):
+            PolicyProposal(_runner(), edges=sq, edge_off=off)
+    with pytest.raises(ValueError, match="need edges"):
+        PolicyProposal(_runner(), scene_idx=[0, 0, 0])
+    with pytest.raises(TypeError):
+        PolicyProposal(object())
+    p = PolicyProposal(_runner(), n_mean=6)
+    with pytest.raises(ValueError, match="n_mean = 6 exceeds the 5 candidates"):
+        p.counts(5)
+    with pytest.raises(ValueError, match="policy rows"):
+        PolicyProposal(_runner(), n_mean=4, prior_fraction=0.5).counts(5)          # n_policy = 5 - 2
+    assert PolicyProposal(_runner()).counts(16) == (1, 12) and PolicyProposal(_runner(), prior_fraction=0.0).counts(1) == (1, 1)
+    assert PolicyProposal(_runner(), prior_fraction=1.0, n_mean=0).counts(5) == (0, 0)
+    two = PolicyProposal(_runner(), edges=np.concatenate([sq, ref.room0_edges()]), edge_off=[0, 8, 97], scene_idx=[1, 0, 1], max_depth=None)
+    assert two.num_scenes == 2 and two.max_depth == 13 and two.edge_off.dtype == np.int32
+
+
+def test_from_scene_file_reads_edges_rings_and_room0(tmp_path):
+    from egogen_amd import synth
+    from egogen_amd.proposal import PolicyProposal, scene_file_edges
+    sq = ref.square_hole_edges()
+    np.savez(tmp_path / "edges.npz", edges=sq)
+    rings = synth.sdf_scene_polygon(synth.make_sdf_scene(8))
+    np.savez(tmp_path / "rings.npz", ring_xy=np.concatenate(rings, 0), ring_off=np.cumsum([0] + [len(r) for r in rings]).astype(np.int32))
+    np.savez(tmp_path / "neither.npz", sdf=np.zeros(3))
+    assert np.array_equal(scene_file_edges(str(tmp_path / "edges.npz")), sq)
+    assert np.array_equal(scene_file_edges(str(tmp_path / "rings.npz")), sq)
+    assert PolicyProposal.from_scene_file(_runner(), "room0", temperature=0.5).edges.shape == (89, 4)
+    with pytest.raises(ValueError, match="neither"):
+        scene_file_edges(str(tmp_path / "neither.npz"))
+
+
+def test_policy_with_a_beam_raises_like_groups():
+    """The check `generate_sequence_to_goal` makes before any device work, on an operator built without a device."""
+    from egogen_amd.genop import GAMMAPrimitiveComboGenOP
+    from egogen_amd.proposal import PolicyProposal, check_beam
+    with pytest.raises(ValueError, match="policy= is the greedy search only: beam_width must be 1"):
+        check_beam(2)
+    check_beam(1)
+    op = GAMMAPrimitiveComboGenOP.__new__(GAMMAPrimitiveComboGenOP)
+    op.body_model = object()
+    data, bparams = np.zeros((2, 3, 201), np.float32), np.zeros((2, 3, 93), np.float32)
+    with pytest.raises(ValueError, match="policy= is the greedy search only"):
+        op.generate_sequence_to_goal(data, bparams, np.zeros(10, np.float32), np.zeros(3, np.float32), 2, 4, beam_width=2,
+                                     policy=PolicyProposal(_runner()))
+    with pytest.raises(TypeError, match="PolicyProposal"):
+        op.generate_sequence_to_goal(data, bparams, np.zeros(10, np.float32), np.zeros(3, np.float32), 2, 4, policy=_runner())
+    with pytest.raises(ValueError, match="n_mean = 5 exceeds the 4 candidates"):
+        op.generate_sequence_to_goal(data, bparams, np.zeros(10, np.float32), np.zeros(3, np.float32), 2, 4,
+                                     policy=PolicyProposal(_runner(), n_mean=5))
