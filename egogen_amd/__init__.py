@@ -11,4 +11,7 @@ def __getattr__(name):      # `from egogen_amd import GeodesicField` without imp
     if name == "PolicyProposal":
         from .proposal import PolicyProposal
         return PolicyProposal
+    if name == "MotionSet":
+        from .metrics import MotionSet
+        return MotionSet
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

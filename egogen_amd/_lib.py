@@ -238,6 +238,15 @@ SIGNATURES = {
                               [C.c_void_p] * 4 + [C.c_int, C.c_float, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 5),
     "egx_policy_propose": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int,
                                      C.c_float, C.c_void_p, C.c_void_p]),
+    # the records (markers, pelvis, rotmat, transl, num_primitives), the frame table (frame_src, num_frames, motion_start on the device
+    # and on the host, num_motions), then: feet_marker_idx_host, goal, goal_thresh, floor_z, pene_count, pene_thres, out_f64, out_i32,
+    # out_per_frame, stream
+    "egx_motion_metrics": (C.c_int, [C.c_void_p] * 4 + [C.c_int, C.c_void_p, C.c_int, C.c_void_p, c_int_p, C.c_int, c_int_p, C.c_void_p,
+                                     C.c_double, C.c_double, C.c_void_p, C.c_int] + [C.c_void_p] * 4),
+    # the records and the frame table, then: group_start, group_member, pair_start, group_start_host, num_groups, num_pairs, max_frames,
+    # body_radius, hold, clearance, marker_dist, pair_list, stream
+    "egx_crowd_metrics": (C.c_int, [C.c_void_p] * 4 + [C.c_int, C.c_void_p, C.c_int, C.c_void_p, c_int_p, C.c_int] + [C.c_void_p] * 3 +
+                          [c_int_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int] + [C.c_void_p] * 4),
     "egx_sample_action": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_int, C.c_int, C.c_void_p,
                                     C.c_void_p, C.c_void_p]),
     "egx_gae": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double, C.c_void_p,

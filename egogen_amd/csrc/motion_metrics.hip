@@ -1,0 +1,427 @@
+// The evaluator of finished motions (egogen_amd/metrics.py): egx_motion_metrics, the per-motion quality figures, and
+// egx_crowd_metrics, the person-to-person figures of the people of one scene and time line.  Both read the records a
+// `PrimitiveSequence` and a motion_*.pkl hold - blended markers, pelvis, and the world frame of every primitive, float32 in the
+// primitive's canonical frame - through a flat frame table (frame_src[i] = primitive * 20 + t) with CSR offsets per motion, so a
+// motion is its frames in order with the seed frames of the later primitives already dropped by the host.
+//
+// Arithmetic is float64 throughout, from the float32 inputs: the world transform R m + T, differences, norms, sums.  A third
+// difference of metre-scale coordinates at 40 Hz loses five digits in float32; in float64 the thresholded outputs agree with a
+// float64 reference except on exact ties.  No world-frame array is materialised: every frame a stencil touches is transformed
+// where it is read (a neighbour's frame up to four times; the inputs of a motion stay in cache).
+//
+// Determinism: no floating-point atomics; a thread sums its frames in ascending order, a wave reduces by the fixed shuffle tree,
+// thread 0 adds the waves in order.  Nothing passes between workgroups, so a motion's and a pair's numbers are the same bits in
+// any batch.  Every index read from device memory is clamped into its array before use.
+#include <cmath>
+
+#include "egx_common.h"
+
+namespace {
+
+constexpr int NT = 20, NMK = 67, NFEET = 6;
+constexpr int MM_BLK = 256, MM_WAVES = MM_BLK / 64;
+constexpr int NF64 = EGX_MM_F64_COLS, NI32 = EGX_MM_I32_COLS, NPF = EGX_MM_FRAME_COLS;
+constexpr double SKATE_THRESH = 0.075, FLOOR_TARGET = 0.02, CONTACT_BAND = 0.05;   // egx_reward.h's two, GAMMA's contact band
+constexpr int MEMBER_LD = 3 * NMK + 2;          // doubles of one staged person: x[67], y[67], z[67], pelvis x, y
+static_assert(NMK >= 64 && NMK < 128, "a wave holds the first 64 markers of a person in registers, one per lane");
+
+struct Records {
+  const float* markers;   // [P,20,67,3]
+  const float* pelvis;    // [P,20,3]
+  const float* rotmat;    // [P,9]
+  const float* transl;    // [P,3]
+  const int* frame_src;   // [Ftot]
+  const int* motion_start;  // [n+1]
+  int P, Ftot, n;
+};
+
+struct MotionArgs {
+  Records r;
+  int feet[NFEET];
+  const float* goal;      // [n,3] or null
+  const int* pene;        // [P*20] or null
+  double goal_thresh, floor_z;
+  int pene_thres;
+  double* out_f;          // [n,NF64]
+  int* out_i;             // [n,NI32]
+  double* per_frame;      // [Ftot,NPF] or null
+};
+
+struct CrowdArgs {
+  Records r;
+  const int* group_start;   // [G+1]
+  const int* group_member;  // [group_start[G]] motion indices
+  const int* pair_start;    // [G+1]
+  int G, npairs, Fmax, maxP, hold;
+  double rr;                // 2 * body_radius
+  double* clearance;        // [npairs,Fmax]
+  double* marker_dist;      // [npairs,Fmax]
+  int* pair_list;           // [npairs,2]
+};
+
+struct V3 { double x, y, z; };
+
+__device__ __forceinline__ V3 to_world(const float* R, const float* T, const float* m) {
+  const double a = m[0], b = m[1], c = m[2];
+  V3 w;
+  w.x = fma((double)R[0], a, fma((double)R[1], b, (double)R[2] * c)) + (double)T[0];
+  w.y = fma((double)R[3], a, fma((double)R[4], b, (double)R[5] * c)) + (double)T[1];
+  w.z = fma((double)R[6], a, fma((double)R[7], b, (double)R[8] * c)) + (double)T[2];
+  return w;
+}
+__device__ __forceinline__ double norm3(double x, double y, double z) { return sqrt(fma(x, x, fma(y, y, z * z))); }
+
+// entry i of the frame table -> primitive * 20 + t, clamped into the records
+__device__ __forceinline__ int src_of(const Records& r, int i) { return min(max(r.frame_src[i], 0), r.P * NT - 1); }
+__device__ __forceinline__ V3 pelvis_w(const Records& r, int src) {
+  const int k = src / NT;
+  return to_world(r.rotmat + (size_t)k * 9, r.transl + (size_t)k * 3, r.pelvis + (size_t)src * 3);
+}
+__device__ __forceinline__ V3 marker_w(const Records& r, int src, int m) {
+  const int k = src / NT;
+  return to_world(r.rotmat + (size_t)k * 9, r.transl + (size_t)k * 3, r.markers + ((size_t)src * NMK + m) * 3);
+}
+// frames [start, start + F) of motion i in the frame table
+__device__ __forceinline__ void motion_span(const Records& r, int i, int& start, int& F) {
+  start = min(max(r.motion_start[i], 0), r.Ftot);
+  F = min(max(r.motion_start[i + 1], start), r.Ftot) - start;
+}
+
+__device__ __forceinline__ double wave_sum(double v) {   // lane 0 holds the sum: the fixed tree
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+  return v;
+}
+__device__ __forceinline__ double wave_min(double v) {
+  for (int o = 32; o > 0; o >>= 1) v = fmin(v, __shfl_down(v, o, 64));
+  return v;
+}
+__device__ __forceinline__ double wave_max(double v) {
+  for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_down(v, o, 64));
+  return v;
+}
+__device__ __forceinline__ long long wave_sum_i(long long v) {
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+  return v;
+}
+__device__ __forceinline__ int wave_min_i(int v) {
+  for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_down(v, o, 64));
+  return v;
+}
+__device__ __forceinline__ int wave_max_i(int v) {
+  for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_down(v, o, 64));
+  return v;
+}
+
+enum { S_SKATE, S_SPEED, S_FLOOR, S_CONTACT, S_PATH, S_ACC, S_JERK, NSUM };          // sums of doubles
+enum { M_SMAX, M_HMAX, NMAX };
+enum { N_HMIN, N_DMIN, NMIN };
+enum { I_SKATE_FRAMES, I_PENE_SUM, I_PENE_FRAMES, NISUM };
+
+}  // namespace
+
+// One workgroup per motion, the threads stride over its frames.
+__global__ __launch_bounds__(MM_BLK) void egx_motion_metrics_kernel(MotionArgs p) {
+  __shared__ double s_sum[NSUM][MM_WAVES], s_max[NMAX][MM_WAVES], s_min[NMIN][MM_WAVES];
+  __shared__ long long s_isum[NISUM][MM_WAVES];
+  __shared__ int s_first[MM_WAVES], s_pmax[MM_WAVES];
+  const Records& r = p.r;
+  const int i = blockIdx.x, tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
+  int start, F;
+  motion_span(r, i, start, F);
+  const double inf = __builtin_inf(), nan = __builtin_nan("");
+  const bool has_goal = p.goal != nullptr, has_pene = p.pene != nullptr;
+  double gx = 0.0, gy = 0.0, gz = 0.0;
+  if (has_goal) { gx = p.goal[(size_t)i * 3]; gy = p.goal[(size_t)i * 3 + 1]; gz = p.goal[(size_t)i * 3 + 2]; }
+
+  double sum[NSUM], mx[NMAX], mn[NMIN];
+  long long isum[NISUM];
+  for (int k = 0; k < NSUM; ++k) sum[k] = 0.0;
+  for (int k = 0; k < NMAX; ++k) mx[k] = -inf;
+  for (int k = 0; k < NMIN; ++k) mn[k] = inf;
+  for (int k = 0; k < NISUM; ++k) isum[k] = 0;
+  int first = 0x7fffffff, pmax = -1;
+
+  for (int f = tid; f < F; f += MM_BLK) {
+    const int src = src_of(r, start + f);
+    const bool interior = f >= 1 && f + 1 < F;
+    const V3 p0 = pelvis_w(r, src);
+    double h = inf;
+    for (int k = 0; k < NFEET; ++k) h = fmin(h, marker_w(r, src, p.feet[k]).z);
+    h -= p.floor_z;
+    sum[S_FLOOR] += fabs(h - FLOOR_TARGET);
+    mx[M_HMAX] = fmax(mx[M_HMAX], h);
+    mn[N_HMIN] = fmin(mn[N_HMIN], h);
+    double s = nan, c = nan, d = nan;
+    if (f + 1 < F) {
+      const int src1 = src_of(r, start + f + 1);
+      const V3 p1 = pelvis_w(r, src1);
+      sum[S_PATH] += sqrt(fma(p1.x - p0.x, p1.x - p0.x, (p1.y - p0.y) * (p1.y - p0.y)));
+      if (interior) {
+        const int srcm = src_of(r, start + f - 1);
+        double slow = inf;
+        for (int k = 0; k < NFEET; ++k) {
+          const V3 a = marker_w(r, src1, p.feet[k]), b = marker_w(r, srcm, p.feet[k]);
+          slow = fmin(slow, norm3(a.x - b.x, a.y - b.y, a.z - b.z));
+        }
+        s = 20.0 * slow;
+        const double excess = fmax(s - SKATE_THRESH, 0.0);
+        c = exp(-fmax(fabs(h) - CONTACT_BAND, 0.0)) * exp(-excess);
+        sum[S_SKATE] += excess;
+        sum[S_SPEED] += s;
+        sum[S_CONTACT] += c;
+        mx[M_SMAX] = fmax(mx[M_SMAX], s);
+        isum[I_SKATE_FRAMES] += (s > SKATE_THRESH) ? 1 : 0;
+        const V3 pm = pelvis_w(r, srcm);
+        sum[S_ACC] += norm3(p1.x - 2.0 * p0.x + pm.x, p1.y - 2.0 * p0.y + pm.y, p1.z - 2.0 * p0.z + pm.z);
+        if (f + 2 < F) {
+          const V3 p2 = pelvis_w(r, src_of(r, start + f + 2));
+          sum[S_JERK] += norm3(p2.x - 3.0 * p1.x + 3.0 * p0.x - pm.x, p2.y - 3.0 * p1.y + 3.0 * p0.y - pm.y,
+                               p2.z - 3.0 * p1.z + 3.0 * p0.z - pm.z);
+        }
+      }
+    }
+    if (has_goal) {
+      d = fmax(norm3(gx - p0.x, gy - p0.y, gz - p0.z), 1e-12);
+      mn[N_DMIN] = fmin(mn[N_DMIN], d);
+      if (d < p.goal_thresh) first = min(first, f);
+      if (f == F - 1) p.out_f[(size_t)i * NF64 + EGX_MM_GOAL_DIST_END] = d;      // one writer
+    }
+    if (has_pene) {
+      const int cnt = p.pene[src];
+      isum[I_PENE_SUM] += cnt;
+      isum[I_PENE_FRAMES] += (cnt >= p.pene_thres) ? 1 : 0;
+      pmax = max(pmax, cnt);
+    }
+    if (p.per_frame) {
+      double* o = p.per_frame + (size_t)(start + f) * NPF;
+      o[0] = s; o[1] = h; o[2] = c; o[3] = d; o[4] = p0.x; o[5] = p0.y;
+    }
+  }
+
+  for (int k = 0; k < NSUM; ++k) { const double v = wave_sum(sum[k]); if (lane == 0) s_sum[k][w] = v; }
+  for (int k = 0; k < NMAX; ++k) { const double v = wave_max(mx[k]); if (lane == 0) s_max[k][w] = v; }
+  for (int k = 0; k < NMIN; ++k) { const double v = wave_min(mn[k]); if (lane == 0) s_min[k][w] = v; }
+  for (int k = 0; k < NISUM; ++k) { const long long v = wave_sum_i(isum[k]); if (lane == 0) s_isum[k][w] = v; }
+  first = wave_min_i(first);
+  pmax = wave_max_i(pmax);
+  if (lane == 0) { s_first[w] = first; s_pmax[w] = pmax; }
+  __syncthreads();
+  if (tid != 0) return;
+  for (int k = 0; k < NSUM; ++k) { double v = s_sum[k][0]; for (int u = 1; u < MM_WAVES; ++u) v += s_sum[k][u]; sum[k] = v; }
+  for (int k = 0; k < NMAX; ++k) { double v = s_max[k][0]; for (int u = 1; u < MM_WAVES; ++u) v = fmax(v, s_max[k][u]); mx[k] = v; }
+  for (int k = 0; k < NMIN; ++k) { double v = s_min[k][0]; for (int u = 1; u < MM_WAVES; ++u) v = fmin(v, s_min[k][u]); mn[k] = v; }
+  for (int k = 0; k < NISUM; ++k) { long long v = s_isum[k][0]; for (int u = 1; u < MM_WAVES; ++u) v += s_isum[k][u]; isum[k] = v; }
+  for (int u = 0; u < MM_WAVES; ++u) { first = min(first, s_first[u]); pmax = max(pmax, s_pmax[u]); }
+
+  double* of = p.out_f + (size_t)i * NF64;
+  int* oi = p.out_i + (size_t)i * NI32;
+  const double duration = (double)(F - 1) / 40.0, inner = (double)(F - 2);
+  of[EGX_MM_DURATION_S] = duration;
+  of[EGX_MM_SKATE_MEAN] = sum[S_SKATE] / inner;
+  of[EGX_MM_SKATE_SPEED_MEAN] = sum[S_SPEED] / inner;
+  of[EGX_MM_SKATE_SPEED_MAX] = mx[M_SMAX];
+  of[EGX_MM_FLOOR_MEAN] = sum[S_FLOOR] / (double)F;
+  of[EGX_MM_FLOOR_MIN] = mn[N_HMIN];
+  of[EGX_MM_FLOOR_MAX] = mx[M_HMAX];
+  of[EGX_MM_CONTACT_SCORE] = sum[S_CONTACT] / inner;
+  of[EGX_MM_PATH_LENGTH] = sum[S_PATH];
+  double disp = nan;
+  if (F >= 1) {
+    const V3 a = pelvis_w(r, src_of(r, start)), b = pelvis_w(r, src_of(r, start + F - 1));
+    disp = sqrt(fma(b.x - a.x, b.x - a.x, (b.y - a.y) * (b.y - a.y)));
+  }
+  of[EGX_MM_DISPLACEMENT] = disp;
+  of[EGX_MM_SPEED_MEAN] = sum[S_PATH] / duration;
+  of[EGX_MM_ACC_MEAN] = 1600.0 * (sum[S_ACC] / inner);
+  of[EGX_MM_JERK_MEAN] = 64000.0 * (sum[S_JERK] / (double)(F - 3));
+  if (!has_goal) of[EGX_MM_GOAL_DIST_END] = nan;
+  of[EGX_MM_GOAL_DIST_MIN] = has_goal ? mn[N_DMIN] : nan;
+  of[EGX_MM_PENE_MEAN] = has_pene ? (double)isum[I_PENE_SUM] / (double)F : nan;
+  oi[EGX_MM_FRAMES] = F;
+  oi[EGX_MM_SKATE_FRAMES] = (int)isum[I_SKATE_FRAMES];
+  oi[EGX_MM_FIRST_REACHED_FRAME] = (has_goal && first != 0x7fffffff) ? first : -1;
+  oi[EGX_MM_PENE_MAX] = has_pene ? pmax : -1;
+  oi[EGX_MM_PENE_FRAMES] = has_pene ? (int)isum[I_PENE_FRAMES] : -1;
+}
+
+// One workgroup per (group, absolute frame): the world markers and pelvis xy of every member present at that frame are staged in
+// LDS as float64 once (per person x[67], y[67], z[67]: consecutive lanes read consecutive doubles), then a wave takes a pair at a
+// time: its 67 x 67 squared distances spread over the lanes, a min by the shuffle tree, one sqrt (sqrt is monotone and correctly
+// rounded, so the root of the least square is the least root).
+__global__ __launch_bounds__(MM_BLK) void egx_crowd_metrics_kernel(CrowdArgs p) {
+  extern __shared__ double s_w[];                   // [maxP][MEMBER_LD]
+  __shared__ int s_motion[EGX_MAX_GROUP], s_src[EGX_MAX_GROUP], s_len[EGX_MAX_GROUP];
+  const Records& r = p.r;
+  const int g = blockIdx.x / p.Fmax, f = blockIdx.x % p.Fmax;
+  const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
+  const int total = max(p.group_start[p.G], 0);
+  const int start = min(max(p.group_start[g], 0), total);
+  const int P = min(min(max(p.group_start[g + 1], start), total) - start, p.maxP);
+  if (P < 2) return;                                // the same in every thread
+  if (tid < P) {
+    const int m = min(max(p.group_member[start + tid], 0), r.n - 1);
+    int st, Fm;
+    motion_span(r, m, st, Fm);
+    s_motion[tid] = m;
+    s_len[tid] = Fm;
+  }
+  __syncthreads();
+  int Fg = 0;
+  for (int k = 0; k < P; ++k) Fg = max(Fg, s_len[k]);
+  if (tid < P) {
+    int st, Fm;
+    motion_span(r, s_motion[tid], st, Fm);
+    int ff = -1;                                    // the member's own frame at absolute frame f; -1: it is not there
+    if (f < Fm) ff = f;
+    else if (p.hold && Fm > 0 && f < Fg) ff = Fm - 1;
+    s_src[tid] = ff >= 0 ? src_of(r, st + ff) : -1;
+  }
+  __syncthreads();
+  for (int e = tid; e < P * (NMK + 1); e += MM_BLK) {
+    const int k = e / (NMK + 1), m = e % (NMK + 1), src = s_src[k];
+    if (src < 0) continue;
+    double* o = s_w + (size_t)k * MEMBER_LD;
+    if (m < NMK) {
+      const V3 v = marker_w(r, src, m);
+      o[m] = v.x; o[NMK + m] = v.y; o[2 * NMK + m] = v.z;
+    } else {
+      const V3 v = pelvis_w(r, src);
+      o[3 * NMK] = v.x; o[3 * NMK + 1] = v.y;
+    }
+  }
+  __syncthreads();
+  const int npair = P * (P - 1) / 2;
+  const int pair0 = max(p.pair_start[g], 0);
+  const double nan = __builtin_nan("");
+  for (int q = w; q < npair; q += MM_WAVES) {       // pair q of the group: (a, b), a < b, in lexicographic order
+    int a = 0, rem = q;
+    while (rem >= P - 1 - a) { rem -= P - 1 - a; ++a; }
+    const int b = a + 1 + rem;
+    const bool both = s_src[a] >= 0 && s_src[b] >= 0;
+    double d2 = __builtin_inf();
+    if (both) {
+      const double* A = s_w + (size_t)a * MEMBER_LD;
+      const double* B = s_w + (size_t)b * MEMBER_LD;
+      // The loop is bound by LDS reads, so a lane keeps marker `lane` of the first person in registers and walks the second person's
+      // 67 (all lanes read one address: a broadcast): 3 reads per distance, not 6.  The first person's markers 64..66 follow,
+      // their 3 x 67 distances spread over the lanes.  A minimum does not depend on the order it is taken in.
+      const double ax = A[lane], ay = A[NMK + lane], az = A[2 * NMK + lane];
+      for (int mb = 0; mb < NMK; ++mb) {
+        const double dx = ax - B[mb], dy = ay - B[NMK + mb], dz = az - B[2 * NMK + mb];
+        d2 = fmin(d2, fma(dx, dx, fma(dy, dy, dz * dz)));
+      }
+      for (int e = lane; e < (NMK - 64) * NMK; e += 64) {
+        const int ma = 64 + e / NMK, mb = e % NMK;
+        const double dx = A[ma] - B[mb], dy = A[NMK + ma] - B[NMK + mb], dz = A[2 * NMK + ma] - B[2 * NMK + mb];
+        d2 = fmin(d2, fma(dx, dx, fma(dy, dy, dz * dz)));
+      }
+    }
+    d2 = wave_min(d2);
+    if (lane == 0 && pair0 + q < p.npairs) {
+      const size_t at = (size_t)(pair0 + q) * p.Fmax + f;
+      if (both) {
+        const double* A = s_w + (size_t)a * MEMBER_LD;
+        const double* B = s_w + (size_t)b * MEMBER_LD;
+        const double dx = A[3 * NMK] - B[3 * NMK], dy = A[3 * NMK + 1] - B[3 * NMK + 1];
+        p.clearance[at] = sqrt(fma(dx, dx, dy * dy)) - p.rr;
+        p.marker_dist[at] = sqrt(d2);
+      } else {
+        p.clearance[at] = nan;
+        p.marker_dist[at] = nan;
+      }
+      if (f == 0) {
+        p.pair_list[(size_t)(pair0 + q) * 2] = s_motion[a];
+        p.pair_list[(size_t)(pair0 + q) * 2 + 1] = s_motion[b];
+      }
+    }
+  }
+}
+
+// the records and the frame table of both entries; min_frames: the shortest motion the entry takes
+static int check_records(const float* blended_marker, const float* pelvis_loc, const float* transf_rotmat, const float* transf_transl,
+                         int num_primitives, const int32_t* frame_src, int num_frames, const int32_t* motion_start,
+                         const int32_t* motion_start_host, int num_motions, int min_frames, int* longest) {
+  EGX_REQUIRE(blended_marker && pelvis_loc && transf_rotmat && transf_transl && frame_src && motion_start && motion_start_host,
+              "null input");
+  EGX_REQUIRE(num_primitives >= 1 && num_primitives <= 0x7fffffff / (NT * NMK * 3), "num_primitives must be positive, the records below 2^31 floats");
+  EGX_REQUIRE(num_frames >= 1 && num_motions >= 1, "need at least one frame and one motion");
+  EGX_REQUIRE(motion_start_host[0] >= 0 && motion_start_host[num_motions] <= num_frames, "motion_start must lie in [0, num_frames]");
+  int mx = 0;
+  for (int i = 0; i < num_motions; ++i) {
+    const int F = motion_start_host[i + 1] - motion_start_host[i];
+    EGX_REQUIRE(motion_start_host[i + 1] >= motion_start_host[i], "motion_start must not decrease");
+    EGX_REQUIRE(F >= min_frames, "a motion is shorter than the entry takes (egx_motion_metrics: 4 frames, egx_crowd_metrics: 1)");
+    mx = F > mx ? F : mx;
+  }
+  *longest = mx;
+  return EGX_OK;
+}
+
+extern "C" int egx_motion_metrics(const float* blended_marker, const float* pelvis_loc, const float* transf_rotmat,
+                                  const float* transf_transl, int num_primitives, const int32_t* frame_src, int num_frames,
+                                  const int32_t* motion_start, const int32_t* motion_start_host, int num_motions,
+                                  const int32_t* feet_marker_idx_host, const float* goal, double goal_thresh, double floor_z,
+                                  const int32_t* pene_count, int pene_thres, double* out_f64, int32_t* out_i32, double* out_per_frame,
+                                  void* stream) {
+  int longest = 0;
+  const int rc = check_records(blended_marker, pelvis_loc, transf_rotmat, transf_transl, num_primitives, frame_src, num_frames,
+                               motion_start, motion_start_host, num_motions, 4, &longest);
+  if (rc != EGX_OK) return rc;
+  EGX_REQUIRE(feet_marker_idx_host && out_f64 && out_i32, "null feet_marker_idx_host or output");
+  EGX_REQUIRE(goal_thresh >= 0.0 && std::isfinite(goal_thresh), "goal_thresh must be finite and not negative");
+  EGX_REQUIRE(std::isfinite(floor_z), "floor_z must be finite");
+  EGX_REQUIRE(pene_thres >= 0, "pene_thres must not be negative");
+  MotionArgs p{};
+  for (int k = 0; k < NFEET; ++k) {
+    EGX_REQUIRE(feet_marker_idx_host[k] >= 0 && feet_marker_idx_host[k] < NMK, "a feet marker index outside [0, 67)");
+    p.feet[k] = feet_marker_idx_host[k];
+  }
+  p.r = Records{blended_marker, pelvis_loc, transf_rotmat, transf_transl, frame_src, motion_start, num_primitives, num_frames, num_motions};
+  p.goal = goal; p.pene = pene_count; p.goal_thresh = goal_thresh; p.floor_z = floor_z; p.pene_thres = pene_thres;
+  p.out_f = out_f64; p.out_i = out_i32; p.per_frame = out_per_frame;
+  hipLaunchKernelGGL(egx_motion_metrics_kernel, dim3(num_motions), dim3(MM_BLK), 0, static_cast<hipStream_t>(stream), p);
+  EGX_HIP_CHECK(hipGetLastError());
+  return EGX_OK;
+}
+
+extern "C" int egx_crowd_metrics(const float* blended_marker, const float* pelvis_loc, const float* transf_rotmat,
+                                 const float* transf_transl, int num_primitives, const int32_t* frame_src, int num_frames,
+                                 const int32_t* motion_start, const int32_t* motion_start_host, int num_motions,
+                                 const int32_t* group_start, const int32_t* group_member, const int32_t* pair_start,
+                                 const int32_t* group_start_host, int num_groups, int num_pairs, int max_frames, double body_radius,
+                                 int hold, double* clearance, double* marker_dist, int32_t* pair_list, void* stream) {
+  int longest = 0;
+  const int rc = check_records(blended_marker, pelvis_loc, transf_rotmat, transf_transl, num_primitives, frame_src, num_frames,
+                               motion_start, motion_start_host, num_motions, 1, &longest);
+  if (rc != EGX_OK) return rc;
+  EGX_REQUIRE(group_start && group_member && pair_start && group_start_host, "null group arrays");
+  EGX_REQUIRE(num_groups >= 1, "num_groups must be at least 1");
+  EGX_REQUIRE(body_radius >= 0.0 && std::isfinite(body_radius), "body_radius must be finite and not negative");
+  EGX_REQUIRE(hold == 0 || hold == 1, "hold must be 0 or 1");
+  EGX_REQUIRE(group_start_host[0] == 0, "group_start must begin at 0");
+  long long pairs = 0;
+  int maxP = 0;
+  for (int g = 0; g < num_groups; ++g) {
+    const int P = group_start_host[g + 1] - group_start_host[g];
+    EGX_REQUIRE(P >= 0, "group_start must not decrease");
+    EGX_REQUIRE(P <= EGX_MAX_GROUP, "a group holds at most EGX_MAX_GROUP people");
+    pairs += (long long)P * (P - 1) / 2;
+    maxP = P > maxP ? P : maxP;
+  }
+  EGX_REQUIRE(pairs == (long long)num_pairs, "num_pairs must be the sum of P (P - 1) / 2 over the groups");
+  EGX_REQUIRE(max_frames >= longest, "max_frames must be at least the longest motion");
+  EGX_REQUIRE((long long)num_groups * max_frames <= 0x7fffffffLL, "num_groups * max_frames must stay below 2^31");
+  if (num_pairs == 0) return EGX_OK;                  // nobody to compare: the outputs are empty
+  EGX_REQUIRE(clearance && marker_dist && pair_list, "null output");
+  CrowdArgs p{};
+  p.r = Records{blended_marker, pelvis_loc, transf_rotmat, transf_transl, frame_src, motion_start, num_primitives, num_frames, num_motions};
+  p.group_start = group_start; p.group_member = group_member; p.pair_start = pair_start;
+  p.G = num_groups; p.npairs = num_pairs; p.Fmax = max_frames; p.maxP = maxP; p.hold = hold;
+  p.rr = body_radius + body_radius;                   // doubling is exact
+  p.clearance = clearance; p.marker_dist = marker_dist; p.pair_list = pair_list;
+  const size_t lds = (size_t)maxP * MEMBER_LD * sizeof(double);
+  hipLaunchKernelGGL(egx_crowd_metrics_kernel, dim3((unsigned)(num_groups * max_frames)), dim3(MM_BLK), lds,
+                     static_cast<hipStream_t>(stream), p);
+  EGX_HIP_CHECK(hipGetLastError());
+  return EGX_OK;
+}

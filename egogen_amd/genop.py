@@ -418,7 +418,8 @@ class GAMMAPrimitiveComboGenOP:
             - scene: None (no penetration term, nothing collides), an SdfScene, or an SdfSceneSet with agent_scene [b]
             - weights: {goal, skate, floor, pene, face} of cost = sum w * term, the terms being the arguments of the env's reward
               terms (distance to the goal in metres, -ln r_skate, -ln r_floor, -ln r_pene, 1 - r_face_target).  The defaults
-              1, 1, 1, 1, 0 are a stated choice: nobody has measured motion quality with them.
+              1, 1, 1, 1, 0 are a stated choice: nobody has measured motion quality with them (the instrument for it, for this
+              and the stated choices below: egogen_amd/metrics.py, exp_GAMMAPrimitive/eval_motion.py).
             - pene_thres: a candidate one of whose 20 bodies has that many vertices inside the scene collides (40: the env's)
             - goal_thresh: None takes testconfig['goal_thresh'] (the policy configs' trainconfig.goal_thresh) where present, else 0.1
             - z: None (N(0, I) from the torch generator, drawn up front) or [n_primitives, b * N, 128]; row i * N + n is

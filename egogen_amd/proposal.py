@@ -62,7 +62,7 @@ class PolicyProposal:
           primitive k is 1 - min(k, max_depth) / max_depth; the clamp is a stated choice, the policy never saw a step above
           max_depth.
     temperature, n_mean and prior_fraction are stated choices like the search's weights: nobody has measured motion quality with
-    them, and no trained checkpoint has been run through this path."""
+    them, and no trained checkpoint has been run through this path (the instrument for it: egogen_amd/metrics.py)."""
 
     def __init__(self, policy, edges=None, edge_off=None, scene_idx=None, temperature: float = 1.0, n_mean: int = 1,
                  prior_fraction: float = 0.25, ray_len: float = 7.0, max_depth: Optional[int] = None):

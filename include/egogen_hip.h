@@ -1083,6 +1083,88 @@ int egx_policy_propose(const float* mu, const float* logvar, const float* eps, f
                        int num_candidates, int n_mean, int n_policy, float temperature, float* z, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Measuring finished motions (csrc/motion_metrics.hip, egogen_amd/metrics.py)
+ * ------------------------------------------------------------------------------------------- */
+/* Columns of the two per-motion tables of egx_motion_metrics; egogen_amd/metrics.py COLUMNS holds their names and units. */
+#define EGX_MM_DURATION_S 0
+#define EGX_MM_SKATE_MEAN 1
+#define EGX_MM_SKATE_SPEED_MEAN 2
+#define EGX_MM_SKATE_SPEED_MAX 3
+#define EGX_MM_FLOOR_MEAN 4
+#define EGX_MM_FLOOR_MIN 5
+#define EGX_MM_FLOOR_MAX 6
+#define EGX_MM_CONTACT_SCORE 7
+#define EGX_MM_PATH_LENGTH 8
+#define EGX_MM_DISPLACEMENT 9
+#define EGX_MM_SPEED_MEAN 10
+#define EGX_MM_ACC_MEAN 11
+#define EGX_MM_JERK_MEAN 12
+#define EGX_MM_GOAL_DIST_END 13
+#define EGX_MM_GOAL_DIST_MIN 14
+#define EGX_MM_PENE_MEAN 15
+#define EGX_MM_F64_COLS 16
+#define EGX_MM_FRAMES 0
+#define EGX_MM_SKATE_FRAMES 1
+#define EGX_MM_FIRST_REACHED_FRAME 2
+#define EGX_MM_PENE_MAX 3
+#define EGX_MM_PENE_FRAMES 4
+#define EGX_MM_I32_COLS 5
+#define EGX_MM_FRAME_COLS 6    /* per-frame output: s, h, c, d, world pelvis x, world pelvis y */
+
+/* The records both entries read are those of a `PrimitiveSequence` / a motion_*.pkl, float32, each primitive in its canonical
+ * frame: blended_marker [num_primitives,20,67,3], pelvis_loc [num_primitives,20,3], transf_rotmat [num_primitives,3,3],
+ * transf_transl [num_primitives,3]; a point m of primitive k stands at R_k m + T_k in the world.  A motion is a run of the frame
+ * table: frame_src [num_frames] holds primitive * 20 + t, and motion i is its entries motion_start[i] .. motion_start[i + 1] - 1
+ * (the host drops the seed frames a later primitive shares with its predecessor: 2 of a '2-frame' primitive, 1 of a '1-frame'
+ * one).  motion_start is given twice: on the device for the kernel, and motion_start_host, the same [num_motions + 1] values in
+ * host memory, which the entry checks before it launches; an index the kernel reads from device memory is clamped into its array.
+ * All arithmetic is float64 from the float32 inputs, world transform included; no world-frame array is written.  No
+ * floating-point atomics, a fixed reduction order, nothing between workgroups: a motion's and a pair's outputs are the same bits
+ * run to run and in any batch.  Both are plain launches on `stream`: no host wait.
+ *
+ * egx_motion_metrics - one workgroup per motion.  With M_{f,k} the world positions of the six feet markers feet_marker_idx_host
+ * (host memory, indices in [0, 67)), p_f the world pelvis, F the motion's frames, at 40 frames per second:
+ *   s_f = 20 min_k |M_{f+1,k} - M_{f-1,k}|                  f = 1 .. F-2 (the reward's central difference, across hand-offs)
+ *   h_f = min_k z(M_{f,k}) - floor_z
+ *   c_f = exp(-max(|h_f| - 0.05, 0)) exp(-max(s_f - 0.075, 0))     f = 1 .. F-2
+ *   d_f = max(|goal - p_f|, 1e-12) in 3-D, where goal [num_motions,3] (world, float32) is not NULL
+ * out_f64 [num_motions, EGX_MM_F64_COLS]: duration_s = (F-1)/40; skate_mean = mean max(s_f - 0.075, 0); skate_speed_mean = mean
+ * s_f; skate_speed_max; floor_mean = mean_f |h_f - 0.02|; floor_min / floor_max of h_f; contact_score = mean c_f; path_length =
+ * sum_f |p_{f+1} - p_f|_xy; displacement = |p_{F-1} - p_0|_xy; speed_mean = path_length / duration_s; acc_mean = 1600
+ * mean_{f=1..F-2} |p_{f+1} - 2 p_f + p_{f-1}|; jerk_mean = 64000 mean_{f=1..F-3} |p_{f+2} - 3 p_{f+1} + 3 p_f - p_{f-1}|;
+ * goal_dist_end = d_{F-1}; goal_dist_min (NaN without goal); pene_mean = mean_f pene_count[frame_src[f]] (NaN where pene_count
+ * [num_primitives*20] is NULL).  out_i32 [num_motions, EGX_MM_I32_COLS]: frames = F; skate_frames = #{s_f > 0.075};
+ * first_reached_frame = the first f with d_f < goal_thresh, else -1; pene_max; pene_frames = #{count >= pene_thres} (both -1 without
+ * pene_count).  out_per_frame [num_frames, EGX_MM_FRAME_COLS] or NULL: s_f, h_f, c_f, d_f, x and y of p_f; NaN where a quantity is not
+ * defined.  EGX_ERR_ARG, and nothing launched, for a NULL required pointer, a motion of fewer than 4 frames, a motion_start_host that
+ * decreases or leaves [0, num_frames], a feet index outside [0, 67), a negative or non-finite goal_thresh, a negative pene_thres,
+ * a non-finite floor_z. */
+int egx_motion_metrics(const float* blended_marker, const float* pelvis_loc, const float* transf_rotmat, const float* transf_transl,
+                       int num_primitives, const int32_t* frame_src, int num_frames, const int32_t* motion_start,
+                       const int32_t* motion_start_host, int num_motions, const int32_t* feet_marker_idx_host, const float* goal,
+                       double goal_thresh, double floor_z, const int32_t* pene_count, int pene_thres, double* out_f64,
+                       int32_t* out_i32, double* out_per_frame, void* stream);
+
+/* egx_crowd_metrics - the people of one scene and time line: group g holds the motions group_member[group_start[g] ..
+ * group_start[g + 1] - 1] (the CSR arrays of `PersonGroups`, at most EGX_MAX_GROUP members), every member starts at absolute frame
+ * 0.  Pair q of the launch is, group after group, the members (a, b), a < b, of a group in lexicographic order; pair_start
+ * [num_groups + 1] (device) holds the first pair of every group, group_start_host the group offsets in host memory (checked
+ * before the launch), num_pairs = sum_g P_g (P_g - 1) / 2.  For every pair and absolute frame f < max_frames:
+ *   clearance   [num_pairs,max_frames] = |p_a - p_b|_xy - 2 body_radius          the cylinder model of the search, in float64
+ *   marker_dist [num_pairs,max_frames] = min over the 67 x 67 pairs of world markers of their distance
+ * hold = 0: a pair is compared on the frames both members recorded, NaN elsewhere.  hold = 1: a member that has ended stands at
+ * its last frame until the longest member of its group ends; NaN after that.  pair_list [num_pairs,2]: the two motions of every
+ * pair.  One workgroup per (group, frame): the members' world markers are staged in LDS as float64 once, a wave takes a pair at a
+ * time.  With num_pairs == 0 nothing is launched and EGX_OK returned.  EGX_ERR_ARG, and nothing launched, for a NULL required pointer,
+ * a motion without frames, a group above EGX_MAX_GROUP, a negative or non-finite body_radius, hold outside {0, 1}, a num_pairs that is
+ * not the groups' pair count, max_frames below the longest motion. */
+int egx_crowd_metrics(const float* blended_marker, const float* pelvis_loc, const float* transf_rotmat, const float* transf_transl,
+                      int num_primitives, const int32_t* frame_src, int num_frames, const int32_t* motion_start,
+                      const int32_t* motion_start_host, int num_motions, const int32_t* group_start, const int32_t* group_member,
+                      const int32_t* pair_start, const int32_t* group_start_host, int num_groups, int num_pairs, int max_frames,
+                      double body_radius, int hold, double* clearance, double* marker_dist, int32_t* pair_list, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * PPO rollout glue
  * ------------------------------------------------------------------------------------------- */
 /* GAMMAPPOPolicy.forward tail (crowd_ppo/ppo_policy.py:169-178): logvar is clamped IN PLACE to [min,max];
