@@ -238,6 +238,14 @@ SIGNATURES = {
                               [C.c_void_p] * 4 + [C.c_int, C.c_float, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 5),
     "egx_policy_propose": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int,
                                      C.c_float, C.c_void_p, C.c_void_p]),
+    # x0, x1, x_ld, R0, T0, num_candidates, num_sequences, box, stream
+    "egx_primitive_people_boxes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
+                                             C.c_void_p]),
+    # egx_primitive_observe's arguments up to num_sequences, then: box, group_start, group_member, member_group, num_groups, obs_xy,
+    # obs_radius, obs_count, obs_index, num_sets, max_obstacles, num_frames, frame, people_count, state, egosensing, dist, time, stream
+    "egx_primitive_observe_people": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 6 + [C.c_int] +
+                                     [C.c_void_p] * 4 + [C.c_int, C.c_float, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 4 + [C.c_int] +
+                                     [C.c_void_p] * 4 + [C.c_int] * 4 + [C.c_void_p] * 6),
     # the records (markers, pelvis, rotmat, transl, num_primitives), the frame table (frame_src, num_frames, motion_start on the device
     # and on the host, num_motions), then: feet_marker_idx_host, goal, goal_thresh, floor_z, pene_count, pene_thres, out_f64, out_i32,
     # out_per_frame, stream

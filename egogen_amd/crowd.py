@@ -14,11 +14,12 @@ MAX_SWEEPS = 8          # EGX_MAX_SWEEPS
 class PersonGroups:
     """ids [b] the group of every sequence as given; start [G+1] / member [b] the CSR form: group g holds the sequences
     member[start[g]:start[g+1]] in ascending order, the groups in order of first appearance.  Built on the host (`from_ids`, no
-    device needed); `to(device)` makes the int32 tensors `group_start` / `group_member` the kernel reads."""
+    device needed); `to(device)` makes the int32 tensors `group_start` / `group_member` the kernel reads, and `member_group` [b], the
+    group of every sequence."""
 
     def __init__(self, ids, start, member):
         self.ids, self.start, self.member = ids, start, member
-        self.device = self.group_start = self.group_member = None
+        self.device = self.group_start = self.group_member = self.member_group = None
 
     def __len__(self):
         return len(self.start) - 1
@@ -57,5 +58,9 @@ class PersonGroups:
         device = torch.device(device)
         self.group_start = torch.from_numpy(self.start).to(device)
         self.group_member = torch.from_numpy(self.member).to(device)
+        # the inverse of the CSR, [b] int32: the group of every sequence (what egx_primitive_observe_people finds a sequence's mates by)
+        of = np.zeros(len(self.member), np.int32)
+        of[self.member] = np.repeat(np.arange(len(self), dtype=np.int32), self.sizes)
+        self.member_group = torch.from_numpy(of).to(device)
         self.device = device
         return self

@@ -121,7 +121,10 @@ class PrimitiveSequence:
     cost) and pair_hit [K,S,b,N] of every row as evaluated in each sweep; choice_trace [K,S,b] the choices after each sweep;
     joint_changed [K,S,G] the members of a group that changed their choice in a sweep (0: a fixed point); crowd_clearance [K,b] the
     clearance of the chosen track against the other members' chosen tracks and crowd_hit [K,b] = crowd_clearance < 0: did the crowd
-    as written overlap.  cost / colliding stay what the selection wrote; status follows the joint choice.  None without groups."""
+    as written overlap.  cost / colliding stay what the selection wrote; status follows the joint choice.  None without groups.
+    With `policy=PolicyProposal(..., sense_people=True)`: policy_sense_people True, people_box [K,b,4] (minx, miny, maxx, maxy) the
+    world xy box of every sequence's two seed frames' markers at each primitive and obs_people_count [K,b] the holes its observation
+    was cast against; False, None, None with a policy that does not sense people, None without a policy."""
     SEARCH_FIELDS = ("goal", "choice", "cost", "cost_terms", "colliding", "status", "goal_dist", "n_valid", "geo_dist")
     BEAM_FIELDS = ("beam_width", "path_slot", "parent", "beam_row", "path_cost", "beam_status")
     OBSTACLE_FIELDS = ("obstacle_term", "clearance", "obstacle_hit")
@@ -129,6 +132,7 @@ class PrimitiveSequence:
                     "crowd_clearance", "crowd_hit", "groups")
     POLICY_FIELDS = ("policy_mu", "policy_logvar", "obs_state", "obs_egosensing", "obs_dist", "obs_time", "policy_temperature",
                      "policy_n_mean", "policy_n_policy", "policy_ray_len", "policy_max_depth")
+    PEOPLE_FIELDS = ("people_box", "obs_people_count", "policy_sense_people")
 
     def __init__(self, markers, params, rotmat, transl, pelvis, z, betas, gender, R0, T0, search: Optional[dict] = None):
         self.markers, self.params, self.rotmat, self.transl, self.pelvis, self.z = markers, params, rotmat, transl, pelvis, z
@@ -136,7 +140,7 @@ class PrimitiveSequence:
         self.search = search
         for k in self.SEARCH_FIELDS:
             setattr(self, k, None if search is None else search[k])
-        for k in self.BEAM_FIELDS + self.OBSTACLE_FIELDS + self.JOINT_FIELDS + self.POLICY_FIELDS:
+        for k in self.BEAM_FIELDS + self.OBSTACLE_FIELDS + self.JOINT_FIELDS + self.POLICY_FIELDS + self.PEOPLE_FIELDS:
             setattr(self, k, None if search is None else search.get(k))
 
     def primitives(self, i: int) -> list:
@@ -475,7 +479,10 @@ class GAMMAPrimitiveComboGenOP:
               * sigma * eps, the rest stay eps, the prior's samples.  scene, geodesic, obstacles and groups act after the proposal
               and work as without it.  The returned z is the chosen row of the rewritten candidates.  The loop stays launches
               only.  The proposal's parameters are stated choices (see `PolicyProposal`): nobody has measured motion quality with
-              them.
+              them.  A proposal built with `sense_people=True` makes the group-mates of `groups` and the tracks of `obstacles` holes
+              of the polygon its rays are cast against (egx_primitive_people_boxes -> egx_primitive_observe_people in place of
+              egx_primitive_observe, the obstacles at the absolute frames obstacle_frame0 + 18 k and + 1 of the two seed frames);
+              without it the policy senses the static polygon only.
         Raises FloatingPointError when a chosen hand-off, or every candidate of a sequence, held a non-finite value (read once,
         after the loop); for a beam, when a node of the returned path did."""
         from .body_model import SdfScene, SdfSceneSet
@@ -630,10 +637,17 @@ class GAMMAPrimitiveComboGenOP:
         joint, policy = s.get("joint"), s.get("policy")
         if joint is not None:
             joint_in = (_lib.ptr(s["lbs_out"]["joints"]), 127, _lib.ptr(s["R0"]), _lib.ptr(s["T0"]), _lib.ptr(s["goal"]))
+        sensed = [()] * K
+        if policy is not None and policy.sense_people:      # what the policy senses of the others: the groups' CSR and the obstacles
+            from .proposal import NO_GROUPS, NO_OBSTACLES
+            crowd = s.get("joint_alive")
+            grp = NO_GROUPS if crowd is None else (_lib.ptr(crowd.group_start), _lib.ptr(crowd.group_member), _lib.ptr(crowd.member_group),
+                                                   len(crowd))
+            sensed = [(grp, NO_OBSTACLES if s["obstacles"] is None else (*s["obstacles"], s["obs_frame0"] + T_PRED * k)) for k in range(K)]
         for k in range(K):
             nxt = s["xs"][(k + 1) % 2]
             if policy is not None:
-                policy.launch(s, k, b, N, st)
+                policy.launch(s, k, b, N, st, *sensed[k])
             self._primitive(s, k, s["pp"], st, s["R0"], s["T0"])
             _lib.check(select(
                 *sel[k % 2], b, N, _vp(s["choice"][k]), _vp(s["status"][k]), _vp(s["reached"][k]),

@@ -4,8 +4,10 @@ egogen_amd/genop.py).  Per primitive and sequence: the observation the env would
 and time; crowd_ppo/crowd_env_2f.py:311-312,524-613,680-727), the actor branch of the policy on it (egx_policy_forward,
 crowd_ppo/ppo_policy.py:142-179), and the candidate latents from `mu, logvar` and the N(0, I) draws the search would have used
 as they are (entry egx_policy_propose): `n_mean` rows are mu, the rows up to `n_policy` are samples round it, the rest stay the
-prior's samples.  The search's selection then scores them like any other candidates.  Launches only: nothing here waits for the
-device once `prepare` has run."""
+prior's samples.  The search's selection then scores them like any other candidates.  With `sense_people=True` the observation is
+the reference's crowd evaluation's: the sequence's group-mates and obstacle tracks are holes of the polygon (entries
+egx_primitive_people_boxes and egx_primitive_observe_people, csrc/genop_policy_people.hip).  Launches only: nothing here waits for
+the device once `prepare` has run."""
 from __future__ import annotations
 
 import ctypes as C
@@ -19,6 +21,8 @@ from . import _lib
 MAX_CANDIDATES = 256        # EGX_MAX_CANDIDATES of include/egogen_hip.h
 POLICY_FIELDS = ("policy_mu", "policy_logvar", "obs_state", "obs_egosensing", "obs_dist", "obs_time", "policy_temperature",
                  "policy_n_mean", "policy_n_policy", "policy_ray_len", "policy_max_depth")
+PEOPLE_FIELDS = ("people_box", "obs_people_count", "policy_sense_people")      # with sense_people; None, None, False without
+NO_GROUPS, NO_OBSTACLES = (None, None, None, 0), (None, None, None, None, 0, 0, 0, 0)
 
 
 def _vp(t):
@@ -61,11 +65,21 @@ class PolicyProposal:
         - ray_len (7.0 m, the env's), max_depth (None: the packaged policy config's trainconfig.max_depth, 13): `time` of
           primitive k is 1 - min(k, max_depth) / max_depth; the clamp is a stated choice, the policy never saw a step above
           max_depth.
+        - sense_people (False): True makes the other people of the call holes of the walkable polygon the rays are cast against, as
+          in the reference's crowd evaluation: per primitive every sequence publishes the world xy box of its two seed frames'
+          markers (entry egx_primitive_people_boxes), and the observation (entry egx_primitive_observe_people in place of
+          egx_primitive_observe) takes the boxes of the sequence's group-mates under `groups=` and of the tracks of its set under
+          `obstacles=` at the two seed frames out of the polygon: an eye in a box sees nothing, a ray ends at the first box or wall.
+          Without groups and obstacles the observation is egx_primitive_observe's, bit for bit.  The result then holds people_box
+          [K,b,4] and obs_people_count [K,b] (the holes of every sequence).
     temperature, n_mean and prior_fraction are stated choices like the search's weights: nobody has measured motion quality with
     them, and no trained checkpoint has been run through this path (the instrument for it: egogen_amd/metrics.py)."""
 
     def __init__(self, policy, edges=None, edge_off=None, scene_idx=None, temperature: float = 1.0, n_mean: int = 1,
-                 prior_fraction: float = 0.25, ray_len: float = 7.0, max_depth: Optional[int] = None):
+                 prior_fraction: float = 0.25, ray_len: float = 7.0, max_depth: Optional[int] = None, sense_people: bool = False):
+        if not isinstance(sense_people, (bool, np.bool_)):
+            raise TypeError(f"sense_people must be a bool, got {type(sense_people).__name__}")
+        self.sense_people = bool(sense_people)
         runner = getattr(policy, "_runner", policy)
         if not (hasattr(runner, "forward") and hasattr(runner, "actor")):
             raise TypeError(f"policy must be a GAMMAPPOPolicy or hold a PolicyHipRunner, got {type(policy).__name__}")
@@ -143,6 +157,8 @@ class PolicyProposal:
         s.update({"policy_mu": rec(128), "policy_logvar": rec(128), "obs_state": rec(2, 402), "obs_egosensing": rec(2, 32),
                   "obs_dist": rec(), "obs_time": rec(), "policy_poly": poly, "policy_alive": alive,
                   "policy_counts": (n_mean, n_policy)})
+        if self.sense_people:
+            s.update({"people_box": rec(4), "obs_people_count": torch.empty(K, b, device=dev, dtype=torch.int32)})
         # the start: the seed bodies in the frame (R0, T0) of the seed, one row per sequence
         bm = op.body_model
         seed0 = s["seed"][::N].contiguous()
@@ -153,31 +169,52 @@ class PolicyProposal:
         self.runner._ws.get(lib.egx_policy_workspace_bytes(b), dev)     # the forward's scratch exists before the loop
         self.runner._weights()
 
-    def launch(self, s: dict, k: int, b: int, N: int, st):
-        """The three launches of primitive k ahead of the search's prefix: observe -> the actor -> propose into s["z"][k]."""
+    def launch(self, s: dict, k: int, b: int, N: int, st, groups=NO_GROUPS, obstacles=NO_OBSTACLES):
+        """The three launches of primitive k ahead of the search's prefix: observe -> the actor -> propose into s["z"][k].  With
+        `sense_people` four: the boxes first, and the observation with the holes of `groups` (group_start, group_member, member_group,
+        num_groups) and `obstacles` (the obstacle arguments of a selection entry from obs_xy to num_frames, then the absolute frame of
+        the first seed frame)."""
         lib = _lib.load()
         cur = s["xs"][k % 2]
         o = (_vp(s["obs_state"][k]), _vp(s["obs_egosensing"][k]), _vp(s["obs_dist"][k]), _vp(s["obs_time"][k]))
-        if k == 0:
-            p0 = s["policy_start"]
-            rc = lib.egx_primitive_observe(_lib.ptr(p0["joints"]), 2, 0, None, 1, _lib.ptr(p0["R0"]), _lib.ptr(p0["T0"]), _lib.ptr(p0["R0"]),
-                                           _lib.ptr(p0["T0"]), _vp(cur[0]), _vp(cur[1]), 201 * N, _lib.ptr(s["goal"]), *s["policy_poly"],
-                                           self.ray_len, 0, self.max_depth, b, *o, st)
+        if self.sense_people:
+            self._observe_people(lib, s, k, b, N, st, cur, o, groups, obstacles)
         else:
-            rc = lib.egx_primitive_observe(_lib.ptr(s["lbs_out"]["joints"]), 20, 18, _vp(s["choice"][k - 1]), N, _vp(s["rotmat"][k - 1]),
-                                           _vp(s["transl"][k - 1]), _lib.ptr(s["R0"]), _lib.ptr(s["T0"]), _vp(cur[0]), _vp(cur[1]), 201,
-                                           _lib.ptr(s["goal"]), *s["policy_poly"], self.ray_len, k, self.max_depth, b, *o, st)
-        _lib.check(rc, "egx_primitive_observe")
-        obs = {"state": s["obs_state"][k], "egosensing": s["obs_egosensing"][k], "dist": s["obs_dist"][k], "time": s["obs_time"][k]}
+            if k == 0:
+                p0 = s["policy_start"]
+                rc = lib.egx_primitive_observe(_lib.ptr(p0["joints"]), 2, 0, None, 1, _lib.ptr(p0["R0"]), _lib.ptr(p0["T0"]), _lib.ptr(p0["R0"]),
+                                               _lib.ptr(p0["T0"]), _vp(cur[0]), _vp(cur[1]), 201 * N, _lib.ptr(s["goal"]), *s["policy_poly"],
+                                               self.ray_len, 0, self.max_depth, b, *o, st)
+            else:
+                rc = lib.egx_primitive_observe(_lib.ptr(s["lbs_out"]["joints"]), 20, 18, _vp(s["choice"][k - 1]), N, _vp(s["rotmat"][k - 1]),
+                                               _vp(s["transl"][k - 1]), _lib.ptr(s["R0"]), _lib.ptr(s["T0"]), _vp(cur[0]), _vp(cur[1]), 201,
+                                               _lib.ptr(s["goal"]), *s["policy_poly"], self.ray_len, k, self.max_depth, b, *o, st)
+            _lib.check(rc, "egx_primitive_observe")
+        obs ={"state": s["obs_state"][k], "egosensing": s["obs_egosensing"][k], "dist": s["obs_dist"][k], "time": s["obs_time"][k]}
         self.runner.forward(obs, want_actor=True, want_critic=False, out={"mu": s["policy_mu"][k], "logvar": s["policy_logvar"][k]})
         n_mean, n_policy = s["policy_counts"]
         zk = s["z"][k]
         _lib.check(lib.egx_policy_propose(_vp(s["policy_mu"][k]), _vp(s["policy_logvar"][k]), _vp(zk), self.min_logvar, self.max_logvar,
                                           b, N, n_mean, n_policy, self.temperature, _vp(zk), st), "egx_policy_propose")
 
+    def _observe_people(self, lib, s, k, b, N, st, cur, o, groups, obstacles):
+        """egx_primitive_people_boxes -> egx_primitive_observe_people on the inputs `launch` hands egx_primitive_observe."""
+        box, tail = _vp(s["people_box"][k]), (*groups, *obstacles, _vp(s["obs_people_count"][k]), *o, st)
+        if k == 0:
+            p0 = s["policy_start"]
+            lead = (_lib.ptr(p0["joints"]), 2, 0, None, 1, _lib.ptr(p0["R0"]), _lib.ptr(p0["T0"]))
+            frame, x_ld, n = (_lib.ptr(p0["R0"]), _lib.ptr(p0["T0"])), 201 * N, 1
+        else:
+            lead = (_lib.ptr(s["lbs_out"]["joints"]), 20, 18, _vp(s["choice"][k - 1]), N, _vp(s["rotmat"][k - 1]), _vp(s["transl"][k - 1]))
+            frame, x_ld, n = (_lib.ptr(s["R0"]), _lib.ptr(s["T0"])), 201, N
+        _lib.check(lib.egx_primitive_people_boxes(_vp(cur[0]), _vp(cur[1]), x_ld, *frame, n, b, box, st), "egx_primitive_people_boxes")
+        _lib.check(lib.egx_primitive_observe_people(*lead, *frame, _vp(cur[0]), _vp(cur[1]), x_ld, _lib.ptr(s["goal"]), *s["policy_poly"],
+                                                    self.ray_len, k, self.max_depth, b, box, *tail), "egx_primitive_observe_people")
+
     def record(self, s: dict) -> dict:
         n_mean, n_policy = s["policy_counts"]
         out = {k: s[k] for k in POLICY_FIELDS[:6]}
         out.update(policy_temperature=self.temperature, policy_n_mean=n_mean, policy_n_policy=n_policy, policy_ray_len=self.ray_len,
-                   policy_max_depth=self.max_depth)
+                   policy_max_depth=self.max_depth, people_box=s.get("people_box"), obs_people_count=s.get("obs_people_count"),
+                   policy_sense_people=self.sense_people)
         return out

@@ -28,6 +28,9 @@ distribution of the search (`PolicyProposal`, egogen_amd/proposal.py): the check
 walkable polygon `--polygon FILE` (default: the file given to `--walkable` or `--scene` where that file holds `edges`; else no
 polygon, every ray reads +1), gives mu, sigma over the latent; the candidates are mu, samples round it (`--policy-temperature`
 scales sigma) and a share `--policy-prior-fraction` of prior samples.  Nobody has measured motion quality with these defaults.
+`--policy-sees-people` (with `--policy`) makes the other people holes of that polygon, as in the reference's crowd evaluation: the
+group-mates of `--people` (the world box of their two seed frames' markers) and the tracks of `--avoid` (the box of their cylinder
+at the two seed frames); without it the policy senses the static polygon only and the selection alone knows about the people.
 
 `--cfg <name>` is the combo config (`crowd_ppo/cfg_samp20/<name>.yml` under the working directory, else the packaged copy): it
 names the predictor's and the regressor's configs, whose checkpoints are read from `results/crowd_ppo/<config>/checkpoints`
@@ -80,6 +83,8 @@ def main(argv=None):
     parser.add_argument("--policy-prior-fraction", type=float, default=0.25, help="share of the candidates left as prior samples (with --policy)")
     parser.add_argument("--polygon", default=None, help="scene file with the walkable polygon (`edges`) the egosensing rays are cast against, or "
                         "room0 (with --policy); default: the --walkable or --scene file where it holds edges")
+    parser.add_argument("--policy-sees-people", action="store_true", help="the policy's egosensing rays stop at the other people: the "
+                        "group-mates of --people and the tracks of --avoid are holes of the polygon (with --policy)")
     args = parser.parse_args(argv)
     people = None
     if args.people is not None:
@@ -103,6 +108,8 @@ def main(argv=None):
         parser.error("--avoid needs --goal")
     if args.policy is None and (args.polygon is not None or args.policy_temperature != 1.0 or args.policy_prior_fraction != 0.25):
         parser.error("--polygon, --policy-temperature and --policy-prior-fraction need --policy")
+    if args.policy is None and args.policy_sees_people:
+        parser.error("--policy-sees-people needs --policy: without a policy nothing senses the people")
     if args.policy is not None and (args.goal is None or args.beam_width != 1):
         parser.error("--policy needs --goal (or --people) and is the greedy search (--beam-width 1)")
     polygon = None
@@ -221,9 +228,11 @@ def main(argv=None):
             policy = sw.build_policy(pargs)
             policy.load_state_dict(torch.load(args.policy, map_location="cuda")["model"])
             policy.eval()
-            proposal = PolicyProposal(policy, edges=polygon, temperature=args.policy_temperature, prior_fraction=args.policy_prior_fraction)
-            print("[INFO] policy {}: {} of {} candidates from the policy, {} of them its mean".format(
-                args.policy, proposal.counts(args.n_candidates)[1], args.n_candidates, proposal.counts(args.n_candidates)[0]))
+            proposal = PolicyProposal(policy, edges=polygon, temperature=args.policy_temperature, prior_fraction=args.policy_prior_fraction,
+                                      sense_people=args.policy_sees_people)
+            print("[INFO] policy {}: {} of {} candidates from the policy, {} of them its mean{}".format(
+                args.policy, proposal.counts(args.n_candidates)[1], args.n_candidates, proposal.counts(args.n_candidates)[0],
+                "; it senses the other people as holes of the polygon" if args.policy_sees_people else ""))
         res = op.generate_sequence_to_goal(data.repeat(nseq, 1), bparams.repeat(nseq, 1), can["betas"].astype(np.float32),
                                            goal, args.n_primitives, args.n_candidates, scene=scene, R0=R0, T0=T0,
                                            beam_width=args.beam_width, geodesic=field, obstacles=obstacles, groups=groups, policy=proposal)

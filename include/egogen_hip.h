@@ -1082,6 +1082,58 @@ int egx_primitive_observe(const float* joints, int frames_per_row, int first_fra
 int egx_policy_propose(const float* mu, const float* logvar, const float* eps, float min_logvar, float max_logvar, int num_sequences,
                        int num_candidates, int n_mean, int n_policy, float temperature, float* z, void* stream);
 
+/* egx_primitive_people_boxes - what a sequence of the search publishes of itself to the people who see it: the axis-aligned world
+ * xy box of the 2 x 67 markers of its two seed frames, one box for both frames (crowd_env_crowd_eval.py:345-352).  x0 / x1 / x_ld /
+ * R0 / T0 / num_candidates as egx_primitive_observe reads them: 201 values at row i * num_candidates of stride x_ld, the frame at
+ * row i * num_candidates.  Per marker m = (mx, my, mz), in float32:
+ *   wx = fma(R0[2], mz, fma(R0[1], my, R0[0] * mx)) + T0[0], the first product rounded, two fused onto it, one rounded addition
+ *   wy likewise with R0[3..5] and T0[1] (the nesting of the obstacle entries' world pelvis)
+ * box [num_sequences,4] = (min wx, min wy, max wx, max wy), min / max exact and order-free (a wavefront reduction by shuffles, one
+ * wave per sequence, no atomics).  A sequence one of whose 2 x 134 world coordinates is not finite gets four NaN: its box is no
+ * hole for anybody.  EGX_ERR_ARG for a NULL argument, num_candidates outside [1, EGX_MAX_CANDIDATES], x_ld < 201. */
+int egx_primitive_people_boxes(const float* x0, const float* x1, int x_ld, const float* R0, const float* T0, int num_candidates,
+                               int num_sequences, float* box, void* stream);
+
+/* egx_primitive_observe_people - egx_primitive_observe for a sequence that sees other people: its group-mates and its obstacle
+ * tracks are holes of the walkable polygon the rays are cast against (the reference's crowd evaluation: dummy_vector_env.py:34-39,
+ * 81-84 the other agents' boxes as holes, crowd_env_crowd_eval.py:796-820 egosensing against that polygon).  Every argument of
+ * egx_primitive_observe up to num_sequences with its meaning, then:
+ *   box [num_sequences,4]  what egx_primitive_people_boxes wrote for the same seed frames; may be NULL without groups
+ *   group_start [num_groups+1] / group_member / member_group [num_sequences]  the groups of egx_primitive_select_joint in CSR form and
+ *          the group of every sequence; all three NULL for no groups.  The holes of sequence i: box[m] of every member m != i of
+ *          group member_group[i] (the group clamped into [0, num_groups), start, size and members as egx_primitive_select_joint
+ *          clamps them, at most EGX_MAX_GROUP members); a member that has reached its goal still is one
+ *   obs_xy [num_sets,max_obstacles,num_frames,2] / obs_radius / obs_count / obs_index / num_sets / max_obstacles / num_frames  the
+ *          obstacles of the *_obstacles selection entries, all NULL / 0 for none; frame: the absolute frame of the first seed frame
+ *          (obstacle_frame0 + 18 k).  Track o < obs_count[set] of sequence i's set (obs_index[i] clamped, set 0 where NULL; the
+ *          count clamped into [0, min(max_obstacles, EGX_MAX_OBSTACLES)]) is the hole (min(ax - r, bx - r), min(ay - r, by - r),
+ *          max(ax + r, bx + r), max(ay + r, by + r)), a and b its positions at the frames `frame` and `frame + 1`, each clamped into
+ *          [0, num_frames) (a track is held at its first / last position), r its radius: one rounded float32 difference or sum each
+ *   A box with a non-finite entry is no hole.  people_count [num_sequences] int32: the holes of the sequence, at most 31 + 32 where it
+ *          is a member of its own group.
+ * egosensing: the walkable region is the static polygon (even-odd over its ring edges; the unbounded plane without edges) minus
+ * the UNION of the holes (shapely's union_all in the reference: a point in two overlapping boxes is in a hole).  The eye sees
+ * nothing, every ray -1, where it lies outside the static polygon or in a hole (minx <= x < maxx and miny <= y < maxy).  Otherwise
+ * d = the smallest hit parameter over the static edges and the four edges of every hole ((lo,lo) -> (hi,lo) -> (hi,hi) -> (lo,hi)
+ * -> (lo,lo)), capped at ray_len, with the intersection test and the |end - eye| step of egosensing_frame, float64 throughout, and
+ * the ray reads -1 + 2 d / ray_len (egosensing_frame_holes, csrc/egx_egosense.h).  A sequence without a hole gets the bits of
+ * egx_primitive_observe; state, dist and time always do.
+ * 256 threads per sequence: wave 0 stages the holes in LDS (one lane each, compacted by a ballot) and holds the 64 (frame, ray)
+ * pairs, the other waves the markers; the static edges are staged as in egx_primitive_observe.  No atomics, no waiting, nothing
+ * between workgroups: row i depends on sequence i's inputs, its mates' box rows and its obstacle set.  EGX_ERR_ARG for everything
+ * egx_primitive_observe rejects, a NULL people_count, some but not all of the group arrays or num_groups < 1 with them, a NULL box
+ * with groups, some but not all of obs_xy / obs_radius / obs_count (or num_sets < 1, or an obs_index) without them, max_obstacles
+ * outside [0, EGX_MAX_OBSTACLES], num_frames < 1 with obstacles. */
+int egx_primitive_observe_people(const float* joints, int frames_per_row, int first_frame, const int32_t* choice, int num_candidates,
+                                 const float* R_prev, const float* T_prev, const float* R0, const float* T0, const float* x0,
+                                 const float* x1, int x_ld, const float* goal, const float* edges, const int32_t* edge_off,
+                                 const int32_t* scene_idx, int num_scenes, float ray_len, int step, int max_depth, int num_sequences,
+                                 const float* box, const int32_t* group_start, const int32_t* group_member,
+                                 const int32_t* member_group, int num_groups, const float* obs_xy, const float* obs_radius,
+                                 const int32_t* obs_count, const int32_t* obs_index, int num_sets, int max_obstacles, int num_frames,
+                                 int frame, int32_t* people_count, float* state, float* egosensing, float* dist, float* time,
+                                 void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Measuring finished motions (csrc/motion_metrics.hip, egogen_amd/metrics.py)
  * ------------------------------------------------------------------------------------------- */
