@@ -6,8 +6,8 @@ crowd_ppo/ppo_policy.py:142-179), and the candidate latents from `mu, logvar` an
 as they are (entry egx_policy_propose): `n_mean` rows are mu, the rows up to `n_policy` are samples round it, the rest stay the
 prior's samples.  The search's selection then scores them like any other candidates.  With `sense_people=True` the observation is
 the reference's crowd evaluation's: the sequence's group-mates and obstacle tracks are holes of the polygon (entries
-egx_primitive_people_boxes and egx_primitive_observe_people, csrc/genop_policy_people.hip).  Launches only: nothing here waits for
-the device once `prepare` has run."""
+egx_primitive_people_boxes and egx_primitive_observe_people; all four entries are csrc/genop_policy.hip).  Launches only: nothing here
+waits for the device once `prepare` has run."""
 from __future__ import annotations
 
 import ctypes as C
@@ -177,39 +177,27 @@ class PolicyProposal:
         lib = _lib.load()
         cur = s["xs"][k % 2]
         o = (_vp(s["obs_state"][k]), _vp(s["obs_egosensing"][k]), _vp(s["obs_dist"][k]), _vp(s["obs_time"][k]))
+        if k == 0:      # the seed bodies in the seed's frame: one row per sequence, its seed frames N rows apart
+            p0 = s["policy_start"]
+            lead = (_lib.ptr(p0["joints"]), 2, 0, None, 1, _lib.ptr(p0["R0"]), _lib.ptr(p0["T0"]))
+            frame, x_ld, n = (_lib.ptr(p0["R0"]), _lib.ptr(p0["T0"])), 201 * N, 1
+        else:           # the last two bodies of the candidate chosen at primitive k - 1, in the frame that primitive was made in
+            lead = (_lib.ptr(s["lbs_out"]["joints"]), 20, 18, _vp(s["choice"][k - 1]), N, _vp(s["rotmat"][k - 1]), _vp(s["transl"][k - 1]))
+            frame, x_ld, n = (_lib.ptr(s["R0"]), _lib.ptr(s["T0"])), 201, N
+        common = (*lead, *frame, _vp(cur[0]), _vp(cur[1]), x_ld, _lib.ptr(s["goal"]), *s["policy_poly"], self.ray_len, k, self.max_depth, b)
         if self.sense_people:
-            self._observe_people(lib, s, k, b, N, st, cur, o, groups, obstacles)
+            box = _vp(s["people_box"][k])
+            _lib.check(lib.egx_primitive_people_boxes(_vp(cur[0]), _vp(cur[1]), x_ld, *frame, n, b, box, st), "egx_primitive_people_boxes")
+            _lib.check(lib.egx_primitive_observe_people(*common, box, *groups, *obstacles, _vp(s["obs_people_count"][k]), *o, st),
+                       "egx_primitive_observe_people")
         else:
-            if k == 0:
-                p0 = s["policy_start"]
-                rc = lib.egx_primitive_observe(_lib.ptr(p0["joints"]), 2, 0, None, 1, _lib.ptr(p0["R0"]), _lib.ptr(p0["T0"]), _lib.ptr(p0["R0"]),
-                                               _lib.ptr(p0["T0"]), _vp(cur[0]), _vp(cur[1]), 201 * N, _lib.ptr(s["goal"]), *s["policy_poly"],
-                                               self.ray_len, 0, self.max_depth, b, *o, st)
-            else:
-                rc = lib.egx_primitive_observe(_lib.ptr(s["lbs_out"]["joints"]), 20, 18, _vp(s["choice"][k - 1]), N, _vp(s["rotmat"][k - 1]),
-                                               _vp(s["transl"][k - 1]), _lib.ptr(s["R0"]), _lib.ptr(s["T0"]), _vp(cur[0]), _vp(cur[1]), 201,
-                                               _lib.ptr(s["goal"]), *s["policy_poly"], self.ray_len, k, self.max_depth, b, *o, st)
-            _lib.check(rc, "egx_primitive_observe")
+            _lib.check(lib.egx_primitive_observe(*common, *o, st), "egx_primitive_observe")
         obs ={"state": s["obs_state"][k], "egosensing": s["obs_egosensing"][k], "dist": s["obs_dist"][k], "time": s["obs_time"][k]}
         self.runner.forward(obs, want_actor=True, want_critic=False, out={"mu": s["policy_mu"][k], "logvar": s["policy_logvar"][k]})
         n_mean, n_policy = s["policy_counts"]
         zk = s["z"][k]
         _lib.check(lib.egx_policy_propose(_vp(s["policy_mu"][k]), _vp(s["policy_logvar"][k]), _vp(zk), self.min_logvar, self.max_logvar,
                                           b, N, n_mean, n_policy, self.temperature, _vp(zk), st), "egx_policy_propose")
-
-    def _observe_people(self, lib, s, k, b, N, st, cur, o, groups, obstacles):
-        """egx_primitive_people_boxes -> egx_primitive_observe_people on the inputs `launch` hands egx_primitive_observe."""
-        box, tail = _vp(s["people_box"][k]), (*groups, *obstacles, _vp(s["obs_people_count"][k]), *o, st)
-        if k == 0:
-            p0 = s["policy_start"]
-            lead = (_lib.ptr(p0["joints"]), 2, 0, None, 1, _lib.ptr(p0["R0"]), _lib.ptr(p0["T0"]))
-            frame, x_ld, n = (_lib.ptr(p0["R0"]), _lib.ptr(p0["T0"])), 201 * N, 1
-        else:
-            lead = (_lib.ptr(s["lbs_out"]["joints"]), 20, 18, _vp(s["choice"][k - 1]), N, _vp(s["rotmat"][k - 1]), _vp(s["transl"][k - 1]))
-            frame, x_ld, n = (_lib.ptr(s["R0"]), _lib.ptr(s["T0"])), 201, N
-        _lib.check(lib.egx_primitive_people_boxes(_vp(cur[0]), _vp(cur[1]), x_ld, *frame, n, b, box, st), "egx_primitive_people_boxes")
-        _lib.check(lib.egx_primitive_observe_people(*lead, *frame, _vp(cur[0]), _vp(cur[1]), x_ld, _lib.ptr(s["goal"]), *s["policy_poly"],
-                                                    self.ray_len, k, self.max_depth, b, box, *tail), "egx_primitive_observe_people")
 
     def record(self, s: dict) -> dict:
         n_mean, n_policy = s["policy_counts"]

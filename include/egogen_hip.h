@@ -1116,7 +1116,7 @@ int egx_primitive_people_boxes(const float* x0, const float* x1, int x_ld, const
  * nothing, every ray -1, where it lies outside the static polygon or in a hole (minx <= x < maxx and miny <= y < maxy).  Otherwise
  * d = the smallest hit parameter over the static edges and the four edges of every hole ((lo,lo) -> (hi,lo) -> (hi,hi) -> (lo,hi)
  * -> (lo,lo)), capped at ray_len, with the intersection test and the |end - eye| step of egosensing_frame, float64 throughout, and
- * the ray reads -1 + 2 d / ray_len (egosensing_frame_holes, csrc/egx_egosense.h).  A sequence without a hole gets the bits of
+ * the ray reads -1 + 2 d / ray_len (HoleEdges through egosensing_rays, csrc/egx_egosense.h).  A sequence without a hole gets the bits of
  * egx_primitive_observe; state, dist and time always do.
  * 256 threads per sequence: wave 0 stages the holes in LDS (one lane each, compacted by a ballot) and holds the 64 (frame, ray)
  * pairs, the other waves the markers; the static edges are staged as in egx_primitive_observe.  No atomics, no waiting, nothing

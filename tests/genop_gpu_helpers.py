@@ -1,7 +1,8 @@
 """What tests/test_genop_gpu.py, test_genop_search_gpu.py and test_genop_beam_gpu.py share: the `held()` yardstick, the synthetic
 walkers and the input pool built from them, the operator on seeded weights (fixtures `small_world`, `search_world`), a wrapper
 per launch of csrc/genop.hip that returns what the kernel wrote, and `patched_loop`, which stands in for a primitive loop of the
-operator for the length of a `with` block.  A plain module: the test files import the names they use, fixtures included."""
+operator for the length of a `with` block; and what tests/test_genop_policy_gpu.py and test_genop_people_gpu.py share: the wrappers
+of the observe entries of csrc/genop_policy.hip and the yardstick of their rays.  A plain module: the test files import the names they use, fixtures included."""
 import contextlib
 import ctypes as C
 import os
@@ -170,7 +171,7 @@ def search_world(small_world):
 
 # ---- the hand-off launches -------------------------------------------------------------------------------------------
 def _vp(t):
-    return C.c_void_p(t.data_ptr())
+    return None if t is None else C.c_void_p(t.data_ptr())
 
 
 def _handoff_args(d, rows, jpb, rf, recs, with_params, Y_gen=None, nan_rows=()):
@@ -356,3 +357,47 @@ def _restate(i, b, N, rf, weights, pene_thres, dtype):
     r = sref.score(i["Y_gen"], i["X"], i["J"], i["mp"], i["R0"], i["T0"], i["pene"], i["goal_rows"], _feet(), weights, pene_thres, rf, dtype)
     terms = torch.stack([r[t] for t in sref.TERMS], -1).reshape(b, N, 5)
     return r["cost"].reshape(b, N), terms, r["colliding"].reshape(b, N)
+
+
+# ---- the observe launches of csrc/genop_policy.hip -------------------------------------------------------------------
+RAY_LEN, MAX_DEPTH = 7.0, 13
+
+
+def _poly_dev(poly):
+    """(edges, edge_off, scene_idx, ...) as numpy or None -> the four polygon arguments of an observe entry, on the device"""
+    if poly is None:
+        return (None, None, None, 0)
+    dev = lambda a, dtype: torch.as_tensor(np.ascontiguousarray(a), dtype=dtype).cuda().contiguous()
+    return (dev(poly[0], torch.float32), dev(poly[1], torch.int32), dev(poly[2], torch.int32), len(poly[1]) - 1)
+
+
+def _observe_lead(g, fpr, first, N, choice, x_ld, poly, step, b, ray_len=RAY_LEN, max_depth=MAX_DEPTH):
+    """the arguments the two observe entries share, up to num_sequences; g: the device tensors joints, R_prev, T_prev, R0, T0, x0,
+    x1 and goal by name, poly: what `_poly_dev` returns"""
+    return (_vp(g["joints"]), fpr, first, _vp(choice), N, _vp(g["R_prev"]), _vp(g["T_prev"]), _vp(g["R0"]), _vp(g["T0"]), _vp(g["x0"]), _vp(g["x1"]),
+            x_ld, _vp(g["goal"]), *[_vp(t) if torch.is_tensor(t) else t for t in poly], float(ray_len), int(step), int(max_depth), b)
+
+
+def _observe_outputs(b):
+    """NaN-filled state, egosensing, dist, time"""
+    f = lambda *s: torch.full(s, float("nan"), device="cuda")
+    return (f(b, 2, 402), f(b, 2, 32), f(b), f(b))
+
+
+def _observe(g, fpr, first, N, choice, x_ld, poly, step, b, **kw):
+    """egx_primitive_observe into NaN-filled outputs -> state, egosensing, dist, time (device tensors)"""
+    from egogen_amd import _lib
+    o = _observe_outputs(b)
+    _lib.check(_lib.load().egx_primitive_observe(*_observe_lead(g, fpr, first, N, choice, x_ld, poly, step, b, **kw), *[_vp(t) for t in o],
+                                                 _lib.current_stream_ptr()), "egx_primitive_observe")
+    torch.cuda.synchronize()
+    return o
+
+
+def _check_rays(name, group, got, ego64, undecidable):
+    from tests.genop_policy_ref import EGO_FLOOR
+    keep = ~undecidable
+    assert float(undecidable.float().mean()) <= UNDECIDABLE_CAP, (name, group, int(undecidable.sum()))
+    err = (got.cpu().double() - ego64.double()).abs()[keep]
+    print(f"| {name} | {group} | rays {int(keep.sum())} of {keep.numel()} | max error {float(err.max()):.3e} | floor {EGO_FLOOR:.1e} |")
+    assert float(err.max()) <= EGO_FLOOR, (name, group, float(err.max()))

@@ -1,4 +1,4 @@
-"""Restatement of the two launches of csrc/genop_policy_people.hip in torch / numpy: the world xy box a sequence publishes of its two
+"""Restatement of the two people launches of csrc/genop_policy.hip in torch / numpy: the world xy box a sequence publishes of its two
 seed frames' markers (float64 the truth of the `held()` rule, float32 its yardstick) and the observation whose rays are cast against
 the static polygon minus the UNION of the boxes of the sequence's group-mates and of its obstacle tracks at the two seed frames.
 State, dist and time are `genop_policy_ref.observe`'s; the rays restate `oracle.env.calc_egosensing` with the holes' containment
@@ -131,10 +131,14 @@ def observe_people(j2, R_prev, T_prev, R0, T0, x0, x1, goal, poly, ray_len, step
 # ---- the cases the CPU and the GPU tests share -----------------------------------------------------------------------------
 def people_polygon(kind):
     """-> (poly or None, eyes [5,2]).  'square': one scene, the obstacle-only sequence starts outside it (blind, with holes);
-    'two': scene 0 the square, scene 1 room0, the group in the square, the two single sequences in room0."""
+    'two': scene 0 the square, scene 1 room0, the group in the square, the two single sequences in room0; 'gon1200': one scene,
+    `genop_policy_ref.gon_edges`, everybody inside it."""
     eyes = np.array([[-1.0, -1.2], [2.6, 2.1], [-2.5, 2.0], [0.0, 2.2], [5.0, 0.3]])
     if kind == "none":
         return None, eyes
+    if kind == "gon1200":
+        gon = ref.gon_edges()
+        return (gon, np.array([0, len(gon)], np.int32), np.zeros(B, np.int32)), eyes
     sq = ref.square_hole_edges()
     if kind == "square":
         return (sq, np.array([0, len(sq)], np.int32), np.zeros(B, np.int32)), eyes

@@ -24,12 +24,26 @@ def room0_edges():
     return synth.rings_to_edges(synth.room0_polygon()).astype(np.float32)
 
 
+GON_EDGES, GON_RADIUS = 1200, 6.0
+
+
+def gon_edges():
+    """A regular GON_EDGES-gon of GON_RADIUS metres about the origin: more edges than the 1024 the observe kernel stages in LDS, so it
+    reads them from global memory; every eye position of the cases (at most 5.2 m from the origin) lies inside it, walls in reach."""
+    a = 2.0 * np.pi * np.arange(GON_EDGES) / GON_EDGES
+    ring = GON_RADIUS * np.stack([np.cos(a), np.sin(a)], 1)
+    return synth.rings_to_edges([np.concatenate([ring, ring[:1]])]).astype(np.float32)
+
+
 def polygon(kind):
     """-> (edges [E,4] float32, edge_off [S+1] int32, scene_idx [B] int32, world xy of the B eyes) or None for no polygon.
     'square': one scene, sequence 2 starts outside it; 'two': scene 0 the square, scene 1 room0 (6 rings, 89 edges), the sequences in
-    scenes 1, 0, 1."""
+    scenes 1, 0, 1; 'gon1200': one scene, `gon_edges`, the square's eye positions, all of them inside."""
     if kind == "none":
         return None
+    if kind == "gon1200":
+        gon = gon_edges()
+        return gon, np.array([0, len(gon)], np.int32), np.zeros(B, np.int32), np.array([[-1.0, -1.2], [2.6, 2.1], [5.0, 0.3]])
     sq = square_hole_edges()
     if kind == "square":
         return sq, np.array([0, len(sq)], np.int32), np.zeros(B, np.int32), np.array([[-1.0, -1.2], [2.6, 2.1], [5.0, 0.3]])
@@ -127,6 +141,7 @@ def undecidable(d, poly, ray_len):
 
 
 OBSERVE_CASES = [(kind, N, mode) for kind in ("none", "square", "two") for N in (1, 5) for mode in ((20, 18), (2, 0))]
+OBSERVE_CASES.append(("gon1200", 5, (20, 18)))          # the branch of a scene too large for LDS
 
 
 def propose(mu, logvar, eps, min_logvar, max_logvar, N, n_mean, n_policy, temperature, dtype):

@@ -101,7 +101,7 @@ def test_boxes_restatement():
     assert len(pref.holes(pref.SEES, b64, groups, None, None, 0, torch.float64)) == 2
 
 
-@pytest.mark.parametrize("kind", ["none", "square", "two"])
+@pytest.mark.parametrize("kind", ["none", "square", "two", "gon1200"])
 def test_every_sequence_plays_its_part(kind):
     """the layout the GPU test relies on: who sees, who is blind and why, who has how many holes"""
     track_seen = 0

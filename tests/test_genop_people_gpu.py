@@ -1,4 +1,4 @@
-"""The policy's observation with other people in it, on the device: the two launches of csrc/genop_policy_people.hip against the
+"""The policy's observation with other people in it, on the device: the people launches of csrc/genop_policy.hip against the
 float64 / float32 restatement of tests/genop_people_ref.py and against egx_primitive_observe, and
 `generate_sequence_to_goal(policy=PolicyProposal(..., sense_people=True))` against its records.
 
@@ -7,33 +7,21 @@ tests use for egosensing (3.6e-4), a ray whose float64 value moves by more than 
 UNDECIDABLE_CAP of the rays of a case (tests/test_genop_people_cpu.py holds that share for these seeds and positions without a device).
 A blind eye reads exactly -1; people_count is exact; state, dist and time, and the rays of a sequence without a hole, are the bits of
 egx_primitive_observe: torch.equal."""
-import ctypes as C
-
 import numpy as np
 import pytest
 import torch
 
 from tests import genop_people_ref as pref
 from tests import genop_policy_ref as ref
-from tests.genop_gpu_helpers import CFG_RF, UNDECIDABLE_CAP, W_TEST, held, patched_loop, search_world, small_world  # noqa: F401
+from tests.genop_gpu_helpers import (CFG_RF, MAX_DEPTH, RAY_LEN, W_TEST, _check_rays, _observe, _observe_lead, _observe_outputs, _poly_dev, _vp,
+                                     held, patched_loop, search_world, small_world)  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-RAY_LEN, MAX_DEPTH = 7.0, 13
 NO_GROUPS, NO_OBS = (None, None, None, 0), (None, None, None, None, 0, 0, 0)
-
-
-def _vp(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
 
 
 def _dev(a, dtype=None):
     return None if a is None else torch.as_tensor(np.ascontiguousarray(a) if isinstance(a, np.ndarray) else a, dtype=dtype).cuda().contiguous()
-
-
-def _poly_dev(poly):
-    if poly is None:
-        return (None, None, None, 0)
-    return (_dev(poly[0], torch.float32), _dev(poly[1], torch.int32), _dev(poly[2], torch.int32), len(poly[1]) - 1)
 
 
 def _groups_dev(ids):
@@ -52,26 +40,6 @@ def _obs_dev(obs, index):
             xy.shape[2])
 
 
-def _lead(g, fpr, first, N, choice, x_ld, poly, step, b):
-    """the arguments the two observe entries share, up to num_sequences"""
-    return (_vp(g["joints"]), fpr, first, _vp(choice), N, _vp(g["R_prev"]), _vp(g["T_prev"]), _vp(g["R0"]), _vp(g["T0"]), _vp(g["x0"]), _vp(g["x1"]),
-            x_ld, _vp(g["goal"]), *[_vp(t) if torch.is_tensor(t) else t for t in poly], float(RAY_LEN), int(step), MAX_DEPTH, b)
-
-
-def _outputs(b):
-    f = lambda *s: torch.full(s, float("nan"), device="cuda")
-    return (f(b, 2, 402), f(b, 2, 32), f(b), f(b))
-
-
-def _observe(g, fpr, first, N, choice, x_ld, poly, step, b):
-    from egogen_amd import _lib
-    o = _outputs(b)
-    _lib.check(_lib.load().egx_primitive_observe(*_lead(g, fpr, first, N, choice, x_ld, poly, step, b), *[_vp(t) for t in o],
-                                                 _lib.current_stream_ptr()), "egx_primitive_observe")
-    torch.cuda.synchronize()
-    return o
-
-
 def _boxes(x0, x1, x_ld, R0, T0, N, b):
     from egogen_amd import _lib
     box = torch.full((b, 4), float("nan"), device="cuda")
@@ -84,10 +52,10 @@ def _boxes(x0, x1, x_ld, R0, T0, N, b):
 def _observe_people(g, fpr, first, N, choice, x_ld, poly, step, b, box, groups, obs, frame):
     """egx_primitive_observe_people into NaN / -7 filled outputs -> state, egosensing, dist, time, people_count"""
     from egogen_amd import _lib
-    o = _outputs(b)
+    o = _observe_outputs(b)
     count = torch.full((b,), -7, dtype=torch.int32, device="cuda")
     tail = [_vp(t) if torch.is_tensor(t) else t for t in (*groups, *obs)]
-    _lib.check(_lib.load().egx_primitive_observe_people(*_lead(g, fpr, first, N, choice, x_ld, poly, step, b), _vp(box), *tail, int(frame),
+    _lib.check(_lib.load().egx_primitive_observe_people(*_observe_lead(g, fpr, first, N, choice, x_ld, poly, step, b), _vp(box), *tail, int(frame),
                                                         _vp(count), *[_vp(t) for t in o], _lib.current_stream_ptr()),
                "egx_primitive_observe_people")
     torch.cuda.synchronize()
@@ -96,14 +64,6 @@ def _observe_people(g, fpr, first, N, choice, x_ld, poly, step, b, box, groups, 
 
 def _to_dev(d):
     return {k: v.cuda().contiguous() for k, v in d.items() if torch.is_tensor(v)}
-
-
-def _check_rays(name, group, got, ego64, undecidable):
-    keep = ~undecidable
-    assert float(undecidable.float().mean()) <= UNDECIDABLE_CAP, (name, group, int(undecidable.sum()))
-    err = (got.cpu().double() - ego64.double()).abs()[keep]
-    print(f"| {name} | {group} | rays {int(keep.sum())} of {keep.numel()} | max error {float(err.max()):.3e} | floor {ref.EGO_FLOOR:.1e} |")
-    assert float(err.max()) <= ref.EGO_FLOOR, (name, group, float(err.max()))
 
 
 # ---- the boxes -----------------------------------------------------------------------------------------------------------------

@@ -45,13 +45,16 @@ def test_time_is_clamped_and_no_polygon_reads_one():
 
 
 def test_undecidable_rays_stay_under_the_cap():
-    """The eye positions of the GPU test's cases: the float64 restatement alone leaves out at most UNDECIDABLE_CAP of all rays."""
+    """The eye positions of the GPU test's cases, the 1200-gon among them: the float64 restatement alone leaves out at most
+    UNDECIDABLE_CAP of the rays of a case, which is what the GPU test asks, and of all rays."""
     left_out = total = 0
+    assert ("gon1200", 5, (20, 18)) in ref.OBSERVE_CASES and ref.polygon("gon1200")[0].shape == (1200, 4)
     for kind, N, (fpr, first) in ref.OBSERVE_CASES:
         poly = ref.polygon(kind)
         if poly is None:
             continue
         u = ref.undecidable(ref.observe_inputs(N, fpr, first, poly[3]), poly, RAY_LEN)
+        assert float(u.float().mean()) <= UNDECIDABLE_CAP, (kind, N, fpr, int(u.sum()), u.numel())
         left_out, total = left_out + int(u.sum()), total + u.numel()
     assert total > 0 and left_out / total <= UNDECIDABLE_CAP, (left_out, total)
 

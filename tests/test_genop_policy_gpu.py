@@ -6,7 +6,6 @@ Yardsticks.  state, dist, time and the sampled rows of the proposal: the project
 the float32 restatement's.  Rays: the floor the env tests use for egosensing (3.6e-4, tests/test_env_gpu.py), a ray whose float64 value
 moves by more than that under a 1e-5 m shift of the eye left out, at most UNDECIDABLE_CAP of all rays.  Everything that is a copy or the
 same device function on the same inputs: torch.equal."""
-import ctypes as C
 import os
 import subprocess
 import sys
@@ -16,44 +15,11 @@ import pytest
 import torch
 
 from tests import genop_policy_ref as ref
-from tests.genop_gpu_helpers import CFG_RF, ROOT, UNDECIDABLE_CAP, W_TEST, held, patched_loop, search_world, small_world  # noqa: F401
+from tests.genop_gpu_helpers import (CFG_RF, MAX_DEPTH, RAY_LEN, ROOT, UNDECIDABLE_CAP, W_TEST, _check_rays, _observe, _poly_dev, _vp, held,
+                                     patched_loop, search_world, small_world)  # noqa: F401
 from tests.helpers import seeded_prior_state_dict, seeded_vposer_state_dict
 
 pytestmark = pytest.mark.gpu
-RAY_LEN, MAX_DEPTH = 7.0, 13
-
-
-def _vp(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
-def _observe(joints, fpr, first, choice, N, R_prev, T_prev, R0, T0, x0, x1, x_ld, goal, poly, ray_len, step, max_depth, b):
-    """egx_primitive_observe into NaN-filled outputs -> state, egosensing, dist, time (device tensors)"""
-    from egogen_amd import _lib
-    f = lambda *s: torch.full(s, float("nan"), device="cuda")
-    o = (f(b, 2, 402), f(b, 2, 32), f(b), f(b))
-    edges, off, idx, S = (None, None, None, 0) if poly is None else poly
-    _lib.check(_lib.load().egx_primitive_observe(_vp(joints), fpr, first, _vp(choice), N, _vp(R_prev), _vp(T_prev), _vp(R0), _vp(T0), _vp(x0),
-                                                 _vp(x1), x_ld, _vp(goal), _vp(edges), _vp(off), _vp(idx), S, float(ray_len), int(step),
-                                                 int(max_depth), b, *[_vp(t) for t in o], _lib.current_stream_ptr()), "egx_primitive_observe")
-    torch.cuda.synchronize()
-    return o
-
-
-def _poly_dev(poly):
-    if poly is None:
-        return None
-    edges, off, idx = poly[:3]
-    return (torch.from_numpy(np.ascontiguousarray(edges, np.float32)).cuda(), torch.from_numpy(np.asarray(off, np.int32)).cuda(),
-            torch.from_numpy(np.asarray(idx, np.int32)).cuda(), len(off) - 1)
-
-
-def _check_rays(name, group, got, ego64, undecidable):
-    keep = ~undecidable
-    assert float(undecidable.float().mean()) <= UNDECIDABLE_CAP, (name, group, int(undecidable.sum()))
-    err = (got.cpu().double() - ego64.double()).abs()[keep]
-    print(f"| {name} | {group} | rays {int(keep.sum())} of {keep.numel()} | max error {float(err.max()):.3e} | floor {ref.EGO_FLOOR:.1e} |")
-    assert float(err.max()) <= ref.EGO_FLOOR, (name, group, float(err.max()))
 
 
 # ---- observe against float64 ---------------------------------------------------------------------------------------------------
@@ -64,8 +30,7 @@ def test_observe_against_float64(kind, N, mode):
     d = ref.observe_inputs(N, fpr, first, None if poly is None else poly[3])
     g = {k: v.cuda().contiguous() for k, v in d.items() if torch.is_tensor(v)}
     step = 15 if N == 5 else 4                   # above max_depth once: clamped
-    got = _observe(g["joints"], fpr, first, g["choice"], N, g["R_prev"], g["T_prev"], g["R0"], g["T0"], g["x0"], g["x1"], 201, g["goal"],
-                   _poly_dev(poly), RAY_LEN, step, MAX_DEPTH, ref.B)
+    got = _observe(g, fpr, first, N, g["choice"], 201, _poly_dev(poly), step, ref.B)
     t64 = ref.observe_case(d, poly, RAY_LEN, step, MAX_DEPTH, torch.float64)
     t32 = ref.observe_case(d, poly, RAY_LEN, step, MAX_DEPTH, torch.float32)
     group = f"{kind} N={N} frame {first} of {fpr}"
@@ -83,10 +48,8 @@ def test_observe_against_float64(kind, N, mode):
         assert torch.equal(got[3].cpu(), torch.zeros(ref.B))
     if N > 1:        # NULL choice is candidate 0
         d0 = dict(d, choice=torch.zeros(ref.B, dtype=torch.int32))
-        got0 = _observe(g["joints"], fpr, first, None, N, g["R_prev"], g["T_prev"], g["R0"], g["T0"], g["x0"], g["x1"], 201, g["goal"],
-                        _poly_dev(poly), RAY_LEN, step, MAX_DEPTH, ref.B)
-        zero = _observe(g["joints"], fpr, first, torch.zeros(ref.B, dtype=torch.int32, device="cuda"), N, g["R_prev"], g["T_prev"], g["R0"],
-                        g["T0"], g["x0"], g["x1"], 201, g["goal"], _poly_dev(poly), RAY_LEN, step, MAX_DEPTH, ref.B)
+        got0 = _observe(g, fpr, first, N, None, 201, _poly_dev(poly), step, ref.B)
+        zero = _observe(g, fpr, first, N, torch.zeros(ref.B, dtype=torch.int32, device="cuda"), 201, _poly_dev(poly), step, ref.B)
         assert all(torch.equal(a, b_) for a, b_ in zip(got0, zero))
         held("observe dist, no choice", group, got0[2], ref.observe_case(d0, poly, RAY_LEN, step, MAX_DEPTH, torch.float64)[2],
              ref.observe_case(d0, poly, RAY_LEN, step, MAX_DEPTH, torch.float32)[2])
@@ -99,12 +62,11 @@ def test_observe_rows_do_not_depend_on_the_batch():
     d = ref.observe_inputs(N, 20, 18, poly[3])
     g = {k: v.cuda().contiguous() for k, v in d.items() if torch.is_tensor(v)}
     pd = _poly_dev(poly)
-    full = _observe(g["joints"], 20, 18, g["choice"], N, g["R_prev"], g["T_prev"], g["R0"], g["T0"], g["x0"], g["x1"], 201, g["goal"], pd,
-                    RAY_LEN, 2, MAX_DEPTH, ref.B)
+    full = _observe(g, 20, 18, N, g["choice"], 201, pd, 2, ref.B)
     one = lambda t, per: t[per:2 * per].contiguous()
-    alone = _observe(one(g["joints"], N * 20), 20, 18, one(g["choice"], 1), N, one(g["R_prev"], 1), one(g["T_prev"], 1), one(g["R0"], N),
-                     one(g["T0"], N), one(g["x0"], N), one(g["x1"], N), 201, one(g["goal"], 1), (pd[0], pd[1], one(pd[2], 1), pd[3]), RAY_LEN,
-                     2, MAX_DEPTH, 1)
+    g1 = {"joints": one(g["joints"], N * 20), "R_prev": one(g["R_prev"], 1), "T_prev": one(g["T_prev"], 1), "R0": one(g["R0"], N),
+          "T0": one(g["T0"], N), "x0": one(g["x0"], N), "x1": one(g["x1"], N), "goal": one(g["goal"], 1)}
+    alone = _observe(g1, 20, 18, N, one(g["choice"], 1), 201, (pd[0], pd[1], one(pd[2], 1), pd[3]), 2, 1)
     for a, f in zip(alone, full):
         assert torch.equal(a[0], f[1])
 
@@ -151,8 +113,10 @@ def test_observe_equals_the_env_step(small_world):
     torch.cuda.synchronize()
     assert env.steps.tolist() == [1] * A
     prev = env.prev_frame
-    got = _observe(env.joints, 20, 18, None, 1, prev[:, :9].contiguous(), prev[:, 9:].contiguous(), env.R0, env.T0, env.state[:, 0], env.state[:, 1],
-                   804, env.wpath[:, 1].contiguous(), (env.edges, env.edge_off, env.scene_idx, 1), env.cfg["ray_len"], 1, env.cfg["max_depth"], A)
+    g = {"joints": env.joints, "R_prev": prev[:, :9].contiguous(), "T_prev": prev[:, 9:].contiguous(), "R0": env.R0, "T0": env.T0,
+         "x0": env.state[:, 0], "x1": env.state[:, 1], "goal": env.wpath[:, 1].contiguous()}
+    got = _observe(g, 20, 18, 1, None, 804, (env.edges, env.edge_off, env.scene_idx, 1), 1, A, ray_len=env.cfg["ray_len"],
+                   max_depth=env.cfg["max_depth"])
     differ = [name for name, mine, theirs in zip(("state", "egosensing", "dist", "time"), got, (env.state, env.obs_ego, env.obs_dist, env.obs_time))
               if not torch.equal(mine, theirs)]
     assert not differ, (differ, (got[1] - env.obs_ego).abs().max().item(), (got[2] - env.obs_dist).abs().max().item())
@@ -314,8 +278,8 @@ def test_search_with_policy(policy_world):
     left_out = total = 0
     for k in range(K):
         j2, Rp, Tp, Rn, Tn, x0, x1 = (t.cpu() for t in inputs[k])
-        direct = _observe(j2.cuda().contiguous(), 2, 0, None, 1, Rp.cuda().contiguous(), Tp.cuda().contiguous(), Rn.cuda().contiguous(),
-                          Tn.cuda().contiguous(), x0.cuda().contiguous(), x1.cuda().contiguous(), 201, goal, pd, prop.ray_len, k, prop.max_depth, b)
+        g = {name: t.cuda().contiguous() for name, t in zip(("joints", "R_prev", "T_prev", "R0", "T0", "x0", "x1"), (j2, Rp, Tp, Rn, Tn, x0, x1))}
+        direct = _observe(dict(g, goal=goal), 2, 0, 1, None, 201, pd, k, b, ray_len=prop.ray_len, max_depth=prop.max_depth)
         for mine, name in zip(direct, ("obs_state", "obs_egosensing", "obs_dist", "obs_time")):
             assert torch.equal(mine, getattr(res, name)[k]), (name, k)
         t64 = ref.observe(j2, Rp, Tp, Rn, Tn, x0, x1, goal.cpu(), poly, prop.ray_len, k, prop.max_depth, torch.float64)
