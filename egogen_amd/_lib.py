@@ -232,6 +232,14 @@ SIGNATURES = {
     # num_groups, sweeps, pair_weight, margin, body_radius, goal_thresh, then the twelve outputs and the stream
     "egx_primitive_select_joint": (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 6 + [C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                              C.c_int, C.c_int] + [C.c_float] * 4 + [C.c_void_p] * 13),
+    # markers_proj, Y_gen, reproj_factor, R0, T0, num_sequences, num_candidates, group_start, group_member, pair_start, num_groups,
+    # num_pairs, pair_dist, row_bad, stream
+    "egx_pair_marker_dist": (C.c_int, [C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 3 +
+                             [C.c_int, C.c_int] + [C.c_void_p] * 3),
+    # pair_dist, row_bad, pair_start, num_pairs, then egx_primitive_select_joint's arguments with pair_skin in the place of body_radius
+    "egx_primitive_select_joint_markers": (C.c_int, [C.c_void_p] * 3 + [C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 6 +
+                                           [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int] + [C.c_float] * 4 +
+                                           [C.c_void_p] * 13),
     # joints, frames_per_row, first_frame, choice, num_candidates, R_prev, T_prev, R0, T0, x0, x1, x_ld, goal, edges, edge_off, scene_idx,
     # num_scenes, ray_len, step, max_depth, num_sequences, state, egosensing, dist, time, stream
     "egx_primitive_observe": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 6 + [C.c_int] +

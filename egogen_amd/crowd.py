@@ -9,17 +9,20 @@ import torch
 
 MAX_GROUP = 32          # EGX_MAX_GROUP of include/egogen_hip.h
 MAX_SWEEPS = 8          # EGX_MAX_SWEEPS
+PAIR_MODELS = ("cylinder", "markers")       # what a person is to the joint step: a cylinder round the pelvis, or the 67 blended markers
+PAIR_TABLE_CAP_BYTES = 1 << 30              # the marker model's distance table (pairs x N x N x 18 float32) may take this much, no more
 
 
 class PersonGroups:
     """ids [b] the group of every sequence as given; start [G+1] / member [b] the CSR form: group g holds the sequences
     member[start[g]:start[g+1]] in ascending order, the groups in order of first appearance.  Built on the host (`from_ids`, no
-    device needed); `to(device)` makes the int32 tensors `group_start` / `group_member` the kernel reads, and `member_group` [b], the
-    group of every sequence."""
+    device needed); `to(device)` makes the int32 tensors `group_start` / `group_member` the kernel reads, `member_group` [b], the
+    group of every sequence, and `pair_start` [G+1], the first unordered pair of members of every group (the cumulative sum of
+    P (P - 1) / 2: the layout of egx_crowd_metrics and of the marker model's distance table)."""
 
     def __init__(self, ids, start, member):
         self.ids, self.start, self.member = ids, start, member
-        self.device = self.group_start = self.group_member = self.member_group = None
+        self.device = self.group_start = self.group_member = self.member_group = self.pair_start = None
 
     def __len__(self):
         return len(self.start) - 1
@@ -27,6 +30,16 @@ class PersonGroups:
     @property
     def sizes(self):
         return np.diff(self.start)
+
+    @property
+    def pair_offsets(self):
+        """[G+1] int64 on the host: pair_start; its last entry is the number of unordered pairs of members"""
+        sizes = self.sizes.astype(np.int64)
+        return np.concatenate([[0], np.cumsum(sizes * (sizes - 1) // 2)])
+
+    def pair_table_bytes(self, n_candidates: int) -> int:
+        """bytes of the marker model's distance table [pairs, N, N, 18] float32"""
+        return int(self.pair_offsets[-1]) * int(n_candidates) ** 2 * 18 * 4
 
     @classmethod
     def from_ids(cls, groups, b: int) -> "PersonGroups":
@@ -62,5 +75,6 @@ class PersonGroups:
         of = np.zeros(len(self.member), np.int32)
         of[self.member] = np.repeat(np.arange(len(self), dtype=np.int32), self.sizes)
         self.member_group = torch.from_numpy(of).to(device)
+        self.pair_start = torch.from_numpy(self.pair_offsets.astype(np.int32)).to(device)
         self.device = device
         return self

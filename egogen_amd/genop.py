@@ -13,7 +13,9 @@ egx_primitive_beam_select_field).  With `obstacles=` (a `MovingObstacles`, egoge
 other people's recorded tracks: a clearance term in the cost and a veto on overlap (entries egx_primitive_select_obstacles,
 egx_primitive_beam_select_obstacles).  With `groups=` (ids, or a `PersonGroups`, egogen_amd/crowd.py) the sequences of one group of the
 greedy search see each other: after the selection the members choose again against each other's current choices (entry
-egx_primitive_select_joint, csrc/genop_joint.hip), and the hand-off continues from that joint choice.  With `policy=` (a
+egx_primitive_select_joint, csrc/genop_joint.hip; with `pair_model="markers"` the people are their 67 blended markers, not
+cylinders: entries egx_pair_marker_dist, egx_primitive_select_joint_markers, csrc/genop_joint_markers.hip), and the hand-off
+continues from that joint choice.  With `policy=` (a
 `PolicyProposal`, egogen_amd/proposal.py) the candidates of the greedy search are no longer all drawn from N(0, I): per primitive
 every sequence senses its surroundings (entry egx_primitive_observe, csrc/genop_policy.hip), the trained policy's actor proposes
 mu, logvar over the latent, and the candidate rows become mu, samples round it and a share of prior samples (entry
@@ -75,13 +77,21 @@ def _load_ckpt(candidates):
     raise FileNotFoundError(f"none of {list(candidates)} could be read: {err}")
 
 
-def _person_groups(groups, data, beam_width, pair_weight, pair_margin, body_radius, joint_sweeps):
+def _person_groups(groups, data, beam_width, pair_weight, pair_margin, body_radius, joint_sweeps, pair_model="cylinder", pair_skin=0.05,
+                   n_candidates=1):
     """The `groups=` argument of `generate_sequence_to_goal` checked on the host, before any device work -> a `PersonGroups` not yet
     on a device (None without groups).  ValueError: groups with a beam, ids of another length than the b seeds of `data`, a group
-    of more than 32, sweeps outside [1, 8], a negative margin or radius, a non-finite weight."""
+    of more than 32, sweeps outside [1, 8], a negative margin or radius, a non-finite weight; an unknown pair_model, "markers"
+    without groups, a negative or non-finite pair_skin, a distance table of the marker model above PAIR_TABLE_CAP_BYTES."""
+    from .crowd import MAX_SWEEPS, PAIR_MODELS, PAIR_TABLE_CAP_BYTES, PersonGroups
+    if pair_model not in PAIR_MODELS:
+        raise ValueError(f"pair_model must be one of {PAIR_MODELS}, got {pair_model!r}")
+    if not (float(pair_skin) >= 0 and np.isfinite(float(pair_skin))):
+        raise ValueError(f"pair_skin must be finite and not negative, got {pair_skin}")
     if groups is None:
+        if pair_model == "markers":
+            raise ValueError('pair_model="markers" is a model of the joint step: it needs groups=')
         return None
-    from .crowd import MAX_SWEEPS, PersonGroups
     if beam_width > 1:
         raise ValueError(f"groups= is the greedy search only: beam_width must be 1 with it, got {beam_width}")
     shape = tuple(np.shape(data))
@@ -98,6 +108,10 @@ def _person_groups(groups, data, beam_width, pair_weight, pair_margin, body_radi
     if not (float(pair_margin) >= 0 and float(body_radius) >= 0 and np.isfinite(float(pair_weight))):
         raise ValueError(f"pair_margin and body_radius must not be negative and pair_weight finite, got {pair_margin}, {body_radius}, "
                          f"{pair_weight}")
+    if pair_model == "markers" and groups.pair_table_bytes(n_candidates) > PAIR_TABLE_CAP_BYTES:
+        raise ValueError(f"the marker model's distance table would take {groups.pair_table_bytes(n_candidates)} bytes "
+                         f"({int(groups.pair_offsets[-1])} pairs x {int(n_candidates)}^2 rows x 72), above the cap of {PAIR_TABLE_CAP_BYTES}: "
+                         f"fewer candidates, smaller groups, or the cylinder model")
     return groups
 
 
@@ -122,6 +136,8 @@ class PrimitiveSequence:
     joint_changed [K,S,G] the members of a group that changed their choice in a sweep (0: a fixed point); crowd_clearance [K,b] the
     clearance of the chosen track against the other members' chosen tracks and crowd_hit [K,b] = crowd_clearance < 0: did the crowd
     as written overlap.  cost / colliding stay what the selection wrote; status follows the joint choice.  None without groups.
+    `search` also holds pair_model ("cylinder" / "markers") and pair_skin (metres); with "markers" the clearances are distances
+    between the two people's nearest blended markers minus pair_skin, in 3-D.
     With `policy=PolicyProposal(..., sense_people=True)`: policy_sense_people True, people_box [K,b,4] (minx, miny, maxx, maxy) the
     world xy box of every sequence's two seed frames' markers at each primitive and obs_people_count [K,b] the holes its observation
     was cast against; False, None, None with a policy that does not sense people, None without a policy."""
@@ -412,7 +428,8 @@ class GAMMAPrimitiveComboGenOP:
                                   beam_width: int = 1, geodesic=None, obstacles=None, obstacle_weight: float = 1.0,
                                   obstacle_margin: float = 0.5, body_radius: float = 0.3,
                                   obstacle_frame0: int = 0, groups=None, pair_weight: float = 1.0, pair_margin: float = 0.5,
-                                  joint_sweeps: int = 2, policy=None) -> PrimitiveSequence:
+                                  joint_sweeps: int = 2, policy=None, pair_model: str = "cylinder",
+                                  pair_skin: float = 0.05) -> PrimitiveSequence:
         """`generate_sequence` steered to a goal through a scene by a greedy best-of-N search: for each of the `n_primitives`
         primitives, `n_candidates` candidates per sequence are generated, scored and the best one is kept; every candidate of the
         next primitive continues from it.  data / bparams / betas / reproj_factor / R0 / T0 as in `generate_sequence` (b seeds,
@@ -470,6 +487,19 @@ class GAMMAPrimitiveComboGenOP:
               one is the search without groups.  The loop stays launches only.
             - pair_weight (1.0), pair_margin (0.5 m), joint_sweeps (2, in [1, 8]): stated choices like the others, informed by a
               toy on the CPU only: nobody has measured motion quality with them.
+            - pair_model: what a person is to the joint step.  "cylinder" (the default) is the model above.  "markers": a person
+              is the 67 blended markers of a candidate - the body model's markers and the prior's predicted markers blended by
+              reproj_factor, exactly what the hand-off records - in the world, in 3-D.  Two launches stand where
+              egx_primitive_select_joint stands: egx_pair_marker_dist writes, for every pair of members of a group and every pair
+              of their candidates, the least of the 67 x 67 marker distances at each predicted frame into a table allocated once
+              before the loop (pairs x N^2 x 72 bytes; ValueError above 1 GiB, crowd.PAIR_TABLE_CAP_BYTES), and
+              egx_primitive_select_joint_markers runs the same sweeps with c_t = that distance to the nearest other member's
+              current choice minus pair_skin; cost term, veto, order, traces and `crowd_clearance` / `crowd_hit` are as above with
+              that c_t.  body_radius is not read by this model (it still is by `obstacles=`, whose recorded tracks stay
+              cylinders).  Needs groups (ValueError without).  The limits that remain: 67 markers sample the surface sparsely, the
+              horizon is one primitive, the others' tracks are their current choices.
+            - pair_skin (0.05 m): markers of two people closer than this count as contact.  The evaluator's `touch_dist`
+              (egogen_amd/metrics.py) by intent: a hit in the search is a touch frame in `crowd_metrics`.  A stated choice.
             - policy: None, or a `PolicyProposal` (egogen_amd/proposal.py): the trained policy as the proposal distribution.  The
               greedy search only (ValueError with beam_width > 1).  `z` (supplied or drawn up front) becomes the eps of the
               proposal.  Before the loop one body-model forward of the b x 2 seed bodies gives the first observation its joints;
@@ -505,7 +535,7 @@ class GAMMAPrimitiveComboGenOP:
                 raise TypeError(f"policy must be None or a PolicyProposal, got {type(policy).__name__}")
             check_beam(W)
             policy.counts(N)
-        people = _person_groups(groups, data, W, pair_weight, pair_margin, body_radius, joint_sweeps)
+        people = _person_groups(groups, data, W, pair_weight, pair_margin, body_radius, joint_sweeps, pair_model, pair_skin, N)
         X, seed, bt = self._seed_inputs(data, bparams, betas, -1, None)
         b, dev, f32, i32 = X.shape[1], self.device, torch.float32, torch.int32
         goal = self._dev(goal, "goal")
@@ -580,7 +610,12 @@ class GAMMAPrimitiveComboGenOP:
                       "individual_choice": rec(dtype=i32), "pair_term": trace(b, N), "pair_clearance": trace(b, N),
                       "joint_cost": trace(b, N), "pair_hit": trace(b, N, dtype=i32), "choice_trace": trace(b, dtype=i32),
                       "joint_changed": trace(G, dtype=i32), "crowd_clearance": rec(), "crowd_hit": rec(dtype=i32),
-                      "groups": torch.as_tensor(people.ids)})
+                      "groups": torch.as_tensor(people.ids), "pair_model": pair_model, "pair_skin": float(pair_skin)})
+            if pair_model == "markers":      # the distance table and the bad-frame masks, allocated once: the loop stays launches only
+                npairs = int(people.pair_offsets[-1])
+                s.update({"pair_dist": torch.empty(npairs, N, N, T_PRED, device=dev, dtype=f32) if npairs else None,
+                          "row_bad": torch.zeros(b * N, device=dev, dtype=i32),
+                          "joint": (*s["joint"][:6], float(pair_skin), float(goal_thresh)), "npairs": npairs})
         if scene is not None:
             s["lbs_out"]["pene_count"] = torch.empty(b * M * T_ALL, device=dev, dtype=i32)
         s["policy"] = policy
@@ -621,15 +656,15 @@ class GAMMAPrimitiveComboGenOP:
         if obs_args is not None:
             search.update({k: s[k] for k in PrimitiveSequence.OBSTACLE_FIELDS})
         if people is not None:
-            search.update({k: s[k] for k in PrimitiveSequence.JOINT_FIELDS})
+            search.update({k: s[k] for k in PrimitiveSequence.JOINT_FIELDS + ("pair_model", "pair_skin")})
         if policy is not None:
             search.update(policy.record(s))
         return self._result(s, zc, bt, R0_end[::M].reshape(b, 3, 3).contiguous(), T0_end[::M].contiguous(), to_numpy, search)
 
     def _search_loop(self, K, b, N, s):
         """The primitive loop of `generate_sequence_to_goal`: launches only, no allocation that depends on k, no host wait.  With
-        groups (s["joint"]) the joint launch stands between the selection and the hand-off; a device copy keeps what the selection
-        chose."""
+        groups (s["joint"]) the joint launch stands between the selection and the hand-off - with the marker model (s["row_bad"])
+        the two launches of csrc/genop_joint_markers.hip in its place; a device copy keeps what the selection chose."""
         lib, st, hand, pp = _lib.load(), _lib.current_stream_ptr(), self._handoff_lead(s), _lib.ptr(s["pp"])
         sel = self._select_lead(s, [s["R0"]] * 2, [s["T0"]] * 2)
         name, field, obs = self._select_tail(s, K, "egx_primitive_select")
@@ -637,6 +672,14 @@ class GAMMAPrimitiveComboGenOP:
         joint, policy = s.get("joint"), s.get("policy")
         if joint is not None:
             joint_in = (_lib.ptr(s["lbs_out"]["joints"]), 127, _lib.ptr(s["R0"]), _lib.ptr(s["T0"]), _lib.ptr(s["goal"]))
+            joint_name, dist_args = "egx_primitive_select_joint", None
+            if s.get("row_bad") is not None:            # the marker model: the table's launch, then the sweeps on it
+                joint_name, crowd, npairs = "egx_primitive_select_joint_markers", s["joint_alive"], s["npairs"]
+                table, bad, pair_start = _lib.ptr(s["pair_dist"]), _lib.ptr(s["row_bad"]), _lib.ptr(crowd.pair_start)
+                joint_in = (table, bad, pair_start, npairs, *joint_in)
+                dist_args = (_lib.ptr(s["lbs_out"]["markers"]), _lib.ptr(s["Y_gen"]), s["rf"], _lib.ptr(s["R0"]), _lib.ptr(s["T0"]), b, N,
+                             _lib.ptr(crowd.group_start), _lib.ptr(crowd.group_member), pair_start, len(crowd), npairs, table, bad, st)
+            joint_entry = getattr(lib, joint_name)
         sensed = [()] * K
         if policy is not None and policy.sense_people:      # what the policy senses of the others: the groups' CSR and the obstacles
             from .proposal import NO_GROUPS, NO_OBSTACLES
@@ -654,11 +697,13 @@ class GAMMAPrimitiveComboGenOP:
                 _vp(s["goal_dist"][k]), _vp(s["cost"][k]), _vp(s["cost_terms"][k]), _vp(s["colliding"][k]), *field, *obs[k], st), name)
             if joint is not None:
                 s["individual_choice"][k].copy_(s["choice"][k])
-                _lib.check(lib.egx_primitive_select_joint(
+                if dist_args is not None:
+                    _lib.check(lib.egx_pair_marker_dist(*dist_args), "egx_pair_marker_dist")
+                _lib.check(joint_entry(
                     *joint_in, _vp(s["cost"][k]), _vp(s["cost_terms"][k]), _vp(s["colliding"][k]), b, N, *joint,
                     _vp(s["choice"][k]), _vp(s["status"][k]), _vp(s["reached"][k]), _vp(s["goal_dist"][k]), _vp(s["pair_term"][k]),
                     _vp(s["pair_clearance"][k]), _vp(s["joint_cost"][k]), _vp(s["pair_hit"][k]), _vp(s["choice_trace"][k]),
-                    _vp(s["joint_changed"][k]), _vp(s["crowd_clearance"][k]), _vp(s["crowd_hit"][k]), st), "egx_primitive_select_joint")
+                    _vp(s["joint_changed"][k]), _vp(s["crowd_clearance"][k]), _vp(s["crowd_hit"][k]), st), joint_name)
             _lib.check(lib.egx_primitive_advance_select(
                 pp, *hand[k % 2], b, _vp(s["choice"][k]), N, _lib.ptr(s["R0"]), _lib.ptr(s["T0"]), _vp(s["markers"][k]),
                 _vp(s["pelvis"][k]), _vp(s["rotmat"][k]), _vp(s["transl"][k]), _vp(s["params"][k]), _lib.ptr(s["seed"]), _vp(nxt[0]),

@@ -11,7 +11,7 @@ include/egogen_hip.h.  Like the rest of the product path there is no CPU fallbac
 
 What the figures are NOT: a perceptual score.  They are the reward's own skate and floor arguments carried across hand-offs,
 smoothness of the pelvis track, goal attainment, scene penetration counts of the body model's vertices, and between people the
-search's cylinder clearance next to a marker-to-marker distance the search never sees.  The contact score's constants (a 5 cm band,
+search's cylinder clearance next to a marker-to-marker distance (which the search sees only with `pair_model="markers"`).  The contact score's constants (a 5 cm band,
 0.075 m/s) are GAMMA's, and `touch_dist` (5 cm between two people's markers) is a stated choice."""
 from __future__ import annotations
 

@@ -22,7 +22,10 @@ sequences) who choose each primitive against each other's current choices, so no
 `motion_<seed>_<variant>_p<person>.pkl` per person, and per variant the minimum crowd clearance, the number of overlapping
 primitives along the written paths and whether the members still changed their minds in a last sweep.  It stands in for
 `--start` and `--goal` and is the greedy search (`--beam-width 1`); `--scene`, `--walkable` (one field per distinct goal) and
-`--avoid` keep working with it.  `--policy CKPT` (with `--goal` or `--people`; the greedy search) makes a trained policy the proposal
+`--avoid` keep working with it.  `--pair-model markers` (with `--people`; default `cylinder`) makes a person, to the others of the group,
+the 67 blended markers of a candidate instead of a cylinder round the pelvis (`generate_sequence_to_goal(pair_model="markers")`):
+limbs avoid limbs; `--pair-skin M` (default 0.05 m) is the marker distance below which two people count as touching, and the printed
+crowd clearance is then the least marker distance minus that skin.  `--policy CKPT` (with `--goal` or `--people`; the greedy search) makes a trained policy the proposal
 distribution of the search (`PolicyProposal`, egogen_amd/proposal.py): the checkpoint main_ppo.py writes (key `model`) is loaded into
 `setup_world.build_policy`'s networks, and per primitive every sequence's observation, with its 32 egosensing rays cast against the
 walkable polygon `--polygon FILE` (default: the file given to `--walkable` or `--scene` where that file holds `edges`; else no
@@ -77,6 +80,10 @@ def main(argv=None):
     parser.add_argument("--start", default=None, help="x,y,yaw_deg: where the seed stands in the world and which way it faces")
     parser.add_argument("--people", default=None, help='"x,y,yaw_deg:gx,gy,gz;...": P people with a start and a goal each, generated together; '
                         "every variant is one group who avoid each other (instead of --start / --goal; greedy search)")
+    parser.add_argument("--pair-model", choices=("cylinder", "markers"), default="cylinder", help="what a person is to the others of a "
+                        "--people group: a cylinder round the pelvis, or the 67 blended markers of a candidate (with --people)")
+    parser.add_argument("--pair-skin", type=float, default=None, help="marker distance in metres below which two people touch "
+                        "(with --pair-model markers; default 0.05)")
     parser.add_argument("--policy", default=None, help="checkpoint of a trained policy (main_ppo.py, key 'model'): the proposal distribution "
                         "of the search (with --goal or --people; greedy search)")
     parser.add_argument("--policy-temperature", type=float, default=1.0, help="scale of the policy's sigma (with --policy)")
@@ -98,6 +105,10 @@ def main(argv=None):
                 any(len(one.split(":")) != 2 or len(one.split(":")[0].split(",")) != 3 for one in args.people.split(";") if one):
             parser.error('--people takes "x,y,yaw_deg:gx,gy,gz" for 1 to 32 people, separated by ";"')
         args.goal = ",".join(str(v) for v in people[0, 3:])          # the goal-steered path; the goals themselves follow below
+    if args.people is None and args.pair_model != "cylinder":
+        parser.error("--pair-model markers needs --people: it is a model of how the people of a group see each other")
+    if args.pair_skin is not None and (args.pair_model != "markers" or not (args.pair_skin >= 0 and np.isfinite(args.pair_skin))):
+        parser.error("--pair-skin needs --pair-model markers and must be finite and not negative")
     if args.goal is None and args.scene is not None:
         parser.error("--scene needs --goal")
     if args.goal is None and args.walkable is not None:
@@ -235,7 +246,8 @@ def main(argv=None):
                 "; it senses the other people as holes of the polygon" if args.policy_sees_people else ""))
         res = op.generate_sequence_to_goal(data.repeat(nseq, 1), bparams.repeat(nseq, 1), can["betas"].astype(np.float32),
                                            goal, args.n_primitives, args.n_candidates, scene=scene, R0=R0, T0=T0,
-                                           beam_width=args.beam_width, geodesic=field, obstacles=obstacles, groups=groups, policy=proposal)
+                                           beam_width=args.beam_width, geodesic=field, obstacles=obstacles, groups=groups, policy=proposal,
+                                           pair_model=args.pair_model, pair_skin=0.05 if args.pair_skin is None else args.pair_skin)
         for v in range(args.n_gens if people is not None else 0):
             mine = range(v * P, (v + 1) * P)
             written = np.stack([np.arange(args.n_primitives) < int(res.n_valid[i]) for i in mine], 1)          # [K,P]: the primitives the files hold

@@ -1038,7 +1038,59 @@ int egx_primitive_select_joint(const float* joints, int joints_per_body, const f
                                float* joint_cost, int32_t* pair_hit, int32_t* choice_trace, int32_t* changed,
                                float* crowd_clearance, int32_t* crowd_hit, void* stream);
 
-/* egx_primitive_observe - the observation of every sequence of the search as the env would have it after the chosen primitive
+/* The marker-level pair model of the joint step (csrc/genop_joint_markers.hip): a person is the 67 blended markers of a candidate
+ * row in the world, not a cylinder.  Two launches stand where egx_primitive_select_joint stands: egx_pair_marker_dist writes every
+ * distance a sweep can ask for, egx_primitive_select_joint_markers runs the sweeps on that table.  Rows, groups and clamping as
+ * egx_primitive_select_joint; rows = num_sequences * num_candidates (N), row r = m * N + n; everything over the predicted frames
+ * t = 2..19.
+ *   blended local marker a of row r at frame t, coordinate d (blend_marker of csrc/genop.hip, the same nesting: what the hand-off
+ *           records):   m_d = rf * markers_proj[(r*20 + t)*201 + 3a + d] + (1 - rf) * Y_gen[((t-2)*rows + r)*201 + 3a + d]
+ *   world marker        w_c = fma(R0[3c+2], m_2, fma(R0[3c+1], m_1, R0[3c] * m_0)) + T0[c], c = 0, 1, 2, R0 / T0 of row r
+ *                       (the nesting of the pelvis of egx_primitive_select_joint, extended to z)
+ *   bad row-frame       any of the 67 x 3 world coordinates of (r, t) is not finite
+ *   pair distance       for rows r, r' of two different members of one group: D(r, r', t) = sqrt(min over the 67 x 67 marker pairs of
+ *                       (dx^2 + dy^2) + dz^2): three rounded differences, three rounded squares, the two rounded sums in that
+ *                       order, no contraction (the same bits with r and r' exchanged); the minimum is order-free; the correctly
+ *                       rounded root once, of the least square.  +inf where either row-frame is bad.
+ *   frame clearance     of row (i, n) against the others' current choices: c_t = (min over the members j != i of
+ *                       D((i, n), (j, choice_j), t)) - pair_skin, one rounded difference; +inf for a group of one or where every
+ *                       other member is bad at t; NaN where the row's own frame is bad (a group of one included).
+ * Everything after c_t is egx_primitive_select_joint's arithmetic and order: pair_clearance, pair_term (the same wave tree),
+ * pair_hit, joint_cost, the classes, the choice by the selection's order, all sweeps always, members in order; choice, status,
+ * goal_dist and reached rewritten as there; the same traces; crowd_clearance / crowd_hit the chosen rows against the chosen rows.
+ * pair_skin: markers sample the surface sparsely, so contact is declared at a marker distance below pair_skin.  body_radius is not
+ * read in this model.
+ *
+ * egx_pair_marker_dist - pair_start [num_groups+1] (device) is the cumulative sum of P (P - 1) / 2 over the groups (the layout of
+ * egx_crowd_metrics: pair q = pair_start[g] + local index of (a, b), a < b, lexicographic, a and b positions in the group),
+ * num_pairs = pair_start[num_groups].  pair_dist [num_pairs,N,N,18]: entry (q, n_a, n_b, t - 2) = D(row n_a of member a, row n_b of
+ * member b, t); NULL exactly where num_pairs == 0.  row_bad [rows] int32: bit t - 2 set where row-frame (r, t) is bad, written
+ * for every row of the launch.  One workgroup per (pair, n_a, tile of 8 n_b): the first row's world markers stay in LDS, the
+ * second member's rows stream through; a wave takes a frame, the 67 x 67 squared distances spread over its lanes; each unordered
+ * pair is computed once.  A further workgroup per sequence writes row_bad.  A pair whose index pair_start does not place inside its
+ * group is not written.  EGX_ERR_ARG for a NULL input or row_bad, num_candidates outside [1, EGX_MAX_CANDIDATES], num_groups < 1,
+ * reproj_factor outside [0, 1] (NaN included), num_pairs < 0, pair_dist NULL with num_pairs > 0 or not NULL with num_pairs == 0. */
+int egx_pair_marker_dist(const float* markers_proj, const float* Y_gen, float reproj_factor, const float* R0, const float* T0,
+                         int num_sequences, int num_candidates, const int32_t* group_start, const int32_t* group_member,
+                         const int32_t* pair_start, int num_groups, int num_pairs, float* pair_dist, int32_t* row_bad, void* stream);
+
+/* egx_primitive_select_joint_markers - the sweeps on the table: pair_dist / row_bad / pair_start / num_pairs as
+ * egx_pair_marker_dist wrote and took them, every other argument and output as egx_primitive_select_joint (pair_skin in the place of
+ * body_radius).  One workgroup of 512 threads per group, a wave per row with lanes 0..17 one frame each; a table index past
+ * num_pairs is not read (that member is not there).  No float atomics, no waiting, nothing between workgroups: a group's outputs
+ * are the same bits in any batch.  EGX_ERR_ARG for a NULL input or output, num_candidates outside [1, EGX_MAX_CANDIDATES], sweeps
+ * outside [1, EGX_MAX_SWEEPS], num_groups < 1, a negative or NaN margin or pair_skin, a non-finite pair_weight, num_pairs < 0,
+ * pair_dist NULL with num_pairs > 0 or not NULL with num_pairs == 0. */
+int egx_primitive_select_joint_markers(const float* pair_dist, const int32_t* row_bad, const int32_t* pair_start, int num_pairs,
+                                       const float* joints, int joints_per_body, const float* R0, const float* T0, const float* goal,
+                                       const float* cost, const float* cost_terms, const int32_t* colliding, int num_sequences,
+                                       int num_candidates, const int32_t* group_start, const int32_t* group_member, int num_groups,
+                                       int sweeps, float pair_weight, float margin, float pair_skin, float goal_thresh,
+                                       int32_t* choice, int32_t* status, int32_t* reached, float* goal_dist, float* pair_term,
+                                       float* pair_clearance, float* joint_cost, int32_t* pair_hit, int32_t* choice_trace,
+                                       int32_t* changed, float* crowd_clearance, int32_t* crowd_hit, void* stream);
+
+/* egx_primitive_observe -the observation of every sequence of the search as the env would have it after the chosen primitive
  * (crowd_ppo/crowd_env_2f.py:311-312 what step() returns; _calc_egosensing :524-613; _get_feature :680-727): the values
  * egx_env_step_post writes to state, obs_ego, obs_dist and obs_time, through the same device functions (csrc/egx_egosense.h,
  * egx_reward.h, egx_frame.h), from what a hand-off entry left on the device.  One launch ahead of egx_policy_forward.

@@ -5,6 +5,7 @@ and that the entries that existed before did not move.  GPU only.
     python scripts/bench_genop_joint.py [--iters 20] [--out-dir profiles]
     python scripts/bench_genop_joint.py --lib <parent .so> --dump outputs.pt        (once, on the parent build)
     python scripts/bench_genop_joint.py --compare outputs.pt [--out-dir profiles]   (once, on this build)
+    python scripts/bench_genop_joint.py --markers [--iters 20] [--out-dir profiles]  (the marker-level pair model)
 
 Timing, in one process: G groups of P people swap places on a circle of 2 m, N candidates each, S = 2 sweeps, at the driver's shape
 (4 variants of 4 people, N = 16) and at 8 groups x 8 people x N = 32.  Device events around --iters passes of the whole primitive
@@ -16,7 +17,13 @@ that: all sweeps always run over all rows.
 Bit identity: `--dump` writes every output of the selection entries that existed before (scripts/bench_genop_obstacles.py's
 inputs for egx_primitive_select, _select_field, _beam_select, _beam_select_field, and the obstacle entries on two of the obstacle
 tests' constructed cases); `--compare` recomputes them and compares bit for bit.
-Writes the sections between the `timings` and the `identity` markers of `<out-dir>/genop_joint.md`."""
+Writes the sections between the `timings` and the `identity` markers of `<out-dir>/genop_joint.md`.
+
+`--markers`: the marker-level pair model (`pair_model="markers"`, csrc/genop_joint_markers.hip) on the same people, at the two shapes
+above and at one group of 32 people x N = 16: the primitive loop with the cylinder model and with the marker model, and single
+launches of the cylinder joint step, of egx_pair_marker_dist and of egx_primitive_select_joint_markers on the same rows; for the
+distance launch also distance evaluations per second (pairs x N^2 x 18 frames x 67 x 67 over the launch time) and what share of
+the fp32 vector peak its arithmetic is.  Writes the `cost` section of `<out-dir>/genop_joint_markers.md`."""
 import argparse
 import ctypes as C
 import os
@@ -31,9 +38,13 @@ sys.path.insert(0, os.path.join(ROOT, "scripts"))
 
 from egogen_amd import _lib  # noqa: E402
 
-MARKS = {"timings": ("<!-- timings:begin -->", "<!-- timings:end -->"), "identity": ("<!-- identity:begin -->", "<!-- identity:end -->")}
-NEW = ("egx_primitive_select_joint",)
+MARKS = {"timings": ("<!-- timings:begin -->", "<!-- timings:end -->"), "identity": ("<!-- identity:begin -->", "<!-- identity:end -->"),
+         "cost": ("<!-- cost:begin -->", "<!-- cost:end -->")}
+NEW = ("egx_primitive_select_joint", "egx_pair_marker_dist", "egx_primitive_select_joint_markers")
 SHAPES = ((4, 4, 16), (8, 8, 32))       # G, P, N
+MARKER_SHAPES = SHAPES + ((1, 32, 16),)
+PEAK_FP32_VECTOR = 157.3e12             # FLOP/s, an FMA counted as two: 78.65e12 vector operations a second
+OPS_PER_DISTANCE = 9                    # three differences, three squares, two sums, one minimum: none of them fuses
 K, S = 4, 2
 
 
@@ -46,11 +57,11 @@ def use_library(path):
             _lib.SIGNATURES.pop(name, None)
 
 
-def write_section(out_dir, which, lines):
+def write_section(out_dir, which, lines, name="genop_joint.md", title="# The joint primitive search\n"):
     begin, end = MARKS[which]
-    md = os.path.join(out_dir, "genop_joint.md")
+    md = os.path.join(out_dir, name)
     os.makedirs(out_dir, exist_ok=True)
-    txt = open(md).read() if os.path.exists(md) else "# The joint primitive search\n"
+    txt = open(md).read() if os.path.exists(md) else title
     body = "\n".join([begin] + lines + [end])
     if begin in txt and end in txt:
         txt = txt[:txt.index(begin)] + body + txt[txt.index(end) + len(end):]
@@ -83,9 +94,84 @@ def same_bits(a, b):
 
 
 # ---- timing ---------------------------------------------------------------------------------------------------------------------
+def swap_people(body, G, P, N, g):
+    """G groups of P people who swap places on a circle of 2 m -> (data, xb, betas, goal, the keywords z / T0 / R0, groups)"""
+    from bench_genop_search import seeds
+    b = G * P
+    data, xb, betas = seeds(body, b, g)
+    z = torch.randn(K, b * N, 128, generator=g).cuda()
+    ang = 2 * np.pi * (np.arange(b) % P) / P
+    T0 = torch.tensor(np.stack([2.0 * np.cos(ang), 2.0 * np.sin(ang), np.zeros(b)], -1), dtype=torch.float32)
+    yaw = ang + np.pi / 2                                         # the seed walks along +y: turned to face the centre
+    R0 = torch.tensor(np.stack([np.stack([np.cos(yaw), -np.sin(yaw), 0 * yaw], -1), np.stack([np.sin(yaw), np.cos(yaw), 0 * yaw], -1),
+                                np.stack([0 * yaw, 0 * yaw, 1 + 0 * yaw], -1)], 1), dtype=torch.float32)
+    return data, xb, betas, -T0 + torch.tensor([0.0, 0.0, 0.9]), dict(z=z, T0=T0, R0=R0, to_numpy=False), np.arange(b) // P
+
+
+def marker_timings(args):
+    """the `cost` section of genop_joint_markers.md"""
+    from bench_genop import alternate
+    from bench_genop_search import build_op, captured
+    lib = _lib.load()
+    op, body = build_op(args.num_verts)
+    g = torch.Generator().manual_seed(1)
+    vp = lambda t: C.c_void_p(t.data_ptr())
+    fmt = lambda v: f"{v['median_us']:.1f} ({v['min_us']:.1f} .. {v['max_us']:.1f})"
+    lines = [f"Device: {torch.cuda.get_device_name(0)}; K = {K} primitives, body of {args.num_verts} vertices, no scene, S = {S} sweeps; one "
+             f"process, {args.iters} loop passes or {10 * args.iters} launches per window, three windows per leg after {args.warmup} warm-up "
+             "passes, the legs taking turns; device events.  Microseconds: median (range of the windows); loops per primitive.", "",
+             "| shape | leg | us |", "|---|---|---|"]
+    notes = []
+    for G, P, N in MARKER_SHAPES:
+        b = G * P
+        data, xb, betas, goal, kw, groups = swap_people(body, G, P, N, g)
+        run = lambda **more: op.generate_sequence_to_goal(data, xb, betas, goal, K, N, groups=groups, joint_sweeps=S, **kw, **more)
+        res = {}
+        cyl, sc = captured(op, "_search_loop", lambda: res.update(c=run()))
+        mk, sm = captured(op, "_search_loop", lambda: res.update(m=run(pair_model="markers")))
+        st, k = _lib.current_stream_ptr(), K - 1
+        legs = {}
+        for name, s in (("cylinder", sc[3]), ("markers", sm[3])):
+            lbs, crowd = s["lbs_out"], s["joint_alive"]
+            tail = (vp(s["cost"][k]), vp(s["cost_terms"][k]), vp(s["colliding"][k]), b, N, *s["joint"], vp(s["choice"][k]), vp(s["status"][k]),
+                    vp(s["reached"][k]), vp(s["goal_dist"][k]), vp(s["pair_term"][k]), vp(s["pair_clearance"][k]), vp(s["joint_cost"][k]),
+                    vp(s["pair_hit"][k]), vp(s["choice_trace"][k]), vp(s["joint_changed"][k]), vp(s["crowd_clearance"][k]), vp(s["crowd_hit"][k]), st)
+            lead = (_lib.ptr(lbs["joints"]), 127, _lib.ptr(s["R0"]), _lib.ptr(s["T0"]), _lib.ptr(s["goal"]))
+            if name == "cylinder":
+                legs["cylinder joint launch"] = lambda a=(*lead, *tail): _lib.check(lib.egx_primitive_select_joint(*a), "egx_primitive_select_joint")
+                continue
+            table = (_lib.ptr(s["pair_dist"]), _lib.ptr(s["row_bad"]), _lib.ptr(crowd.pair_start), s["npairs"])
+            dist = (_lib.ptr(lbs["markers"]), _lib.ptr(s["Y_gen"]), s["rf"], _lib.ptr(s["R0"]), _lib.ptr(s["T0"]), b, N, _lib.ptr(crowd.group_start),
+                    _lib.ptr(crowd.group_member), table[2], len(crowd), s["npairs"], table[0], table[1], st)
+            legs["distance launch"] = lambda a=dist: _lib.check(lib.egx_pair_marker_dist(*a), "egx_pair_marker_dist")
+            legs["sweep launch"] = lambda a=(*table, *lead, *tail): _lib.check(lib.egx_primitive_select_joint_markers(*a),
+                                                                              "egx_primitive_select_joint_markers")
+            npairs = s["npairs"]
+        t = alternate({"loop, cylinder model": cyl, "loop, marker model": mk}, args.iters, args.warmup)
+        for v in t.values():
+            for q in ("median_us", "min_us", "max_us"):
+                v[q] /= K
+        t.update(alternate(legs, 10 * args.iters, args.warmup))
+        for name, v in t.items():
+            lines.append(f"| G={G} P={P} N={N} (b={b}) | {name} | {fmt(v)} |")
+        evals = npairs * N * N * 18 * 67 * 67
+        rate = evals / (t["distance launch"]["median_us"] * 1e-6)
+        rc, rm = res["c"], res["m"]
+        notes.append(f"G={G} P={P} N={N}: {npairs} pairs, a table of {npairs * N * N * 72 / 1e6:.2f} MB, {evals / 1e9:.3f} G distance evaluations per "
+                     f"launch: {rate / 1e12:.2f} T evaluations/s, {OPS_PER_DISTANCE} vector operations each = "
+                     f"{100 * rate * OPS_PER_DISTANCE / (PEAK_FP32_VECTOR / 2):.1f} % of the fp32 vector peak ({PEAK_FP32_VECTOR / 2e12:.2f} T "
+                     f"operations/s, an FMA being one; the bound is arithmetic, the launch reads {npairs * N * (N + -(-N // 8)) * 18 * 201 * 8 / 1e6:.1f} "
+                     f"MB).  Crowd hits per primitive, cylinder / marker model (each in its own measure): {rc.crowd_hit.sum(1).tolist()} / "
+                     f"{rm.crowd_hit.sum(1).tolist()}; members still changing in the last sweep: {rc.joint_changed[:, -1].sum(1).tolist()} / "
+                     f"{rm.joint_changed[:, -1].sum(1).tolist()}.")
+    lines += [""] + notes
+    write_section(args.out_dir, "cost", lines, "genop_joint_markers.md", "# The marker-level pair model of the joint search\n")
+    print("\n".join(lines))
+
+
 def timings(args):
     from bench_genop import alternate
-    from bench_genop_search import build_op, captured, seeds
+    from bench_genop_search import build_op, captured
     lib = _lib.load()
     op, body = build_op(args.num_verts)
     g = torch.Generator().manual_seed(1)
@@ -98,16 +184,7 @@ def timings(args):
     notes = []
     for G, P, N in SHAPES:
         b = G * P
-        data, xb, betas = seeds(body, b, g)
-        z = torch.randn(K, b * N, 128, generator=g).cuda()
-        ang = 2 * np.pi * (np.arange(b) % P) / P                      # the P people of a group swap places on a circle of 2 m
-        T0 = torch.tensor(np.stack([2.0 * np.cos(ang), 2.0 * np.sin(ang), np.zeros(b)], -1), dtype=torch.float32)
-        yaw = ang + np.pi / 2                                         # the seed walks along +y: turned to face the centre
-        R0 = torch.tensor(np.stack([np.stack([np.cos(yaw), -np.sin(yaw), 0 * yaw], -1), np.stack([np.sin(yaw), np.cos(yaw), 0 * yaw], -1),
-                                    np.stack([0 * yaw, 0 * yaw, 1 + 0 * yaw], -1)], 1), dtype=torch.float32)
-        goal = -T0 + torch.tensor([0.0, 0.0, 0.9])
-        kw = dict(z=z, T0=T0, R0=R0, to_numpy=False)
-        groups = np.arange(b) // P
+        data, xb, betas, goal, kw, groups = swap_people(body, G, P, N, g)
         plain, _ = captured(op, "_search_loop", lambda: op.generate_sequence_to_goal(data, xb, betas, goal, K, N, **kw))
         res = {}
         joint, sf = captured(op, "_search_loop",
@@ -145,6 +222,7 @@ def main():
     ap.add_argument("--lib", default=None, help="run on this build of libegogen_hip.so instead of the package's")
     ap.add_argument("--dump", default=None)
     ap.add_argument("--compare", default=None)
+    ap.add_argument("--markers", action="store_true", help="the marker-level pair model: the cost section of genop_joint_markers.md")
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--num-verts", type=int, default=None)
@@ -168,6 +246,8 @@ def main():
         write_section(args.out_dir, "identity", lines)
         print(lines[0])
         sys.exit(1 if differ else 0)
+    elif args.markers:
+        marker_timings(args)
     else:
         timings(args)
 

@@ -4,11 +4,16 @@ who swap places in the README's `gen_motion.py --people` example, on the synthet
 without `groups=`, 8 variants of 10 primitives each.  GPU only.
 
     python scripts/sweep_search_quality.py [--out-dir profiles] [--num-verts V]
+    python scripts/sweep_search_quality.py --pair-models [--out-dir profiles]       (cylinder against marker pair model)
 
 The motion prior is `setup_world.build_motion_prior`'s seeded random initialisation and the body the seeded synthetic one (licensed
 assets are not used here even where present, so the table can be reproduced anywhere).  The table therefore measures what the
 SEARCH does to such motions - is the goal reached, are overlaps avoided, what does it cost in skating - and says nothing about the
-motion quality of a trained model.  Writes `<out-dir>/motion_quality.md`."""
+motion quality of a trained model.  Writes `<out-dir>/motion_quality.md`.
+
+`--pair-models`: the same four people, with `groups=`, at n_candidates 4 and 16, the joint step's cylinder model against its marker
+model (`pair_model="markers"`, pair_skin 0.05 = the evaluator's touch_dist).  Writes the section between the `effect` markers of
+`<out-dir>/genop_joint_markers.md` and leaves motion_quality.md alone."""
 import argparse
 import os
 import sys
@@ -72,28 +77,80 @@ def setup(num_verts, seed):
     return op, data.repeat(nseq, 1), bparams.repeat(nseq, 1), can["betas"].astype(np.float32), goal, R0, T0, np.arange(nseq) // P
 
 
+def measure(op, data, bparams, betas, goal, R0, T0, variant, N, seed, **search):
+    """one arm: the search with `search`'s keywords at N candidates, then the evaluator -> the figures of a table row"""
+    torch.manual_seed(seed)
+    res = op.generate_sequence_to_goal(data, bparams, betas, goal, K, N, R0=R0, T0=T0, **search)
+    ms = metrics.MotionSet.from_sequences(res)
+    per = metrics.motion_metrics(ms, goal_thresh=0.1)
+    crowd = metrics.crowd_metrics(ms, groups=variant, hold=True)
+    row = {"N": N, "reached": float((per["first_reached_frame"] >= 0).mean())}
+    row.update({k: float(np.mean(per[k])) for k in PER_MOTION})
+    row.update(clearance_min=float(crowd["group"]["clearance_min"].min()), marker_dist_min=float(crowd["group"]["marker_dist_min"].min()),
+               overlap=int(crowd["group"]["overlap_frames"].sum()), touch=int(crowd["group"]["touch_frames"].sum()),
+               compared=int(crowd["group"]["frames_compared"].sum()))
+    if search.get("groups") is not None:
+        row.update(search_hits=int(np.asarray(res.crowd_hit).sum()), still_changing=int(np.asarray(res.joint_changed)[:, -1].sum()))
+    return row
+
+
+EFFECT_MARKS = ("<!-- effect:begin -->", "<!-- effect:end -->")
+EFFECT_COLS = ("N", "pair_model", "touch", "marker_dist_min", "overlap", "clearance_min", "goal_dist_end", "reached", "skate_mean", "search_hits",
+               "still_changing", "compared")
+EFFECT_HEAD = ("n_candidates", "pair_model", "touch (frames)", "marker_dist_min (m)", "overlap (frames)", "clearance_min (m)", "goal_dist_end (m)",
+               "reached", "skate_mean (m/s)", "crowd hits in the search (member-primitives)", "members changing in a last sweep", "frames compared")
+
+
+def pair_models(args):
+    """the `effect` section of genop_joint_markers.md"""
+    world = setup(args.num_verts, args.seed)
+    variant = world[-1]
+    rows = []
+    for N in (4, 16):
+        for model in ("cylinder", "markers"):
+            row = measure(*world, N, args.seed, groups=variant, pair_model=model)
+            row["pair_model"] = model
+            rows.append(row)
+            print(row)
+    fmt = lambda v: v if isinstance(v, str) else (str(v) if isinstance(v, int) else f"{v:.4g}")
+    lines = [EFFECT_MARKS[0],
+             f"The four-people swap of motion_quality.md ({VARIANTS} variants, {K} primitives, default weights and margins, `groups=`), the joint step with "
+             "its cylinder model against its marker model (pair_skin 0.05 m); the evaluator's figures as there (`crowd_metrics` with body_radius 0.3, "
+             "touch_dist 0.05, hold on), per-motion columns means over the files of an arm.  **This is a random-init prior, so the table shows the "
+             "mechanism and not motion quality.**  Written by scripts/sweep_search_quality.py --pair-models.", "",
+             "| " + " | ".join(EFFECT_HEAD) + " |", "|" + "---|" * len(EFFECT_HEAD)]
+    lines += ["| " + " | ".join(fmt(r[k]) for k in EFFECT_COLS) + " |" for r in rows]
+    lines += ["", f"Device: {torch.cuda.get_device_name(0)}; synthetic body of {args.num_verts} vertices, seed {args.seed}.", EFFECT_MARKS[1]]
+    md = os.path.join(args.out_dir, "genop_joint_markers.md")
+    os.makedirs(args.out_dir, exist_ok=True)
+    txt = open(md).read() if os.path.exists(md) else "# The marker-level pair model of the joint search\n"
+    body = "\n".join(lines)
+    if EFFECT_MARKS[0] in txt and EFFECT_MARKS[1] in txt:
+        txt = txt[:txt.index(EFFECT_MARKS[0])] + body + txt[txt.index(EFFECT_MARKS[1]) + len(EFFECT_MARKS[1]):]
+    else:
+        txt += "\n" + body + "\n"
+    with open(md, "w") as fh:
+        fh.write(txt)
+    print(body)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out-dir", default=os.path.join(ROOT, "profiles"))
     ap.add_argument("--num-verts", type=int, default=synth.NUM_VERTS)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--pair-models", action="store_true", help="cylinder against marker pair model: the effect section of genop_joint_markers.md")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("sweep_search_quality.py runs the search on the GPU; no device is visible")
+    if args.pair_models:
+        return pair_models(args)
     op, data, bparams, betas, goal, R0, T0, variant = setup(args.num_verts, args.seed)
     rows = []
     for N in CANDIDATES:
         for joint in (False, True):
-            torch.manual_seed(args.seed)
-            res = op.generate_sequence_to_goal(data, bparams, betas, goal, K, N, R0=R0, T0=T0, groups=variant if joint else None)
-            ms = metrics.MotionSet.from_sequences(res)
-            per = metrics.motion_metrics(ms, goal_thresh=0.1)
-            crowd = metrics.crowd_metrics(ms, groups=variant, hold=True)
-            row = {"N": N, "groups": "yes" if joint else "no", "reached": float((per["first_reached_frame"] >= 0).mean())}
-            row.update({k: float(np.mean(per[k])) for k in PER_MOTION})
-            row.update(clearance_min=float(crowd["group"]["clearance_min"].min()), marker_dist_min=float(crowd["group"]["marker_dist_min"].min()),
-                       overlap=int(crowd["group"]["overlap_frames"].sum()), touch=int(crowd["group"]["touch_frames"].sum()),
-                       compared=int(crowd["group"]["frames_compared"].sum()))
+            row = measure(op, data, bparams, betas, goal, R0, T0, variant, N, args.seed, groups=variant if joint else None)
+            row["groups"] = "yes" if joint else "no"
             rows.append(row)
             print(row)
     units = dict((c[0], c[1]) for c in metrics.COLUMNS)
