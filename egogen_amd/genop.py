@@ -605,8 +605,9 @@ class GAMMAPrimitiveComboGenOP:
         if people is not None:
             S, G = int(joint_sweeps), len(people.to(dev))
             trace = lambda *tail, dtype=f32: torch.empty(K, S, *tail, device=dev, dtype=dtype)
+            reach = float(pair_skin if pair_model == "markers" else body_radius)      # what the model's people keep clear of each other
             s.update({"joint": (_lib.ptr(people.group_start), _lib.ptr(people.group_member), G, S, float(pair_weight), float(pair_margin),
-                                float(body_radius), float(goal_thresh)), "joint_alive": people,
+                                reach, float(goal_thresh)), "joint_alive": people,
                       "individual_choice": rec(dtype=i32), "pair_term": trace(b, N), "pair_clearance": trace(b, N),
                       "joint_cost": trace(b, N), "pair_hit": trace(b, N, dtype=i32), "choice_trace": trace(b, dtype=i32),
                       "joint_changed": trace(G, dtype=i32), "crowd_clearance": rec(), "crowd_hit": rec(dtype=i32),
@@ -614,8 +615,7 @@ class GAMMAPrimitiveComboGenOP:
             if pair_model == "markers":      # the distance table and the bad-frame masks, allocated once: the loop stays launches only
                 npairs = int(people.pair_offsets[-1])
                 s.update({"pair_dist": torch.empty(npairs, N, N, T_PRED, device=dev, dtype=f32) if npairs else None,
-                          "row_bad": torch.zeros(b * N, device=dev, dtype=i32),
-                          "joint": (*s["joint"][:6], float(pair_skin), float(goal_thresh)), "npairs": npairs})
+                          "row_bad": torch.zeros(b * N, device=dev, dtype=i32), "npairs": npairs})
         if scene is not None:
             s["lbs_out"]["pene_count"] = torch.empty(b * M * T_ALL, device=dev, dtype=i32)
         s["policy"] = policy
@@ -661,6 +661,19 @@ class GAMMAPrimitiveComboGenOP:
             search.update(policy.record(s))
         return self._result(s, zc, bt, R0_end[::M].reshape(b, 3, 3).contiguous(), T0_end[::M].contiguous(), to_numpy, search)
 
+    @staticmethod
+    def _joint_lead(s, b, N, st):
+        """-> (the joint entry of the state's pair model, what it takes before the selection's rows, the arguments of the distance
+        launch that goes before it or None)"""
+        rows = (_lib.ptr(s["lbs_out"]["joints"]), 127, _lib.ptr(s["R0"]), _lib.ptr(s["T0"]), _lib.ptr(s["goal"]))
+        if s.get("row_bad") is None:
+            return "egx_primitive_select_joint", rows, None
+        crowd, npairs = s["joint_alive"], s["npairs"]         # the marker model: the table's launch, then the sweeps on it
+        table, bad, pair_start = _lib.ptr(s["pair_dist"]), _lib.ptr(s["row_bad"]), _lib.ptr(crowd.pair_start)
+        dist_args = (_lib.ptr(s["lbs_out"]["markers"]), _lib.ptr(s["Y_gen"]), s["rf"], _lib.ptr(s["R0"]), _lib.ptr(s["T0"]), b, N,
+                     _lib.ptr(crowd.group_start), _lib.ptr(crowd.group_member), pair_start, len(crowd), npairs, table, bad, st)
+        return "egx_primitive_select_joint_markers", (table, bad, pair_start, npairs, *rows), dist_args
+
     def _search_loop(self, K, b, N, s):
         """The primitive loop of `generate_sequence_to_goal`: launches only, no allocation that depends on k, no host wait.  With
         groups (s["joint"]) the joint launch stands between the selection and the hand-off - with the marker model (s["row_bad"])
@@ -671,14 +684,7 @@ class GAMMAPrimitiveComboGenOP:
         select = getattr(lib, name)
         joint, policy = s.get("joint"), s.get("policy")
         if joint is not None:
-            joint_in = (_lib.ptr(s["lbs_out"]["joints"]), 127, _lib.ptr(s["R0"]), _lib.ptr(s["T0"]), _lib.ptr(s["goal"]))
-            joint_name, dist_args = "egx_primitive_select_joint", None
-            if s.get("row_bad") is not None:            # the marker model: the table's launch, then the sweeps on it
-                joint_name, crowd, npairs = "egx_primitive_select_joint_markers", s["joint_alive"], s["npairs"]
-                table, bad, pair_start = _lib.ptr(s["pair_dist"]), _lib.ptr(s["row_bad"]), _lib.ptr(crowd.pair_start)
-                joint_in = (table, bad, pair_start, npairs, *joint_in)
-                dist_args = (_lib.ptr(s["lbs_out"]["markers"]), _lib.ptr(s["Y_gen"]), s["rf"], _lib.ptr(s["R0"]), _lib.ptr(s["T0"]), b, N,
-                             _lib.ptr(crowd.group_start), _lib.ptr(crowd.group_member), pair_start, len(crowd), npairs, table, bad, st)
+            joint_name, joint_in, dist_args = self._joint_lead(s, b, N, st)
             joint_entry = getattr(lib, joint_name)
         sensed = [()] * K
         if policy is not None and policy.sense_people:      # what the policy senses of the others: the groups' CSR and the obstacles

@@ -6,6 +6,8 @@ and that the entries that existed before did not move.  GPU only.
     python scripts/bench_genop_joint.py --lib <parent .so> --dump outputs.pt        (once, on the parent build)
     python scripts/bench_genop_joint.py --compare outputs.pt [--out-dir profiles]   (once, on this build)
     python scripts/bench_genop_joint.py --markers [--iters 20] [--out-dir profiles]  (the marker-level pair model)
+    python scripts/bench_genop_joint.py [--markers] --lib <parent .so> --save parent.json, then [--markers] --parent parent.json
+                                                                                     (both builds side by side, one process each)
 
 Timing, in one process: G groups of P people swap places on a circle of 2 m, N candidates each, S = 2 sweeps, at the driver's shape
 (4 variants of 4 people, N = 16) and at 8 groups x 8 people x N = 32.  Device events around --iters passes of the whole primitive
@@ -16,7 +18,8 @@ that: all sweeps always run over all rows.
 
 Bit identity: `--dump` writes every output of the selection entries that existed before (scripts/bench_genop_obstacles.py's
 inputs for egx_primitive_select, _select_field, _beam_select, _beam_select_field, and the obstacle entries on two of the obstacle
-tests' constructed cases); `--compare` recomputes them and compares bit for bit.
+tests' constructed cases) and every output of the three joint entries on the first draw of the cases of their kernel tests
+(`joint_outputs`); `--compare` recomputes them and compares bit for bit, NaN traces included.
 Writes the sections between the `timings` and the `identity` markers of `<out-dir>/genop_joint.md`.
 
 `--markers`: the marker-level pair model (`pair_model="markers"`, csrc/genop_joint_markers.hip) on the same people, at the two shapes
@@ -89,6 +92,28 @@ def existing_outputs():
     return out
 
 
+def joint_outputs():
+    """every output of the three joint entries on the first draw of each case of their kernel tests"""
+    from egogen_amd import synth
+    from egogen_amd.body_model import BodyModelHandle
+    from tests import genop_gpu_helpers as gh
+    from tests import test_genop_joint_gpu as jg
+    from tests import test_genop_joint_markers_gpu as mg
+    V = gh.V_SMALL
+    world = {"handle": BodyModelHandle(synth.make_body_model(0, num_verts=V), synth.marker_ids(V), synth.feet_vids(V))}
+    out = {}
+    for case, (sizes, N, S, jpb, extra, interleave, mode) in jg.KERNEL_CASES.items():
+        c = jg._case(world, sizes, N, 40 + N + len(sizes), jpb, extra, interleave, mode)
+        out.update({f"select_joint {case} {k}": v for k, v in jg._joint(c, S).items()})
+    for case, (sizes, N, extra, interleave) in mg.DIST_CASES.items():
+        d = mg._dist(mg._mcase(world, sizes, N, 60 + N + len(sizes), 127, extra, interleave))
+        out.update({f"pair_marker_dist {case} D": d["D"].cpu(), f"pair_marker_dist {case} row_bad": d["bad"].cpu()})
+    for case, (sizes, N, S, jpb, extra, interleave, mode) in mg.SWEEP_CASES.items():
+        c = mg._mcase(world, sizes, N, 40 + N + len(sizes), jpb, extra, interleave, mode)
+        out.update({f"select_joint_markers {case} {k}": v for k, v in mg._sweep(c, S, mg._dist(c)).items()})
+    return out
+
+
 def same_bits(a, b):
     return a.shape == b.shape and a.dtype == b.dtype and bool((a.contiguous().view(torch.int32) == b.contiguous().view(torch.int32)).all())
 
@@ -108,6 +133,44 @@ def swap_people(body, G, P, N, g):
     return data, xb, betas, -T0 + torch.tensor([0.0, 0.0, 0.9]), dict(z=z, T0=T0, R0=R0, to_numpy=False), np.arange(b) // P
 
 
+def joint_launches(op, lib, s, k, b, N):
+    """single launches of the joint step of a captured loop state s on the rows of primitive k -> {"joint": launch} and, with the
+    marker model, {"distance": launch} too"""
+    vp = lambda t: C.c_void_p(t.data_ptr())
+    st = _lib.current_stream_ptr()
+    name, lead, dist = op._joint_lead(s, b, N, st)
+    tail = (vp(s["cost"][k]), vp(s["cost_terms"][k]), vp(s["colliding"][k]), b, N, *s["joint"], vp(s["choice"][k]), vp(s["status"][k]),
+            vp(s["reached"][k]), vp(s["goal_dist"][k]), vp(s["pair_term"][k]), vp(s["pair_clearance"][k]), vp(s["joint_cost"][k]),
+            vp(s["pair_hit"][k]), vp(s["choice_trace"][k]), vp(s["joint_changed"][k]), vp(s["crowd_clearance"][k]), vp(s["crowd_hit"][k]), st)
+    out = {"joint": lambda: _lib.check(getattr(lib, name)(*lead, *tail), name)}
+    if dist is not None:
+        out["distance"] = lambda: _lib.check(lib.egx_pair_marker_dist(*dist), "egx_pair_marker_dist")
+    return out
+
+
+BOUND = 1.03        # a leg's median against the parent build's of the same call; the recorded window ranges of these legs reach about 3 %
+
+
+def table(args, rows):
+    """rows [(shape, leg, {median_us, min_us, max_us})] -> the lines of the table; --save keeps them for a later run, --parent puts
+    that run's next to this one's: held where the median is within BOUND of the parent's or inside the parent's own window"""
+    import json
+    fmt = lambda v: f"{v['median_us']:.1f} ({v['min_us']:.1f} .. {v['max_us']:.1f})"
+    if args.save:
+        with open(args.save, "w") as fh:
+            json.dump(rows, fh)
+    if not args.parent:
+        return ["| shape | leg | us |", "|---|---|---|"] + [f"| {shape} | {leg} | {fmt(v)} |" for shape, leg, v in rows]
+    with open(args.parent) as fh:
+        parent = {(shape, leg): v for shape, leg, v in json.load(fh)}
+    lines = ["| shape | leg | parent build, us | this build, us | ratio of the medians | held |", "|---|---|---|---|---|---|"]
+    for shape, leg, v in rows:
+        q = parent[(shape, leg)]
+        ok = v["median_us"] <= max(BOUND * q["median_us"], q["max_us"])
+        lines.append(f"| {shape} | {leg} | {fmt(q)} | {fmt(v)} | {v['median_us'] / q['median_us']:.3f} | {'yes' if ok else 'NO'} |")
+    return lines
+
+
 def marker_timings(args):
     """the `cost` section of genop_joint_markers.md"""
     from bench_genop import alternate
@@ -115,13 +178,10 @@ def marker_timings(args):
     lib = _lib.load()
     op, body = build_op(args.num_verts)
     g = torch.Generator().manual_seed(1)
-    vp = lambda t: C.c_void_p(t.data_ptr())
-    fmt = lambda v: f"{v['median_us']:.1f} ({v['min_us']:.1f} .. {v['max_us']:.1f})"
     lines = [f"Device: {torch.cuda.get_device_name(0)}; K = {K} primitives, body of {args.num_verts} vertices, no scene, S = {S} sweeps; one "
              f"process, {args.iters} loop passes or {10 * args.iters} launches per window, three windows per leg after {args.warmup} warm-up "
-             "passes, the legs taking turns; device events.  Microseconds: median (range of the windows); loops per primitive.", "",
-             "| shape | leg | us |", "|---|---|---|"]
-    notes = []
+             "passes, the legs taking turns; device events.  Microseconds: median (range of the windows); loops per primitive.", ""]
+    rows, notes = [], []
     for G, P, N in MARKER_SHAPES:
         b = G * P
         data, xb, betas, goal, kw, groups = swap_people(body, G, P, N, g)
@@ -129,31 +189,15 @@ def marker_timings(args):
         res = {}
         cyl, sc = captured(op, "_search_loop", lambda: res.update(c=run()))
         mk, sm = captured(op, "_search_loop", lambda: res.update(m=run(pair_model="markers")))
-        st, k = _lib.current_stream_ptr(), K - 1
-        legs = {}
-        for name, s in (("cylinder", sc[3]), ("markers", sm[3])):
-            lbs, crowd = s["lbs_out"], s["joint_alive"]
-            tail = (vp(s["cost"][k]), vp(s["cost_terms"][k]), vp(s["colliding"][k]), b, N, *s["joint"], vp(s["choice"][k]), vp(s["status"][k]),
-                    vp(s["reached"][k]), vp(s["goal_dist"][k]), vp(s["pair_term"][k]), vp(s["pair_clearance"][k]), vp(s["joint_cost"][k]),
-                    vp(s["pair_hit"][k]), vp(s["choice_trace"][k]), vp(s["joint_changed"][k]), vp(s["crowd_clearance"][k]), vp(s["crowd_hit"][k]), st)
-            lead = (_lib.ptr(lbs["joints"]), 127, _lib.ptr(s["R0"]), _lib.ptr(s["T0"]), _lib.ptr(s["goal"]))
-            if name == "cylinder":
-                legs["cylinder joint launch"] = lambda a=(*lead, *tail): _lib.check(lib.egx_primitive_select_joint(*a), "egx_primitive_select_joint")
-                continue
-            table = (_lib.ptr(s["pair_dist"]), _lib.ptr(s["row_bad"]), _lib.ptr(crowd.pair_start), s["npairs"])
-            dist = (_lib.ptr(lbs["markers"]), _lib.ptr(s["Y_gen"]), s["rf"], _lib.ptr(s["R0"]), _lib.ptr(s["T0"]), b, N, _lib.ptr(crowd.group_start),
-                    _lib.ptr(crowd.group_member), table[2], len(crowd), s["npairs"], table[0], table[1], st)
-            legs["distance launch"] = lambda a=dist: _lib.check(lib.egx_pair_marker_dist(*a), "egx_pair_marker_dist")
-            legs["sweep launch"] = lambda a=(*table, *lead, *tail): _lib.check(lib.egx_primitive_select_joint_markers(*a),
-                                                                              "egx_primitive_select_joint_markers")
-            npairs = s["npairs"]
+        cylinder, markers = joint_launches(op, lib, sc[3], K - 1, b, N), joint_launches(op, lib, sm[3], K - 1, b, N)
+        legs = {"cylinder joint launch": cylinder["joint"], "distance launch": markers["distance"], "sweep launch": markers["joint"]}
+        npairs = sm[3]["npairs"]
         t = alternate({"loop, cylinder model": cyl, "loop, marker model": mk}, args.iters, args.warmup)
         for v in t.values():
             for q in ("median_us", "min_us", "max_us"):
                 v[q] /= K
         t.update(alternate(legs, 10 * args.iters, args.warmup))
-        for name, v in t.items():
-            lines.append(f"| G={G} P={P} N={N} (b={b}) | {name} | {fmt(v)} |")
+        rows += [(f"G={G} P={P} N={N} (b={b})", name, v) for name, v in t.items()]
         evals = npairs * N * N * 18 * 67 * 67
         rate = evals / (t["distance launch"]["median_us"] * 1e-6)
         rc, rm = res["c"], res["m"]
@@ -164,7 +208,7 @@ def marker_timings(args):
                      f"MB).  Crowd hits per primitive, cylinder / marker model (each in its own measure): {rc.crowd_hit.sum(1).tolist()} / "
                      f"{rm.crowd_hit.sum(1).tolist()}; members still changing in the last sweep: {rc.joint_changed[:, -1].sum(1).tolist()} / "
                      f"{rm.joint_changed[:, -1].sum(1).tolist()}.")
-    lines += [""] + notes
+    lines += table(args, rows) + [""] + notes
     write_section(args.out_dir, "cost", lines, "genop_joint_markers.md", "# The marker-level pair model of the joint search\n")
     print("\n".join(lines))
 
@@ -176,12 +220,10 @@ def timings(args):
     op, body = build_op(args.num_verts)
     g = torch.Generator().manual_seed(1)
     vp = lambda t: C.c_void_p(t.data_ptr())
-    fmt = lambda v: f"{v['median_us']:.1f} ({v['min_us']:.1f} .. {v['max_us']:.1f})"
     lines = [f"Device: {torch.cuda.get_device_name(0)}; K = {K} primitives, body of {args.num_verts} vertices, no scene, S = {S} sweeps; one "
              f"process, {args.iters} loop passes or {10 * args.iters} launches per window, three windows per leg, the legs taking turns.  "
-             "Microseconds: median (range of the windows); loops per primitive.", "",
-             "| shape | leg | us |", "|---|---|---|"]
-    notes = []
+             "Microseconds: median (range of the windows); loops per primitive.", ""]
+    rows, notes = [], []
     for G, P, N in SHAPES:
         b = G * P
         data, xb, betas, goal, kw, groups = swap_people(body, G, P, N, g)
@@ -192,26 +234,22 @@ def timings(args):
         s, st = sf[3], _lib.current_stream_ptr()
         cur, lbs, k = s["xs"][(K - 1) % 2], s["lbs_out"], K - 1
         outs = (vp(s["choice"][k]), vp(s["status"][k]), vp(s["reached"][k]), vp(s["goal_dist"][k]))
-        rows = (vp(s["cost"][k]), vp(s["cost_terms"][k]), vp(s["colliding"][k]))
+        scored = (vp(s["cost"][k]), vp(s["cost_terms"][k]), vp(s["colliding"][k]))
         lead = (_lib.ptr(s["Y_gen"]), vp(cur[0]), vp(cur[1]), 201, _lib.ptr(lbs["joints"]), 127, _lib.ptr(lbs["markers"]), _lib.ptr(s["R0"]),
                 _lib.ptr(s["T0"]), None, _lib.ptr(s["goal"]), _lib.ptr(s["feet"]), s["weights"], s["pene_thres"], s["goal_thresh"], s["rf"], b, N)
-        jargs = (_lib.ptr(lbs["joints"]), 127, _lib.ptr(s["R0"]), _lib.ptr(s["T0"]), _lib.ptr(s["goal"]), *rows, b, N, *s["joint"], *outs,
-                 vp(s["pair_term"][k]), vp(s["pair_clearance"][k]), vp(s["joint_cost"][k]), vp(s["pair_hit"][k]), vp(s["choice_trace"][k]),
-                 vp(s["joint_changed"][k]), vp(s["crowd_clearance"][k]), vp(s["crowd_hit"][k]))
-        launches = {"select launch": lambda: _lib.check(lib.egx_primitive_select(*lead, *outs, *rows, st), "egx_primitive_select"),
-                    "joint launch": lambda: _lib.check(lib.egx_primitive_select_joint(*jargs, st), "egx_primitive_select_joint")}
+        launches = {"select launch": lambda: _lib.check(lib.egx_primitive_select(*lead, *outs, *scored, st), "egx_primitive_select"),
+                    "joint launch": joint_launches(op, lib, s, k, b, N)["joint"]}
         t = alternate({"loop without groups": plain, "loop with groups": joint}, args.iters, args.warmup)
         for v in t.values():
             for q in ("median_us", "min_us", "max_us"):
                 v[q] /= K
         t.update(alternate(launches, 10 * args.iters, args.warmup))
-        for name, v in t.items():
-            lines.append(f"| G={G} P={P} N={N} (b={b}) | {name} | {fmt(v)} |")
+        rows += [(f"G={G} P={P} N={N} (b={b})", name, v) for name, v in t.items()]
         r = res["r"]
         notes.append(f"G={G} P={P} N={N}: members that changed their choice per primitive, first / last sweep: "
                      f"{r.joint_changed[:, 0].sum(1).tolist()} / {r.joint_changed[:, -1].sum(1).tolist()}; crowd hits per primitive "
                      f"{r.crowd_hit.sum(1).tolist()}.")
-    lines += [""] + notes
+    lines += table(args, rows) + [""] + notes
     write_section(args.out_dir, "timings", lines)
     print("\n".join(lines))
 
@@ -223,6 +261,8 @@ def main():
     ap.add_argument("--dump", default=None)
     ap.add_argument("--compare", default=None)
     ap.add_argument("--markers", action="store_true", help="the marker-level pair model: the cost section of genop_joint_markers.md")
+    ap.add_argument("--save", default=None, help="keep the timing table as JSON (on the parent build, with --lib)")
+    ap.add_argument("--parent", default=None, help="a table kept by --save on the parent build in the same call: both builds side by side")
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--num-verts", type=int, default=None)
@@ -235,13 +275,15 @@ def main():
     if not torch.cuda.is_available():
         sys.exit("bench_genop_joint.py measures on the GPU; no device is visible")
     if args.dump:
-        torch.save(existing_outputs(), args.dump)
+        torch.save({**existing_outputs(), **joint_outputs()}, args.dump)
         print(f"wrote {args.dump}")
     elif args.compare:
-        want, got = torch.load(args.compare), existing_outputs()
+        want, got = torch.load(args.compare), {**existing_outputs(), **joint_outputs()}
         differ = sorted(k for k in want if k not in got or not same_bits(want[k], got[k])) + sorted(k for k in got if k not in want)
         lines = [f"{len(want)} outputs of egx_primitive_select, _select_field, _beam_select, _beam_select_field, _select_obstacles and "
-                 f"_beam_select_obstacles on the pooled test inputs, dumped by the parent commit's build and recomputed by this one: "
+                 f"_beam_select_obstacles on the pooled test inputs, and of egx_primitive_select_joint, egx_pair_marker_dist and "
+                 f"egx_primitive_select_joint_markers on the first draw of every case of their kernel tests (compared through their int32 "
+                 f"view: NaN traces count), dumped by the parent commit's build and recomputed by this one: "
                  + ("every one bit-identical." if not differ else f"{len(differ)} differ: " + "; ".join(differ[:20]) + ".")]
         write_section(args.out_dir, "identity", lines)
         print(lines[0])

@@ -11,11 +11,12 @@ exhaustive tables of the larger GPU cases are billions of distances: those are c
 
 A `state` is one group, a plain dict: members (sequence indices, in order), choice {sequence: row}, D {(a, b): [N,N,18]} a distance
 table as `group_table` gives it (or as the device wrote it), bad [b,N,18] bool, cost [b,N], terms [b,N,5], colliding [b,N], and
-the scalars w, margin, skin.  `member_step`, `sweeps` and `crowd_clearance` are those of tests/genop_joint_ref.py with the frame
-clearance read from the table: c_t = min over the others of D - skin."""
+the scalars w, margin, skin.  The frame clearance is read from the table, c_t = min over the others of D - skin; from there on
+`member_step` and `sweeps` are those of tests/genop_joint_ref.py (`step_of_clearances`, `sweeps`)."""
 import torch
 
-from tests.genop_joint_ref import first_by_key, state_before  # noqa: F401  (the order and the trace bookkeeping are the cylinder model's)
+from tests import genop_joint_ref as jref
+from tests.genop_joint_ref import first_by_key, state_before  # noqa: F401  (the order and the trace bookkeeping are shared)
 
 CHUNK = 1 << 26          # elements of the largest intermediate of `pair_dist`
 
@@ -95,36 +96,11 @@ def _clearances(state, i, rows, dtype):
 def member_step(state, i, dtype):
     """-> dict over the N rows of member i: term, clearance, hit, joint_cost, finite, cls, and `choice`"""
     w, margin, _ = _scalars(state, dtype)
-    m = state["members"][i]
-    N = state["cost"].shape[1]
-    c = _clearances(state, i, list(range(N)), dtype)
-    pen = torch.where(torch.isnan(c), c, (margin - c).clamp(min=0))
-    clearance, term = c.amin(1), pen.sum(1) / 18
-    hit = clearance < 0
-    cost = torch.as_tensor(state["cost"][m]).to(dtype)
-    jc = cost + w * term
-    finite = torch.isfinite(cost) & torch.isfinite(torch.as_tensor(state["terms"][m])).all(-1) & torch.isfinite(term) & torch.isfinite(jc)
-    cls = (~finite).long() * 2 + (torch.as_tensor(state["colliding"][m]).bool() | hit).long()
-    choice = first_by_key(cls, torch.where(finite, jc, torch.zeros_like(jc)))
-    return {"term": term, "clearance": clearance, "hit": hit, "joint_cost": jc, "finite": finite, "cls": cls, "choice": choice}
+    return jref.step_of_clearances(state, i, _clearances(state, i, list(range(state["cost"].shape[1])), dtype), w, margin)
 
 
 def sweeps(state, S, dtype):
-    """S sweeps over the members in order, from state["choice"], which ends as the joint choice -> dict: steps [S][P], choice_trace
-    [S,P], changed [S]"""
-    P = len(state["members"])
-    steps, trace, changed = [], [], []
-    for _ in range(S):
-        row, n = [], 0
-        for i, m in enumerate(state["members"]):
-            r = member_step(state, i, dtype)
-            n += int(r["choice"] != int(state["choice"][m]))
-            state["choice"][m] = r["choice"]
-            row.append(r)
-        steps.append(row)
-        trace.append([int(state["choice"][m]) for m in state["members"]])
-        changed.append(n)
-    return {"steps": steps, "choice_trace": torch.tensor(trace, dtype=torch.long).reshape(S, P), "changed": torch.tensor(changed)}
+    return jref.sweeps(state, S, dtype, member_step)
 
 
 def crowd_clearance(state, dtype):

@@ -9,7 +9,8 @@ either track [b,N,18,2] (world xy of the pelvis at the predicted frames, given) 
 w, margin, body_radius.
 
   * `member_step(state, i, dtype)`: the rows of member i against the others' current choices -> row terms and the choice;
-  * `sweeps(state, S, dtype)`: S Gauss-Seidel sweeps from the state's choices (the state's choices follow) -> traces;
+  * `step_of_clearances(state, i, c, w, margin)`: the same from given frame clearances onward: what every pair model shares;
+  * `sweeps(state, S, dtype, step)`: S Gauss-Seidel sweeps of `step` from the state's choices (which follow) -> traces;
   * `crowd_clearance(state, dtype)`: every member's chosen track against the others' chosen tracks;
   * `state_before(start, trace, s, i)`: the choices a member step saw, from a choice trace."""
 import torch
@@ -57,15 +58,14 @@ def first_by_key(cls, cost):
     return min(range(len(cls)), key=lambda n: (int(cls[n]), float(cost[n]), n))
 
 
-def member_step(state, i, dtype):
-    """-> dict over the N rows of member i: term, clearance, hit, joint_cost, finite, cls, and `choice`"""
-    w, margin, rr = _scalars(state, dtype)
+def step_of_clearances(state, i, c, w, margin):
+    """the member step from the frame clearances c [N,18] of the rows of member i onward, whatever the pair model they come from
+    -> dict over the N rows: term, clearance, hit, joint_cost, finite, cls, and `choice`"""
     m = state["members"][i]
-    c = _clearances(tracks(state, dtype)[m], _others(state, i, dtype), rr)
     pen = torch.where(torch.isnan(c), c, (margin - c).clamp(min=0))
     clearance, term = c.amin(1), pen.sum(1) / 18
     hit = clearance < 0
-    cost = torch.as_tensor(state["cost"][m]).to(dtype)
+    cost = torch.as_tensor(state["cost"][m]).to(c.dtype)
     jc = cost + w * term
     finite = torch.isfinite(cost) & torch.isfinite(torch.as_tensor(state["terms"][m])).all(-1) & torch.isfinite(term) & torch.isfinite(jc)
     cls = (~finite).long() * 2 + (torch.as_tensor(state["colliding"][m]).bool() | hit).long()
@@ -73,15 +73,22 @@ def member_step(state, i, dtype):
     return {"term": term, "clearance": clearance, "hit": hit, "joint_cost": jc, "finite": finite, "cls": cls, "choice": choice}
 
 
-def sweeps(state, S, dtype):
+def member_step(state, i, dtype):
+    """-> dict over the N rows of member i: term, clearance, hit, joint_cost, finite, cls, and `choice`"""
+    w, margin, rr = _scalars(state, dtype)
+    c = _clearances(tracks(state, dtype)[state["members"][i]], _others(state, i, dtype), rr)
+    return step_of_clearances(state, i, c, w, margin)
+
+
+def sweeps(state, S, dtype, step=member_step):
     """S sweeps over the members in order, from state["choice"], which ends as the joint choice -> dict: steps [S][P] (what
-    `member_step` gave), choice_trace [S,P], changed [S]"""
+    `step`, the pair model's member step, gave), choice_trace [S,P], changed [S]"""
     P = len(state["members"])
     steps, trace, changed = [], [], []
     for _ in range(S):
         row, n = [], 0
         for i, m in enumerate(state["members"]):
-            r = member_step(state, i, dtype)
+            r = step(state, i, dtype)
             n += int(r["choice"] != int(state["choice"][m]))
             state["choice"][m] = r["choice"]
             row.append(r)

@@ -156,6 +156,20 @@ def _case(world, sizes, N, seed, jpb=127, extra=0, interleave=False, mode="plain
     return {"b": b, "N": N, "jpb": jpb, "groups": groups, "i": i, "sel": o, "alive": (alive, fld, x), "weights": weights}
 
 
+OUTS = PER_SEQ[:4] + TRACES + ("choice_trace", "changed", "crowd_clearance", "crowd_hit")      # in the order of both sweep entries
+
+
+def _sweep_outputs(c, S, G):
+    """the twelve outputs of either sweep entry: the selection's four as copies (the case can be launched again), the rest NaN / -7"""
+    b, N = c["b"], c["N"]
+    fi = lambda *s: torch.full(s, -7, dtype=torch.int32, device="cuda")
+    ff = lambda *s: torch.full(s, float("nan"), device="cuda")
+    o = {k: c["sel"][k].clone() for k in ("choice", "status", "reached", "goal_dist")}
+    o.update({"pair_term": ff(S, b, N), "pair_clearance": ff(S, b, N), "joint_cost": ff(S, b, N), "pair_hit": fi(S, b, N), "choice_trace": fi(S, b),
+              "changed": fi(S, G), "crowd_clearance": ff(b), "crowd_hit": fi(b)})
+    return o
+
+
 def _joint(c, S, groups=None, w=W_PAIR, margin=MARGIN, body=BODY):
     """egx_primitive_select_joint on the selection outputs of case c (copies: the case can be launched again) -> outputs on the CPU"""
     from egogen_amd import _lib
@@ -164,19 +178,13 @@ def _joint(c, S, groups=None, w=W_PAIR, margin=MARGIN, body=BODY):
     G = len(groups)
     start = torch.tensor(np.cumsum([0] + [len(g) for g in groups]), dtype=torch.int32, device="cuda")
     member = torch.tensor([m for g in groups for m in g] or [0], dtype=torch.int32, device="cuda")
-    fi = lambda *s: torch.full(s, -7, dtype=torch.int32, device="cuda")
-    ff = lambda *s: torch.full(s, float("nan"), device="cuda")
-    o = {k: c["sel"][k].clone() for k in ("choice", "status", "reached", "goal_dist")}
-    o.update({"pair_term": ff(S, b, N), "pair_clearance": ff(S, b, N), "joint_cost": ff(S, b, N), "pair_hit": fi(S, b, N), "choice_trace": fi(S, b),
-              "changed": fi(S, G), "crowd_clearance": ff(b), "crowd_hit": fi(b)})
+    o = _sweep_outputs(c, S, G)
     goal = c["alive"][0][0]
     keep = {k: c["sel"][k].clone() for k in ("cost", "terms", "colliding")}
     _lib.check(_lib.load().egx_primitive_select_joint(
         _lib.ptr(i["J"]), c["jpb"], _lib.ptr(i["R0"]), _lib.ptr(i["T0"]), _lib.ptr(goal), _lib.ptr(c["sel"]["cost"]), _lib.ptr(c["sel"]["terms"]),
-        _lib.ptr(c["sel"]["colliding"]), b, N, _lib.ptr(start), _lib.ptr(member), G, S, w, margin, body, GOAL_THRESH, _lib.ptr(o["choice"]),
-        _lib.ptr(o["status"]), _lib.ptr(o["reached"]), _lib.ptr(o["goal_dist"]), _lib.ptr(o["pair_term"]), _lib.ptr(o["pair_clearance"]),
-        _lib.ptr(o["joint_cost"]), _lib.ptr(o["pair_hit"]), _lib.ptr(o["choice_trace"]), _lib.ptr(o["changed"]), _lib.ptr(o["crowd_clearance"]),
-        _lib.ptr(o["crowd_hit"]), _lib.current_stream_ptr()), "egx_primitive_select_joint")
+        _lib.ptr(c["sel"]["colliding"]), b, N, _lib.ptr(start), _lib.ptr(member), G, S, w, margin, body, GOAL_THRESH, *[_lib.ptr(o[k]) for k in OUTS],
+        _lib.current_stream_ptr()), "egx_primitive_select_joint")
     torch.cuda.synchronize()
     for k, v in keep.items():
         assert torch.equal(c["sel"][k], v), k                                                # the selection's rows are only read
@@ -184,10 +192,11 @@ def _joint(c, S, groups=None, w=W_PAIR, margin=MARGIN, body=BODY):
 
 
 # ---- the checks of one launch ----------------------------------------------------------------------------------------------------
-def _base_state(c, w=W_PAIR, margin=MARGIN, body=BODY):
-    b, N, i, sel = c["b"], c["N"], c["i"], c["sel"]
-    return {"R0": i["R0"], "T0": i["T0"], "J": i["J"], "cost": sel["cost"].cpu(), "terms": sel["terms"].cpu(), "colliding": sel["colliding"].cpu().bool(),
-            "w": w, "margin": margin, "body_radius": body, "_tracks": {}}
+def _cylinder_state(c, w=W_PAIR, margin=MARGIN, body=BODY):
+    """what a state of tests/genop_joint_ref.py carries beyond the common keys, the same for every group (the tracks are cached)"""
+    i = c["i"]
+    state = {"R0": i["R0"], "T0": i["T0"], "J": i["J"], "w": w, "margin": margin, "body_radius": body, "_tracks": {}}
+    return lambda gi: state
 
 
 def _device_classes(c, o, s):
@@ -198,10 +207,12 @@ def _device_classes(c, o, s):
     return (~finite).long() * 2 + (sel["colliding"].cpu().bool() | o["pair_hit"][s].bool()).long()
 
 
-def _check_launch(name, c, o, S, pool, w=W_PAIR, margin=MARGIN, body=BODY):
-    """every member step and the whole launch of case c with outputs o; the held() groups are appended to `pool`"""
+def _check_launch(name, c, o, S, pool, ref, model_state):
+    """every member step and the whole launch of case c with outputs o of either sweep entry; the held() groups are appended to
+    `pool`.  ref: the pair model's restatement (tests/genop_joint_ref.py, tests/genop_joint_markers_ref.py); model_state(gi): what a
+    state of group gi carries for it beyond the common keys (cost, terms, colliding, members, choice)"""
     b, N, sel = c["b"], c["N"], {k: v.cpu() for k, v in c["sel"].items()}
-    base = _base_state(c, w, margin, body)
+    common = {"cost": sel["cost"], "terms": sel["terms"], "colliding": sel["colliding"].bool()}
     start = {m: int(sel["choice"][m]) for m in range(b)}
     trace = o["choice_trace"].long()
     in_group = sorted(m for g in c["groups"] for m in g)
@@ -211,12 +222,12 @@ def _check_launch(name, c, o, S, pool, w=W_PAIR, margin=MARGIN, body=BODY):
         cls_dev = _device_classes(c, o, s)
         for gi, members in enumerate(c["groups"]):
             for k, m in enumerate(members):
-                st = dict(base, members=members, choice=jref.state_before(members, start, trace, s, k))
-                r64, r32 = jref.member_step(st, k, torch.float64), jref.member_step(st, k, torch.float32)
+                st = dict(common, **model_state(gi), members=members, choice=ref.state_before(members, start, trace, s, k))
+                r64, r32 = ref.member_step(st, k, torch.float64), ref.member_step(st, k, torch.float32)
                 assert torch.equal(o["pair_hit"][s, m].bool(), r64["hit"]) and torch.equal(r32["hit"], r64["hit"]), (name, s, m)
                 assert torch.equal(cls_dev[m], r64["cls"]) and torch.equal(r32["cls"], r64["cls"]), (name, s, m)
                 key = torch.where(cls_dev[m] < 2, o["joint_cost"][s, m], torch.zeros(N))
-                assert int(trace[s, m]) == jref.first_by_key(cls_dev[m], key), (name, s, m)   # the order on the device's own values
+                assert int(trace[s, m]) == ref.first_by_key(cls_dev[m], key), (name, s, m)   # the order on the device's own values
                 wn = r64["choice"]
                 same = [n for n in range(N) if n != wn and int(r64["cls"][n]) == int(r64["cls"][wn])]
                 ok = True
@@ -252,10 +263,12 @@ def _check_launch(name, c, o, S, pool, w=W_PAIR, margin=MARGIN, body=BODY):
             if abs(d64 - GOAL_THRESH) > 3.0 * e32:
                 assert int(o["reached"][m]) == int(d64 < GOAL_THRESH), (name, m)
     for gi, members in enumerate(c["groups"]):
-        st = dict(base, members=members, choice={m: int(final[m]) for m in members})
-        c64, c32 = jref.crowd_clearance(st, torch.float64), jref.crowd_clearance(st, torch.float32)
+        st = dict(common, **model_state(gi), members=members, choice={m: int(final[m]) for m in members})
+        c64, c32 = ref.crowd_clearance(st, torch.float64), ref.crowd_clearance(st, torch.float32)
+        fin = ~torch.isnan(c64)                                                                 # a NaN truth (a bad row) is held exactly
         assert torch.equal(o["crowd_hit"][members].bool(), c64 < 0) and torch.equal(c32 < 0, c64 < 0), (name, gi)
-        pool["crowd"].append((o["crowd_clearance"][members], c64, c32))
+        assert torch.equal(torch.isnan(o["crowd_clearance"][members]), ~fin), (name, gi)
+        pool["crowd"].append((o["crowd_clearance"][members][fin], c64[fin], c32[fin]))
     for m in out_group:                                                                       # a sequence of no group: nothing of it is touched
         for k in ("choice", "status", "reached"):
             assert int(o[k][m]) == int(sel[k][m]), (k, m)
@@ -275,12 +288,15 @@ def _held_finite(name, what, got, t64, t32):
 
 
 def _close_pool(name, pool, need_term):
+    """the pooled yardsticks of a case; a NaN truth (a bad row of the marker model) is held exactly"""
     got, r64, r32 = (torch.cat(pool[k], 1) for k in ("got", "r64", "r32"))
     assert got.shape[1] >= MIN_GROUP or not need_term, (name, got.shape)
     if need_term:
-        assert float(r64[0].max()) > 0.1, name                                                # the term is exercised, not only the veto
+        assert float(r64[0][torch.isfinite(r64[0])].max()) > 0.1, name                       # the term is exercised, not only the veto
     for j, what in enumerate(("pair_term", "pair_clearance", "joint_cost")):
-        _held_finite(name, what, got[j], r64[j], r32[j])
+        nan = torch.isnan(r64[j])
+        assert torch.equal(torch.isnan(got[j]), nan) and torch.equal(torch.isnan(r32[j]), nan), (name, what)
+        _held_finite(name, what, got[j][~nan], r64[j][~nan], r32[j][~nan])
     if pool["crowd"]:
         _held_finite(name, "crowd_clearance", *(torch.cat([v[j] for v in pool["crowd"]]) for j in range(3)))
     ok = torch.tensor(pool["ok"])
@@ -319,7 +335,7 @@ def test_select_joint_kernel(small_world, case):
         assert ok, (name, draw)
         hits, near, draw = hits + h, near + nm, draw + 1
         o = _joint(c, S)
-        _check_launch(name, c, o, S, pool)
+        _check_launch(name, c, o, S, pool, jref, _cylinder_state(c))
     emit(f"| {name} | candidate pairs x frames: hits / near misses | {hits} / {near} | draws {draw} | |")
     assert not pairs or (hits > 0 and near > 0)
     _close_pool(name, pool, pairs)
@@ -340,7 +356,7 @@ def test_two_members_one_gives_way(small_world):
     assert float((o["crowd_clearance"] - 0.3).abs().max()) < 1e-5 and abs(float(o["pair_clearance"][0, 0, 0]) + 0.3) < 1e-5
     assert torch.equal(o["goal_dist"][1], sel["goal_dist"][1]) and abs(float(o["goal_dist"][0]) - float(sel["terms"][0, 1, 0])) < 1e-5
     pool = _new_pool()
-    _check_launch("select_joint two people", c, o, 2, pool, w=1.0)
+    _check_launch("select_joint two people", c, o, 2, pool, jref, _cylinder_state(c, w=1.0))
     got, r64 = torch.cat(pool["got"], 1), torch.cat(pool["r64"], 1)
     fin = torch.isfinite(r64)
     assert float((got.double() - r64)[fin].abs().max()) < 1e-5 and all(pool["ok"])

@@ -28,9 +28,8 @@ import pytest
 import torch
 
 from tests import genop_joint_markers_ref as mref
-from tests import genop_search_ref as sref
 from tests import test_genop_joint_gpu as jg
-from tests.genop_gpu_helpers import (CFG_RF, MIN_GROUP, ROOT, UNDECIDABLE_CAP, V_SMALL, W_TEST, _feet, emit, held, patched_loop,  # noqa: F401
+from tests.genop_gpu_helpers import (CFG_RF, MIN_GROUP, ROOT, V_SMALL, W_TEST, emit, held, patched_loop,  # noqa: F401
                                      search_world, small_world)
 
 pytestmark = pytest.mark.gpu
@@ -39,8 +38,7 @@ SKIN, MARGIN, W_PAIR = 0.2, 0.6, 1.3
 BAND = 0.05
 SPREAD, DELTA, HEIGHT = 0.02, 0.05, 1.7
 GOAL_THRESH = jg.GOAL_THRESH
-OUTS = ("choice", "status", "reached", "goal_dist", "pair_term", "pair_clearance", "joint_cost", "pair_hit", "choice_trace", "changed",
-        "crowd_clearance", "crowd_hit")
+OUTS = jg.OUTS
 
 
 # ---- inputs ----------------------------------------------------------------------------------------------------------------------
@@ -127,11 +125,7 @@ def _sweep(c, S, d, groups=None, w=W_PAIR, margin=MARGIN, skin=SKIN):
     b, N, i = c["b"], c["N"], c["i"]
     G = len(groups)
     start, member, pstart, ps = _csr(groups)
-    fi = lambda *s: torch.full(s, -7, dtype=torch.int32, device="cuda")
-    ff = lambda *s: torch.full(s, float("nan"), device="cuda")
-    o = {k: c["sel"][k].clone() for k in ("choice", "status", "reached", "goal_dist")}
-    o.update({"pair_term": ff(S, b, N), "pair_clearance": ff(S, b, N), "joint_cost": ff(S, b, N), "pair_hit": fi(S, b, N), "choice_trace": fi(S, b),
-              "changed": fi(S, G), "crowd_clearance": ff(b), "crowd_hit": fi(b)})
+    o = jg._sweep_outputs(c, S, G)
     goal = c["alive"][0][0]
     keep = {k: c["sel"][k].clone() for k in ("cost", "terms", "colliding")}
     bad = d["bad"].reshape(-1).contiguous()
@@ -316,103 +310,14 @@ def test_a_non_finite_marker(small_world):
 
 
 # ---- the sweep entry, fed the device's own table -------------------------------------------------------------------------------------
-def _new_pool():
-    return {"ok": [], "got": [], "r64": [], "r32": [], "crowd": [], "dist": []}
-
-
-def _device_classes(c, o, s):
-    return jg._device_classes(c, o, s)
+_new_pool, _close_pool = jg._new_pool, jg._close_pool
 
 
 def _check_launch(name, c, o, S, d, pool, w=W_PAIR, margin=MARGIN, skin=SKIN):
-    """every member step and the whole launch of case c with outputs o on the device's table d; `_check_launch` of
-    tests/test_genop_joint_gpu.py with the marker model's restatement"""
-    b, N, sel = c["b"], c["N"], {k: v.cpu() for k, v in c["sel"].items()}
-    base = {"cost": sel["cost"], "terms": sel["terms"], "colliding": sel["colliding"].bool(), "bad": (d["bad"].cpu()[..., None] >> torch.arange(18)) & 1 != 0,
-            "w": w, "margin": margin, "skin": skin}
+    """`_check_launch` of tests/test_genop_joint_gpu.py with the marker model's restatement on the device's table d"""
+    model = {"bad": (d["bad"].cpu()[..., None] >> torch.arange(18)) & 1 != 0, "w": w, "margin": margin, "skin": skin}
     tables = [{k: v.cpu() for k, v in _group_tables(d, gi).items()} for gi in range(len(c["groups"]))]
-    start = {m: int(sel["choice"][m]) for m in range(b)}
-    trace = o["choice_trace"].long()
-    in_group = sorted(m for g in c["groups"] for m in g)
-    out_group = [m for m in range(b) if m not in in_group]
-    assert int(trace[:, in_group].min()) >= 0 and int(trace[:, in_group].max()) < N
-    for s in range(S):
-        cls_dev = _device_classes(c, o, s)
-        for gi, members in enumerate(c["groups"]):
-            for k, m in enumerate(members):
-                st = dict(base, members=members, D=tables[gi], choice=mref.state_before(members, start, trace, s, k))
-                r64, r32 = mref.member_step(st, k, torch.float64), mref.member_step(st, k, torch.float32)
-                assert torch.equal(o["pair_hit"][s, m].bool(), r64["hit"]) and torch.equal(r32["hit"], r64["hit"]), (name, s, m)
-                assert torch.equal(cls_dev[m], r64["cls"]) and torch.equal(r32["cls"], r64["cls"]), (name, s, m)
-                key = torch.where(cls_dev[m] < 2, o["joint_cost"][s, m], torch.zeros(N))
-                assert int(trace[s, m]) == mref.first_by_key(cls_dev[m], key), (name, s, m)   # the order on the device's own values
-                wn = r64["choice"]
-                same = [n for n in range(N) if n != wn and int(r64["cls"][n]) == int(r64["cls"][wn])]
-                ok = True
-                if same and int(r64["cls"][wn]) < 2:
-                    gap = min(float(r64["joint_cost"][n]) for n in same) - float(r64["joint_cost"][wn])
-                    ok = gap > 6.0 * float((r32["joint_cost"].double() - r64["joint_cost"]).abs().max())
-                if ok:
-                    assert r32["choice"] == wn and int(trace[s, m]) == wn, (name, s, m, int(trace[s, m]), wn)
-                pool["ok"].append(ok)
-                pool["got"].append(torch.stack([o["pair_term"][s, m], o["pair_clearance"][s, m], o["joint_cost"][s, m]]))
-                pool["r64"].append(torch.stack([r64["term"], r64["clearance"], r64["joint_cost"]]))
-                pool["r32"].append(torch.stack([r32["term"], r32["clearance"], r32["joint_cost"]]))
-            prev = [start[m] if s == 0 else int(trace[s - 1, m]) for m in members]
-            assert int(o["changed"][s, gi]) == sum(int(trace[s, m]) != p for m, p in zip(members, prev)), (name, s, gi)
-    final = trace[S - 1]
-    cls_last = _device_classes(c, o, S - 1)
-    i = c["i"]
-    r = {dt: sref.score(i["Y_gen"], i["X"], i["J"], i["mp"], i["R0"], i["T0"], i["pene"], i["goal_rows"], _feet(), c["weights"], 40.0, CFG_RF, dt)["dist"]
-         .reshape(b, N) for dt in (torch.float64, torch.float32)}
-    e32 = float((r[torch.float32].double() - r[torch.float64]).abs().max())
-    for m in in_group:
-        ch = int(final[m])
-        assert int(o["choice"][m]) == ch
-        cl = int(cls_last[m, ch])
-        assert int(o["status"][m]) == (cl & 1) | (2 if cl >= 2 else 0), (name, m)
-        if ch == start[m]:
-            assert torch.equal(o["goal_dist"][m], sel["goal_dist"][m]) and int(o["reached"][m]) == int(sel["reached"][m]), (name, m)
-        else:
-            d64 = float(r[torch.float64][m, ch])
-            err = abs(float(o["goal_dist"][m]) - d64)
-            pool["dist"].append((err, e32))
-            assert err <= 3.0 * e32, (name, m, err, e32)
-            if abs(d64 - GOAL_THRESH) > 3.0 * e32:
-                assert int(o["reached"][m]) == int(d64 < GOAL_THRESH), (name, m)
-    for gi, members in enumerate(c["groups"]):
-        st = dict(base, members=members, D=tables[gi], choice={m: int(final[m]) for m in members})
-        c64, c32 = mref.crowd_clearance(st, torch.float64), mref.crowd_clearance(st, torch.float32)
-        fin = ~torch.isnan(c64)
-        assert torch.equal(o["crowd_hit"][members].bool(), c64 < 0) and torch.equal(c32 < 0, c64 < 0), (name, gi)
-        assert torch.equal(torch.isnan(o["crowd_clearance"][members]), ~fin), (name, gi)
-        pool["crowd"].append((o["crowd_clearance"][members][fin], c64[fin], c32[fin]))
-    for m in out_group:                                                                       # a sequence of no group: nothing of it is touched
-        for k in ("choice", "status", "reached"):
-            assert int(o[k][m]) == int(sel[k][m]), (k, m)
-        assert torch.equal(o["goal_dist"][m], sel["goal_dist"][m])
-        assert int(o["crowd_hit"][m]) == -7 and bool(torch.isnan(o["crowd_clearance"][m])) and bool((o["choice_trace"][:, m] == -7).all())
-        assert bool((o["pair_hit"][:, m] == -7).all())
-        for k in ("pair_term", "pair_clearance", "joint_cost"):
-            assert bool(torch.isnan(o[k][:, m]).all()), (k, m)
-
-
-def _close_pool(name, pool, need_term):
-    """`_close_pool` of tests/test_genop_joint_gpu.py; a NaN truth (a bad row) is held exactly"""
-    got, r64, r32 = (torch.cat(pool[k], 1) for k in ("got", "r64", "r32"))
-    assert got.shape[1] >= MIN_GROUP or not need_term, (name, got.shape)
-    if need_term:
-        assert float(r64[0][torch.isfinite(r64[0])].max()) > 0.1, name                       # the term is exercised, not only the veto
-    for j, what in enumerate(("pair_term", "pair_clearance", "joint_cost")):
-        nan = torch.isnan(r64[j])
-        assert torch.equal(torch.isnan(got[j]), nan) and torch.equal(torch.isnan(r32[j]), nan), (name, what)
-        jg._held_finite(name, what, got[j][~nan], r64[j][~nan], r32[j][~nan])
-    if pool["crowd"]:
-        jg._held_finite(name, "crowd_clearance", *(torch.cat([v[j] for v in pool["crowd"]]) for j in range(3)))
-    ok = torch.tensor(pool["ok"])
-    share = 1.0 - float(ok.float().mean())
-    emit(f"| {name} | undecidable member steps | {int((~ok).sum())} of {ok.numel()} | {share:.3f} | changed goal_dist {len(pool['dist'])} |")
-    assert share <= UNDECIDABLE_CAP, (name, share)
+    jg._check_launch(name, c, o, S, pool, mref, lambda gi: dict(model, D=tables[gi]))
 
 
 # sizes, N, S, jpb, extra, interleave, mode
