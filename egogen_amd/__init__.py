@@ -14,4 +14,7 @@ def __getattr__(name):      # `from egogen_amd import GeodesicField` without imp
     if name == "MotionSet":
         from .metrics import MotionSet
         return MotionSet
+    if name == "Routes":
+        from .route import Routes
+        return Routes
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

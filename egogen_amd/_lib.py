@@ -263,6 +263,13 @@ SIGNATURES = {
     # body_radius, hold, clearance, marker_dist, pair_list, stream
     "egx_crowd_metrics": (C.c_int, [C.c_void_p] * 4 + [C.c_int, C.c_void_p, C.c_int, C.c_void_p, c_int_p, C.c_int] + [C.c_void_p] * 3 +
                           [c_int_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int] + [C.c_void_p] * 4),
+    # the records and the frame table, then: waypoints, count, max_waypoints, pass_radius, pass_frame, approach_min, waypoints_passed,
+    # stream
+    "egx_route_metrics": (C.c_int, [C.c_void_p] * 4 + [C.c_int, C.c_void_p, C.c_int, C.c_void_p, c_int_p, C.c_int, C.c_void_p, C.c_void_p,
+                                    C.c_int, C.c_double] + [C.c_void_p] * 4),
+    # pelvis_loc, transf_rotmat, transf_transl, waypoints, count, field_of, num_sequences, max_waypoints, pass_radius, cursor, goal,
+    # field_index, reached, route_cursor, route_goal, route_pass_dist, stream
+    "egx_route_advance": (C.c_int, [C.c_void_p] * 6 + [C.c_int, C.c_int, C.c_float] + [C.c_void_p] * 8),
     "egx_sample_action": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_int, C.c_int, C.c_void_p,
                                     C.c_void_p, C.c_void_p]),
     "egx_gae": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double, C.c_void_p,

@@ -19,7 +19,9 @@ continues from that joint choice.  With `policy=` (a
 `PolicyProposal`, egogen_amd/proposal.py) the candidates of the greedy search are no longer all drawn from N(0, I): per primitive
 every sequence senses its surroundings (entry egx_primitive_observe, csrc/genop_policy.hip), the trained policy's actor proposes
 mu, logvar over the latent, and the candidate rows become mu, samples round it and a share of prior samples (entry
-egx_policy_propose); the selection scores them as before.
+egx_policy_propose); the selection scores them as before.  With `route=` (a `Routes`, egogen_amd/route.py) every sequence of the
+greedy search walks an itinerary of waypoints: one launch per primitive after the hand-off (entry egx_route_advance,
+csrc/genop_route.hip) moves a per-sequence cursor and rewrites the goal buffer every kernel of the loop reads.
 
 The three chains share their host path: `_chain_state` builds the state dict (checked inputs, defaults, the loop's buffers, the
 records) for b seeds of M rows each, `_primitive` launches what every primitive begins with (prior, parameter assembly, body
@@ -115,6 +117,32 @@ def _person_groups(groups, data, beam_width, pair_weight, pair_margin, body_radi
     return groups
 
 
+def _checked_route(route, data, goal, beam_width, goal_thresh):
+    """The `route=` argument of `generate_sequence_to_goal` checked on the host, before any device work -> the `Routes` (None without
+    one).  TypeError for anything but a `Routes`; ValueError: another number of routes than the b seeds of `data`, a route with a
+    beam, a `goal` that is neither None nor the routes' last waypoints, a pass_radius below goal_thresh."""
+    if route is None:
+        return None
+    from .route import Routes
+    if not isinstance(route, Routes):
+        raise TypeError(f"route must be None or a Routes, got {type(route).__name__}")
+    if beam_width > 1:
+        raise ValueError(f"route= is the greedy search only: beam_width must be 1 with it, got {beam_width}")
+    shape = tuple(np.shape(data))
+    if len(shape) != 3:
+        raise ValueError(f"data must be [>=2,b,>=201], got {shape}")
+    if len(route) != shape[1]:
+        raise ValueError(f"route must hold {shape[1]} routes, one per sequence, got {len(route)}")
+    if goal is not None:
+        g = np.asarray(goal.detach().cpu() if torch.is_tensor(goal) else goal, np.float32)
+        if g.shape not in ((3,), (shape[1], 3)) or not np.array_equal(np.broadcast_to(g, (shape[1], 3)), route.last()):
+            raise ValueError("goal contradicts the route: with route= it must be None or route.last(), the last waypoint of every route")
+    if route.pass_radius < float(goal_thresh):
+        raise ValueError(f"pass_radius {route.pass_radius} is below goal_thresh {goal_thresh}: a point the selection calls reached must "
+                         f"also count as passed")
+    return route
+
+
 class PrimitiveSequence:
     """What `generate_sequence` returns: K primitives of b sequences.
     markers [K,b,20,67,3] blended markers, params [K,b,20,93], rotmat [K,b,3,3] / transl [K,b,3] the world frame each primitive
@@ -140,7 +168,11 @@ class PrimitiveSequence:
     between the two people's nearest blended markers minus pair_skin, in 3-D.
     With `policy=PolicyProposal(..., sense_people=True)`: policy_sense_people True, people_box [K,b,4] (minx, miny, maxx, maxy) the
     world xy box of every sequence's two seed frames' markers at each primitive and obs_people_count [K,b] the holes its observation
-    was cast against; False, None, None with a policy that does not sense people, None without a policy."""
+    was cast against; False, None, None with a policy that does not sense people, None without a policy.
+    With `route=`: route_waypoints [b,P,3] / route_count [b] the routes, pass_radius; route_goal [K,b,3] the waypoint primitive k was
+    scored against, route_pass_dist [K,b] the least horizontal distance of its 18 predicted frames to that waypoint (NaN for a NaN
+    position), route_cursor [K,b] the cursor after primitive k.  goal is then the last waypoint of every route; goal_dist[k] and
+    cost_terms[..., 0] stay what the selection wrote: the distance to route_goal[k].  None without a route."""
     SEARCH_FIELDS = ("goal", "choice", "cost", "cost_terms", "colliding", "status", "goal_dist", "n_valid", "geo_dist")
     BEAM_FIELDS = ("beam_width", "path_slot", "parent", "beam_row", "path_cost", "beam_status")
     OBSTACLE_FIELDS = ("obstacle_term", "clearance", "obstacle_hit")
@@ -149,6 +181,7 @@ class PrimitiveSequence:
     POLICY_FIELDS = ("policy_mu", "policy_logvar", "obs_state", "obs_egosensing", "obs_dist", "obs_time", "policy_temperature",
                      "policy_n_mean", "policy_n_policy", "policy_ray_len", "policy_max_depth")
     PEOPLE_FIELDS = ("people_box", "obs_people_count", "policy_sense_people")
+    ROUTE_FIELDS = ("route_waypoints", "route_count", "route_cursor", "route_goal", "route_pass_dist", "pass_radius")
 
     def __init__(self, markers, params, rotmat, transl, pelvis, z, betas, gender, R0, T0, search: Optional[dict] = None):
         self.markers, self.params, self.rotmat, self.transl, self.pelvis, self.z = markers, params, rotmat, transl, pelvis, z
@@ -156,7 +189,7 @@ class PrimitiveSequence:
         self.search = search
         for k in self.SEARCH_FIELDS:
             setattr(self, k, None if search is None else search[k])
-        for k in self.BEAM_FIELDS + self.OBSTACLE_FIELDS + self.JOINT_FIELDS + self.POLICY_FIELDS + self.PEOPLE_FIELDS:
+        for k in self.BEAM_FIELDS + self.OBSTACLE_FIELDS + self.JOINT_FIELDS + self.POLICY_FIELDS + self.PEOPLE_FIELDS + self.ROUTE_FIELDS:
             setattr(self, k, None if search is None else search.get(k))
 
     def primitives(self, i: int) -> list:
@@ -167,10 +200,15 @@ class PrimitiveSequence:
 
     def save(self, outfolder: str, i: int, man_id=None) -> str:
         """`motion_<man_id>.pkl` of sequence i with a two-point wpath in the world frame: first pelvis, then the goal of a
-        goal-steered result, else the last pelvis."""
+        goal-steered result, else the last pelvis.  A result searched with `route=` writes the whole route: first pelvis, then
+        every waypoint."""
         from .utils import save_rollout_results
         as_t = lambda x: torch.as_tensor(x)
         first = as_t(self.rotmat[0, i]) @ as_t(self.pelvis[0, i, 0]) + as_t(self.transl[0, i])
+        if self.route_waypoints is not None:
+            way = as_t(self.route_waypoints[i][:int(self.route_count[i])]).to(first)
+            scene = {"wpath": torch.cat([first[None], way]), "navmesh_path": None}
+            return save_rollout_results(scene, self.primitives(i), outfolder, man_id=man_id)
         if self.goal is not None:
             last = as_t(self.goal[i]).to(first)
         else:
@@ -429,12 +467,12 @@ class GAMMAPrimitiveComboGenOP:
                                   obstacle_margin: float = 0.5, body_radius: float = 0.3,
                                   obstacle_frame0: int = 0, groups=None, pair_weight: float = 1.0, pair_margin: float = 0.5,
                                   joint_sweeps: int = 2, policy=None, pair_model: str = "cylinder",
-                                  pair_skin: float = 0.05) -> PrimitiveSequence:
+                                  pair_skin: float = 0.05, route=None) -> PrimitiveSequence:
         """`generate_sequence` steered to a goal through a scene by a greedy best-of-N search: for each of the `n_primitives`
         primitives, `n_candidates` candidates per sequence are generated, scored and the best one is kept; every candidate of the
         next primitive continues from it.  data / bparams / betas / reproj_factor / R0 / T0 as in `generate_sequence` (b seeds,
         one sequence each).
-            - goal: [b,3] or [3], world coordinates
+            - goal: [b,3] or [3], world coordinates; None (or the last waypoints) with `route=`
             - n_candidates: N in [1, 256] (ValueError above)
             - scene: None (no penetration term, nothing collides), an SdfScene, or an SdfSceneSet with agent_scene [b]
             - weights: {goal, skate, floor, pene, face} of cost = sum w * term, the terms being the arguments of the env's reward
@@ -513,6 +551,22 @@ class GAMMAPrimitiveComboGenOP:
               of the polygon its rays are cast against (egx_primitive_people_boxes -> egx_primitive_observe_people in place of
               egx_primitive_observe, the obstacles at the absolute frames obstacle_frame0 + 18 k and + 1 of the two seed frames);
               without it the policy senses the static polygon only.
+            - route: None, or a `Routes` (egogen_amd/route.py) of b routes: every sequence walks an itinerary of 1 to 16 waypoints,
+              the last of which is its goal (`goal` must then be None or `route.last()`; ValueError otherwise).  Every kernel of the
+              loop reads the goal from one [b,3] device buffer; that buffer starts at the first waypoints, and one more launch per
+              primitive after the hand-off (egx_route_advance, csrc/genop_route.hip) moves a per-sequence cursor and rewrites it -
+              and, with `geodesic=`, the [b] index that picks each sequence's field.  The rule, over the 18 predicted frames of the
+              chosen primitive in order: a waypoint that is not the last is passed at the first frame whose pelvis is within
+              `route.pass_radius` of it horizontally; the next one may be passed from that same frame on.  The greedy search only
+              (ValueError with beam_width > 1): the slots of a beam would need a cursor and a goal each.  pass_radius must not be
+              below goal_thresh (ValueError): a point the selection calls reached must also count as passed.  With `geodesic=` the
+              field must hold one field per entry of `route.field_goals()`, in that order (ValueError otherwise).  scene, obstacles,
+              groups (both pair models) and policy work as they are: they read the goal through the same pointer, so a policy's
+              observation aims at the current waypoint.  The result's `goal` is `route.last()`, and `ROUTE_FIELDS` hold the trace.
+              The loop stays launches only.  The limits: the goal term is the distance to the current waypoint only - a candidate
+              that passes it mid-primitive gets no credit for the leg beyond; arrival at the last waypoint can be recognised one
+              primitive late when the cursor reaches it during that same primitive (`reached` of a primitive scored against an
+              intermediate point is cleared); after the last waypoint the person still keeps walking.
         Raises FloatingPointError when a chosen hand-off, or every candidate of a sequence, held a non-finite value (read once,
         after the loop); for a beam, when a node of the returned path did."""
         from .body_model import SdfScene, SdfSceneSet
@@ -536,9 +590,12 @@ class GAMMAPrimitiveComboGenOP:
             check_beam(W)
             policy.counts(N)
         people = _person_groups(groups, data, W, pair_weight, pair_margin, body_radius, joint_sweeps, pair_model, pair_skin, N)
+        if goal_thresh is None:
+            goal_thresh = self.testconfig.get("goal_thresh", 0.1)
+        route = _checked_route(route, data, goal, W, goal_thresh)
         X, seed, bt = self._seed_inputs(data, bparams, betas, -1, None)
         b, dev, f32, i32 = X.shape[1], self.device, torch.float32, torch.int32
-        goal = self._dev(goal, "goal")
+        goal = self._dev(goal if route is None else route.last(), "goal")
         if goal.shape == (3,):
             goal = goal.reshape(1, 3).repeat(b, 1)
         if goal.shape != (b, 3):
@@ -549,13 +606,20 @@ class GAMMAPrimitiveComboGenOP:
             from .geodesic import GeodesicField
             if not isinstance(geodesic, GeodesicField):
                 raise TypeError(f"geodesic must be None or a GeodesicField, got {type(geodesic).__name__}")
-            if len(geodesic) not in (1, b):
+            if route is None and len(geodesic) not in (1, b):
                 raise ValueError(f"geodesic must hold 1 or {b} fields, got {len(geodesic)}")
             if geodesic.dist.device != dev:
                 raise ValueError(f"geodesic lives on {geodesic.dist.device}, the operator on {dev}")
-            if not torch.equal(geodesic.goals[:, :2].to(dev).expand(b, 2), goal[:, :2]):
-                raise ValueError("the fields of `geodesic` were built for other goals than `goal` (their xy must be equal)")
-            field_args, field_alive = geodesic.select_args(b)
+            if route is None:
+                if not torch.equal(geodesic.goals[:, :2].to(dev).expand(b, 2), goal[:, :2]):
+                    raise ValueError("the fields of `geodesic` were built for other goals than `goal` (their xy must be equal)")
+                field_args, field_alive = geodesic.select_args(b)
+            else:       # one field per distinct waypoint; the index of every sequence is a buffer the route launch rewrites
+                want = torch.from_numpy(route.field_goals()[:, :2])
+                if len(geodesic) != len(want) or not torch.equal(geodesic.goals[:, :2].cpu(), want):
+                    raise ValueError("the fields of `geodesic` must be those of route.field_goals(), in that order (their xy must be equal)")
+                field_alive = torch.from_numpy(route.field_of[:, 0].copy()).to(dev).contiguous()
+                field_args = (*geodesic.select_args(b)[0][:6], _lib.ptr(field_alive))
         obs_args = obs_alive = None
         if obstacles is not None:
             from .obstacles import MovingObstacles
@@ -589,8 +653,6 @@ class GAMMAPrimitiveComboGenOP:
             if unknown:
                 raise ValueError(f"unknown weights {sorted(unknown)}: the terms are {list(w)}")
             w.update({k: float(v) for k, v in weights.items()})
-        if goal_thresh is None:
-            goal_thresh = self.testconfig.get("goal_thresh", 0.1)
         s = self._chain_state(X, seed, bt, K, M, z, reproj_factor, R0, T0)
         rec = lambda *tail, dtype=f32: torch.empty(K, b, *tail, device=dev, dtype=dtype)
         s.update({"goal": goal, "scene": scene, "rows_scene": rows_scene, "pp": torch.empty(b * M, T_ALL, XB, device=dev, dtype=f32),
@@ -618,6 +680,12 @@ class GAMMAPrimitiveComboGenOP:
                           "row_bad": torch.zeros(b * N, device=dev, dtype=i32), "npairs": npairs})
         if scene is not None:
             s["lbs_out"]["pene_count"] = torch.empty(b * M * T_ALL, device=dev, dtype=i32)
+        s["route"] = None
+        if route is not None:       # the live goal is a buffer of its own: search["goal"] stays the last waypoints
+            rd, P = route.to(dev), route.waypoints.shape[1]
+            s.update({"goal": rd["waypoints"][:, 0].clone().contiguous(), "route_alive": rd, "route_state": torch.zeros(b, device=dev, dtype=i32),
+                      "route_cursor": rec(dtype=i32), "route_goal": rec(3), "route_pass_dist": rec(),
+                      "route": (_lib.ptr(rd["waypoints"]), _lib.ptr(rd["count"]), _lib.ptr(rd["field_of"]), b, P, float(route.pass_radius))})
         s["policy"] = policy
         if policy is not None:
             if z is not None:
@@ -659,6 +727,10 @@ class GAMMAPrimitiveComboGenOP:
             search.update({k: s[k] for k in PrimitiveSequence.JOINT_FIELDS + ("pair_model", "pair_skin")})
         if policy is not None:
             search.update(policy.record(s))
+        if route is not None:
+            search.update({"route_waypoints": s["route_alive"]["waypoints"], "route_count": s["route_alive"]["count"],
+                           "route_cursor": s["route_cursor"], "route_goal": s["route_goal"], "route_pass_dist": s["route_pass_dist"],
+                           "pass_radius": float(route.pass_radius)})
         return self._result(s, zc, bt, R0_end[::M].reshape(b, 3, 3).contiguous(), T0_end[::M].contiguous(), to_numpy, search)
 
     @staticmethod
@@ -677,12 +749,15 @@ class GAMMAPrimitiveComboGenOP:
     def _search_loop(self, K, b, N, s):
         """The primitive loop of `generate_sequence_to_goal`: launches only, no allocation that depends on k, no host wait.  With
         groups (s["joint"]) the joint launch stands between the selection and the hand-off - with the marker model (s["row_bad"])
-        the two launches of csrc/genop_joint_markers.hip in its place; a device copy keeps what the selection chose."""
+        the two launches of csrc/genop_joint_markers.hip in its place; a device copy keeps what the selection chose.  With a route
+        (s["route"]) one launch after the hand-off moves the cursors and rewrites the goal buffer the next primitive reads."""
         lib, st, hand, pp = _lib.load(), _lib.current_stream_ptr(), self._handoff_lead(s), _lib.ptr(s["pp"])
         sel = self._select_lead(s, [s["R0"]] * 2, [s["T0"]] * 2)
         name, field, obs = self._select_tail(s, K, "egx_primitive_select")
         select = getattr(lib, name)
-        joint, policy = s.get("joint"), s.get("policy")
+        joint, policy, route = s.get("joint"), s.get("policy"), s.get("route")
+        if route is not None:
+            route_out = (_lib.ptr(s["route_state"]), _lib.ptr(s["goal"]), _lib.ptr(s["field_alive"]) if s["field"] else None)
         if joint is not None:
             joint_name, joint_in, dist_args = self._joint_lead(s, b, N, st)
             joint_entry = getattr(lib, joint_name)
@@ -714,6 +789,10 @@ class GAMMAPrimitiveComboGenOP:
                 pp, *hand[k % 2], b, _vp(s["choice"][k]), N, _lib.ptr(s["R0"]), _lib.ptr(s["T0"]), _vp(s["markers"][k]),
                 _vp(s["pelvis"][k]), _vp(s["rotmat"][k]), _vp(s["transl"][k]), _vp(s["params"][k]), _lib.ptr(s["seed"]), _vp(nxt[0]),
                 _vp(nxt[1]), NM3, _lib.ptr(s["nonfinite"]), st), "egx_primitive_advance_select")
+            if route is not None:
+                _lib.check(lib.egx_route_advance(
+                    _vp(s["pelvis"][k]), _vp(s["rotmat"][k]), _vp(s["transl"][k]), *route, *route_out, _vp(s["reached"][k]),
+                    _vp(s["route_cursor"][k]), _vp(s["route_goal"][k]), _vp(s["route_pass_dist"][k]), st), "egx_route_advance")
 
     def _beam_loop(self, K, b, W, N, s):
         """The primitive loop of the beam search and the backtrack after it: launches only, no allocation that depends on k, no

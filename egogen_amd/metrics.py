@@ -4,7 +4,8 @@
 table that makes each motion one run of frames: primitive 0 contributes its frames 0..19, a later '2-frame' primitive its frames
 2..19, a later '1-frame' primitive 1..19 (the rule of `MovingObstacles.from_rollout_files` and `utils.rollout_primitives`).  It is
 built on the host and needs no device.  `motion_metrics` gives the per-motion figures of `COLUMNS` (entry egx_motion_metrics),
-`crowd_metrics` the person-to-person figures of the people of one scene and time line (entry egx_crowd_metrics); both kernels are
+`crowd_metrics` the person-to-person figures of the people of one scene and time line (entry egx_crowd_metrics), `route_metrics`
+whether a motion followed its route of waypoints (entry egx_route_metrics); the kernels are
 csrc/motion_metrics.hip, float64 from the float32 records, deterministic, and their definitions are written out in
 include/egogen_hip.h.  Like the rest of the product path there is no CPU fallback: without the library or a device both raise
 `EgxError`.  (tests/motion_metrics_ref.py is the numpy float64 restatement the kernels are tested against.)
@@ -25,6 +26,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .route import MAX_WAYPOINTS
 
 T_ALL, T_HIS, NMK, XB = 20, 2, 67, 93
 FPS = 40.0
@@ -81,9 +83,11 @@ class MotionSet:
     """n motions of P primitives in all.  markers [P,20,67,3], pelvis [P,20,3], rotmat [P,3,3], transl [P,3], params [P,20,93],
     betas [P,10] (float32, the primitives of motion 0 first); prim_start [n+1] the primitives of each motion; frame_src [Ftot] int32
     (primitive * 20 + t) and motion_start [n+1] int32 the frames of each motion; goals [n,3] float32 (a NaN row: no goal) or None;
-    groups [n] ids or None; names [n].  `len()` is n."""
+    groups [n] ids or None; names [n]; routes: a list of n entries, [n_i,3] float32 (the waypoints of a motion generated with
+    `route=`, at most 16) or None for a motion without a route, or None where no motion has one.  `len()` is n."""
 
-    def __init__(self, markers, pelvis, rotmat, transl, params, betas, prim_start, mp_types, goals=None, groups=None, names=None):
+    def __init__(self, markers, pelvis, rotmat, transl, params, betas, prim_start, mp_types, goals=None, groups=None, names=None,
+                 routes=None):
         self.markers, self.pelvis, self.rotmat, self.transl = _np(markers), _np(pelvis), _np(rotmat), _np(transl)
         self.params, self.betas = _np(params), _np(betas)
         self.prim_start = np.asarray(prim_start, np.int64)
@@ -122,6 +126,14 @@ class MotionSet:
         self.names = [str(i) for i in range(n)] if names is None else [str(v) for v in names]
         if len(self.names) != n:
             raise ValueError(f"names must hold {n} entries, got {len(self.names)}")
+        self.routes = None
+        if routes is not None and any(r is not None for r in routes):
+            if len(routes) != n:
+                raise ValueError(f"routes must hold {n} entries, got {len(routes)}")
+            self.routes = [None if r is None else _np(r).reshape(-1, 3) for r in routes]
+            for r in self.routes:
+                if r is not None and (not 1 <= len(r) <= MAX_WAYPOINTS or not np.isfinite(r).all()):
+                    raise ValueError(f"a route holds 1 to {MAX_WAYPOINTS} finite waypoints, got {len(r)}")
         self._dev = None
 
     def __len__(self):
@@ -137,12 +149,13 @@ class MotionSet:
         """seqs: a `PrimitiveSequence` (numpy or torch) or a list of them; every sequence i of every result becomes one motion of
         its first n_valid[i] primitives (all K where the result has no n_valid), every primitive '2-frame'.  The goal is
         `search["goal"][i]` of a goal-steered result; the `groups` of a joint result carry over (two results never share a
-        group; a sequence of a result without groups is alone)."""
+        group; a sequence of a result without groups is alone); so do the routes of a result searched with `route=`
+        (`PrimitiveSequence.ROUTE_FIELDS`)."""
         seqs = list(seqs) if isinstance(seqs, (list, tuple)) else [seqs]
         if not seqs:
             raise ValueError("no sequence to measure")
         rec = {k: [] for k in ("markers", "pelvis", "rotmat", "transl", "params", "betas")}
-        prim_start, goals, groups, names, any_group, next_group = [0], [], [], [], False, 0
+        prim_start, goals, groups, names, any_group, next_group, routes = [0], [], [], [], False, 0, []
         for r, q in enumerate(seqs):
             try:
                 mk, pl, R, t, pp, bt = (_np(getattr(q, k)) for k in ("markers", "pelvis", "rotmat", "transl", "params", "betas"))
@@ -161,8 +174,11 @@ class MotionSet:
             ids = getattr(q, "groups", None)
             ids = None if ids is None else _np(ids, np.int64).reshape(b)
             any_group |= ids is not None
+            way = getattr(q, "route_waypoints", None)
+            cnt = None if way is None else _np(q.route_count, np.int64).reshape(b)
             remap = {}
             for i in range(b):
+                routes.append(None if way is None else _np(way)[i, :int(cnt[i])])
                 n = int(min(max(n_valid[i], 1), K))
                 for k, a in (("markers", mk), ("pelvis", pl), ("rotmat", R), ("transl", t), ("params", pp)):
                     rec[k].append(a[:n, i])
@@ -177,18 +193,20 @@ class MotionSet:
                 names.append(f"{r}:{i}" if len(seqs) > 1 else str(i))
         rec = {k: np.concatenate(v, 0) for k, v in rec.items()}
         return cls(rec["markers"], rec["pelvis"], rec["rotmat"], rec["transl"], rec["params"], rec["betas"], prim_start,
-                   ["2-frame"] * int(prim_start[-1]), goals, groups if any_group else None, names)
+                   ["2-frame"] * int(prim_start[-1]), goals, groups if any_group else None, names, routes)
 
     @classmethod
     def from_rollout_files(cls, paths, groups=None) -> "MotionSet":
         """The same from `motion_*.pkl` files (`PrimitiveSequence.save`, `utils.save_rollout_results`), one motion per file: reads
         blended_marker, smplx_params, betas, transf_rotmat, transf_transl, pelvis_loc and mp_type of every primitive; the goal is
-        wpath[-1], as `PrimitiveSequence.save` writes it.  groups: None, [n] ids, or "names" for `groups_from_file_names`."""
+        wpath[-1], as `PrimitiveSequence.save` writes it, and a wpath of more than two points is a route: wpath[1:].  A wpath that
+        cannot be one (more than 16 points after the first, as a navmesh path may have, or a non-finite point) leaves the motion
+        without a route; its other figures are measured as before.  groups: None, [n] ids, or "names" for `groups_from_file_names`."""
         paths = [paths] if isinstance(paths, (str, bytes)) or hasattr(paths, "__fspath__") else list(paths)
         if not paths:
             raise ValueError("no file to measure")
         rec = {k: [] for k in ("markers", "pelvis", "rotmat", "transl", "params", "betas")}
-        prim_start, goals, types = [0], [], []
+        prim_start, goals, types, routes = [0], [], [], []
         for path in paths:
             with open(path, "rb") as fh:
                 node = pickle.load(fh)
@@ -209,13 +227,15 @@ class MotionSet:
             prim_start.append(prim_start[-1] + len(motion))
             wpath = node.get("wpath")
             goals.append(np.full(3, np.nan, np.float32) if wpath is None else _np(wpath).reshape(-1, 3)[-1])
+            way = None if wpath is None else _np(wpath).reshape(-1, 3)[1:]
+            routes.append(way if way is not None and 2 <= len(way) <= MAX_WAYPOINTS and np.isfinite(way).all() else None)
         rec = {k: np.concatenate(v, 0) for k, v in rec.items()}
         if isinstance(groups, str):
             if groups != "names":
                 raise ValueError(f'groups must be None, ids or "names", got {groups!r}')
             groups = groups_from_file_names(paths)
         return cls(rec["markers"], rec["pelvis"], rec["rotmat"], rec["transl"], rec["params"], rec["betas"], prim_start, types, goals,
-                   groups, [os.fspath(p) for p in paths])
+                   groups, [os.fspath(p) for p in paths], routes)
 
     # ------------------------------------------------------------------------------------------------------------------
     def to(self, device) -> dict:
@@ -345,6 +365,44 @@ def motion_metrics(motions, goal_thresh: Optional[float] = None, floor_z: float 
     if per_frame:
         res.update(per_frame=frames.cpu().numpy(), frame_src=ms.frame_src.copy(), motion_start=ms.motion_start.copy())
     return res
+
+
+def launch_route_metrics(ms: MotionSet, pass_radius):
+    """One launch of egx_route_metrics over all motions of `ms` on the current stream, no host wait -> pass_frame [n,16] int32,
+    approach_min [n,16] float64, waypoints_passed [n] int32, on the device.  A motion without a route has count 0."""
+    dev = _device()
+    d, n, P = ms.to(dev), len(ms), MAX_WAYPOINTS
+    way, cnt = np.zeros((n, P, 3), np.float32), np.zeros(n, np.int32)
+    for i, r in enumerate(ms.routes or []):
+        if r is not None:
+            way[i, :len(r)], cnt[i] = r, len(r)
+    way_d, cnt_d = torch.from_numpy(way).to(dev), torch.from_numpy(cnt).to(dev)
+    pass_frame = torch.empty(n, P, device=dev, dtype=torch.int32)
+    approach = torch.empty(n, P, device=dev, dtype=torch.float64)
+    passed = torch.empty(n, device=dev, dtype=torch.int32)
+    lead, _alive = ms.lead_args(d)
+    _lib.check(_lib.load().egx_route_metrics(*lead, _lib.ptr(way_d), _lib.ptr(cnt_d), P, float(pass_radius), _lib.ptr(pass_frame),
+                                             _lib.ptr(approach), _lib.ptr(passed), _lib.current_stream_ptr()), "egx_route_metrics")
+    return pass_frame, approach, passed
+
+
+def route_metrics(motions, pass_radius: float = 0.5) -> dict:
+    """Did every motion follow its route (`MotionSet.routes`): the ordered rule of the search's egx_route_advance at frame
+    resolution over the whole motion, from one launch of egx_route_metrics -> dict of numpy arrays
+        - pass_frame [n,16] int32: the frame at which waypoint j, not the last one, was first within pass_radius horizontally,
+          searched from the pass frame of j - 1 on (frame 0 for j = 0); -1 where it never was, for the last waypoint (it is arrived
+          at: `motion_metrics`' first_reached_frame), and on padding
+        - approach_min [n,16] float64: the least horizontal distance to waypoint j from that start frame on; NaN where j - 1 was
+          never passed and on padding
+        - waypoints_passed [n] int32, and count [n] int32 the waypoints of each route
+    A motion without a route gets -1 / NaN / 0.  pass_radius: 0.5 m is the search's default (`Routes`), a stated choice."""
+    ms = _motion_set(motions)
+    if not (float(pass_radius) >= 0 and np.isfinite(float(pass_radius))):
+        raise ValueError(f"pass_radius must be finite and not negative, got {pass_radius}")
+    pass_frame, approach, passed = launch_route_metrics(ms, pass_radius)
+    count = np.asarray([0 if r is None else len(r) for r in (ms.routes or [None] * len(ms))], np.int32)
+    return {"pass_frame": pass_frame.cpu().numpy(), "approach_min": approach.cpu().numpy(), "waypoints_passed": passed.cpu().numpy(),
+            "count": count}
 
 
 def crowd_metrics(motions, groups=None, body_radius: float = 0.3, touch_dist: float = 0.05, hold: bool = False) -> dict:

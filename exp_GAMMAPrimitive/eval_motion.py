@@ -4,7 +4,9 @@
 
 `--in` takes files and directories (every motion_*.pkl of a directory, sorted).  Files named motion_<seed>_<variant>_p<person>.pkl, as
 `gen_motion.py --people` names them, are the people of one scene and time line: one group per (seed, variant), measured against
-each other (`crowd_metrics`); every other file is measured alone.  The goal of a file is the last point of its `wpath`.  With
+each other (`crowd_metrics`); every other file is measured alone.  The goal of a file is the last point of its `wpath`; a
+`wpath` of more than two points is a route (`gen_motion.py` with several waypoints), and such a file's row also says which of its
+waypoints the motion passed, at which frame, and how near it came (`route_metrics`, `--pass-radius`).  With
 `--scene file.npz` (keys sdf, center, scale) the bodies are posed again and their vertices inside the scene counted, on the
 licensed SMPL-X model where present, else on the seeded synthetic body of `--num-verts` vertices, as in the other drivers.
 
@@ -47,12 +49,14 @@ def collect(inputs):
     return paths
 
 
-def evaluate(paths, scene=None, body_model=None, goal_thresh=None, floor_z=0.0, body_radius=0.3, touch_dist=0.05, hold=False):
+def evaluate(paths, scene=None, body_model=None, goal_thresh=None, floor_z=0.0, body_radius=0.3, touch_dist=0.05, hold=False,
+             pass_radius=0.5):
     """-> the dict `main` writes"""
     ms = metrics.MotionSet.from_rollout_files(paths, groups="names")
     per = metrics.motion_metrics(ms, goal_thresh=goal_thresh, floor_z=floor_z, scene=scene, body_model=body_model)
     crowd = metrics.crowd_metrics(ms, body_radius=body_radius, touch_dist=touch_dist, hold=hold)
     names = [c[0] for c in metrics.COLUMNS]
+    route = None if ms.routes is None else metrics.route_metrics(ms, pass_radius=pass_radius)
     size_of = dict(zip(crowd["group"]["id"].tolist(), crowd["group"]["size"].tolist()))
     files = []
     for i, path in enumerate(paths):
@@ -60,6 +64,11 @@ def evaluate(paths, scene=None, body_model=None, goal_thresh=None, floor_z=0.0, 
         row.update({k: _plain(per[k][i]) for k in names})
         if size_of[int(ms.groups[i])] > 1:
             row.update({k: _plain(crowd["person"][k][i]) for k in PERSON})
+        if route is not None and route["count"][i] > 0:          # the file carries a route: wpath[1:]
+            n = int(route["count"][i])
+            row.update({"waypoints": n, "waypoints_passed": int(route["waypoints_passed"][i]),
+                        "pass_frame": [int(v) for v in route["pass_frame"][i, :n]],
+                        "approach_min": [_plain(float(v)) for v in route["approach_min"][i, :n]]})
         files.append(row)
     groups = []
     for g, gid in enumerate(crowd["group"]["id"].tolist()):
@@ -71,7 +80,7 @@ def evaluate(paths, scene=None, body_model=None, goal_thresh=None, floor_z=0.0, 
     with np.errstate(all="ignore"):
         mean = {k: _plain(np.nanmean(per[k].astype(np.float64))) if np.isfinite(per[k].astype(np.float64)).any() else None for k in names}
     return {"columns": [{"name": c[0], "unit": c[1], "meaning": c[3]} for c in metrics.COLUMNS], "goal_thresh": 0.1 if goal_thresh is None else goal_thresh,
-            "floor_z": floor_z, "body_radius": body_radius, "touch_dist": touch_dist, "hold": bool(hold), "files": files, "groups": groups, "mean": mean}
+            **({} if route is None else {"pass_radius": pass_radius}), "floor_z": floor_z, "body_radius": body_radius, "touch_dist": touch_dist, "hold": bool(hold), "files": files, "groups": groups, "mean": mean}
 
 
 def main(argv=None):
@@ -82,6 +91,7 @@ def main(argv=None):
     parser.add_argument("--floor-z", type=float, default=0.0, help="height of the floor in the world")
     parser.add_argument("--body-radius", type=float, default=0.3, help="radius of the search's cylinder model of a person")
     parser.add_argument("--touch-dist", type=float, default=0.05, help="two people's markers closer than this touch")
+    parser.add_argument("--pass-radius", type=float, default=0.5, help="a waypoint of a route counts as passed within this horizontal distance")
     parser.add_argument("--hold", action="store_true", help="a person whose file has ended stands at the last position")
     parser.add_argument("--num-verts", type=int, default=None, help="vertices of the synthetic body (with --scene, without SMPL-X)")
     parser.add_argument("--seed", type=int, default=0, help="seed of the synthetic body (with --scene)")
@@ -104,7 +114,7 @@ def main(argv=None):
             scene = SdfScene({k: f[k] for k in ("sdf", "center", "scale")})
         print("[INFO] body model: {}".format("SMPL-X" if real_body else "synthetic"))
     try:
-        res = evaluate(paths, scene, body, args.goal_thresh, args.floor_z, args.body_radius, args.touch_dist, args.hold)
+        res = evaluate(paths, scene, body, args.goal_thresh, args.floor_z, args.body_radius, args.touch_dist, args.hold, args.pass_radius)
     except (ValueError, OSError, KeyError, pickle.UnpicklingError, EOFError) as e:
         raise SystemExit("eval_motion: {!r}".format(e))
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)

@@ -34,6 +34,11 @@ scales sigma) and a share `--policy-prior-fraction` of prior samples.  Nobody ha
 `--policy-sees-people` (with `--policy`) makes the other people holes of that polygon, as in the reference's crowd evaluation: the
 group-mates of `--people` (the world box of their two seed frames' markers) and the tracks of `--avoid` (the box of their cylinder
 at the two seed frames); without it the policy senses the static polygon only and the selection alone knows about the people.
+`--goal "x,y,z;x,y,z;..."` is a route (`generate_sequence_to_goal(route=)`, `Routes`, egogen_amd/route.py): every variant walks via
+the points in order to the last one, a waypoint counting as passed within `--pass-radius` metres (default 0.5) horizontally; with
+`--people` the waypoints of one person are chained with `>`: "x,y,yaw_deg:g1x,g1y,g1z>g2x,g2y,g2z;...".  A route is the greedy
+search (`--beam-width 1`); `--walkable` then builds one field per distinct waypoint; the files' `wpath` holds the whole route and
+the driver prints how many waypoints each path passed.  One point per person is the path without a route, unchanged.
 
 `--cfg <name>` is the combo config (`crowd_ppo/cfg_samp20/<name>.yml` under the working directory, else the packaged copy): it
 names the predictor's and the regressor's configs, whose checkpoints are read from `results/crowd_ppo/<config>/checkpoints`
@@ -57,6 +62,38 @@ from egogen_amd.canonicalize import canonicalize_frames  # noqa: E402
 from egogen_amd.genop import GAMMAPrimitiveComboGenOP  # noqa: E402
 from egogen_amd.models import PREDICTOR_CFG, REGRESSOR_CFG  # noqa: E402
 from egogen_amd.utils import rollout_primitives  # noqa: E402
+
+
+def _points(text, sep):
+    """ "x,y,z<sep>x,y,z..." -> [n,3] float64; ValueError for anything else"""
+    pts = np.asarray([[float(v) for v in one.split(",")] for one in text.split(sep)], np.float64)
+    if pts.ndim != 2 or pts.shape[1] != 3 or not np.isfinite(pts).all():
+        raise ValueError("every point takes x,y,z")
+    return pts
+
+
+def parse_goal_route(text):
+    """`--goal` with ";" -> the waypoints [n,3] float64 (ValueError for anything else)"""
+    return _points(text, ";")
+
+
+def parse_people_routes(text):
+    """`--people` with ">" -> (people [P,6] float64: x, y, yaw_deg and the LAST waypoint of each person, the routes: a list of
+    [n_i,3] float64); ValueError for anything else"""
+    people, routes = [], []
+    for one in text.split(";"):
+        if not one:
+            continue
+        halves = one.split(":")
+        if len(halves) != 2 or len(halves[0].split(",")) != 3:
+            raise ValueError("a person takes x,y,yaw_deg:waypoints")
+        start, way = [float(v) for v in halves[0].split(",")], _points(halves[1], ">")
+        people.append(start + way[-1].tolist())
+        routes.append(way)
+    people = np.asarray(people, np.float64)
+    if people.ndim != 2 or not 1 <= people.shape[0] <= 32 or not np.isfinite(people).all():
+        raise ValueError("1 to 32 people")
+    return people, routes
 
 
 def main(argv=None):
@@ -92,11 +129,19 @@ def main(argv=None):
                         "room0 (with --policy); default: the --walkable or --scene file where it holds edges")
     parser.add_argument("--policy-sees-people", action="store_true", help="the policy's egosensing rays stop at the other people: the "
                         "group-mates of --people and the tracks of --avoid are holes of the polygon (with --policy)")
+    parser.add_argument("--pass-radius", type=float, default=None, help="horizontal distance in metres within which a waypoint of a "
+                        'route counts as passed (with ";" in --goal or ">" in --people; default 0.5)')
     args = parser.parse_args(argv)
-    people = None
-    if args.people is not None:
-        if args.start is not None or args.goal is not None or args.beam_width != 1:
-            parser.error("--people stands in for --start and --goal and is the greedy search (--beam-width 1)")
+    people = way = None          # way: the waypoints of every person of a run with a route, a list of [n_i,3]
+    if args.people is not None and (args.start is not None or args.goal is not None or args.beam_width != 1):
+        parser.error("--people stands in for --start and --goal and is the greedy search (--beam-width 1)")
+    if args.people is not None and ">" in args.people:
+        try:
+            people, way = parse_people_routes(args.people)
+        except ValueError:
+            parser.error('--people takes "x,y,yaw_deg:gx,gy,gz>gx,gy,gz..." for 1 to 32 people, separated by ";"')
+        args.goal = ",".join(str(v) for v in people[0, 3:])
+    elif args.people is not None:
         try:
             people = np.asarray([[float(v) for half in one.split(":") for v in half.split(",")] for one in args.people.split(";") if one], np.float64)
         except ValueError:
@@ -105,6 +150,16 @@ def main(argv=None):
                 any(len(one.split(":")) != 2 or len(one.split(":")[0].split(",")) != 3 for one in args.people.split(";") if one):
             parser.error('--people takes "x,y,yaw_deg:gx,gy,gz" for 1 to 32 people, separated by ";"')
         args.goal = ",".join(str(v) for v in people[0, 3:])          # the goal-steered path; the goals themselves follow below
+    if args.people is None and args.goal is not None and ";" in args.goal:
+        if args.beam_width != 1:
+            parser.error('a route (";" in --goal) is the greedy search (--beam-width 1)')
+        try:
+            way = [parse_goal_route(args.goal)]
+        except ValueError:
+            parser.error('--goal takes x,y,z, or "x,y,z;x,y,z;..." for a route')
+        args.goal = ",".join(str(v) for v in way[0][-1])
+    if args.pass_radius is not None and way is None:
+        parser.error('--pass-radius needs a route: ";" in --goal or ">" in --people')
     if args.people is None and args.pair_model != "cylinder":
         parser.error("--pair-model markers needs --people: it is a model of how the people of a group see each other")
     if args.pair_skin is not None and (args.pair_model != "markers" or not (args.pair_skin >= 0 and np.isfinite(args.pair_skin))):
@@ -156,12 +211,19 @@ def main(argv=None):
         except (OSError, ValueError, KeyError, pickle.UnpicklingError, EOFError, AttributeError) as e:
             raise SystemExit("--avoid {}: {!r}".format(args.avoid, e))
         print("[INFO] avoiding {} people over {} frames".format(int(obstacles.count[0]), obstacles.num_frames))
+    P = 1 if people is None else people.shape[0]
+    route = None
+    if way is not None:          # before the models and the device; sequence v * P + p walks the route of person p
+        from egogen_amd.route import Routes
+        try:
+            route = Routes.from_lists([way[i % P] for i in range(args.n_gens * P)], pass_radius=0.5 if args.pass_radius is None else args.pass_radius)
+        except ValueError as e:
+            raise SystemExit("route: {}".format(e))
     if not torch.cuda.is_available():
         raise SystemExit("gen_motion needs a HIP device: the MI355X path has no CPU fallback")
     np.random.seed(args.seed)
     torch.manual_seed(args.seed)
     goal = field = None
-    P = 1 if people is None else people.shape[0]
     if people is not None:          # sequence v * P + p is person p of variant v
         goal = np.tile(people[:, 3:].astype(np.float32), (args.n_gens, 1))
     elif args.goal is not None:
@@ -171,9 +233,12 @@ def main(argv=None):
     if args.walkable:        # before the models: a file without a raster, or a goal off it, ends the run here
         from egogen_amd.geodesic import GeodesicField
         try:
-            distinct, of_row = np.unique(goal.reshape(-1, 3), axis=0, return_inverse=True)
-            field = GeodesicField.from_scene(sw.load_scene_file(args.walkable, raster=True), distinct)
-            if people is not None:          # one field per distinct goal is computed, every sequence then reads its own copy
+            if route is not None:          # one field per distinct waypoint: the search picks each sequence's by its cursor
+                field = GeodesicField.from_scene(sw.load_scene_file(args.walkable, raster=True), route.field_goals())
+            else:
+                distinct, of_row = np.unique(goal.reshape(-1, 3), axis=0, return_inverse=True)
+                field = GeodesicField.from_scene(sw.load_scene_file(args.walkable, raster=True), distinct)
+            if people is not None and route is None:          # one field per distinct goal is computed, every sequence then reads its own copy
                 idx = torch.as_tensor(of_row.reshape(-1), device=field.dist.device)
                 field = GeodesicField(field.dist[idx].contiguous(), field.origin[idx].contiguous(), field.cell, field.goals[idx].contiguous(),
                                       field.passes)
@@ -244,10 +309,12 @@ def main(argv=None):
             print("[INFO] policy {}: {} of {} candidates from the policy, {} of them its mean{}".format(
                 args.policy, proposal.counts(args.n_candidates)[1], args.n_candidates, proposal.counts(args.n_candidates)[0],
                 "; it senses the other people as holes of the polygon" if args.policy_sees_people else ""))
+        search = dict(scene=scene, R0=R0, T0=T0, beam_width=args.beam_width, geodesic=field, obstacles=obstacles, groups=groups, policy=proposal,
+                      pair_model=args.pair_model, pair_skin=0.05 if args.pair_skin is None else args.pair_skin)
+        if route is not None:
+            search["route"] = route
         res = op.generate_sequence_to_goal(data.repeat(nseq, 1), bparams.repeat(nseq, 1), can["betas"].astype(np.float32),
-                                           goal, args.n_primitives, args.n_candidates, scene=scene, R0=R0, T0=T0,
-                                           beam_width=args.beam_width, geodesic=field, obstacles=obstacles, groups=groups, policy=proposal,
-                                           pair_model=args.pair_model, pair_skin=0.05 if args.pair_skin is None else args.pair_skin)
+                                           None if route is not None else goal, args.n_primitives, args.n_candidates, **search)
         for v in range(args.n_gens if people is not None else 0):
             mine = range(v * P, (v + 1) * P)
             written = np.stack([np.arange(args.n_primitives) < int(res.n_valid[i]) for i in mine], 1)          # [K,P]: the primitives the files hold
@@ -257,8 +324,15 @@ def main(argv=None):
         for i in range(nseq):
             last = int(res.n_valid[i]) - 1
             along = "" if field is None else " ({:.3f} m along the walkable raster)".format(float(res.geo_dist[last, i]))
-            print("[INFO] {}: {} primitives, final distance to the goal {:.3f} m{}, colliding choices {}".format(
-                "variant {}".format(i) if people is None else "variant {} person {}".format(i // P, i % P), last + 1, float(res.goal_dist[last, i]), along, int((res.status[:last + 1, i] & 1).sum())))
+            aim = "goal"
+            if route is not None:          # goal_dist[k] is the distance to the waypoint primitive k was scored against
+                scored = int(res.route_cursor[last - 1, i]) if last > 0 else 0
+                aim = "goal" if scored == int(route.count[i]) - 1 else "waypoint {} of {} the last primitive aimed at".format(scored + 1, int(route.count[i]))
+            print("[INFO] {}: {} primitives, final distance to the {} {:.3f} m{}, colliding choices {}".format(
+                "variant {}".format(i) if people is None else "variant {} person {}".format(i // P, i % P), last + 1, aim, float(res.goal_dist[last, i]), along, int((res.status[:last + 1, i] & 1).sum())))
+            if route is not None:
+                print("[INFO] variant {}{}: passed {} of {} waypoints on the way".format(
+                    i // P, "" if people is None else " person {}".format(i % P), int(res.route_cursor[last, i]), int(route.count[i]) - 1))
             if obstacles is not None:
                 ch = np.asarray(res.choice[:last + 1, i], np.int64)
                 clear = np.asarray(res.clearance)[np.arange(last + 1), i, ch]

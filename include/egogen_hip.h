@@ -40,6 +40,7 @@ extern "C" {
 #define EGX_MAX_GROUP 32       /* people of one group of egx_primitive_select_joint: their chosen tracks (18 x 32 xy, 4.6 KB) are one
                                   workgroup's table in LDS */
 #define EGX_MAX_SWEEPS 8       /* Gauss-Seidel sweeps of egx_primitive_select_joint */
+#define EGX_MAX_WAYPOINTS 16   /* waypoints of one route of egx_route_advance and egx_route_metrics */
 #define EGX_GEODESIC_OFF 1.0e4f /* metres: what a geodesic field gives where none of the four surrounding cells holds a distance */
 #define EGX_GEODESIC_BATCH 8    /* passes egx_geodesic_field launches between two reads of its flag */
 #define EGX_NUM_BETAS 10
@@ -1267,6 +1268,47 @@ int egx_crowd_metrics(const float* blended_marker, const float* pelvis_loc, cons
                       const int32_t* motion_start_host, int num_motions, const int32_t* group_start, const int32_t* group_member,
                       const int32_t* pair_start, const int32_t* group_start_host, int num_groups, int num_pairs, int max_frames,
                       double body_radius, int hold, double* clearance, double* marker_dist, int32_t* pair_list, void* stream);
+
+/* egx_route_metrics - did a motion follow its route: the ordered rule of egx_route_advance (below) at frame resolution over the
+ * whole motion.  waypoints [num_motions,max_waypoints,3] (world, float32, padded), count [num_motions] the live waypoints of each
+ * motion (clamped into [0, max_waypoints]; 0: the motion has no route).  With h_f(j) = |p_f - w_j|_xy in float64 and s_0 = 0,
+ * s_j = pass_frame[j-1]:
+ *   pass_frame   [num_motions,max_waypoints] = the first f >= s_j with h_f(j) < pass_radius for j < count - 1 where j - 1 was passed
+ *                (the next waypoint may be passed at that same frame), else -1; the last waypoint is arrived at, never passed: -1
+ *   approach_min [num_motions,max_waypoints] = min_{f >= s_j} h_f(j) for j < count where j - 1 was passed, else NaN
+ *   waypoints_passed [num_motions] = #{j : pass_frame[j] >= 0}
+ * One workgroup per motion; the minima do not depend on an order.  EGX_ERR_ARG, and nothing launched, for a NULL pointer, a motion
+ * without frames, max_waypoints outside [1, EGX_MAX_WAYPOINTS], a negative or non-finite pass_radius. */
+int egx_route_metrics(const float* blended_marker, const float* pelvis_loc, const float* transf_rotmat, const float* transf_transl,
+                      int num_primitives, const int32_t* frame_src, int num_frames, const int32_t* motion_start,
+                      const int32_t* motion_start_host, int num_motions, const float* waypoints, const int32_t* count,
+                      int max_waypoints, double pass_radius, int32_t* pass_frame, double* approach_min, int32_t* waypoints_passed,
+                      void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Waypoint routes of the primitive search (csrc/genop_route.hip, egogen_amd/route.py)
+ * ------------------------------------------------------------------------------------------- */
+/* egx_route_advance - one launch per primitive of `generate_sequence_to_goal(route=)`, after egx_primitive_advance_select: moves the
+ * cursor of every sequence along its route and rewrites the live goal (and field index) every kernel of the next primitive reads.
+ * It reads only what the hand-off recorded for the primitive: pelvis_loc [b,20,3], transf_rotmat [b,3,3], transf_transl [b,3]; and
+ * waypoints [b,max_waypoints,3] (world, padded), count [b] (clamped into [1, max_waypoints]), cursor [b] (clamped into
+ * [0, count - 1]), field_of [b,max_waypoints] (the field of every waypoint; read only with field_index).  For sequence g with
+ * cursor c, count n, waypoints w, in float32 with one rounding per operation:
+ *   x_f = fma(R2, p2, fma(R1, p1, R0 * p0)) + T0, y_f likewise with row 1 of R, for the predicted frames f = 2 .. 19
+ *   h(f, j) = sqrt(dx * dx + dy * dy), dx = x_f - w_j.x, dy = y_f - w_j.y
+ *   route_goal[g] = w[c] and route_pass_dist[g] = min_f h(f, c), both before the update
+ *   cascade: f0 = 2; while c < n - 1: the first f in [f0, 19] with h(f, c) < pass_radius; none: stop; else c += 1, f0 = f (the
+ *   next waypoint may be passed at that same frame).  The last waypoint is never passed.
+ * A NaN in any of the 18 positions: the cursor stays and route_pass_dist is NaN.  Written: cursor[g] and route_cursor[g] (the cursor
+ * after the primitive), goal[g] = w[c] (bitwise), field_index[g] = field_of[g][c] where field_index is not NULL, and reached[g] = 0
+ * unless the cursor before the update stood on the last waypoint (the selection wrote that flag against an intermediate point).
+ * One wave per sequence, a frame per lane; the first frame is a ballot and the distance a minimum, neither depends on an order; no
+ * atomics.  A plain launch on `stream`.  EGX_ERR_ARG for a NULL pointer (field_of and field_index may be NULL; field_index needs
+ * field_of), num_sequences < 1, max_waypoints outside [1, EGX_MAX_WAYPOINTS], a negative or NaN pass_radius. */
+int egx_route_advance(const float* pelvis_loc, const float* transf_rotmat, const float* transf_transl, const float* waypoints,
+                      const int32_t* count, const int32_t* field_of, int num_sequences, int max_waypoints, float pass_radius,
+                      int32_t* cursor, float* goal, int32_t* field_index, int32_t* reached, int32_t* route_cursor, float* route_goal,
+                      float* route_pass_dist, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * PPO rollout glue
