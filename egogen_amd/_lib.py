@@ -228,6 +228,21 @@ SIGNATURES = {
                                             [C.c_void_p] * 13 +
                                             [C.c_void_p, C.c_void_p, C.c_float, C.c_int, C.c_int, C.c_int, C.c_void_p] +
                                             [C.c_void_p] * 4 + [C.c_int] * 4 + [C.c_float] * 3 + [C.c_void_p] * 4),
+    # markers_proj, Y_gen, reproj_factor, R0, T0, num_sequences, rows_per_sequence, obs_markers, obs_count, obs_index, num_sets,
+    # max_obstacles, num_frames, frame0, skin, frame_clearance, stream
+    "egx_obstacle_marker_clearance": (C.c_int, [C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_int, C.c_int] +
+                                      [C.c_void_p] * 3 + [C.c_int] * 4 + [C.c_float, C.c_void_p, C.c_void_p]),
+    # the *_field entries' arguments up to field_index, then: frame_clearance, obstacle_weight, margin, obs_term, obs_clearance, obs_hit,
+    # stream
+    "egx_primitive_select_obstacle_markers": (C.c_int, [C.c_void_p] * 3 + [C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 6 +
+                                              [C.POINTER(C.c_float), C.c_float, C.c_float, C.c_float, C.c_int, C.c_int] + [C.c_void_p] * 7 +
+                                              [C.c_void_p, C.c_void_p, C.c_float, C.c_int, C.c_int, C.c_int, C.c_void_p] +
+                                              [C.c_void_p, C.c_float, C.c_float] + [C.c_void_p] * 4),
+    "egx_primitive_beam_select_obstacle_markers": (C.c_int, [C.c_void_p] * 3 + [C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 6 +
+                                                   [C.POINTER(C.c_float), C.c_float, C.c_float, C.c_float, C.c_int, C.c_int, C.c_int] +
+                                                   [C.c_void_p] * 13 +
+                                                   [C.c_void_p, C.c_void_p, C.c_float, C.c_int, C.c_int, C.c_int, C.c_void_p] +
+                                                   [C.c_void_p, C.c_float, C.c_float] + [C.c_void_p] * 4),
     # joints, joints_per_body, R0, T0, goal, cost, cost_terms, colliding, num_sequences, num_candidates, group_start, group_member,
     # num_groups, sweeps, pair_weight, margin, body_radius, goal_thresh, then the twelve outputs and the stream
     "egx_primitive_select_joint": (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 6 + [C.c_int, C.c_int, C.c_void_p, C.c_void_p,

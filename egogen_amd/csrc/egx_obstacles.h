@@ -1,6 +1,7 @@
 // Moving obstacles of the primitive search (genop.hip): S sets of up to EGX_MAX_OBSTACLES tracks, a track a world xy per absolute
 // frame and a radius: a person as a vertical cylinder.  The device functions behind the obstacle phase of the selection kernels:
-// the window of one primitive staged into LDS, and the clearance of one point against one frame of that window.
+// the window of one primitive staged into LDS, and the clearance of one point against one frame of that window.  With the marker
+// model of recorded tracks the phase reads its frame clearances from a table instead (frame_clearance below) and stages nothing.
 #pragma once
 #include "egx_common.h"
 
@@ -17,6 +18,8 @@ struct ObstaclesDev {
   float* term;          // [rows] outputs of the phase
   float* clearance;     // [rows]
   int* hit;             // [rows]
+  const float* frame_clearance;  // [rows,18] c_t of every row and predicted frame, written ahead of the launch by
+                                 // egx_obstacle_marker_clearance (genop_obstacle_markers.hip): the marker model; null: cylinders
 };
 
 // The window of group g's set for the primitive that starts at absolute frame ob.frame0, by the whole workgroup: s_x / s_y [f][o] the

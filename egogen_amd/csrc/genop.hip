@@ -8,7 +8,9 @@
 // the scoring); the entries without a field launch the same kernels with a null field.  With moving obstacles
 // (egx_primitive_select_obstacles, egx_primitive_beam_select_obstacles; egx_obstacles.h) a third phase adds the obstacle term to
 // the cost and the hit to the collision of every row (obstacle_group); the other entries launch the same kernels with a null
-// obstacle descriptor.  Device code is shared (advance_body, score_group, field_row_cost, obstacle_group, key_before); so is the host side: the three hand-off entries go through advance_entry and the selection entries
+// obstacle descriptor.  With the marker model of recorded tracks (egx_primitive_select_obstacle_markers,
+// egx_primitive_beam_select_obstacle_markers) that phase reads its frame clearances from the table egx_obstacle_marker_clearance
+// (genop_obstacle_markers.hip) wrote: kernels of their own, compile-time variants of the same bodies.  Device code is shared (advance_body, score_group, field_row_cost, obstacle_group, key_before); so is the host side: the three hand-off entries go through advance_entry and the selection entries
 // through select_entry (common checks, common fields, launch check), and each entry states only the checks, fields and launch
 // that are its own.
 //
@@ -365,23 +367,34 @@ __device__ __forceinline__ float wave_min(float v) {   // every lane's partner c
 // the fixed wave_sum tree, divided by 18; clearance by wave_min.  Lane 0 writes obs_term / obs_clearance / obs_hit and the row's
 // cost = cost_prev + w_obs * term (cost_prev read back: what the launch wrote so far), both rounded on their own, and hands
 // (n, row, term, cost, hit) to update(), which redoes the LDS key tables of the row.  Ends on a barrier.
-template <class Update>
+//
+// TABLE (the marker model of recorded tracks, entries *_obstacle_markers): nothing is staged and c_t is read from ob.frame_clearance
+// [rows,18], which egx_obstacle_marker_clearance (genop_obstacle_markers.hip) wrote ahead of the launch; everything after c_t is the
+// same code.  A compile-time variant and not a branch: the cylinder instantiation is the code as it stood before the table came.
+template <bool TABLE, class Update>
 __device__ __forceinline__ void obstacle_group(const SelectArgs& p, const ObstaclesDev& ob, int g, int M, Update update) {
   __shared__ float s_ox[EGX_OBS_FRAMES][EGX_MAX_OBSTACLES], s_oy[EGX_OBS_FRAMES][EGX_MAX_OBSTACLES], s_rr[EGX_MAX_OBSTACLES];
   const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
-  const int cnt = egx_obstacles_stage(ob, g, s_ox, s_oy, s_rr);
-  __syncthreads();
+  int cnt = 0;
+  if constexpr (!TABLE) {
+    cnt = egx_obstacles_stage(ob, g, s_ox, s_oy, s_rr);
+    __syncthreads();
+  }
   for (int n = w; n < M; n += SEL_WAVES) {
     const size_t row = (size_t)g * M + n;
     float c = __builtin_inff(), pen = 0.f;
     int bad = 0;
     if (lane < EGX_OBS_FRAMES) {
-      const float* R0 = p.R0 + row * 9;
-      const float* T0 = p.T0 + row * 3;
-      const float* j = p.joints + (row * NT + THIS + lane) * p.jpb * 3;
-      const float x = fmaf(R0[2], j[2], fmaf(R0[1], j[1], R0[0] * j[0])) + T0[0];
-      const float y = fmaf(R0[5], j[2], fmaf(R0[4], j[1], R0[3] * j[0])) + T0[1];
-      c = egx_obstacle_clearance(x, y, cnt, s_ox[lane], s_oy[lane], s_rr);
+      if constexpr (TABLE) {
+        c = ob.frame_clearance[row * EGX_OBS_FRAMES + lane];
+      } else {
+        const float* R0 = p.R0 + row * 9;
+        const float* T0 = p.T0 + row * 3;
+        const float* j = p.joints + (row * NT + THIS + lane) * p.jpb * 3;
+        const float x = fmaf(R0[2], j[2], fmaf(R0[1], j[1], R0[0] * j[0])) + T0[0];
+        const float y = fmaf(R0[5], j[2], fmaf(R0[4], j[1], R0[3] * j[0])) + T0[1];
+        c = egx_obstacle_clearance(x, y, cnt, s_ox[lane], s_oy[lane], s_rr);
+      }
       bad = isnan(c) ? 1 : 0;
       pen = bad ? c : fmaxf(0.f, egx_sub(ob.margin, c));
     }
@@ -405,7 +418,10 @@ __device__ __forceinline__ void obstacle_group(const SelectArgs& p, const Obstac
 
 }  // namespace
 
-__global__ __launch_bounds__(SEL_BLK) void egx_primitive_select_kernel(SelectArgs p, ObstaclesDev ob) {
+namespace {
+// the body of the greedy selection kernels; TABLE: the obstacle phase reads its frame clearances from a table (obstacle_group)
+template <bool TABLE>
+__device__ __forceinline__ void select_body(const SelectArgs& p, const ObstaclesDev& ob) {
   __shared__ float s_feet[SEL_WAVES][NT][NF * 3];   // blended feet markers of the row a wave is scoring
   __shared__ float s_cost[MAXC], s_dist[MAXC];
   __shared__ int s_cls[MAXC];
@@ -425,7 +441,7 @@ __global__ __launch_bounds__(SEL_BLK) void egx_primitive_select_kernel(SelectArg
     __syncthreads();
   }
   if (ob.term)                                 // workgroup-uniform; the costs of the rows are visible: a barrier precedes
-    obstacle_group(p, ob, g, N, [&](int n, size_t row, float term, float c, bool hit) {
+    obstacle_group<TABLE>(p, ob, g, N, [&](int n, size_t row, float term, float c, bool hit) {
       const bool finite = !(s_cls[n] & 2) && isfinite(term) && isfinite(c);
       const int coll = (s_cls[n] & 1) | (hit ? 1 : 0);
       p.colliding[row] = coll;
@@ -452,12 +468,20 @@ __global__ __launch_bounds__(SEL_BLK) void egx_primitive_select_kernel(SelectArg
     }
   }
 }
+}  // namespace
+
+__global__ __launch_bounds__(SEL_BLK) void egx_primitive_select_kernel(SelectArgs p, ObstaclesDev ob) { select_body<false>(p, ob); }
+__global__ __launch_bounds__(SEL_BLK) void egx_primitive_select_obstacle_markers_kernel(SelectArgs p, ObstaclesDev ob) {
+  select_body<true>(p, ob);
+}
 
 // ---- beam: scoring and top-W selection -------------------------------------------------------------------------------------
 // One workgroup per sequence scores its W * N rows as above, then every row counts the rows whose path key precedes its own:
 // (non-finite, colliding nodes on the path, accumulated cost, row index) is a total order, so that count is the row's rank
 // whatever the order of the comparisons, and the rows of rank < W are the beam, slot = rank.
-__global__ __launch_bounds__(SEL_BLK) void egx_primitive_beam_select_kernel(SelectArgs p, BeamArgs q, ObstaclesDev ob) {
+namespace {
+template <bool TABLE>
+__device__ __forceinline__ void beam_select_body(const SelectArgs& p, const BeamArgs& q, const ObstaclesDev& ob) {
   __shared__ float s_feet[SEL_WAVES][NT][NF * 3];
   __shared__ float s_path[MAXC], s_q[MAXC], s_dist[MAXC];   // path cost (0 where non-finite), q and dist of every row
   __shared__ int s_key[MAXC], s_flag[MAXC];                 // (non-finite, colliding nodes) in one int; bit 0 collides, bit 1 non-finite
@@ -487,7 +511,7 @@ __global__ __launch_bounds__(SEL_BLK) void egx_primitive_beam_select_kernel(Sele
     __syncthreads();
   }
   if (ob.term)                                 // as in the greedy kernel; q gains the product the cost gained, a hit is a colliding node
-    obstacle_group(p, ob, g, M, [&](int n, size_t row, float term, float c, bool hit) {
+    obstacle_group<TABLE>(p, ob, g, M, [&](int n, size_t row, float term, float c, bool hit) {
       const bool row_finite = !(s_flag[n] & 2) && isfinite(term) && isfinite(c);
       const float path = q.acc[(size_t)g * W + n / N] + (row_finite ? c : 0.f);
       const bool finite = row_finite && isfinite(path);
@@ -518,6 +542,14 @@ __global__ __launch_bounds__(SEL_BLK) void egx_primitive_beam_select_kernel(Sele
       q.reached[o] = (s_dist[tid] < p.goal_thresh) ? 1 : 0;
     }
   }
+}
+}  // namespace
+
+__global__ __launch_bounds__(SEL_BLK) void egx_primitive_beam_select_kernel(SelectArgs p, BeamArgs q, ObstaclesDev ob) {
+  beam_select_body<false>(p, q, ob);
+}
+__global__ __launch_bounds__(SEL_BLK) void egx_primitive_beam_select_obstacle_markers_kernel(SelectArgs p, BeamArgs q, ObstaclesDev ob) {
+  beam_select_body<true>(p, q, ob);
 }
 
 // ---- beam: the returned path --------------------------------------------------------------------------------------------
@@ -656,7 +688,8 @@ int greedy_select(const float* Y_gen, const float* x0, const float* x1, int x_ld
                       pene_thres, goal_thresh, reproj_factor, num_sequences, num_candidates, cost, cost_terms, colliding, field, obs,
                       [&](SelectArgs& p, const ObstaclesDev& ob) {
     p.choice = choice; p.status = status; p.reached = reached; p.goal_dist = goal_dist;
-    hipLaunchKernelGGL(egx_primitive_select_kernel, dim3(num_sequences), dim3(SEL_BLK), 0, static_cast<hipStream_t>(stream), p, ob);
+    hipLaunchKernelGGL(ob.frame_clearance ? egx_primitive_select_obstacle_markers_kernel : egx_primitive_select_kernel, dim3(num_sequences),
+                       dim3(SEL_BLK), 0, static_cast<hipStream_t>(stream), p, ob);
   });
 }
 
@@ -678,7 +711,8 @@ int beam_select(const float* Y_gen, const float* x0, const float* x1, int x_ld, 
                       pene_thres, goal_thresh, reproj_factor, num_sequences, beam_width * num_candidates, cost, cost_terms, colliding,
                       field, obs, [&](SelectArgs& p, const ObstaclesDev& ob) {
     const BeamArgs q{acc, ncoll, beam_row, parent, acc_out, ncoll_out, path_cost, beam_status, goal_dist, reached, beam_width, num_candidates};
-    hipLaunchKernelGGL(egx_primitive_beam_select_kernel, dim3(num_sequences), dim3(SEL_BLK), 0, static_cast<hipStream_t>(stream), p, q, ob);
+    hipLaunchKernelGGL(ob.frame_clearance ? egx_primitive_beam_select_obstacle_markers_kernel : egx_primitive_beam_select_kernel,
+                       dim3(num_sequences), dim3(SEL_BLK), 0, static_cast<hipStream_t>(stream), p, q, ob);
   });
 }
 
@@ -708,6 +742,26 @@ extern "C" int egx_primitive_select_field(const float* Y_gen, const float* x0, c
                        pene_thres, goal_thresh, reproj_factor, num_sequences, num_candidates, choice, status, reached, goal_dist, cost,
                        cost_terms, colliding, GeoFieldDev{field_dist, field_origin, field_index, field_cell, field_H, field_W, num_fields},
                        nullptr, stream);
+}
+
+// egx_primitive_select_field with the marker model of recorded tracks: the obstacle phase on a table of frame clearances
+extern "C" int egx_primitive_select_obstacle_markers(const float* Y_gen, const float* x0, const float* x1, int x_ld, const float* joints,
+                                                     int joints_per_body, const float* markers_proj, const float* R0, const float* T0,
+                                                     const int32_t* pene_count, const float* goal, const int32_t* feet_marker_idx,
+                                                     const float* weights, float pene_thres, float goal_thresh, float reproj_factor,
+                                                     int num_sequences, int num_candidates, int32_t* choice, int32_t* status,
+                                                     int32_t* reached, float* goal_dist, float* cost, float* cost_terms, int32_t* colliding,
+                                                     const float* field_dist, const float* field_origin, float field_cell, int field_H,
+                                                     int field_W, int num_fields, const int32_t* field_index, const float* frame_clearance,
+                                                     float obstacle_weight, float margin, float* obs_term, float* obs_clearance,
+                                                     int32_t* obs_hit, void* stream) {
+  EGX_REQUIRE(frame_clearance, "null input");
+  const ObstaclesDev obs{nullptr, nullptr, nullptr, nullptr, 1, 0, 1, 0, obstacle_weight, margin, 0.f, obs_term, obs_clearance, obs_hit,
+                         frame_clearance};
+  return greedy_select(Y_gen, x0, x1, x_ld, joints, joints_per_body, markers_proj, R0, T0, pene_count, goal, feet_marker_idx, weights,
+                       pene_thres, goal_thresh, reproj_factor, num_sequences, num_candidates, choice, status, reached, goal_dist, cost,
+                       cost_terms, colliding, GeoFieldDev{field_dist, field_origin, field_index, field_cell, field_H, field_W, num_fields},
+                       &obs, stream);
 }
 
 // extends egx_primitive_select_field
@@ -771,6 +825,28 @@ extern "C" int egx_primitive_beam_select_field(const float* Y_gen, const float* 
                      pene_thres, goal_thresh, reproj_factor, num_sequences, beam_width, num_candidates, acc, ncoll, cost, cost_terms,
                      colliding, beam_row, parent, acc_out, ncoll_out, path_cost, beam_status, goal_dist, reached,
                      GeoFieldDev{field_dist, field_origin, field_index, field_cell, field_H, field_W, num_fields}, nullptr, stream);
+}
+
+// egx_primitive_beam_select_field with the marker model of recorded tracks
+extern "C" int egx_primitive_beam_select_obstacle_markers(const float* Y_gen, const float* x0, const float* x1, int x_ld, const float* joints,
+                                                          int joints_per_body, const float* markers_proj, const float* R0, const float* T0,
+                                                          const int32_t* pene_count, const float* goal, const int32_t* feet_marker_idx,
+                                                          const float* weights, float pene_thres, float goal_thresh, float reproj_factor,
+                                                          int num_sequences, int beam_width, int num_candidates, const float* acc,
+                                                          const int32_t* ncoll, float* cost, float* cost_terms, int32_t* colliding,
+                                                          int32_t* beam_row, int32_t* parent, float* acc_out, int32_t* ncoll_out,
+                                                          float* path_cost, int32_t* beam_status, float* goal_dist, int32_t* reached,
+                                                          const float* field_dist, const float* field_origin, float field_cell,
+                                                          int field_H, int field_W, int num_fields, const int32_t* field_index,
+                                                          const float* frame_clearance, float obstacle_weight, float margin,
+                                                          float* obs_term, float* obs_clearance, int32_t* obs_hit, void* stream) {
+  EGX_REQUIRE(frame_clearance, "null input");
+  const ObstaclesDev obs{nullptr, nullptr, nullptr, nullptr, 1, 0, 1, 0, obstacle_weight, margin, 0.f, obs_term, obs_clearance, obs_hit,
+                         frame_clearance};
+  return beam_select(Y_gen, x0, x1, x_ld, joints, joints_per_body, markers_proj, R0, T0, pene_count, goal, feet_marker_idx, weights,
+                     pene_thres, goal_thresh, reproj_factor, num_sequences, beam_width, num_candidates, acc, ncoll, cost, cost_terms,
+                     colliding, beam_row, parent, acc_out, ncoll_out, path_cost, beam_status, goal_dist, reached,
+                     GeoFieldDev{field_dist, field_origin, field_index, field_cell, field_H, field_W, num_fields}, &obs, stream);
 }
 
 // extends egx_primitive_beam_select_field

@@ -14,13 +14,14 @@
 //
 // No float atomics, no spin waits, nothing passes between workgroups within a launch, every loop bound is a launch argument or a
 // constant: a group's outputs are the same bits in any batch.  A translation unit of its own, for the reason genop_joint.hip gives:
-// nothing here is compiled together with the selection kernels or with the cylinder kernel; the expression of blend_marker
-// (genop.hip) is stated here again.
+// nothing here is compiled together with the selection kernels or with the cylinder kernel; the blend, the world marker and the
+// squared distance are those of egx_markers.h, shared with the marker model of recorded tracks (genop_obstacle_markers.hip).
 #include "egx_joint_sweep.h"
+#include "egx_markers.h"
 
 namespace {
 
-constexpr int NMK = 67, MD = NMK * 3;
+constexpr int NMK = EGX_MK;
 constexpr int DIST_WAVES = 9, DIST_BLK = DIST_WAVES * 64;   // 18 frames: two per wave
 constexpr int TILE = 8;                                      // rows of the second member per workgroup
 constexpr int RB = 4;                                        // of which a lane holds this many in registers at a time
@@ -43,35 +44,14 @@ struct DistArgs {
   int* row_bad;               // [rows]
 };
 
-__device__ __forceinline__ float blend_marker(float rf, float proj, float pred) { return rf * proj + (1.f - rf) * pred; }
-
-// world marker a of row r at frame t (2..19): the blended local marker in the row's frame, pelvis_xy's nesting extended to z;
-// .w = 1 where a coordinate is not finite
+// world marker a of row r at frame t (2..19) of the launch's rows (egx_markers.h)
 __device__ __forceinline__ float4 world_marker(const DistArgs& p, size_t r, int t, int a) {
-  const size_t rows = (size_t)p.b * p.N;
-  const float* pr = p.markers_proj + (r * NT + t) * MD + 3 * a;
-  const float* pd = p.Y_gen + ((size_t)(t - THIS) * rows + r) * MD + 3 * a;
-  const float* R0 = p.R0 + r * 9;
-  const float* T0 = p.T0 + r * 3;
-  const float m0 = blend_marker(p.rf, pr[0], pd[0]), m1 = blend_marker(p.rf, pr[1], pd[1]), m2 = blend_marker(p.rf, pr[2], pd[2]);
-  float4 v;
-  v.x = fmaf(R0[2], m2, fmaf(R0[1], m1, R0[0] * m0)) + T0[0];
-  v.y = fmaf(R0[5], m2, fmaf(R0[4], m1, R0[3] * m0)) + T0[1];
-  v.z = fmaf(R0[8], m2, fmaf(R0[7], m1, R0[6] * m0)) + T0[2];
-  v.w = (isfinite(v.x) && isfinite(v.y) && isfinite(v.z)) ? 0.f : 1.f;
-  return v;
+  return egx_world_marker(p.markers_proj, p.Y_gen, p.R0, p.T0, (size_t)p.b * p.N, p.rf, r, t, a);
 }
 
 // the world markers of the 18 predicted frames of row r into s [18][67], by the whole workgroup; the caller's barrier follows
 __device__ __forceinline__ void stage_row(const DistArgs& p, size_t r, float4 (*s)[NMK]) {
   for (int e = threadIdx.x; e < NF * NMK; e += DIST_BLK) s[e / NMK][e % NMK] = world_marker(p, r, THIS + e / NMK, e % NMK);
-}
-
-// the squared distance of two world markers: three rounded differences, three rounded squares, (dx^2 + dy^2) + dz^2 in that order,
-// no contraction.  The same bits with the two markers exchanged.
-__device__ __forceinline__ float dist2(const float4& a, const float4& b) {
-  const float dx = egx_sub(a.x, b.x), dy = egx_sub(a.y, b.y), dz = egx_sub(a.z, b.z);
-  return egx_add(egx_add(egx_mul(dx, dx), egx_mul(dy, dy)), egx_mul(dz, dz));
 }
 
 // local pair q of a group of P, lexicographic (a, b), a < b  <->  (a, b)

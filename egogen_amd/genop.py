@@ -11,7 +11,9 @@ egx_beam_backtrack).  With `geodesic=` (a `GeodesicField`, egogen_amd/geodesic.p
 along the walkable raster of the scene instead of the straight line (entries egx_primitive_select_field,
 egx_primitive_beam_select_field).  With `obstacles=` (a `MovingObstacles`, egogen_amd/obstacles.py) either search also avoids
 other people's recorded tracks: a clearance term in the cost and a veto on overlap (entries egx_primitive_select_obstacles,
-egx_primitive_beam_select_obstacles).  With `groups=` (ids, or a `PersonGroups`, egogen_amd/crowd.py) the sequences of one group of the
+egx_primitive_beam_select_obstacles; with `obstacle_model="markers"` the recorded people are their 67 world markers per frame: entry
+egx_obstacle_marker_clearance, csrc/genop_obstacle_markers.hip, ahead of egx_primitive_select_obstacle_markers /
+egx_primitive_beam_select_obstacle_markers).  With `groups=` (ids, or a `PersonGroups`, egogen_amd/crowd.py) the sequences of one group of the
 greedy search see each other: after the selection the members choose again against each other's current choices (entry
 egx_primitive_select_joint, csrc/genop_joint.hip; with `pair_model="markers"` the people are their 67 blended markers, not
 cylinders: entries egx_pair_marker_dist, egx_primitive_select_joint_markers, csrc/genop_joint_markers.hip), and the hand-off
@@ -53,6 +55,7 @@ T_ALL, T_PRED, NM3, XB = 20, 18, 201, 93
 MAX_CANDIDATES = 256        # EGX_MAX_CANDIDATES of include/egogen_hip.h
 MAX_BEAM = 32               # EGX_MAX_BEAM
 NULL_FIELD = (None, None, 0.0, 0, 0, 0, None)      # the field arguments of a selection entry without a field
+OBSTACLE_MODELS = ("cylinder", "markers")       # what a recorded person of `obstacles=` is: a cylinder round the pelvis, or its 67 world markers
 SEARCH_WEIGHTS = {"goal": 1.0, "skate": 1.0, "floor": 1.0, "pene": 1.0, "face": 0.0}
 GENERATE_PPO_NOT_BUILT = ("generate_ppo is not built: nothing in the reference calls it, and its policy_model(X, obj_points=, "
                           "target_ori=, local_map=) signature belongs to no class in the tree")
@@ -157,7 +160,9 @@ class PrimitiveSequence:
     choice [K,b] the path's row within its W*N, status [K,b] the path node's bits (0: collides, 1: non-finite row, 2: non-finite
     hand-off); and beam_width, path_slot [K,b], parent / beam_row / path_cost / beam_status [K,b,W], which a greedy result has as
     None.  With `obstacles=`: obstacle_term [K,b,M] (metres), clearance [K,b,M] (metres, +inf for an empty set) and obstacle_hit
-    [K,b,M] of every row (M = N, or W*N for a beam), colliding then includes the hits; None without obstacles.
+    [K,b,M] of every row (M = N, or W*N for a beam), colliding then includes the hits; None without obstacles.  `search` then also
+    holds obstacle_model ("cylinder" / "markers") and obstacle_skin (metres); with "markers" clearance is the distance between the
+    nearest markers of the candidate and of a recorded person minus obstacle_skin, in 3-D.
     With `groups=` (S = joint_sweeps, G groups): groups [b] the ids; individual_choice [K,b] what the selection chose before the
     members saw each other (choice is the joint choice, choice_trace[:, -1]); pair_term / pair_clearance / joint_cost (metres, metres,
     cost) and pair_hit [K,S,b,N] of every row as evaluated in each sweep; choice_trace [K,S,b] the choices after each sweep;
@@ -413,12 +418,28 @@ class GAMMAPrimitiveComboGenOP:
                  s["goal_thresh"], s["rf"]) for x, R0, T0 in zip(s["xs"], R0s, T0s)]
 
     @staticmethod
+    def _clearance_lead(s, K, b, M, R0s, T0s, st):
+        """Per primitive the arguments of egx_obstacle_marker_clearance, the launch that goes before the selection with the marker
+        model of the obstacles (None without it); R0s / T0s: the frames of the rows at even and at odd k."""
+        if s.get("frame_clearance") is None:
+            return None
+        lead = [(_lib.ptr(s["lbs_out"]["markers"]), _lib.ptr(s["Y_gen"]), s["rf"], _lib.ptr(R0), _lib.ptr(T0), b, M, *s["obs_markers"])
+                for R0, T0 in zip(R0s, T0s)]
+        return [(*lead[k % 2], s["obs_frame0"] + T_PRED * k, s["obs_skin"], _lib.ptr(s["frame_clearance"]), st) for k in range(K)]
+
+    @staticmethod
     def _select_tail(s, K, base):
         """What follows the outputs of a selection entry, built once per loop -> (entry name, field arguments, per primitive the
         obstacle arguments): `base` and nothing; with a field `base`_field and the field; with obstacles `base`_obstacles, the field
-        (a null one without) and, for primitive k, the obstacles with frame0 = obstacle_frame0 + 18 k and the outputs' row k."""
+        (a null one without) and, for primitive k, the obstacles with frame0 = obstacle_frame0 + 18 k and the outputs' row k; with the
+        marker model of the obstacles `base`_obstacle_markers, the field, and the table, the two scalars and the outputs' row k."""
         if s["obstacles"] is None:
             return (base + "_field", s["field"], [()] * K) if s["field"] else (base, (), [()] * K)
+        if s.get("frame_clearance") is not None:      # the marker model: the phase reads the table the clearance launch wrote
+            w_obs, margin, _ = s["obs_scalars"]
+            obs = [(_lib.ptr(s["frame_clearance"]), w_obs, margin, _vp(s["obstacle_term"][k]), _vp(s["clearance"][k]),
+                    _vp(s["obstacle_hit"][k])) for k in range(K)]
+            return base + "_obstacle_markers", s["field"] or NULL_FIELD, obs
         obs = [(*s["obstacles"], s["obs_frame0"] + T_PRED * k, *s["obs_scalars"], _vp(s["obstacle_term"][k]), _vp(s["clearance"][k]),
                 _vp(s["obstacle_hit"][k])) for k in range(K)]
         return base + "_obstacles", s["field"] or NULL_FIELD, obs
@@ -467,7 +488,8 @@ class GAMMAPrimitiveComboGenOP:
                                   obstacle_margin: float = 0.5, body_radius: float = 0.3,
                                   obstacle_frame0: int = 0, groups=None, pair_weight: float = 1.0, pair_margin: float = 0.5,
                                   joint_sweeps: int = 2, policy=None, pair_model: str = "cylinder",
-                                  pair_skin: float = 0.05, route=None) -> PrimitiveSequence:
+                                  pair_skin: float = 0.05, route=None, obstacle_model: str = "cylinder",
+                                  obstacle_skin: float = 0.05) -> PrimitiveSequence:
         """`generate_sequence` steered to a goal through a scene by a greedy best-of-N search: for each of the `n_primitives`
         primitives, `n_candidates` candidates per sequence are generated, scored and the best one is kept; every candidate of the
         next primitive continues from it.  data / bparams / betas / reproj_factor / R0 / T0 as in `generate_sequence` (b seeds,
@@ -509,6 +531,22 @@ class GAMMAPrimitiveComboGenOP:
               stands at its first or last position.  The loop stays launches only.
             - obstacle_weight (1.0), obstacle_margin (0.5 m), body_radius (0.3 m, the searching body's own cylinder): stated
               choices, like the weights above: nobody has measured motion quality with them.
+            - obstacle_model: what a person of `obstacles` is.  "cylinder" (the default) is the model above: the same launches, the
+              same buffers.  "markers": a recorded person is the 67 world markers of each of its frames (`MovingObstacles` built with
+              markers: `from_sequences(..., markers=True)`, `from_rollout_files(..., markers=True)`, `from_tracks(..., markers=)`), a
+              candidate is its own 67 blended markers in the world, in 3-D, as in pair_model "markers".  Per primitive one launch
+              (egx_obstacle_marker_clearance, csrc/genop_obstacle_markers.hip) goes before the selection and writes c_t = the least
+              of the 67 x 67 marker distances to the nearest recorded person at that absolute frame minus obstacle_skin for every
+              row and predicted frame into a [b*M,18] table allocated once before the loop; the selection, greedy or beam
+              (egx_primitive_select_obstacle_markers, egx_primitive_beam_select_obstacle_markers), reads it, and cost term, veto,
+              order, the beam's accumulation and OBSTACLE_FIELDS are as above with that c_t: `clearance` is then the 3-D marker
+              distance minus the skin.  body_radius is not read by this model.  It combines with scene, geodesic, route, policy and
+              groups (either pair model) exactly as the cylinder model does; a policy that senses people still senses the tracks'
+              cylinders.  ValueError for an unknown model, "markers" without obstacles or with obstacles that hold no markers, a
+              negative or non-finite obstacle_skin.  Not built: marker boxes for `sense_people`, a skin per track, culling by
+              bounding volumes, vertex-level penetration.  The loop stays launches only.
+            - obstacle_skin (0.05 m): a recorded person's marker closer than this to one of the candidate's counts as contact.  The
+              evaluator's `touch_dist` (egogen_amd/metrics.py) by intent, like pair_skin.  A stated choice.
             - groups: None, or [b] integer ids (or a `PersonGroups`, egogen_amd/crowd.py): sequences with equal ids are the people of
               one scene and time line, at most 32 of them, and see each other.  The greedy search only (ValueError with beam_width
               > 1).  Per primitive, after the selection (plain, with a field or with obstacles), one more launch
@@ -589,6 +627,13 @@ class GAMMAPrimitiveComboGenOP:
                 raise TypeError(f"policy must be None or a PolicyProposal, got {type(policy).__name__}")
             check_beam(W)
             policy.counts(N)
+        if obstacle_model not in OBSTACLE_MODELS:
+            raise ValueError(f"obstacle_model must be one of {OBSTACLE_MODELS}, got {obstacle_model!r}")
+        if not (float(obstacle_skin) >= 0 and np.isfinite(float(obstacle_skin))):
+            raise ValueError(f"obstacle_skin must be finite and not negative, got {obstacle_skin}")
+        if obstacle_model == "markers" and (obstacles is None or getattr(obstacles, "markers", None) is None):
+            raise ValueError('obstacle_model="markers" needs obstacles= that carry markers (MovingObstacles.from_sequences / '
+                             'from_rollout_files with markers=True, or from_tracks(..., markers=))')
         people = _person_groups(groups, data, W, pair_weight, pair_margin, body_radius, joint_sweeps, pair_model, pair_skin, N)
         if goal_thresh is None:
             goal_thresh = self.testconfig.get("goal_thresh", 0.1)
@@ -635,6 +680,8 @@ class GAMMAPrimitiveComboGenOP:
                 raise ValueError(f"obstacle_margin and body_radius must not be negative and obstacle_weight finite, got "
                                  f"{obstacle_margin}, {body_radius}, {obstacle_weight}")
             obs_args, obs_alive = obstacles.select_args(b)
+            if obstacle_model == "markers":
+                obs_marker_args, obs_marker_alive = obstacles.marker_args(b)
         rows_scene = None
         if isinstance(scene, SdfSceneSet):
             if agent_scene is None:
@@ -664,6 +711,9 @@ class GAMMAPrimitiveComboGenOP:
         if obs_args is not None:
             s.update({"obs_scalars": (float(obstacle_weight), float(obstacle_margin), float(body_radius)), "obs_frame0": int(obstacle_frame0),
                       "obstacle_term": rec(M), "clearance": rec(M), "obstacle_hit": rec(M, dtype=i32)})
+            if obstacle_model == "markers":      # the table of frame clearances, allocated once: the loop stays launches only
+                s.update({"obs_markers": obs_marker_args, "obs_markers_alive": obs_marker_alive, "obs_skin": float(obstacle_skin),
+                          "frame_clearance": torch.empty(b * M, T_PRED, device=dev, dtype=f32)})
         if people is not None:
             S, G = int(joint_sweeps), len(people.to(dev))
             trace = lambda *tail, dtype=f32: torch.empty(K, S, *tail, device=dev, dtype=dtype)
@@ -722,7 +772,7 @@ class GAMMAPrimitiveComboGenOP:
         if W > 1:
             search.update({k: s[k] for k in ("path_slot", "parent", "beam_row", "path_cost", "beam_status")}, beam_width=W)
         if obs_args is not None:
-            search.update({k: s[k] for k in PrimitiveSequence.OBSTACLE_FIELDS})
+            search.update({k: s[k] for k in PrimitiveSequence.OBSTACLE_FIELDS}, obstacle_model=obstacle_model, obstacle_skin=float(obstacle_skin))
         if people is not None:
             search.update({k: s[k] for k in PrimitiveSequence.JOINT_FIELDS + ("pair_model", "pair_skin")})
         if policy is not None:
@@ -755,6 +805,7 @@ class GAMMAPrimitiveComboGenOP:
         sel = self._select_lead(s, [s["R0"]] * 2, [s["T0"]] * 2)
         name, field, obs = self._select_tail(s, K, "egx_primitive_select")
         select = getattr(lib, name)
+        clear = self._clearance_lead(s, K, b, N, [s["R0"]] * 2, [s["T0"]] * 2, st)
         joint, policy, route = s.get("joint"), s.get("policy"), s.get("route")
         if route is not None:
             route_out = (_lib.ptr(s["route_state"]), _lib.ptr(s["goal"]), _lib.ptr(s["field_alive"]) if s["field"] else None)
@@ -773,6 +824,8 @@ class GAMMAPrimitiveComboGenOP:
             if policy is not None:
                 policy.launch(s, k, b, N, st, *sensed[k])
             self._primitive(s, k, s["pp"], st, s["R0"], s["T0"])
+            if clear is not None:
+                _lib.check(lib.egx_obstacle_marker_clearance(*clear[k]), "egx_obstacle_marker_clearance")
             _lib.check(select(
                 *sel[k % 2], b, N, _vp(s["choice"][k]), _vp(s["status"][k]), _vp(s["reached"][k]),
                 _vp(s["goal_dist"][k]), _vp(s["cost"][k]), _vp(s["cost_terms"][k]), _vp(s["colliding"][k]), *field, *obs[k], st), name)
@@ -802,10 +855,13 @@ class GAMMAPrimitiveComboGenOP:
         sel = self._select_lead(s, s["R0s"], s["T0s"])
         name, field, obs = self._select_tail(s, K, "egx_primitive_beam_select")
         select = getattr(lib, name)
+        clear = self._clearance_lead(s, K, b, W * N, s["R0s"], s["T0s"], st)
         for k in range(K):
             nxt = s["xs"][(k + 1) % 2]
             R0, T0, R0n, T0n = s["R0s"][k % 2], s["T0s"][k % 2], s["R0s"][(k + 1) % 2], s["T0s"][(k + 1) % 2]
             self._primitive(s, k, s["pp"], st, R0, T0)
+            if clear is not None:
+                _lib.check(lib.egx_obstacle_marker_clearance(*clear[k]), "egx_obstacle_marker_clearance")
             _lib.check(select(
                 *sel[k % 2], b, W, N, _vp(s["acc"][k]), _vp(s["ncoll"][k]), _vp(s["cost"][k]), _vp(s["cost_terms"][k]),
                 _vp(s["colliding"][k]), _vp(s["beam_row"][k]), _vp(s["parent"][k]), _vp(s["acc"][k + 1]), _vp(s["ncoll"][k + 1]),

@@ -15,6 +15,10 @@ straight-line one.  `--avoid a.pkl,b.pkl` (with `--goal`) makes the people of ea
 (`MovingObstacles.from_rollout_files`: a vertical cylinder of 0.3 m round each recorded pelvis track, frame 0 of every file being
 frame 0 of this run): a candidate pays for coming within 0.5 m of one and is vetoed where the cylinders overlap, so a crowd is
 composed by prioritised planning, one run per person; the driver prints the minimum clearance along each written path.
+`--obstacle-model markers` (with `--avoid`; default `cylinder`) makes those recorded people the 67 world markers of each of their
+frames, which the files already hold, and a candidate its own 67 blended markers (`generate_sequence_to_goal(obstacle_model=
+"markers")`): limbs avoid limbs, the greedy search and the beam alike; `--obstacle-skin M` (default 0.05 m) is the marker distance
+below which the two touch, and the printed clearance is then the least marker distance minus that skin.
 `--start x,y,yaw_deg` places the seed's world frame (the origin, facing +y, without it): two runs without it start inside each
 other.  `--people "x,y,yaw_deg:gx,gy,gz;..."` generates P people TOGETHER instead: each starts at its x,y,yaw_deg and walks to its own
 goal, and every variant of `--n-gens` is one group of those P people (`generate_sequence_to_goal(groups=)`, b = n_gens * P
@@ -114,6 +118,10 @@ def main(argv=None):
                         "becomes the distance along the raster, round obstacles (with --goal; independent of --scene)")
     parser.add_argument("--avoid", default=None, help="comma-separated motion_*.pkl files of earlier runs: their people are moving "
                         "obstacles of this one (with --goal)")
+    parser.add_argument("--obstacle-model", choices=("cylinder", "markers"), default="cylinder", help="what a recorded person of --avoid "
+                        "is: a cylinder round the pelvis track, or the 67 world markers of every frame of its file (with --avoid)")
+    parser.add_argument("--obstacle-skin", type=float, default=None, help="marker distance in metres below which a candidate touches a "
+                        "recorded person (with --obstacle-model markers; default 0.05)")
     parser.add_argument("--start", default=None, help="x,y,yaw_deg: where the seed stands in the world and which way it faces")
     parser.add_argument("--people", default=None, help='"x,y,yaw_deg:gx,gy,gz;...": P people with a start and a goal each, generated together; '
                         "every variant is one group who avoid each other (instead of --start / --goal; greedy search)")
@@ -164,6 +172,10 @@ def main(argv=None):
         parser.error("--pair-model markers needs --people: it is a model of how the people of a group see each other")
     if args.pair_skin is not None and (args.pair_model != "markers" or not (args.pair_skin >= 0 and np.isfinite(args.pair_skin))):
         parser.error("--pair-skin needs --pair-model markers and must be finite and not negative")
+    if args.avoid is None and args.obstacle_model != "cylinder":
+        parser.error("--obstacle-model markers needs --avoid: it is a model of the recorded people of those files")
+    if args.obstacle_skin is not None and (args.obstacle_model != "markers" or not (args.obstacle_skin >= 0 and np.isfinite(args.obstacle_skin))):
+        parser.error("--obstacle-skin needs --obstacle-model markers and must be finite and not negative")
     if args.goal is None and args.scene is not None:
         parser.error("--scene needs --goal")
     if args.goal is None and args.walkable is not None:
@@ -207,10 +219,11 @@ def main(argv=None):
     if args.avoid:          # before the models and the device: a bad file ends the run here
         from egogen_amd.obstacles import MovingObstacles
         try:
-            obstacles = MovingObstacles.from_rollout_files([f for f in args.avoid.split(",") if f])
+            obstacles = MovingObstacles.from_rollout_files([f for f in args.avoid.split(",") if f], markers=args.obstacle_model == "markers")
         except (OSError, ValueError, KeyError, pickle.UnpicklingError, EOFError, AttributeError) as e:
             raise SystemExit("--avoid {}: {!r}".format(args.avoid, e))
-        print("[INFO] avoiding {} people over {} frames".format(int(obstacles.count[0]), obstacles.num_frames))
+        print("[INFO] avoiding {} people over {} frames{}".format(int(obstacles.count[0]), obstacles.num_frames,
+                                                                  " by their markers" if args.obstacle_model == "markers" else ""))
     P = 1 if people is None else people.shape[0]
     route = None
     if way is not None:          # before the models and the device; sequence v * P + p walks the route of person p
@@ -310,7 +323,8 @@ def main(argv=None):
                 args.policy, proposal.counts(args.n_candidates)[1], args.n_candidates, proposal.counts(args.n_candidates)[0],
                 "; it senses the other people as holes of the polygon" if args.policy_sees_people else ""))
         search = dict(scene=scene, R0=R0, T0=T0, beam_width=args.beam_width, geodesic=field, obstacles=obstacles, groups=groups, policy=proposal,
-                      pair_model=args.pair_model, pair_skin=0.05 if args.pair_skin is None else args.pair_skin)
+                      pair_model=args.pair_model, pair_skin=0.05 if args.pair_skin is None else args.pair_skin,
+                      obstacle_model=args.obstacle_model, obstacle_skin=0.05 if args.obstacle_skin is None else args.obstacle_skin)
         if route is not None:
             search["route"] = route
         res = op.generate_sequence_to_goal(data.repeat(nseq, 1), bparams.repeat(nseq, 1), can["betas"].astype(np.float32),

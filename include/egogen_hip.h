@@ -993,6 +993,66 @@ int egx_primitive_beam_select_obstacles(const float* Y_gen, const float* x0, con
                                         int max_obstacles, int num_frames, int frame0, float obstacle_weight, float margin,
                                         float body_radius, float* obs_term, float* obs_clearance, int32_t* obs_hit, void* stream);
 
+/* The marker model of recorded tracks (csrc/genop_obstacle_markers.hip, the obstacle phase of csrc/genop.hip): the people of the
+ * obstacle sets are their 67 world markers per absolute frame instead of cylinders, a candidate row is its own 67 blended markers in
+ * the world.  Per primitive one launch of egx_obstacle_marker_clearance writes the frame clearances of every row, then
+ * egx_primitive_select_obstacle_markers or egx_primitive_beam_select_obstacle_markers stands where the *_obstacles entry stands.
+ *
+ * egx_obstacle_marker_clearance - rows = num_sequences * rows_per_sequence (N, or W * N for a beam), row r belongs to sequence
+ * g = r / rows_per_sequence; markers_proj / Y_gen / R0 / T0 as the selection of the same primitive reads them.  obs_markers
+ * [num_sets,max_obstacles,num_frames,67,3] world markers of each track per absolute frame (the host sends finite values), obs_count
+ * [num_sets], obs_index [num_sequences] or NULL as in egx_primitive_select_obstacles.  For row r and predicted frame f = 0..17, t = f + 2:
+ *   set   = obs_index ? clamp(obs_index[g], 0, num_sets - 1) : 0;  cnt = clamp(obs_count[set], 0, min(max_obstacles, EGX_MAX_OBSTACLES))
+ *   a     = clamp(frame0 + 2 + f, 0, num_frames - 1), evaluated in 64 bits
+ *   m_d   = fma(rf, markers_proj[(r*20 + t)*201 + 3i + d], (1 - rf) * Y_gen[((t-2)*rows + r)*201 + 3i + d]): 1 - rf rounded, its product
+ *           rounded, one fused multiply-add (the blend of egx_pair_marker_dist, every rounding stated)
+ *   W_c   = fma(R0[3c+2], m_2, fma(R0[3c+1], m_1, R0[3c] * m_0)) + T0[c], c = 0, 1, 2 (the world marker of egx_pair_marker_dist)
+ *   frame_clearance[r*18 + f] = sqrt(min over o < cnt and i, j < 67 of (dx^2 + dy^2) + dz^2) - skin, d. = W(r,t,i). - obs_markers[set,o,a,j].:
+ *           three rounded differences, three rounded squares, the two rounded sums in that order, no contraction; the minimum is
+ *           order-free; the correctly rounded root once, of the least square; one rounded subtraction.
+ * +inf for an empty set.  NaN where any of the 201 world coordinates of (r, t) is not finite: the row then ranks as non-finite in
+ * the selection, as a NaN pelvis does with cylinders.  A NaN obstacle coordinate drops out of the minimum (that marker is not
+ * there).  One workgroup of 576 threads per row: the row's 18 x 67 world markers staged once in LDS (19.3 KB), a wave per two
+ * frames, the tracks of a frame four at a time in registers.  No atomics, no waiting, nothing between workgroups.  EGX_ERR_ARG for
+ * a NULL input (obs_index may be NULL) or output, num_sequences < 1, rows_per_sequence outside [1, EGX_MAX_CANDIDATES],
+ * reproj_factor outside [0, 1], max_obstacles outside [0, EGX_MAX_OBSTACLES], num_frames < 1, num_sets < 1, a negative or
+ * non-finite skin (NaN included). */
+int egx_obstacle_marker_clearance(const float* markers_proj, const float* Y_gen, float reproj_factor, const float* R0, const float* T0,
+                                  int num_sequences, int rows_per_sequence, const float* obs_markers, const int32_t* obs_count,
+                                  const int32_t* obs_index, int num_sets, int max_obstacles, int num_frames, int frame0, float skin,
+                                  float* frame_clearance, void* stream);
+
+/* egx_primitive_select_obstacle_markers / egx_primitive_beam_select_obstacle_markers - egx_primitive_select_field /
+ * egx_primitive_beam_select_field (the same arguments up to field_index; field_dist may be NULL) with the obstacle phase of the
+ * *_obstacles entries on a table: c_t of row r and predicted frame t is frame_clearance[r*18 + t - 2] ([rows,18], as
+ * egx_obstacle_marker_clearance wrote it for the rows of this launch), and everything after c_t is that phase's arithmetic and
+ * order: clearance = min_t c_t; term = (sum_t max(0, margin - c_t)) / 18, one rounded difference per frame, the frame sum by the fixed
+ * tree of the wave reduction (lane t - 2 holds frame t, partners 32, 16, 8, 4, 2, 1 lanes up), one rounded division; hit =
+ * clearance < 0; a NaN frame makes term and clearance NaN and the row non-finite, not a hit; cost = cost_prev + obstacle_weight *
+ * term, one rounded product and one rounded addition; the beam's q gains the same product; colliding = the SDF collision OR hit.
+ * Kernels of their own, compile-time variants of the selection kernels: the cylinder entries run the code they ran before.
+ * EGX_ERR_ARG for a NULL frame_clearance or obstacle output and a negative or NaN margin, and the *_field entries' own. */
+int egx_primitive_select_obstacle_markers(const float* Y_gen, const float* x0, const float* x1, int x_ld, const float* joints,
+                                          int joints_per_body, const float* markers_proj, const float* R0, const float* T0,
+                                          const int32_t* pene_count, const float* goal, const int32_t* feet_marker_idx,
+                                          const float* weights, float pene_thres, float goal_thresh, float reproj_factor,
+                                          int num_sequences, int num_candidates, int32_t* choice, int32_t* status, int32_t* reached,
+                                          float* goal_dist, float* cost, float* cost_terms, int32_t* colliding, const float* field_dist,
+                                          const float* field_origin, float field_cell, int field_H, int field_W, int num_fields,
+                                          const int32_t* field_index, const float* frame_clearance, float obstacle_weight, float margin,
+                                          float* obs_term, float* obs_clearance, int32_t* obs_hit, void* stream);
+int egx_primitive_beam_select_obstacle_markers(const float* Y_gen, const float* x0, const float* x1, int x_ld, const float* joints,
+                                               int joints_per_body, const float* markers_proj, const float* R0, const float* T0,
+                                               const int32_t* pene_count, const float* goal, const int32_t* feet_marker_idx,
+                                               const float* weights, float pene_thres, float goal_thresh, float reproj_factor,
+                                               int num_sequences, int beam_width, int num_candidates, const float* acc,
+                                               const int32_t* ncoll, float* cost, float* cost_terms, int32_t* colliding,
+                                               int32_t* beam_row, int32_t* parent, float* acc_out, int32_t* ncoll_out, float* path_cost,
+                                               int32_t* beam_status, float* goal_dist, int32_t* reached, const float* field_dist,
+                                               const float* field_origin, float field_cell, int field_H, int field_W, int num_fields,
+                                               const int32_t* field_index, const float* frame_clearance, float obstacle_weight,
+                                               float margin, float* obs_term, float* obs_clearance, int32_t* obs_hit, void* stream);
+
 /* egx_primitive_select_joint - the joint step of the greedy search: the people of one scene and time line choose again against
  * each other's CURRENT choices.  One launch between a greedy selection entry (egx_primitive_select, _field or _obstacles, whose
  * cost [rows], cost_terms [rows,5], colliding [rows] it reads and whose choice / status / reached / goal_dist [num_sequences] it
@@ -1046,6 +1106,8 @@ int egx_primitive_select_joint(const float* joints, int joints_per_body, const f
  * t = 2..19.
  *   blended local marker a of row r at frame t, coordinate d (blend_marker of csrc/genop.hip, the same nesting: what the hand-off
  *           records):   m_d = rf * markers_proj[(r*20 + t)*201 + 3a + d] + (1 - rf) * Y_gen[((t-2)*rows + r)*201 + 3a + d]
+ *                       evaluated as fma(rf, proj, (1 - rf) * pred): 1 - rf rounded, its product rounded, one fused multiply-add
+ *                       (csrc/egx_markers.h, shared with egx_obstacle_marker_clearance)
  *   world marker        w_c = fma(R0[3c+2], m_2, fma(R0[3c+1], m_1, R0[3c] * m_0)) + T0[c], c = 0, 1, 2, R0 / T0 of row r
  *                       (the nesting of the pelvis of egx_primitive_select_joint, extended to z)
  *   bad row-frame       any of the 67 x 3 world coordinates of (r, t) is not finite
