@@ -247,6 +247,13 @@ SIGNATURES = {
     # num_groups, sweeps, pair_weight, margin, body_radius, goal_thresh, then the twelve outputs and the stream
     "egx_primitive_select_joint": (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 6 + [C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                              C.c_int, C.c_int] + [C.c_float] * 4 + [C.c_void_p] * 13),
+    # egx_primitive_select_joint's arguments with lookahead (int) and slack (float) after body_radius
+    "egx_primitive_select_joint_ahead": (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 6 + [C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                                   C.c_int, C.c_int] + [C.c_float] * 3 + [C.c_int, C.c_float, C.c_float] + [C.c_void_p] * 13),
+    # joints, joints_per_body, R0, T0, num_sequences, rows_per_sequence, obs_xy, obs_radius, obs_count, obs_index, num_sets,
+    # max_obstacles, num_frames, frame0, body_radius, lookahead, slack, frame_clearance, stream
+    "egx_obstacle_ahead_clearance": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 4 +
+                                     [C.c_int] * 4 + [C.c_float, C.c_int, C.c_float, C.c_void_p, C.c_void_p]),
     # markers_proj, Y_gen, reproj_factor, R0, T0, num_sequences, num_candidates, group_start, group_member, pair_start, num_groups,
     # num_pairs, pair_dist, row_bad, stream
     "egx_pair_marker_dist": (C.c_int, [C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 3 +

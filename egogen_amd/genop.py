@@ -17,7 +17,10 @@ egx_primitive_beam_select_obstacle_markers).  With `groups=` (ids, or a `PersonG
 greedy search see each other: after the selection the members choose again against each other's current choices (entry
 egx_primitive_select_joint, csrc/genop_joint.hip; with `pair_model="markers"` the people are their 67 blended markers, not
 cylinders: entries egx_pair_marker_dist, egx_primitive_select_joint_markers, csrc/genop_joint_markers.hip), and the hand-off
-continues from that joint choice.  With `policy=` (a
+continues from that joint choice.  With `lookahead=` H > 0 the cylinder models of `obstacles=` and `groups=` see H further
+primitives ahead: everybody is predicted to repeat the displacement of the own primitive (entries egx_obstacle_ahead_clearance,
+csrc/genop_obstacle_ahead.hip, ahead of the *_obstacle_markers selection entries, and egx_primitive_select_joint_ahead,
+csrc/genop_joint_ahead.hip, in the place of egx_primitive_select_joint).  With `policy=` (a
 `PolicyProposal`, egogen_amd/proposal.py) the candidates of the greedy search are no longer all drawn from N(0, I): per primitive
 every sequence senses its surroundings (entry egx_primitive_observe, csrc/genop_policy.hip), the trained policy's actor proposes
 mu, logvar over the latent, and the candidate rows become mu, samples round it and a share of prior samples (entry
@@ -55,6 +58,7 @@ T_ALL, T_PRED, NM3, XB = 20, 18, 201, 93
 MAX_CANDIDATES = 256        # EGX_MAX_CANDIDATES of include/egogen_hip.h
 MAX_BEAM = 32               # EGX_MAX_BEAM
 NULL_FIELD = (None, None, 0.0, 0, 0, 0, None)      # the field arguments of a selection entry without a field
+MAX_LOOKAHEAD = 8           # EGX_MAX_LOOKAHEAD
 OBSTACLE_MODELS = ("cylinder", "markers")       # what a recorded person of `obstacles=` is: a cylinder round the pelvis, or its 67 world markers
 SEARCH_WEIGHTS = {"goal": 1.0, "skate": 1.0, "floor": 1.0, "pene": 1.0, "face": 0.0}
 GENERATE_PPO_NOT_BUILT = ("generate_ppo is not built: nothing in the reference calls it, and its policy_model(X, obj_points=, "
@@ -120,6 +124,30 @@ def _person_groups(groups, data, beam_width, pair_weight, pair_margin, body_radi
     return groups
 
 
+def _checked_lookahead(lookahead, lookahead_slack, obstacles, groups, obstacle_model, pair_model):
+    """The `lookahead=` / `lookahead_slack=` arguments of `generate_sequence_to_goal` checked on the host, before any device work ->
+    (H, slack).  ValueError: H not an integer in [0, 8], a negative or non-finite slack, H > 0 with neither obstacles nor groups, H > 0
+    with a marker model (look-ahead is built for the cylinder models only)."""
+    try:
+        H = int(lookahead)
+        whole = not isinstance(lookahead, bool) and H == lookahead
+    except (TypeError, ValueError, OverflowError):
+        H, whole = 0, False
+    if not whole or not 0 <= H <= MAX_LOOKAHEAD:
+        raise ValueError(f"lookahead must be an integer in [0, {MAX_LOOKAHEAD}], got {lookahead!r}")
+    try:
+        slack = float(lookahead_slack)
+    except (TypeError, ValueError):
+        slack = float("nan")
+    if not (slack >= 0 and np.isfinite(slack)):
+        raise ValueError(f"lookahead_slack must be finite and not negative, got {lookahead_slack!r}")
+    if H > 0 and obstacles is None and groups is None:
+        raise ValueError("lookahead > 0 is about when the other people are seen: it needs obstacles= or groups=")
+    if H > 0 and (obstacle_model == "markers" or pair_model == "markers"):
+        raise ValueError('lookahead > 0 is built for the cylinder models only: not with obstacle_model="markers" or pair_model="markers"')
+    return H, slack
+
+
 def _checked_route(route, data, goal, beam_width, goal_thresh):
     """The `route=` argument of `generate_sequence_to_goal` checked on the host, before any device work -> the `Routes` (None without
     one).  TypeError for anything but a `Routes`; ValueError: another number of routes than the b seeds of `data`, a route with a
@@ -171,6 +199,9 @@ class PrimitiveSequence:
     as written overlap.  cost / colliding stay what the selection wrote; status follows the joint choice.  None without groups.
     `search` also holds pair_model ("cylinder" / "markers") and pair_skin (metres); with "markers" the clearances are distances
     between the two people's nearest blended markers minus pair_skin, in 3-D.
+    With obstacles or groups `search` also holds lookahead (H, 0: none) and lookahead_slack (metres per primitive); with H > 0
+    clearance / obstacle_term / obstacle_hit and pair_clearance / pair_term / pair_hit are those of the look-ahead c_t (the least of
+    the present clearance and the predicted ones, each floored at 0 and raised by h * slack), crowd_clearance / crowd_hit stay the present's.
     With `policy=PolicyProposal(..., sense_people=True)`: policy_sense_people True, people_box [K,b,4] (minx, miny, maxx, maxy) the
     world xy box of every sequence's two seed frames' markers at each primitive and obs_people_count [K,b] the holes its observation
     was cast against; False, None, None with a policy that does not sense people, None without a policy.
@@ -419,23 +450,30 @@ class GAMMAPrimitiveComboGenOP:
 
     @staticmethod
     def _clearance_lead(s, K, b, M, R0s, T0s, st):
-        """Per primitive the arguments of egx_obstacle_marker_clearance, the launch that goes before the selection with the marker
-        model of the obstacles (None without it); R0s / T0s: the frames of the rows at even and at odd k."""
+        """-> (entry name, per primitive its arguments) of the launch that goes before the selection and writes the table of frame
+        clearances: egx_obstacle_marker_clearance with the marker model of the obstacles, egx_obstacle_ahead_clearance with the
+        look-ahead of the cylinder model; (None, None) without a table.  R0s / T0s: the frames of the rows at even and at odd k."""
         if s.get("frame_clearance") is None:
-            return None
+            return None, None
+        if s.get("obs_ahead") is not None:
+            lead = [(_lib.ptr(s["lbs_out"]["joints"]), 127, _lib.ptr(R0), _lib.ptr(T0), b, M, *s["obstacles"]) for R0, T0 in zip(R0s, T0s)]
+            return "egx_obstacle_ahead_clearance", [(*lead[k % 2], s["obs_frame0"] + T_PRED * k, *s["obs_ahead"], _lib.ptr(s["frame_clearance"]), st)
+                                                    for k in range(K)]
         lead = [(_lib.ptr(s["lbs_out"]["markers"]), _lib.ptr(s["Y_gen"]), s["rf"], _lib.ptr(R0), _lib.ptr(T0), b, M, *s["obs_markers"])
                 for R0, T0 in zip(R0s, T0s)]
-        return [(*lead[k % 2], s["obs_frame0"] + T_PRED * k, s["obs_skin"], _lib.ptr(s["frame_clearance"]), st) for k in range(K)]
+        return "egx_obstacle_marker_clearance", [(*lead[k % 2], s["obs_frame0"] + T_PRED * k, s["obs_skin"], _lib.ptr(s["frame_clearance"]), st)
+                                                 for k in range(K)]
 
     @staticmethod
     def _select_tail(s, K, base):
         """What follows the outputs of a selection entry, built once per loop -> (entry name, field arguments, per primitive the
         obstacle arguments): `base` and nothing; with a field `base`_field and the field; with obstacles `base`_obstacles, the field
         (a null one without) and, for primitive k, the obstacles with frame0 = obstacle_frame0 + 18 k and the outputs' row k; with the
-        marker model of the obstacles `base`_obstacle_markers, the field, and the table, the two scalars and the outputs' row k."""
+        marker model of the obstacles, or the look-ahead of their cylinder model, `base`_obstacle_markers, the field, and the table, the
+        two scalars and the outputs' row k."""
         if s["obstacles"] is None:
             return (base + "_field", s["field"], [()] * K) if s["field"] else (base, (), [()] * K)
-        if s.get("frame_clearance") is not None:      # the marker model: the phase reads the table the clearance launch wrote
+        if s.get("frame_clearance") is not None:      # the marker model, the look-ahead: the phase reads the table the clearance launch wrote
             w_obs, margin, _ = s["obs_scalars"]
             obs = [(_lib.ptr(s["frame_clearance"]), w_obs, margin, _vp(s["obstacle_term"][k]), _vp(s["clearance"][k]),
                     _vp(s["obstacle_hit"][k])) for k in range(K)]
@@ -489,7 +527,8 @@ class GAMMAPrimitiveComboGenOP:
                                   obstacle_frame0: int = 0, groups=None, pair_weight: float = 1.0, pair_margin: float = 0.5,
                                   joint_sweeps: int = 2, policy=None, pair_model: str = "cylinder",
                                   pair_skin: float = 0.05, route=None, obstacle_model: str = "cylinder",
-                                  obstacle_skin: float = 0.05) -> PrimitiveSequence:
+                                  obstacle_skin: float = 0.05, lookahead: int = 0,
+                                  lookahead_slack: float = 0.1) -> PrimitiveSequence:
         """`generate_sequence` steered to a goal through a scene by a greedy best-of-N search: for each of the `n_primitives`
         primitives, `n_candidates` candidates per sequence are generated, scored and the best one is kept; every candidate of the
         next primitive continues from it.  data / bparams / betas / reproj_factor / R0 / T0 as in `generate_sequence` (b seeds,
@@ -605,6 +644,30 @@ class GAMMAPrimitiveComboGenOP:
               that passes it mid-primitive gets no credit for the leg beyond; arrival at the last waypoint can be recognised one
               primitive late when the cursor reaches it during that same primitive (`reached` of a primitive scored against an
               intermediate point is cleared); after the last waypoint the person still keeps walking.
+            - lookahead: H in [0, 8], the further primitives the cylinder models of `obstacles` and `groups` look ahead.  0 (the
+              default) is the search as described above: the same launches, the same buffers, the same bits.  With H > 0 a candidate
+              is predicted to repeat its own net displacement d = p(19) - p(1) (frames 18 and 19 become the next seed, so frame t of
+              the next primitive corresponds to t + 18 of this one): p_h(t) = p(t) + h d, and the frame clearance both terms score is
+              c_t = min(c_{t,0}, min_{h=1..H} max(0, c_{t,h}) + h * lookahead_slack), c_{t,0} the clearance described above and c_{t,h}
+              the same at the predicted positions.  A prediction can cost but only the present can veto: a predicted overlap never
+              puts a candidate into the colliding class by itself; the slack makes far predictions count less.  A non-finite own
+              pelvis at frame 1, t or 19 that makes a prediction NaN makes the row non-finite, as a NaN pelvis does today.  With
+              `obstacles` (greedy or beam) only the candidate is predicted - the recorded person's future is on record and is read
+              at the absolute frames obstacle_frame0 + 18 (k + h) + t: one launch per primitive (egx_obstacle_ahead_clearance) goes
+              before the selection and writes c_t into a [b*M,18] table allocated once before the loop, which the selection reads
+              through the entries that take a table (egx_primitive_select_obstacle_markers /
+              egx_primitive_beam_select_obstacle_markers).  With `groups` both people are predicted, the others by the displacement of
+              their CURRENT choice: egx_primitive_select_joint_ahead stands where egx_primitive_select_joint stands; pair_clearance /
+              pair_term / pair_hit are then those of the look-ahead c_t, crowd_clearance / crowd_hit stay at h = 0.  It combines
+              with scene, geodesic, route, policy (with and without sense_people) and beam_width > 1 exactly as the cylinder models
+              do.  ValueError for an H that is not an integer in [0, 8], a negative or non-finite slack, H > 0 with neither obstacles
+              nor groups, H > 0 with obstacle_model="markers" or pair_model="markers".  The limits: repeating one primitive's
+              displacement at constant velocity is a guess, not a plan; predictions use pelvis cylinders only; a member that has
+              reached its goal is still predicted to walk on.  Not built: look-ahead for the marker models, velocity obstacles,
+              predictions from anything but the own primitive.  The loop stays launches only.
+            - lookahead_slack (0.1 m per primitive of look-ahead; with the default margins of 0.5 m a prediction five primitives
+              ahead has no cost left) and the default lookahead of 0: stated choices like the others: nobody has measured motion
+              quality with them.
         Raises FloatingPointError when a chosen hand-off, or every candidate of a sequence, held a non-finite value (read once,
         after the loop); for a beam, when a node of the returned path did."""
         from .body_model import SdfScene, SdfSceneSet
@@ -635,6 +698,7 @@ class GAMMAPrimitiveComboGenOP:
             raise ValueError('obstacle_model="markers" needs obstacles= that carry markers (MovingObstacles.from_sequences / '
                              'from_rollout_files with markers=True, or from_tracks(..., markers=))')
         people = _person_groups(groups, data, W, pair_weight, pair_margin, body_radius, joint_sweeps, pair_model, pair_skin, N)
+        H, slack = _checked_lookahead(lookahead, lookahead_slack, obstacles, groups, obstacle_model, pair_model)
         if goal_thresh is None:
             goal_thresh = self.testconfig.get("goal_thresh", 0.1)
         route = _checked_route(route, data, goal, W, goal_thresh)
@@ -714,6 +778,8 @@ class GAMMAPrimitiveComboGenOP:
             if obstacle_model == "markers":      # the table of frame clearances, allocated once: the loop stays launches only
                 s.update({"obs_markers": obs_marker_args, "obs_markers_alive": obs_marker_alive, "obs_skin": float(obstacle_skin),
                           "frame_clearance": torch.empty(b * M, T_PRED, device=dev, dtype=f32)})
+            elif H > 0:      # the look-ahead's table of frame clearances, likewise allocated once
+                s.update({"obs_ahead": (float(body_radius), H, slack), "frame_clearance": torch.empty(b * M, T_PRED, device=dev, dtype=f32)})
         if people is not None:
             S, G = int(joint_sweeps), len(people.to(dev))
             trace = lambda *tail, dtype=f32: torch.empty(K, S, *tail, device=dev, dtype=dtype)
@@ -724,6 +790,9 @@ class GAMMAPrimitiveComboGenOP:
                       "joint_cost": trace(b, N), "pair_hit": trace(b, N, dtype=i32), "choice_trace": trace(b, dtype=i32),
                       "joint_changed": trace(G, dtype=i32), "crowd_clearance": rec(), "crowd_hit": rec(dtype=i32),
                       "groups": torch.as_tensor(people.ids), "pair_model": pair_model, "pair_skin": float(pair_skin)})
+            if H > 0:        # the look-ahead entry takes H and the slack after body_radius
+                s["joint"] = (*s["joint"][:7], H, slack, s["joint"][7])
+                s["joint_ahead"] = True
             if pair_model == "markers":      # the distance table and the bad-frame masks, allocated once: the loop stays launches only
                 npairs = int(people.pair_offsets[-1])
                 s.update({"pair_dist": torch.empty(npairs, N, N, T_PRED, device=dev, dtype=f32) if npairs else None,
@@ -775,6 +844,8 @@ class GAMMAPrimitiveComboGenOP:
             search.update({k: s[k] for k in PrimitiveSequence.OBSTACLE_FIELDS}, obstacle_model=obstacle_model, obstacle_skin=float(obstacle_skin))
         if people is not None:
             search.update({k: s[k] for k in PrimitiveSequence.JOINT_FIELDS + ("pair_model", "pair_skin")})
+        if obs_args is not None or people is not None:
+            search.update(lookahead=H, lookahead_slack=slack)
         if policy is not None:
             search.update(policy.record(s))
         if route is not None:
@@ -788,8 +859,8 @@ class GAMMAPrimitiveComboGenOP:
         """-> (the joint entry of the state's pair model, what it takes before the selection's rows, the arguments of the distance
         launch that goes before it or None)"""
         rows = (_lib.ptr(s["lbs_out"]["joints"]), 127, _lib.ptr(s["R0"]), _lib.ptr(s["T0"]), _lib.ptr(s["goal"]))
-        if s.get("row_bad") is None:
-            return "egx_primitive_select_joint", rows, None
+        if s.get("row_bad") is None:       # the cylinders; with a look-ahead their entry that predicts (s["joint"] then carries H and the slack)
+            return "egx_primitive_select_joint_ahead" if s.get("joint_ahead") else "egx_primitive_select_joint", rows, None
         crowd, npairs = s["joint_alive"], s["npairs"]         # the marker model: the table's launch, then the sweeps on it
         table, bad, pair_start = _lib.ptr(s["pair_dist"]), _lib.ptr(s["row_bad"]), _lib.ptr(crowd.pair_start)
         dist_args = (_lib.ptr(s["lbs_out"]["markers"]), _lib.ptr(s["Y_gen"]), s["rf"], _lib.ptr(s["R0"]), _lib.ptr(s["T0"]), b, N,
@@ -805,7 +876,8 @@ class GAMMAPrimitiveComboGenOP:
         sel = self._select_lead(s, [s["R0"]] * 2, [s["T0"]] * 2)
         name, field, obs = self._select_tail(s, K, "egx_primitive_select")
         select = getattr(lib, name)
-        clear = self._clearance_lead(s, K, b, N, [s["R0"]] * 2, [s["T0"]] * 2, st)
+        clear_name, clear = self._clearance_lead(s, K, b, N, [s["R0"]] * 2, [s["T0"]] * 2, st)
+        clear_entry = clear_name and getattr(lib, clear_name)
         joint, policy, route = s.get("joint"), s.get("policy"), s.get("route")
         if route is not None:
             route_out = (_lib.ptr(s["route_state"]), _lib.ptr(s["goal"]), _lib.ptr(s["field_alive"]) if s["field"] else None)
@@ -825,7 +897,7 @@ class GAMMAPrimitiveComboGenOP:
                 policy.launch(s, k, b, N, st, *sensed[k])
             self._primitive(s, k, s["pp"], st, s["R0"], s["T0"])
             if clear is not None:
-                _lib.check(lib.egx_obstacle_marker_clearance(*clear[k]), "egx_obstacle_marker_clearance")
+                _lib.check(clear_entry(*clear[k]), clear_name)
             _lib.check(select(
                 *sel[k % 2], b, N, _vp(s["choice"][k]), _vp(s["status"][k]), _vp(s["reached"][k]),
                 _vp(s["goal_dist"][k]), _vp(s["cost"][k]), _vp(s["cost_terms"][k]), _vp(s["colliding"][k]), *field, *obs[k], st), name)
@@ -855,13 +927,14 @@ class GAMMAPrimitiveComboGenOP:
         sel = self._select_lead(s, s["R0s"], s["T0s"])
         name, field, obs = self._select_tail(s, K, "egx_primitive_beam_select")
         select = getattr(lib, name)
-        clear = self._clearance_lead(s, K, b, W * N, s["R0s"], s["T0s"], st)
+        clear_name, clear = self._clearance_lead(s, K, b, W * N, s["R0s"], s["T0s"], st)
+        clear_entry = clear_name and getattr(lib, clear_name)
         for k in range(K):
             nxt = s["xs"][(k + 1) % 2]
             R0, T0, R0n, T0n = s["R0s"][k % 2], s["T0s"][k % 2], s["R0s"][(k + 1) % 2], s["T0s"][(k + 1) % 2]
             self._primitive(s, k, s["pp"], st, R0, T0)
             if clear is not None:
-                _lib.check(lib.egx_obstacle_marker_clearance(*clear[k]), "egx_obstacle_marker_clearance")
+                _lib.check(clear_entry(*clear[k]), clear_name)
             _lib.check(select(
                 *sel[k % 2], b, W, N, _vp(s["acc"][k]), _vp(s["ncoll"][k]), _vp(s["cost"][k]), _vp(s["cost_terms"][k]),
                 _vp(s["colliding"][k]), _vp(s["beam_row"][k]), _vp(s["parent"][k]), _vp(s["acc"][k + 1]), _vp(s["ncoll"][k + 1]),

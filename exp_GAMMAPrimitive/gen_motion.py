@@ -43,6 +43,10 @@ the points in order to the last one, a waypoint counting as passed within `--pas
 `--people` the waypoints of one person are chained with `>`: "x,y,yaw_deg:g1x,g1y,g1z>g2x,g2y,g2z;...".  A route is the greedy
 search (`--beam-width 1`); `--walkable` then builds one field per distinct waypoint; the files' `wpath` holds the whole route and
 the driver prints how many waypoints each path passed.  One point per person is the path without a route, unchanged.
+`--lookahead H` (with `--avoid` or `--people`, cylinder models only; 0 to 8, default 0: the horizon is one primitive) lets those terms
+look H further primitives ahead (`generate_sequence_to_goal(lookahead=)`): a candidate, and with `--people` everybody else, is predicted
+to repeat the displacement of the own primitive, the recorded people of `--avoid` are read ahead on their tracks; a predicted overlap
+costs, less `--lookahead-slack M` metres (default 0.1) per primitive of look-ahead, and only a present one vetoes.
 
 `--cfg <name>` is the combo config (`crowd_ppo/cfg_samp20/<name>.yml` under the working directory, else the packaged copy): it
 names the predictor's and the regressor's configs, whose checkpoints are read from `results/crowd_ppo/<config>/checkpoints`
@@ -139,7 +143,20 @@ def main(argv=None):
                         "group-mates of --people and the tracks of --avoid are holes of the polygon (with --policy)")
     parser.add_argument("--pass-radius", type=float, default=None, help="horizontal distance in metres within which a waypoint of a "
                         'route counts as passed (with ";" in --goal or ">" in --people; default 0.5)')
+    parser.add_argument("--lookahead", type=int, default=0, help="further primitives the cylinder models of --avoid and --people look "
+                        "ahead, 0 to 8: everybody is predicted to repeat the displacement of the own primitive (0: the horizon is one primitive)")
+    parser.add_argument("--lookahead-slack", type=float, default=None, help="metres of clearance a prediction is forgiven per primitive of "
+                        "look-ahead (default 0.1; an argument error without --lookahead above 0, as --pair-skin is without its model: "
+                        "the operator itself takes a slack at lookahead=0 and does not read it)")
     args = parser.parse_args(argv)
+    if not 0 <= args.lookahead <= 8:
+        parser.error("--lookahead takes 0 to 8 primitives")
+    if args.lookahead_slack is not None and (args.lookahead == 0 or not (args.lookahead_slack >= 0 and np.isfinite(args.lookahead_slack))):
+        parser.error("--lookahead-slack needs --lookahead above 0 and must be finite and not negative")
+    if args.lookahead > 0 and args.avoid is None and args.people is None:
+        parser.error("--lookahead needs --avoid or --people: it is about when the other people are seen")
+    if args.lookahead > 0 and (args.obstacle_model == "markers" or args.pair_model == "markers"):
+        parser.error("--lookahead is built for the cylinder models only: not with --obstacle-model markers or --pair-model markers")
     people = way = None          # way: the waypoints of every person of a run with a route, a list of [n_i,3]
     if args.people is not None and (args.start is not None or args.goal is not None or args.beam_width != 1):
         parser.error("--people stands in for --start and --goal and is the greedy search (--beam-width 1)")
@@ -324,7 +341,8 @@ def main(argv=None):
                 "; it senses the other people as holes of the polygon" if args.policy_sees_people else ""))
         search = dict(scene=scene, R0=R0, T0=T0, beam_width=args.beam_width, geodesic=field, obstacles=obstacles, groups=groups, policy=proposal,
                       pair_model=args.pair_model, pair_skin=0.05 if args.pair_skin is None else args.pair_skin,
-                      obstacle_model=args.obstacle_model, obstacle_skin=0.05 if args.obstacle_skin is None else args.obstacle_skin)
+                      obstacle_model=args.obstacle_model, obstacle_skin=0.05 if args.obstacle_skin is None else args.obstacle_skin,
+                      lookahead=args.lookahead, lookahead_slack=0.1 if args.lookahead_slack is None else args.lookahead_slack)
         if route is not None:
             search["route"] = route
         res = op.generate_sequence_to_goal(data.repeat(nseq, 1), bparams.repeat(nseq, 1), can["betas"].astype(np.float32),

@@ -41,6 +41,8 @@ extern "C" {
                                   workgroup's table in LDS */
 #define EGX_MAX_SWEEPS 8       /* Gauss-Seidel sweeps of egx_primitive_select_joint */
 #define EGX_MAX_WAYPOINTS 16   /* waypoints of one route of egx_route_advance and egx_route_metrics */
+#define EGX_MAX_LOOKAHEAD 8    /* further primitives egx_obstacle_ahead_clearance and egx_primitive_select_joint_ahead predict: the
+                                  window of a set over 9 x 18 frames (41.6 KB) is staged into one workgroup's LDS */
 #define EGX_GEODESIC_OFF 1.0e4f /* metres: what a geodesic field gives where none of the four surrounding cells holds a distance */
 #define EGX_GEODESIC_BATCH 8    /* passes egx_geodesic_field launches between two reads of its flag */
 #define EGX_NUM_BETAS 10
@@ -1098,6 +1100,62 @@ int egx_primitive_select_joint(const float* joints, int joints_per_body, const f
                                int32_t* status, int32_t* reached, float* goal_dist, float* pair_term, float* pair_clearance,
                                float* joint_cost, int32_t* pair_hit, int32_t* choice_trace, int32_t* changed,
                                float* crowd_clearance, int32_t* crowd_hit, void* stream);
+
+/* Look-ahead in the primitive search (csrc/genop_obstacle_ahead.hip, csrc/genop_joint_ahead.hip): the cylinder models of the recorded
+ * tracks and of the joint step see `lookahead` = H in [0, EGX_MAX_LOOKAHEAD] further primitives ahead.  The prediction rule of both:
+ * with p(t) the world xy of joint 0 of body t of a row (x = fma(R0[2], j.z, fma(R0[1], j.y, R0[0] j.x)) + T0.x, y likewise: the
+ * obstacle entries' nesting), a row repeats its own net displacement
+ *   d      = p(19) - p(1), one rounded difference per axis (frames 18 and 19 become the next seed frames: frame t of the next
+ *            primitive corresponds to this primitive's t + 18)
+ *   p_h(t) = p(t) + h * d, h as a float, one rounded product and one rounded addition per axis, no contraction
+ * and the clearance of predicted frame t = 2..19 is
+ *   c_t    = min(c_{t,0}, min_{h=1..H} (max(0, c_{t,h}) + h * slack)), one rounded product h * slack and one rounded addition
+ * where c_{t,0} is the cylinder clearance of the entry without look-ahead, same functions, same roundings, and c_{t,h} the same
+ * clearance at the predicted positions.  The max means a prediction can cost but only the present can veto: a predicted overlap
+ * alone never puts a row into the colliding class.  The minimum is order-free.  NaN: c_t is NaN where c_{t,0} or any c_{t,h} is
+ * NaN, which the row's own coordinates alone can cause (a NaN p(t), or a NaN or infinite - infinite d from p(1) / p(19)); the test
+ * for NaN comes before the max.  Everything after c_t is the existing arithmetic of the entry that reads it.
+ *
+ * egx_obstacle_ahead_clearance - one launch per primitive ahead of egx_primitive_select_obstacle_markers /
+ * egx_primitive_beam_select_obstacle_markers, which read its table.  rows = num_sequences * rows_per_sequence (N, or W * N for a
+ * beam), row r belongs to sequence g = r / rows_per_sequence; joints / R0 / T0 as the selection of the same primitive reads them; the
+ * obstacle sets as egx_primitive_select_obstacles takes them (obs_index may be NULL; obs_xy / obs_radius / obs_count may be NULL with
+ * max_obstacles 0).  Only the candidate is predicted - the other person's future is on record:
+ *   set   = obs_index ? clamp(obs_index[g], 0, num_sets - 1) : 0;  cnt = clamp(obs_count[set], 0, min(max_obstacles, EGX_MAX_OBSTACLES))
+ *   a_h   = clamp(frame0 + t + 18 h, 0, num_frames - 1), evaluated in 64 bits
+ *   c_{t,h} = min_{o < cnt} sqrt((p_h(t).x - o.x)^2 + (p_h(t).y - o.y)^2) - (r_o + body_radius) over obs_xy[set, o, a_h]: r_o + body_radius
+ *           rounded once, two rounded differences, two rounded squares, their rounded sum, the correctly rounded root, one rounded
+ *           difference (egx_primitive_select_obstacles' c_t); +inf for an empty set; a track's NaN coordinate drops out of the minimum
+ *   frame_clearance[r*18 + t - 2] = c_t
+ * With lookahead 0 the table fed to the *_obstacle_markers entries gives the bits of the *_obstacles entries.  One workgroup of 512
+ * threads per sequence: the set's window over the (H + 1) x 18 consecutive absolute frames staged once in LDS, a wave per row, lanes
+ * 0..17 one frame each.  No atomics, no waiting, nothing between workgroups.  EGX_ERR_ARG for a NULL joints / R0 / T0 /
+ * frame_clearance, a NULL obs_xy / obs_radius / obs_count with max_obstacles > 0, num_sequences < 1, joints_per_body < 1,
+ * rows_per_sequence outside [1, EGX_MAX_CANDIDATES], max_obstacles outside [0, EGX_MAX_OBSTACLES], num_frames < 1, num_sets < 1,
+ * lookahead outside [0, EGX_MAX_LOOKAHEAD], a negative or non-finite (NaN included) slack or body_radius, 2^31 rows or more. */
+int egx_obstacle_ahead_clearance(const float* joints, int joints_per_body, const float* R0, const float* T0, int num_sequences,
+                                 int rows_per_sequence, const float* obs_xy, const float* obs_radius, const int32_t* obs_count,
+                                 const int32_t* obs_index, int num_sets, int max_obstacles, int num_frames, int frame0, float body_radius,
+                                 int lookahead, float slack, float* frame_clearance, void* stream);
+
+/* egx_primitive_select_joint_ahead - egx_primitive_select_joint (the same sweeps, arguments, outputs and traces; lookahead and slack
+ * follow body_radius) with both people predicted: the table holds, next to every member j's 18 xy columns, the displacement d_j of its
+ * CURRENT choice, rewritten with the column when the member chooses.  For row n of member i, with d its own displacement:
+ *   c_{t,0} = egx_primitive_select_joint's c_t
+ *   c_{t,h} = min over the members j != i of sqrt((p_h(t).x - q.x)^2 + (p_h(t).y - q.y)^2) - rr,  q = (x_j + h * d_j.x, y_j + h * d_j.y),
+ *           one rounded product and one rounded addition per axis for either person, then c_{t,0}'s roundings; +inf for a group of
+ *           one; another member's NaN q drops out of the minimum; a NaN p_h(t) gives NaN
+ * pair_clearance is then min_t of the look-ahead c_t, pair_term its penalty, pair_hit = pair_clearance < 0 (which c_{t,0} alone can
+ * cause).  crowd_clearance / crowd_hit stay at h = 0: did the crowd as written overlap.  With lookahead 0 every output is
+ * egx_primitive_select_joint's, bit for bit.  EGX_ERR_ARG for what egx_primitive_select_joint rejects, lookahead outside
+ * [0, EGX_MAX_LOOKAHEAD], a negative or non-finite (NaN included) slack. */
+int egx_primitive_select_joint_ahead(const float* joints, int joints_per_body, const float* R0, const float* T0, const float* goal,
+                                     const float* cost, const float* cost_terms, const int32_t* colliding, int num_sequences,
+                                     int num_candidates, const int32_t* group_start, const int32_t* group_member, int num_groups,
+                                     int sweeps, float pair_weight, float margin, float body_radius, int lookahead, float slack,
+                                     float goal_thresh, int32_t* choice, int32_t* status, int32_t* reached, float* goal_dist,
+                                     float* pair_term, float* pair_clearance, float* joint_cost, int32_t* pair_hit, int32_t* choice_trace,
+                                     int32_t* changed, float* crowd_clearance, int32_t* crowd_hit, void* stream);
 
 /* The marker-level pair model of the joint step (csrc/genop_joint_markers.hip): a person is the 67 blended markers of a candidate
  * row in the world, not a cylinder.  Two launches stand where egx_primitive_select_joint stands: egx_pair_marker_dist writes every
